@@ -3,7 +3,7 @@
 (`--workload esrgan` measures the next row to the same contract: Real-ESRGAN-4x f16, 256^2 -> 1024^2, batch 16,
 BASELINE.json configs[2].)
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: started without RANK in the environment, `--gpus N` launches the second form itself as a
@@ -132,6 +132,25 @@ def pipeline_child(args):
     print(json.dumps(res))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, one DIR/<name>.npy per array (float32 / float64), so two builds can be
+    compared output for output on the same seeded inputs. Above 64 MB in all, a fixed sample (seed 0) of rows along the leading (batch) axis
+    is written instead, the same rows in every run with the same arguments."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    total = sum(v.nbytes for v in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(len(a) * DUMP_MAX_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,8 +170,14 @@ def main():
     ap.add_argument("--profile-groups", action="store_true", help="print the per-kernel-group table to stderr")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path on one GPU)")
     ap.add_argument("--device", type=int, default=None, help="force this HIP device for every rank (gloo rehearsal only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="depthany: after the timed steps write the last timed step's depth maps to DIR/depth.npy (float32, [batch, H, W])")
     ap.add_argument("--pipeline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "depthany":
+        ap.error("--dump-outputs is implemented for the depthany workload only")
     if args.pipeline_child:
         return pipeline_child(args)
 
@@ -269,6 +294,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = ev.step_ms()
+    # the soak below steps on into the same buffer: keep the last timed step's output as it was
+    timed_out = out.cpu().numpy() if args.dump_outputs and rank == 0 else None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -395,6 +422,9 @@ def main():
             res["kernel_groups_ms_in_graph_shapes"] = {k: round(v["ms"], 3) for k, v in sorted(acc_split.items(), key=lambda kv: -kv[1]["ms"]) if not k.startswith("__end")}
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, imgs, o, args.cpu_images, args.cpu_threads)
+        if timed_out is not None:
+            dump_outputs(args.dump_outputs, {"depth": timed_out})
+            res["dumped_outputs"] = str(Path(args.dump_outputs) / "depth.npy")
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()
