@@ -13,9 +13,11 @@
 // those sources themselves: src/visp/arch/dino.cpp and depth-anything.cpp compile unmodified against these headers with
 // -DVISP_GGML_NAMES -DVISP_ARCH_FROM_SOURCE (tests/test_reference_sources_compile.py). With VISP_ARCH_FROM_SOURCE the pipeline pieces
 // the reference defines in depth-anything.cpp (image_extent / process_input / process_output) are declared here, not defined.
-// Not covered: the *_predict builders of the other families (hand schedules only), migan_* (family not built).
+// Not covered: the *_predict builders of the other families (hand schedules only). migan_* loads through visp_migan_load
+// (visp_model_load refuses the family).
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -254,6 +256,63 @@ inline image_data depthany_process_output(std::span<float const> output_data, i3
     return normalized;
 }
 #endif
+
+// MI-GAN (vision.h:257-279): image rgb/rgba u8 + alpha_u8 mask of any extent -> rgba_u8 at that extent, alpha = mask (vision.cpp:172-203)
+using migan_model = detail::model_handle<VISP_MIGAN>;
+inline migan_model migan_load_model(char const* filepath, backend_device const& dev) {
+    visp_model* m = nullptr;
+    detail::check(visp_migan_load(filepath, dev.handle, &m));
+    return migan_model(m);
+}
+inline image_data migan_compute(migan_model& model, image_view image, image_view mask) {
+    visp_image_view in = detail::c_view(image), mk = detail::c_view(mask), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_migan_compute(model.handle, &in, &mk, &out, &owner));
+    return detail::take(out, owner);
+}
+struct migan_params { int resolution = 256; bool invert_mask = true; }; // vision.h:263-266
+inline migan_params migan_detect_params(migan_model const& model) { // the GGUF key migan.image_size, read from the loaded model
+    visp_migan_info info{};
+    detail::check(visp_migan_get_info(model.handle, &info));
+    return migan_params{info.resolution, true};
+}
+// migan.cpp:142-159, 181-196: both inputs scaled to resolution^2, then {a - 0.5, a (2 rgb - 1)} with a = 1 - mask (inverted) -> rgba_f32
+inline image_data migan_process_input(image_view image, image_view mask, migan_params const& p) {
+    const i32x2 res{p.resolution, p.resolution};
+    image_data si, sm;
+    if (image.extent != res) { si = image_scale(image, res); image = image_view(si); }
+    if (mask.extent != res) { sm = image_scale(mask, res); mask = image_view(sm); }
+    const int ch = n_channels(image.format);
+    if (ch != 3 && ch != 4) throw exception("Unsupported image format for migan image input");
+    image_data out = image_alloc(res, image_format::rgba_f32);
+    float* o = reinterpret_cast<float*>(out.data.get());
+    for (int y = 0; y < res[1]; ++y)
+        for (int x = 0; x < res[0]; ++x) {
+            const uint8_t* px = static_cast<const uint8_t*>(image.data) + size_t(y) * image.stride + size_t(x) * ch;
+            float a = static_cast<const uint8_t*>(mask.data)[size_t(y) * mask.stride + x] / 255.0f;
+            if (p.invert_mask) a = 1.0f - a;
+            float* d = o + (size_t(y) * res[0] + x) * 4;
+            d[0] = a - 0.5f;
+            for (int c = 0; c < 3; ++c) d[1 + c] = a * (px[c] / 255.0f * 2.0f - 1.0f);
+        }
+    return out;
+}
+// migan.cpp:198-206: rgb f32 at resolution^2 -> scaled to extent -> rgba_u8 with x * 0.5 + 0.5 (alpha 255; vision.cpp then sets the mask)
+inline image_data migan_process_output(std::span<float const> data, i32x2 extent, migan_params const& p) {
+    const i32x2 res{p.resolution, p.resolution};
+    image_view img(res, image_format::rgb_f32, data.data());
+    image_data scaled;
+    if (extent != res) { scaled = image_scale(img, extent); img = image_view(scaled); }
+    image_data out = image_alloc(extent, image_format::rgba_u8);
+    for (int y = 0; y < extent[1]; ++y)
+        for (int x = 0; x < extent[0]; ++x) {
+            const float* s = reinterpret_cast<const float*>(static_cast<const uint8_t*>(img.data) + size_t(y) * img.stride) + size_t(x) * 3;
+            uint8_t* d = out.data.get() + (size_t(y) * extent[0] + x) * 4;
+            for (int c = 0; c < 3; ++c) d[c] = uint8_t(std::clamp(s[c] * 0.5f + 0.5f, 0.0f, 1.0f) * 255.0f);
+            d[3] = 255;
+        }
+    return out;
+}
 
 // ESRGAN (vision.h:284-304): any size, tiled, -> rgba_u8 at scale x the input extent (vision.cpp:220-253)
 using esrgan_model = detail::model_handle<VISP_ESRGAN>;

@@ -6,7 +6,7 @@
  * ctypes binding (bindings/python/visioncpp/_lib.py:118-171) binds. Return value 1 = ok,
  * 0 = error with the message available from visp_get_last_error() (thread-local,
  * c-api.cpp:6-21). Built behind it: depth_anything, esrgan, sam (MobileSAM: image encoder + prompt encoder / mask decoder) and
- * birefnet (swin-T / BiRefNet-lite); migan returns an error ("not built in this backend").
+ * birefnet (swin-T / BiRefNet-lite); migan through visp_migan_load (visp_model_load returns "not built in this backend").
  *
  * Part 2 is the batched, device-resident extension the reference does not have (its
  * depthany_compute is batch 1, src/visp/vision.cpp:155): it is what bench.py and a
@@ -182,6 +182,31 @@ VISP_API int32_t visp_esrgan_compute_batch_host(visp_model* m, uint8_t const* im
 VISP_API int32_t visp_esrgan_generate_host(visp_model* m, float const* rgb, int32_t n, int32_t w, int32_t h, float* out);
 VISP_API int32_t visp_esrgan_enable_timing(visp_model* m, int32_t enable);
 VISP_API int32_t visp_esrgan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n);
+
+/* ---- MI-GAN extension (family 3; reference vision.h:257-279, vision.cpp:172-203, migan.cpp) ---------------------------
+ * Loaded through visp_migan_load only: visp_model_load(.., VISP_MIGAN) and auto-detect keep refusing the family. A loaded handle
+ * works with visp_model_compute(h, VISP_MIGAN, {image, mask}, 2, ..) (reference c-api.cpp:87-92) and is destroyed with
+ * visp_model_destroy(h, VISP_MIGAN). */
+typedef struct visp_migan_info { int32_t resolution, n_levels, channels[9]; } visp_migan_info; /* channels[i] at resolution >> i */
+VISP_API int32_t visp_migan_load(char const* filepath, visp_device const* dev, visp_model** out);
+VISP_API int32_t visp_migan_get_info(visp_model const* m, visp_migan_info* out);
+/* migan_compute: image rgb/rgba u8 of any extent + alpha_u8 mask of the same extent -> rgba_u8 at that extent, alpha = mask */
+VISP_API int32_t visp_migan_compute(visp_model* m, visp_image_view const* image, visp_image_view const* mask, visp_image_view* out_image,
+                                    visp_image_data** out_data);
+/* img u8 [B,res,res,channels] (3 or 4), mask u8 [B,res,res] -> rgba_u8 [B,res,res,4]; device pointers; stream = hipStream_t or NULL
+ * (NULL: the device's stream, synchronised before returning). Replayed as a hipGraph per (batch, channels) after the first call. */
+VISP_API int32_t visp_migan_compute_batch_device(visp_model* m, void const* img, int32_t channels, void const* mask, int32_t batch,
+                                                 void* out_rgba, void* stream);
+VISP_API int32_t visp_migan_compute_batch_host(visp_model* m, uint8_t const* img, int32_t channels, uint8_t const* mask, int32_t batch,
+                                               uint8_t* out_rgba);
+/* the generator on migan_process_input's f32 [n,res,res,4] -> rgb f32 [n,res,res,3] (host buffers; for tests) */
+VISP_API int32_t visp_migan_generate_host(visp_model* m, float const* in4, int32_t n, float* out_rgb);
+/* captures of the next computes: "enc.feat<r>", "enc.out", "syn.b<r>.x", "syn.b<r>.img" (computes run without the hipGraph) */
+VISP_API int32_t visp_migan_enable_captures(visp_model* m, int32_t enable);
+VISP_API int32_t visp_migan_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written,
+                                         int64_t shape[4]);
+VISP_API int32_t visp_migan_enable_timing(visp_model* m, int32_t enable);
+VISP_API int32_t visp_migan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n);
 
 /* ---- MobileSAM extension (family 0; reference vision.h:186-222, vision.cpp:26-92, mobile-sam.cpp) ----
  * visp_model_load / visp_model_compute work as in the reference: one image + 2 (point) or 4 (box) integer arguments in

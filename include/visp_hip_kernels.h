@@ -72,6 +72,8 @@ enum vx_epilogue {
                              (depth-anything.cpp:15-30)                                          */
     VX_EPI_HEAD_OUT = 8,  /* N == 32: out f32 [M] = head_scale * relu(sum_n relu(acc+bias)[n] * lambda[n] + head_bias):
                              head.conv2 + ReLU + head.conv3 (1x1 -> 1) + ReLU fused (depth-anything.cpp:87-94) */
+    VX_EPI_LRELU_AGC = 9, /* MI-GAN: out f16 = clamp(lrelu_0.2(acc + bias + noise[m % noise_hw]) * sqrt2, +-256); noise f32 plane
+                             or NULL; then + res1 f16 [M, ldo] if given (plain GEMM only; migan.cpp:17-26, 53-82) */
 };
 
 typedef struct {
@@ -121,6 +123,8 @@ typedef struct {
      * summed in a fixed order by a second launch that applies bias / ReLU / res1 -- deterministic. Epilogues F16, F16_RELU, F16_ADD. */
     int k_splits; float* k_partial;
     void* debug_stamps; /* diagnostics only: u64 [blocks][8] s_memtime stamps per phase, NULL in product */
+    const float* noise; /* VX_EPI_LRELU_AGC: f32 [noise_hw] (noise_const * noise_strength) added at row m % noise_hw, or NULL */
+    int noise_hw;
 } vx_gemm_args;
 
 VX_API int vx_gemm_f16(const vx_gemm_args* args, void* stream);
@@ -399,6 +403,25 @@ VX_API int vx_image_planes_f32(const float* x, void* y, int64_t n_pix, int C, vo
 /* 1x1 convolution to one channel: out f32 [M] = scale * act(sum_c x[m,c] w[c] + bias), x f16 [M][C] (depth-anything.cpp:91-95) */
 VX_API int vx_conv1x1_to1_f32(const void* x, const float* w, float bias, int relu, float scale, float* out, int64_t M, int C, void* stream);
 VX_API int vx_im2col_patches_f32(const float* x, void* patches, int B, int H, int W, int C, int ps, int Kp, void* stream);
+
+
+/* ---- MI-GAN inpainting (migan.cpp, kernels_migan.hip): NHWC f16, f32 arithmetic, lrelu_agc = clamp(lrelu_0.2(v) * sqrt2, +-256).
+ * Depthwise weights f16 [9][C] tap-major + f32 bias [C]; 4x4 FIR filters f32 [16][C]. */
+/* y = lrelu_agc(dw3x3(x) + bias) [B,H,W,C]; with down_fir: then the 4x4 / stride 2 / pad 1 FIR, y [B,H/2,W/2,C] (C % 64 == 0) */
+VX_API int vx_migan_dwconv_f16(const void* x, const void* w, const float* bias, const float* down_fir, void* y, int B, int H, int W, int C,
+                               void* stream);
+/* out [B,2h,2w,C] = lrelu_agc(upFIR(y) + noise[2h*2w] (nullable)) + feat (nullable); upFIR = zero insertion x2, 4x4 FIR pad 2, crop */
+VX_API int vx_migan_upsample_f16(const void* y, const float* fir, const float* noise, const void* feat, void* out, int B, int h, int w, int C,
+                                 void* stream);
+/* img f32 [B,H,W,3] = x [B,H,W,C] . w[3][C] + bias[3] (+ upFIR(img_prev [B,H/2,W/2,3]) with fir f32 [16][3]); C <= 512 */
+VX_API int vx_migan_torgb(const void* x, const float* w, const float* bias, const float* img_prev, const float* fir, float* img, int B, int H, int W,
+                          int C, void* stream);
+/* out f16 [n_pixels, C] = lrelu_agc(fromrgb(p)) with p = {a - 0.5, a (2 rgb/255 - 1)}, a = 1 - mask/255 from a u8 image (3 or 4
+ * channels) + u8 mask, or p = in4 f32 [n_pixels, 4] when in4 != NULL; fromrgb w f32 [C][4], bias f32 [C] */
+VX_API int vx_migan_preprocess(const uint8_t* img, int img_channels, const uint8_t* mask, const float* in4, const float* w, const float* bias,
+                               void* out, int64_t n_pixels, int C, void* stream);
+/* rgba u8 [n_pixels, 4] = trunc(clamp(img * 0.5 + 0.5, 0, 1) * 255) of rgb f32, alpha = mask */
+VX_API int vx_migan_postprocess(const float* img, const uint8_t* mask, uint8_t* rgba, int64_t n_pixels, void* stream);
 
 #ifdef __cplusplus
 }

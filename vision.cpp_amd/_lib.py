@@ -34,6 +34,10 @@ class EsrganInfo(ctypes.Structure):  # == visp_esrgan_info
     _fields_ = [(n, c_int32) for n in ("scale", "n_blocks", "n_filters", "growth", "tile_group")]
 
 
+class MiganInfo(ctypes.Structure):  # == visp_migan_info
+    _fields_ = [("resolution", c_int32), ("n_levels", c_int32), ("channels", c_int32 * 9)]
+
+
 class DconvArgs(ctypes.Structure):  # == vx_dconv_args
     _fields_ = [
         ("x", c_void_p), ("x_plane", c_int64), ("cin", c_int), ("up2", c_int), ("B", c_int), ("H", c_int), ("W", c_int),
@@ -67,6 +71,7 @@ class GemmArgs(ctypes.Structure):  # == vx_gemm_args
         ("ps_s", c_int), ("ps_Cout", c_int), ("ps_H", c_int), ("ps_W", c_int),
         ("res1", c_void_p), ("res2", c_void_p), ("n_valid", c_int), ("stages", c_int), ("head_bias", c_float), ("head_scale", c_float),
         ("post_gelu", c_int), ("win_ws", c_int), ("win_res", c_int), ("win_res_h", c_int), ("win_shift", c_int), ("k_splits", c_int), ("k_partial", c_void_p), ("debug_stamps", c_void_p),
+        ("noise", c_void_p), ("noise_hw", c_int),
     ]
 
 
@@ -88,7 +93,7 @@ class DinoBlockArgs(ctypes.Structure):  # == vx_dino_block_args
     ]
 
 
-EPI_F16, EPI_F16_GELU, EPI_F16_RELU, EPI_RESID_F32, EPI_TOKENS, EPI_QKV, EPI_PIXSHUF, EPI_F16_ADD, EPI_HEAD_OUT = range(9)
+EPI_F16, EPI_F16_GELU, EPI_F16_RELU, EPI_RESID_F32, EPI_TOKENS, EPI_QKV, EPI_PIXSHUF, EPI_F16_ADD, EPI_HEAD_OUT, EPI_LRELU_AGC = range(10)
 
 import os
 
@@ -119,7 +124,8 @@ C_API_SYMBOLS = [
     "visp_file_load", "visp_file_destroy", "visp_file_n_tensors", "visp_file_get_int", "visp_file_get_int_array", "visp_file_get_string", "visp_weights_from_file",
     "visp_graph_create", "visp_graph_destroy", "visp_graph_add_weight", "visp_graph_find_weight", "visp_graph_input",
     "visp_graph_op", "visp_graph_set_name", "visp_graph_get_tensor", "visp_graph_output", "visp_graph_tensor_info", "visp_graph_read_constant",
-    "visp_graph_allocate", "visp_graph_set_fused_models", "visp_graph_use_hip_graph", "visp_graph_compute", "visp_graph_tensor_set", "visp_graph_tensor_get", "visp_graph_describe",
+    "visp_graph_allocate", "visp_graph_set_fused_models", "visp_graph_use_hip_graph", "visp_graph_compute", "visp_graph_tensor_set", "visp_graph_tensor_get", "visp_graph_describe",    "visp_migan_load", "visp_migan_get_info", "visp_migan_compute", "visp_migan_compute_batch_device", "visp_migan_compute_batch_host",
+    "visp_migan_generate_host", "visp_migan_enable_captures", "visp_migan_read_capture", "visp_migan_enable_timing", "visp_migan_read_timing",
 ]
 KERNEL_SYMBOLS = [
     "vx_last_error", "vx_device_count", "vx_set_device", "vx_device_info", "vx_malloc", "vx_free", "vx_memset",
@@ -135,7 +141,7 @@ KERNEL_SYMBOLS = [
     "vx_swin_attention_pack_bias", "vx_window_attention_masked_f16", "vx_swin_layernorm_f16", "vx_swin_layernorm_strided_f16", "vx_swin_merge_layernorm_f16", "vx_swin_window_reverse_add_f16",
     "vx_headconv_frag_bytes", "vx_headconv_pack", "vx_headconv_supported", "vx_headconv_bil_f16", "vx_headconv_set_stamps",
     "vx_copy_strided_f16", "vx_binary_rows", "vx_unary_f16", "vx_convert", "vx_im2col_patches_f32", "vx_conv1x1_to1_f32",
-    "vx_dino_block_supported", "vx_dino_block_mlp_bytes", "vx_dino_block_qkv_bytes", "vx_dino_block16_pack_mlp", "vx_dino_block16_pack_qkv", "vx_dino_block16_f16",
+    "vx_dino_block_supported", "vx_dino_block_mlp_bytes", "vx_dino_block_qkv_bytes", "vx_dino_block16_pack_mlp", "vx_dino_block16_pack_qkv", "vx_dino_block16_f16",    "vx_migan_dwconv_f16", "vx_migan_upsample_f16", "vx_migan_torgb", "vx_migan_preprocess", "vx_migan_postprocess",
 ]
 
 
@@ -207,6 +213,16 @@ def init() -> ctypes.CDLL:
     lib.visp_esrgan_generate_host.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]
     lib.visp_esrgan_enable_timing.argtypes = [c_void_p, c_int32]
     lib.visp_esrgan_read_timing.argtypes = [c_void_p, POINTER(Timing), c_int32, POINTER(c_int32)]
+    lib.visp_migan_load.argtypes = [c_char_p, c_void_p, POINTER(c_void_p)]
+    lib.visp_migan_get_info.argtypes = [c_void_p, POINTER(MiganInfo)]
+    lib.visp_migan_compute.argtypes = [c_void_p, POINTER(ImageView), POINTER(ImageView), POINTER(ImageView), POINTER(c_void_p)]
+    lib.visp_migan_compute_batch_device.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]
+    lib.visp_migan_compute_batch_host.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]
+    lib.visp_migan_generate_host.argtypes = [c_void_p, c_void_p, c_int32, c_void_p]
+    lib.visp_migan_enable_captures.argtypes = [c_void_p, c_int32]
+    lib.visp_migan_read_capture.argtypes = [c_void_p, c_char_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64)]
+    lib.visp_migan_enable_timing.argtypes = [c_void_p, c_int32]
+    lib.visp_migan_read_timing.argtypes = [c_void_p, POINTER(Timing), c_int32, POINTER(c_int32)]
     lib.visp_sam_encode.argtypes = [c_void_p, POINTER(ImageView)]
     lib.visp_sam_read_embedding.argtypes = [c_void_p, c_void_p, c_int64, POINTER(c_int64)]
     lib.visp_sam_encode_batch_device.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
@@ -352,6 +368,11 @@ def init() -> ctypes.CDLL:
     lib.vx_dconv_bilinear_supported.argtypes = [c_int, c_int, c_int, c_int, c_int]
     lib.vx_esrgan_tiles_in.argtypes = [c_void_p, c_int, c_int, c_int, c_int, POINTER(TileLayout), c_void_p, c_void_p]
     lib.vx_esrgan_tiles_out.argtypes = [c_void_p, c_int, POINTER(TileLayout), c_void_p, c_void_p, c_void_p]
+    lib.vx_migan_dwconv_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_migan_upsample_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_migan_torgb.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_migan_preprocess.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    lib.vx_migan_postprocess.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     for name in KERNEL_SYMBOLS[1:]:
         getattr(lib, name).restype = c_int
     lib.vx_attention_set_fast_limit.restype = None

@@ -16,6 +16,7 @@
 #include "../../include/visp_hip_kernels.h"
 #include "depthany.h"
 #include "esrgan.h"
+#include "migan.h"
 #include "tinyvit.h"
 #include "swin.h"
 #include "birefnet.h"
@@ -66,6 +67,10 @@ depthany_model const& as_depthany(visp_model const* m) {
 esrgan_model& as_esrgan(visp_model* m) {
     if (family_of(m) != VISP_ESRGAN) throw except("model handle is not an esrgan model (family %d)", family_of(m));
     return *static_cast<esrgan_model*>(reinterpret_cast<model_base*>(m));
+}
+migan_model& as_migan(visp_model* m) {
+    if (family_of(m) != VISP_MIGAN) throw except("model handle is not a migan model (family %d)", family_of(m));
+    return *static_cast<migan_model*>(reinterpret_cast<model_base*>(m));
 }
 sam_model& as_sam(visp_model* m) {
     if (family_of(m) != VISP_SAM) throw except("model handle is not a sam model (family %d)", family_of(m));
@@ -234,6 +239,7 @@ void visp_model_destroy(visp_model* model, int32_t arch) {
     (void)arch;
     if (base->family == VISP_DEPTH_ANYTHING) delete static_cast<depthany_model*>(base);
     else if (base->family == VISP_ESRGAN) delete static_cast<esrgan_model*>(base);
+    else if (base->family == VISP_MIGAN) delete static_cast<migan_model*>(base);
     else if (base->family == VISP_SAM) delete static_cast<sam_model*>(base);
     else if (base->family == VISP_BIREFNET) delete static_cast<swin_model*>(base); // swin encoder or full birefnet model (virtual destructor)
 }
@@ -241,6 +247,13 @@ void visp_model_destroy(visp_model* model, int32_t arch) {
 int32_t visp_model_compute(visp_model* model, int32_t family, visp_image_view* inputs, int32_t n_inputs, int32_t* args, int32_t n_args,
                            visp_image_view* out_image, visp_image_data** out_data) {
     return handle_errors([&]() {
+        if (family == VISP_MIGAN && model && family_of(model) == VISP_MIGAN) { // model_funcs<migan>::compute (reference c-api.cpp:87-92)
+            if (n_inputs != 2) throw except("Expected %d input images, but got %d.", 2, n_inputs);
+            image_view in[2];
+            for (int i = 0; i < 2; ++i) in[i] = image_view{i32x2{{inputs[i].width, inputs[i].height}}, inputs[i].stride, image_format(inputs[i].format), inputs[i].data};
+            return_image(migan_compute(as_migan(model), in[0], in[1]), out_image, out_data);
+            return;
+        }
         require_built(family);
         if (family_of(model) != family) throw except("model handle belongs to family %d, not %d", family_of(model), family);
         if (n_inputs != 1) throw except("Expected %d input images, but got %d.", 1, n_inputs);
@@ -530,6 +543,80 @@ int32_t visp_esrgan_read_timing(visp_model* m, visp_timing* out, int32_t cap, in
         esrgan_model& em = as_esrgan(m);
         int32_t count = 0;
         for (timing_entry const& t : em.last_timing) {
+            if (count >= cap) break;
+            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
+            out[count].ms = t.ms;
+            out[count].launches = t.launches;
+            out[count].flops = t.flops;
+            out[count].bytes = t.bytes;
+            ++count;
+        }
+        *n = count;
+    });
+}
+
+// ---- MI-GAN (loaded only through visp_migan_load) ----
+
+int32_t visp_migan_load(char const* filepath, visp_device const* dev, visp_model** out) {
+    return handle_errors([&]() {
+        if (!dev || !out) throw except("migan: null argument");
+        *out = handle_of(migan_load_model(filepath, *dev));
+    });
+}
+
+int32_t visp_migan_get_info(visp_model const* m, visp_migan_info* out) {
+    return handle_errors([&]() {
+        migan_model const& mm = as_migan(const_cast<visp_model*>(m));
+        memset(out, 0, sizeof *out);
+        out->resolution = mm.params.resolution;
+        out->n_levels = (int32_t)mm.levels.size();
+        for (size_t i = 0; i < mm.levels.size() && i < 9; ++i) out->channels[i] = mm.levels[i].ch;
+    });
+}
+
+int32_t visp_migan_compute(visp_model* m, visp_image_view const* image, visp_image_view const* mask, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!image || !image->data || !mask || !mask->data || !out_image || !out_data) throw except("migan: null argument");
+        image_view im{i32x2{{image->width, image->height}}, image->stride, image_format(image->format), image->data};
+        image_view mk{i32x2{{mask->width, mask->height}}, mask->stride, image_format(mask->format), mask->data};
+        return_image(migan_compute(as_migan(m), im, mk), out_image, out_data);
+    });
+}
+
+int32_t visp_migan_compute_batch_device(visp_model* m, void const* img, int32_t channels, void const* mask, int32_t batch, void* out_rgba, void* stream) {
+    return handle_errors([&]() { migan_compute_batch_device(as_migan(m), img, channels, mask, batch, out_rgba, stream); });
+}
+
+int32_t visp_migan_compute_batch_host(visp_model* m, uint8_t const* img, int32_t channels, uint8_t const* mask, int32_t batch, uint8_t* out_rgba) {
+    return handle_errors([&]() { migan_compute_batch_host(as_migan(m), img, channels, mask, batch, out_rgba); });
+}
+
+int32_t visp_migan_generate_host(visp_model* m, float const* in4, int32_t n, float* out_rgb) {
+    return handle_errors([&]() { migan_generate_host(as_migan(m), in4, n, out_rgb); });
+}
+
+int32_t visp_migan_enable_captures(visp_model* m, int32_t enable) {
+    return handle_errors([&]() { as_migan(m).captures = enable != 0; });
+}
+
+int32_t visp_migan_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
+    return handle_errors([&]() {
+        migan_model& mm = as_migan(m);
+        if (!name || !n_written) throw except("migan: null argument");
+        device_turn turn(*mm.backend);
+        read_capture(*mm.backend, mm.capture_bufs, name, host_out, capacity, n_written, shape);
+    });
+}
+
+int32_t visp_migan_enable_timing(visp_model* m, int32_t enable) {
+    return handle_errors([&]() { as_migan(m).timing = enable != 0; });
+}
+
+int32_t visp_migan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
+    return handle_errors([&]() {
+        migan_model& mm = as_migan(m);
+        int32_t count = 0;
+        for (timing_entry const& t : mm.last_timing) {
             if (count >= cap) break;
             snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
             out[count].ms = t.ms;

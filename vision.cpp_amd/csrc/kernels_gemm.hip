@@ -47,7 +47,7 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 
 constexpr bool epi_is_f16_tile(int epi) {
     return epi == VX_EPI_F16 || epi == VX_EPI_F16_GELU || epi == VX_EPI_F16_RELU || epi == VX_EPI_F16_ADD ||
-           epi == VX_EPI_QKV || epi == VX_EPI_PIXSHUF || epi == VX_EPI_HEAD_OUT;
+           epi == VX_EPI_QKV || epi == VX_EPI_PIXSHUF || epi == VX_EPI_HEAD_OUT || epi == VX_EPI_LRELU_AGC;
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int EPI, bool CONV>
@@ -392,6 +392,15 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                         if constexpr (EPI == VX_EPI_F16_ADD) { if (p.relu) v[j] = fmaxf(v[j], 0.0f); }
                         if constexpr (EPI == VX_EPI_QKV) v[j] *= out_scale;
                     }
+                    if constexpr (EPI == VX_EPI_LRELU_AGC) { // MI-GAN: (+ noise plane of the pixel) -> lrelu 0.2 -> x sqrt2 -> clamp 256
+                        const int m = m0 + wr * WM + ps * WPP + mp * 32 + r;
+                        const float nz = (p.noise && m < p.M) ? p.noise[m % p.noise_hw] : 0.0f;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float t = v[j] + nz;
+                            v[j] = fminf(fmaxf((t < 0.0f ? 0.2f * t : t) * 1.41421356f, -256.0f), 256.0f);
+                        }
+                    }
                     f16x4 o = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
                     const int c8 = nl >> 2;
                     const int phys16 = (c8 >> 1) ^ (ml & (NCH16 - 1));
@@ -419,7 +428,14 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                 part += __shfl_xor(part, 1, 64);
                 part += __shfl_xor(part, 2, 64);
                 if (j == 0) reinterpret_cast<float*>(p.out)[m] = fmaxf(part + p.head_bias, 0.0f) * p.head_scale;
-            } else if constexpr (EPI == VX_EPI_F16 || EPI == VX_EPI_F16_GELU || EPI == VX_EPI_F16_RELU) {
+            } else if constexpr (EPI == VX_EPI_F16 || EPI == VX_EPI_F16_GELU || EPI == VX_EPI_F16_RELU || EPI == VX_EPI_LRELU_AGC) {
+                if constexpr (EPI == VX_EPI_LRELU_AGC) { // + a feature map after the activation (MI-GAN synthesis b4, migan.cpp:119-120)
+                    if (p.res1) {
+                        const f16x8 a = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res1) + (long)m * p.ldo + n);
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) v[q] = (f16)((float)v[q] + (float)a[q]);
+                    }
+                }
                 *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(p.out) + (long)m * p.ldo + n) = v;
             } else if constexpr (EPI == VX_EPI_F16_ADD) {
                 long o = (long)m * p.ldo + n;
@@ -536,6 +552,7 @@ int dispatch_epi(const vx_gemm_args& a, hipStream_t s) {
             case VX_EPI_TOKENS: return dispatch_tile<VX_EPI_TOKENS, false>(a, s);
             case VX_EPI_QKV: return dispatch_tile<VX_EPI_QKV, false>(a, s);
             case VX_EPI_PIXSHUF: return dispatch_tile<VX_EPI_PIXSHUF, false>(a, s);
+            case VX_EPI_LRELU_AGC: return dispatch_tile<VX_EPI_LRELU_AGC, false>(a, s);
             default: break;
         }
     }
@@ -630,6 +647,7 @@ extern "C" int vx_gemm_f16_raw(const vx_gemm_args* args, void* stream) {
         VX_REQUIRE(a.M % (nw * nwh * a.win_ws * a.win_ws) == 0, "vx_gemm_f16: M=%d is not a whole number of %ld x %ld window maps", a.M, nw, nwh);
         VX_REQUIRE(a.win_shift >= 0 && a.win_shift < a.win_ws && a.win_res_h >= 0, "vx_gemm_f16: bad window shift / height");
     }
+    if (a.epi == VX_EPI_LRELU_AGC) VX_REQUIRE(!a.noise || a.noise_hw > 0, "vx_gemm_f16: lrelu_agc noise plane needs noise_hw > 0");
     if (a.epi == VX_EPI_HEAD_OUT) VX_REQUIRE(a.N == 32 && a.lambda, "vx_gemm_f16: head epilogue needs N == 32 and conv3 weights");
     if (a.conv_kh > 0) {
         VX_REQUIRE(a.conv_Cin % 8 == 0, "vx_gemm_f16: conv Cin=%d must be a multiple of 8", a.conv_Cin);

@@ -705,3 +705,93 @@ def write_birefnet_gguf(path: str | Path, cfg: SwinConfig = SWIN_T, seed: int = 
         w.add_tensor(name, t)
     w.write()
     return Path(path)
+
+
+# ---- MI-GAN (reference tests/test_migan.py Encoder / Synthesis, scripts/convert.py:482-499) -------------------------
+
+def migan_channels(res: int, ch_base: int = 32768, ch_max: int = 512) -> list[int]:
+    """Widths of the levels res, res/2, ..., 4: min(ch_base // r, ch_max)."""
+    out, r = [], res
+    while r >= 4:
+        out.append(min(ch_base // r, ch_max))
+        r //= 2
+    return out
+
+
+def _migan_fir(rng, c: int, gain: float) -> np.ndarray:
+    """setup_filter([1, 3, 3, 1], gain) repeated per channel [c, 1, 4, 4], each channel scaled by 1 +- a few %
+    (a trained file holds the same filter everywhere; the perturbation makes the per-channel layout observable)."""
+    f = np.outer([1.0, 3.0, 3.0, 1.0], [1.0, 3.0, 3.0, 1.0])
+    f = f / f.sum() * gain
+    scale = 1.0 + 0.05 * rng.standard_normal((c, 1, 1, 1))
+    return (f[None, None] * scale).astype(np.float32)
+
+
+def migan_state_dict(res: int = 512, ch_base: int = 32768, ch_max: int = 512, seed: int = 0) -> dict[str, np.ndarray]:
+    """float32 tensors with the names and shapes of the torch Encoder(resolution=res, ic_n=4) + Synthesis modules."""
+    rng = np.random.default_rng(seed)
+    sd: dict[str, np.ndarray] = {}
+    ch = migan_channels(res, ch_base, ch_max)
+    rs = [res >> i for i in range(len(ch))]
+
+    def sep(p, cin, cout, r_out, down=False, up=False, noise=False):
+        sd[f"{p}.conv1.weight"] = (rng.standard_normal((cin, 1, 3, 3)) / 3.0).astype(np.float32)
+        sd[f"{p}.conv1.bias"] = (rng.standard_normal(cin) * 0.05).astype(np.float32)
+        sd[f"{p}.conv2.weight"] = (rng.standard_normal((cout, cin, 1, 1)) / np.sqrt(cin)).astype(np.float32)
+        if down:
+            sd[f"{p}.downsample.filter.weight"] = _migan_fir(rng, cin, 1.0)
+        if up:
+            sd[f"{p}.upsample.filter_const"] = np.tile(np.array([[1.0, 0.0], [0.0, 0.0]], np.float32), (r_out // 2, r_out // 2))[None, None]
+            sd[f"{p}.upsample.filter.weight"] = _migan_fir(rng, cout, 4.0)
+        if noise:
+            sd[f"{p}.noise_const"] = rng.standard_normal((r_out, r_out)).astype(np.float32)
+            sd[f"{p}.noise_strength"] = np.array([rng.uniform(0.05, 0.2)], np.float32)
+
+    sd[f"encoder.b{res}.fromrgb.weight"] = (rng.standard_normal((ch[0], 4, 1, 1)) / 2.0).astype(np.float32)
+    sd[f"encoder.b{res}.fromrgb.bias"] = (rng.standard_normal(ch[0]) * 0.05).astype(np.float32)
+    n = len(ch)
+    for i in range(n):
+        last = i == n - 1
+        sep(f"encoder.b{rs[i]}.conv1", ch[i], ch[i], rs[i])
+        sep(f"encoder.b{rs[i]}.conv2", ch[i], ch[i] if last else ch[i + 1], rs[i] if last else rs[i] // 2, down=not last)
+    for i in range(n - 1, -1, -1):
+        first = i == n - 1
+        p = f"synthesis.b{rs[i]}"
+        cin = ch[i] if first else ch[i + 1]
+        sep(f"{p}.conv1", cin, ch[i], rs[i], up=not first, noise=not first)
+        sep(f"{p}.conv2", ch[i], ch[i], rs[i], noise=not first)
+        sd[f"{p}.torgb.weight"] = (rng.standard_normal((3, ch[i], 1, 1)) * 0.12 / np.sqrt(ch[i])).astype(np.float32)
+        sd[f"{p}.torgb.bias"] = (rng.standard_normal(3) * 0.02).astype(np.float32)
+        if not first:
+            sd[f"{p}.upsample.filter_const"] = np.tile(np.array([[1.0, 0.0], [0.0, 0.0]], np.float32), (rs[i] // 2, rs[i] // 2))[None, None]
+            sd[f"{p}.upsample.filter.weight"] = _migan_fir(rng, 3, 4.0)
+    return sd
+
+
+def migan_gguf_tensors(sd: dict[str, np.ndarray]):
+    """convert_migan (scripts/convert.py:482-499) with the default layout: conv kernels (is_conv_2d) stay OIHW and are listed
+    in migan.conv2d_weights; everything stored f16."""
+    out: dict[str, np.ndarray] = {}
+    conv2d: list[int] = []
+    for name, t in sd.items():
+        if _is_conv_2d(name, t):
+            conv2d.append(len(out))
+        out[name] = t.astype(np.float16)
+    return out, conv2d
+
+
+def write_migan_gguf(path: str | Path, res: int = 512, ch_base: int = 32768, ch_max: int = 512, seed: int = 0,
+                     sd: dict[str, np.ndarray] | None = None) -> Path:
+    sd = sd if sd is not None else migan_state_dict(res, ch_base, ch_max, seed)
+    tensors, conv2d = migan_gguf_tensors(sd)
+    w = GGUFWriter(path, "migan")
+    w.add_string("migan.tensor_data_layout", "whcn")
+    w.add_int32("migan.image_size", res)
+    w.add_uint32("general.quantization_version", 2)
+    w.add_uint32("general.file_type", 1)
+    if conv2d:
+        w.add_array_i32("migan.conv2d_weights", conv2d)
+    for name, t in tensors.items():
+        w.add_tensor(name, t)
+    w.write()
+    return Path(path)

@@ -121,7 +121,7 @@ class Model:
         return res
 
     def _family_fn(self, name: str):
-        prefix = {Arch.esrgan: "visp_esrgan_", Arch.sam: "visp_sam_", Arch.birefnet: "visp_swin_"}.get(self.arch, "visp_depthany_")
+        prefix = {Arch.esrgan: "visp_esrgan_", Arch.sam: "visp_sam_", Arch.birefnet: "visp_swin_", Arch.migan: "visp_migan_"}.get(self.arch, "visp_depthany_")
         return getattr(self._api, prefix + name)
 
     # ---- batched extension
@@ -428,3 +428,53 @@ class SwinEncoder(Model):
 
     def encode_batch_device(self, rgb_dev: int, batch: int, w: int, h: int, outs_dev, stream: int | None = None):
         check(self._api.visp_swin_encode_batch_device(self._handle, rgb_dev, batch, w, h, (c_void_p * 4)(*outs_dev), stream))
+
+
+class Migan(Model):
+    """MI-GAN inpainting (reference migan_load_model / migan_compute, vision.h:257-279). Loaded through visp_migan_load:
+    visp_model_load keeps refusing the family."""
+
+    @classmethod
+    def load(cls, path, device: Device):
+        api = get_lib()
+        handle = c_void_p()
+        check(api.visp_migan_load(lib.path_to_char_p(path), device._handle, byref(handle)))
+        return cls(api, handle, Arch.migan, device)
+
+    @property
+    def info(self) -> dict:
+        i = lib.MiganInfo()
+        check(self._api.visp_migan_get_info(self._handle, byref(i)))
+        return dict(resolution=i.resolution, channels=[i.channels[k] for k in range(i.n_levels)])
+
+    def compute(self, image: np.ndarray, mask: np.ndarray, format: ImageFormat | None = None) -> np.ndarray:
+        """image u8 [h, w, 3 | 4], mask u8 [h, w] (alpha_u8) of any extent -> rgba u8 [h, w, 4], alpha = mask."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        msk = np.ascontiguousarray(mask, dtype=np.uint8)
+        h, w, c = img.shape
+        fmt = format or (ImageFormat.rgb_u8 if c == 3 else ImageFormat.rgba_u8)
+        iv = lib.ImageView(w, h, w * c, fmt.value, img.ctypes.data)
+        mv = lib.ImageView(msk.shape[1], msk.shape[0], msk.shape[1], ImageFormat.alpha_u8.value, msk.ctypes.data)
+        out_view, out_data = lib.ImageView(), c_void_p()
+        check(self._api.visp_migan_compute(self._handle, byref(iv), byref(mv), byref(out_view), byref(out_data)))
+        return self._take_image(out_view, out_data)
+
+    def compute_batch(self, images: np.ndarray, masks: np.ndarray) -> np.ndarray:
+        """images u8 [B, res, res, 3 | 4], masks u8 [B, res, res] -> rgba u8 [B, res, res, 4]."""
+        imgs = np.ascontiguousarray(images, dtype=np.uint8)
+        msks = np.ascontiguousarray(masks, dtype=np.uint8)
+        b, h, w, c = imgs.shape
+        assert msks.shape == (b, h, w), (msks.shape, imgs.shape)
+        out = np.empty((b, h, w, 4), np.uint8)
+        check(self._api.visp_migan_compute_batch_host(self._handle, imgs.ctypes.data, c, msks.ctypes.data, b, out.ctypes.data))
+        return out
+
+    def compute_batch_device(self, img_dev: int, channels: int, mask_dev: int, batch: int, out_dev: int, stream: int | None = None):
+        check(self._api.visp_migan_compute_batch_device(self._handle, img_dev, channels, mask_dev, batch, out_dev, stream))
+
+    def generate(self, x: np.ndarray) -> np.ndarray:
+        """migan_process_input's f32 [n, res, res, 4] -> the generator's rgb f32 [n, res, res, 3]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.empty(x.shape[:3] + (3,), np.float32)
+        check(self._api.visp_migan_generate_host(self._handle, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
