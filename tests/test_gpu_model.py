@@ -329,7 +329,7 @@ def test_sharded_entry_two_models_two_threads(small, device, tmp_path):
 
 def test_two_host_threads_two_models_one_device(small, device, tmp_path):
     """Models of one visp_device share its compute stream; every entry that enqueues, captures or synchronises on it holds the device's turn
-    (csrc/depthany.h device_turn). Two host threads, each driving its own model at the same time -- the overlapped pipeline (hipGraph capture on
+    (csrc/model.h device_turn). Two host threads, each driving its own model at the same time -- the overlapped pipeline (hipGraph capture on
     first use, then replay), visp_model_compute on an image of another extent (workspace re-reserve, eager launches, the graph is dropped and
     captured again) -- give results bit-identical to the serial runs. One run, no repeats."""
     import threading

@@ -125,15 +125,7 @@ struct bf_exec {
     void mark(const char* name, double flops, double bytes) { if (m.timing && !dry) tm.mark(name, flops, bytes, stream); }
     static void* off16(void* p, size_t elems) { return p ? static_cast<uint8_t*>(p) + elems * 2 : nullptr; } // f16 element offset
     void capture(const std::string& name, const void* src, int B, int h, int w, int C) { // parity-test hook: contiguous f16 [B, h, w, C]
-        if (!m.captures || dry) return;
-        capture_entry& c = m.capture_bufs[name];
-        const size_t bytes = (size_t)B * h * w * C * 2;
-        vx_free(c.dev);
-        c.dev = nullptr;
-        VX(vx_malloc(&c.dev, bytes));
-        c.shape[0] = B; c.shape[1] = h; c.shape[2] = w; c.shape[3] = C;
-        c.f16 = true;
-        VX(vx_memcpy_d2d(c.dev, src, bytes, stream));
+        if (m.captures && !dry) m.keep_capture(name, src, {B, h, w, C}, true, stream);
     }
 
     void gemm(packed_gemm const& g, const void* A, long M, int lda, void* out, int ldo, int epi, const void* res1, const char* group) {
@@ -313,11 +305,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                 if (m.timing) ex.tm.finish(s, timing, true);
                 swin_encode_pixels(m, low8, B, w / 2, h / 2, so, s);
                 if (m.timing)
-                    for (timing_entry const& t : m.last_timing) {
-                        auto it = std::find_if(timing.begin(), timing.end(), [&](timing_entry const& e) { return e.name == t.name; });
-                        if (it == timing.end()) timing.push_back(t);
-                        else { it->ms += t.ms; it->launches += t.launches; it->flops += t.flops; it->bytes += t.bytes; }
-                    }
+                    for (timing_entry const& t : m.last_timing) timing_add(timing, t);
                 // encode_concat: upscaled half-resolution features behind the full-resolution ones, then stages 0..2 scaled down into stage 3
                 for (int i = 0; i < 4; ++i) {
                     ex.mark("resize", 0, (double)Mi[i] * dims[i][2] * 2.5);

@@ -3,6 +3,7 @@
 // birefnet_load_model / birefnet_compute (reference src/visp/vision.cpp:98-132), birefnet_detect_params / image_extent /
 // process_input / process_output / predict (src/visp/arch/birefnet.cpp:252-323).
 #pragma once
+#include "image.h"
 #include "swin.h"
 
 namespace visp {

@@ -56,30 +56,17 @@ int32_t family_of(visp_model const* m) {
     if (!m) throw except("model handle is null");
     return reinterpret_cast<model_base const*>(m)->family;
 }
-depthany_model& as_depthany(visp_model* m) {
-    if (family_of(m) != VISP_DEPTH_ANYTHING) throw except("model handle is not a depth_anything model (family %d)", family_of(m));
-    return *static_cast<depthany_model*>(reinterpret_cast<model_base*>(m));
+// the handle as family T's model, or the family's refusal
+template <typename T>
+T& as(visp_model const* m, int32_t family, char const* what) {
+    if (family_of(m) != family) throw except("model handle is not %s (family %d)", what, family_of(m));
+    return *static_cast<T*>(reinterpret_cast<model_base*>(const_cast<visp_model*>(m)));
 }
-depthany_model const& as_depthany(visp_model const* m) {
-    if (family_of(m) != VISP_DEPTH_ANYTHING) throw except("model handle is not a depth_anything model (family %d)", family_of(m));
-    return *static_cast<depthany_model const*>(reinterpret_cast<model_base const*>(m));
-}
-esrgan_model& as_esrgan(visp_model* m) {
-    if (family_of(m) != VISP_ESRGAN) throw except("model handle is not an esrgan model (family %d)", family_of(m));
-    return *static_cast<esrgan_model*>(reinterpret_cast<model_base*>(m));
-}
-migan_model& as_migan(visp_model* m) {
-    if (family_of(m) != VISP_MIGAN) throw except("model handle is not a migan model (family %d)", family_of(m));
-    return *static_cast<migan_model*>(reinterpret_cast<model_base*>(m));
-}
-sam_model& as_sam(visp_model* m) {
-    if (family_of(m) != VISP_SAM) throw except("model handle is not a sam model (family %d)", family_of(m));
-    return *static_cast<sam_model*>(reinterpret_cast<model_base*>(m));
-}
-swin_model& as_swin(visp_model* m) { // the encoder half of the birefnet family (visp_swin_load)
-    if (family_of(m) != VISP_BIREFNET) throw except("model handle is not a swin encoder (family %d)", family_of(m));
-    return *static_cast<swin_model*>(reinterpret_cast<model_base*>(m));
-}
+depthany_model& as_depthany(visp_model const* m) { return as<depthany_model>(m, VISP_DEPTH_ANYTHING, "a depth_anything model"); }
+esrgan_model& as_esrgan(visp_model const* m) { return as<esrgan_model>(m, VISP_ESRGAN, "an esrgan model"); }
+migan_model& as_migan(visp_model const* m) { return as<migan_model>(m, VISP_MIGAN, "a migan model"); }
+sam_model& as_sam(visp_model const* m) { return as<sam_model>(m, VISP_SAM, "a sam model"); }
+swin_model& as_swin(visp_model const* m) { return as<swin_model>(m, VISP_BIREFNET, "a swin encoder"); } // the encoder half of the birefnet family (visp_swin_load)
 birefnet_model& as_birefnet(visp_model* m) {
     swin_model& s = as_swin(m);
     if (!s.full) throw except("model handle is a swin encoder (visp_swin_load), not a birefnet model");
@@ -103,23 +90,38 @@ void require_built(int32_t family) {
         throw except("Model family %d is not built in this backend (MI355X backend implements depth_anything, esrgan, sam and birefnet)", family);
 }
 
-void read_capture(backend_device const& dev, std::map<std::string, capture_entry> const& bufs, char const* name, float* host_out,
-                  int64_t capacity, int64_t* n_written, int64_t shape[4]) {
-    auto it = bufs.find(name);
-    if (it == bufs.end()) throw except("capture '%s' not available (enable captures before compute)", name);
+// the accessors every family with captures / timing shares (`who` names the family in the null-argument message)
+void read_capture(model_base& m, char const* who, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
+    if (!name || !n_written) throw except("%s: null argument", who);
+    device_turn turn(*m.backend);
+    auto it = m.capture_bufs.find(name);
+    if (it == m.capture_bufs.end()) throw except("capture '%s' not available (enable captures before compute)", name);
     capture_entry const& c = it->second;
     int64_t n = c.shape[0] * c.shape[1] * c.shape[2] * c.shape[3];
     *n_written = n;
     if (shape) memcpy(shape, c.shape, sizeof(int64_t) * 4);
     if (n > capacity) return; // caller learns the size and retries
-    if (!vx_set_device(dev.index)) throw except("%s", vx_last_error());
     if (c.f16) {
         std::unique_ptr<uint16_t[]> tmp(new uint16_t[(size_t)n]);
-        if (!vx_memcpy_d2h(tmp.get(), c.dev, (size_t)n * 2, dev.stream)) throw except("%s", vx_last_error());
+        if (!vx_memcpy_d2h(tmp.get(), c.dev, (size_t)n * 2, m.backend->stream)) throw except("%s", vx_last_error());
         for (int64_t i = 0; i < n; ++i) host_out[i] = f16_to_f32(tmp[(size_t)i]);
     } else {
-        if (!vx_memcpy_d2h(host_out, c.dev, (size_t)n * 4, dev.stream)) throw except("%s", vx_last_error());
+        if (!vx_memcpy_d2h(host_out, c.dev, (size_t)n * 4, m.backend->stream)) throw except("%s", vx_last_error());
     }
+}
+
+void read_timing(model_base const& m, visp_timing* out, int32_t cap, int32_t* n) {
+    int32_t count = 0;
+    for (timing_entry const& t : m.last_timing) {
+        if (count >= cap) break;
+        snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
+        out[count].ms = t.ms;
+        out[count].launches = t.launches;
+        out[count].flops = t.flops;
+        out[count].bytes = t.bytes;
+        ++count;
+    }
+    *n = count;
 }
 
 void return_image(image_data&& img, visp_image_view* out_image, visp_image_data** out_data) {
@@ -235,13 +237,8 @@ int32_t visp_model_load(char const* filepath, visp_device const* dev, int32_t ar
 void visp_model_destroy(visp_model* model, int32_t arch) {
     if (!model) return;
     // the handle carries its own family; `arch` is what the reference's destroy switch uses (c-api.cpp:224-229)
-    model_base* base = reinterpret_cast<model_base*>(model);
     (void)arch;
-    if (base->family == VISP_DEPTH_ANYTHING) delete static_cast<depthany_model*>(base);
-    else if (base->family == VISP_ESRGAN) delete static_cast<esrgan_model*>(base);
-    else if (base->family == VISP_MIGAN) delete static_cast<migan_model*>(base);
-    else if (base->family == VISP_SAM) delete static_cast<sam_model*>(base);
-    else if (base->family == VISP_BIREFNET) delete static_cast<swin_model*>(base); // swin encoder or full birefnet model (virtual destructor)
+    delete reinterpret_cast<model_base*>(model); // (virtual destructor)
 }
 
 int32_t visp_model_compute(visp_model* model, int32_t family, visp_image_view* inputs, int32_t n_inputs, int32_t* args, int32_t n_args,
@@ -367,7 +364,7 @@ int32_t visp_depthany_compute_sharded(visp_model* const* models, int32_t n_model
         std::vector<std::string> errors((size_t)n_models);
         std::vector<std::thread> threads;
         // models that sit on the same backend_device share its compute stream (a one-GPU rehearsal of the multi-device call): every call
-        // that touches that stream holds the device's turn (device_turn, csrc/depthany.h), so the shards interleave chunk by chunk and a
+        // that touches that stream holds the device's turn (device_turn, csrc/model.h), so the shards interleave chunk by chunk and a
         // hipGraph capture by one thread is never crossed by another thread's launches
         const int base = batch / n_models, rem = batch % n_models;
         for (int i = 0; i < n_models; ++i) {
@@ -444,10 +441,7 @@ int32_t visp_depthany_enable_captures(visp_model* m, int32_t enable) {
 
 int32_t visp_depthany_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written,
                                    int64_t shape[4]) {
-    return handle_errors([&]() {
-        depthany_model& dm = as_depthany(m);
-        read_capture(*dm.backend, dm.capture_bufs, name, host_out, capacity, n_written, shape);
-    });
+    return handle_errors([&]() { read_capture(as_depthany(m), "depthany", name, host_out, capacity, n_written, shape); });
 }
 
 int32_t visp_depthany_enable_timing(visp_model* m, int32_t enable) {
@@ -456,27 +450,14 @@ int32_t visp_depthany_enable_timing(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_depthany_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
-    return handle_errors([&]() {
-        depthany_model& dm = as_depthany(m);
-        int32_t count = 0;
-        for (timing_entry const& t : dm.last_timing) {
-            if (count >= cap) break;
-            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
-            out[count].ms = t.ms;
-            out[count].launches = t.launches;
-            out[count].flops = t.flops;
-            out[count].bytes = t.bytes;
-            ++count;
-        }
-        *n = count;
-    });
+    return handle_errors([&]() { read_timing(as_depthany(m), out, cap, n); });
 }
 
 // ---- ESRGAN extension ----------------------------------------------------------------------
 
 int32_t visp_esrgan_get_info(visp_model const* m, visp_esrgan_info* out) {
     return handle_errors([&]() {
-        esrgan_model const& em = as_esrgan(const_cast<visp_model*>(m));
+        esrgan_model const& em = as_esrgan(m);
         out->scale = em.params.scale;
         out->n_blocks = em.params.n_blocks;
         out->n_filters = em.nf;
@@ -539,20 +520,7 @@ int32_t visp_esrgan_enable_timing(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_esrgan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
-    return handle_errors([&]() {
-        esrgan_model& em = as_esrgan(m);
-        int32_t count = 0;
-        for (timing_entry const& t : em.last_timing) {
-            if (count >= cap) break;
-            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
-            out[count].ms = t.ms;
-            out[count].launches = t.launches;
-            out[count].flops = t.flops;
-            out[count].bytes = t.bytes;
-            ++count;
-        }
-        *n = count;
-    });
+    return handle_errors([&]() { read_timing(as_esrgan(m), out, cap, n); });
 }
 
 // ---- MI-GAN (loaded only through visp_migan_load) ----
@@ -566,7 +534,7 @@ int32_t visp_migan_load(char const* filepath, visp_device const* dev, visp_model
 
 int32_t visp_migan_get_info(visp_model const* m, visp_migan_info* out) {
     return handle_errors([&]() {
-        migan_model const& mm = as_migan(const_cast<visp_model*>(m));
+        migan_model const& mm = as_migan(m);
         memset(out, 0, sizeof *out);
         out->resolution = mm.params.resolution;
         out->n_levels = (int32_t)mm.levels.size();
@@ -600,12 +568,7 @@ int32_t visp_migan_enable_captures(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_migan_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
-    return handle_errors([&]() {
-        migan_model& mm = as_migan(m);
-        if (!name || !n_written) throw except("migan: null argument");
-        device_turn turn(*mm.backend);
-        read_capture(*mm.backend, mm.capture_bufs, name, host_out, capacity, n_written, shape);
-    });
+    return handle_errors([&]() { read_capture(as_migan(m), "migan", name, host_out, capacity, n_written, shape); });
 }
 
 int32_t visp_migan_enable_timing(visp_model* m, int32_t enable) {
@@ -613,20 +576,7 @@ int32_t visp_migan_enable_timing(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_migan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
-    return handle_errors([&]() {
-        migan_model& mm = as_migan(m);
-        int32_t count = 0;
-        for (timing_entry const& t : mm.last_timing) {
-            if (count >= cap) break;
-            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
-            out[count].ms = t.ms;
-            out[count].launches = t.launches;
-            out[count].flops = t.flops;
-            out[count].bytes = t.bytes;
-            ++count;
-        }
-        *n = count;
-    });
+    return handle_errors([&]() { read_timing(as_migan(m), out, cap, n); });
 }
 
 // ---- MobileSAM image encoder (TinyViT) ----
@@ -701,10 +651,7 @@ int32_t visp_sam_enable_captures(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_sam_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
-    return handle_errors([&]() {
-        sam_model& sm = as_sam(m);
-        read_capture(*sm.backend, sm.capture_bufs, name, host_out, capacity, n_written, shape);
-    });
+    return handle_errors([&]() { read_capture(as_sam(m), "sam", name, host_out, capacity, n_written, shape); });
 }
 
 int32_t visp_sam_enable_timing(visp_model* m, int32_t enable) {
@@ -712,20 +659,7 @@ int32_t visp_sam_enable_timing(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_sam_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
-    return handle_errors([&]() {
-        sam_model& sm = as_sam(m);
-        int32_t count = 0;
-        for (timing_entry const& t : sm.last_timing) {
-            if (count >= cap) break;
-            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
-            out[count].ms = t.ms;
-            out[count].launches = t.launches;
-            out[count].flops = t.flops;
-            out[count].bytes = t.bytes;
-            ++count;
-        }
-        *n = count;
-    });
+    return handle_errors([&]() { read_timing(as_sam(m), out, cap, n); });
 }
 
 // ---- SWIN encoder (BiRefNet backbone) ----------------------------------------------------------------------------------
@@ -775,10 +709,7 @@ int32_t visp_swin_enable_captures(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_swin_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
-    return handle_errors([&]() {
-        swin_model& sm = as_swin(m);
-        read_capture(*sm.backend, sm.capture_bufs, name, host_out, capacity, n_written, shape);
-    });
+    return handle_errors([&]() { read_capture(as_swin(m), "swin", name, host_out, capacity, n_written, shape); });
 }
 
 int32_t visp_swin_set_mask_mode(visp_model* m, int32_t shifted_only) {
@@ -790,19 +721,7 @@ int32_t visp_swin_enable_timing(visp_model* m, int32_t enable) {
 }
 
 int32_t visp_swin_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
-    return handle_errors([&]() {
-        int32_t count = 0;
-        for (timing_entry const& t : as_swin(m).last_timing) {
-            if (count >= cap) break;
-            snprintf(out[count].name, sizeof out[count].name, "%s", t.name.c_str());
-            out[count].ms = t.ms;
-            out[count].launches = t.launches;
-            out[count].flops = t.flops;
-            out[count].bytes = t.bytes;
-            ++count;
-        }
-        *n = count;
-    });
+    return handle_errors([&]() { read_timing(as_swin(m), out, cap, n); });
 }
 
 // ---- model file: the GGUF key/value surface of the reference's model_file (ml.h:85-103, ml.cpp:206-281) ----

@@ -23,35 +23,6 @@ T round_up(T x, T m) { return (x + m - 1) / m * m; }
 } // namespace
 
 //
-// backend (reference src/visp/ml.cpp:59-95)
-
-device_turn::device_turn(backend_device const& dev) : lock(dev.turn) { VX(vx_set_device(dev.index)); }
-
-backend_device* backend_init(int device_index) {
-    int n = vx_device_count();
-    if (n <= 0) throw except("Failed to initialize backend, no suitable device available");
-    if (device_index < 0 || device_index >= n) throw except("Failed to initialize backend, device index %d out of range (%d devices)", device_index, n);
-    VX(vx_set_device(device_index));
-    char name[256] = {0}, arch[128] = {0};
-    size_t total = 0;
-    int n_cu = 0;
-    VX(vx_device_info(device_index, name, sizeof name, arch, sizeof arch, &total, nullptr, &n_cu));
-    if (strncmp(arch, "gfx950", 6) != 0)
-        throw except("Failed to initialize backend: device %d is %s, this backend is built for gfx950 (MI355X) only", device_index, arch);
-    auto* d = new backend_device;
-    d->index = device_index;
-    d->name = std::string("HIP") + std::to_string(device_index);
-    d->description = std::string(name) + " (" + arch + ")";
-    d->total_mem = total;
-    d->n_cu = n_cu;
-    VX(vx_stream_create(&d->stream));
-    return d;
-}
-backend_device::~backend_device() {
-    if (stream) vx_stream_destroy(stream);
-}
-
-//
 // params (reference dino.cpp:119-126, depth-anything.cpp:112-128)
 
 dino_params dino_detect_params(model_file const& file) {
@@ -356,25 +327,16 @@ void run_parts(depthany_model& m, depthany_step& s, void* stream) {
         }
     }
     if (!timed) return;
-    std::map<std::string, timing_entry> by;
-    std::vector<std::string> order;
+    m.last_timing.clear();
     for (size_t i = 0; i + 1 < stamps.size(); ++i) {
         if (stamps[i].launch < 0) continue; // the end mark of a part
         graph_launch const& l = s.parts[(size_t)stamps[i].part].g->launches[(size_t)stamps[i].launch];
-        float ms = 0;
-        VX(vx_event_elapsed_ms(stamps[i].ev, stamps[i + 1].ev, &ms));
         static const bool detail = getenv("VISP_TIMING_DETAIL") != nullptr; // one row per launch (tools/dpt_launches.py)
-        std::string name = l.group.empty() ? "other" : l.group;
-        if (detail) name += "#" + std::to_string(i) + " " + l.desc.substr(0, 40);
-        auto it = by.find(name);
-        if (it == by.end()) { order.push_back(name); it = by.emplace(name, timing_entry{name, 0, 0, 0, 0}).first; }
-        it->second.ms += ms;
-        it->second.launches += 1;
-        it->second.flops += l.flops;
-        it->second.bytes += l.bytes;
+        timing_entry t{l.group.empty() ? "other" : l.group, 0, 1, l.flops, l.bytes};
+        if (detail) t.name += "#" + std::to_string(i) + " " + l.desc.substr(0, 40);
+        VX(vx_event_elapsed_ms(stamps[i].ev, stamps[i + 1].ev, &t.ms));
+        timing_add(m.last_timing, t);
     }
-    m.last_timing.clear();
-    for (auto const& nm : order) m.last_timing.push_back(by[nm]);
     for (auto& st : stamps) vx_event_destroy(st.ev);
 }
 
@@ -387,17 +349,11 @@ void collect_captures(depthany_model& m, depthany_step& s, void* stream) {
         int r = kv.second;
         while (g.nodes[r].alias_of >= 0) r = g.nodes[r].alias_of;
         if (g.nodes[r].buffer < 0) continue;
-        capture_entry& c = m.capture_bufs[kv.first];
-        if (c.dev) vx_free(c.dev);
-        c.f16 = g.nodes[r].dtype == gdt_f16;
         // ggml ne order -> the slowest dimension first, batch in front: tokens [D, T, B, 1] -> {B, T, D, 1}; maps [C, W, H, B] -> {B, H, W, C}
         const int64_t* ne = n.ne;
         const bool token_rows = kv.first == "tokens" || kv.first.rfind("layer_", 0) == 0 || kv.first.rfind("dino_layer_", 0) == 0;
-        if (token_rows) { c.shape[0] = ne[2]; c.shape[1] = ne[1]; c.shape[2] = ne[0]; c.shape[3] = 1; }
-        else { c.shape[0] = ne[3]; c.shape[1] = ne[2]; c.shape[2] = ne[1]; c.shape[3] = ne[0]; }
-        const size_t bytes = (size_t)n.n_elements() * (c.f16 ? 2 : 4);
-        VX(vx_malloc(&c.dev, bytes));
-        VX(vx_memcpy_d2d(c.dev, graph_tensor_device_ptr(g, kv.second), bytes, stream));
+        const int64_t shape[4] = {token_rows ? ne[2] : ne[3], token_rows ? ne[1] : ne[2], token_rows ? ne[0] : ne[1], token_rows ? 1 : ne[0]};
+        m.keep_capture(kv.first, graph_tensor_device_ptr(g, kv.second), shape, g.nodes[r].dtype == gdt_f16, stream);
     }
 }
 
@@ -484,7 +440,6 @@ depthany_model::~depthany_model() {
     for (void* s : aux_stream) vx_stream_destroy(s);
     vx_event_destroy(fork_event);
     for (void* e : join_event) vx_event_destroy(e);
-    for (auto& c : capture_bufs) vx_free(c.second.dev);
 }
 
 depthany_model* depthany_clone_executor(depthany_model const& src) {

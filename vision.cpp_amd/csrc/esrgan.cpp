@@ -4,7 +4,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 
 #include "../../include/visp_hip_kernels.h"
 #include "graph.h"
@@ -286,40 +285,10 @@ esrgan_step& step_for(esrgan_model& m, int lane, int n, int w, int h) {
 struct exec {
     esrgan_model& m;
     void* stream;
-    std::vector<std::pair<std::string, void*>> marks;
-    std::vector<timing_entry> acc;
+    timing_marks tm;
 
-    void mark(const char* name, double flops, double bytes) {
-        if (!m.timing) return;
-        void* ev = nullptr;
-        VX(vx_event_create(&ev));
-        VX(vx_event_record(ev, stream));
-        marks.push_back({name, ev});
-        acc.push_back({name, 0, 1, flops, bytes});
-    }
-    void finish_timing() {
-        if (!m.timing) return;
-        void* ev = nullptr;
-        VX(vx_event_create(&ev));
-        VX(vx_event_record(ev, stream));
-        marks.push_back({"end", ev});
-        std::map<std::string, timing_entry> by;
-        std::vector<std::string> order;
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float ms = 0;
-            VX(vx_event_elapsed_ms(marks[i].second, marks[i + 1].second, &ms));
-            auto it = by.find(marks[i].first);
-            if (it == by.end()) { order.push_back(marks[i].first); it = by.emplace(marks[i].first, timing_entry{marks[i].first, 0, 0, 0, 0}).first; }
-            it->second.ms += ms;
-            it->second.launches += acc[i].launches;
-            it->second.flops += acc[i].flops;
-            it->second.bytes += acc[i].bytes;
-        }
-        m.last_timing.clear();
-        for (auto& n : order) m.last_timing.push_back(by[n]);
-        for (auto& mk : marks) vx_event_destroy(mk.second);
-        marks.clear();
-    }
+    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
+    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
 
     // esrgan_generate (esrgan.cpp:55-79) on n tiles: rgb f32 [n, h, w, 3] -> rgb f32 [n, h*s, w*s, 3], both in the call's workspace
     void generate(int lane, const float* x0, int n, int w, int h, float* out) {
@@ -369,7 +338,7 @@ void esrgan_compute_batch_device(esrgan_model& m, void const* img_dev, int batch
     tile_layout tiles_out = tile_scale(tiles, m.params.scale);
     const int n_total = batch * tiles.total();
     reserve(m, n_total, tiles.tile_size[0], tiles.tile_size[1]);
-    exec ex{m, s, {}, {}};
+    exec ex{m, s, {}};
     vx_tile_layout tin = to_vx(tiles), tout = to_vx(tiles_out);
     ex.mark("tiles_in", 0, (double)n_total * tiles.tile_size[0] * tiles.tile_size[1] * 15);
     VX(vx_esrgan_tiles_in_f32(static_cast<const uint8_t*>(img_dev), batch, w, h, int(format), &tin, static_cast<float*>(m.ws.x0), s));
@@ -423,7 +392,7 @@ void esrgan_generate_host(esrgan_model& m, float const* rgb, int n, int w, int h
     const size_t px = (size_t)n * w * h;
     void* s = m.backend->stream;
     VX(vx_memcpy_h2d(m.ws.x0, rgb, px * 3 * 4, s));
-    exec ex{m, s, {}, {}};
+    exec ex{m, s, {}};
     run_tiles(m, ex, n, w, h);
     ex.finish_timing();
     const int sc = m.params.scale;

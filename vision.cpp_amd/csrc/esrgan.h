@@ -11,7 +11,9 @@
 #include <string>
 #include <vector>
 
-#include "depthany.h"
+#include "gguf.h"
+#include "image.h"
+#include "model.h"
 
 namespace visp {
 
@@ -54,7 +56,6 @@ struct esrgan_step {
 
 struct esrgan_model : model_base { // vision.h:361-369 counterpart
     esrgan_model() : model_base(family_esrgan) {}
-    backend_device const* backend = nullptr;
     esrgan_params params;
     int nf = 64, gc = 32;                    // filters / growth channels of the file
     std::shared_ptr<weight_store> store;     // the file's tensors + their packed device images (one arena: what a load-time broadcast moves)
@@ -69,9 +70,7 @@ struct esrgan_model : model_base { // vision.h:361-369 counterpart
     int streams = 2;
     void* aux_stream = nullptr;
     void *fork_event = nullptr, *join_event = nullptr;
-    bool timing = false;
-    std::vector<timing_entry> last_timing;
-    ~esrgan_model();
+    ~esrgan_model() override;
 };
 
 esrgan_model* esrgan_load_model(char const* filepath, backend_device const& dev, int flags = load_default);

@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "depthany.h"
+#include "model.h"
 #include "gguf.h"
 
 namespace visp {

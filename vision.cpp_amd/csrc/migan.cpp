@@ -206,51 +206,16 @@ struct migan_exec {
     uint8_t* ws;
     migan_layout L;
     int B;
-    std::vector<std::pair<std::string, void*>> marks;
-    std::vector<timing_entry> acc;
+    timing_marks tm;
 
     template <typename T = float>
     const T* w(size_t off) const { return off == SIZE_MAX ? nullptr : reinterpret_cast<const T*>(wa + off); }
     void* at(size_t off) const { return ws + off; }
 
-    void mark(const char* name, double flops, double bytes) {
-        if (!m.timing) return;
-        void* ev = nullptr;
-        VX(vx_event_create(&ev));
-        VX(vx_event_record(ev, stream));
-        marks.push_back({name, ev});
-        acc.push_back({name, 0, 1, flops, bytes});
-    }
-    void finish_timing() {
-        if (!m.timing) return;
-        mark("end", 0, 0);
-        std::map<std::string, timing_entry> by;
-        std::vector<std::string> order;
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float ms = 0;
-            VX(vx_event_elapsed_ms(marks[i].second, marks[i + 1].second, &ms));
-            auto it = by.find(marks[i].first);
-            if (it == by.end()) { order.push_back(marks[i].first); it = by.emplace(marks[i].first, timing_entry{marks[i].first, 0, 0, 0, 0}).first; }
-            it->second.ms += ms;
-            it->second.launches += acc[i].launches;
-            it->second.flops += acc[i].flops;
-            it->second.bytes += acc[i].bytes;
-        }
-        m.last_timing.clear();
-        for (auto& n : order) m.last_timing.push_back(by[n]);
-        for (auto& mk : marks) vx_event_destroy(mk.second);
-        marks.clear();
-    }
+    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
+    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
     void capture(std::string const& name, const void* src, int res, int C, bool f16) {
-        if (!m.captures) return;
-        capture_entry& c = m.capture_bufs[name];
-        const size_t bytes = (size_t)B * res * res * C * (f16 ? 2 : 4);
-        vx_free(c.dev);
-        c.dev = nullptr;
-        VX(vx_malloc(&c.dev, bytes));
-        c.shape[0] = B; c.shape[1] = res; c.shape[2] = res; c.shape[3] = C;
-        c.f16 = f16;
-        VX(vx_memcpy_d2d(c.dev, src, bytes, stream));
+        if (m.captures) m.keep_capture(name, src, {B, res, res, C}, f16, stream);
     }
 
     void dw(migan_sep const& s, const void* x, void* y) {
@@ -335,7 +300,7 @@ migan_exec make_exec(migan_model& m, int B, void* stream) {
         m.ws.bytes = L.total;
         m.ws_batch = B;
     }
-    return migan_exec{m, stream, static_cast<const uint8_t*>(m.weight_arena.ptr), static_cast<uint8_t*>(m.ws.ptr), plan(m, B), B, {}, {}};
+    return migan_exec{m, stream, static_cast<const uint8_t*>(m.weight_arena.ptr), static_cast<uint8_t*>(m.ws.ptr), plan(m, B), B, {}};
 }
 
 // the u8 -> rgba launch list on the workspace's own input / output buffers
@@ -355,7 +320,6 @@ void run_u8(migan_exec& ex, int img_channels) {
 
 migan_model::~migan_model() {
     drop_graphs(*this);
-    for (auto& c : capture_bufs) vx_free(c.second.dev);
     vx_free(ws.ptr);
     vx_free(weight_arena.ptr);
 }

@@ -9,7 +9,9 @@
 #include <memory>
 #include <vector>
 
-#include "depthany.h"
+#include "gguf.h"
+#include "image.h"
+#include "model.h"
 
 namespace visp {
 
@@ -36,7 +38,6 @@ struct migan_level {
 
 struct migan_model : model_base { // vision.h:371-375 counterpart
     migan_model() : model_base(family_migan) {}
-    backend_device const* backend = nullptr;
     migan_params params;
     std::vector<migan_level> levels; // [0] = resolution ... [n-1] = 4
     size_t fromrgb_w = SIZE_MAX, fromrgb_b = SIZE_MAX; // f32 [ch0][4], [ch0]
@@ -44,10 +45,8 @@ struct migan_model : model_base { // vision.h:371-375 counterpart
     device_buffer ws;
     int ws_batch = 0;
     std::map<int, void*> graphs; // batch size -> captured launch list of the u8 -> rgba path (one stream, no branches)
-    bool use_graph = true, captures = false, timing = false;
-    std::map<std::string, capture_entry> capture_bufs;
-    std::vector<timing_entry> last_timing;
-    ~migan_model();
+    bool use_graph = true;
+    ~migan_model() override;
 };
 
 migan_model* migan_load_model(char const* filepath, backend_device const& dev);

@@ -1,0 +1,86 @@
+// What every model family of the MI355X backend shares: the device and its turn, the handle base with the per-group timing and
+// the captured intermediate maps of the last pass, and the small weight / buffer records the loaders pack. Host C++ only; all
+// device work goes through the vx_* C ABI (include/visp_hip_kernels.h).
+#pragma once
+#include <cstdint>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace visp {
+
+enum class backend_type : int32_t { cpu = 1, gpu = 2, vulkan = 2 | 1 << 8 }; // include/visp/ml.h:32-36
+
+struct backend_device { // include/visp/ml.h:44-55, here: one HIP device + its compute stream
+    int index = 0;
+    std::string name, description;
+    void* stream = nullptr;
+    size_t total_mem = 0;
+    int n_cu = 0;
+    backend_type type() const { return backend_type::gpu; }
+    // Every model and graph made on this device shares `stream`. Whatever enqueues on it, captures a hipGraph on it or synchronises it
+    // holds the device's turn (device_turn below), so that host threads driving different models of one device cannot interleave a
+    // capture with another thread's launches ("capturing stream has unjoined work"). Recursive: entry points nest.
+    mutable std::recursive_mutex turn;
+    ~backend_device();
+};
+// makes the device current for the calling thread and holds its turn for the scope
+struct device_turn {
+    std::unique_lock<std::recursive_mutex> lock;
+    explicit device_turn(backend_device const& dev);
+};
+backend_device* backend_init(int device_index); // throws visp::exception if no gfx950 device
+
+// One GEMM-shaped weight in a packed arena: f16 [N][K] (both padded for the kernel's tiles, pads are zero) + optional f32 bias [N]
+// (the model loaders that pack for hand schedules: tinyvit.cpp, swin.cpp, birefnet.cpp)
+struct packed_gemm {
+    size_t w = 0, b = SIZE_MAX; // byte offsets into the arena
+    size_t dw = SIZE_MAX;       // 3x3 convs with Cin % 32 == 0, Cout in {32, 64}: the same kernel as vx_dconv3x3_f16 slabs
+    int d_cin = 0;              // [cin/32][9][cout][32] f16 (16-byte groups at g ^ ((n >> 2) & 3)), see kernels_dconv.hip
+    int N = 0, K = 0;           // padded
+    int n_real = 0, k_real = 0; // for FLOP accounting and n_valid
+};
+struct packed_vec { size_t off = SIZE_MAX; int n = 0; }; // f32 vector
+
+struct device_buffer { void* ptr = nullptr; size_t bytes = 0; };
+
+struct capture_entry { void* dev = nullptr; int64_t shape[4] = {1, 1, 1, 1}; bool f16 = true; };
+
+struct timing_entry { std::string name; float ms = 0; int launches = 0; double flops = 0, bytes = 0; };
+// adds t to the row of its name, or appends it as a new row: a table keeps its rows in first-seen order
+void timing_add(std::vector<timing_entry>& rows, timing_entry const& t);
+
+// every model handle starts with its family (the C ABI's handles are untyped: c-api.cpp:193 any_model)
+enum model_family_id : int32_t { family_sam = 0, family_birefnet, family_depth_anything, family_migan, family_esrgan, family_count };
+struct model_base {
+    int32_t family;
+    backend_device const* backend = nullptr;
+    bool captures = false, timing = false;
+    std::map<std::string, capture_entry> capture_bufs; // named intermediate maps of the last pass with captures on (the parity tests)
+    std::vector<timing_entry> last_timing;             // per kernel group, of the last pass with timing on
+    explicit model_base(int32_t f) : family(f) {}
+    model_base(model_base const&) = delete;
+    model_base& operator=(model_base const&) = delete;
+    virtual ~model_base(); // frees the capture buffers on the model's device
+    // a device copy of the contiguous map at src (shape[0] * .. * shape[3] f16 or f32 elements), enqueued on stream, as capture `name`
+    void keep_capture(std::string const& name, void const* src, int64_t const (&shape)[4], bool f16, void* stream);
+};
+
+// per-kernel-group timing of one pass on one stream: an event in front of every launch, summed per group name by finish()
+struct timing_marks {
+    std::vector<void*> events;           // events[i] is recorded in front of launches[i]
+    std::vector<timing_entry> launches;
+    timing_marks() = default;
+    timing_marks(timing_marks const&) = delete; // owns its events
+    timing_marks& operator=(timing_marks const&) = delete;
+    void mark(const char* name, double flops, double bytes, void* stream);
+    // out = the marked groups (append: added to the rows out already holds); the events are released
+    void finish(void* stream, std::vector<timing_entry>& out, bool append = false);
+    void release();
+    ~timing_marks() { release(); }
+};
+
+enum load_flags { load_default = 0, load_no_upload = 1 };
+
+} // namespace visp

@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "../../include/visp_hip_kernels.h"
-#include "tinyvit.h" // packed_gemm / packed_vec (depthany.h), packed_dw
+#include "tinyvit.h" // packed_gemm / packed_vec (model.h), packed_dw
 #include "visp_util.h"
 
 namespace visp {

@@ -38,7 +38,6 @@ swin_params swin_detect_params(model_file const& f) { // swin.cpp:293-302
 
 swin_model::~swin_model() {
     vx_free(ws.ptr);
-    for (auto& c : capture_bufs) vx_free(c.second.dev);
     vx_free(weight_arena.ptr);
 }
 
@@ -140,40 +139,6 @@ void swin_output_dims(swin_model const& m, int w, int h, int dims[4][3]) {
     }
 }
 
-void timing_marks::mark(const char* name, double flops, double bytes, void* stream) {
-    void* ev = nullptr;
-    VX(vx_event_create(&ev));
-    VX(vx_event_record(ev, stream));
-    marks.push_back({name, ev});
-    acc.push_back({name, 0, 1, flops, bytes});
-}
-
-void timing_marks::finish(void* stream, std::vector<timing_entry>& out, bool append) {
-    void* ev = nullptr;
-    VX(vx_event_create(&ev));
-    VX(vx_event_record(ev, stream));
-    marks.push_back({"end", ev});
-    std::map<std::string, timing_entry> by;
-    std::vector<std::string> order;
-    if (append)
-        for (timing_entry const& t : out) { order.push_back(t.name); by[t.name] = t; }
-    for (size_t i = 0; i + 1 < marks.size(); ++i) {
-        float ms = 0;
-        VX(vx_event_elapsed_ms(marks[i].second, marks[i + 1].second, &ms));
-        auto it = by.find(marks[i].first);
-        if (it == by.end()) { order.push_back(marks[i].first); it = by.emplace(marks[i].first, timing_entry{marks[i].first, 0, 0, 0, 0}).first; }
-        it->second.ms += ms;
-        it->second.launches += acc[i].launches;
-        it->second.flops += acc[i].flops;
-        it->second.bytes += acc[i].bytes;
-    }
-    out.clear();
-    for (auto& n : order) out.push_back(by[n]);
-    for (auto& mk : marks) vx_event_destroy(mk.second);
-    marks.clear();
-    acc.clear();
-}
-
 namespace {
 
 struct swin_exec {
@@ -199,15 +164,7 @@ struct swin_exec {
         VX(vx_gemm_f16(&a, stream));
     }
     void capture(const std::string& name, const void* src, int B, int h, int w, int C) {
-        if (!m.captures) return;
-        capture_entry& c = m.capture_bufs[name];
-        const size_t bytes = (size_t)B * h * w * C * 2;
-        vx_free(c.dev);
-        c.dev = nullptr;
-        VX(vx_malloc(&c.dev, bytes));
-        c.shape[0] = B; c.shape[1] = h; c.shape[2] = w; c.shape[3] = C;
-        c.f16 = true;
-        VX(vx_memcpy_d2d(c.dev, src, bytes, stream));
+        if (m.captures) m.keep_capture(name, src, {B, h, w, C}, true, stream);
     }
 };
 

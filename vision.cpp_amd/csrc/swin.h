@@ -6,17 +6,10 @@
 #pragma once
 #include <vector>
 
-#include "depthany.h"
+#include "gguf.h"
+#include "model.h"
 
 namespace visp {
-
-// per-kernel-group timing of one pass (HIP events between launches), shared by the swin and birefnet executors
-struct timing_marks {
-    std::vector<std::pair<std::string, void*>> marks;
-    std::vector<timing_entry> acc;
-    void mark(const char* name, double flops, double bytes, void* stream);
-    void finish(void* stream, std::vector<timing_entry>& out, bool append = false);
-};
 
 struct swin_layer_t { int depth, n_heads, n_features; };
 struct swin_params { // vision.h swin_params; swin_t_params / swin_l_params of swin.cpp:264-291
@@ -43,21 +36,17 @@ struct swin_weights {
 struct swin_model : model_base { // the encoder half of vision.h birefnet_model
     swin_model() : model_base(family_birefnet) {}
     bool full = false; // true: this object is a birefnet_model (birefnet.h) -- encoder + decoder
-    backend_device const* backend = nullptr;
     swin_params params;
     swin_weights weights;
     device_buffer weight_arena;
     device_buffer ws;
-    bool timing = false, captures = false;
     // Shift-mask semantics. The reference's swin::layer hands the layer's attn_mask to EVERY block (swin.cpp:226-237) and
     // swin::block forwards it to window_attention unconditionally (:128-139), so the -inf edge mask of compute_attention_mask
     // (:165-210) also acts in the UNSHIFTED blocks (the windows of the last row / column). That is what the reference computes,
     // and the default here. Its torch twin (tests/test_birefnet.py:249-255, the original Swin) masks shifted blocks only:
     // mask_shifted_only = true (visp_swin_set_mask_mode(m, 1) / VISP_SWIN_MASK_SHIFTED_ONLY=1 at load) selects that.
     bool mask_shifted_only = false;
-    std::vector<timing_entry> last_timing;
-    std::map<std::string, capture_entry> capture_bufs;
-    virtual ~swin_model();
+    ~swin_model() override;
 };
 
 swin_model* swin_load_model(char const* filepath, backend_device const& dev, char const* prefix = "bb");

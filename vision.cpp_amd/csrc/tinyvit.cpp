@@ -5,7 +5,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <map>
 
 #include "../../include/visp_hip_kernels.h"
 #include "packer.h"
@@ -224,7 +223,6 @@ sam_model::~sam_model() {
     vx_free(ws.ptr);
     vx_free(embed.ptr);
     vx_free(dec_ws.ptr);
-    for (auto& c : capture_bufs) vx_free(c.second.dev);
     vx_free(weight_arena.ptr);
 }
 
@@ -234,42 +232,12 @@ struct tv_exec {
     sam_model& m;
     void* stream;
     const uint8_t* wa;
-    std::vector<std::pair<std::string, void*>> marks;
-    std::vector<timing_entry> acc;
+    timing_marks tm;
     int gemm_variant = 0; // vx_gemm_args.stages: tile-shape selector of the plain GEMM (0 = its default)
 
     const float* fptr(packed_vec const& v) const { return reinterpret_cast<const float*>(wa + v.off); }
-    void mark(const char* name, double flops, double bytes) {
-        if (!m.timing) return;
-        void* ev = nullptr;
-        VX(vx_event_create(&ev));
-        VX(vx_event_record(ev, stream));
-        marks.push_back({name, ev});
-        acc.push_back({name, 0, 1, flops, bytes});
-    }
-    void finish_timing() {
-        if (!m.timing) return;
-        void* ev = nullptr;
-        VX(vx_event_create(&ev));
-        VX(vx_event_record(ev, stream));
-        marks.push_back({"end", ev});
-        std::map<std::string, timing_entry> by;
-        std::vector<std::string> order;
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float ms = 0;
-            VX(vx_event_elapsed_ms(marks[i].second, marks[i + 1].second, &ms));
-            auto it = by.find(marks[i].first);
-            if (it == by.end()) { order.push_back(marks[i].first); it = by.emplace(marks[i].first, timing_entry{marks[i].first, 0, 0, 0, 0}).first; }
-            it->second.ms += ms;
-            it->second.launches += acc[i].launches;
-            it->second.flops += acc[i].flops;
-            it->second.bytes += acc[i].bytes;
-        }
-        m.last_timing.clear();
-        for (auto& n : order) m.last_timing.push_back(by[n]);
-        for (auto& mk : marks) vx_event_destroy(mk.second);
-        marks.clear();
-    }
+    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
+    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
 
     // C[M, N] = A[M, lda] * W^T (+bias) with the epilogues of the GEMM family
     void gemm(packed_gemm const& g, const void* A, long M, int lda, void* out, int epi, const void* res1, const char* group,
@@ -323,15 +291,7 @@ struct tv_exec {
         VX(vx_gemm_fp8(&a, stream));
     }
     void capture(const char* name, const void* src, int B, int res, int C) {
-        if (!m.captures) return;
-        capture_entry& c = m.capture_bufs[name];
-        const size_t bytes = (size_t)B * res * res * C * 2;
-        vx_free(c.dev);
-        c.dev = nullptr;
-        VX(vx_malloc(&c.dev, bytes));
-        c.shape[0] = B; c.shape[1] = res; c.shape[2] = res; c.shape[3] = C;
-        c.f16 = true;
-        VX(vx_memcpy_d2d(c.dev, src, bytes, stream));
+        if (m.captures) m.keep_capture(name, src, {B, res, res, C}, true, stream);
     }
     void dw(packed_dw const& d, const void* x, void* y, int B, int H, int W, int stride, bool gelu, const char* group) {
         mark(group, 2.0 * B * (H / stride) * (W / stride) * 9 * d.C, (double)B * H * W * d.C * 2 * (1.0 + 1.0 / (stride * stride)));
@@ -367,7 +327,7 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
     void* in8 = base + 4 * big;
     void* pe = base + 4 * big + in_bytes;
 
-    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}, {}};
+    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}};
     if (const char* e = getenv("VISP_TV_GEMM_VARIANT")) ex.gemm_variant = atoi(e);
     const bool fuse_mbconv = !getenv("VISP_TV_NO_FUSED_MBCONV");
     ex.mark("preprocess", 0, (double)B * S * S * 19);
@@ -577,7 +537,7 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
     void *pq = P(o_pq), *pk = P(o_pk), *pv = P(o_pv), *ao = P(o_ao), *u1 = P(o_u1), *u1n = P(o_u1n), *u2p = P(o_u2p), *u2 = P(o_u2);
     void *hy = P(o_hy), *ha = P(o_ha), *hb = P(o_hb), *masks_d = P(o_mask), *iou_d = P(o_iou), *scaled = P(o_scaled), *mask_u8 = P(o_out);
 
-    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}, {}};
+    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}};
     const bool timing = m.timing;
     m.timing = false; // the per-group table belongs to the encoder
     const uint8_t* wa = ex.wa;

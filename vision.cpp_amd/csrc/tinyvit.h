@@ -5,7 +5,9 @@
 #pragma once
 #include <vector>
 
-#include "depthany.h"
+#include "gguf.h"
+#include "image.h"
+#include "model.h"
 
 namespace visp {
 
@@ -66,7 +68,6 @@ struct samdec_weights {
 
 struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     sam_model() : model_base(family_sam) {}
-    backend_device const* backend = nullptr;
     tiny_vit_params params;
     tinyvit_weights weights;
     device_buffer weight_arena;
@@ -78,15 +79,12 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     float last_iou[4] = {0, 0, 0, 0};
     device_buffer embed;          // image embedding of the last sam_encode: f32 [64, 64, 256] (NHWC)
     i32x2 image_extent = {{0, 0}}; // extent of the image passed to sam_encode (vision.h sam_model::image_extent)
-    bool timing = false, captures = false;
     // BASELINE.json configs[4] ("fp8 GGUF weights on CDNA4 fp8 MFMA"), opt-in and never the default: the MLPs of the transformer stages
     // (mobile-sam.cpp:150-160: fc1 + gelu, fc2 + residual -- 39 % of the encoder's time) on the block-scaled e4m3 matrix instruction, activations
     // quantised per token on the way in. The decision on accuracy stands (tests/test_fp8_decision.py: mask IoU below the bar); this is the measured form of it.
     bool fp8_mlp = false;
     device_buffer fp8_arena, fp8_ws;
-    std::vector<timing_entry> last_timing;
-    std::map<std::string, capture_entry> capture_bufs;
-    ~sam_model();
+    ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
 
