@@ -13,8 +13,8 @@
 // those sources themselves: src/visp/arch/dino.cpp and depth-anything.cpp compile unmodified against these headers with
 // -DVISP_GGML_NAMES -DVISP_ARCH_FROM_SOURCE (tests/test_reference_sources_compile.py). With VISP_ARCH_FROM_SOURCE the pipeline pieces
 // the reference defines in depth-anything.cpp (image_extent / process_input / process_output) are declared here, not defined.
-// Not covered: the *_predict builders of the other families (hand schedules only). migan_* loads through visp_migan_load
-// (visp_model_load refuses the family).
+// Not covered: the *_predict builders of the other families (hand schedules only). migan_* loads through visp_migan_load and
+// yolov9t::* through visp_yolov9t_load (visp_model_load refuses both).
 #pragma once
 
 #include <algorithm>
@@ -26,6 +26,7 @@
 #include <span>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../visp_c_api.h"
 
@@ -313,6 +314,51 @@ inline image_data migan_process_output(std::span<float const> data, i32x2 extent
         }
     return out;
 }
+
+// YOLOv9t (reference src/visp/arch/yolov9t.h, namespace visp::yolov9t): loaded through visp_yolov9t_load, since the reference has no
+// model_family for it. detect = letterbox + network + non_max_suppression + scale_boxes
+// (inference_yolov9t.cpp:300-405); inputs rgb_u8 / rgba_u8 (alpha ignored).
+namespace yolov9t {
+using detected_obj = visp_detection; // {x1, y1, x2, y2, confidence, class_id, class_confidence} (yolov9t.h:30-35)
+struct NMSParams { // yolov9t.h:68-74 field names; the defaults are the values inference_yolov9t.cpp:383 passes (max_det 300, max_wh 640)
+    float conf_thres = 0.25f;
+    float iou_thres = 0.45f;
+    int max_det = 300;
+    int max_nms = 30000;
+    int max_wh = 640;
+};
+struct LetterboxResult { image_data img; float gain = 1, pad_w = 0, pad_h = 0; }; // yolov9t.h:13-18
+using yolov9t_model = detail::model_handle<VISP_FAMILY_COUNT>; // outside visp_model_family; visp_model_destroy ignores the family
+struct yolov9t_params { int num_classes = 80, input_size = 640, reg_max = 16; };
+
+inline yolov9t_model yolov9t_load_model(char const* filepath, backend_device const& dev) {
+    visp_model* m = nullptr;
+    detail::check(visp_yolov9t_load(filepath, dev.handle, &m));
+    return yolov9t_model(m);
+}
+inline yolov9t_params yolov9t_detect_params(yolov9t_model const& model) {
+    visp_yolov9t_info info{};
+    detail::check(visp_yolov9t_get_info(model.handle, &info));
+    return yolov9t_params{info.num_classes, info.input_size, info.reg_max};
+}
+// letterbox (yolov9t.cpp:1028-1083) to size x size rgb_u8 with the colour-114 border
+inline LetterboxResult letterbox(image_view image, int size = 640) {
+    LetterboxResult r;
+    r.img = image_alloc(i32x2{size, size}, image_format::rgb_u8);
+    visp_image_view in = detail::c_view(image);
+    detail::check(visp_yolov9t_letterbox(&in, size, r.img.data.get(), &r.gain, &r.pad_w, &r.pad_h));
+    return r;
+}
+inline std::vector<detected_obj> yolov9t_detect(yolov9t_model& model, image_view image, NMSParams const& p = {}) {
+    const visp_yolov9t_nms_params c{p.conf_thres, p.iou_thres, p.max_det, p.max_nms, p.max_wh};
+    std::vector<detected_obj> out(size_t(std::max(p.max_det, 0)));
+    visp_image_view in = detail::c_view(image);
+    int32_t n = 0;
+    detail::check(visp_yolov9t_detect(model.handle, &in, &c, out.data(), int32_t(out.size()), &n));
+    out.resize(size_t(std::min<int32_t>(n, int32_t(out.size()))));
+    return out;
+}
+} // namespace yolov9t
 
 // ESRGAN (vision.h:284-304): any size, tiled, -> rgba_u8 at scale x the input extent (vision.cpp:220-253)
 using esrgan_model = detail::model_handle<VISP_ESRGAN>;

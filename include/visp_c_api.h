@@ -6,7 +6,8 @@
  * ctypes binding (bindings/python/visioncpp/_lib.py:118-171) binds. Return value 1 = ok,
  * 0 = error with the message available from visp_get_last_error() (thread-local,
  * c-api.cpp:6-21). Built behind it: depth_anything, esrgan, sam (MobileSAM: image encoder + prompt encoder / mask decoder) and
- * birefnet (swin-T / BiRefNet-lite); migan through visp_migan_load (visp_model_load returns "not built in this backend").
+ * birefnet (swin-T / BiRefNet-lite); migan through visp_migan_load (visp_model_load returns "not built in this backend"); yolov9t
+ * through visp_yolov9t_load (the reference has no model_family for it).
  *
  * Part 2 is the batched, device-resident extension the reference does not have (its
  * depthany_compute is batch 1, src/visp/vision.cpp:155): it is what bench.py and a
@@ -207,6 +208,46 @@ VISP_API int32_t visp_migan_read_capture(visp_model* m, char const* name, float*
                                          int64_t shape[4]);
 VISP_API int32_t visp_migan_enable_timing(visp_model* m, int32_t enable);
 VISP_API int32_t visp_migan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n);
+
+/* ---- YOLOv9t extension (reference src/visp/arch/yolov9t.cpp, src/cli/inference_yolov9t.cpp:300-405) ------------------------------
+ * The reference never adds the family to model_family: visp_model_load and visp_model_detect_family keep refusing / ignoring a
+ * "yolov9t" file; it loads through visp_yolov9t_load and is destroyed with visp_model_destroy. Inputs are rgb_u8 / rgba_u8 (alpha
+ * ignored). Detections are in the pixel coordinates of the image given (detect) or of the S x S input (batch entries). */
+typedef struct visp_detection { float x1, y1, x2, y2, confidence; int32_t class_id; float class_confidence; } visp_detection; /* detected_obj */
+/* non_max_suppression's arguments; visp_yolov9t_nms_defaults gives the CLI's: conf 0.25, iou 0.45, max_det 300, max_nms 30000, max_wh 640.
+ * Every (anchor, class) with score >= conf is a candidate (multi-label); ties of the score are ordered by (anchor, class). */
+typedef struct visp_yolov9t_nms_params { float conf, iou; int32_t max_det, max_nms, max_wh; } visp_yolov9t_nms_params;
+typedef struct visp_yolov9t_info { int32_t input_size, num_classes, reg_max, n_anchors; } visp_yolov9t_info; /* n_anchors at input_size */
+VISP_API void visp_yolov9t_nms_defaults(visp_yolov9t_nms_params* out);
+VISP_API int32_t visp_yolov9t_load(char const* filepath, visp_device const* dev, visp_model** out);
+VISP_API int32_t visp_yolov9t_get_info(visp_model const* m, visp_yolov9t_info* out);
+/* one image of any extent: letterbox to input_size, network, NMS, boxes scaled back to the image. params NULL = defaults.
+ * Writes min(found, capacity) detections in score order and the number found to *n. */
+VISP_API int32_t visp_yolov9t_detect(visp_model* m, visp_image_view const* image, visp_yolov9t_nms_params const* params, visp_detection* out,
+                                     int32_t capacity, int32_t* n);
+/* B images already letterboxed, u8 [B, size, size, channels] (3 or 4) -> out [B][max_det] detections in input pixels + counts [B].
+ * size: a multiple of 32 from 64 up. The device form reads a device pointer (stream = hipStream_t or NULL) and returns host results;
+ * the launch list is replayed as a hipGraph per (batch, size, channels, conf) after the first call. */
+VISP_API int32_t visp_yolov9t_detect_batch_host(visp_model* m, uint8_t const* img, int32_t channels, int32_t batch, int32_t size,
+                                                visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts);
+VISP_API int32_t visp_yolov9t_detect_batch_device(visp_model* m, void const* img, int32_t channels, int32_t batch, int32_t size,
+                                                  visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts, void* stream);
+/* the network on f32 rgb [n, size, size, 3] in [0, 1] -> boxes f32 [n, A, 4] (xyxy, input pixels), scores f32 [n, A, nc] (host buffers) */
+VISP_API int32_t visp_yolov9t_forward_host(visp_model* m, float const* rgb, int32_t n, int32_t size, float* boxes, float* scores);
+/* host only: letterbox (rgb_u8 / rgba_u8 of any extent -> rgb_u8 [size, size, 3]) and NMS over dense boxes [A, 4] / scores [A, nc] */
+VISP_API int32_t visp_yolov9t_letterbox(visp_image_view const* image, int32_t size, uint8_t* out_rgb, float* gain, float* pad_w, float* pad_h);
+/* host only: scale_boxes (yolov9t.cpp:1255-1281) in place: (v - pad) / gain with the unrounded pads, clamped to [0, width] / [0, height] */
+VISP_API int32_t visp_yolov9t_scale_boxes(visp_detection* dets, int32_t n, int32_t width, int32_t height, float gain, float pad_w, float pad_h);
+/* the last batch call (detect, detect_batch_*) split in ms: {launch list on the device (HIP events), candidate readback, host NMS} */
+VISP_API int32_t visp_yolov9t_last_split(visp_model const* m, float out_ms[3]);
+VISP_API int32_t visp_yolov9t_nms(float const* boxes, float const* scores, int32_t n_anchors, int32_t nc, visp_yolov9t_nms_params const* params,
+                                  visp_detection* out, int32_t capacity, int32_t* n);
+/* captures of the next computes: "model.<i>" (i = 0..21), "detect.raw<l>", "boxes", "scores" (computes run without the hipGraph) */
+VISP_API int32_t visp_yolov9t_enable_captures(visp_model* m, int32_t enable);
+VISP_API int32_t visp_yolov9t_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written,
+                                           int64_t shape[4]);
+VISP_API int32_t visp_yolov9t_enable_timing(visp_model* m, int32_t enable);
+VISP_API int32_t visp_yolov9t_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n);
 
 /* ---- MobileSAM extension (family 0; reference vision.h:186-222, vision.cpp:26-92, mobile-sam.cpp) ----
  * visp_model_load / visp_model_compute work as in the reference: one image + 2 (point) or 4 (box) integer arguments in

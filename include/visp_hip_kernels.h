@@ -74,6 +74,8 @@ enum vx_epilogue {
                              head.conv2 + ReLU + head.conv3 (1x1 -> 1) + ReLU fused (depth-anything.cpp:87-94) */
     VX_EPI_LRELU_AGC = 9, /* MI-GAN: out f16 = clamp(lrelu_0.2(acc + bias + noise[m % noise_hw]) * sqrt2, +-256); noise f32 plane
                              or NULL; then + res1 f16 [M, ldo] if given (plain GEMM only; migan.cpp:17-26, 53-82) */
+    VX_EPI_SILU = 10,     /* YOLOv9t Conv: out f16 = silu(acc + bias), then + res1 f16 [M, ld_res1] if given (the RepBottleneck
+                             shortcut, added after the activation; yolov9t.cpp:78-120, 304-330). Plain GEMM and implicit conv */
 };
 
 typedef struct {
@@ -125,6 +127,10 @@ typedef struct {
     void* debug_stamps; /* diagnostics only: u64 [blocks][8] s_memtime stamps per phase, NULL in product */
     const float* noise; /* VX_EPI_LRELU_AGC: f32 [noise_hw] (noise_const * noise_strength) added at row m % noise_hw, or NULL */
     int noise_hw;
+    /* implicit conv: elements between consecutive input pixels (0 = conv_Cin), so that a conv reads a channel slice of a wider
+     * NHWC map (A points at the slice's first channel; a multiple of 8, >= conv_Cin) */
+    int64_t conv_pix;
+    int64_t ld_res1;    /* row stride of res1 in elements (0 = ldo); VX_EPI_SILU only */
 } vx_gemm_args;
 
 VX_API int vx_gemm_f16(const vx_gemm_args* args, void* stream);
@@ -422,6 +428,28 @@ VX_API int vx_migan_preprocess(const uint8_t* img, int img_channels, const uint8
                                void* out, int64_t n_pixels, int C, void* stream);
 /* rgba u8 [n_pixels, 4] = trunc(clamp(img * 0.5 + 0.5, 0, 1) * 255) of rgb f32, alpha = mask */
 VX_API int vx_migan_postprocess(const float* img, const uint8_t* mask, uint8_t* rgba, int64_t n_pixels, void* stream);
+
+/* ---- YOLOv9t detector (yolov9t.cpp, kernels_yolov9t.hip): NHWC f16 maps, f32 arithmetic. *_pix = elements between consecutive
+ * pixels of a map, so that a producer writes (or a consumer reads) a channel slice of a wider concat buffer; C % 8 == 0, pointers
+ * and pixel strides 16-byte aligned.
+ * preprocess: rgb / rgba u8 [n][channels] (alpha ignored) or f32 rgb [n][3] -> f16 [n][8] = v / 255 (u8) or v (f32), channels 3..7 zero */
+VX_API int vx_yolo_preprocess(const uint8_t* img_u8, int channels, const float* img_f32, void* out8, int64_t n_pixels, void* stream);
+/* AConv's avg_pool 2x2 / stride 1 / no pad (yolov9t.cpp:165-185): x [B, H, W, C] -> y [B, H-1, W-1, C] (contiguous) */
+VX_API int vx_yolo_avgpool2_f16(const void* x, int64_t x_pix, void* y, int B, int H, int W, int C, void* stream);
+/* SPPELAN's three chained 5x5 / stride 1 / pad 2 max pools (yolov9t.cpp:449-484) in one pass: buf [B, H, W, pix] holds cv1's
+ * output in channels [0, C); channels [C, 2C), [2C, 3C), [3C, 4C) receive the 5-, 9- and 13-wide window maxima (clipped at the
+ * border, which equals the chained pools with -inf padding). pix >= 4C */
+VX_API int vx_yolo_spp_f16(void* buf, int64_t pix, int B, int H, int W, int C, void* stream);
+/* nearest x2 upsample (yolov9t.cpp:486-493): x [B, h, w, C] -> y [B, 2h, 2w, C] */
+VX_API int vx_yolo_upsample2_f16(const void* x, int64_t x_pix, void* y, int64_t y_pix, int B, int h, int w, int C, void* stream);
+/* Detect inference (yolov9t.cpp:631-770, 875-925): raw[l] f16 [B, S/s_l, S/s_l, 64 + nc] with s_l = 8, 16, 32 (channels: 4 sides x 16
+ * DFL bins side-major, then nc class logits). Per anchor (levels in order, y-major): softmax over the bins and the expectation with
+ * arange(16), dist2bbox xyxy around cell + 0.5, times the stride -> boxes f32 [B, A, 4]; sigmoid -> scores f32 [B, A, nc]. Every
+ * (anchor, class) with score >= conf is appended to image b's list: cand_idx[b * A * nc + i] = anchor * nc + class, cand_score the
+ * same f32 score; cand_count i32 [B] must be zero on entry (the list holds A * nc entries and cannot overflow; its order is not
+ * deterministic). cand_* may be NULL (dense outputs only). nc % 8 == 0 */
+VX_API int vx_yolo_decode(const void* raw0, const void* raw1, const void* raw2, int B, int S, int nc, float* boxes, float* scores, float conf,
+                          int* cand_count, int* cand_idx, float* cand_score, void* stream);
 
 #ifdef __cplusplus
 }

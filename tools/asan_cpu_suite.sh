@@ -7,7 +7,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 src=$root/vision.cpp_amd/csrc
 make -s -C "$src"
 mkdir -p /tmp/asan && rm -f /tmp/asan/*.o /tmp/asan/log* /tmp/asan/ublog*
-host="gguf image image_resize model depthany esrgan tinyvit swin birefnet migan graph c_api"
+host="gguf image image_resize model depthany esrgan tinyvit swin birefnet migan yolov9t graph c_api"
 for f in $host; do g++ -O1 -g -fPIC -std=c++17 -fvisibility=hidden -fsanitize=address,undefined -fno-omit-frame-pointer -c "$src/$f.cpp" -o /tmp/asan/$f.o; done
 objs=$(make -s -C "$src" print-obj | tr ' ' '\n' | grep -v -E "build/($(echo $host | tr ' ' '|'))\.o" | sed "s|^|$src/|" | tr '\n' ' ')
 g++ -shared -fPIC -o /tmp/asan/libvisioncpp_asan.so $objs /tmp/asan/*.o -fsanitize=address,undefined -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib

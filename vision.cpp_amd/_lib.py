@@ -38,6 +38,19 @@ class MiganInfo(ctypes.Structure):  # == visp_migan_info
     _fields_ = [("resolution", c_int32), ("n_levels", c_int32), ("channels", c_int32 * 9)]
 
 
+class Detection(ctypes.Structure):  # == visp_detection
+    _fields_ = [("x1", c_float), ("y1", c_float), ("x2", c_float), ("y2", c_float), ("confidence", c_float), ("class_id", c_int32),
+                ("class_confidence", c_float)]
+
+
+class Yolov9tNmsParams(ctypes.Structure):  # == visp_yolov9t_nms_params
+    _fields_ = [("conf", c_float), ("iou", c_float), ("max_det", c_int32), ("max_nms", c_int32), ("max_wh", c_int32)]
+
+
+class Yolov9tInfo(ctypes.Structure):  # == visp_yolov9t_info
+    _fields_ = [(n, c_int32) for n in ("input_size", "num_classes", "reg_max", "n_anchors")]
+
+
 class DconvArgs(ctypes.Structure):  # == vx_dconv_args
     _fields_ = [
         ("x", c_void_p), ("x_plane", c_int64), ("cin", c_int), ("up2", c_int), ("B", c_int), ("H", c_int), ("W", c_int),
@@ -71,7 +84,7 @@ class GemmArgs(ctypes.Structure):  # == vx_gemm_args
         ("ps_s", c_int), ("ps_Cout", c_int), ("ps_H", c_int), ("ps_W", c_int),
         ("res1", c_void_p), ("res2", c_void_p), ("n_valid", c_int), ("stages", c_int), ("head_bias", c_float), ("head_scale", c_float),
         ("post_gelu", c_int), ("win_ws", c_int), ("win_res", c_int), ("win_res_h", c_int), ("win_shift", c_int), ("k_splits", c_int), ("k_partial", c_void_p), ("debug_stamps", c_void_p),
-        ("noise", c_void_p), ("noise_hw", c_int),
+        ("noise", c_void_p), ("noise_hw", c_int), ("conv_pix", c_int64), ("ld_res1", c_int64),
     ]
 
 
@@ -93,7 +106,7 @@ class DinoBlockArgs(ctypes.Structure):  # == vx_dino_block_args
     ]
 
 
-EPI_F16, EPI_F16_GELU, EPI_F16_RELU, EPI_RESID_F32, EPI_TOKENS, EPI_QKV, EPI_PIXSHUF, EPI_F16_ADD, EPI_HEAD_OUT, EPI_LRELU_AGC = range(10)
+EPI_F16, EPI_F16_GELU, EPI_F16_RELU, EPI_RESID_F32, EPI_TOKENS, EPI_QKV, EPI_PIXSHUF, EPI_F16_ADD, EPI_HEAD_OUT, EPI_LRELU_AGC, EPI_SILU = range(11)
 
 import os
 
@@ -126,6 +139,9 @@ C_API_SYMBOLS = [
     "visp_graph_op", "visp_graph_set_name", "visp_graph_get_tensor", "visp_graph_output", "visp_graph_tensor_info", "visp_graph_read_constant",
     "visp_graph_allocate", "visp_graph_set_fused_models", "visp_graph_use_hip_graph", "visp_graph_compute", "visp_graph_tensor_set", "visp_graph_tensor_get", "visp_graph_describe",    "visp_migan_load", "visp_migan_get_info", "visp_migan_compute", "visp_migan_compute_batch_device", "visp_migan_compute_batch_host",
     "visp_migan_generate_host", "visp_migan_enable_captures", "visp_migan_read_capture", "visp_migan_enable_timing", "visp_migan_read_timing",
+    "visp_yolov9t_nms_defaults", "visp_yolov9t_load", "visp_yolov9t_get_info", "visp_yolov9t_detect", "visp_yolov9t_detect_batch_host",
+    "visp_yolov9t_detect_batch_device", "visp_yolov9t_forward_host", "visp_yolov9t_letterbox", "visp_yolov9t_nms", "visp_yolov9t_enable_captures",
+    "visp_yolov9t_read_capture", "visp_yolov9t_enable_timing", "visp_yolov9t_read_timing", "visp_yolov9t_scale_boxes", "visp_yolov9t_last_split",
 ]
 KERNEL_SYMBOLS = [
     "vx_last_error", "vx_device_count", "vx_set_device", "vx_device_info", "vx_malloc", "vx_free", "vx_memset",
@@ -142,6 +158,7 @@ KERNEL_SYMBOLS = [
     "vx_headconv_frag_bytes", "vx_headconv_pack", "vx_headconv_supported", "vx_headconv_bil_f16", "vx_headconv_set_stamps",
     "vx_copy_strided_f16", "vx_binary_rows", "vx_unary_f16", "vx_convert", "vx_im2col_patches_f32", "vx_conv1x1_to1_f32",
     "vx_dino_block_supported", "vx_dino_block_mlp_bytes", "vx_dino_block_qkv_bytes", "vx_dino_block16_pack_mlp", "vx_dino_block16_pack_qkv", "vx_dino_block16_f16",    "vx_migan_dwconv_f16", "vx_migan_upsample_f16", "vx_migan_torgb", "vx_migan_preprocess", "vx_migan_postprocess",
+    "vx_yolo_preprocess", "vx_yolo_avgpool2_f16", "vx_yolo_spp_f16", "vx_yolo_upsample2_f16", "vx_yolo_decode",
 ]
 
 
@@ -223,6 +240,23 @@ def init() -> ctypes.CDLL:
     lib.visp_migan_read_capture.argtypes = [c_void_p, c_char_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64)]
     lib.visp_migan_enable_timing.argtypes = [c_void_p, c_int32]
     lib.visp_migan_read_timing.argtypes = [c_void_p, POINTER(Timing), c_int32, POINTER(c_int32)]
+    lib.visp_yolov9t_nms_defaults.argtypes = [POINTER(Yolov9tNmsParams)]
+    lib.visp_yolov9t_load.argtypes = [c_char_p, c_void_p, POINTER(c_void_p)]
+    lib.visp_yolov9t_get_info.argtypes = [c_void_p, POINTER(Yolov9tInfo)]
+    lib.visp_yolov9t_detect.argtypes = [c_void_p, POINTER(ImageView), POINTER(Yolov9tNmsParams), c_void_p, c_int32, POINTER(c_int32)]
+    lib.visp_yolov9t_detect_batch_host.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(Yolov9tNmsParams), c_void_p,
+                                                   POINTER(c_int32)]
+    lib.visp_yolov9t_detect_batch_device.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(Yolov9tNmsParams), c_void_p,
+                                                     POINTER(c_int32), c_void_p]
+    lib.visp_yolov9t_forward_host.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]
+    lib.visp_yolov9t_letterbox.argtypes = [POINTER(ImageView), c_int32, c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]
+    lib.visp_yolov9t_nms.argtypes = [c_void_p, c_void_p, c_int32, c_int32, POINTER(Yolov9tNmsParams), c_void_p, c_int32, POINTER(c_int32)]
+    lib.visp_yolov9t_scale_boxes.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_float]
+    lib.visp_yolov9t_last_split.argtypes = [c_void_p, c_void_p]
+    lib.visp_yolov9t_enable_captures.argtypes = [c_void_p, c_int32]
+    lib.visp_yolov9t_read_capture.argtypes = [c_void_p, c_char_p, c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64)]
+    lib.visp_yolov9t_enable_timing.argtypes = [c_void_p, c_int32]
+    lib.visp_yolov9t_read_timing.argtypes = [c_void_p, POINTER(Timing), c_int32, POINTER(c_int32)]
     lib.visp_sam_encode.argtypes = [c_void_p, POINTER(ImageView)]
     lib.visp_sam_read_embedding.argtypes = [c_void_p, c_void_p, c_int64, POINTER(c_int64)]
     lib.visp_sam_encode_batch_device.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
@@ -287,6 +321,7 @@ def init() -> ctypes.CDLL:
     lib.visp_depthany_pipeline_destroy.restype = None
     lib.visp_graph_destroy.restype = None
     lib.visp_weights_destroy.restype = None
+    lib.visp_yolov9t_nms_defaults.restype = None
     lib.visp_file_destroy.restype = None
 
     lib.vx_last_error.restype = c_char_p
@@ -373,6 +408,11 @@ def init() -> ctypes.CDLL:
     lib.vx_migan_torgb.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.vx_migan_preprocess.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
     lib.vx_migan_postprocess.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vx_yolo_preprocess.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vx_yolo_avgpool2_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_yolo_spp_f16.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_yolo_upsample2_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_yolo_decode.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in KERNEL_SYMBOLS[1:]:
         getattr(lib, name).restype = c_int
     lib.vx_attention_set_fast_limit.restype = None

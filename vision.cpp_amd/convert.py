@@ -161,3 +161,58 @@ def convert_sam(state_dict: dict[str, np.ndarray], out_path: str | Path) -> Path
         w.add_tensor(name, t)
     w.write()
     return Path(out_path)
+
+
+# ---- YOLOv9t (reference src/visp/arch/yolov9t.cpp; the reference ships no converter for this family) ------------------------
+
+def fold_yolov9t(state_dict: dict[str, np.ndarray], bn_eps: float = 1e-3) -> dict[str, np.ndarray]:
+    """A torch state dict of the tiny model (e.g. the yolov9t_converted.pth the reference's scripts/yolov9t.py saves) -> the tensor
+    set the graph reads: every `<p>.bn.*` folded into `<p>.conv.weight` / `<p>.conv.bias` (Conv is always called with bn=false,
+    yolov9t.cpp:78-120), the head renamed from `model.22.` to `detect.`, the fixed DFL projection (dfl.conv.weight = arange(16)) and
+    num_batches_tracked dropped. bn_eps: the checkpoint's BatchNorm eps (1e-3 for ultralytics). A dict that is already folded passes."""
+    sd = {k: np.asarray(v) for k, v in state_dict.items()}
+    out: dict[str, np.ndarray] = {}
+    for k, v in sd.items():
+        if k.startswith("model.22."):
+            k = "detect." + k[len("model.22."):]
+        if ".dfl." in k or k.endswith("num_batches_tracked") or ".bn." in k:
+            continue
+        out[k] = v.astype(np.float32)
+    for k, v in sd.items():
+        if not k.endswith(".bn.weight"):
+            continue
+        p = k[: -len(".bn.weight")]
+        gamma, beta = v.astype(np.float64), sd[p + ".bn.bias"].astype(np.float64)
+        mean, var = sd[p + ".bn.running_mean"].astype(np.float64), sd[p + ".bn.running_var"].astype(np.float64)
+        q = "detect." + p[len("model.22."):] if p.startswith("model.22.") else p
+        w = sd[p + ".conv.weight"].astype(np.float64)
+        b = sd[p + ".conv.bias"].astype(np.float64) if p + ".conv.bias" in sd else np.zeros(w.shape[0])
+        s = gamma / np.sqrt(var + bn_eps)
+        out[q + ".conv.weight"] = (w * s[:, None, None, None]).astype(np.float32)
+        out[q + ".conv.bias"] = ((b - mean) * s + beta).astype(np.float32)
+    return out
+
+
+def convert_yolov9t(state_dict: dict[str, np.ndarray], out_path: str | Path, bn_eps: float = 1e-3) -> Path:
+    """fold_yolov9t, then GGUF: general.architecture = "yolov9t", yolov9t.tensor_data_layout = "whcn", conv kernels f16 OIHW listed
+    in yolov9t.conv2d_weights, biases f32, general.file_type 1 (f16), tensors in state-dict order."""
+    sd = fold_yolov9t(state_dict, bn_eps)
+    if "detect.cv3.0.2.weight" not in sd:
+        raise ValueError("not a YOLOv9t state dict: no detect.cv3.0.2.weight (or model.22.cv3.0.2.weight)")
+    w = GGUFWriter(out_path, "yolov9t")
+    w.add_string("yolov9t.tensor_data_layout", "whcn")
+    w.add_uint32("general.quantization_version", 2)
+    w.add_uint32("general.file_type", 1)
+    conv2d: list[int] = []
+    tensors: dict[str, np.ndarray] = {}
+    for name, t in sd.items():
+        if name.endswith(".weight") and t.ndim == 4:
+            conv2d.append(len(tensors))
+            tensors[name] = t.astype(np.float16)
+        else:
+            tensors[name] = t.astype(np.float32)
+    w.add_array_i32("yolov9t.conv2d_weights", conv2d)
+    for name, t in tensors.items():
+        w.add_tensor(name, t)
+    w.write()
+    return Path(out_path)

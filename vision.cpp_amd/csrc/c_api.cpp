@@ -17,6 +17,7 @@
 #include "depthany.h"
 #include "esrgan.h"
 #include "migan.h"
+#include "yolov9t.h"
 #include "tinyvit.h"
 #include "swin.h"
 #include "birefnet.h"
@@ -65,6 +66,7 @@ T& as(visp_model const* m, int32_t family, char const* what) {
 depthany_model& as_depthany(visp_model const* m) { return as<depthany_model>(m, VISP_DEPTH_ANYTHING, "a depth_anything model"); }
 esrgan_model& as_esrgan(visp_model const* m) { return as<esrgan_model>(m, VISP_ESRGAN, "an esrgan model"); }
 migan_model& as_migan(visp_model const* m) { return as<migan_model>(m, VISP_MIGAN, "a migan model"); }
+yolov9t_model& as_yolov9t(visp_model const* m) { return as<yolov9t_model>(m, family_yolov9t, "a yolov9t model"); }
 sam_model& as_sam(visp_model const* m) { return as<sam_model>(m, VISP_SAM, "a sam model"); }
 swin_model& as_swin(visp_model const* m) { return as<swin_model>(m, VISP_BIREFNET, "a swin encoder"); } // the encoder half of the birefnet family (visp_swin_load)
 birefnet_model& as_birefnet(visp_model* m) {
@@ -577,6 +579,135 @@ int32_t visp_migan_enable_timing(visp_model* m, int32_t enable) {
 
 int32_t visp_migan_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
     return handle_errors([&]() { read_timing(as_migan(m), out, cap, n); });
+}
+
+// ---- YOLOv9t (loaded only through visp_yolov9t_load) ----
+
+void visp_yolov9t_nms_defaults(visp_yolov9t_nms_params* out) {
+    if (!out) return;
+    yolo_nms_params d;
+    *out = visp_yolov9t_nms_params{d.conf, d.iou, d.max_det, d.max_nms, d.max_wh};
+}
+
+static yolo_nms_params nms_params(visp_yolov9t_nms_params const* p) {
+    yolo_nms_params d;
+    if (p) d = yolo_nms_params{p->conf, p->iou, p->max_det, p->max_nms, p->max_wh};
+    return d;
+}
+
+static visp_detection to_c(yolo_detection const& d) { return visp_detection{d.x1, d.y1, d.x2, d.y2, d.confidence, d.class_id, d.class_confidence}; }
+
+static void write_detections(std::vector<yolo_detection> const& d, visp_detection* out, int32_t capacity, int32_t* n) {
+    for (size_t i = 0; i < d.size() && (int64_t)i < capacity; ++i) out[i] = to_c(d[i]);
+    *n = (int32_t)d.size();
+}
+
+static void write_batch(std::vector<std::vector<yolo_detection>> const& r, int max_det, visp_detection* out, int32_t* counts) {
+    for (size_t b = 0; b < r.size(); ++b) {
+        for (size_t i = 0; i < r[b].size(); ++i) out[b * (size_t)max_det + i] = to_c(r[b][i]);
+        counts[b] = (int32_t)r[b].size();
+    }
+}
+
+int32_t visp_yolov9t_load(char const* filepath, visp_device const* dev, visp_model** out) {
+    return handle_errors([&]() {
+        if (!filepath || !dev || !out) throw except("yolov9t: null argument");
+        *out = handle_of(yolov9t_load_model(filepath, *dev));
+    });
+}
+
+int32_t visp_yolov9t_get_info(visp_model const* m, visp_yolov9t_info* out) {
+    return handle_errors([&]() {
+        if (!out) throw except("yolov9t: null argument");
+        yolov9t_model const& ym = as_yolov9t(m);
+        *out = visp_yolov9t_info{ym.input_size, ym.num_classes, ym.reg_max, yolov9t_anchors(ym.input_size)};
+    });
+}
+
+int32_t visp_yolov9t_detect(visp_model* m, visp_image_view const* image, visp_yolov9t_nms_params const* params, visp_detection* out, int32_t capacity,
+                            int32_t* n) {
+    return handle_errors([&]() {
+        if (!image || !image->data || (!out && capacity > 0) || !n) throw except("yolov9t: null argument");
+        image_view im{i32x2{{image->width, image->height}}, image->stride, image_format(image->format), image->data};
+        write_detections(yolov9t_detect(as_yolov9t(m), im, nms_params(params)), out, capacity, n);
+    });
+}
+
+int32_t visp_yolov9t_detect_batch_host(visp_model* m, uint8_t const* img, int32_t channels, int32_t batch, int32_t size,
+                                       visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts) {
+    return handle_errors([&]() {
+        if (!img || !out || !counts) throw except("yolov9t: null input/output pointer");
+        yolo_nms_params p = nms_params(params);
+        write_batch(yolov9t_detect_batch_host(as_yolov9t(m), img, channels, batch, size, p), p.max_det, out, counts);
+    });
+}
+
+int32_t visp_yolov9t_detect_batch_device(visp_model* m, void const* img, int32_t channels, int32_t batch, int32_t size,
+                                         visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts, void* stream) {
+    return handle_errors([&]() {
+        if (!img || !out || !counts) throw except("yolov9t: null input/output pointer");
+        yolo_nms_params p = nms_params(params);
+        write_batch(yolov9t_detect_batch_device(as_yolov9t(m), img, channels, batch, size, p, stream), p.max_det, out, counts);
+    });
+}
+
+int32_t visp_yolov9t_forward_host(visp_model* m, float const* rgb, int32_t n, int32_t size, float* boxes, float* scores) {
+    return handle_errors([&]() { yolov9t_forward_host(as_yolov9t(m), rgb, n, size, boxes, scores); });
+}
+
+int32_t visp_yolov9t_letterbox(visp_image_view const* image, int32_t size, uint8_t* out_rgb, float* gain, float* pad_w, float* pad_h) {
+    return handle_errors([&]() {
+        if (!image || !image->data || !out_rgb || !gain || !pad_w || !pad_h) throw except("yolov9t: null argument");
+        image_view im{i32x2{{image->width, image->height}}, image->stride, image_format(image->format), image->data};
+        yolo_letterbox lb = yolov9t_letterbox(im, size);
+        memcpy(out_rgb, lb.img.data.get(), (size_t)size * size * 3);
+        *gain = lb.gain;
+        *pad_w = lb.pad_w;
+        *pad_h = lb.pad_h;
+    });
+}
+
+int32_t visp_yolov9t_nms(float const* boxes, float const* scores, int32_t n_anchors, int32_t nc, visp_yolov9t_nms_params const* params, visp_detection* out,
+                         int32_t capacity, int32_t* n) {
+    return handle_errors([&]() {
+        if ((!out && capacity > 0) || !n) throw except("yolov9t: null argument");
+        write_detections(yolov9t_nms(boxes, scores, n_anchors, nc, nms_params(params)), out, capacity, n);
+    });
+}
+
+int32_t visp_yolov9t_scale_boxes(visp_detection* dets, int32_t n, int32_t width, int32_t height, float gain, float pad_w, float pad_h) {
+    return handle_errors([&]() {
+        if ((!dets && n > 0) || n < 0) throw except("yolov9t: null argument");
+        if (!(gain > 0.0f)) throw except("yolov9t: gain %g must be positive", gain);
+        std::vector<yolo_detection> d((size_t)n);
+        for (int32_t i = 0; i < n; ++i) d[(size_t)i] = yolo_detection{dets[i].x1, dets[i].y1, dets[i].x2, dets[i].y2, dets[i].confidence, dets[i].class_id, dets[i].class_confidence};
+        yolov9t_scale_boxes(d, i32x2{{width, height}}, gain, pad_w, pad_h);
+        for (int32_t i = 0; i < n; ++i) dets[i] = to_c(d[(size_t)i]);
+    });
+}
+
+int32_t visp_yolov9t_last_split(visp_model const* m, float out_ms[3]) {
+    return handle_errors([&]() {
+        if (!out_ms) throw except("yolov9t: null argument");
+        yolov9t_model const& ym = as_yolov9t(m);
+        for (int i = 0; i < 3; ++i) out_ms[i] = ym.last_split_ms[i];
+    });
+}
+
+int32_t visp_yolov9t_enable_captures(visp_model* m, int32_t enable) {
+    return handle_errors([&]() { as_yolov9t(m).captures = enable != 0; });
+}
+
+int32_t visp_yolov9t_read_capture(visp_model* m, char const* name, float* host_out, int64_t capacity, int64_t* n_written, int64_t shape[4]) {
+    return handle_errors([&]() { read_capture(as_yolov9t(m), "yolov9t", name, host_out, capacity, n_written, shape); });
+}
+
+int32_t visp_yolov9t_enable_timing(visp_model* m, int32_t enable) {
+    return handle_errors([&]() { as_yolov9t(m).timing = enable != 0; });
+}
+
+int32_t visp_yolov9t_read_timing(visp_model* m, visp_timing* out, int32_t cap, int32_t* n) {
+    return handle_errors([&]() { read_timing(as_yolov9t(m), out, cap, n); });
 }
 
 // ---- MobileSAM image encoder (TinyViT) ----

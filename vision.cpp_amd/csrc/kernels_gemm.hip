@@ -45,9 +45,14 @@ __device__ __forceinline__ float gelu_tanh(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+__device__ __forceinline__ float silu(float x) { // x * sigmoid(x) = x / (1 + exp(-x)); exp2 of a large argument gives inf and x * 0
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));
+}
+
 constexpr bool epi_is_f16_tile(int epi) {
     return epi == VX_EPI_F16 || epi == VX_EPI_F16_GELU || epi == VX_EPI_F16_RELU || epi == VX_EPI_F16_ADD ||
-           epi == VX_EPI_QKV || epi == VX_EPI_PIXSHUF || epi == VX_EPI_HEAD_OUT || epi == VX_EPI_LRELU_AGC;
+           epi == VX_EPI_QKV || epi == VX_EPI_PIXSHUF || epi == VX_EPI_HEAD_OUT || epi == VX_EPI_LRELU_AGC ||
+           epi == VX_EPI_SILU;
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int EPI, bool CONV>
@@ -140,6 +145,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
     // lane l lands at row + l/8, physical chunk l%8, so it must fetch logical chunk (l%8) ^ swz(row)
     const int l_row = lane >> 3, l_pos = lane & 7;
     long a_off[A_INSTR];   // plain: element offset of the row start; conv: image base
+    const long a_pix = CONV ? (p.conv_pix > 0 ? p.conv_pix : p.conv_Cin) : 0; // conv: elements between input pixels
     int a_iy0[A_INSTR], a_ix0[A_INSTR], a_chunk[A_INSTR];
 #pragma unroll
     for (int i = 0; i < A_INSTR; ++i) {
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                 int ohw = p.conv_OH * p.conv_OW;
                 int b = m / ohw, rm = m - b * ohw;
                 int oy = rm / p.conv_OW, ox = rm - oy * p.conv_OW;
-                a_off[i] = (long)b * p.conv_H * p.conv_W * p.conv_Cin;
+                a_off[i] = (long)b * p.conv_H * p.conv_W * a_pix;
                 a_iy0[i] = oy * p.conv_stride - p.conv_pad;
                 a_ix0[i] = ox * p.conv_stride - p.conv_pad;
             } else {
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                     int ky = tap / p.conv_kw, kx = tap - ky * p.conv_kw;
                     int iy = a_iy0[i] + ky, ix = a_ix0[i] + kx;
                     if ((unsigned)iy < (unsigned)p.conv_H && (unsigned)ix < (unsigned)p.conv_W)
-                        src = Ag + a_off[i] + ((long)iy * p.conv_W + ix) * p.conv_Cin + c8 * 8;
+                        src = Ag + a_off[i] + ((long)iy * p.conv_W + ix) * a_pix + c8 * 8;
                 }
             } else {
                 src = Ag + a_off[i] + k0 + a_chunk[i] * 8;
@@ -391,6 +397,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                         if constexpr (EPI == VX_EPI_F16_RELU || EPI == VX_EPI_HEAD_OUT) v[j] = fmaxf(v[j], 0.0f);
                         if constexpr (EPI == VX_EPI_F16_ADD) { if (p.relu) v[j] = fmaxf(v[j], 0.0f); }
                         if constexpr (EPI == VX_EPI_QKV) v[j] *= out_scale;
+                        if constexpr (EPI == VX_EPI_SILU) v[j] = silu(v[j]);
                     }
                     if constexpr (EPI == VX_EPI_LRELU_AGC) { // MI-GAN: (+ noise plane of the pixel) -> lrelu 0.2 -> x sqrt2 -> clamp 256
                         const int m = m0 + wr * WM + ps * WPP + mp * 32 + r;
@@ -428,10 +435,12 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
                 part += __shfl_xor(part, 1, 64);
                 part += __shfl_xor(part, 2, 64);
                 if (j == 0) reinterpret_cast<float*>(p.out)[m] = fmaxf(part + p.head_bias, 0.0f) * p.head_scale;
-            } else if constexpr (EPI == VX_EPI_F16 || EPI == VX_EPI_F16_GELU || EPI == VX_EPI_F16_RELU || EPI == VX_EPI_LRELU_AGC) {
-                if constexpr (EPI == VX_EPI_LRELU_AGC) { // + a feature map after the activation (MI-GAN synthesis b4, migan.cpp:119-120)
+            } else if constexpr (EPI == VX_EPI_F16 || EPI == VX_EPI_F16_GELU || EPI == VX_EPI_F16_RELU || EPI == VX_EPI_LRELU_AGC || EPI == VX_EPI_SILU) {
+                if constexpr (EPI == VX_EPI_LRELU_AGC || EPI == VX_EPI_SILU) {
+                    // + a feature map after the activation (MI-GAN synthesis b4, migan.cpp:119-120; the RepBottleneck shortcut)
                     if (p.res1) {
-                        const f16x8 a = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res1) + (long)m * p.ldo + n);
+                        const long ldr = (EPI == VX_EPI_SILU && p.ld_res1 > 0) ? p.ld_res1 : p.ldo;
+                        const f16x8 a = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res1) + (long)m * ldr + n);
 #pragma unroll
                         for (int q = 0; q < 8; ++q) v[q] = (f16)((float)v[q] + (float)a[q]);
                     }
@@ -544,6 +553,7 @@ int dispatch_epi(const vx_gemm_args& a, hipStream_t s) {
         case VX_EPI_F16_RELU: return dispatch_tile<VX_EPI_F16_RELU, CONV>(a, s);
         case VX_EPI_F16_ADD: return dispatch_tile<VX_EPI_F16_ADD, CONV>(a, s);
         case VX_EPI_HEAD_OUT: return launch<128, 32, 32, 32, 1, VX_EPI_HEAD_OUT, CONV>(a, s); // N == 32 only
+        case VX_EPI_SILU: return dispatch_tile<VX_EPI_SILU, CONV>(a, s);
         default: break;
     }
     if constexpr (!CONV) {
@@ -649,11 +659,15 @@ extern "C" int vx_gemm_f16_raw(const vx_gemm_args* args, void* stream) {
     }
     if (a.epi == VX_EPI_LRELU_AGC) VX_REQUIRE(!a.noise || a.noise_hw > 0, "vx_gemm_f16: lrelu_agc noise plane needs noise_hw > 0");
     if (a.epi == VX_EPI_HEAD_OUT) VX_REQUIRE(a.N == 32 && a.lambda, "vx_gemm_f16: head epilogue needs N == 32 and conv3 weights");
+    if (a.ld_res1 != 0) VX_REQUIRE(a.epi == VX_EPI_SILU && a.ld_res1 % 8 == 0, "vx_gemm_f16: ld_res1=%ld needs the SiLU epilogue and a multiple of 8", (long)a.ld_res1);
     if (a.conv_kh > 0) {
         VX_REQUIRE(a.conv_Cin % 8 == 0, "vx_gemm_f16: conv Cin=%d must be a multiple of 8", a.conv_Cin);
+        VX_REQUIRE(a.conv_pix == 0 || (a.conv_pix % 8 == 0 && a.conv_pix >= a.conv_Cin), "vx_gemm_f16: conv pixel stride %ld must be a multiple of 8 and >= Cin=%d",
+                   (long)a.conv_pix, a.conv_Cin);
         VX_REQUIRE(a.K >= a.conv_kh * a.conv_kw * a.conv_Cin, "vx_gemm_f16: conv K too small");
         return dispatch_epi<true>(a, as_stream(stream));
     }
+    VX_REQUIRE(a.conv_pix == 0, "vx_gemm_f16: conv_pix is an implicit-conv field");
     VX_REQUIRE(a.lda % 8 == 0, "vx_gemm_f16: lda=%ld must be a multiple of 8", (long)a.lda);
     return dispatch_epi<false>(a, as_stream(stream));
 }

@@ -53,6 +53,8 @@ void timing_add(std::vector<timing_entry>& rows, timing_entry const& t);
 
 // every model handle starts with its family (the C ABI's handles are untyped: c-api.cpp:193 any_model)
 enum model_family_id : int32_t { family_sam = 0, family_birefnet, family_depth_anything, family_migan, family_esrgan, family_count };
+// families outside the public visp_model_family range: the generic entry points (visp_model_compute, ..) refuse their handles
+constexpr int32_t family_yolov9t = 64;
 struct model_base {
     int32_t family;
     backend_device const* backend = nullptr;

@@ -795,3 +795,107 @@ def write_migan_gguf(path: str | Path, res: int = 512, ch_base: int = 32768, ch_
         w.add_tensor(name, t)
     w.write()
     return Path(path)
+
+
+# ---- YOLOv9t (reference src/visp/arch/yolov9t.cpp: yolov9t_backbone :507-630, detect_forward :770-800) ---------------------
+
+YOLO_REP_N = 3            # RepCSP depth of every RepNCSPELAN4
+YOLO_HEAD_CH = (64, 96, 128)
+
+
+def yolov9t_convs(nc: int = 80) -> list[tuple[str, int, int, int, str]]:
+    """Every conv of the tiny topology as (prefix, cin, cout, k, kind): kind "conv" = Conv (conv + BatchNorm + SiLU; tensors
+    <prefix>.conv.*, <prefix>.bn.*), "plain" = the detect head's 1x1 conv_2d with bias (<prefix>.weight / .bias)."""
+    out: list[tuple[str, int, int, int, str]] = []
+
+    def conv(p, cin, cout, k):
+        out.append((p, cin, cout, k, "conv"))
+
+    def repcsp(p, c1, c2):
+        c_ = c2 // 2
+        conv(f"{p}.cv1", c1, c_, 1)
+        conv(f"{p}.cv2", c1, c_, 1)
+        for j in range(YOLO_REP_N):
+            conv(f"{p}.m.{j}.cv1.conv1", c_, c_, 3)  # RepConv: 3x3 + 1x1 branches
+            conv(f"{p}.m.{j}.cv1.conv2", c_, c_, 1)
+            conv(f"{p}.m.{j}.cv2", c_, c_, 3)
+        conv(f"{p}.cv3", 2 * c_, c2, 1)
+
+    def elan4(p, c1, c2, c3, c4):
+        conv(f"{p}.cv1", c1, c3, 1)
+        repcsp(f"{p}.cv2.0", c3 // 2, c4)
+        conv(f"{p}.cv2.1", c4, c4, 3)
+        repcsp(f"{p}.cv3.0", c4, c4)
+        conv(f"{p}.cv3.1", c4, c4, 3)
+        conv(f"{p}.cv4", c3 + 2 * c4, c2, 1)
+
+    conv("model.0", 3, 16, 3)
+    conv("model.1", 16, 32, 3)
+    conv("model.2.cv1", 32, 32, 1)
+    conv("model.2.cv2", 16, 16, 3)
+    conv("model.2.cv3", 16, 16, 3)
+    conv("model.2.cv4", 64, 32, 1)
+    conv("model.3.cv1", 32, 64, 3)
+    elan4("model.4", 64, 64, 64, 32)
+    conv("model.5.cv1", 64, 96, 3)
+    elan4("model.6", 96, 96, 96, 48)
+    conv("model.7.cv1", 96, 128, 3)
+    elan4("model.8", 128, 128, 128, 64)
+    conv("model.9.cv1", 128, 64, 1)
+    conv("model.9.cv5", 256, 128, 1)
+    elan4("model.12", 224, 96, 96, 48)
+    elan4("model.15", 160, 64, 64, 32)
+    conv("model.16.cv1", 64, 48, 3)
+    elan4("model.18", 144, 96, 96, 48)
+    conv("model.19.cv1", 96, 64, 3)
+    elan4("model.21", 192, 128, 128, 64)
+    c3 = max(YOLO_HEAD_CH[0], min(nc, 100))
+    for lv, ch in enumerate(YOLO_HEAD_CH):
+        conv(f"detect.cv2.{lv}.0", ch, 64, 3)
+        conv(f"detect.cv2.{lv}.1", 64, 64, 3)
+        out.append((f"detect.cv2.{lv}.2", 64, 64, 1, "plain"))
+        conv(f"detect.cv3.{lv}.0", ch, c3, 3)
+        conv(f"detect.cv3.{lv}.1", c3, c3, 3)
+        out.append((f"detect.cv3.{lv}.2", c3, nc, 1, "plain"))
+    return out
+
+
+def yolov9t_state_dict(seed: int = 0, nc: int = 80, fused: bool = True, class_bias: float = -4.3, gain: float = 1.45, head_gain: float = 10.0,
+                       head_prefix: str = "detect.", bn_eps: float = 1e-3) -> dict[str, np.ndarray]:
+    """Seeded float32 weights for the tiny channel table, fan-in scaled so activations stay O(1) through the depth.
+    fused=False: the checkpoint as ultralytics stores it (conv without bias + BatchNorm with running statistics, head under
+    `head_prefix`, e.g. "model.22.", plus the fixed dfl.conv.weight); fused=True: BatchNorm folded with bn_eps (convert.fold_yolov9t).
+    class_bias: bias of the class logits, which sets how many (anchor, class) pairs pass the 0.25 threshold."""
+    rng = np.random.default_rng(seed)
+    sd: dict[str, np.ndarray] = {}
+    for p, cin, cout, k, kind in yolov9t_convs(nc):
+        g = gain * (0.35 if ".m." in p and p.endswith(".cv2") else 1.0)  # RepBottleneck branch: keeps the residual chain O(1)
+        if ".conv1" in p or ".conv2" in p:
+            g *= 0.7  # the two RepConv branches are summed
+        w = (rng.standard_normal((cout, cin, k, k)) * g / np.sqrt(cin * k * k)).astype(np.float32)
+        if kind == "plain":
+            name = p if not p.startswith("detect.") else head_prefix + p[len("detect."):]
+            is_cls = ".cv3." in p
+            sd[f"{name}.weight"] = w * head_gain / gain  # the body settles at activations of about 0.1: the head scales them up
+            b = rng.standard_normal(cout) * (0.2 if is_cls else 0.3) + (class_bias if is_cls else 0.0)
+            sd[f"{name}.bias"] = b.astype(np.float32)
+            continue
+        name = p if not p.startswith("detect.") else head_prefix + p[len("detect."):]
+        sd[f"{name}.conv.weight"] = w
+        sd[f"{name}.bn.weight"] = rng.uniform(0.7, 1.3, cout).astype(np.float32)
+        sd[f"{name}.bn.bias"] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+        sd[f"{name}.bn.running_mean"] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+        sd[f"{name}.bn.running_var"] = rng.uniform(0.6, 1.4, cout).astype(np.float32)
+        sd[f"{name}.bn.num_batches_tracked"] = np.array(1000, np.int64)
+    sd[f"{head_prefix}dfl.conv.weight"] = np.arange(16, dtype=np.float32).reshape(1, 16, 1, 1)
+    if fused:
+        from .convert import fold_yolov9t
+        sd = fold_yolov9t(sd, bn_eps)
+    return sd
+
+
+def write_yolov9t_gguf(path: str | Path, seed: int = 0, sd: dict[str, np.ndarray] | None = None, **kw) -> Path:
+    """The folded state dict through convert.convert_yolov9t (f16 OIHW conv kernels listed in yolov9t.conv2d_weights, f32 biases)."""
+    from .convert import convert_yolov9t
+    sd = sd if sd is not None else yolov9t_state_dict(seed, **kw)
+    return convert_yolov9t(sd, path)

@@ -478,3 +478,121 @@ class Migan(Model):
         out = np.empty(x.shape[:3] + (3,), np.float32)
         check(self._api.visp_migan_generate_host(self._handle, x.ctypes.data, x.shape[0], out.ctypes.data))
         return out
+
+
+# ---- YOLOv9t (reference src/visp/arch/yolov9t.cpp; loaded through visp_yolov9t_load) --------------
+
+DETECTION_DTYPE = np.dtype([("x1", np.float32), ("y1", np.float32), ("x2", np.float32), ("y2", np.float32), ("confidence", np.float32),
+                            ("class_id", np.int32), ("class_confidence", np.float32)])  # == visp_detection (detected_obj)
+assert DETECTION_DTYPE.itemsize == ctypes.sizeof(lib.Detection)
+
+
+def _nms_params(conf=None, iou=None, max_det=None, max_nms=None, max_wh=None) -> lib.Yolov9tNmsParams:
+    """visp_yolov9t_nms_defaults (conf 0.25, iou 0.45, max_det 300, max_nms 30000, max_wh 640) with the given fields replaced."""
+    p = lib.Yolov9tNmsParams()
+    get_lib().visp_yolov9t_nms_defaults(byref(p))
+    for k, v in dict(conf=conf, iou=iou, max_det=max_det, max_nms=max_nms, max_wh=max_wh).items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def _image_view(image: np.ndarray):
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    h, w, c = img.shape
+    if c not in (3, 4):
+        raise ValueError(f"expected an rgb or rgba u8 image, got {c} channels")
+    fmt = ImageFormat.rgb_u8 if c == 3 else ImageFormat.rgba_u8
+    return img, lib.ImageView(w, h, w * c, fmt.value, img.ctypes.data)
+
+
+def yolov9t_letterbox(image: np.ndarray, size: int = 640):
+    """letterbox (yolov9t.cpp:1028-1083) on the host: rgb / rgba u8 [h, w, 3|4] -> (rgb u8 [size, size, 3], gain, pad_w, pad_h)."""
+    img, view = _image_view(image)
+    out = np.empty((size, size, 3), np.uint8)
+    gain, pw, ph = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+    check(get_lib().visp_yolov9t_letterbox(byref(view), size, out.ctypes.data, byref(gain), byref(pw), byref(ph)))
+    return out, gain.value, pw.value, ph.value
+
+
+def yolov9t_nms(boxes: np.ndarray, scores: np.ndarray, **nms) -> np.ndarray:
+    """non_max_suppression (yolov9t.cpp:1145-1253) on the host: boxes f32 [A, 4], scores f32 [A, nc] -> DETECTION_DTYPE [n]."""
+    b = np.ascontiguousarray(boxes, np.float32)
+    s = np.ascontiguousarray(scores, np.float32)
+    a, nc = s.shape
+    assert b.shape == (a, 4), (b.shape, s.shape)
+    p = _nms_params(**nms)
+    out, n = np.empty(p.max_det, DETECTION_DTYPE), c_int32()
+    check(get_lib().visp_yolov9t_nms(b.ctypes.data, s.ctypes.data, a, nc, byref(p), out.ctypes.data, p.max_det, byref(n)))
+    return out[: n.value].copy()
+
+
+def yolov9t_scale_boxes(dets: np.ndarray, width: int, height: int, gain: float, pad_w: float, pad_h: float) -> np.ndarray:
+    """scale_boxes (yolov9t.cpp:1255-1281) on the host: DETECTION_DTYPE boxes in letterbox pixels -> a copy in image pixels."""
+    out = np.ascontiguousarray(dets, DETECTION_DTYPE).copy()
+    check(get_lib().visp_yolov9t_scale_boxes(out.ctypes.data, out.size, width, height, gain, pad_w, pad_h))
+    return out
+
+
+class Yolov9t(Model):
+    """YOLOv9t object detection (reference yolov9t.cpp + inference_yolov9t.cpp:300-405). Loaded through visp_yolov9t_load: the
+    reference has no model_family for it, so visp_model_load refuses the file."""
+
+    @classmethod
+    def load(cls, path, device: Device):
+        api = get_lib()
+        handle = c_void_p()
+        check(api.visp_yolov9t_load(lib.path_to_char_p(path), device._handle, byref(handle)))
+        return cls(api, handle, Arch.unknown, device)
+
+    def _family_fn(self, name: str):
+        return getattr(self._api, "visp_yolov9t_" + name)
+
+    @property
+    def info(self) -> dict:
+        i = lib.Yolov9tInfo()
+        check(self._api.visp_yolov9t_get_info(self._handle, byref(i)))
+        return dict(input_size=i.input_size, num_classes=i.num_classes, reg_max=i.reg_max, n_anchors=i.n_anchors)
+
+    def detect(self, image: np.ndarray, **nms) -> np.ndarray:
+        """rgb / rgba u8 [h, w, 3|4] of any extent -> DETECTION_DTYPE [n] in the image's pixels, in score order."""
+        img, view = _image_view(image)
+        p = _nms_params(**nms)
+        out, n = np.empty(p.max_det, DETECTION_DTYPE), c_int32()
+        check(self._api.visp_yolov9t_detect(self._handle, byref(view), byref(p), out.ctypes.data, p.max_det, byref(n)))
+        return out[: min(n.value, p.max_det)].copy()
+
+    def detect_batch(self, images: np.ndarray, **nms) -> list[np.ndarray]:
+        """letterboxed u8 [B, S, S, 3|4] -> one DETECTION_DTYPE array per image, in input pixels."""
+        imgs = np.ascontiguousarray(images, dtype=np.uint8)
+        b, h, w, c = imgs.shape
+        assert h == w, imgs.shape
+        p = _nms_params(**nms)
+        out, counts = np.empty((b, p.max_det), DETECTION_DTYPE), np.zeros(b, np.int32)
+        check(self._api.visp_yolov9t_detect_batch_host(self._handle, imgs.ctypes.data, c, b, h, byref(p), out.ctypes.data,
+                                                       counts.ctypes.data_as(ctypes.POINTER(c_int32))))
+        return [out[i, : counts[i]].copy() for i in range(b)]
+
+    def detect_batch_device(self, img_dev: int, channels: int, batch: int, size: int, stream: int | None = None, **nms) -> list[np.ndarray]:
+        p = _nms_params(**nms)
+        out, counts = np.empty((batch, p.max_det), DETECTION_DTYPE), np.zeros(batch, np.int32)
+        check(self._api.visp_yolov9t_detect_batch_device(self._handle, img_dev, channels, batch, size, byref(p), out.ctypes.data,
+                                                         counts.ctypes.data_as(ctypes.POINTER(c_int32)), stream))
+        return [out[i, : counts[i]].copy() for i in range(batch)]
+
+    @property
+    def last_split(self) -> dict:
+        """The last batch call in ms: the launch list on the device (HIP events), the candidate readback, the host NMS."""
+        out = (ctypes.c_float * 3)()
+        check(self._api.visp_yolov9t_last_split(self._handle, out))
+        return dict(device_ms=out[0], readback_ms=out[1], nms_ms=out[2])
+
+    def forward(self, x: np.ndarray):
+        """f32 rgb [n, S, S, 3] in [0, 1] -> (boxes f32 [n, A, 4] xyxy in input pixels, scores f32 [n, A, nc])."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n, s = x.shape[0], x.shape[1]
+        a = (s // 8) ** 2 + (s // 16) ** 2 + (s // 32) ** 2
+        boxes = np.empty((n, a, 4), np.float32)
+        scores = np.empty((n, a, self.info["num_classes"]), np.float32)
+        check(self._api.visp_yolov9t_forward_host(self._handle, x.ctypes.data, n, s, boxes.ctypes.data, scores.ctypes.data))
+        return boxes, scores
