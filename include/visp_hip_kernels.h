@@ -225,7 +225,7 @@ VX_API int vx_mbconv_pack_w3(const void* w3_rows_host, void* packed_host);
 VX_API int vx_mbconv_dw_pw_f16(const void* h, const void* w2, const float* b2, const void* w3, const float* b3, const void* x, void* y, int B, int H,
                                int W, int C, int Cout, void* stream);
 /* LayerNorm of f16 rows (nn.cpp:14-19). ws > 0: output rows in window order of a res x res map (window_partition,
- * mobile-sam.cpp:25-46; padded positions = norm of zero = bias). out_f32: f32 output. C <= 512. */
+ * mobile-sam.cpp:25-46; padded positions = norm of zero = bias). out_f32: f32 output. C <= 1024 (above 512: one wave per row). */
 VX_API int vx_layernorm_f16(const void* x, const float* w, const float* b, void* y, int64_t rows_out, int C, float eps, int res, int ws,
                             int out_f32, void* stream);
 /* window attention with relative position bias, head_dim 32, on MFMA (mobile-sam.cpp:112-131; kernels_winattn.hip): qkv f16
@@ -382,6 +382,13 @@ VX_API int vx_headconv_supported(int cin, int cout, int H, int W, int hs, int ws
 VX_API void vx_headconv_set_stamps(void* stamps);
 VX_API int vx_headconv_bil_f16(const void* x, const void* wfrag, const float* bias, const float* w3, float b3, float scale, float* out, int B, int H, int W,
                                int hs, int ws, void* stream);
+/* the same tail for x f16 [B, hs, ws, cin], cin = 64 or 128 (the Base / Large heads), in 32-channel K slices: `wfrag` =
+ * vx_headconv_wide_pack (host code) of the rows [32][Kp], k = (ky, kx, c); vx_headconv_wide_frag_bytes(cin) bytes */
+VX_API int vx_headconv_wide_supported(int cin, int cout, int H, int W, int hs, int ws); /* cin 64 / 128, cout 32, the same resize bound */
+VX_API size_t vx_headconv_wide_frag_bytes(int cin);
+VX_API int vx_headconv_wide_pack(const void* w_rows, int cin, int Kp, void* out_frag);
+VX_API int vx_headconv_wide_bil_f16(const void* x, int cin, const void* wfrag, const float* bias, const float* w3, float b3, float scale, float* out, int B,
+                                    int H, int W, int hs, int ws, void* stream);
 
 /* ---- post-processing: per-image min/max then (v-min)/(max-min) (image.cpp:537-576);
  * minmax: f32 [B,2] scratch ------------------------------------------------------------------ */

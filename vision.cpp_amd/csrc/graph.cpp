@@ -780,11 +780,12 @@ struct lowering {
     bool head_tail(int t) {
         graph_node const& up = g.nodes[t];
         graph_node const& x = g.nodes[up.src[0]];
-        if ((up.ip[2] & 255) != 1 || !(up.ip[2] & 256) || x.ne[0] != 32) return false;
+        const int cin = (int)x.ne[0];
+        if ((up.ip[2] & 255) != 1 || !(up.ip[2] & 256) || (cin != 32 && cin != 64 && cin != 128)) return false;
         const int c2 = sole_consumer(t);
         if (c2 < 0 || g.nodes[c2].op != gop_conv_2d || g.nodes[c2].src[0] != t || g.nodes[c2].n_src != 3) return false;
         graph_node const& w2 = g.nodes[g.nodes[c2].src[1]];
-        if (w2.ne[0] != 32 || w2.ne[1] != 3 || w2.ne[2] != 3 || w2.ne[3] != 32 || g.nodes[c2].ip[0] != 1 || g.nodes[c2].ip[1] != 1) return false;
+        if (w2.ne[0] != cin || w2.ne[1] != 3 || w2.ne[2] != 3 || w2.ne[3] != 32 || g.nodes[c2].ip[0] != 1 || g.nodes[c2].ip[1] != 1) return false;
         const int r1 = sole_consumer(c2);
         if (r1 < 0 || g.nodes[r1].op != gop_relu) return false;
         const int c3 = sole_consumer(r1);
@@ -792,18 +793,22 @@ struct lowering {
         const int r2 = sole_consumer(c3);
         if (r2 < 0 || g.nodes[r2].op != gop_relu) return false; // the kernel's last ReLU is not optional
         const int H = (int)up.ne[2], W = (int)up.ne[1], hs = (int)x.ne[2], ws = (int)x.ne[1], B = (int)x.ne[3];
-        if (!vx_headconv_supported(32, 32, H, W, hs, ws) || (size_t)B * hs * ws * 64 >= ((size_t)1 << 31)) return false;
+        if (cin == 32 ? !vx_headconv_supported(32, 32, H, W, hs, ws) || (size_t)B * hs * ws * 64 >= ((size_t)1 << 31)
+                      : !vx_headconv_wide_supported(cin, 32, H, W, hs, ws) || (size_t)B * hs * ws * cin >= ((size_t)1 << 32))
+            return false;
         int last = r2;
         float scale = 1.0f;
         const int sc = sole_consumer(r2);
         if (sc >= 0 && g.nodes[sc].op == gop_scale) { scale = g.nodes[sc].fp[0]; last = sc; }
-        // the 3x3 kernel as the head kernel's register fragments
+        // the 3x3 kernel as the head kernel's MFMA fragments (Cin 64 / 128: one 32-channel slice after the other)
         const int wt = g.nodes[c2].src[1];
         void* frag = cached(wt, 5, [&](bool st) {
-            std::vector<uint16_t> rows((size_t)32 * 320, 0), out(vx_headconv_frag_bytes() / 2);
+            const int K = 9 * cin, Kp = cin == 32 ? 320 : K;
+            std::vector<uint16_t> rows((size_t)32 * Kp, 0), out((cin == 32 ? vx_headconv_frag_bytes() : vx_headconv_wide_frag_bytes(cin)) / 2);
             for (int r = 0; r < 32; ++r)
-                for (int k = 0; k < 288; ++k) rows[(size_t)r * 320 + k] = f32_to_f16(w2.values()[(size_t)r * 288 + k]);
-            VX(vx_headconv_pack(rows.data(), 320, out.data()));
+                for (int k = 0; k < K; ++k) rows[(size_t)r * Kp + k] = f32_to_f16(w2.values()[(size_t)r * K + k]);
+            if (cin == 32) VX(vx_headconv_pack(rows.data(), Kp, out.data()));
+            else VX(vx_headconv_wide_pack(rows.data(), cin, Kp, out.data()));
             return upload(out.data(), out.size() * 2, st);
         });
         const float* bias2 = const_f32(g.nodes[c2].src[2]);
@@ -823,10 +828,13 @@ struct lowering {
         const int obuf = n.buffer;
         auto xp = ptr(xbuf), op = ptr(obuf);
         char d[160];
-        snprintf(d, sizeof d, "head_tail[resize %dx%d -> %dx%d, conv3x3 32->32, relu, conv1x1 -> 1, relu%s] B=%d <- %s", ws, hs, W, H, scale != 1.0f ? ", scale" : "", B,
+        snprintf(d, sizeof d, "head_tail[resize %dx%d -> %dx%d, conv3x3 %d->32, relu, conv1x1 -> 1, relu%s] B=%d <- %s", ws, hs, W, H, cin, scale != 1.0f ? ", scale" : "", B,
                  g.nodes[wt].name.c_str());
-        emit(d, {xbuf}, {obuf}, [=](void* st) { VX(vx_headconv_bil_f16(xp(), frag, bias2, w3, b3, scale, reinterpret_cast<float*>(op()), B, H, W, hs, ws, st)); });
-        tag("head_conv2+3", 2.0 * B * H * W * 32.0 * (288 + 1), (double)B * ((double)hs * ws * 64 + (double)H * W * 4));
+        if (cin == 32)
+            emit(d, {xbuf}, {obuf}, [=](void* st) { VX(vx_headconv_bil_f16(xp(), frag, bias2, w3, b3, scale, reinterpret_cast<float*>(op()), B, H, W, hs, ws, st)); });
+        else
+            emit(d, {xbuf}, {obuf}, [=](void* st) { VX(vx_headconv_wide_bil_f16(xp(), cin, frag, bias2, w3, b3, scale, reinterpret_cast<float*>(op()), B, H, W, hs, ws, st)); });
+        tag("head_conv2+3", 2.0 * B * H * W * 32.0 * (9.0 * cin + 1), (double)B * ((double)hs * ws * cin * 2 + (double)H * W * 4));
         return true;
     }
 
@@ -2062,7 +2070,7 @@ struct lowering {
                 case gop_layer_norm: {
                     const int xbuf = buf_of(n.src[0]);
                     const int C = (int)n.ne[0];
-                    if (C % 8 || C > 512) throw except("layer_norm: %d channels (a multiple of 8, at most 512)", C);
+                    if (C % 8 || C > 1024) throw except("layer_norm: %d channels (a multiple of 8, at most 1024)", C);
                     float *w = const_f32(n.src[1]), *b = const_f32(n.src[2]);
                     materialise(t);
                     const int obuf = n.buffer;

@@ -313,6 +313,249 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+// ---- the same tail for Cin = 64 / 128 (the Base / Large heads: head.conv1 writes fusion_hidden / 2 channels, conv2 reduces them to 32).
+// The 32-channel design does not scale: its register-resident kernel would take 144 / 288 VGPRs per lane and its two source patches
+// plus halo 113 / 157 KB of LDS. This kernel walks the reduction in K SLICES of 32 channels instead, each slice being exactly the
+// 32-channel problem above: the slice's source patch is staged in LDS (12 x 21 pixels x 64 bytes), interpolated into the same swizzled
+// 18 x 34 halo, and reduced by the same 72 MFMAs per wave with the slice's A fragments (72 VGPRs, read from global per slice: 18 KB that
+// every block reads, so they stay in L2) into accumulators that live across the slices. The next slice's patch is fetched after this
+// slice's MFMAs (held in registers under them it pushed the kernel 16 VGPRs past 256 into scratch), so its latency is covered by the
+// other block on the CU, not by this one; a slice costs two barriers. LDS is 56 KB (halo + one patch): with the
+// accumulators, the fragments and the interpolation pipeline the kernel needs about as many registers as the 32-channel one, so TWO
+// blocks share a CU and one block's interpolation phase runs under the other's matrix phase. Not persistent: one 16 x 32 tile per block
+// (a tile reads Cin / 32 patches, so a persistent loop would only overlap the first one). The interpolation arithmetic and the
+// epilogue are the 32-channel kernel's, instruction for instruction.
+constexpr int W_SRC_BYTES = PR * PC * PIXB + PIXB;
+constexpr int W_SMEM_BYTES = HALO_BYTES + W_SRC_BYTES + TAB_BYTES + 256; // 56.1 KB
+
+template <int NS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void headconv_wide_kernel(
+    const f16* __restrict__ x, const f16* __restrict__ wfrag, const float* __restrict__ bias, const float* __restrict__ w3, float b3, float out_scale,
+    float* __restrict__ out, int B, int H, int W, int Hs, int Ws, int tiles_x, int tiles_y) {
+    constexpr int CIN = NS * 32;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const halo = smem;
+    unsigned char* const src = smem + HALO_BYTES;
+    uint2* const tab_y = reinterpret_cast<uint2*>(smem + HALO_BYTES + W_SRC_BYTES);
+    uint2* const tab_x = tab_y + HH;
+    float* const w3_lds = reinterpret_cast<float*>(smem + HALO_BYTES + W_SRC_BYTES + TAB_BYTES);
+    float* const bias_lds = w3_lds + 32;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 31, h = lane >> 5;
+
+    // XCD-aware tile order as in the 32-channel kernel: blocks b, b + 8, ... share an XCD and walk a contiguous run of tiles
+    const int n_tiles = tiles_x * tiles_y * B;
+    int t;
+    {
+        const int nwg = gridDim.x, bk = blockIdx.x;
+        const int q = nwg >> 3, rem = nwg & 7, xcd = bk & 7;
+        t = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bk >> 3);
+    }
+    if (t >= n_tiles) return; // (grid == n_tiles: never taken)
+    const int per_image = tiles_x * tiles_y;
+    const int pb = t / per_image, tk = t - pb * per_image, ty0 = tk / tiles_x;
+    const int y0 = ty0 * TH, x0 = (tk - ty0 * tiles_x) * TW;
+
+    const float sfy = (H > 1 && Hs > 1) ? (float)(H - 1) / (float)(Hs - 1) : (float)H / (float)Hs;
+    const float sfx = (W > 1 && Ws > 1) ? (float)(W - 1) / (float)(Ws - 1) : (float)W / (float)Ws;
+    auto src_index = [](int o, float sf, int n_src, float& f) {
+        const float sc = (float)o / sf;
+        int i0 = (int)floorf(sc);
+        i0 = max(0, min(i0, n_src - 1));
+        f = fminf(fmaxf(sc - (float)i0, 0.0f), 1.0f);
+        return i0;
+    };
+    int py0, px0;
+    {
+        float dummy;
+        py0 = src_index(max(y0 - 1, 0), sfy, Hs, dummy);
+        px0 = src_index(max(x0 - 1, 0), sfx, Ws, dummy);
+    }
+
+    // ---- once per block: conv3's weights and conv2's bias in accumulator order, the halo's source tables, the zero pixel
+    if (tid < 32) {
+        const int c = (tid & 3) + 8 * ((tid & 15) >> 2) + 4 * (tid >> 4);
+        w3_lds[tid] = w3[c];
+        bias_lds[tid] = bias[c];
+    }
+    if (tid < HH + HW) {
+        const bool isx = tid >= HH;
+        const int o = (isx ? x0 + (tid - HH) : y0 + tid) - 1, n_out = isx ? W : H, n_src = isx ? Ws : Hs;
+        uint2 e = {0x80000000u, 0u};
+        if (o >= 0 && o < n_out) {
+            float f;
+            const int i0 = src_index(o, isx ? sfx : sfy, n_src, f);
+            const unsigned short fh = __builtin_bit_cast(unsigned short, (f16)f);
+            e.x = (unsigned)(i0 - (isx ? px0 : py0)) | (i0 + 1 < n_src ? 0x8000u : 0u);
+            e.y = (unsigned)fh | (unsigned)fh << 16;
+        }
+        (isx ? tab_x[tid - HH] : tab_y[tid]) = e;
+    }
+    if (tid < 4) *reinterpret_cast<uint4*>(src + ZERO_OFF + tid * 16) = uint4{0, 0, 0, 0};
+
+    // source patch items (pixel, 8-channel chunk) of this thread: the global address of slice 0 (rows / columns past the map repeat
+    // its last one, which is never weighted) and the LDS slot
+    constexpr int N_ITEMS = PR * PC * 4, N_IT = (N_ITEMS + 255) / 256;
+    unsigned pg[N_IT]; // element offsets (the source tensor is below 2^32 elements: checked by the host)
+#pragma unroll
+    for (int it = 0; it < N_IT; ++it) {
+        const int i = min(tid + it * 256, N_ITEMS - 1);
+        const int pix = i >> 2, chunk = i & 3, pr = pix / PC, pc = pix - pr * PC;
+        const int sy = min(py0 + pr, Hs - 1), sx = min(px0 + pc, Ws - 1);
+        pg[it] = (((unsigned)pb * Hs + sy) * Ws + sx) * CIN + chunk * 8;
+    }
+    f16x8 pr_regs[N_IT];
+    auto load_patch = [&](int s) {
+#pragma unroll
+        for (int it = 0; it < N_IT; ++it) pr_regs[it] = *reinterpret_cast<const f16x8*>(x + (pg[it] + s * 32));
+    };
+    auto store_patch = [&]() {
+#pragma unroll
+        for (int it = 0; it < N_IT; ++it)
+            if (tid + it * 256 < N_ITEMS) *reinterpret_cast<f16x8*>(src + (tid + it * 256) * 16) = pr_regs[it];
+    };
+    load_patch(0);
+    store_patch();
+
+    constexpr int I_ITEMS = HH * HW * 4, I_IT = (I_ITEMS + 255) / 256;
+    unsigned ipack[I_IT];
+#pragma unroll
+    for (int it = 0; it < I_IT; ++it) {
+        int i = tid + it * 256;
+        if (i >= I_ITEMS) i -= 256;
+        const int pix = i >> 2, chunk = i & 3, hy = pix / HW, hx = pix - hy * HW;
+        ipack[it] = (unsigned)hy | (unsigned)hx << 8 | (unsigned)chunk << 16;
+    }
+    unsigned boff[3][2];
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int px = n + dx, chunk = ks * 2 + h;
+            boff[dx][ks] = (unsigned)((4 * wave * HW + px) * PIXB + ((chunk ^ ((px >> 1) & 3)) * 16));
+        }
+    __syncthreads();
+
+    f32x16 acc[4]; // conv2's sums over all slices, starting at the bias (one tile per block: the moves happen once)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(bias_lds + 16 * h + 4 * g);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j][4 * g + q] = v[q];
+    }
+
+    for (int s = 0; s < NS; ++s) {
+        // ---- interpolate this slice's halo from the patch in LDS (the 32-channel kernel's pipeline: reads one batch ahead)
+        {
+            uint2 ty[I_IT], tx[I_IT];
+#pragma unroll
+            for (int k = 0; k < I_IT; ++k) {
+                ty[k] = tab_y[ipack[k] & 0xff];
+                tx[k] = tab_x[(ipack[k] >> 8) & 0xff];
+            }
+            auto lerp2 = [](h2 v, h2 w, h2 f) { return f * w + (v - f * v); };
+            f16x8 rd[2][2][4];
+            auto load_batch = [&](int bt, f16x8 (&r)[2][4]) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int k = 2 * bt + u;
+                    const unsigned chunk16 = ((ipack[k] >> 16) & 3) * 16;
+                    const bool outside = (int)(ty[k].x | tx[k].x) < 0;
+                    const unsigned sy = ty[k].x & 0x7fffu, sx = tx[k].x & 0x7fffu;
+                    const unsigned o00 = (outside ? (unsigned)ZERO_OFF : (sy * PC + sx) * PIXB) + chunk16;
+                    const unsigned o01 = o00 + (outside ? 0u : ((tx[k].x >> 15) & 1u) * PIXB);
+                    const unsigned dy = outside ? 0u : ((ty[k].x >> 15) & 1u) * (PC * PIXB);
+                    r[u][0] = *reinterpret_cast<const f16x8*>(src + o00);
+                    r[u][1] = *reinterpret_cast<const f16x8*>(src + o01);
+                    r[u][2] = *reinterpret_cast<const f16x8*>(src + o00 + dy);
+                    r[u][3] = *reinterpret_cast<const f16x8*>(src + o01 + dy);
+                }
+            };
+            load_batch(0, rd[0]);
+#pragma unroll
+            for (int bt = 0; bt < I_IT / 2; ++bt) {
+                if (bt + 1 < I_IT / 2) load_batch(bt + 1, rd[(bt + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int k = 2 * bt + u;
+                    f16x8 const(&r)[4] = rd[bt & 1][u];
+                    const h2 fx = __builtin_bit_cast(h2, tx[k].y), fy = __builtin_bit_cast(h2, ty[k].y);
+                    f16x8 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const h2 aa = {r[0][2 * q], r[0][2 * q + 1]}, bb = {r[1][2 * q], r[1][2 * q + 1]}, cc = {r[2][2 * q], r[2][2 * q + 1]}, dd = {r[3][2 * q], r[3][2 * q + 1]};
+                        const h2 v = lerp2(lerp2(aa, bb, fx), lerp2(cc, dd, fx), fy);
+                        o[2 * q] = v[0];
+                        o[2 * q + 1] = v[1];
+                    }
+                    const unsigned pk = ipack[k], hy = pk & 0xff, hx = (pk >> 8) & 0xff, chunk = pk >> 16;
+                    *reinterpret_cast<f16x8*>(halo + (hy * HW + hx) * PIXB + ((chunk ^ ((hx >> 1) & 3)) * 16)) = o;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __syncthreads(); // the halo is complete; every wave is done reading the patch
+
+        // ---- the slice's A fragments, then conv2's partial product on the matrix pipe
+        f16x8 wf[18];
+#pragma unroll
+        for (int i = 0; i < 18; ++i) wf[i] = *reinterpret_cast<const f16x8*>(wfrag + (((size_t)s * 18 + i) * 64 + lane) * 8);
+        f16x8 bf[2][6];
+        auto load_row = [&](int hr, f16x8 (&r)[6]) {
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) r[dx * 2 + ks] = *reinterpret_cast<const f16x8*>(halo + boff[dx][ks] + hr * (HW * PIXB));
+        };
+        load_row(0, bf[0]);
+#pragma unroll
+        for (int hr = 0; hr < 6; ++hr) {
+            if (hr + 1 < 6) load_row(hr + 1, bf[(hr + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+                    for (int dy = 0; dy < 3; ++dy) {
+                        const int j = hr - dy;
+                        if (j >= 0 && j < 4) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[(dy * 3 + dx) * 2 + ks], bf[hr & 1][dx * 2 + ks], acc[j], 0, 0, 0);
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (s + 1 < NS) {
+            load_patch(s + 1);
+            store_patch(); // (every wave passed the barrier above: nobody reads the patch any more)
+            __syncthreads(); // the next patch is in LDS; every wave is done reading the halo
+        }
+    }
+
+    // ---- ReLU, conv3, ReLU, scale (the 32-channel kernel's epilogue)
+    const int ox = x0 + n;
+    float w3v[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w3_lds + 16 * h + 4 * g);
+        w3v[4 * g] = v[0]; w3v[4 * g + 1] = v[1]; w3v[4 * g + 2] = v[2]; w3v[4 * g + 3] = v[3];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) sum = fmaf(relu1(acc[j][e]), w3v[e], sum);
+        sum += other_half(sum);
+        const int oy = y0 + 4 * wave + j;
+        if (h == 0 && ox < W && oy < H) out[((size_t)pb * H + oy) * W + ox] = out_scale * fmaxf(sum + b3, 0.0f);
+    }
+}
+
 } // namespace
 
 // conv kernel rows [32][Kp] f16 with k = (ky, kx, c) (the GEMM family's operand) -> the A fragments above: [tap * 2 + ks][lane][8]
@@ -333,6 +576,42 @@ extern "C" int vx_headconv_supported(int cin, int cout, int H, int W, int hs, in
     const double sy = (double)(hs - 1) / (H - 1), sx = (double)(ws - 1) / (W - 1);
     // halo rows y0-1 .. y0+16 span 17 steps, columns 33: floor(first) .. floor(last) + 1 must fit the patch
     return (int)(17 * sy) + 3 <= PR && (int)(33 * sx) + 3 <= PC;
+}
+
+// conv kernel rows [32][Kp] f16 with k = (ky, kx, c), c < cin (64 or 128) -> the wide kernel's A fragments, one 32-channel slice after
+// the other: [slice][tap * 2 + ks][lane][8], lane (m = lane & 31 -> cout, h) holding W[m][tap][32 slice + 16 ks + 8 h .. + 7]
+extern "C" int vx_headconv_wide_pack(const void* w_rows, int cin, int Kp, void* out_frag) {
+    VX_REQUIRE(w_rows && out_frag && (cin == 64 || cin == 128) && Kp >= 9 * cin, "vx_headconv_wide_pack: cin 64 or 128, rows of at least 9 cin elements");
+    const uint16_t* w = static_cast<const uint16_t*>(w_rows);
+    uint16_t* o = static_cast<uint16_t*>(out_frag);
+    for (int s = 0; s < cin / 32; ++s)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int ks = 0; ks < 2; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int q = 0; q < 8; ++q)
+                        o[((((size_t)s * 9 + tap) * 2 + ks) * 64 + lane) * 8 + q] = w[(size_t)(lane & 31) * Kp + tap * cin + s * 32 + ks * 16 + 8 * (lane >> 5) + q];
+    return 1;
+}
+// the same source-patch bound as the 32-channel kernel: the K slices share its halo and patch geometry
+extern "C" int vx_headconv_wide_supported(int cin, int cout, int H, int W, int hs, int ws) {
+    return (cin == 64 || cin == 128) && vx_headconv_supported(32, cout, H, W, hs, ws);
+}
+extern "C" size_t vx_headconv_wide_frag_bytes(int cin) { return (size_t)(cin / 32) * 18 * 64 * 8 * 2; }
+
+extern "C" int vx_headconv_wide_bil_f16(const void* x, int cin, const void* wfrag, const float* bias, const float* w3, float b3, float scale, float* out, int B,
+                                        int H, int W, int hs, int ws, void* stream) {
+    VX_REQUIRE(x && wfrag && bias && w3 && out && B > 0, "vx_headconv_wide_bil_f16: null operand");
+    VX_REQUIRE(vx_headconv_wide_supported(cin, 32, H, W, hs, ws),
+               "vx_headconv_wide_bil_f16: cin %d (64 or 128), %dx%d from %dx%d (scale up to 0.58)", cin, W, H, ws, hs);
+    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
+    const long n_tiles = (long)tiles_x * tiles_y * B;
+    VX_REQUIRE((size_t)B * hs * ws * cin < ((size_t)1 << 32), "vx_headconv_wide_bil_f16: the source tensor must be below 2^32 elements (32-bit offsets)");
+    auto kernel = cin == 64 ? headconv_wide_kernel<2> : headconv_wide_kernel<4>;
+    VX_CHECK(vx_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), W_SMEM_BYTES));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles), dim3(256), W_SMEM_BYTES, as_stream(stream), reinterpret_cast<const f16*>(x),
+                       reinterpret_cast<const f16*>(wfrag), bias, w3, b3, scale, out, B, H, W, hs, ws, tiles_x, tiles_y);
+    VX_LAUNCH_CHECK();
+    return 1;
 }
 
 // diagnostics: u64 [blocks][4 waves][8] = cycles in {tables, wait + barriers, DMA issue + interpolation, MFMA + epilogue}, tiles, lifetime

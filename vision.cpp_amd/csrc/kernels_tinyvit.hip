@@ -179,6 +179,89 @@ __global__ __launch_bounds__(256) void tv_layernorm_kernel(const f16* __restrict
     }
 }
 
+// ---- LayerNorm of rows wider than 512 channels (C in (512, 1024], a multiple of 8: the ViT-B / ViT-L encoders' 768 / 1024). One wave
+// per row, each lane holding V = 2 chunks of 8 channels (two 16-byte loads, channels 8 lane and 512 + 8 lane): the row is in registers,
+// so the two-pass f32 statistics cost a full-wave xor reduction each and the row is read once. At these widths a row is 1.5-2 KB, and
+// one wave streaming it with 16-byte loads is what the memory side needs; a narrower group would leave lanes holding four chunks for no
+// gain, a wider one (two waves) needs an LDS exchange per reduction. Same window / padding / out_f32 semantics as tv_layernorm_kernel.
+template <int V>
+__global__ __launch_bounds__(256) void tv_layernorm_wide_kernel(const f16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                                void* __restrict__ y, long rows_out, int C, float eps, int res, int ws, int nw,
+                                                                int out_f32) {
+    const int lane = threadIdx.x & 63;
+    const long row = ((long)blockIdx.x * 256 + threadIdx.x) / 64; // uniform per wave
+    if (row >= rows_out) return;
+    long src = row;
+    bool padded = false;
+    if (ws > 0) {
+        const int N = ws * ws;
+        const int in = (int)(row % N);
+        long wq = row / N;
+        const int wx = (int)(wq % nw);
+        wq /= nw;
+        const int wy = (int)(wq % nw), bb = (int)(wq / nw);
+        const int py = wy * ws + in / ws, px = wx * ws + in % ws;
+        padded = py >= res || px >= res;
+        src = ((long)bb * res + py) * res + px;
+    }
+    float v[V][8];
+    bool has[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const int c0 = (lane + 64 * k) * 8;
+        has[k] = c0 < C;
+        if (has[k] && !padded) {
+            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + src * C + c0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[k][j] = (float)xv[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[k][j] = 0.0f;
+        }
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum += v[k][j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const float inv_c = 1.0f / (float)C;
+    const float mean = sum * inv_c;
+    float sq = 0.0f;
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[k][j] = has[k] ? v[k][j] - mean : 0.0f;
+            sq += v[k][j] * v[k][j];
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    const float rstd = __builtin_amdgcn_rsqf(fmaf(sq, inv_c, eps));
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        if (!has[k]) continue;
+        const int c0 = (lane + 64 * k) * 8;
+        const float4 w0 = *reinterpret_cast<const float4*>(w + c0), w1 = *reinterpret_cast<const float4*>(w + c0 + 4);
+        const float4 b0 = *reinterpret_cast<const float4*>(b + c0), b1 = *reinterpret_cast<const float4*>(b + c0 + 4);
+        const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w}, bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = v[k][j] * rstd * wv[j] + bv[j];
+        if (out_f32) {
+            float* dst = reinterpret_cast<float*>(y) + row * C + c0;
+            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        } else {
+            f16x8 ov;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ov[j] = (f16)o[j];
+            *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(y) + row * C + c0) = ov;
+        }
+    }
+}
+
 // ---- window_reverse + residual (mobile-sam.cpp:48-64, 146-149): y[b, py, px, :] = x[b, py, px, :] + a[window row of (py, px), :]
 __global__ void tv_window_reverse_add_kernel(const f16* __restrict__ a, const f16* __restrict__ x, f16* __restrict__ y, int B, int res, int ws,
                                              int nw, int C) {
@@ -388,7 +471,7 @@ int vx_dwconv3x3_f16(const void* x, const void* w, const float* bias, void* y, i
 
 int vx_layernorm_f16(const void* x, const float* w, const float* b, void* y, int64_t rows_out, int C, float eps, int res, int ws, int out_f32,
                      void* stream) {
-    VX_REQUIRE(x && w && b && y && rows_out > 0 && C > 0 && C <= 512 && C % 8 == 0, "vx_layernorm_f16: bad operands (C = %d: a multiple of 8, at most 512)", C);
+    VX_REQUIRE(x && w && b && y && rows_out > 0 && C > 0 && C <= 1024 && C % 8 == 0, "vx_layernorm_f16: bad operands (C = %d: a multiple of 8, at most 1024)", C);
     const int nw = ws > 0 ? (res + ws - 1) / ws : 0;
     VX_REQUIRE(ws == 0 || rows_out % ((int64_t)nw * nw * ws * ws) == 0, "vx_layernorm_f16: rows do not form whole images of %d x %d windows", nw, nw);
     const f16* xp = reinterpret_cast<const f16*>(x);
@@ -396,7 +479,8 @@ int vx_layernorm_f16(const void* x, const float* w, const float* b, void* y, int
     hipStream_t s = as_stream(stream);
     if (C <= 128) hipLaunchKernelGGL(tv_layernorm_kernel<16>, dim3(blocks_for(rows, 16)), dim3(256), 0, s, xp, w, b, y, rows, C, eps, res, ws, nw, out_f32);
     else if (C <= 256) hipLaunchKernelGGL(tv_layernorm_kernel<32>, dim3(blocks_for(rows, 8)), dim3(256), 0, s, xp, w, b, y, rows, C, eps, res, ws, nw, out_f32);
-    else hipLaunchKernelGGL(tv_layernorm_kernel<64>, dim3(blocks_for(rows, 4)), dim3(256), 0, s, xp, w, b, y, rows, C, eps, res, ws, nw, out_f32);
+    else if (C <= 512) hipLaunchKernelGGL(tv_layernorm_kernel<64>, dim3(blocks_for(rows, 4)), dim3(256), 0, s, xp, w, b, y, rows, C, eps, res, ws, nw, out_f32);
+    else hipLaunchKernelGGL(tv_layernorm_wide_kernel<2>, dim3(blocks_for(rows, 4)), dim3(256), 0, s, xp, w, b, y, rows, C, eps, res, ws, nw, out_f32);
     VX_LAUNCH_CHECK();
     return 1;
 }

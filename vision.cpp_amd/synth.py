@@ -27,9 +27,14 @@ class Config:
     mlp_ratio: int = 4
     neck_sizes: tuple = (48, 96, 192, 384)
     fusion_size: int = 64
-    head_size: int = 32
+    head_size: int = 32  # head.conv1's output channels (fusion_hidden_size / 2 in HF's DPT head)
     feature_layers: tuple = (2, 5, 8, 11)
     name: str = "small"
+    head_hidden: int = 0  # head.conv2's output channels (HF head_hidden_size, 32 for every released checkpoint); 0 = head_size
+
+    @property
+    def head_out(self) -> int:
+        return self.head_hidden or self.head_size
 
     @property
     def grid(self) -> int:
@@ -46,6 +51,18 @@ MINI = Config(embed_dim=128, n_layers=4, n_heads=2, image_size=112, neck_sizes=(
 # "short": the north-star widths (384 / 1536, 6 heads of 64) with 3 layers on 8x8 patches -- the smallest model that runs
 # the token-stationary block kernel (csrc/kernels_block16.hip); the last two taps name the same layer
 SHORT = Config(embed_dim=384, n_layers=3, n_heads=6, image_size=112, feature_layers=(0, 1, 2, 2), name="short")
+# the Base and Large checkpoints at full size (HF Depth-Anything-V2-Base / -Large: ViT-B/14 and ViT-L/14, DPT neck of 96..768 / 256..1024
+# channels, fusion 128 / 256, head.conv1 to fusion / 2, head.conv2 to 32)
+BASE = Config(embed_dim=768, n_layers=12, n_heads=12, neck_sizes=(96, 192, 384, 768), fusion_size=128, head_size=64, head_hidden=32,
+              name="base")
+LARGE = Config(embed_dim=1024, n_layers=24, n_heads=16, neck_sizes=(256, 512, 1024, 1024), fusion_size=256, head_size=128, head_hidden=32,
+               feature_layers=(4, 11, 17, 23), name="large")
+# their widths and heads with 4 layers on 8x8 patches (the spirit of SHORT; four layers, not three, because transformers refuses a
+# repeated tap and these configs are pinned on it): every kernel the full models run, at a fraction of the cost
+BASE_SHORT = Config(embed_dim=768, n_layers=4, n_heads=12, image_size=112, neck_sizes=(96, 192, 384, 768), fusion_size=128, head_size=64,
+                    head_hidden=32, feature_layers=(0, 1, 2, 3), name="base_short")
+LARGE_SHORT = Config(embed_dim=1024, n_layers=4, n_heads=16, image_size=112, neck_sizes=(256, 512, 1024, 1024), fusion_size=256,
+                     head_size=128, head_hidden=32, feature_layers=(0, 1, 2, 3), name="large_short")
 
 
 def state_dict(cfg: Config = SMALL, seed: int = 0) -> dict[str, np.ndarray]:
@@ -110,8 +127,8 @@ def state_dict(cfg: Config = SMALL, seed: int = 0) -> dict[str, np.ndarray]:
             conv(f"{p}.{rl}.convolution1", F, F, 3, gain=1.2)
             conv(f"{p}.{rl}.convolution2", F, F, 3, gain=0.7)
     conv("head.conv1", cfg.head_size, F, 3)
-    conv("head.conv2", cfg.head_size, cfg.head_size, 3, gain=1.4)
-    conv("head.conv3", 1, cfg.head_size, 1, gain=1.0)
+    conv("head.conv2", cfg.head_out, cfg.head_size, 3, gain=1.4)
+    conv("head.conv3", 1, cfg.head_out, 1, gain=1.0)
     # non-negative 1x1 weights + positive bias: the final ReLU stays active, so the min-max
     # normalised depth map is well conditioned (a real checkpoint behaves the same way)
     sd["head.conv3.weight"] = np.abs(sd["head.conv3.weight"])
