@@ -200,6 +200,19 @@ def test_batch_entry_against_oracle_and_single(device, tmp_path_factory, res):
         np.testing.assert_array_equal(got[i][..., 3], masks[i])
 
 
+def test_graph_recaptured_after_workspace_growth(device, tmp_path_factory):
+    """Batch 1 (captured, then replayed), batch 4 (the workspace grows: the batch-1 graph is dropped), batch 1 again (captured
+    anew on the new workspace, then replayed): bit-identical batch-1 results. A fresh model, so the workspace starts small."""
+    _, _, path = _model(device, tmp_path_factory, 256, seed=1)
+    model = vision.Migan.load(path, device)
+    imgs, masks = _inputs(4, 256, seed=21)
+    first = model.compute_batch(imgs[:1], masks[:1])
+    np.testing.assert_array_equal(model.compute_batch(imgs[:1], masks[:1]), first)
+    model.compute_batch(imgs, masks)
+    for _ in range(2):
+        np.testing.assert_array_equal(model.compute_batch(imgs[:1], masks[:1]), first)
+
+
 @pytest.mark.parametrize("w,h,channels", [(640, 480, 3), (512, 512, 4)])
 def test_migan_compute_any_extent(device, tmp_path_factory, w, h, channels):
     model, sd, _ = _model(device, tmp_path_factory, 512, seed=1)

@@ -209,6 +209,25 @@ def test_graph_replay_matches_direct_launches(small):
         small.use_graph(False)
 
 
+def test_graph_replay_after_step_eviction(small):
+    """Four extents through the captured path evict the first one's step (three stay lowered); the first extent again is
+    lowered and captured anew and gives the same bits as direct launches."""
+    extents = [(112, 112), (126, 112), (112, 126), (140, 112)]
+    imgs = {e: synth.images(2, e[1], e[0], seed=30 + i) for i, e in enumerate(extents)}
+    w0, h0 = extents[0]
+    want = small.compute_batch(imgs[extents[0]])
+    small.use_graph(True)
+    try:
+        for w, h in extents + [extents[0]]:
+            rgb = vision.DeviceBuffer.from_numpy(imgs[(w, h)])
+            out = vision.DeviceBuffer(2 * w * h * 4)
+            small.compute_batch_device(rgb.ptr, 2, w, h, out.ptr)
+            if (w, h) == (w0, h0):
+                np.testing.assert_array_equal(out.to_numpy(np.float32, (2, h0, w0)), want)
+    finally:
+        small.use_graph(False)
+
+
 def test_reference_c_api_compute(small):
     """visp_model_compute as the reference's ctypes binding calls it (vision.py:103-128): one image of
     arbitrary extent and channel order in, alpha_u8 out. 640x480 -> model extent 700x518 (non-square, so

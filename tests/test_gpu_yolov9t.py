@@ -205,6 +205,20 @@ def test_batch_equals_single_calls_and_graph_replay(device, tmp_path_factory):
         assert np.array_equal(first[b], again[b]) and np.array_equal(first[b], singles[b]) and np.array_equal(first[b], four[b])
 
 
+def test_graph_recaptured_after_workspace_growth(device, tmp_path_factory):
+    """Batch 1 (captured, then replayed), batch 4 (the workspace grows: the batch-1 graph is dropped), batch 1 again (captured
+    anew on the new workspace, then replayed): equal detections. A fresh model, so the workspace starts small."""
+    _, _, path = _model(device, tmp_path_factory)
+    model = vision.Yolov9t.load(path, device)
+    imgs = synth.images(4, 320, 320, seed=5)
+    first = model.detect_batch(imgs[:1])[0]
+    assert len(first) > 0
+    assert np.array_equal(model.detect_batch(imgs[:1])[0], first)
+    model.detect_batch(imgs)
+    for _ in range(2):
+        assert np.array_equal(model.detect_batch(imgs[:1])[0], first)
+
+
 def _as_tuples(d):
     return [(r["x1"], r["y1"], r["x2"], r["y2"], r["confidence"], int(r["class_id"])) for r in d]
 

@@ -12,11 +12,6 @@
 
 namespace visp {
 
-birefnet_model::~birefnet_model() {
-    vx_free(dws.ptr);
-    vx_free(dec_arena.ptr);
-}
-
 i32x2 birefnet_image_extent(i32x2 input_extent, birefnet_params const& p) { // birefnet.cpp:283-301
     if (p.image_size != -1) return {{p.image_size, p.image_size}};
     if (input_extent[0] <= 0 || input_extent[1] <= 0) throw except("birefnet: dynamic models need a positive input extent");
@@ -255,10 +250,7 @@ birefnet_model* birefnet_load_model(char const* filepath, backend_device const& 
         if (k != 1 || D.conv_out1.n_real != 1 || cin != carried + D.ipt[4].cout) throw except("birefnet: decoder.conv_out1.0 has an unexpected shape");
     }
     device_turn turn(dev);
-    model->dec_arena.bytes = round_up<size_t>(ab.data.size(), 256) + 4096;
-    VX(vx_malloc(&model->dec_arena.ptr, model->dec_arena.bytes));
-    VX(vx_memcpy_h2d(model->dec_arena.ptr, ab.data.data(), ab.data.size(), dev.stream));
-    VX(vx_stream_sync(dev.stream));
+    model->dec_arena = upload_arena(ab.data, dev.stream);
     return model.release();
 }
 
@@ -402,15 +394,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
     };
 
     const size_t need = pass(true) + 4096;
-    if (m.dws.bytes < need) {
-        VX(vx_stream_sync(m.backend->stream));
-        VX(vx_stream_sync(s));
-        vx_free(m.dws.ptr);
-        m.dws = {};
-        VX(vx_malloc(&m.dws.ptr, need));
-        m.dws.bytes = need;
-        VX(vx_memset(m.dws.ptr, 0, need, s)); // GEMM rows are read up to K padded to 64: stale bytes must be finite
-    }
+    grow(m.dws, need, {m.backend->stream, s}, s); // zero-filled: GEMM rows are read up to K padded to 64, stale bytes must be finite
     pass(false);
     if (!stream) VX(vx_stream_sync(s));
 }
@@ -419,20 +403,11 @@ void birefnet_compute_batch_host(birefnet_model& m, uint8_t const* rgb, int B, i
     if (B < 1 || !rgb || !mask) throw except("birefnet: empty batch or null pointer");
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
-    void *in = nullptr, *out = nullptr;
-    auto release = [&]() { vx_free(in); vx_free(out); };
-    try {
-        VX(vx_malloc(&in, (size_t)B * w * h * 3));
-        VX(vx_malloc(&out, (size_t)B * w * h * 4));
-        VX(vx_memcpy_h2d(in, rgb, (size_t)B * w * h * 3, s));
-        birefnet_compute_batch_device(m, in, B, w, h, out, s);
-        VX(vx_memcpy_d2h(mask, out, (size_t)B * w * h * 4, s));
-        VX(vx_stream_sync(s));
-    } catch (...) {
-        release();
-        throw;
-    }
-    release();
+    device_buffer in((size_t)B * w * h * 3), out((size_t)B * w * h * 4);
+    VX(vx_memcpy_h2d(in.ptr, rgb, (size_t)B * w * h * 3, s));
+    birefnet_compute_batch_device(m, in.ptr, B, w, h, out.ptr, s);
+    VX(vx_memcpy_d2h(mask, out.ptr, (size_t)B * w * h * 4, s));
+    VX(vx_stream_sync(s));
 }
 
 image_data birefnet_compute(birefnet_model& m, image_view image) { // vision.cpp:108-132

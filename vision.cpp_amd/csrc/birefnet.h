@@ -34,7 +34,6 @@ struct birefnet_model : swin_model { // vision.h birefnet_model counterpart; the
     birefnet_weights dec;
     device_buffer dec_arena;
     device_buffer dws; // decoder / feature workspace
-    ~birefnet_model() override;
 };
 
 birefnet_model* birefnet_load_model(char const* filepath, backend_device const& dev);

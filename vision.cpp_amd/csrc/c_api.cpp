@@ -105,10 +105,10 @@ void read_capture(model_base& m, char const* who, char const* name, float* host_
     if (n > capacity) return; // caller learns the size and retries
     if (c.f16) {
         std::unique_ptr<uint16_t[]> tmp(new uint16_t[(size_t)n]);
-        if (!vx_memcpy_d2h(tmp.get(), c.dev, (size_t)n * 2, m.backend->stream)) throw except("%s", vx_last_error());
+        if (!vx_memcpy_d2h(tmp.get(), c.dev.ptr, (size_t)n * 2, m.backend->stream)) throw except("%s", vx_last_error());
         for (int64_t i = 0; i < n; ++i) host_out[i] = f16_to_f32(tmp[(size_t)i]);
     } else {
-        if (!vx_memcpy_d2h(host_out, c.dev, (size_t)n * 4, m.backend->stream)) throw except("%s", vx_last_error());
+        if (!vx_memcpy_d2h(host_out, c.dev.ptr, (size_t)n * 4, m.backend->stream)) throw except("%s", vx_last_error());
     }
 }
 

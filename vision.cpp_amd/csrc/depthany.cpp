@@ -197,12 +197,8 @@ struct depthany_step {
     };
     std::vector<part> parts;
     device_buffer staging;     // u8 input | normalised out | raw depth of the whole batch: what a captured hipGraph reads and writes
-    void* graph_exec = nullptr;
+    captured_graph graph_exec; // (declared after the buffers: destroyed before the buffers it launches over)
     long last_use = 0;
-    ~depthany_step() {
-        if (graph_exec) vx_graph_destroy(graph_exec);
-        vx_free(staging.ptr);
-    }
 };
 
 namespace {
@@ -237,10 +233,9 @@ depthany_step& ensure_step(depthany_model& m, int B, int W, int H) {
     static const bool block_off = getenv("VISP_NO_BLOCK") != nullptr;
     const bool fused = m.schedule != 0 && !(block_off && m.schedule < 0);
     const int n_split = pick_split(m, B, m.captures);
-    static long clock = 0;
     for (auto& s : m.steps)
         if (s->B == B && s->W == W && s->H == H && s->fused == fused && s->captures == m.captures && (int)s->parts.size() == n_split) {
-            s->last_use = ++clock;
+            s->last_use = ++m.step_clock;
             return *s;
         }
     while (m.steps.size() >= 3) { // a few shapes stay lowered (the timing pass, a second extent); the least recently used one goes
@@ -257,7 +252,7 @@ depthany_step& ensure_step(depthany_model& m, int B, int W, int H) {
         p.g = build_part(m, p.nb, W, H, fused, m.captures, p);
         graph_allocate(*p.g, m.backend);
     }
-    s->last_use = ++clock;
+    s->last_use = ++m.step_clock;
     m.steps.push_back(std::move(s));
     return *m.steps.back();
 }
@@ -398,15 +393,13 @@ depthany_model* depthany_load_model(char const* filepath, backend_device const& 
         need = plan->plan_store_bytes;
     }
     weight_store& ws = *model->store;
-    ws.arena.bytes = need + (1u << 20);
-    VX(vx_malloc(&ws.arena.ptr, ws.arena.bytes));
+    ws.arena = device_buffer(need + (1u << 20));
     {
         depthany_step::part scratch;
         std::unique_ptr<graph> warm = build_part(*model, 1, side, side, true, false, scratch);
         graph_allocate(*warm, &dev);
     }
-    model->weight_arena.ptr = ws.arena.ptr;
-    model->weight_arena.bytes = round_up<size_t>(ws.arena_used, 256);
+    model->weight_arena = {ws.arena.ptr, round_up<size_t>(ws.arena_used, 256)};
     model->weights_uploaded = with_data;
     return model.release();
 }
@@ -462,8 +455,7 @@ depthany_model* depthany_clone_executor(depthany_model const& src) {
 
 void depthany_drop_captured_steps(depthany_model& m) {
     if (m.backend) vx_set_device(m.backend->index);
-    for (auto& s : m.steps)
-        if (s->graph_exec) { vx_graph_destroy(s->graph_exec); s->graph_exec = nullptr; }
+    for (auto& s : m.steps) s->graph_exec = {};
 }
 
 void depthany_reserve(depthany_model& m, int B, int W, int H) {
@@ -480,10 +472,7 @@ void depthany_compute_batch_device(depthany_model& m, void const* rgb_dev, int b
     const size_t in_bytes = (size_t)batch * h * w * 3, out_bytes = (size_t)batch * h * w * 4;
     if (m.use_graph && !m.captures && !m.timing) {
         // the captured launch sequence bakes pointers in: it reads and writes the step's own staging buffers
-        if (!s.staging.ptr) {
-            s.staging.bytes = round_up<size_t>(in_bytes, 256) + 2 * round_up<size_t>(out_bytes, 256);
-            VX(vx_malloc(&s.staging.ptr, s.staging.bytes));
-        }
+        if (!s.staging.ptr) s.staging = device_buffer(round_up<size_t>(in_bytes, 256) + 2 * round_up<size_t>(out_bytes, 256));
         uint8_t* in = static_cast<uint8_t*>(s.staging.ptr);
         float* out = reinterpret_cast<float*>(in + round_up<size_t>(in_bytes, 256));
         float* raw = reinterpret_cast<float*>(in + round_up<size_t>(in_bytes, 256) + round_up<size_t>(out_bytes, 256));
@@ -491,18 +480,9 @@ void depthany_compute_batch_device(depthany_model& m, void const* rgb_dev, int b
         if (!s.graph_exec) {
             bind_parts(s, in, out, raw);
             run_parts(m, s, strm); // eager once: every kernel attribute is set before the capture
-            VX(vx_graph_begin_capture(strm));
-            try {
-                run_parts(m, s, strm);
-            } catch (...) {
-                void* dead = nullptr;
-                vx_graph_end_capture(strm, &dead);
-                if (dead) vx_graph_destroy(dead);
-                throw;
-            }
-            VX(vx_graph_end_capture(strm, &s.graph_exec));
+            s.graph_exec = capture(strm, [&] { run_parts(m, s, strm); });
         }
-        VX(vx_graph_launch(s.graph_exec, strm));
+        s.graph_exec.launch(strm);
         VX(vx_memcpy_d2d(out_dev, out, out_bytes, strm));
         if (raw_out_dev) VX(vx_memcpy_d2d(raw_out_dev, raw, out_bytes, strm));
     } else {
@@ -517,12 +497,7 @@ void depthany_compute_batch_host(depthany_model& m, uint8_t const* rgb, int batc
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
     const size_t in_bytes = (size_t)batch * h * w * 3, out_bytes = (size_t)batch * h * w * 4;
-    if (m.host_io.bytes < in_bytes + 2 * out_bytes + 512) {
-        VX(vx_free(m.host_io.ptr));
-        m.host_io = {};
-        VX(vx_malloc(&m.host_io.ptr, in_bytes + 2 * out_bytes + 512));
-        m.host_io.bytes = in_bytes + 2 * out_bytes + 512;
-    }
+    grow(m.host_io, in_bytes + 2 * out_bytes + 512, {});
     uint8_t* in = static_cast<uint8_t*>(m.host_io.ptr);
     uint8_t* o = in + round_up<size_t>(in_bytes, 256);
     uint8_t* r = o + round_up<size_t>(out_bytes, 256);
@@ -568,8 +543,8 @@ depthany_pipeline* depthany_pipeline_create(depthany_model& m, int batch, int w,
     for (auto& s : p->slots) {
         VX(vx_malloc_host(&s.pin_in, p->in_bytes));
         VX(vx_malloc_host(&s.pin_out, p->out_bytes));
-        VX(vx_malloc(&s.dev_in, p->in_bytes));
-        VX(vx_malloc(&s.dev_out, p->out_bytes));
+        s.dev_in = device_buffer(p->in_bytes);
+        s.dev_out = device_buffer(p->out_bytes);
         VX(vx_event_create(&s.uploaded));
         VX(vx_event_create(&s.computed));
         VX(vx_event_create(&s.downloaded));
@@ -582,7 +557,6 @@ depthany_pipeline::~depthany_pipeline() {
     for (auto& s : slots) {
         if (s.busy) vx_event_sync(s.downloaded);
         vx_free_host(s.pin_in); vx_free_host(s.pin_out);
-        vx_free(s.dev_in); vx_free(s.dev_out);
         vx_event_destroy(s.uploaded); vx_event_destroy(s.computed); vx_event_destroy(s.downloaded);
     }
     if (h2d_stream) vx_stream_destroy(h2d_stream);
@@ -615,13 +589,13 @@ int depthany_pipeline_submit(depthany_pipeline& p, uint8_t const* rgb) {
     }
     if (rgb && rgb != s.pin_in) memcpy(s.pin_in, rgb, p.in_bytes);
     void* cs = p.compute_stream[e];
-    VX(vx_memcpy_h2d_async(s.dev_in, s.pin_in, p.in_bytes, p.h2d_stream));
+    VX(vx_memcpy_h2d_async(s.dev_in.ptr, s.pin_in, p.in_bytes, p.h2d_stream));
     VX(vx_event_record(s.uploaded, p.h2d_stream));
     VX(vx_stream_wait_event(cs, s.uploaded));
-    depthany_compute_batch_device(em, s.dev_in, p.batch, p.w, p.h, s.dev_out, nullptr, cs);
+    depthany_compute_batch_device(em, s.dev_in.ptr, p.batch, p.w, p.h, s.dev_out.ptr, nullptr, cs);
     VX(vx_event_record(s.computed, cs));
     VX(vx_stream_wait_event(p.d2h_stream, s.computed));
-    VX(vx_memcpy_d2h_async(s.pin_out, s.dev_out, p.out_bytes, p.d2h_stream));
+    VX(vx_memcpy_d2h_async(s.pin_out, s.dev_out.ptr, p.out_bytes, p.d2h_stream));
     VX(vx_event_record(s.downloaded, p.d2h_stream));
     s.busy = true;
     p.next = (p.next + 1) % p.n_slots;

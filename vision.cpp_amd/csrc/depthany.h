@@ -39,10 +39,11 @@ struct depthany_model : model_base { // vision.h:339-347 counterpart: {backend, 
     depthany_model();
     depthany_params params;
     std::shared_ptr<weight_store> store; // the model's tensors by name + their device images per consumer role, all in one arena (shared by cloned executors)
-    device_buffer weight_arena;          // that arena: what rank 0 broadcasts and the other ranks receive (not owned here: the store frees it)
+    device_span weight_arena;            // that arena: what rank 0 broadcasts and the other ranks receive
     bool weights_uploaded = false;
     bool block_shape = false; // embed dim 384 / mlp 1536 / head dim 64: the encoder groups lower to the token-stationary block kernel
     std::vector<std::unique_ptr<depthany_step>> steps; // a few lowered shapes, least recently used first out
+    long step_clock = 0;                                // ticks of steps[i]->last_use
     device_buffer host_io;    // device staging of the blocking host entry
     bool use_graph = false;
     int split = 0; // sub-batches of a step on parallel streams: 0 = automatic (3 from batch 24, 2 from batch 8; $VISP_SPLIT overrides), 1 = none, 2..4
@@ -86,7 +87,8 @@ struct depthany_pipeline {
     int batch = 0, w = 0, h = 0, n_slots = 0;
     size_t in_bytes = 0, out_bytes = 0;
     struct slot {
-        void *pin_in = nullptr, *pin_out = nullptr, *dev_in = nullptr, *dev_out = nullptr;
+        void *pin_in = nullptr, *pin_out = nullptr;
+        device_buffer dev_in, dev_out;
         void *uploaded = nullptr, *computed = nullptr, *downloaded = nullptr; // events
         bool busy = false;
     };

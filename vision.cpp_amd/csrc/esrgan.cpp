@@ -184,15 +184,13 @@ esrgan_model* esrgan_load_model(char const* filepath, backend_device const& dev,
         need = plan->plan_store_bytes;
     }
     weight_store& ws = *model->store;
-    ws.arena.bytes = need + (1u << 20);
-    VX(vx_malloc(&ws.arena.ptr, ws.arena.bytes));
+    ws.arena = device_buffer(need + (1u << 20));
     {
         int in, out;
         std::unique_ptr<graph> warm = generator_graph(*model, 1, 32, 32, &in, &out);
         graph_allocate(*warm, &dev);
     }
-    model->weight_arena.ptr = ws.arena.ptr;
-    model->weight_arena.bytes = round_up<size_t>(ws.arena_used, 256);
+    model->weight_arena = {ws.arena.ptr, round_up<size_t>(ws.arena_used, 256)};
     model->weights_uploaded = with_data;
     if (const char* e = getenv("VISP_ESRGAN_TILE_GROUP")) model->tile_group = std::max(1, atoi(e));
     if (const char* e = getenv("VISP_ESRGAN_STREAMS")) model->streams = std::max(1, atoi(e));
@@ -216,8 +214,6 @@ esrgan_model::~esrgan_model() {
     if (fork_event) vx_event_destroy(fork_event);
     if (join_event) vx_event_destroy(join_event);
     for (auto& lane : steps) lane.clear();
-    vx_free(ws.arena.ptr);
-    weight_arena = {}; // (the store owns it)
 }
 
 //
@@ -244,14 +240,7 @@ void reserve(esrgan_model& m, int n_tiles_total, int tw, int th) {
         {&ws.x0, (size_t)n_tiles_total * px * 3 * 4}, {&ws.tiles_out, (size_t)n_tiles_total * px * s * s * 3 * 4}};
     size_t total = 0;
     for (item& it : items) total += round_up<size_t>(it.bytes, 256);
-    if (total > ws.arena.bytes) {
-        VX(vx_stream_sync(m.backend->stream));
-        if (m.aux_stream) VX(vx_stream_sync(m.aux_stream));
-        vx_free(ws.arena.ptr);
-        ws.arena = {};
-        VX(vx_malloc(&ws.arena.ptr, total));
-        ws.arena.bytes = total;
-    }
+    grow(ws.arena, total, {m.backend->stream, m.aux_stream});
     uint8_t* p = static_cast<uint8_t*>(ws.arena.ptr);
     for (item& it : items) {
         *it.p = p;

@@ -59,7 +59,7 @@ struct esrgan_model : model_base { // vision.h:361-369 counterpart
     esrgan_params params;
     int nf = 64, gc = 32;                    // filters / growth channels of the file
     std::shared_ptr<weight_store> store;     // the file's tensors + their packed device images (one arena: what a load-time broadcast moves)
-    device_buffer weight_arena;              // = the store's arena
+    device_span weight_arena;                // = the store's arena
     std::vector<std::unique_ptr<esrgan_step>> steps[2]; // per lane: graphs of the most recent tile-group shapes
     bool weights_uploaded = false;
     esrgan_workspace ws;

@@ -190,14 +190,9 @@ const char* graph_op_name(int32_t op) { return op >= 0 && op < gop_count ? op_na
 
 graph::~graph() {
     if (dev) vx_set_device(dev->index); // frees go to the device the graph lives on, whatever the calling thread's current device is
-    if (graph_exec) vx_graph_destroy(graph_exec);
-    if (arena.ptr) vx_free(arena.ptr);
-    for (void* p : const_allocs) vx_free(p);
 }
 weight_store::~weight_store() {
     if (dev) vx_set_device(dev->index);
-    if (arena.ptr) vx_free(arena.ptr);
-    for (void* p : allocs) vx_free(p);
 }
 
 std::shared_ptr<weight_store> weights_create() { return std::make_shared<weight_store>(); }
@@ -620,9 +615,10 @@ struct lowering {
             ws.device_bytes += bytes;
         } else {
             if (to_store && ws.no_data) throw except("graph: this rank holds no weight data (the arena came by broadcast) and the image it needs is not part of the arena");
-            VX(vx_malloc(&d, bytes + 256));
-            if (to_store) { ws.allocs.push_back(d); ws.device_bytes += bytes; }
-            else g.const_allocs.push_back(d);
+            device_buffer b(bytes + 256);
+            d = b.ptr;
+            if (to_store) { ws.allocs.push_back(std::move(b)); ws.device_bytes += bytes; }
+            else g.const_allocs.push_back(std::move(b));
         }
         if (to_store && ws.no_data) return d; // laid out, filled by the broadcast
         VX(vx_memcpy_h2d(d, host, bytes, g.dev->stream));
@@ -2236,8 +2232,7 @@ void graph_allocate(graph& g, backend_device const* dev) {
     lowering low(g);
     low.run();
     if (g.dev) {
-        VX(vx_malloc(&g.arena.ptr, g.arena_bytes));
-        g.arena.bytes = g.arena_bytes;
+        g.arena = device_buffer(g.arena_bytes);
         VX(vx_memset(g.arena.ptr, 0, g.arena_bytes, g.dev->stream));
         VX(vx_stream_sync(g.dev->stream));
     }
@@ -2254,24 +2249,16 @@ void graph_compute(graph& g) {
     device_turn turn(*g.dev);
     void* st = g.dev->stream;
     if (g.use_hip_graph && g.graph_exec) {
-        VX(vx_graph_launch(g.graph_exec, st));
+        g.graph_exec.launch(st);
         VX(vx_stream_sync(st));
         return;
     }
     for (auto& l : g.launches) l.run(st);
     VX(vx_stream_sync(st));
-    if (g.use_hip_graph) { // the eager pass above set every kernel attribute; now record the same launches once
-        VX(vx_graph_begin_capture(st));
-        try {
+    if (g.use_hip_graph) // the eager pass above set every kernel attribute; now record the same launches once
+        g.graph_exec = capture(st, [&] {
             for (auto& l : g.launches) l.run(st);
-        } catch (...) {
-            void* dead = nullptr;
-            vx_graph_end_capture(st, &dead);
-            if (dead) vx_graph_destroy(dead);
-            throw;
-        }
-        VX(vx_graph_end_capture(st, &g.graph_exec));
-    }
+        });
 }
 
 static char* tensor_ptr(graph& g, int t, const char* what) {

@@ -105,7 +105,7 @@ struct weight_store {
     std::map<std::string, entry, std::less<>> tensors;
     backend_device const* dev = nullptr;                    // bound by the first graph_allocate with a device
     std::map<std::pair<std::string, int>, void*> packs;     // (name, role) -> device image
-    std::vector<void*> allocs;
+    std::vector<device_buffer> allocs;
     size_t device_bytes = 0;
     // One device arena for every image (optional; depthany's loader sizes it from a planning pass): images are then bump-allocated in
     // lowering order, which is the same on every rank -- the arena IS the model on the device, one RCCL broadcast moves it. no_data: the
@@ -135,10 +135,10 @@ struct graph {
     size_t arena_bytes = 0, sum_bytes = 0; // with recycling / if every buffer had its own storage
     size_t plan_store_bytes = 0;           // planning only (no device): bytes of weight images this graph would add to the shared store
     device_buffer arena;
-    std::vector<void*> const_allocs;       // packed weights and constants (device)
+    std::vector<device_buffer> const_allocs; // packed weights and constants (device)
     size_t const_bytes = 0;
     bool use_hip_graph = false;
-    void* graph_exec = nullptr;
+    captured_graph graph_exec; // (after the buffers: destroyed before them)
     // fused_models: the lowering may replace whole node groups by the kernels written for them (the dino::layer group -> attention + one
     // token-stationary block launch with an f32 residual stream, interpolate -> conv 3x3 -> the resizing halo loader, ...). false: one
     // launch per (epilogue-fused) node on f16 activations -- what visp_depthany_set_schedule(model, 0) selects.

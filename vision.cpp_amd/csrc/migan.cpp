@@ -157,19 +157,11 @@ migan_model* migan_load_model(char const* filepath, backend_device const& dev) {
     }
 
     device_turn turn(dev);
-    model->weight_arena.bytes = round_up<size_t>(ab.data.size(), 256) + 4096;
-    VX(vx_malloc(&model->weight_arena.ptr, model->weight_arena.bytes));
-    VX(vx_memcpy_h2d(model->weight_arena.ptr, ab.data.data(), ab.data.size(), dev.stream));
-    VX(vx_stream_sync(dev.stream));
+    model->weight_arena = upload_arena(ab.data, dev.stream);
     return model.release();
 }
 
 namespace {
-
-void drop_graphs(migan_model& m) {
-    for (auto& g : m.graphs) vx_graph_destroy(g.second);
-    m.graphs.clear();
-}
 
 // workspace layout for a batch: the skip features of every level, three activation buffers of the largest map, two f32 image
 // planes, the u8 inputs / output and the f32 input of the parity path
@@ -290,14 +282,7 @@ struct migan_exec {
 migan_exec make_exec(migan_model& m, int B, void* stream) {
     if (B < 1) throw except("migan: empty batch");
     if (B > m.ws_batch) {
-        migan_layout L = plan(m, B);
-        VX(vx_stream_sync(m.backend->stream));
-        if (stream) VX(vx_stream_sync(stream));
-        drop_graphs(m);
-        vx_free(m.ws.ptr);
-        m.ws = {};
-        VX(vx_malloc(&m.ws.ptr, L.total));
-        m.ws.bytes = L.total;
+        if (grow(m.ws, plan(m, B).total, {m.backend->stream, stream})) m.graphs.clear();
         m.ws_batch = B;
     }
     return migan_exec{m, stream, static_cast<const uint8_t*>(m.weight_arena.ptr), static_cast<uint8_t*>(m.ws.ptr), plan(m, B), B, {}};
@@ -318,12 +303,6 @@ void run_u8(migan_exec& ex, int img_channels) {
 
 } // namespace
 
-migan_model::~migan_model() {
-    drop_graphs(*this);
-    vx_free(ws.ptr);
-    vx_free(weight_arena.ptr);
-}
-
 void migan_compute_batch_device(migan_model& m, void const* img_dev, int img_channels, void const* mask_dev, int batch, void* out_rgba_dev, void* stream) {
     if (!img_dev || !mask_dev || !out_rgba_dev) throw except("migan: null input/output pointer");
     if (img_channels != 3 && img_channels != 4) throw except("migan: image must have 3 or 4 channels, got %d", img_channels);
@@ -340,21 +319,9 @@ void migan_compute_batch_device(migan_model& m, void const* img_dev, int img_cha
     if (eager || it == m.graphs.end()) {
         run_u8(ex, img_channels); // eager; the first call of a shape also warms up every kernel before the capture
         ex.finish_timing();
-        if (!eager) {
-            void* g = nullptr;
-            VX(vx_graph_begin_capture(s));
-            try {
-                run_u8(ex, img_channels);
-            } catch (...) {
-                vx_graph_end_capture(s, &g);
-                if (g) vx_graph_destroy(g);
-                throw;
-            }
-            VX(vx_graph_end_capture(s, &g));
-            m.graphs[key] = g;
-        }
+        if (!eager) m.graphs[key] = capture(s, [&] { run_u8(ex, img_channels); });
     } else {
-        VX(vx_graph_launch(it->second, s));
+        it->second.launch(s);
     }
     VX(vx_memcpy_d2d(out_rgba_dev, ex.at(ex.L.out_rgba), px * 4, s));
     if (!stream) VX(vx_stream_sync(s));
@@ -368,22 +335,12 @@ void migan_compute_batch_host(migan_model& m, uint8_t const* img, int img_channe
     void* s = m.backend->stream;
     const int R = m.params.resolution;
     const size_t px = (size_t)batch * R * R;
-    void *din = nullptr, *dmask = nullptr, *dout = nullptr;
-    auto release = [&]() { vx_free(din); vx_free(dmask); vx_free(dout); };
-    try {
-        VX(vx_malloc(&din, px * img_channels));
-        VX(vx_malloc(&dmask, px));
-        VX(vx_malloc(&dout, px * 4));
-        VX(vx_memcpy_h2d(din, img, px * img_channels, s));
-        VX(vx_memcpy_h2d(dmask, mask, px, s));
-        migan_compute_batch_device(m, din, img_channels, dmask, batch, dout, s);
-        VX(vx_memcpy_d2h(out_rgba, dout, px * 4, s));
-        VX(vx_stream_sync(s));
-    } catch (...) {
-        release();
-        throw;
-    }
-    release();
+    device_buffer din(px * img_channels), dmask(px), dout(px * 4);
+    VX(vx_memcpy_h2d(din.ptr, img, px * img_channels, s));
+    VX(vx_memcpy_h2d(dmask.ptr, mask, px, s));
+    migan_compute_batch_device(m, din.ptr, img_channels, dmask.ptr, batch, dout.ptr, s);
+    VX(vx_memcpy_d2h(out_rgba, dout.ptr, px * 4, s));
+    VX(vx_stream_sync(s));
 }
 
 void migan_generate_host(migan_model& m, float const* in4, int n, float* out_rgb) {

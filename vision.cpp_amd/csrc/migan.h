@@ -44,9 +44,8 @@ struct migan_model : model_base { // vision.h:371-375 counterpart
     device_buffer weight_arena;
     device_buffer ws;
     int ws_batch = 0;
-    std::map<int, void*> graphs; // batch size -> captured launch list of the u8 -> rgba path (one stream, no branches)
+    std::map<int, captured_graph> graphs; // batch size -> captured launch list of the u8 -> rgba path (one stream, no branches)
     bool use_graph = true;
-    ~migan_model() override;
 };
 
 migan_model* migan_load_model(char const* filepath, backend_device const& dev);

@@ -6,6 +6,10 @@
 #include "visp_util.h"
 
 namespace visp {
+namespace {
+template <typename T>
+T round_up(T x, T m) { return (x + m - 1) / m * m; }
+} // namespace
 
 #define VX(call)                                        \
     do {                                                \
@@ -42,22 +46,79 @@ backend_device::~backend_device() {
 }
 
 //
+// device memory and captured graphs
+
+device_buffer::device_buffer(size_t n) : bytes(n) { VX(vx_malloc(&ptr, n)); }
+device_buffer& device_buffer::operator=(device_buffer&& o) noexcept {
+    if (this != &o) {
+        vx_free(ptr);
+        ptr = o.ptr;
+        bytes = o.bytes;
+        o.ptr = nullptr;
+        o.bytes = 0;
+    }
+    return *this;
+}
+device_buffer::~device_buffer() { vx_free(ptr); }
+
+bool grow(device_buffer& b, size_t need, std::initializer_list<void*> syncs, void* zero_on) {
+    if (b.bytes >= need) return false;
+    for (void* s : syncs)
+        if (s) VX(vx_stream_sync(s));
+    b = {};
+    b = device_buffer(need);
+    if (zero_on) VX(vx_memset(b.ptr, 0, need, zero_on));
+    return true;
+}
+
+device_buffer upload_arena(std::vector<uint8_t> const& image, void* stream, bool copy) {
+    device_buffer b(round_up<size_t>(image.size(), 256) + 4096);
+    if (copy) {
+        VX(vx_memcpy_h2d(b.ptr, image.data(), image.size(), stream));
+        VX(vx_stream_sync(stream));
+    }
+    return b;
+}
+
+captured_graph& captured_graph::operator=(captured_graph&& o) noexcept {
+    if (this != &o) {
+        vx_graph_destroy(exec);
+        exec = o.exec;
+        o.exec = nullptr;
+    }
+    return *this;
+}
+captured_graph::~captured_graph() { vx_graph_destroy(exec); }
+void captured_graph::launch(void* stream) const { VX(vx_graph_launch(exec, stream)); }
+
+captured_graph capture(void* stream, std::function<void()> const& record) {
+    captured_graph g;
+    VX(vx_graph_begin_capture(stream));
+    try {
+        record();
+    } catch (...) {
+        vx_graph_end_capture(stream, &g.exec); // (g drops what a partial capture instantiated)
+        throw;
+    }
+    VX(vx_graph_end_capture(stream, &g.exec));
+    return g;
+}
+
+//
 // instrumentation
 
 model_base::~model_base() {
     if (backend) vx_set_device(backend->index);
-    for (auto& c : capture_bufs) vx_free(c.second.dev);
 }
 
 void model_base::keep_capture(std::string const& name, void const* src, int64_t const (&shape)[4], bool f16, void* stream) {
     capture_entry& c = capture_bufs[name];
-    vx_free(c.dev);
-    c.dev = nullptr;
+    c.dev = {};
     const size_t bytes = (size_t)(shape[0] * shape[1] * shape[2] * shape[3]) * (f16 ? 2 : 4);
-    VX(vx_malloc(&c.dev, bytes));
+    c.dev = device_buffer(bytes);
     memcpy(c.shape, shape, sizeof c.shape);
     c.f16 = f16;
-    VX(vx_memcpy_d2d(c.dev, src, bytes, stream));
+    VX(vx_memcpy_d2d(c.dev.ptr, src, bytes, stream));
 }
 
 void timing_add(std::vector<timing_entry>& rows, timing_entry const& t) {

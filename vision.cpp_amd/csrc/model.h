@@ -3,6 +3,8 @@
 // device work goes through the vx_* C ABI (include/visp_hip_kernels.h).
 #pragma once
 #include <cstdint>
+#include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -43,9 +45,42 @@ struct packed_gemm {
 };
 struct packed_vec { size_t off = SIZE_MAX; int n = 0; }; // f32 vector
 
-struct device_buffer { void* ptr = nullptr; size_t bytes = 0; };
+// Device memory with one owner: freed by the destructor, moved but never copied. Kernel arguments and the weight store's packs
+// keep raw pointers into it.
+struct device_buffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    device_buffer() = default;
+    explicit device_buffer(size_t n); // throws visp::exception
+    device_buffer(device_buffer&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    device_buffer& operator=(device_buffer&& o) noexcept; // frees what this one held first
+    ~device_buffer();
+};
+// a view of device memory another object owns (the weight store's arena)
+struct device_span { void* ptr = nullptr; size_t bytes = 0; };
 
-struct capture_entry { void* dev = nullptr; int64_t shape[4] = {1, 1, 1, 1}; bool f16 = true; };
+// Makes b hold at least `need` bytes. When it is smaller: synchronises the non-null streams of `syncs` (the work that may still
+// use it), frees it, allocates `need` bytes and zero-fills them on `zero_on` if that is not null. Returns whether b moved: a
+// hipGraph captured over it is stale then.
+bool grow(device_buffer& b, size_t need, std::initializer_list<void*> syncs, void* zero_on = nullptr);
+// the device copy of a packed host arena: round_up(size, 256) + 4096 bytes, uploaded on stream, which is then synchronised;
+// copy = false only allocates (the data comes later: a broadcast from the rank that read the file)
+device_buffer upload_arena(std::vector<uint8_t> const& image, void* stream, bool copy = true);
+
+// A captured hipGraph exec with one owner: destroyed by the destructor, moved but never copied.
+struct captured_graph {
+    void* exec = nullptr;
+    captured_graph() = default;
+    captured_graph(captured_graph&& o) noexcept : exec(o.exec) { o.exec = nullptr; }
+    captured_graph& operator=(captured_graph&& o) noexcept; // destroys what this one held first
+    ~captured_graph();
+    explicit operator bool() const { return exec != nullptr; }
+    void launch(void* stream) const;
+};
+// the launches `record` enqueues on stream, captured and instantiated; if it throws, the partial capture is ended and dropped
+captured_graph capture(void* stream, std::function<void()> const& record);
+
+struct capture_entry { device_buffer dev; int64_t shape[4] = {1, 1, 1, 1}; bool f16 = true; };
 
 struct timing_entry { std::string name; float ms = 0; int launches = 0; double flops = 0, bytes = 0; };
 // adds t to the row of its name, or appends it as a new row: a table keeps its rows in first-seen order
@@ -64,7 +99,7 @@ struct model_base {
     explicit model_base(int32_t f) : family(f) {}
     model_base(model_base const&) = delete;
     model_base& operator=(model_base const&) = delete;
-    virtual ~model_base(); // frees the capture buffers on the model's device
+    virtual ~model_base(); // the capture buffers are freed on the model's device
     // a device copy of the contiguous map at src (shape[0] * .. * shape[3] f16 or f32 elements), enqueued on stream, as capture `name`
     void keep_capture(std::string const& name, void const* src, int64_t const (&shape)[4], bool f16, void* stream);
 };

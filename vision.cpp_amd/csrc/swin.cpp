@@ -36,11 +36,6 @@ swin_params swin_detect_params(model_file const& f) { // swin.cpp:293-302
     return p;
 }
 
-swin_model::~swin_model() {
-    vx_free(ws.ptr);
-    vx_free(weight_arena.ptr);
-}
-
 swin_model* swin_load_model(char const* filepath, backend_device const& dev, char const* prefix) {
     model_file file = model_load(filepath, /*header_only=*/false);
     if (file.arch() != "birefnet")
@@ -125,10 +120,7 @@ void swin_load_into(swin_model& mdl, model_file const& file, backend_device cons
         Wt.out_norm_b[l] = pk.vec(e + "norm" + std::to_string(l) + ".bias");
     }
     device_turn turn(dev);
-    model->weight_arena.bytes = round_up<size_t>(ab.data.size(), 256) + 4096;
-    VX(vx_malloc(&model->weight_arena.ptr, model->weight_arena.bytes));
-    VX(vx_memcpy_h2d(model->weight_arena.ptr, ab.data.data(), ab.data.size(), dev.stream));
-    VX(vx_stream_sync(dev.stream));
+    model->weight_arena = upload_arena(ab.data, dev.stream);
 }
 
 void swin_output_dims(swin_model const& m, int w, int h, int dims[4][3]) {
@@ -206,15 +198,7 @@ void swin_encode_pixels(swin_model& m, void const* in8_arg, int B, int w, int h,
     }
     const size_t in_bytes = round_up<size_t>((size_t)B * w * h * 8 * 2 + 4096, 4096);
     const size_t need = 4 * big + in_bytes;
-    if (m.ws.bytes < need) {
-        VX(vx_stream_sync(m.backend->stream));
-        VX(vx_stream_sync(s));
-        vx_free(m.ws.ptr);
-        m.ws = {};
-        VX(vx_malloc(&m.ws.ptr, need));
-        m.ws.bytes = need;
-        VX(vx_memset(m.ws.ptr, 0, need, s)); // GEMM rows are read up to K padded to 64: stale bytes must be finite (pads of W are 0)
-    }
+    grow(m.ws, need, {m.backend->stream, s}, s); // zero-filled: GEMM rows are read up to K padded to 64, stale bytes must be finite (pads of W are 0)
     uint8_t* base = static_cast<uint8_t*>(m.ws.ptr);
     void *x = base, *t1 = base + big, *t2 = base + 2 * big, *t3 = base + 3 * big;
     const void* in8 = in8_arg ? in8_arg : base + 4 * big;
@@ -286,21 +270,17 @@ void swin_encode_batch_host(swin_model& m, uint8_t const* rgb, int B, int w, int
     void* s = m.backend->stream;
     int dims[4][3];
     swin_output_dims(m, w, h, dims);
-    void* in = nullptr;
-    void* dev_out[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto release = [&]() { vx_free(in); for (void* p : dev_out) vx_free(p); };
-    try {
-        VX(vx_malloc(&in, (size_t)B * w * h * 3));
-        VX(vx_memcpy_h2d(in, rgb, (size_t)B * w * h * 3, s));
-        for (int i = 0; i < 4; ++i) VX(vx_malloc(&dev_out[i], (size_t)B * dims[i][0] * dims[i][1] * dims[i][2] * 4));
-        swin_encode_batch_device(m, in, B, w, h, dev_out, s);
-        for (int i = 0; i < 4; ++i) VX(vx_memcpy_d2h(outs[i], dev_out[i], (size_t)B * dims[i][0] * dims[i][1] * dims[i][2] * 4, s));
-        VX(vx_stream_sync(s));
-    } catch (...) {
-        release();
-        throw;
+    device_buffer in((size_t)B * w * h * 3);
+    VX(vx_memcpy_h2d(in.ptr, rgb, (size_t)B * w * h * 3, s));
+    device_buffer out[4];
+    void* dev_out[4];
+    for (int i = 0; i < 4; ++i) {
+        out[i] = device_buffer((size_t)B * dims[i][0] * dims[i][1] * dims[i][2] * 4);
+        dev_out[i] = out[i].ptr;
     }
-    release();
+    swin_encode_batch_device(m, in.ptr, B, w, h, dev_out, s);
+    for (int i = 0; i < 4; ++i) VX(vx_memcpy_d2h(outs[i], dev_out[i], out[i].bytes, s));
+    VX(vx_stream_sync(s));
 }
 
 } // namespace visp

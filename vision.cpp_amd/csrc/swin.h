@@ -46,7 +46,6 @@ struct swin_model : model_base { // the encoder half of vision.h birefnet_model
     // and the default here. Its torch twin (tests/test_birefnet.py:249-255, the original Swin) masks shifted blocks only:
     // mask_shifted_only = true (visp_swin_set_mask_mode(m, 1) / VISP_SWIN_MASK_SHIFTED_ONLY=1 at load) selects that.
     bool mask_shifted_only = false;
-    ~swin_model() override;
 };
 
 swin_model* swin_load_model(char const* filepath, backend_device const& dev, char const* prefix = "bb");

@@ -143,13 +143,8 @@ sam_model* sam_load_model(char const* filepath, backend_device const& dev, int f
     }
 
     device_turn turn(dev);
-    model->weight_arena.bytes = round_up<size_t>(ab.data.size(), 256) + 4096;
-    VX(vx_malloc(&model->weight_arena.ptr, model->weight_arena.bytes));
-    if (with_data) {
-        VX(vx_memcpy_h2d(model->weight_arena.ptr, ab.data.data(), ab.data.size(), dev.stream));
-        VX(vx_stream_sync(dev.stream));
-        sam_weights_ready(*model);
-    }
+    model->weight_arena = upload_arena(ab.data, dev.stream, with_data);
+    if (with_data) sam_weights_ready(*model);
     return model.release();
 }
 
@@ -210,20 +205,10 @@ void sam_set_fp8_mlp(sam_model& m, bool enable) {
             b.fc1_e4m3 = quantise(b.fc1);
             b.fc2_e4m3 = quantise(b.fc2);
         }
-    VX(vx_malloc(&m.fp8_arena.ptr, host.size()));
-    m.fp8_arena.bytes = host.size();
+    m.fp8_arena = device_buffer(host.size());
     VX(vx_memcpy_h2d(m.fp8_arena.ptr, host.data(), host.size(), m.backend->stream));
     VX(vx_stream_sync(m.backend->stream));
     m.fp8_mlp = true;
-}
-
-sam_model::~sam_model() {
-    vx_free(fp8_arena.ptr);
-    vx_free(fp8_ws.ptr);
-    vx_free(ws.ptr);
-    vx_free(embed.ptr);
-    vx_free(dec_ws.ptr);
-    vx_free(weight_arena.ptr);
 }
 
 namespace {
@@ -270,13 +255,7 @@ struct tv_exec {
     // out f16 [M, n_out] = act(A W^T + b) [+ res] with A f16 [M, k_in] quantised to e4m3 rows first (scratch: m.fp8_ws)
     void fp8_linear_launch(fp8_linear const& f, packed_gemm const& g, const void* A, long M, int k_in, void* out, int n_out, int act, const void* res, const char* group) {
         const size_t need = (size_t)M * f.Kp + (size_t)M * 4 + 512;
-        if (m.fp8_ws.bytes < need) {
-            VX(vx_stream_sync(stream));
-            vx_free(m.fp8_ws.ptr);
-            m.fp8_ws = {};
-            VX(vx_malloc(&m.fp8_ws.ptr, need));
-            m.fp8_ws.bytes = need;
-        }
+        grow(m.fp8_ws, need, {stream});
         uint8_t* q = static_cast<uint8_t*>(m.fp8_ws.ptr);
         float* qs = reinterpret_cast<float*>(q + ((size_t)M * f.Kp + 255) / 256 * 256);
         const uint8_t* fa = static_cast<const uint8_t*>(m.fp8_arena.ptr);
@@ -313,15 +292,7 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
     const size_t big = (size_t)B * 256 * 256 * 256 * 2 + 4096;
     const size_t in_bytes = (size_t)B * S * S * 8 * 2 + 4096, pe_bytes = (size_t)B * (S / 2) * (S / 2) * 32 * 2 + 4096;
     const size_t need = 4 * big + in_bytes + pe_bytes;
-    if (m.ws.bytes < need) {
-        VX(vx_stream_sync(m.backend->stream));
-        VX(vx_stream_sync(s));
-        vx_free(m.ws.ptr);
-        m.ws = {};
-        VX(vx_malloc(&m.ws.ptr, need));
-        m.ws.bytes = need;
-        VX(vx_memset(m.ws.ptr, 0, need, s)); // GEMM rows are read up to K padded to 64: stale bytes must be finite (pads of W are 0)
-    }
+    grow(m.ws, need, {m.backend->stream, s}, s); // zero-filled: GEMM rows are read up to K padded to 64, stale bytes must be finite (pads of W are 0)
     uint8_t* base = static_cast<uint8_t*>(m.ws.ptr);
     void* buf[4] = {base, base + big, base + 2 * big, base + 3 * big};
     void* in8 = base + 4 * big;
@@ -411,22 +382,12 @@ void sam_encode_batch_host(sam_model& m, uint8_t const* rgb, int B, float* out) 
     device_turn turn(*m.backend);
     const int S = m.params.img_size, R = m.params.layers[3].resolution;
     const size_t in_bytes = (size_t)B * S * S * 3, out_bytes = (size_t)B * R * R * 256 * 4;
-    void *din = nullptr, *dout = nullptr;
-    VX(vx_malloc(&din, in_bytes));
-    VX(vx_malloc(&dout, out_bytes));
+    device_buffer din(in_bytes), dout(out_bytes);
     void* s = m.backend->stream;
-    try {
-        VX(vx_memcpy_h2d(din, rgb, in_bytes, s));
-        sam_encode_batch_device(m, din, B, dout, s);
-        VX(vx_memcpy_d2h(out, dout, out_bytes, s));
-        VX(vx_stream_sync(s));
-    } catch (...) {
-        vx_free(din);
-        vx_free(dout);
-        throw;
-    }
-    vx_free(din);
-    vx_free(dout);
+    VX(vx_memcpy_h2d(din.ptr, rgb, in_bytes, s));
+    sam_encode_batch_device(m, din.ptr, B, dout.ptr, s);
+    VX(vx_memcpy_d2h(out, dout.ptr, out_bytes, s));
+    VX(vx_stream_sync(s));
 }
 
 void sam_encode(sam_model& m, image_view image) {
@@ -458,10 +419,7 @@ void sam_encode(sam_model& m, image_view image) {
     device_turn turn(*m.backend);
     const int R = m.params.layers[3].resolution;
     const size_t out_bytes = (size_t)R * R * 256 * 4;
-    if (!m.embed.ptr) { // embedding + the staging copy of the input stay with the model
-        VX(vx_malloc(&m.embed.ptr, out_bytes + square.size()));
-        m.embed.bytes = out_bytes + square.size();
-    }
+    if (!m.embed.ptr) m.embed = device_buffer(out_bytes + square.size()); // embedding + the staging copy of the input stay with the model
     void* din = static_cast<uint8_t*>(m.embed.ptr) + out_bytes;
     void* s = m.backend->stream;
     VX(vx_memcpy_h2d(din, square.data(), square.size(), s));
@@ -523,14 +481,7 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
     const size_t o_u1 = take((size_t)4 * Nk * D.up_c1), o_u1n = take((size_t)4 * Nk * D.up_c1), o_u2p = take((size_t)16 * Nk * D.up_c2), o_u2 = take((size_t)16 * Nk * D.up_c2 + 64);
     const size_t o_hy = take((size_t)32 * 64), o_ha = take(tok), o_hb = take(tok), o_mask = take((size_t)16 * Nk * 8), o_iou = take(64);
     const size_t o_scaled = take((size_t)image_size * image_size * 2 /* f32 */), o_out = take(((size_t)m.image_extent[0] * m.image_extent[1] + 1) / 2);
-    if (m.dec_ws.bytes < cursor) {
-        VX(vx_stream_sync(s));
-        vx_free(m.dec_ws.ptr);
-        m.dec_ws = {};
-        VX(vx_malloc(&m.dec_ws.ptr, cursor));
-        m.dec_ws.bytes = cursor;
-        VX(vx_memset(m.dec_ws.ptr, 0, cursor, s));
-    }
+    grow(m.dec_ws, cursor, {s}, s);
     uint8_t* base = static_cast<uint8_t*>(m.dec_ws.ptr);
     auto P = [&](size_t off) { return static_cast<void*>(base + off); };
     void *T = P(o_T), *Q = P(o_Q), *t1 = P(o_t1), *t2 = P(o_t2), *hbuf = P(o_h), *K = P(o_K), *k1 = P(o_k1), *k2 = P(o_k2);

@@ -84,7 +84,6 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // quantised per token on the way in. The decision on accuracy stands (tests/test_fp8_decision.py: mask IoU below the bar); this is the measured form of it.
     bool fp8_mlp = false;
     device_buffer fp8_arena, fp8_ws;
-    ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
 

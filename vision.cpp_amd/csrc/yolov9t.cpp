@@ -167,10 +167,7 @@ yolov9t_model* yolov9t_load_model(char const* filepath, backend_device const& de
     }
 
     device_turn turn(dev);
-    model->weight_arena.bytes = round_up<size_t>(ab.data.size(), 256) + 4096;
-    VX(vx_malloc(&model->weight_arena.ptr, model->weight_arena.bytes));
-    VX(vx_memcpy_h2d(model->weight_arena.ptr, ab.data.data(), ab.data.size(), dev.stream));
-    VX(vx_stream_sync(dev.stream));
+    model->weight_arena = upload_arena(ab.data, dev.stream);
     return model.release();
 }
 
@@ -411,11 +408,6 @@ struct yolo_exec {
     }
 };
 
-void drop_graphs(yolov9t_model& m) {
-    for (auto& g : m.graphs) vx_graph_destroy(g.second);
-    m.graphs.clear();
-}
-
 void check_extent(int B, int S) {
     if (B < 1) throw except("yolov9t: empty batch");
     if (S < 64 || S % 32 != 0 || S > 4096) throw except("yolov9t: input size %d is not a multiple of 32 in [64, 4096]", S);
@@ -430,15 +422,7 @@ yolo_exec make_exec(yolov9t_model& m, int B, int S, void* stream) {
         dry.run_u8(3, 0.0f);
         total = dry.cur;
     }
-    if (total > m.ws.bytes) {
-        VX(vx_stream_sync(m.backend->stream));
-        if (stream) VX(vx_stream_sync(stream));
-        drop_graphs(m);
-        vx_free(m.ws.ptr);
-        m.ws = {};
-        VX(vx_malloc(&m.ws.ptr, total));
-        m.ws.bytes = total;
-    }
+    if (grow(m.ws, total, {m.backend->stream, stream})) m.graphs.clear();
     return yolo_exec(m, stream, B, S, false);
 }
 
@@ -492,10 +476,7 @@ std::vector<yolo_detection> nms_candidates(std::vector<cand>& c, float const* bo
 } // namespace
 
 yolov9t_model::~yolov9t_model() {
-    drop_graphs(*this);
     for (void* e : events) vx_event_destroy(e);
-    vx_free(ws.ptr);
-    vx_free(weight_arena.ptr);
 }
 
 std::vector<yolo_detection> yolov9t_nms(float const* boxes, float const* scores, int A, int nc, yolo_nms_params const& p) {
@@ -565,22 +546,13 @@ std::vector<std::vector<yolo_detection>> run_batch(yolov9t_model& m, yolo_exec& 
     if (eager || it == m.graphs.end()) {
         ex.run_u8(channels, p.conf); // eager; the first call of a shape also warms up every kernel before the capture
         ex.finish_timing();
-        if (!eager) {
-            void* g = nullptr;
-            VX(vx_graph_begin_capture(s));
-            try {
+        if (!eager)
+            m.graphs[gkey] = capture(s, [&] {
                 yolo_exec cap(m, s, batch, S, false); // a fresh pass: the same workspace offsets as ex
                 cap.run_u8(channels, p.conf);
-            } catch (...) {
-                vx_graph_end_capture(s, &g);
-                if (g) vx_graph_destroy(g);
-                throw;
-            }
-            VX(vx_graph_end_capture(s, &g));
-            m.graphs[gkey] = g;
-        }
+            });
     } else {
-        VX(vx_graph_launch(it->second, s));
+        it->second.launch(s);
     }
     VX(vx_event_record(m.events[1], s));
     VX(vx_event_elapsed_ms(m.events[0], m.events[1], &m.last_split_ms[0])); // waits for the launch list

@@ -49,7 +49,7 @@ struct yolov9t_model : model_base {
     device_buffer weight_arena;
     device_buffer ws;
     // (batch * 8 + channels, S, bits of conf) -> captured u8 launch list (one stream, no branches; the threshold is baked into the decode)
-    std::map<std::tuple<int, int, int>, void*> graphs;
+    std::map<std::tuple<int, int, int>, captured_graph> graphs;
     void* events[2] = {nullptr, nullptr};     // around the launch list of a batch call
     float last_split_ms[3] = {0, 0, 0};       // last batch call: launch list on the device (events), candidate readback, host NMS
     bool use_graph = true;
