@@ -404,9 +404,9 @@ VX_API int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[4], 
                                void* stream);
 /* y[i] = a[i] (op) b[i mod b_period]; op 0 add, 1 mul; each operand f16 or f32 */
 VX_API int vx_binary_rows(int op, const void* a, int a_f32, const void* b, int b_f32, int64_t b_period, void* y, int y_f32, int64_t n, void* stream);
-/* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s; f16 */
+/* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s, 3 leaky ReLU x > 0 ? x : s x (ggml_leaky_relu, any slope); f16, 16-byte aligned */
 VX_API int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, void* stream);
-/* op: 0 gelu, 1 relu, 2 x * s, 3 leaky relu max(x, s x) */
+/* y = x, f32 -> f16 (round to nearest even) or f16 -> f32 */
 VX_API int vx_convert(const void* x, int x_f32, void* y, int y_f32, int64_t n, void* stream);
 /* ggml_interpolate(NEAREST) of an NHWC f16 map (ml.cpp:782-788; esrgan.cpp:15) */
 VX_API int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream);

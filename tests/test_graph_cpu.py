@@ -245,3 +245,67 @@ def test_esrgan_lowers_to_the_planar_dense_block_schedule(tmp_path):
     G.esrgan_generate(G.ModelRef(g2), g2.input((3, 40, 56, 1), G.F32, "image"), cfg.scale, cfg.num_blocks)
     with pytest.raises(L.Error, match="Cin = 3 must be a multiple of 8|read before it is computed|f32"):
         g2.allocate()
+
+
+# ---- fusion near-misses: graphs one step off a fusion pattern lower to a correct fallback (numbers: tests/test_gpu_graph_ops.py) ----------
+
+import graph_cases as GC  # noqa: E402
+
+
+@pytest.mark.parametrize("cout", [64, 32])
+def test_conv_relu_add_is_not_a_dconv_epilogue(cout):
+    """conv3x3 to 32 / 64 channels on a 20-wide map (the LDS-ring conv's shape) -> relu -> + another map: the conv keeps the relu in its epilogue,
+    the add is a launch of its own (the conv adds its residuals before its activation)."""
+    g = _g()
+    GC.conv_relu_add(g, np.random.default_rng(1), cout)
+    g.allocate()
+    lines = g.describe().strip().splitlines()
+    assert lines[0].startswith(f"dconv3x3[relu] M=720 N={cout} K=576") and lines[1].startswith(f"add n={720 * cout} period={720 * cout}")
+    assert g.summary()["launches"] == 2
+
+
+def test_residual_unit_whose_skip_lives_as_planes():
+    """dpt::residual_conv on a map that lives as planes (the first conv of the f32 image): not the residual-unit kernel, whose epilogue reads an
+    NHWC skip, and not the planar conv either, which has no loader relu: the map is copied out as NHWC once, the first conv applies the relu in
+    its loader, the second adds the skip."""
+    g = _g()
+    GC.residual_unit_on_planes(g, np.random.default_rng(2))
+    g.allocate()
+    lines = [l.split(" M=")[0] for l in g.describe().strip().splitlines()[:-1]]
+    assert lines == ["image_planes [3, 20, 18, 2]", "dconv3x3(planes)[f32 image]", "planes_to_nhwc [64, 20, 18, 2]", "dconv3x3[relu-in][relu]", "dconv3x3[+res]"]
+
+
+@pytest.mark.parametrize("planar", [False, True])
+def test_relu_into_a_conv_that_is_an_output(planar):
+    """relu -> conv whose result is a graph output: the relu is applied by the conv's loader, on an NHWC map as on the copy of a planar one."""
+    g = _g()
+    GC.relu_into_output_conv(g, np.random.default_rng(3), planar)
+    g.allocate()
+    lines = [l.split(" M=")[0] for l in g.describe().strip().splitlines()[:-1]]
+    if planar:
+        assert lines == ["image_planes [3, 20, 18, 2]", "dconv3x3(planes)[f32 image]", "planes_to_nhwc [64, 20, 18, 2]", "dconv3x3[relu-in]"]
+    else:
+        assert lines == ["dconv3x3[relu-in]"]
+
+
+@pytest.mark.parametrize("slope", [0.1, 1.5, -0.5])
+def test_conv_leaky_relu_other_slopes_stay_launches(slope):
+    """conv3x3 -> leaky_relu with a slope other than the 0.2 the LDS-ring conv's epilogue has: a leaky_relu launch of its own."""
+    g = _g()
+    GC.conv_leaky(g, np.random.default_rng(4), slope)
+    g.allocate()
+    lines = g.describe().strip().splitlines()[:-1]
+    assert len(lines) == 2 and lines[0].startswith("dconv3x3 M=720 N=64 K=576") and lines[1] == f"leaky_relu n={720 * 64}"
+
+
+@pytest.mark.parametrize("scales,fused", [((0.125, 0.125), True), ((0.125, 0.5), False), ((0.5, 0.125), False)])
+def test_encoder_chain_needs_one_attention_scale(scales, fused):
+    """prepare_tokens + two 384 / 1536 layers: with one attention scale the chain is the token-stationary block kernel's (dino_block launches,
+    one q scale for all); with a different scale in a later layer it is lowered node by node, where each attention takes its own."""
+    g = _g()
+    GC.encoder_chain(g, np.random.default_rng(5), scales)
+    g.allocate()
+    d = g.describe()
+    assert (d.count("dino_block[") == 3) == fused and ("dino_block[" in d) == fused
+    if not fused:
+        assert d.count("attention B=2 heads=6 T=5") == 2 and d.count("gemm[qkv heads-major]") == 2

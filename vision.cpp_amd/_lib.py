@@ -415,6 +415,15 @@ def init() -> ctypes.CDLL:
     lib.vx_migan_preprocess.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
     lib.vx_migan_postprocess.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vx_yolo_preprocess.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vx_copy_strided_f16.argtypes = [c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_float, c_void_p]
+    lib.vx_binary_rows.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_void_p]
+    lib.vx_unary_f16.argtypes = [c_int, c_void_p, c_void_p, c_int64, c_float, c_void_p]
+    lib.vx_convert.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]
+    lib.vx_nearest_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_image_planes_f32.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    lib.vx_conv1x1_to1_f32.argtypes = [c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_int64, c_int, c_void_p]
+    lib.vx_im2col_patches_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.vx_esrgan_tiles_in_f32.argtypes = [c_void_p, c_int, c_int, c_int, c_int, POINTER(TileLayout), c_void_p, c_void_p]
     lib.vx_yolo_avgpool2_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.vx_yolo_spp_f16.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]
     lib.vx_yolo_upsample2_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]

@@ -710,9 +710,9 @@ struct lowering {
     // the sole reader of t, if it is not an output
     int sole_consumer(int t) const { return uses[t] == 1 && !g.nodes[t].is_output && consumers[t].size() == 1 ? consumers[t][0] : -1; }
 
-    // epilogue fusion behind a matrix product: [gelu | relu] then [+ residual]
+    // epilogue fusion behind a matrix product: [gelu | relu] then [+ residual]; `res_after_relu` false: an add behind a relu stays a launch
     struct epilogue { int act = 0; int res = -1; int res2 = -1; int last = -1; int scale = -1; };
-    epilogue fuse_epilogue(int t, bool allow_gelu, bool allow_scale = false, bool allow_two = false) {
+    epilogue fuse_epilogue(int t, bool allow_gelu, bool allow_scale = false, bool allow_two = false, bool res_after_relu = true) {
         epilogue e;
         e.last = t;
         int c = sole_consumer(t);
@@ -737,13 +737,10 @@ struct lowering {
             c = sole_consumer(c);
         }
         // up to two residual adds (dpt::residual_conv's skip, then feature_fusion's x0 + ..., depth-anything.cpp:15-33)
-        for (int round = 0; round < 2 && c >= 0 && g.nodes[c].op == gop_add && e.act != 1; ++round) {
+        for (int round = 0; round < 2 && c >= 0 && g.nodes[c].op == gop_add && e.act != 1 && (e.act == 0 || res_after_relu); ++round) {
             graph_node const& a = g.nodes[c];
             const int other = root(a.src[0]) == root(e.last) ? a.src[1] : a.src[0];
-            graph_node const& o = g.nodes[other];
-            bool same = !o.constant && o.dtype == gdt_f16 && root(other) != root(t) && root(other) < t; // already computed when this launch runs
-            for (int i = 0; i < 4; ++i) same = same && o.ne[i] == g.nodes[t].ne[i];
-            if (!(same && g.nodes[root(other)].buffer >= 0)) break;
+            if (!residual_ready(other, t)) break;
             if (round == 1 && !allow_two) break;
             (round == 0 ? e.res : e.res2) = other;
             skip[c] = 1;
@@ -753,6 +750,13 @@ struct lowering {
             c = sole_consumer(c);
         }
         return e;
+    }
+    // `other` can be the residual operand of the epilogue of t's launch: an f16 map of t's shape, in an NHWC buffer before that launch runs
+    bool residual_ready(int other, int t) const {
+        graph_node const& o = g.nodes[other];
+        bool same = !o.constant && o.dtype == gdt_f16 && root(other) != root(t) && root(other) < t; // already computed when this launch runs
+        for (int i = 0; i < 4; ++i) same = same && o.ne[i] == g.nodes[t].ne[i];
+        return same && g.nodes[root(other)].buffer >= 0;
     }
     static const char* act_name(int a) { return a == 1 ? "gelu" : (a == 2 ? "relu" : ""); }
 
@@ -987,6 +991,7 @@ struct lowering {
     bool planar_conv(int t, std::string const& who) {
         graph_node& n = g.nodes[t];
         if (!g.fused_models || !is_conv3x3(n, g.nodes[n.src[1]]) || (n.n_src == 3 && !g.nodes[n.src[2]].constant)) return false;
+        if (relu_on_load[t]) return false; // relu -> conv: the NHWC form applies it in its loader
         const int xs = n.src[0], xr = root(xs);
         graph_node const& x = g.nodes[xr];
         const int cin = (int)g.nodes[xs].ne[0], cout = (int)n.ne[0], H = (int)n.ne[2], W = (int)n.ne[1], B = (int)n.ne[3];
@@ -1187,6 +1192,7 @@ struct lowering {
             graph_node const& a = g.nodes[a1];
             const int other = root(a.src[0]) == c2 ? a.src[1] : a.src[0];
             if (root(other) != root(xs) || (root(a.src[0]) != c2 && root(a.src[1]) != c2)) return false; // the first addend must be the unit's own input
+            if (!residual_ready(other, c2)) return false; // e.g. a map that lives as planes only: the epilogue below could not take it
         }
         skip[r1] = 1;
         g.nodes[r1].alias_of = t;
@@ -1365,8 +1371,7 @@ struct lowering {
         const int xs = n.src[0], wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
         graph_node const& x = g.nodes[xs];
         const int cin = (int)x.ne[0], cout = (int)n.ne[0], H = (int)n.ne[2], W = (int)n.ne[1], B = (int)n.ne[3];
-        epilogue e = fuse_epilogue(t, false, false, true);
-        if (e.act == 2 && e.res >= 0) throw except("graph: internal: relu between a conv and its residual add is not a dconv epilogue");
+        epilogue e = fuse_epilogue(t, false, false, true, false); // the LDS-ring conv adds its residuals before the activation: an add behind a relu is a launch
         vx_dconv_args d;
         memset(&d, 0, sizeof d);
         int d_cin = 0;
@@ -1690,6 +1695,7 @@ struct lowering {
         float eps = g.nodes[chain[0].ln1].fp[0];
         for (auto& L : chain) {
             if (g.nodes[L.ln1].fp[0] != eps) return;
+            if (g.nodes[L.att].fp[0] != g.nodes[chain[0].att].fp[0]) return; // the block launches take one q scale for the whole chain
             for (int t : L.taps) {
                 if (tap_w < 0) { tap_w = g.nodes[t].src[1]; tap_b = g.nodes[t].src[2]; }
                 if (g.nodes[t].src[1] != tap_w || g.nodes[t].src[2] != tap_b || g.nodes[t].fp[0] != eps) return; // one shared final LayerNorm

@@ -15,6 +15,13 @@ __device__ __forceinline__ float gelu_tanh_g(float x) { // ggml_gelu, the form o
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// an f32 result kept as f32 before its f16 rounding: the compiler folds f32 product -> f16 into one fma_mix rounding in some kernels and not
+// in others, so the same data would give different bits on the vector and the scalar path
+__device__ __forceinline__ float f32_rounded(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 inline int blocks_for(int64_t n, int per_block = 256) {
     int64_t b = (n + per_block - 1) / per_block;
     return (int)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b)); // at most 64 blocks per CU, grid-stride beyond
@@ -35,7 +42,7 @@ __global__ __launch_bounds__(256) void copy_strided_kernel(const f16* __restrict
         const long i2 = r % s.ne[2];
         const long i3 = r / s.ne[2];
         f16 v = src[i0 * s.ss[0] + i1 * s.ss[1] + i2 * s.ss[2] + i3 * s.ss[3]];
-        if (scaled) v = (f16)((float)v * scale);
+        if (scaled) v = (f16)f32_rounded((float)v * scale);
         dst[i0 * s.ds[0] + i1 * s.ds[1] + i2 * s.ds[2] + i3 * s.ds[3]] = v;
     }
 }
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(256) void copy_strided8_kernel(const f16* __restric
         f16x8 v = *reinterpret_cast<const f16x8*>(src + i0 * 8 + i1 * s.ss[1] + i2 * s.ss[2] + i3 * s.ss[3]);
         if (scaled) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (f16)((float)v[j] * scale);
+            for (int j = 0; j < 8; ++j) v[j] = (f16)f32_rounded((float)v[j] * scale);
         }
         *reinterpret_cast<f16x8*>(dst + i0 * 8 + i1 * s.ds[1] + i2 * s.ds[2] + i3 * s.ds[3]) = v;
     }
@@ -64,7 +71,7 @@ template <int OP, typename TA, typename TB, typename TY>
 __global__ __launch_bounds__(256) void binary_kernel(const TA* __restrict__ a, const TB* __restrict__ b, long period, TY* __restrict__ y, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float av = ld(a, i), bv = ld(b, period == n ? i : i % period);
-        y[i] = (TY)(OP == 0 ? av + bv : av * bv);
+        y[i] = (TY)f32_rounded(OP == 0 ? av + bv : av * bv);
     }
 }
 // the common case: f16 (op) f16 -> f16, n and period multiples of 8
@@ -77,13 +84,13 @@ __global__ __launch_bounds__(256) void binary8_kernel(const f16* __restrict__ a,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float bv = (float)b[bo + j];
-            o[j] = (f16)(OP == 0 ? (float)av[j] + bv : (float)av[j] * bv);
+            o[j] = (f16)f32_rounded(OP == 0 ? (float)av[j] + bv : (float)av[j] * bv);
         }
         *reinterpret_cast<f16x8*>(y + i * 8) = o;
     }
 }
 
-// 0 gelu, 1 relu, 2 scale
+// 0 gelu, 1 relu, 2 scale, 3 leaky relu (ggml_leaky_relu: x > 0 ? x : s x, for any slope)
 template <int OP>
 __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n, float s) {
     const long n8 = n >> 3;
@@ -92,14 +99,14 @@ __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float f = (float)v[j];
-            v[j] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? fmaxf(f, f * s) : f * s)));
+            v[j] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
         }
         *reinterpret_cast<f16x8*>(y + i * 8) = v;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) { // tail
         const long i = (n8 << 3) + threadIdx.x;
         const float f = (float)x[i];
-        y[i] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? fmaxf(f, f * s) : f * s)));
+        y[i] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
     }
 }
 
@@ -118,8 +125,9 @@ __global__ __launch_bounds__(256) void nearest_kernel(const f16* __restrict__ x,
 }
 
 // An f32 image [pixels][C], C <= 16, as ONE 32-channel f16 plane for the LDS-ring conv: channels 0..C-1 the values rounded to f16, channels C..2C-1 what
-// the rounding dropped (x - f16(x), itself exact in f16 for an image in [0, 1]), the rest zero. The conv's operand repeats its C input columns, so the
-// products see the f32 image (what csrc/esrgan.cpp's tile loader does for the u8 image).
+// the rounding dropped (x - f16(x), exact in f32, then rounded to f16 itself), the rest zero. The conv's operand repeats its C input columns, so the
+// products see the f32 image up to that second rounding: for x in [0, 1] the residue is below 2^-12, where the f16 spacing is at most 2^-23, so
+// |hi + lo - x| <= 2^-24 (about one f32 ulp; 159 of the 256 levels k / 255 are not exact). What csrc/esrgan.cpp's tile loader does for the u8 image.
 __global__ __launch_bounds__(256) void image_planes_kernel(const float* __restrict__ x, f16* __restrict__ y, int C, long n_pix) {
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n_pix; p += (long)gridDim.x * 256) {
         f16 v[32];
