@@ -19,7 +19,8 @@ from visioncpp_amd import synth, vision
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "timing_tables.json"
-PREFIX = {"depthany": "visp_depthany_", "esrgan": "visp_esrgan_", "migan": "visp_migan_", "sam": "visp_sam_", "swin": "visp_swin_"}
+PREFIX = {"depthany": "visp_depthany_", "esrgan": "visp_esrgan_", "migan": "visp_migan_", "sam": "visp_sam_", "swin": "visp_swin_",
+          "yolov9t": "visp_yolov9t_"}
 
 
 def _depthany(dev, tmp, timing):
@@ -62,6 +63,12 @@ def _birefnet(dev, tmp):
     return m, "swin", lambda: m.segment_batch(imgs), "squeeze"
 
 
+def _yolov9t(dev, tmp):
+    m = vision.Yolov9t.load(synth.write_yolov9t_gguf(tmp / "yolov9t.gguf", seed=3), dev)
+    imgs = synth.images(2, 640, 640, seed=9)
+    return m, "yolov9t", lambda: m.detect_batch(imgs), "model.13"
+
+
 CASES = {
     "depthany": (lambda d, t: _depthany(d, t, 1), 1),
     "depthany_split": (lambda d, t: _depthany(d, t, 2), 2),
@@ -70,6 +77,7 @@ CASES = {
     "sam": (_sam, 1),
     "swin": (_swin, 1),
     "birefnet": (_birefnet, 1),
+    "yolov9t": (_yolov9t, 1),
 }
 
 

@@ -97,52 +97,39 @@ bf_block_weights pack_block(packer& pk, arena_builder& ab, std::string const& p)
     return b;
 }
 
-size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
-
 // launches of one pass; with dry = true nothing is launched and only the workspace high-water mark is recorded
-struct bf_exec {
-    birefnet_model& m;
-    void* stream;
-    const uint8_t* wa;
-    bool dry;
-    uint8_t* base = nullptr;
-    size_t cur = 0, peak = 0;
-    timing_marks tm;
+struct bf_exec : model_pass<birefnet_model> {
+    uint8_t* base;
+    workspace_layout layout;
+    size_t peak = 0;
     void* splitk = nullptr; // scratch of split-K convs (f32 partial sums)
     size_t splitk_bytes = 0;
 
+    bf_exec(birefnet_model& mm, void* s, bool d) : model_pass(mm, s, mm.dec_arena.ptr, d), base(static_cast<uint8_t*>(mm.dws.ptr)) {}
     void* take(size_t bytes) {
-        const size_t off = cur;
-        cur = align_up(cur + bytes + 256); // slack: GEMM A rows are read up to K padded to 64
-        peak = std::max(peak, cur);
+        const size_t off = layout.take(bytes, 256); // slack: GEMM A rows are read up to K padded to 64
+        peak = std::max(peak, layout.top);
         return dry ? nullptr : base + off;
     }
-    void mark(const char* name, double flops, double bytes) { if (m.timing && !dry) tm.mark(name, flops, bytes, stream); }
     static void* off16(void* p, size_t elems) { return p ? static_cast<uint8_t*>(p) + elems * 2 : nullptr; } // f16 element offset
-    void capture(const std::string& name, const void* src, int B, int h, int w, int C) { // parity-test hook: contiguous f16 [B, h, w, C]
-        if (m.captures && !dry) m.keep_capture(name, src, {B, h, w, C}, true, stream);
-    }
+    void capture(const std::string& name, const void* src, int B, int h, int w, int C) { keep(name, src, {B, h, w, C}); } // contiguous f16 [B, h, w, C]
 
     void gemm(packed_gemm const& g, const void* A, long M, int lda, void* out, int ldo, int epi, const void* res1, const char* group) {
         if (dry) return;
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = A; a.lda = lda;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = (int)M; a.N = g.N; a.K = g.K; a.n_valid = (g.n_real + 7) / 8 * 8; // 1-, 3-, 27-, 147-column outputs: the pad columns (zero weights) land in the row's slack
+        a.M = (int)M; a.n_valid = round_up(g.n_real, 8); // 1-, 3-, 27-, 147-column outputs: the pad columns (zero weights) land in the row's slack
         a.epi = epi; a.out = out; a.ldo = ldo; a.res1 = res1;
         mark(group, 2.0 * M * g.n_real * g.k_real, (double)M * (g.k_real + g.n_real) * 2);
         VX(vx_gemm_f16(&a, stream));
     }
     void conv(packed_gemm const& g, const void* x, int B, int H, int W, int Cpix, int k, int pad, void* out, int ldo, int epi, const char* group) {
         if (dry) return;
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = x;
         a.conv_kh = a.conv_kw = k; a.conv_stride = 1; a.conv_pad = pad;
         a.conv_H = H; a.conv_W = W; a.conv_Cin = Cpix; a.conv_OH = H; a.conv_OW = W;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = B * H * W; a.N = g.N; a.K = g.K; a.n_valid = (g.n_real + 7) / 8 * 8; // 1-, 3-, 27-, 147-column outputs: the pad columns (zero weights) land in the row's slack
+        a.M = B * H * W; a.n_valid = round_up(g.n_real, 8); // as in gemm
         a.epi = epi; a.out = out; a.ldo = ldo;
         // 3x3 convs over thousands of channels on 32 x 32 maps (squeeze / block4 conv_in: K = 25920 / 29160, 64 workgroups): split-K.
         // The split is chosen from the shape of ONE image, so a result never depends on the batch it was computed in.
@@ -159,7 +146,7 @@ struct bf_exec {
 // basic_decoder_block (birefnet.cpp:144-150) on x [B, h, w, cin] (row stride = cin) -> y [B*h*w, ldy] (first cout channels)
 void decoder_block(bf_exec& ex, bf_block_weights const& bw, const void* x, int B, int h, int w, void* y, int ldy) {
     const long M = (long)B * h * w;
-    const size_t mark0 = ex.cur;
+    const size_t mark0 = ex.layout.top;
     void* a = ex.take((size_t)M * bw.inter * 2);
     ex.conv(bw.conv_in, x, B, h, w, bw.cin, 3, 1, a, bw.inter, VX_EPI_F16_RELU, "dec_conv3x3");
     const int ldc = 5 * bw.planes;
@@ -167,7 +154,7 @@ void decoder_block(bf_exec& ex, bf_block_weights const& bw, const void* x, int B
     for (int j = 0; j < 4; ++j) { // aspp_module_deformable x 4 (birefnet.cpp:110-127)
         bf_deform_weights const& d = bw.aspp[j];
         const int k = d.k, taps = k * k, ldom = (3 * taps + 7) / 8 * 8;
-        const size_t mark1 = ex.cur;
+        const size_t mark1 = ex.layout.top;
         void* om = ex.take((size_t)M * ldom * 2);
         if (k == 1) ex.gemm(d.offmod, a, M, bw.inter, om, ldom, VX_EPI_F16, nullptr, "deform_offsets");
         else ex.conv(d.offmod, a, B, h, w, bw.inter, k, k / 2, om, ldom, VX_EPI_F16, "deform_offsets");
@@ -177,7 +164,7 @@ void decoder_block(bf_exec& ex, bf_block_weights const& bw, const void* x, int B
             VX(vx_bf_deform_cols_f16(a, om, ldom, cols, B, h, w, bw.inter, k, ex.stream));
         }
         ex.gemm(d.conv, cols, M, taps * bw.inter, bf_exec::off16(cat, (size_t)j * bw.planes), ldc, VX_EPI_F16_RELU, nullptr, "deform_gemm");
-        ex.cur = mark1;
+        ex.layout.top = mark1;
     }
     { // global_avg_pool (birefnet.cpp:94-108, 128-133)
         void* mean = ex.take((size_t)std::max(B, 8) * bw.inter * 2 + 4096);
@@ -196,7 +183,7 @@ void decoder_block(bf_exec& ex, bf_block_weights const& bw, const void* x, int B
     void* d = ex.take((size_t)M * bw.inter * 2);
     ex.gemm(bw.conv1, cat, M, ldc, d, bw.inter, VX_EPI_F16_RELU, nullptr, "dec_conv1x1");
     ex.conv(bw.conv_out, d, B, h, w, bw.inter, 3, 1, y, ldy, VX_EPI_F16, "dec_conv3x3");
-    ex.cur = mark0;
+    ex.layout.top = mark0;
 }
 
 } // namespace
@@ -269,8 +256,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
     std::vector<timing_entry> timing;
 
     auto pass = [&](bool dry) -> size_t {
-        bf_exec ex{m, s, static_cast<const uint8_t*>(m.dec_arena.ptr), dry, nullptr, 0, 0, {}};
-        ex.base = static_cast<uint8_t*>(m.dws.ptr);
+        bf_exec ex(m, s, dry);
         long Mi[4];
         void* F[4];
         ex.splitk_bytes = (size_t)8 * B * dims[2][0] * dims[2][1] * 128 * 4; // up to 8 ranges of a stage-2-sized map, 128 columns
@@ -280,7 +266,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
             F[i] = ex.take((size_t)Mi[i] * ccat[i] * 2);
         }
         { // ---- birefnet::encode (birefnet.cpp:43-73)
-            const size_t mark0 = ex.cur;
+            const size_t mark0 = ex.layout.top;
             void* low8 = ex.take((size_t)B * (w / 2) * (h / 2) * 8 * 2);
             void* L[4];
             for (int i = 0; i < 4; ++i) L[i] = ex.take((size_t)Mi[i] / 4 * dims[i][2] * 2);
@@ -294,7 +280,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                 ex.mark("preprocess", 0, (double)B * w * h * 7);
                 VX(vx_bf_preprocess_half(rgb, low8, B, h, w, s));
                 for (int i = 0; i < 4; ++i) so[i] = {L[i], dims[i][2], false};
-                if (m.timing) ex.tm.finish(s, timing, true);
+                ex.finish_timing(timing, true);
                 swin_encode_pixels(m, low8, B, w / 2, h / 2, so, s);
                 if (m.timing)
                     for (timing_entry const& t : m.last_timing) timing_add(timing, t);
@@ -311,7 +297,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                     off += ccat[i];
                 }
             }
-            ex.cur = mark0;
+            ex.layout.top = mark0;
         }
         for (int i = 0; i < 4; ++i) ex.capture("feature_" + std::to_string(i), F[i], B, dims[i][1], dims[i][0], ccat[i]);
         // ---- squeeze block, decoder (birefnet.cpp:170-250)
@@ -337,7 +323,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                 ex.gemm(D.lateral[i - 1], F[st], M, ccat[st], X, bw.cin, VX_EPI_F16_ADD, X, "dec_conv1x1");
             }
             { // ipt block on image_to_patches (birefnet.cpp:152-167, 176-181)
-                const size_t mark1 = ex.cur;
+                const size_t mark1 = ex.layout.top;
                 const int grid = 32 >> i, cp = 3 * grid * grid, c1 = D.ipt[i].conv1.n_real;
                 void* patches = ex.take((size_t)M * cp * 2);
                 void* t = ex.take((size_t)M * c1 * 2);
@@ -347,12 +333,12 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                 }
                 ex.conv(D.ipt[i].conv1, patches, B, lh, lw, cp, 3, 1, t, c1, VX_EPI_F16, "ipt_conv3x3");
                 ex.conv(D.ipt[i].conv_out, t, B, lh, lw, c1, 3, 1, bf_exec::off16(X, (size_t)cc), bw.cin, VX_EPI_F16, "ipt_conv3x3");
-                ex.cur = mark1;
+                ex.layout.top = mark1;
             }
             void* y = ex.take((size_t)M * bw.cout * 2);
             decoder_block(ex, bw, X, B, lh, lw, y, bw.cout);
             if (i < 3) { // gdt attention (birefnet.cpp:183-192)
-                const size_t mark1 = ex.cur;
+                const size_t mark1 = ex.layout.top;
                 const int cg = D.gdt[i].n_real;
                 void* g = ex.take((size_t)M * cg * 2);
                 void* a = ex.take((size_t)M * 8 * 2);
@@ -362,7 +348,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                     ex.mark("dec_gdt_mul", 0, (double)M * bw.cout * 4);
                     VX(vx_bf_mul_sigmoid_f16(y, bw.cout, a, 8, M, bw.cout, s));
                 }
-                ex.cur = mark1;
+                ex.layout.top = mark1;
             }
             ex.capture("p" + std::to_string(4 - i), y, B, lh, lw, bw.cout);
             carried = y;
@@ -389,7 +375,7 @@ void birefnet_compute_batch_device(birefnet_model& m, void const* rgb_dev, int B
                 VX(vx_bf_sigmoid_out_f32(a, 8, static_cast<float*>(mask_dev), M, s));
             }
         }
-        if (m.timing && !dry) { ex.tm.finish(s, timing, true); m.last_timing = timing; }
+        if (ex.finish_timing(timing, true)) m.last_timing = timing;
         return ex.peak;
     };
 

@@ -12,16 +12,6 @@
 
 namespace visp {
 
-#define VX(call)                                        \
-    do {                                                \
-        if (!(call)) throw except("%s", vx_last_error()); \
-    } while (0)
-
-namespace {
-template <typename T>
-T round_up(T x, T m) { return (x + m - 1) / m * m; }
-} // namespace
-
 //
 // params (reference dino.cpp:119-126, depth-anything.cpp:112-128)
 
@@ -354,7 +344,7 @@ void collect_captures(depthany_model& m, depthany_step& s, void* stream) {
 
 } // namespace
 
-depthany_model::depthany_model() : model_base(family_depth_anything) {}
+depthany_model::depthany_model() : model_base(family_depth_anything) { use_graph = false; }
 
 depthany_model* depthany_load_model(char const* filepath, backend_device const& dev, int flags) {
     const bool with_data = !(flags & load_no_upload);
@@ -382,24 +372,12 @@ depthany_model* depthany_load_model(char const* filepath, backend_device const& 
     VX(vx_event_create(&model->fork_event));
     for (void*& e : model->join_event) VX(vx_event_create(&e));
 
-    // The weight arena: one planning pass of the model's graph at its native extent says how many bytes of images the lowering makes of the
-    // weights (per consumer role); the second pass packs them into one allocation in lowering order -- the same order on every rank.
+    // the weight arena, laid out by the model's graph at its native extent
     const int side = P.image_size - P.image_size % P.dino.patch_size;
-    size_t need = 0;
-    {
+    model->weight_arena = build_weight_arena(*model->store, dev, [&] {
         depthany_step::part scratch;
-        std::unique_ptr<graph> plan = build_part(*model, 1, side, side, true, false, scratch);
-        graph_allocate(*plan, nullptr);
-        need = plan->plan_store_bytes;
-    }
-    weight_store& ws = *model->store;
-    ws.arena = device_buffer(need + (1u << 20));
-    {
-        depthany_step::part scratch;
-        std::unique_ptr<graph> warm = build_part(*model, 1, side, side, true, false, scratch);
-        graph_allocate(*warm, &dev);
-    }
-    model->weight_arena = {ws.arena.ptr, round_up<size_t>(ws.arena_used, 256)};
+        return build_part(*model, 1, side, side, true, false, scratch);
+    });
     model->weights_uploaded = with_data;
     return model.release();
 }
@@ -470,7 +448,7 @@ void depthany_compute_batch_device(depthany_model& m, void const* rgb_dev, int b
     const bool own_stream = stream == nullptr;
     void* strm = own_stream ? m.backend->stream : stream;
     const size_t in_bytes = (size_t)batch * h * w * 3, out_bytes = (size_t)batch * h * w * 4;
-    if (m.use_graph && !m.captures && !m.timing) {
+    if (m.replays()) {
         // the captured launch sequence bakes pointers in: it reads and writes the step's own staging buffers
         if (!s.staging.ptr) s.staging = device_buffer(round_up<size_t>(in_bytes, 256) + 2 * round_up<size_t>(out_bytes, 256));
         uint8_t* in = static_cast<uint8_t*>(s.staging.ptr);

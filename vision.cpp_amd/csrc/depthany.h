@@ -45,7 +45,6 @@ struct depthany_model : model_base { // vision.h:339-347 counterpart: {backend, 
     std::vector<std::unique_ptr<depthany_step>> steps; // a few lowered shapes, least recently used first out
     long step_clock = 0;                                // ticks of steps[i]->last_use
     device_buffer host_io;    // device staging of the blocking host entry
-    bool use_graph = false;
     int split = 0; // sub-batches of a step on parallel streams: 0 = automatic (3 from batch 24, 2 from batch 8; $VISP_SPLIT overrides), 1 = none, 2..4
     bool timing_split = false; // with timing: keep the step's sub-batch split (launches timed per stream while the other streams run)
     depthany_pipeline* shard_pipeline = nullptr; // visp_depthany_compute_sharded's overlapped host pipeline for this model (owned, lazily made)

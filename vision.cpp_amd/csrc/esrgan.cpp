@@ -11,15 +11,7 @@
 
 namespace visp {
 
-#define VX(call)                                        \
-    do {                                                \
-        if (!(call)) throw except("%s", vx_last_error()); \
-    } while (0)
-
 namespace {
-
-template <typename T>
-T round_up(T x, T m) { return (x + m - 1) / m * m; }
 
 constexpr int esrgan_default_tile_size = 224; // vision.cpp:208
 constexpr int esrgan_tile_overlap = 16;       // vision.cpp:221
@@ -174,23 +166,11 @@ esrgan_model* esrgan_load_model(char const* filepath, backend_device const& dev,
 
     device_turn turn(dev);
     VX(vx_dconv_prepare());
-    // The weight arena: one planning pass of the generator's graph says how many bytes of operand images the lowering makes of the weights; the second
-    // pass packs them into one allocation in lowering order -- the same order on every rank (what the RCCL broadcast at load time moves).
-    size_t need = 0;
-    {
+    // the weight arena, laid out by the generator's graph
+    model->weight_arena = build_weight_arena(*model->store, dev, [&] {
         int in, out;
-        std::unique_ptr<graph> plan = generator_graph(*model, 1, 32, 32, &in, &out);
-        graph_allocate(*plan, nullptr);
-        need = plan->plan_store_bytes;
-    }
-    weight_store& ws = *model->store;
-    ws.arena = device_buffer(need + (1u << 20));
-    {
-        int in, out;
-        std::unique_ptr<graph> warm = generator_graph(*model, 1, 32, 32, &in, &out);
-        graph_allocate(*warm, &dev);
-    }
-    model->weight_arena = {ws.arena.ptr, round_up<size_t>(ws.arena_used, 256)};
+        return generator_graph(*model, 1, 32, 32, &in, &out);
+    });
     model->weights_uploaded = with_data;
     if (const char* e = getenv("VISP_ESRGAN_TILE_GROUP")) model->tile_group = std::max(1, atoi(e));
     if (const char* e = getenv("VISP_ESRGAN_STREAMS")) model->streams = std::max(1, atoi(e));
@@ -234,18 +214,12 @@ void reserve(esrgan_model& m, int n_tiles_total, int tw, int th) {
     // (up-sampled) map of a group below 2 GiB
     const int addr_cap = (int)std::max<size_t>(1, ((size_t)1 << 30) / (px * s * s * 64));
     const int group = std::min({(n_tiles_total + lanes - 1) / lanes, m.tile_group, addr_cap});
-    struct item { void** p; size_t bytes; };
-    std::vector<item> items = {
-        {&ws.in_u8, img_in_bytes}, {&ws.out_u8, img_out_bytes},
-        {&ws.x0, (size_t)n_tiles_total * px * 3 * 4}, {&ws.tiles_out, (size_t)n_tiles_total * px * s * s * 3 * 4}};
-    size_t total = 0;
-    for (item& it : items) total += round_up<size_t>(it.bytes, 256);
-    grow(ws.arena, total, {m.backend->stream, m.aux_stream});
+    workspace_layout L;
+    const size_t in_u8 = L.take(img_in_bytes), out_u8 = L.take(img_out_bytes), x0 = L.take((size_t)n_tiles_total * px * 3 * 4),
+                 tiles_out = L.take((size_t)n_tiles_total * px * s * s * 3 * 4);
+    grow(ws.arena, L.top, {m.backend->stream, m.aux_stream});
     uint8_t* p = static_cast<uint8_t*>(ws.arena.ptr);
-    for (item& it : items) {
-        *it.p = p;
-        p += round_up<size_t>(it.bytes, 256);
-    }
+    ws.in_u8 = p + in_u8; ws.out_u8 = p + out_u8; ws.x0 = p + x0; ws.tiles_out = p + tiles_out;
     ws.group = group; ws.lanes = lanes; ws.tile_w = tw; ws.tile_h = th; ws.scale = s;
 }
 
@@ -271,13 +245,8 @@ esrgan_step& step_for(esrgan_model& m, int lane, int n, int w, int h) {
     return *cache.back();
 }
 
-struct exec {
-    esrgan_model& m;
-    void* stream;
-    timing_marks tm;
-
-    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
-    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
+struct exec : model_pass<esrgan_model> { // stream: the lane's
+    using model_pass::model_pass;
 
     // esrgan_generate (esrgan.cpp:55-79) on n tiles: rgb f32 [n, h, w, 3] -> rgb f32 [n, h*s, w*s, 3], both in the call's workspace
     void generate(int lane, const float* x0, int n, int w, int h, float* out) {
@@ -327,7 +296,7 @@ void esrgan_compute_batch_device(esrgan_model& m, void const* img_dev, int batch
     tile_layout tiles_out = tile_scale(tiles, m.params.scale);
     const int n_total = batch * tiles.total();
     reserve(m, n_total, tiles.tile_size[0], tiles.tile_size[1]);
-    exec ex{m, s, {}};
+    exec ex(m, s, m.weight_arena.ptr);
     vx_tile_layout tin = to_vx(tiles), tout = to_vx(tiles_out);
     ex.mark("tiles_in", 0, (double)n_total * tiles.tile_size[0] * tiles.tile_size[1] * 15);
     VX(vx_esrgan_tiles_in_f32(static_cast<const uint8_t*>(img_dev), batch, w, h, int(format), &tin, static_cast<float*>(m.ws.x0), s));
@@ -381,7 +350,7 @@ void esrgan_generate_host(esrgan_model& m, float const* rgb, int n, int w, int h
     const size_t px = (size_t)n * w * h;
     void* s = m.backend->stream;
     VX(vx_memcpy_h2d(m.ws.x0, rgb, px * 3 * 4, s));
-    exec ex{m, s, {}};
+    exec ex(m, s, m.weight_arena.ptr);
     run_tiles(m, ex, n, w, h);
     ex.finish_timing();
     const int sc = m.params.scale;

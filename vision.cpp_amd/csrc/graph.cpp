@@ -10,16 +10,7 @@
 #include "visp_util.h"
 
 namespace visp {
-
-#define VX(call)                                          \
-    do {                                                  \
-        if (!(call)) throw except("%s", vx_last_error()); \
-    } while (0)
-
 namespace {
-
-template <typename T>
-T round_up(T x, T m) { return (x + m - 1) / m * m; }
 
 const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_norm", "gelu", "relu", "scale", "add", "mul", "conv_2d",
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
@@ -2224,6 +2215,18 @@ struct lowering {
 };
 
 } // namespace
+
+device_span build_weight_arena(weight_store& ws, backend_device const& dev, std::function<std::unique_ptr<graph>()> const& make_graph) {
+    size_t need = 0;
+    {
+        std::unique_ptr<graph> plan = make_graph();
+        graph_allocate(*plan, nullptr);
+        need = plan->plan_store_bytes;
+    }
+    ws.arena = device_buffer(need + (1u << 20));
+    graph_allocate(*make_graph(), &dev);
+    return {ws.arena.ptr, round_up<size_t>(ws.arena_used, 256)};
+}
 
 void graph_allocate(graph& g, backend_device const* dev) {
     if (g.allocated) return;

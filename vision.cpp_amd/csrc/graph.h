@@ -164,4 +164,9 @@ void graph_bind_external(graph&, int t, void* ptr);
 void* graph_tensor_device_ptr(graph&, int t);                                    // where an input / output tensor lives
 std::string graph_describe(graph const&); // one line per launch, then the arena summary
 
+// The one weight arena of a graph-driven model: a planning pass of make_graph() says how many bytes of images the lowering makes of the
+// weights, the arena gets that plus 1 MiB, and a second graph allocated on dev packs them into it in lowering order (the same order on every
+// rank: what the broadcast at load time moves). Returns the part that holds images.
+device_span build_weight_arena(weight_store&, backend_device const& dev, std::function<std::unique_ptr<graph>()> const& make_graph);
+
 } // namespace visp

@@ -5,7 +5,6 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/visp_hip_kernels.h"
 #include "packer.h"
 #include "visp_util.h"
 
@@ -68,7 +67,7 @@ struct migan_loader {
         if (k != 1 || ci != cin || g.n_real != cout || g.K != cin || g.b != SIZE_MAX)
             throw except("migan: %s.conv2 is %dx%d %d -> %d%s, expected 1x1 %d -> %d without bias", p.c_str(), k, k, ci, g.n_real,
                          g.b != SIZE_MAX ? " with bias" : "", cin, cout);
-        s.pw_w = g.w;
+        s.pw = g;
         if (down) s.down = fir(p + ".downsample.filter.weight", cin);
         const int ores = up ? 2 * res : (down ? res / 2 : res);
         if (up) {
@@ -172,43 +171,34 @@ struct migan_layout {
 
 migan_layout plan(migan_model const& m, int B) {
     migan_layout L;
-    size_t cur = 0;
-    auto bump = [&](size_t bytes) { size_t o = cur; cur = round_up<size_t>(cur + bytes, 256); return o; };
+    workspace_layout ws;
     size_t big = 0;
     for (migan_level const& lv : m.levels) {
         const size_t px = (size_t)B * lv.res * lv.res;
-        L.feat.push_back(bump(px * lv.ch * 2));
+        L.feat.push_back(ws.take(px * lv.ch * 2));
         big = std::max(big, px * lv.ch * 2);
     }
-    for (auto& a : L.act) a = bump(big);
+    for (auto& a : L.act) a = ws.take(big);
     const size_t px = (size_t)B * m.params.resolution * m.params.resolution;
-    for (auto& i : L.img) i = bump(px * 3 * 4);
-    L.in_img = bump(px * 4);
-    L.in_mask = bump(px);
-    L.out_rgba = bump(px * 4);
-    L.in4 = bump(px * 4 * 4);
-    L.total = cur;
+    for (auto& i : L.img) i = ws.take(px * 3 * 4);
+    L.in_img = ws.take(px * 4);
+    L.in_mask = ws.take(px);
+    L.out_rgba = ws.take(px * 4);
+    L.in4 = ws.take(px * 4 * 4);
+    L.total = ws.top;
     return L;
 }
 
-struct migan_exec {
-    migan_model& m;
-    void* stream;
-    const uint8_t* wa;
+struct migan_exec : model_pass<migan_model> {
     uint8_t* ws;
     migan_layout L;
     int B;
-    timing_marks tm;
 
     template <typename T = float>
     const T* w(size_t off) const { return off == SIZE_MAX ? nullptr : reinterpret_cast<const T*>(wa + off); }
     void* at(size_t off) const { return ws + off; }
 
-    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
-    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
-    void capture(std::string const& name, const void* src, int res, int C, bool f16) {
-        if (m.captures) m.keep_capture(name, src, {B, res, res, C}, f16, stream);
-    }
+    void capture(std::string const& name, const void* src, int res, int C, bool f16) { keep(name, src, {B, res, res, C}, f16); }
 
     void dw(migan_sep const& s, const void* x, void* y) {
         const double px = (double)B * s.res * s.res;
@@ -218,12 +208,10 @@ struct migan_exec {
     }
     // 1x1 conv at extent res: out = act(x W^T (+ noise)) (+ res1); act = false: the raw product (before an upsample)
     void pw(migan_sep const& s, int res, const void* x, void* out, bool act, const void* res1) {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(s.pw, wa);
         const long M = (long)B * res * res;
         a.A = x; a.lda = s.cin;
-        a.W = w<uint16_t>(s.pw_w);
-        a.M = (int)M; a.N = s.cout; a.K = s.cin; a.n_valid = s.cout;
+        a.M = (int)M;
         a.epi = act ? VX_EPI_LRELU_AGC : VX_EPI_F16;
         a.out = out; a.ldo = s.cout;
         if (act && s.noise != SIZE_MAX) { a.noise = w(s.noise); a.noise_hw = res * res; }
@@ -285,7 +273,7 @@ migan_exec make_exec(migan_model& m, int B, void* stream) {
         if (grow(m.ws, plan(m, B).total, {m.backend->stream, stream})) m.graphs.clear();
         m.ws_batch = B;
     }
-    return migan_exec{m, stream, static_cast<const uint8_t*>(m.weight_arena.ptr), static_cast<uint8_t*>(m.ws.ptr), plan(m, B), B, {}};
+    return migan_exec{{m, stream, m.weight_arena.ptr}, static_cast<uint8_t*>(m.ws.ptr), plan(m, B), B};
 }
 
 // the u8 -> rgba launch list on the workspace's own input / output buffers
@@ -313,16 +301,10 @@ void migan_compute_batch_device(migan_model& m, void const* img_dev, int img_cha
     const size_t px = (size_t)batch * R * R;
     VX(vx_memcpy_d2d(ex.at(ex.L.in_img), img_dev, px * img_channels, s));
     VX(vx_memcpy_d2d(ex.at(ex.L.in_mask), mask_dev, px, s));
-    const bool eager = !m.use_graph || m.timing || m.captures;
-    const int key = batch * 8 + img_channels;
-    auto it = m.graphs.find(key);
-    if (eager || it == m.graphs.end()) {
-        run_u8(ex, img_channels); // eager; the first call of a shape also warms up every kernel before the capture
+    replay_or_run(m, m.graphs, batch * 8 + img_channels, s, [&] {
+        run_u8(ex, img_channels);
         ex.finish_timing();
-        if (!eager) m.graphs[key] = capture(s, [&] { run_u8(ex, img_channels); });
-    } else {
-        it->second.launch(s);
-    }
+    });
     VX(vx_memcpy_d2d(out_rgba_dev, ex.at(ex.L.out_rgba), px * 4, s));
     if (!stream) VX(vx_stream_sync(s));
 }

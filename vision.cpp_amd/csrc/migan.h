@@ -26,7 +26,7 @@ struct migan_sep {
     int res = 0, cin = 0, cout = 0; // extent of the depthwise conv's input; channels in / out
     size_t dw_w = SIZE_MAX, dw_b = SIZE_MAX; // f16 [9][cin], f32 [cin]
     size_t down = SIZE_MAX;                  // f32 [16][cin] or none
-    size_t pw_w = SIZE_MAX;                  // f16 [cout][cin]: the 1x1 conv (no bias)
+    packed_gemm pw;                          // f16 [cout][cin]: the 1x1 conv (no bias)
     size_t up = SIZE_MAX;                    // f32 [16][cout] or none
     size_t noise = SIZE_MAX;                 // f32 [out res]^2 = noise_const * noise_strength, or none
 };
@@ -45,7 +45,6 @@ struct migan_model : model_base { // vision.h:371-375 counterpart
     device_buffer ws;
     int ws_batch = 0;
     std::map<int, captured_graph> graphs; // batch size -> captured launch list of the u8 -> rgba path (one stream, no branches)
-    bool use_graph = true;
 };
 
 migan_model* migan_load_model(char const* filepath, backend_device const& dev);

@@ -2,19 +2,9 @@
 
 #include <cstring>
 
-#include "../../include/visp_hip_kernels.h"
 #include "visp_util.h"
 
 namespace visp {
-namespace {
-template <typename T>
-T round_up(T x, T m) { return (x + m - 1) / m * m; }
-} // namespace
-
-#define VX(call)                                        \
-    do {                                                \
-        if (!(call)) throw except("%s", vx_last_error()); \
-    } while (0)
 
 //
 // backend (reference src/visp/ml.cpp:59-95)
@@ -102,6 +92,23 @@ captured_graph capture(void* stream, std::function<void()> const& record) {
     }
     VX(vx_graph_end_capture(stream, &g.exec));
     return g;
+}
+
+vx_gemm_args gemm_args(packed_gemm const& g, const uint8_t* arena) {
+    vx_gemm_args a;
+    memset(&a, 0, sizeof a);
+    a.W = arena + g.w;
+    a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(arena + g.b);
+    a.N = g.N;
+    a.K = g.K;
+    a.n_valid = g.n_real;
+    return a;
+}
+
+size_t workspace_layout::take(size_t bytes, size_t slack) {
+    const size_t o = top;
+    top = round_up<size_t>(top + bytes + slack, 256);
+    return o;
 }
 
 //

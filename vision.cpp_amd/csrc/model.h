@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/visp_hip_kernels.h"
+
 namespace visp {
 
 enum class backend_type : int32_t { cpu = 1, gpu = 2, vulkan = 2 | 1 << 8 }; // include/visp/ml.h:32-36
@@ -44,6 +46,14 @@ struct packed_gemm {
     int n_real = 0, k_real = 0; // for FLOP accounting and n_valid
 };
 struct packed_vec { size_t off = SIZE_MAX; int n = 0; }; // f32 vector
+// a zeroed GEMM argument block with what the pack decides: W, bias (null without one), the padded N and K, n_valid = n_real
+vx_gemm_args gemm_args(packed_gemm const& g, const uint8_t* arena);
+
+// offsets of one workspace, bumped: every offset starts 256-aligned; slack: bytes left free behind the block
+struct workspace_layout {
+    size_t top = 0;
+    size_t take(size_t bytes, size_t slack = 0);
+};
 
 // Device memory with one owner: freed by the destructor, moved but never copied. Kernel arguments and the weight store's packs
 // keep raw pointers into it.
@@ -94,6 +104,7 @@ struct model_base {
     int32_t family;
     backend_device const* backend = nullptr;
     bool captures = false, timing = false;
+    bool use_graph = true; // replay captured launch lists (MI-GAN, YOLOv9t, Depth-Anything's device entry)
     std::map<std::string, capture_entry> capture_bufs; // named intermediate maps of the last pass with captures on (the parity tests)
     std::vector<timing_entry> last_timing;             // per kernel group, of the last pass with timing on
     explicit model_base(int32_t f) : family(f) {}
@@ -102,6 +113,7 @@ struct model_base {
     virtual ~model_base(); // the capture buffers are freed on the model's device
     // a device copy of the contiguous map at src (shape[0] * .. * shape[3] f16 or f32 elements), enqueued on stream, as capture `name`
     void keep_capture(std::string const& name, void const* src, int64_t const (&shape)[4], bool f16, void* stream);
+    bool replays() const { return use_graph && !timing && !captures; } // timing and captures need the eager launches
 };
 
 // per-kernel-group timing of one pass on one stream: an event in front of every launch, summed per group name by finish()
@@ -116,6 +128,41 @@ struct timing_marks {
     void finish(void* stream, std::vector<timing_entry>& out, bool append = false);
     void release();
     ~timing_marks() { release(); }
+};
+
+// the launch list `run` enqueues on stream, replayed from graphs[key] when the model replays and holds a capture of key; otherwise run
+// eagerly (the first call of a key also warms every kernel up) and, when the model replays, captured into graphs[key] by a second run
+template <typename Key>
+void replay_or_run(model_base const& m, std::map<Key, captured_graph>& graphs, Key const& key, void* stream, std::function<void()> const& run) {
+    auto it = graphs.find(key);
+    if (m.replays() && it != graphs.end()) return it->second.launch(stream);
+    run();
+    if (m.replays()) graphs[key] = capture(stream, run);
+}
+
+// One pass of a family's launch list on one stream (Model: the family's model). Its timing marks and captures record only when the model
+// asks for them and the pass is not a dry one (a sizing pass: the family launches nothing either).
+template <typename Model>
+struct model_pass {
+    Model& m;
+    void* stream;
+    const uint8_t* wa; // the model's weight arena
+    bool dry = false;
+    timing_marks tm;
+
+    model_pass(Model& model, void* s, const void* arena, bool d = false) : m(model), stream(s), wa(static_cast<const uint8_t*>(arena)), dry(d) {}
+    void mark(const char* group, double flops, double bytes) { if (m.timing && !dry) tm.mark(group, flops, bytes, stream); }
+    void keep(std::string const& name, const void* src, int64_t const (&shape)[4], bool f16 = true) {
+        if (m.captures && !dry) m.keep_capture(name, src, shape, f16, stream);
+    }
+    // the marked groups into out (append: added to its rows); false when the pass does not time
+    bool finish_timing(std::vector<timing_entry>& out, bool append = false) {
+        if (!m.timing || dry) return false;
+        tm.finish(stream, out, append);
+        return true;
+    }
+    void finish_timing() { finish_timing(m.last_timing); }
+    const float* vec(packed_vec const& v) const { return reinterpret_cast<const float*>(wa + v.off); }
 };
 
 enum load_flags { load_default = 0, load_no_upload = 1 };

@@ -13,16 +13,7 @@
 #include "visp_util.h"
 
 namespace visp {
-
-#define VX(call)                                        \
-    do {                                                \
-        if (!(call)) throw except("%s", vx_last_error()); \
-    } while (0)
-
 namespace {
-
-template <typename T>
-T round_up(T x, T m) { return (x + m - 1) / m * m; }
 
 struct arena_builder {
     std::vector<uint8_t> data;

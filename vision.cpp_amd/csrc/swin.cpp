@@ -133,31 +133,20 @@ void swin_output_dims(swin_model const& m, int w, int h, int dims[4][3]) {
 
 namespace {
 
-struct swin_exec {
-    swin_model& m;
-    void* stream;
-    const uint8_t* wa;
-    timing_marks tm;
-
-    const float* fptr(packed_vec const& v) const { return reinterpret_cast<const float*>(wa + v.off); }
-    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
-    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
+struct swin_exec : model_pass<swin_model> {
+    using model_pass::model_pass;
     // win_ws > 0: rows are window tokens of a win_w x win_h map rolled by win_shift; out / res1 are addressed at their pixels
     void gemm(packed_gemm const& g, const void* A, long M, int lda, void* out, int epi, const void* res1, const char* group, int win_ws = 0,
               int win_w = 0, int win_h = 0, int win_shift = 0) {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = A; a.lda = lda;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = (int)M; a.N = g.N; a.K = g.K; a.n_valid = g.n_real;
+        a.M = (int)M;
         a.epi = epi; a.out = out; a.ldo = g.n_real; a.res1 = res1;
         a.win_ws = win_ws; a.win_res = win_w; a.win_res_h = win_h; a.win_shift = win_shift;
         mark(group, 2.0 * M * g.n_real * g.k_real, (double)M * (g.k_real + g.n_real) * 2);
         VX(vx_gemm_f16(&a, stream));
     }
-    void capture(const std::string& name, const void* src, int B, int h, int w, int C) {
-        if (m.captures) m.keep_capture(name, src, {B, h, w, C}, true, stream);
-    }
+    void capture(const std::string& name, const void* src, int B, int h, int w, int C) { keep(name, src, {B, h, w, C}); }
 };
 
 } // namespace
@@ -203,26 +192,24 @@ void swin_encode_pixels(swin_model& m, void const* in8_arg, int B, int w, int h,
     void *x = base, *t1 = base + big, *t2 = base + 2 * big, *t3 = base + 3 * big;
     const void* in8 = in8_arg ? in8_arg : base + 4 * big;
 
-    swin_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}};
+    swin_exec ex(m, s, m.weight_arena.ptr);
     if (!in8_arg) {
         ex.mark("preprocess", 0, (double)B * w * h * 19);
         VX(vx_tv_preprocess(static_cast<const uint8_t*>(rgb_dev), base + 4 * big, (int64_t)B * w * h, s)); // same mean / std as sam (birefnet.cpp:259-270)
     }
     { // patch_embed (nn.cpp:166-180): 4x4 stride-4 conv as implicit GEMM on the 8-channel pixels, then LayerNorm
         packed_gemm const& g = Wt.patch_embed;
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, ex.wa);
         a.A = in8;
         a.conv_kh = a.conv_kw = 4; a.conv_stride = 4; a.conv_pad = 0;
         a.conv_H = h; a.conv_W = w; a.conv_Cin = 8; a.conv_OH = H0; a.conv_OW = W0;
-        a.W = ex.wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(ex.wa + g.b);
-        a.M = B * H0 * W0; a.N = g.N; a.K = g.K; a.n_valid = g.n_real;
+        a.M = B * H0 * W0;
         a.epi = VX_EPI_F16; a.out = Wt.pe_norm ? t1 : x; a.ldo = g.n_real;
         ex.mark("patch_embed", 2.0 * a.M * g.n_real * 48, (double)B * w * h * 16 + (double)a.M * g.n_real * 2);
         VX(vx_gemm_f16(&a, s));
         if (Wt.pe_norm) {
             ex.mark("layernorm", 0, (double)a.M * g.n_real * 4);
-            VX(vx_swin_layernorm_f16(t1, ex.fptr(Wt.pe_norm_w), ex.fptr(Wt.pe_norm_b), x, a.M, g.n_real, 1e-5f, 0, 0, 0, 0, 0, s));
+            VX(vx_swin_layernorm_f16(t1, ex.vec(Wt.pe_norm_w), ex.vec(Wt.pe_norm_b), x, a.M, g.n_real, 1e-5f, 0, 0, 0, 0, 0, s));
         }
     }
     int cw = W0, ch = H0;
@@ -237,7 +224,7 @@ void swin_encode_pixels(swin_model& m, void const* in8_arg, int B, int w, int h,
             const int shift = bi % 2 == 0 ? 0 : ws / 2;
             const bool masked = shift > 0 || !m.mask_shifted_only; // swin.cpp:226-237: the reference masks every block
             ex.mark("layernorm", 0, (double)(T + rows) * C * 2);
-            VX(vx_swin_layernorm_f16(x, ex.fptr(b.norm1_w), ex.fptr(b.norm1_b), t1, rows, C, 1e-5f, ch, cw, ws, shift, 0, s));
+            VX(vx_swin_layernorm_f16(x, ex.vec(b.norm1_w), ex.vec(b.norm1_b), t1, rows, C, 1e-5f, ch, cw, ws, shift, 0, s));
             ex.gemm(b.qkv, t1, rows, C, t2, VX_EPI_F16, nullptr, "gemm_qkv");
             ex.mark("window_attention", 4.0 * rows * N * C, (double)rows * C * 8);
             VX(vx_window_attention_masked_f16(t2, ex.wa + b.bias.off, t1, (int)(rows / N), N, L.n_heads, masked ? nwx : 0, masked ? nwy : 0, s));
@@ -245,16 +232,16 @@ void swin_encode_pixels(swin_model& m, void const* in8_arg, int B, int w, int h,
             // (vx_swin_window_reverse_add_f16 is the unfused form, kept for the kernel-level parity test)
             ex.gemm(b.proj, t1, rows, C, t3, VX_EPI_F16_ADD, x, "gemm_proj", ws, cw, ch, shift);
             ex.mark("layernorm", 0, (double)T * C * 4);
-            VX(vx_swin_layernorm_f16(t3, ex.fptr(b.norm2_w), ex.fptr(b.norm2_b), t1, T, C, 1e-5f, 0, 0, 0, 0, 0, s));
+            VX(vx_swin_layernorm_f16(t3, ex.vec(b.norm2_w), ex.vec(b.norm2_b), t1, T, C, 1e-5f, 0, 0, 0, 0, 0, s));
             ex.gemm(b.fc1, t1, T, C, t2, VX_EPI_F16_GELU, nullptr, "gemm_fc1");
             ex.gemm(b.fc2, t2, T, b.fc1.n_real, x, VX_EPI_F16_ADD, t3, "gemm_fc2");
             ex.capture("block_" + std::to_string(l) + "_" + std::to_string(bi), x, B, ch, cw, C);
         }
         ex.mark("layernorm", 0, (double)T * C * 6);
-        VX(vx_swin_layernorm_strided_f16(x, ex.fptr(Wt.out_norm_w[l]), ex.fptr(Wt.out_norm_b[l]), outs[l].ptr, T, C, 1e-5f, outs[l].ld, outs[l].f32 ? 1 : 0, s)); // swin.cpp:255-258
+        VX(vx_swin_layernorm_strided_f16(x, ex.vec(Wt.out_norm_w[l]), ex.vec(Wt.out_norm_b[l]), outs[l].ptr, T, C, 1e-5f, outs[l].ld, outs[l].f32 ? 1 : 0, s)); // swin.cpp:255-258
         if (l < 3) { // patch_merging (swin.cpp:140-161)
             ex.mark("merge_layernorm", 0, (double)T * C * 4);
-            VX(vx_swin_merge_layernorm_f16(x, ex.fptr(Wt.merge_norm_w[l]), ex.fptr(Wt.merge_norm_b[l]), t1, B, ch, cw, C, 1e-5f, s));
+            VX(vx_swin_merge_layernorm_f16(x, ex.vec(Wt.merge_norm_w[l]), ex.vec(Wt.merge_norm_b[l]), t1, B, ch, cw, C, 1e-5f, s));
             ex.gemm(Wt.merge_reduction[l], t1, T / 4, 4 * C, t2, VX_EPI_F16, nullptr, "gemm_reduction");
             std::swap(x, t2);
             cw /= 2; ch /= 2;

@@ -213,25 +213,16 @@ void sam_set_fp8_mlp(sam_model& m, bool enable) {
 
 namespace {
 
-struct tv_exec {
-    sam_model& m;
-    void* stream;
-    const uint8_t* wa;
-    timing_marks tm;
+struct tv_exec : model_pass<sam_model> {
+    using model_pass::model_pass;
     int gemm_variant = 0; // vx_gemm_args.stages: tile-shape selector of the plain GEMM (0 = its default)
-
-    const float* fptr(packed_vec const& v) const { return reinterpret_cast<const float*>(wa + v.off); }
-    void mark(const char* name, double flops, double bytes) { if (m.timing) tm.mark(name, flops, bytes, stream); }
-    void finish_timing() { if (m.timing) tm.finish(stream, m.last_timing); }
 
     // C[M, N] = A[M, lda] * W^T (+bias) with the epilogues of the GEMM family
     void gemm(packed_gemm const& g, const void* A, long M, int lda, void* out, int epi, const void* res1, const char* group,
               bool post_gelu = false, int win_ws = 0, int win_res = 0) {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = A; a.lda = lda;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = (int)M; a.N = g.N; a.K = g.K; a.n_valid = g.n_real;
+        a.M = (int)M;
         a.epi = epi; a.out = out; a.ldo = g.n_real; a.res1 = res1;
         a.stages = gemm_variant;
         a.post_gelu = post_gelu; a.win_ws = win_ws; a.win_res = win_res;
@@ -241,13 +232,11 @@ struct tv_exec {
     // k x k conv as implicit GEMM on NHWC f16
     void conv(packed_gemm const& g, const void* x, int B, int H, int W, int Cpix, int k, int stride, int pad, void* out, int epi, const char* group) {
         const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = x;
         a.conv_kh = a.conv_kw = k; a.conv_stride = stride; a.conv_pad = pad;
         a.conv_H = H; a.conv_W = W; a.conv_Cin = Cpix; a.conv_OH = OH; a.conv_OW = OW;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = B * OH * OW; a.N = g.N; a.K = g.K; a.n_valid = g.n_real;
+        a.M = B * OH * OW;
         a.epi = epi; a.out = out; a.ldo = g.n_real;
         mark(group, 2.0 * a.M * g.n_real * g.k_real, (double)B * H * W * Cpix * 2 + (double)a.M * g.n_real * 2);
         VX(vx_gemm_f16(&a, stream));
@@ -264,14 +253,12 @@ struct tv_exec {
         vx_gemm_fp8_args a;
         memset(&a, 0, sizeof a);
         a.A = q; a.a_scale = qs; a.W = fa + f.w; a.w_scale = reinterpret_cast<const float*>(fa + f.s);
-        a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
+        a.bias = gemm_args(g, wa).bias;
         a.M = (int)M; a.N = f.N; a.Kp = f.Kp; a.n_valid = n_out; a.out = out; a.ldo = n_out; a.act = act; a.res = res;
         mark(group, 2.0 * M * g.n_real * g.k_real, (double)M * (g.k_real + 2.0 * g.n_real));
         VX(vx_gemm_fp8(&a, stream));
     }
-    void capture(const char* name, const void* src, int B, int res, int C) {
-        if (m.captures) m.keep_capture(name, src, {B, res, res, C}, true, stream);
-    }
+    void capture(const char* name, const void* src, int B, int res, int C) { keep(name, src, {B, res, res, C}); }
     void dw(packed_dw const& d, const void* x, void* y, int B, int H, int W, int stride, bool gelu, const char* group) {
         mark(group, 2.0 * B * (H / stride) * (W / stride) * 9 * d.C, (double)B * H * W * d.C * 2 * (1.0 + 1.0 / (stride * stride)));
         VX(vx_dwconv3x3_f16(x, wa + d.w, reinterpret_cast<const float*>(wa + d.b), y, B, H, W, d.C, stride, gelu, stream));
@@ -298,7 +285,7 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
     void* in8 = base + 4 * big;
     void* pe = base + 4 * big + in_bytes;
 
-    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}};
+    tv_exec ex(m, s, m.weight_arena.ptr);
     if (const char* e = getenv("VISP_TV_GEMM_VARIANT")) ex.gemm_variant = atoi(e);
     const bool fuse_mbconv = !getenv("VISP_TV_NO_FUSED_MBCONV");
     ex.mark("preprocess", 0, (double)B * S * S * 19);
@@ -343,7 +330,7 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
         const long T = (long)B * res * res, rows = (long)B * nw * nw * N;
         for (tv_block_weights const& b : Wt.blocks[l]) { // tiny_vit_block (mobile-sam.cpp:133-160)
             ex.mark("layernorm", 0, (double)(T + rows) * C * 2);
-            VX(vx_layernorm_f16(x, ex.fptr(b.attn_ln_w), ex.fptr(b.attn_ln_b), t1, rows, C, 1e-5f, res, ws, 0, s));
+            VX(vx_layernorm_f16(x, ex.vec(b.attn_ln_w), ex.vec(b.attn_ln_b), t1, rows, C, 1e-5f, res, ws, 0, s));
             ex.gemm(b.qkv, t1, rows, C, t2, VX_EPI_F16, nullptr, "gemm_qkv");
             ex.mark("window_attention", 4.0 * rows * N * C, (double)rows * C * 8);
             VX(vx_window_attention_f16(t2, ex.wa + b.bias.off, t1, (int)(rows / N), N, L.num_heads, s));
@@ -351,7 +338,7 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
             ex.gemm(b.proj, t1, rows, C, t2, VX_EPI_F16_ADD, x, "gemm_proj", false, ws, res);
             ex.dw(b.local_conv, t2, t3, B, res, res, 1, false, "depthwise");
             ex.mark("layernorm", 0, (double)T * C * 4);
-            VX(vx_layernorm_f16(t3, ex.fptr(b.mlp_ln_w), ex.fptr(b.mlp_ln_b), t1, T, C, 1e-5f, 0, 0, 0, s));
+            VX(vx_layernorm_f16(t3, ex.vec(b.mlp_ln_w), ex.vec(b.mlp_ln_b), t1, T, C, 1e-5f, 0, 0, 0, s));
             if (m.fp8_mlp) { // opt-in: both products on the e4m3 matrix instruction, activations quantised per token in between
                 const int hid = b.fc1.n_real;
                 ex.fp8_linear_launch(b.fc1_e4m3, b.fc1, t1, T, C, t2, hid, 1, nullptr, "gemm_fc1_e4m3");
@@ -369,10 +356,10 @@ void sam_encode_batch_device(sam_model& m, void const* rgb_dev, int B, void* out
     ex.gemm(Wt.neck0, x, T, C, t1, VX_EPI_F16, nullptr, "neck");
     const int NC = Wt.neck0.n_real;
     ex.mark("layernorm", 0, (double)T * NC * 4);
-    VX(vx_layernorm_f16(t1, ex.fptr(Wt.neck1_w), ex.fptr(Wt.neck1_b), t2, T, NC, 1e-5f, 0, 0, 0, s));
+    VX(vx_layernorm_f16(t1, ex.vec(Wt.neck1_w), ex.vec(Wt.neck1_b), t2, T, NC, 1e-5f, 0, 0, 0, s));
     ex.conv(Wt.neck2, t2, B, res, res, NC, 3, 1, 1, t1, VX_EPI_F16, "neck");
     ex.mark("layernorm", 0, (double)T * NC * 6);
-    VX(vx_layernorm_f16(t1, ex.fptr(Wt.neck3_w), ex.fptr(Wt.neck3_b), out_dev, T, Wt.neck2.n_real, 1e-5f, 0, 0, 1, s));
+    VX(vx_layernorm_f16(t1, ex.vec(Wt.neck3_w), ex.vec(Wt.neck3_b), out_dev, T, Wt.neck2.n_real, 1e-5f, 0, 0, 1, s));
     ex.finish_timing();
     if (!stream) VX(vx_stream_sync(s));
 }
@@ -474,21 +461,21 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
 
     // ---- scratch (f16 elements)
     const size_t big = (size_t)Nk * dim, tok = (size_t)8 * dim;
-    size_t cursor = 0;
-    auto take = [&](size_t elems) { size_t o = cursor; cursor += round_up<size_t>(elems * 2 + 256, 256); return o; };
+    workspace_layout layout;
+    auto take = [&](size_t elems) { return layout.take(elems * 2, 256); };
     const size_t o_T = take(tok), o_Q = take(tok), o_t1 = take(tok), o_t2 = take(tok), o_h = take((size_t)8 * 2048 + 64);
     const size_t o_K = take(big), o_k1 = take(big), o_k2 = take(big), o_pq = take(big), o_pk = take(big), o_pv = take(big), o_ao = take(big);
     const size_t o_u1 = take((size_t)4 * Nk * D.up_c1), o_u1n = take((size_t)4 * Nk * D.up_c1), o_u2p = take((size_t)16 * Nk * D.up_c2), o_u2 = take((size_t)16 * Nk * D.up_c2 + 64);
     const size_t o_hy = take((size_t)32 * 64), o_ha = take(tok), o_hb = take(tok), o_mask = take((size_t)16 * Nk * 8), o_iou = take(64);
     const size_t o_scaled = take((size_t)image_size * image_size * 2 /* f32 */), o_out = take(((size_t)m.image_extent[0] * m.image_extent[1] + 1) / 2);
-    grow(m.dec_ws, cursor, {s}, s);
+    grow(m.dec_ws, layout.top, {s}, s);
     uint8_t* base = static_cast<uint8_t*>(m.dec_ws.ptr);
     auto P = [&](size_t off) { return static_cast<void*>(base + off); };
     void *T = P(o_T), *Q = P(o_Q), *t1 = P(o_t1), *t2 = P(o_t2), *hbuf = P(o_h), *K = P(o_K), *k1 = P(o_k1), *k2 = P(o_k2);
     void *pq = P(o_pq), *pk = P(o_pk), *pv = P(o_pv), *ao = P(o_ao), *u1 = P(o_u1), *u1n = P(o_u1n), *u2p = P(o_u2p), *u2 = P(o_u2);
     void *hy = P(o_hy), *ha = P(o_ha), *hb = P(o_hb), *masks_d = P(o_mask), *iou_d = P(o_iou), *scaled = P(o_scaled), *mask_u8 = P(o_out);
 
-    tv_exec ex{m, s, static_cast<const uint8_t*>(m.weight_arena.ptr), {}};
+    tv_exec ex(m, s, m.weight_arena.ptr);
     const bool timing = m.timing;
     m.timing = false; // the per-group table belongs to the encoder
     const uint8_t* wa = ex.wa;
@@ -502,7 +489,7 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
         ex.gemm(g, A, M, g.k_real, out, epi, res1, "decoder");
     };
     auto norm = [&](packed_vec const& w, packed_vec const& b, const void* x, void* y, long rows, int C) {
-        VX(vx_layernorm_f16(x, ex.fptr(w), ex.fptr(b), y, rows, C, 1e-5f, 0, 0, 0, s));
+        VX(vx_layernorm_f16(x, ex.vec(w), ex.vec(b), y, rows, C, 1e-5f, 0, 0, 0, s));
     };
     // decoder_attention (mobile-sam.cpp:306-320); out = [res1 +] out_proj(attention(q_proj(q), k_proj(k), v_proj(v)))
     auto attention = [&](sam_attn_weights const& w, const void* q, int Nq, const void* k, const void* v, int Nkv, void* out, const void* res1) {
@@ -541,11 +528,9 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
 
     // upscale_outputs (mobile-sam.cpp:396-404): convT k2 s2 -> LayerNorm -> GELU -> convT k2 s2 -> GELU
     auto conv_transpose = [&](packed_gemm const& g, const void* x, int hw, int cin, int cout, void* out) {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(g, wa);
         a.A = x; a.lda = cin;
-        a.W = wa + g.w; a.bias = g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b);
-        a.M = hw * hw; a.N = g.N; a.K = g.K; a.n_valid = g.n_real;
+        a.M = hw * hw;
         a.epi = VX_EPI_PIXSHUF; a.out = out; a.ldo = cout;
         a.ps_s = 2; a.ps_Cout = cout; a.ps_H = hw; a.ps_W = hw;
         VX(vx_gemm_f16(&a, s));
@@ -563,13 +548,14 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
         a.A = A; a.lda = lda; a.W = W; a.bias = bias; a.M = M; a.N = N; a.K = Kp; a.n_valid = n_valid; a.epi = epi; a.out = out; a.ldo = ldo;
         VX(vx_gemm_f16(&a, s));
     };
-    auto bias_of = [&](packed_gemm const& g) { return g.b == SIZE_MAX ? nullptr : reinterpret_cast<const float*>(wa + g.b); };
     for (int i = 0; i < 4; ++i) {
         const uint8_t* tok_i = static_cast<const uint8_t*>(Q) + (size_t)(1 + i) * dim * 2;
         linear(D.hyper[i][0], tok_i, 1, ha, VX_EPI_F16_RELU);
         linear(D.hyper[i][1], ha, 1, hb, VX_EPI_F16_RELU);
-        packed_gemm const& g = D.hyper[i][2];
-        raw_gemm(hb, 1, g.k_real, wa + g.w, bias_of(g), g.N, g.K, g.n_real, static_cast<uint8_t*>(hy) + (size_t)i * 64 * 2, 64, VX_EPI_F16);
+        vx_gemm_args a = gemm_args(D.hyper[i][2], wa);
+        a.A = hb; a.lda = D.hyper[i][2].k_real; a.M = 1;
+        a.epi = VX_EPI_F16; a.out = static_cast<uint8_t*>(hy) + (size_t)i * 64 * 2; a.ldo = 64;
+        VX(vx_gemm_f16(&a, s));
     }
     // masks[i][pixel] = <upscaled[pixel], hyper_in[i]> (mobile-sam.cpp:472-473): M = 16 Nk pixels, K = up_c2, 4 of 8 stored columns real
     raw_gemm(u2, 16 * Nk, D.up_c2, hy, nullptr, 32, 64, 8, masks_d, 8, VX_EPI_F16);

@@ -33,6 +33,14 @@ inline exception except(const char* fmt, ...) {
 constexpr int32_t div_ceil(int32_t a, int32_t b) { return (a + b - 1) / b; }
 constexpr int64_t div_ceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
 constexpr int32_t next_multiple(int32_t x, int32_t m) { return div_ceil(x, m) * m; }
+template <typename T>
+constexpr T round_up(T x, T m) { return (x + m - 1) / m * m; }
+
+// a vx_* call (include/visp_hip_kernels.h) that failed throws its message
+#define VX(call)                                          \
+    do {                                                  \
+        if (!(call)) throw ::visp::except("%s", vx_last_error()); \
+    } while (0)
 
 } // namespace visp
 

@@ -9,7 +9,6 @@
 #include <numeric>
 #include <string>
 
-#include "../../include/visp_hip_kernels.h"
 #include "packer.h"
 #include "visp_util.h"
 
@@ -184,23 +183,17 @@ struct fmap { // an NHWC f16 map, possibly a channel slice of a wider buffer
 
 // One pass over the launch list for a (batch, S). The same code lays out the workspace (dry: bump offsets only, nothing launched)
 // and enqueues the launches, so the layout cannot drift from the schedule.
-struct yolo_exec {
-    yolov9t_model& m;
-    void* stream;
-    const uint8_t* wa;
+struct yolo_exec : model_pass<yolov9t_model> {
     uint8_t* ws;
-    bool dry;
     int B, S, A, nc;
-    size_t cur = 0;
-    timing_marks tm;
+    workspace_layout layout;
     // fixed buffers (laid out first, in this order)
     uint8_t *in_u8 = nullptr, *in_f32 = nullptr, *boxes = nullptr, *scores = nullptr, *cand_count = nullptr, *cand_idx = nullptr, *cand_score = nullptr,
             *cap_tmp = nullptr;
     fmap in8, raw[3];
 
     yolo_exec(yolov9t_model& mm, void* s, int b, int size, bool d)
-        : m(mm), stream(s), wa(static_cast<const uint8_t*>(mm.weight_arena.ptr)), ws(static_cast<uint8_t*>(mm.ws.ptr)), dry(d), B(b), S(size),
-          A(yolov9t_anchors(size)), nc(mm.num_classes) {
+        : model_pass(mm, s, mm.weight_arena.ptr, d), ws(static_cast<uint8_t*>(mm.ws.ptr)), B(b), S(size), A(yolov9t_anchors(size)), nc(mm.num_classes) {
         in_u8 = alloc((size_t)B * S * S * 4);
         in_f32 = alloc((size_t)B * S * S * 12);
         boxes = alloc((size_t)B * A * 16);
@@ -212,20 +205,9 @@ struct yolo_exec {
         in8 = map(S, S, 8);
     }
 
-    uint8_t* alloc(size_t bytes) {
-        const size_t o = cur;
-        cur = round_up<size_t>(cur + bytes, 256);
-        return reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ws) + o);
-    }
+    uint8_t* alloc(size_t bytes) { return reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ws) + layout.take(bytes)); }
     fmap map(int H, int W, int C) { return fmap{alloc((size_t)B * H * W * C * 2), C, H, W, C}; }
-    const void* w(size_t off) const { return wa + off; }
 
-    void mark(const char* name, double flops, double bytes) {
-        if (!dry && m.timing) tm.mark(name, flops, bytes, stream);
-    }
-    void finish_timing() {
-        if (!dry && m.timing) tm.finish(stream, m.last_timing);
-    }
     void capture(std::string const& name, fmap const& v) {
         if (dry || !m.captures) return;
         const void* src = v.p;
@@ -235,11 +217,9 @@ struct yolo_exec {
             VX(vx_copy_strided_f16(v.p, cap_tmp, ne, ss, ds, 1.0f, stream));
             src = cap_tmp;
         }
-        m.keep_capture(name, src, {B, v.H, v.W, v.C}, true, stream);
+        keep(name, src, {B, v.H, v.W, v.C});
     }
-    void capture_f32(std::string const& name, const void* src, int64_t d1, int64_t d2) {
-        if (!dry && m.captures) m.keep_capture(name, src, {B, d1, d2, 1}, false, stream);
-    }
+    void capture_f32(std::string const& name, const void* src, int64_t d1, int64_t d2) { keep(name, src, {B, d1, d2, 1}, false); }
 
     // one conv on the GEMM family: out = act(conv(in) + bias) [+ res]; act = SiLU (Conv) or none (the head's plain 1x1)
     void conv(std::string const& key, fmap const& in, fmap const& out, int stride, const fmap* res, bool act, const char* group) {
@@ -254,17 +234,14 @@ struct yolo_exec {
         mark(group, 2.0 * M * c.cout * c.k * c.k * c.cin_real,
              ((double)B * in.H * in.W * c.cin + M * c.cout * (res ? 2 : 1)) * 2 + (double)c.cout * c.k * c.k * c.cin * 2);
         if (dry) return;
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
+        vx_gemm_args a = gemm_args(c.g, wa);
         a.A = in.p;
         a.conv_kh = a.conv_kw = c.k;
         a.conv_stride = stride;
         a.conv_pad = pad;
         a.conv_H = in.H; a.conv_W = in.W; a.conv_Cin = c.cin; a.conv_OH = OH; a.conv_OW = OW;
         a.conv_pix = in.pix;
-        a.W = w(c.g.w);
-        a.bias = static_cast<const float*>(w(c.g.b));
-        a.M = (int)M; a.N = c.g.N; a.K = c.g.K; a.n_valid = c.cout;
+        a.M = (int)M;
         a.epi = act ? VX_EPI_SILU : VX_EPI_F16;
         a.out = out.p; a.ldo = out.pix;
         if (res) { a.res1 = res->p; a.ld_res1 = res->pix; }
@@ -420,7 +397,7 @@ yolo_exec make_exec(yolov9t_model& m, int B, int S, void* stream) {
     {
         yolo_exec dry(m, stream, B, S, true);
         dry.run_u8(3, 0.0f);
-        total = dry.cur;
+        total = dry.layout.top;
     }
     if (grow(m.ws, total, {m.backend->stream, stream})) m.graphs.clear();
     return yolo_exec(m, stream, B, S, false);
@@ -538,22 +515,14 @@ std::vector<std::vector<yolo_detection>> run_batch(yolov9t_model& m, yolo_exec& 
     for (void*& e : m.events)
         if (!e) VX(vx_event_create(&e));
     VX(vx_event_record(m.events[0], s));
-    const bool eager = !m.use_graph || m.timing || m.captures;
     uint32_t conf_bits;
     memcpy(&conf_bits, &p.conf, 4);
     const auto gkey = std::make_tuple(batch * 8 + channels, S, (int)conf_bits); // the decode's threshold is part of the launch list
-    auto it = m.graphs.find(gkey);
-    if (eager || it == m.graphs.end()) {
-        ex.run_u8(channels, p.conf); // eager; the first call of a shape also warms up every kernel before the capture
-        ex.finish_timing();
-        if (!eager)
-            m.graphs[gkey] = capture(s, [&] {
-                yolo_exec cap(m, s, batch, S, false); // a fresh pass: the same workspace offsets as ex
-                cap.run_u8(channels, p.conf);
-            });
-    } else {
-        it->second.launch(s);
-    }
+    replay_or_run(m, m.graphs, gkey, s, [&] {
+        yolo_exec pass(m, s, batch, S, false); // a fresh pass: the same workspace offsets as ex
+        pass.run_u8(channels, p.conf);
+        pass.finish_timing();
+    });
     VX(vx_event_record(m.events[1], s));
     VX(vx_event_elapsed_ms(m.events[0], m.events[1], &m.last_split_ms[0])); // waits for the launch list
     const clock_type::time_point t_read = clock_type::now();

@@ -52,7 +52,6 @@ struct yolov9t_model : model_base {
     std::map<std::tuple<int, int, int>, captured_graph> graphs;
     void* events[2] = {nullptr, nullptr};     // around the launch list of a batch call
     float last_split_ms[3] = {0, 0, 0};       // last batch call: launch list on the device (events), candidate readback, host NMS
-    bool use_graph = true;
     ~yolov9t_model() override;
 };
 
