@@ -153,7 +153,7 @@ VX_API int vx_conv3x3_f16(const vx_gemm_args* args, void* stream);
  *   mutually exclusive with res1, res2 still applies afterwards.
  * up2: the source is [B, H/2, W/2, 32] per plane and is nearest-upsampled on the fly (esrgan.cpp:13-19).
  * w: packed by the host as [cin/32][9 taps][cout][32] f16 with the four 16-byte groups of every (tap, n) row
- *    stored at position g ^ ((n >> 2) & 3)  (see packer::conv in csrc/esrgan.cpp).
+ *    stored at position g ^ ((n >> 2) & 3)  (see pack_dconv in csrc/graph.cpp).
  * VX_DC_RGB_F32: cout = 32 (3 real), out = f32 [B, H, W, 3], no activation / residuals.
  * VX_DC_HEAD_F32: cout = 32, out = f32 [B, H, W] = head_scale * relu(sum_n relu(v)[n] * head_w[n] + head_bias)
  *   (head.conv2 + ReLU + head.conv3 1x1 + ReLU of the DPT head, depth-anything.cpp:87-94).

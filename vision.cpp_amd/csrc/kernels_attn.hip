@@ -46,20 +46,9 @@ constexpr int Q_PER_WAVE = 32;
 constexpr int TILE_BYTES = KV_TILE * HD * 2;
 constexpr float FAST_LIMIT_DEFAULT = 1024.0f; // a lane's partial row sum above this sends the tile to the full path
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __fp16 hv4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
-__device__ __forceinline__ int k_swz(int row, int chunk16) { return chunk16 ^ ((row >> 1) & 7); }
 __device__ __forceinline__ int v_swz(int row, int chunk16) { return chunk16 ^ (((row >> 1) & 1) << 2); }
-
-// value held by the same lane of the other 32-lane half (lanes l and l+32 own the same query column)
-__device__ __forceinline__ float other_half(float v) {
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    // after the swap r[0] = {low: own low, high: low half's values}, r[1] = {low: high half's values, high: own high}
-    return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
 
 // four waves per SIMD: the register allocation is held at 128 (the steady-state tile runs spill-free in it, the rare full path keeps
 // a few invariants in scratch). NW waves per block = 32 NW queries share one K/V tile stream: the 16 LDS-DMA instructions of a tile
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VISP_AT
         for (int i = 0; i < PER; ++i) {
             const int piece = wave * PER + i, row = piece * 8 + l_row;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(k_rsrc, (lptr_t)(sk + piece * 1024), 16,
-                                                     tile_bytes0 + row * (HD * 2) + k_swz(row, l_pos) * 16, 0, 0, 0);
+                                                     tile_bytes0 + row * (HD * 2) + swz128(row, l_pos) * 16, 0, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rsrc, (lptr_t)(sv + piece * 1024), 16,
                                                      tile_bytes0 + row * (HD * 2) + v_swz(row, l_pos) * 16, 0, 0, 0);
         }
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VISP_AT
     const int tr_q = (lane & 15) >> 2, tr_p = lane & 3, tr_d0 = 16 * ((lane >> 4) & 1);
     // LDS byte offsets: K fragment of d-step st, key block kb = (k_off0 ^ st*32) + kb*4096 (the swizzle (r>>1)&7 is per lane and
     // the d-step only flips bits 5-6 of it); V^T tr-read of d block db, key step ks, half a/b = (v_off0 ^ db*64) + ks*2048 (+1024).
-    const int k_off0 = r * 128 + k_swz(r, h) * 16;
+    const int k_off0 = r * 128 + swz128(r, h) * 16;
     int v_off0;
     {
         const int key = 4 * h + tr_q, dd = tr_d0 + 4 * tr_p;
@@ -236,7 +225,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VISP_AT
         unsigned long long c0 = 0, c1 = 0, c2 = 0;
         if constexpr (STAMP) c0 = __builtin_amdgcn_s_memtime();
         // (one barrier per TWO tiles with a 4-stage ring was measured in round 3: no change -- the wait is landing + issue, not skew)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads(); // tile t landed; every wave finished tile t-1, so the other stage is free
         if (t + 1 < n_tiles) issue_loads(t + 1, BUF ^ 1);
         if constexpr (STAMP) { c1 = __builtin_amdgcn_s_memtime(); st_wait += c1 - c0; }

@@ -17,7 +17,6 @@
 
 namespace {
 
-inline unsigned blocks_for(long items, int per_block = 256) { return (unsigned)((items + per_block - 1) / per_block); }
 
 __device__ __forceinline__ float norm_px(unsigned char v, int c) {
     const float mean[3] = {0.485f, 0.456f, 0.406f}, inv_std[3] = {1.0f / 0.229f, 1.0f / 0.224f, 1.0f / 0.225f};
@@ -38,17 +37,15 @@ __global__ __launch_bounds__(256) void bf_preprocess_half_kernel(const unsigned 
     const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
     const float ty = fy - (float)y0, tx = fx - (float)x0;
     const unsigned char* p = rgb + b * (long)H * W * 3;
-    f16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+    float v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float a = norm_px(p[((long)y0 * W + x0) * 3 + c], c), bq = norm_px(p[((long)y0 * W + x1) * 3 + c], c);
         const float cq = norm_px(p[((long)y1 * W + x0) * 3 + c], c), d = norm_px(p[((long)y1 * W + x1) * 3 + c], c);
-        const float top = a + (bq - a) * tx, bot = cq + (d - cq) * tx, v = top + (bot - top) * ty;
-        const f16 hv = (f16)v;
-        o[c] = hv;
-        o[3 + c] = (f16)(v - (float)hv);
+        const float top = a + (bq - a) * tx, bot = cq + (d - cq) * tx;
+        v[c] = top + (bot - top) * ty;
     }
-    *reinterpret_cast<f16x8*>(out + i * 8) = o;
+    *reinterpret_cast<f16x8*>(out + i * 8) = residue_pixel(v);
 }
 
 // patches [B, h, w, gw*gh*3]: channel gx + gw (gy + gh c) of pixel (py, px) = normalised image (gy h + py, gx w + px, c).

@@ -89,8 +89,6 @@ __device__ __forceinline__ float row_sum4(float v) {
     return v;
 }
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 // 16 bytes per lane global -> LDS (global_load_lds_dwordx4; LDS destination = M0 + 16 * lane), issued from inline asm so that hipcc
 // does not count it: with the builtin it waits vmcnt(0) in front of every later LDS read (it cannot tell the ring stages apart).
 // The kernel's own vmcnt(0) in front of the step barrier is the wait these copies need. M0 is written in the same statement.
@@ -202,13 +200,13 @@ __global__ __launch_bounds__(512) void dino_block16_kernel(const vx_dino_block_a
         constexpr int YOUNGER = CI(yc);
         if constexpr (DBG & 1024) { // diagnostic: how long this wave waits for its copies / at the barrier (slots 11 .. 13 of the stamps)
             const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNGER) : "memory");
+            wait_vmcnt<YOUNGER>();
             const unsigned long long t1 = __builtin_amdgcn_s_memtime();
             __syncthreads();
             const unsigned long long t2 = __builtin_amdgcn_s_memtime();
             w_vm += t1 - t0; w_bar += t2 - t1; w_n += 1;
         } else {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNGER) : "memory");
+        wait_vmcnt<YOUNGER>();
         if constexpr (!(DBG & 64)) __syncthreads();
         }
         curx = rd0 + st * SLAB;

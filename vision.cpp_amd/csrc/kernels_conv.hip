@@ -22,8 +22,6 @@ constexpr int TH = 8, TW = 32;                 // output tile (rows x cols); one
 constexpr int HH = TH + 2, HW = TW + 2;        // halo
 constexpr int HALO_PIX = HH * HW;              // 340
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __attribute__((aligned(16))) unsigned char g_conv_zero_page[64];
 
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const vx_gemm_args p)
 
     f16x8 wf[2][NI][KS];
     load_w(0, wf[0]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // halo (and first weights) landed
+    wait_vmcnt<0>(); // halo (and first weights) landed
     __syncthreads();
 
     // wave owns output rows 2*wave, 2*wave+1 of the tile; lane r = pixel column

@@ -32,9 +32,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // out-of-map lanes of an edge tile store here (one KiB per wave) instead of being masked off, so every wave issues
 // the same number of store instructions per tile and the ring can wait with a COUNTED vmcnt that leaves the
 // stores in flight
@@ -69,11 +66,6 @@ struct tile_grid {
 // depth-anything.cpp:15-23).
 // RES: number of weight slabs kept RESIDENT in LDS for the whole launch (all cin/32 chunks of the conv fit next to the
 // halo ring), 0 = slabs stream through a 2-stage ring. HSV: halo ring stages of this variant.
-// max(x, 0) as ONE instruction: fmaxf() on an MFMA result costs a canonicalising v_max_f32 x, x, x first (IEEE mode), and the depth
-// head's epilogue is 32 of them per tile in a kernel bound by VALU issue. Signed-integer max with 0 (same order as floats for non-NaN
-// values, -0.0 and negatives -> +0), NOT an inline-asm v_max_f32: the hazard recogniser does not look into inline asm, and one placed
-// right behind an accumulator's last MFMA reads it before the matrix pipe has written it (kernels_headconv.hip met exactly that).
-__device__ __forceinline__ float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
 // BIL: the input is a LOW-resolution map and the conv runs on its bilinear (align_corners) resize (the DPT head's two
 // `interpolate` calls, depth-anything.cpp:36-38 / 84-85 -> ml.cpp:782-788 ggml_interpolate): the resized map never exists. Per step
@@ -602,7 +594,7 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
         advance_halo(0);
         advance_halo(1);
         setup_interp(cur);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -636,16 +628,16 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
         {
             const bool st = EPI == VX_DC_F16 && stores_in_flight;
             if (HS == 3 && prev_halo) {
-                if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HJ + NCH16) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HJ) : "memory");
+                if (st) wait_vmcnt<HJ + NCH16>();
+                else wait_vmcnt<HJ>();
             } else {
-                if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NCH16) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (st) wait_vmcnt<NCH16>();
+                else wait_vmcnt<0>();
             }
         }
         stores_in_flight = false;
         stamp(0); // waited for the step's DMA
-        if constexpr (BIL) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's share of the step's interpolated halo is written
+        if constexpr (BIL) wait_lgkmcnt0(); // this wave's share of the step's interpolated halo is written
         // raw s_barrier: __syncthreads() carries a fence that drains vmcnt, i.e. the halo prefetched for later steps
         __builtin_amdgcn_s_barrier(); // the step's data is in LDS for everyone; everyone has left the previous step's stages
         asm volatile("" ::: "memory");
@@ -716,7 +708,7 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
                 if (h == 0 && oy < H && ox < W)
                     reinterpret_cast<float*>(p.out)[((long)cur.b * H + oy) * W + ox] = fmaxf(part + p.head_bias, 0.0f) * p.head_scale;
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // data-dependent store count: drain before the next counted wait
+            wait_vmcnt<0>(); // data-dependent store count: drain before the next counted wait
             prev_halo = false;
         } else if constexpr (EPI == VX_DC_RGB_F32) {
             // channels 0..2 of pixel r sit in acc[mi][0][0..2] of the lanes with h == 0
@@ -733,7 +725,7 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
                 }
             }
             // the number of store instructions is data dependent here: drain before the next counted wait
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             prev_halo = false;
         } else {
             asm volatile("" ::: "memory");
@@ -798,7 +790,7 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
             const long off1 = ((long)jp * p.res1_plane + je) * 2, off2 = ((long)jp * p.res2_plane + je) * 2, offo = ((long)jp * p.out_plane + je) * 2;
             const bool unit = p.s1 == 1.0f && p.s2 == 1.0f;
             const int rp1 = (int)res1_pix * 2, rp2 = (int)res2_pix * 2, rpo = (int)out_pix * 2; // byte strides between pixels
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // wave-local hand-over of the staged rows: no block barrier
+            wait_lgkmcnt0(); // wave-local hand-over of the staged rows: no block barrier
             const float s1 = p.s1, s2 = p.s2;
 #pragma unroll
             for (int ib = 0; ib < NCH16; ib += NB) {
@@ -971,18 +963,10 @@ __global__ void esr_tiles_in_kernel(const uint8_t* __restrict__ img, int B, int 
     const int cx = tile % t.n_x, cy = tile / t.n_x;
     const int sx = min(cx * (t.tile_w - t.overlap_x) + x, w - 1), sy = min(cy * (t.tile_h - t.overlap_y) + y, h - 1);
     const uint8_t* s = img + (((long)b * h + sy) * w + sx) * ch;
-    const int idx[3] = {ir, ig, ib};
-    f16x8 lo = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = (float)s[idx[c]] / 255.0f;
-        const f16 hi = (f16)v;
-        lo[c] = hi;
-        lo[3 + c] = (f16)(v - (float)hi);
-    }
+    const float v[3] = {(float)s[ir] / 255.0f, (float)s[ig] / 255.0f, (float)s[ib] / 255.0f};
     f16x8* o = reinterpret_cast<f16x8*>(out + i * 32);
     const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    o[0] = lo;
+    o[0] = residue_pixel(v);
     o[1] = z;
     o[2] = z;
     o[3] = z;

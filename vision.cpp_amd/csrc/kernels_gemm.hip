@@ -30,25 +30,6 @@ constexpr int WAVE = 64;
 
 __device__ __attribute__((aligned(16))) unsigned char g_zero_page[64]; // source of padded conv taps
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ int swz_chunk(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ float gelu_tanh(float x) {
-    // ggml_gelu: 0.5*x*(1+tanh(u)), u = sqrt(2/pi)*x*(1+0.044715*x*x). With tanh(u) = 2*sigmoid(2u) - 1
-    // this is x * sigmoid(2u) = x / (1 + exp(-2u)): 7 VALU ops, two of them transcendental.
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f; // -2*sqrt(2/pi)*log2(e)
-    const float c3 = c1 * 0.044715f;
-    float w = fmaf(x * x, c3, c1);
-    float e = __builtin_amdgcn_exp2f(x * w);
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-__device__ __forceinline__ float silu(float x) { // x * sigmoid(x) = x / (1 + exp(-x)); exp2 of a large argument gives inf and x * 0
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));
-}
-
 constexpr bool epi_is_f16_tile(int epi) {
     return epi == VX_EPI_F16 || epi == VX_EPI_F16_GELU || epi == VX_EPI_F16_RELU || epi == VX_EPI_F16_ADD ||
            epi == VX_EPI_QKV || epi == VX_EPI_PIXSHUF || epi == VX_EPI_HEAD_OUT || epi == VX_EPI_LRELU_AGC ||
@@ -150,7 +131,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
 #pragma unroll
     for (int i = 0; i < A_INSTR; ++i) {
         const int row = (wave * A_INSTR + i) * 8 + l_row;
-        a_chunk[i] = swz_chunk(row, l_pos);
+        a_chunk[i] = swz128(row, l_pos);
         int m = m0 + row;
         if constexpr (CONV) {
             if (m < p.M) {
@@ -177,7 +158,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
 #pragma unroll
     for (int i = 0; i < B_INSTR; ++i) {
         const int row = (wave * B_INSTR + i) * 8 + l_row;
-        b_chunk[i] = swz_chunk(row, l_pos);
+        b_chunk[i] = swz128(row, l_pos);
         b_off[i] = (long)(n0 + row) * p.K;
     }
     const int cin8 = CONV ? (p.conv_Cin >> 3) : 1;
@@ -223,7 +204,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
     // multiples of 32), so 4 per-lane offsets cover every (mi / ni, k-step) through immediates
     int f_off[BK / 16];
 #pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) f_off[ks] = r * 128 + swz_chunk(r, ks * 2 + h) * 16;
+    for (int ks = 0; ks < BK / 16; ++ks) f_off[ks] = r * 128 + swz128(r, ks * 2 + h) * 16;
 
     auto compute = [&](int stage) {
         const unsigned char* const sa = smem + stage * STAGE_BYTES + wr * WM * 128;
@@ -260,7 +241,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
     };
     // raw barrier: __syncthreads() would drain the LDS-DMA queue (vmcnt(0)) and serialise the ring
     auto barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt0();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
@@ -269,7 +250,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
     if constexpr (STAGES == 1) {
         issue_loads(0, 0);
         for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             barrier(); // k-tile kt has landed in LDS for every wave
             if (kt == 0) stamp(2);
             compute(0);
@@ -284,9 +265,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_kernel(const 
         int stage = 0;
         for (int kt = 0; kt < nk; ++kt) {
             const int ahead = min(STAGES - 2, nk - 1 - kt); // tiles that may stay in flight behind tile kt
-            if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LOADS) : "memory");
-            else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (ahead >= 2) wait_vmcnt<2 * LOADS>();
+            else if (ahead == 1) wait_vmcnt<LOADS>();
+            else wait_vmcnt<0>();
             barrier(); // tile kt visible to all waves; all waves are done with tile kt-1, its stage is free
             int next_stage = stage == 0 ? STAGES - 1 : stage - 1; // == (kt + STAGES - 1) % STAGES
             if (kt + STAGES - 1 < nk) issue_loads(kt + STAGES - 1, next_stage);

@@ -17,16 +17,9 @@ namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int BM = 128, BN = 128, BKB = 128; // tile rows (tokens), tile columns (features), k bytes per step
 constexpr int STAGE = (BM + BN) * BKB;       // 32 KiB
-
-__device__ __forceinline__ float gelu_tanh(float x) { // ggml_gelu as kernels_gemm.hip computes it
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f, c3 = c1 * 0.044715f;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * fmaf(x * x, c3, c1)));
-}
 
 template <int ACT>
 __global__ __launch_bounds__(256) void gemm_fp8_kernel(const vx_gemm_fp8_args p) {
@@ -80,7 +73,7 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(const vx_gemm_fp8_args p)
     issue(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
         const int st = kt & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads(); // k-tile kt landed; every wave is done with the other stage
         if (kt + 1 < nk) issue(kt + 1, st ^ 1);
         const unsigned char* sa = smem + st * STAGE;

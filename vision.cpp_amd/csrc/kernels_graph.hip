@@ -7,14 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ float gelu_tanh_g(float x) { // ggml_gelu, the form of kernels_gemm.hip's epilogue
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f;
-    const float c3 = c1 * 0.044715f;
-    float w = fmaf(x * x, c3, c1);
-    float e = __builtin_amdgcn_exp2f(x * w);
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
 // an f32 result kept as f32 before its f16 rounding: the compiler folds f32 product -> f16 into one fma_mix rounding in some kernels and not
 // in others, so the same data would give different bits on the vector and the scalar path
 __device__ __forceinline__ float f32_rounded(float v) {
@@ -22,10 +14,7 @@ __device__ __forceinline__ float f32_rounded(float v) {
     return v;
 }
 
-inline int blocks_for(int64_t n, int per_block = 256) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (int)(b > 256 * 64 ? 256 * 64 : (b < 1 ? 1 : b)); // at most 64 blocks per CU, grid-stride beyond
-}
+constexpr int GRID_CAP = 256 * 64; // at most 64 blocks per CU, grid-stride beyond
 
 struct copy_shape {
     long ne[4];
@@ -99,14 +88,14 @@ __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float f = (float)v[j];
-            v[j] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
+            v[j] = (f16)(OP == 0 ? gelu_tanh(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
         }
         *reinterpret_cast<f16x8*>(y + i * 8) = v;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) { // tail
         const long i = (n8 << 3) + threadIdx.x;
         const float f = (float)x[i];
-        y[i] = (f16)(OP == 0 ? gelu_tanh_g(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
+        y[i] = (f16)(OP == 0 ? gelu_tanh(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
     }
 }
 
@@ -200,7 +189,7 @@ __global__ __launch_bounds__(256) void conv1x1_to1_kernel(const f16* __restrict_
 
 extern "C" int vx_conv1x1_to1_f32(const void* x, const float* w, float bias, int relu, float scale, float* out, int64_t M, int C, void* stream) {
     VX_REQUIRE(x && w && out && M > 0 && C > 0 && C % 8 == 0, "vx_conv1x1_to1_f32: bad operands (C = %d: a multiple of 8)", C);
-    hipLaunchKernelGGL(conv1x1_to1_kernel, dim3(blocks_for(M)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(x), w, bias, relu, scale, out, (long)M, C);
+    hipLaunchKernelGGL(conv1x1_to1_kernel, dim3(grid_stride_blocks(M, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(x), w, bias, relu, scale, out, (long)M, C);
     VX_LAUNCH_CHECK();
     return 1;
 }
@@ -221,9 +210,9 @@ extern "C" int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[
     if (vec) {
         s.ne[0] = ne[0] / 8;
         n /= 8;
-        hipLaunchKernelGGL(copy_strided8_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
+        hipLaunchKernelGGL(copy_strided8_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
     } else {
-        hipLaunchKernelGGL(copy_strided_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
+        hipLaunchKernelGGL(copy_strided_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
     }
     VX_LAUNCH_CHECK();
     return 1;
@@ -233,11 +222,11 @@ template <int OP>
 static int launch_binary(const void* a, int a_f32, const void* b, int b_f32, int64_t period, void* y, int y_f32, int64_t n, hipStream_t st) {
     const bool al16 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
     if (!a_f32 && !y_f32 && n % 8 == 0 && period % 8 == 0 && al16) {
-        if (b_f32) hipLaunchKernelGGL((binary8_kernel<OP, float>), dim3(blocks_for(n / 8)), dim3(256), 0, st, (const f16*)a, (const float*)b, (long)period, (f16*)y, (long)(n / 8));
-        else hipLaunchKernelGGL((binary8_kernel<OP, f16>), dim3(blocks_for(n / 8)), dim3(256), 0, st, (const f16*)a, (const f16*)b, (long)period, (f16*)y, (long)(n / 8));
+        if (b_f32) hipLaunchKernelGGL((binary8_kernel<OP, float>), dim3(grid_stride_blocks(n / 8, GRID_CAP)), dim3(256), 0, st, (const f16*)a, (const float*)b, (long)period, (f16*)y, (long)(n / 8));
+        else hipLaunchKernelGGL((binary8_kernel<OP, f16>), dim3(grid_stride_blocks(n / 8, GRID_CAP)), dim3(256), 0, st, (const f16*)a, (const f16*)b, (long)period, (f16*)y, (long)(n / 8));
         return 1;
     }
-    const dim3 g(blocks_for(n)), t(256);
+    const dim3 g(grid_stride_blocks(n, GRID_CAP)), t(256);
 #define VX_BIN(TA, TB, TY) hipLaunchKernelGGL((binary_kernel<OP, TA, TB, TY>), g, t, 0, st, (const TA*)a, (const TB*)b, (long)period, (TY*)y, (long)n)
     switch ((a_f32 ? 4 : 0) | (b_f32 ? 2 : 0) | (y_f32 ? 1 : 0)) {
         case 0: VX_BIN(f16, f16, f16); break;
@@ -265,7 +254,7 @@ extern "C" int vx_binary_rows(int op, const void* a, int a_f32, const void* b, i
 extern "C" int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, void* stream) {
     VX_REQUIRE(x && y && n > 0, "vx_unary_f16: bad operands");
     VX_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "vx_unary_f16: operands must be 16-byte aligned");
-    const dim3 g(blocks_for(n / 8 + 1)), t(256);
+    const dim3 g(grid_stride_blocks(n / 8 + 1, GRID_CAP)), t(256);
     switch (op) {
         case 0: hipLaunchKernelGGL(unary_kernel<0>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
         case 1: hipLaunchKernelGGL(unary_kernel<1>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
@@ -280,22 +269,22 @@ extern "C" int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, 
 extern "C" int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream) {
     VX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 8 == 0, "vx_nearest_f16: bad operands (C a multiple of 8)");
     const long n = (long)B * OH * OW * (C / 8);
-    hipLaunchKernelGGL(nearest_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, H, W, C / 8, OH, OW, (float)OH / (float)H, (float)OW / (float)W, n);
+    hipLaunchKernelGGL(nearest_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, H, W, C / 8, OH, OW, (float)OH / (float)H, (float)OW / (float)W, n);
     VX_LAUNCH_CHECK();
     return 1;
 }
 
 extern "C" int vx_image_planes_f32(const float* x, void* y, int64_t n_pix, int C, void* stream) {
     VX_REQUIRE(x && y && n_pix > 0 && C >= 1 && C <= 16, "vx_image_planes_f32: 1..16 channels");
-    hipLaunchKernelGGL(image_planes_kernel, dim3(blocks_for(n_pix)), dim3(256), 0, as_stream(stream), x, (f16*)y, C, (long)n_pix);
+    hipLaunchKernelGGL(image_planes_kernel, dim3(grid_stride_blocks(n_pix, GRID_CAP)), dim3(256), 0, as_stream(stream), x, (f16*)y, C, (long)n_pix);
     VX_LAUNCH_CHECK();
     return 1;
 }
 
 extern "C" int vx_convert(const void* x, int x_f32, void* y, int y_f32, int64_t n, void* stream) {
     VX_REQUIRE(x && y && n > 0 && x_f32 != y_f32, "vx_convert: bad operands");
-    if (x_f32) hipLaunchKernelGGL((convert_kernel<float, f16>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), (const float*)x, (f16*)y, (long)n);
-    else hipLaunchKernelGGL((convert_kernel<f16, float>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), (const f16*)x, (float*)y, (long)n);
+    if (x_f32) hipLaunchKernelGGL((convert_kernel<float, f16>), dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const float*)x, (f16*)y, (long)n);
+    else hipLaunchKernelGGL((convert_kernel<f16, float>), dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (float*)y, (long)n);
     VX_LAUNCH_CHECK();
     return 1;
 }
@@ -304,7 +293,7 @@ extern "C" int vx_im2col_patches_f32(const float* x, void* patches, int B, int H
     VX_REQUIRE(x && patches && B > 0 && ps > 0 && H % ps == 0 && W % ps == 0 && C > 0, "vx_im2col_patches_f32: the image must be a whole number of patches");
     VX_REQUIRE(Kp % 8 == 0 && Kp >= ps * ps * C, "vx_im2col_patches_f32: Kp = %d must be a multiple of 8 and at least %d", Kp, ps * ps * C);
     const long n8 = (long)B * (H / ps) * (W / ps) * (Kp / 8);
-    hipLaunchKernelGGL(im2col_patches_kernel, dim3(blocks_for(n8)), dim3(256), 0, as_stream(stream), x, reinterpret_cast<f16*>(patches), H, W, C, ps, Kp, n8);
+    hipLaunchKernelGGL(im2col_patches_kernel, dim3(grid_stride_blocks(n8, GRID_CAP)), dim3(256), 0, as_stream(stream), x, reinterpret_cast<f16*>(patches), H, W, C, ps, Kp, n8);
     VX_LAUNCH_CHECK();
     return 1;
 }

@@ -36,20 +36,71 @@ constexpr int ZERO_OFF = PR * PC * PIXB;
 constexpr int TAB_BYTES = (HH + HW) * 8;
 constexpr int SMEM_BYTES = HALO_BYTES + 2 * SRC_BYTES + TAB_BYTES + 256; // 76.3 KB: two blocks per CU
 
-// ReLU in ONE instruction the compiler can see: fmaxf on an MFMA result costs a canonicalising v_max first, and an inline-asm v_max_f32
-// is invisible to the hazard recogniser -- placed right behind the accumulator's last MFMA it read the registers before the matrix pipe
-// had written them (found by this kernel's first parity run: every wave's first row off by a few per cent). Signed-integer max with 0
-// orders non-NaN floats the same way and maps -0.0 and every negative value to +0.
-__device__ __forceinline__ float relu1(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
-__device__ __forceinline__ float other_half(float v) { // the same lane of the other 32-lane half
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
+struct tile_pos { int b, y0, x0; };
+
+// ---- what the 32-channel kernel and the K-sliced one below share as functions. The interpolation pipeline, the halo row reads and
+// the epilogue are the same text in both kernels and stay written out in each: called through a function (whole, or per item) the
+// compiler schedules either kernel differently, and these two are held to their instructions.
+
+constexpr int I_ITEMS = HH * HW * 4, I_IT = (I_ITEMS + 255) / 256; // (halo pixel, 8-channel chunk) items, 10 per thread
+
+__device__ __forceinline__ float resize_factor(int n_out, int n_src) { // align_corners
+    return (n_out > 1 && n_src > 1) ? (float)(n_out - 1) / (float)(n_src - 1) : (float)n_out / (float)n_src;
+}
+// source index and weight of output coordinate o
+__device__ __forceinline__ int src_index(int o, float sf, int n_src, float& f) {
+    const float sc = (float)o / sf;
+    int i0 = (int)floorf(sc);
+    i0 = max(0, min(i0, n_src - 1));
+    f = fminf(fmaxf(sc - (float)i0, 0.0f), 1.0f);
+    return i0;
+}
+// first source row / column of the patch of the tile at (y0, x0)
+__device__ __forceinline__ void patch_origin(int y0, int x0, float sfy, float sfx, int Hs, int Ws, int& py0, int& px0) {
+    float dummy;
+    py0 = src_index(max(y0 - 1, 0), sfy, Hs, dummy);
+    px0 = src_index(max(x0 - 1, 0), sfx, Ws, dummy);
 }
 
-typedef __attribute__((address_space(3))) void* lptr_t;
+// conv2's bias and conv3's weights in accumulator order per lane half: LDS, read back per tile (32 registers the interpolation
+// phase needs)
+__device__ __forceinline__ void stage_bias_w3(int tid, const float* __restrict__ bias, const float* __restrict__ w3, float* bias_lds, float* w3_lds) {
+    if (tid < 32) {
+        const int c = (tid & 3) + 8 * ((tid & 15) >> 2) + 4 * (tid >> 4);
+        w3_lds[tid] = w3[c];
+        bias_lds[tid] = bias[c];
+    }
+}
 
-struct tile_pos { int b, y0, x0; };
+// source coordinates of a tile's halo rows / columns: .x = patch-relative index | has-next << 15 | outside << 31, .y = weight f as
+// packed f16 (f, f)
+__device__ __forceinline__ void halo_tables(int tid, int y0, int x0, int py0, int px0, int H, int W, int Hs, int Ws, float sfy, float sfx, uint2* tab_y, uint2* tab_x) {
+    if (tid < HH + HW) {
+        const bool isx = tid >= HH;
+        const int o = (isx ? x0 + (tid - HH) : y0 + tid) - 1, n_out = isx ? W : H, n_src = isx ? Ws : Hs;
+        uint2 e = {0x80000000u, 0u};
+        if (o >= 0 && o < n_out) {
+            float f;
+            const int i0 = src_index(o, isx ? sfx : sfy, n_src, f);
+            const unsigned short fh = __builtin_bit_cast(unsigned short, (f16)f);
+            e.x = (unsigned)(i0 - (isx ? px0 : py0)) | (i0 + 1 < n_src ? 0x8000u : 0u);
+            e.y = (unsigned)fh | (unsigned)fh << 16;
+        }
+        (isx ? tab_x[tid - HH] : tab_y[tid]) = e;
+    }
+}
+
+// the static part of interpolation item i: halo row | halo column << 8 | chunk << 16 (threads past the last item repeat an earlier
+// one: identical bytes to the same place, no branch)
+__device__ __forceinline__ unsigned interp_item(int i) {
+    if (i >= I_ITEMS) i -= 256;
+    const int pix = i >> 2, chunk = i & 3, hy = pix / HW, hx = pix - hy * HW;
+    return (unsigned)hy | (unsigned)hx << 8 | (unsigned)chunk << 16;
+}
+// byte offset of a lane's B fragment in halo row 4 wave: pixel px, 8-channel chunk (swizzled as the interpolation stores it)
+__device__ __forceinline__ unsigned b_fragment_offset(int wave, int px, int chunk) {
+    return (unsigned)((4 * wave * HW + px) * PIXB + ((chunk ^ ((px >> 1) & 3)) * 16));
+}
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void headconv_kernel(
     const f16* __restrict__ x, const f16* __restrict__ wfrag, const float* __restrict__ bias, const float* __restrict__ w3, float b3, float out_scale,
@@ -86,57 +137,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     f16x8 wf[18];
 #pragma unroll
     for (int i = 0; i < 18; ++i) wf[i] = *reinterpret_cast<const f16x8*>(wfrag + ((size_t)i * 64 + lane) * 8);
-    // conv2's bias and conv3's weights in accumulator order per lane half: LDS, read back per tile (32 registers the interpolation
-    // phase needs)
     float* const w3_lds = reinterpret_cast<float*>(smem + HALO_BYTES + 2 * SRC_BYTES + TAB_BYTES);
     float* const bias_lds = w3_lds + 32;
-    if (tid < 32) {
-        const int c = (tid & 3) + 8 * ((tid & 15) >> 2) + 4 * (tid >> 4);
-        w3_lds[tid] = w3[c];
-        bias_lds[tid] = bias[c];
-    }
-    constexpr int I_ITEMS = HH * HW * 4, I_IT = (I_ITEMS + 255) / 256; // (halo pixel, 8-channel chunk) items, 10 per thread
-    unsigned ipack[I_IT]; // halo row | halo column << 8 | chunk << 16 (threads past the last item repeat an earlier one: identical
-                          // bytes to the same place, no branch)
+    stage_bias_w3(tid, bias, w3, bias_lds, w3_lds);
+    unsigned ipack[I_IT];
 #pragma unroll
-    for (int it = 0; it < I_IT; ++it) {
-        int i = tid + it * 256;
-        if (i >= I_ITEMS) i -= 256;
-        const int pix = i >> 2, chunk = i & 3, hy = pix / HW, hx = pix - hy * HW;
-        ipack[it] = (unsigned)hy | (unsigned)hx << 8 | (unsigned)chunk << 16;
-    }
-    unsigned boff[3][2]; // byte offset of the lane's B fragment in halo row 4 wave: pixel n + dx, channels 16 ks + 8 h
+    for (int it = 0; it < I_IT; ++it) ipack[it] = interp_item(tid + it * 256);
+    unsigned boff[3][2];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int px = n + dx, chunk = ks * 2 + h;
-            boff[dx][ks] = (unsigned)((4 * wave * HW + px) * PIXB + ((chunk ^ ((px >> 1) & 3)) * 16));
-        }
+        for (int ks = 0; ks < 2; ++ks) boff[dx][ks] = b_fragment_offset(wave, n + dx, ks * 2 + h);
     if (tid < 8) { // the zero pixel of both source buffers (what halo positions outside the map read)
         *reinterpret_cast<uint4*>(src_buf(tid >> 2) + ZERO_OFF + (tid & 3) * 16) = uint4{0, 0, 0, 0};
     }
 
-    const float sfy = (H > 1 && Hs > 1) ? (float)(H - 1) / (float)(Hs - 1) : (float)H / (float)Hs;
-    const float sfx = (W > 1 && Ws > 1) ? (float)(W - 1) / (float)(Ws - 1) : (float)W / (float)Ws;
-    auto src_index = [](int o, float sf, int n_src, float& f) {
-        const float sc = (float)o / sf;
-        int i0 = (int)floorf(sc);
-        i0 = max(0, min(i0, n_src - 1));
-        f = fminf(fmaxf(sc - (float)i0, 0.0f), 1.0f);
-        return i0;
-    };
-    auto patch_origin = [&](tile_pos const& p, int& py0, int& px0) {
-        float dummy;
-        py0 = src_index(max(p.y0 - 1, 0), sfy, Hs, dummy);
-        px0 = src_index(max(p.x0 - 1, 0), sfx, Ws, dummy);
-    };
+    const float sfy = resize_factor(H, Hs), sfx = resize_factor(W, Ws);
     // source patch of a tile -> LDS by DMA (rows / columns past the map repeat its last one: never weighted, has-next is 0 there).
     // One descriptor over the whole tensor; a lane's 16 bytes land at its item's slot.
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(x), 0, (int)((size_t)B * Hs * Ws * PIXB), 0x00020000);
     auto issue_patch = [&](tile_pos const& p, int k) {
         int py0, px0;
-        patch_origin(p, py0, px0);
+        patch_origin(p.y0, p.x0, sfy, sfx, Hs, Ws, py0, px0);
         constexpr int N_ITEMS = PR * PC * 4, N_IT = (N_ITEMS + 255) / 256;
         unsigned char* const dst = src_buf(k);
 #pragma unroll
@@ -166,25 +188,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (; t < t_end; t += per_xcd_blocks, cur ^= 1, ++n_done) {
         const tile_pos p = locate(t);
         int py0, px0;
-        patch_origin(p, py0, px0);
-        // ---- this tile's source coordinates of the halo rows / columns: .x = patch-relative index | has-next << 15 | outside << 31,
-        // .y = weight f as packed f16 (f, f). (Every wave is past the previous tile's MFMA phase only after the barrier below; the
-        // tables are read after it, and the previous tile's readers of them finished before its second barrier.)
-        if (tid < HH + HW) {
-            const bool isx = tid >= HH;
-            const int o = (isx ? p.x0 + (tid - HH) : p.y0 + tid) - 1, n_out = isx ? W : H, n_src = isx ? Ws : Hs;
-            uint2 e = {0x80000000u, 0u};
-            if (o >= 0 && o < n_out) {
-                float f;
-                const int i0 = src_index(o, isx ? sfx : sfy, n_src, f);
-                const unsigned short fh = __builtin_bit_cast(unsigned short, (f16)f);
-                e.x = (unsigned)(i0 - (isx ? px0 : py0)) | (i0 + 1 < n_src ? 0x8000u : 0u);
-                e.y = (unsigned)fh | (unsigned)fh << 16;
-            }
-            (isx ? tab_x[tid - HH] : tab_y[tid]) = e;
-        }
+        patch_origin(p.y0, p.x0, sfy, sfx, Hs, Ws, py0, px0);
+        // ---- this tile's halo tables. (Every wave is past the previous tile's MFMA phase only after the barrier below; the tables are
+        // read after it, and the previous tile's readers of them finished before its second barrier.)
+        halo_tables(tid, p.y0, p.x0, py0, px0, H, W, Hs, Ws, sfy, sfx, tab_y, tab_x);
         stamp(0); // tables
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this tile's patch (issued one tile ago) and the previous tile's stores
+        wait_vmcnt<0>(); // this tile's patch (issued one tile ago) and the previous tile's stores
         __syncthreads();                                  // ... from every wave; and every wave is done reading the halo
         stamp(1); // wait + barrier
 
@@ -358,41 +367,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int pb = t / per_image, tk = t - pb * per_image, ty0 = tk / tiles_x;
     const int y0 = ty0 * TH, x0 = (tk - ty0 * tiles_x) * TW;
 
-    const float sfy = (H > 1 && Hs > 1) ? (float)(H - 1) / (float)(Hs - 1) : (float)H / (float)Hs;
-    const float sfx = (W > 1 && Ws > 1) ? (float)(W - 1) / (float)(Ws - 1) : (float)W / (float)Ws;
-    auto src_index = [](int o, float sf, int n_src, float& f) {
-        const float sc = (float)o / sf;
-        int i0 = (int)floorf(sc);
-        i0 = max(0, min(i0, n_src - 1));
-        f = fminf(fmaxf(sc - (float)i0, 0.0f), 1.0f);
-        return i0;
-    };
+    const float sfy = resize_factor(H, Hs), sfx = resize_factor(W, Ws);
     int py0, px0;
-    {
-        float dummy;
-        py0 = src_index(max(y0 - 1, 0), sfy, Hs, dummy);
-        px0 = src_index(max(x0 - 1, 0), sfx, Ws, dummy);
-    }
+    patch_origin(y0, x0, sfy, sfx, Hs, Ws, py0, px0);
 
     // ---- once per block: conv3's weights and conv2's bias in accumulator order, the halo's source tables, the zero pixel
-    if (tid < 32) {
-        const int c = (tid & 3) + 8 * ((tid & 15) >> 2) + 4 * (tid >> 4);
-        w3_lds[tid] = w3[c];
-        bias_lds[tid] = bias[c];
-    }
-    if (tid < HH + HW) {
-        const bool isx = tid >= HH;
-        const int o = (isx ? x0 + (tid - HH) : y0 + tid) - 1, n_out = isx ? W : H, n_src = isx ? Ws : Hs;
-        uint2 e = {0x80000000u, 0u};
-        if (o >= 0 && o < n_out) {
-            float f;
-            const int i0 = src_index(o, isx ? sfx : sfy, n_src, f);
-            const unsigned short fh = __builtin_bit_cast(unsigned short, (f16)f);
-            e.x = (unsigned)(i0 - (isx ? px0 : py0)) | (i0 + 1 < n_src ? 0x8000u : 0u);
-            e.y = (unsigned)fh | (unsigned)fh << 16;
-        }
-        (isx ? tab_x[tid - HH] : tab_y[tid]) = e;
-    }
+    stage_bias_w3(tid, bias, w3, bias_lds, w3_lds);
+    halo_tables(tid, y0, x0, py0, px0, H, W, Hs, Ws, sfy, sfx, tab_y, tab_x);
     if (tid < 4) *reinterpret_cast<uint4*>(src + ZERO_OFF + tid * 16) = uint4{0, 0, 0, 0};
 
     // source patch items (pixel, 8-channel chunk) of this thread: the global address of slice 0 (rows / columns past the map repeat
@@ -419,23 +400,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_patch(0);
     store_patch();
 
-    constexpr int I_ITEMS = HH * HW * 4, I_IT = (I_ITEMS + 255) / 256;
     unsigned ipack[I_IT];
 #pragma unroll
-    for (int it = 0; it < I_IT; ++it) {
-        int i = tid + it * 256;
-        if (i >= I_ITEMS) i -= 256;
-        const int pix = i >> 2, chunk = i & 3, hy = pix / HW, hx = pix - hy * HW;
-        ipack[it] = (unsigned)hy | (unsigned)hx << 8 | (unsigned)chunk << 16;
-    }
+    for (int it = 0; it < I_IT; ++it) ipack[it] = interp_item(tid + it * 256);
     unsigned boff[3][2];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int px = n + dx, chunk = ks * 2 + h;
-            boff[dx][ks] = (unsigned)((4 * wave * HW + px) * PIXB + ((chunk ^ ((px >> 1) & 3)) * 16));
-        }
+        for (int ks = 0; ks < 2; ++ks) boff[dx][ks] = b_fragment_offset(wave, n + dx, ks * 2 + h);
     __syncthreads();
 
     f32x16 acc[4]; // conv2's sums over all slices, starting at the bias (one tile per block: the moves happen once)

@@ -23,13 +23,6 @@ namespace {
 constexpr int MB_C = 256, MB_CO = 64, MB_PX = 64, MB_P = 8;
 constexpr int MB_ROW = MB_C * 2; // bytes per LDS row (one pixel of A, one output channel of W3)
 
-__device__ __forceinline__ float mb_gelu(float x) { // ggml_gelu (tanh form) = x * sigmoid(2u) = x / (1 + exp2(x * w)): 5 VALU + v_exp + v_rcp
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f; // -2 sqrt(2/pi) log2(e)
-    const float c3 = c1 * 0.044715f;
-    const float w = fmaf(x * x, c3, c1);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * w)); // exp2 -> inf gives -0, exp2 -> 0 gives x
-}
-
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void mbconv_dw_pw_kernel(const f16* __restrict__ h, const f16* __restrict__ w2, const float* __restrict__ b2,
                                                            const f16* __restrict__ w3, const float* __restrict__ b3, const f16* __restrict__ x,
                                                            f16* __restrict__ y, int B, int H, int W) {
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             const int px = strip * MB_P + p;
             f16x8 o;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)mb_gelu(acc[p][j] + bv[j]);
+            for (int j = 0; j < 8; ++j) o[j] = (f16)gelu_tanh(acc[p][j] + bv[j]);
             *reinterpret_cast<f16x8*>(sa + px * MB_ROW + ((c8 ^ (px & 15)) * 16)) = o;
         }
     }
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const float bq[4] = {bb.x, bb.y, bb.z, bb.w};
         f16x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (f16)mb_gelu(acc[g * 4 + j] + bq[j] + (float)xv[j]);
+        for (int j = 0; j < 4; ++j) o[j] = (f16)gelu_tanh(acc[g * 4 + j] + bq[j] + (float)xv[j]);
         *reinterpret_cast<f16x4*>(yr + c) = o;
     }
 }

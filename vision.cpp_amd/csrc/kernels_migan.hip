@@ -231,8 +231,6 @@ __global__ __launch_bounds__(256) void migan_postprocess_kernel(const float* __r
     reinterpret_cast<uchar4*>(rgba)[pix] = o;
 }
 
-unsigned blocks_for(int64_t items) { return (unsigned)((items + 255) / 256); }
-
 } // namespace
 
 extern "C" {

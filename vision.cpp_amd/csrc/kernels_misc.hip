@@ -235,11 +235,6 @@ __global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict_
     }
 }
 
-inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
-    long g = (total + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 } // namespace
 
 extern "C" {
@@ -276,7 +271,7 @@ int vx_preprocess_patches(const uint8_t* rgb, void* patches, int B, int H, int W
 int vx_preprocess_f32(const uint8_t* rgb, float* out, int B, int H, int W, const float mean[3], const float inv_std[3],
                       void* stream) {
     long n = (long)B * H * W * 3;
-    hipLaunchKernelGGL(preprocess_f32_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), rgb, out, n, mean[0],
+    hipLaunchKernelGGL(preprocess_f32_kernel, dim3(grid_stride_blocks(n, 256 * 16)), dim3(256), 0, as_stream(stream), rgb, out, n, mean[0],
                        mean[1], mean[2], inv_std[0], inv_std[1], inv_std[2]);
     VX_LAUNCH_CHECK();
     return 1;
@@ -305,7 +300,7 @@ int vx_head_out_f32(const void* x, const float* w, float bias, float max_depth, 
                     void* stream) {
     hipStream_t s = as_stream(stream);
     const f16* xx = reinterpret_cast<const f16*>(x);
-    dim3 grid(grid_for(n_pixels)), block(256);
+    dim3 grid(grid_stride_blocks(n_pixels, 256 * 16)), block(256);
     if (C == 32) hipLaunchKernelGGL(head_out_kernel<32>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
     else if (C == 64) hipLaunchKernelGGL(head_out_kernel<64>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
     else if (C == 8) hipLaunchKernelGGL(head_out_kernel<8>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
@@ -319,7 +314,7 @@ int vx_minmax_normalize(const float* depth, float* out, float* minmax, int B, in
     hipStream_t s = as_stream(stream);
     unsigned* mm = reinterpret_cast<unsigned*>(minmax);
     hipLaunchKernelGGL(minmax_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, mm, B);
-    int gx = grid_for(n, 256, 64);
+    int gx = grid_stride_blocks(n, 64);
     const int gmm = B >= 16 ? 16 : (B >= 4 ? 32 : 64); // blocks per image of the reduction: ~512 blocks, 2 atomics each
     hipLaunchKernelGGL(minmax_kernel, dim3(gmm < gx ? gmm : gx, B), dim3(256), 0, s, depth, mm, (long)n);
     hipLaunchKernelGGL(normalize_kernel, dim3(gx, B), dim3(256), 0, s, depth, out, mm, (long)n);
@@ -328,7 +323,7 @@ int vx_minmax_normalize(const float* depth, float* out, float* minmax, int B, in
 }
 
 int vx_f32_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream) {
-    hipLaunchKernelGGL(f32_to_u8_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, dst, (long)n);
+    hipLaunchKernelGGL(f32_to_u8_kernel, dim3(grid_stride_blocks(n, 256 * 16)), dim3(256), 0, as_stream(stream), src, dst, (long)n);
     VX_LAUNCH_CHECK();
     return 1;
 }

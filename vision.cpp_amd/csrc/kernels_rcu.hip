@@ -52,18 +52,8 @@ __host__ inline rcu_geom rcu_geometry(int H, int W) {
     return g;
 }
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int RSLAB = RC * RC * 2; // one tap of a conv (or the projection): [64 output channels][64 input channels] f16, 8 KB
 constexpr int RRING = 4;           // slabs in the LDS ring: three taps in flight ahead of the one being multiplied
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-}
 
 template <bool PROJ>
 __global__ __launch_bounds__(64 * RNW) void rcu_fused_kernel(const vx_rcu_args p, const int TH, const int TW, const int ncx, const int ncy) {
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(64 * RNW) void rcu_fused_kernel(const vx_rcu_args p
             if (id < chunks && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)
                 v[i] = *reinterpret_cast<const f16x8*>(X + ((long)gy * W + gx) * RC + c * 8);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the region's loads (and the first three slabs) before the tap loop starts counting copies
+        wait_vmcnt<0>(); // the region's loads (and the first three slabs) before the tap loop starts counting copies
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int id = tid + i * 64 * RNW;
@@ -127,7 +117,8 @@ __global__ __launch_bounds__(64 * RNW) void rcu_fused_kernel(const vx_rcu_args p
         }
     }
     // weight fragment of (32-channel half ni, k-step ks) in a slab: row ni * 32 + r, 16-byte group (2 ks + h) ^ ((r >> 1) & 7): the rows of 16
-    // consecutive lanes alternate between the two 128-byte halves of the bank row and take 8 different groups inside each
+    // consecutive lanes alternate between the two 128-byte halves of the bank row and take 8 different groups inside each (swz128(r, h) written
+    // out: through the call the compiler swaps the operands of this kernel's two v_bitop3, and its instructions are held fixed)
     const int w_off = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
 
     // one 3x3 conv stage over a flat region: this wave's M-tiles are wave and wave + 8. src_w = row length of the source region, dst_w of the
@@ -157,9 +148,9 @@ __global__ __launch_bounds__(64 * RNW) void rcu_fused_kernel(const vx_rcu_args p
             const int sl = S0 + tap;
             // slab sl has landed once at most min(2, slabs issued after it) copies of this wave are in flight; the barrier extends that to every wave's
             // part of it and says that everybody is done with slab sl - 1, whose slot the copy issued next overwrites
-            if (sl + 2 < N_SLABS) wait_vm<2>();
-            else if (sl + 1 < N_SLABS) wait_vm<1>();
-            else wait_vm<0>();
+            if (sl + 2 < N_SLABS) wait_vmcnt<2>();
+            else if (sl + 1 < N_SLABS) wait_vmcnt<1>();
+            else wait_vmcnt<0>();
             __syncthreads();
             if (sl + 3 < N_SLABS) issue_slab(sl + 3);
             if (!any) continue;
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(64 * RNW) void rcu_fused_kernel(const vx_rcu_args p
 
     // ---- the projection: 1x1, 64 -> 64 on the staged tile (slab 18)
     {
-        wait_vm<0>();
+        wait_vmcnt<0>();
         __syncthreads(); // the slab and the staged tile
         const int n_mt = (n_out + 31) >> 5;
         if (wave >= n_mt) return;

@@ -14,8 +14,6 @@
 
 namespace {
 
-inline unsigned blocks_for(long items, int per_block = 256) { return (unsigned)((items + per_block - 1) / per_block); }
-
 // sum over the LPR lanes that share a row (LPR = 16, 32 or 64 consecutive lanes)
 template <int LPR>
 __device__ __forceinline__ float row_sum(float v) {

@@ -9,30 +9,16 @@
 
 namespace {
 
-__device__ __forceinline__ float gelu_tanh_f(float x) { // ggml_gelu (tanh form), the reference's activation everywhere
-    // 0.5 x (1 + tanh(u)) = x * sigmoid(2u) = x / (1 + exp2(x * w)): exp2 -> inf gives -0, exp2 -> 0 gives x (no inf/inf);
-    // v_rcp instead of an IEEE division (a dozen VALU ops per element: the depthwise kernels were VALU bound on it)
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f; // -2 sqrt(2/pi) log2(e)
-    const float c3 = c1 * 0.044715f;
-    const float w = fmaf(x * x, c3, c1);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * w));
-}
-
 // ---- u8 rgb -> f16 [pixels][8]: (v/255 - mean) / std as value (channels 0..2) + f16 rounding residue (3..5), 6..7 zero
 // (sam_process_input, mobile-sam.cpp:533-547; the first conv's weights are duplicated on channels 3..5)
 __global__ void tv_preprocess_kernel(const uint8_t* __restrict__ rgb, f16* __restrict__ out, long n_pix) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pix) return;
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    f16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+    float v[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = ((float)rgb[i * 3 + c] / 255.0f + (0.0f - mean[c])) * (1.0f / stdv[c]); // image_u8_to_f32(img, -mean, 1/std)
-        const f16 hi = (f16)v;
-        o[c] = hi;
-        o[3 + c] = (f16)(v - (float)hi);
-    }
-    reinterpret_cast<f16x8*>(out)[i] = o;
+    for (int c = 0; c < 3; ++c) v[c] = ((float)rgb[i * 3 + c] / 255.0f + (0.0f - mean[c])) * (1.0f / stdv[c]); // image_u8_to_f32(img, -mean, 1/std)
+    reinterpret_cast<f16x8*>(out)[i] = residue_pixel(v);
 }
 
 // ---- depthwise 3x3, pad 1, stride 1 or 2, NHWC f16, weights [9][C] f16 (tap-major), bias f32 [C]; optional GELU
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(256) void tv_dwconv3x3_kernel(const f16* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float v = acc[p][j] + bv[j];
-            if (gelu) v = gelu_tanh_f(v);
+            if (gelu) v = gelu_tanh(v);
             o[j] = (f16)v;
         }
         *reinterpret_cast<f16x8*>(out + (long)p * C) = o;
@@ -292,15 +278,13 @@ __global__ void tv_add_gelu_kernel(const f16* __restrict__ a, const f16* __restr
     if (b) {
         const f16x8 bv = reinterpret_cast<const f16x8*>(b)[i];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (f16)gelu_tanh_f((float)av[j] + (float)bv[j]);
+        for (int j = 0; j < 8; ++j) o[j] = (f16)gelu_tanh((float)av[j] + (float)bv[j]);
     } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (f16)gelu_tanh_f((float)av[j]);
+        for (int j = 0; j < 8; ++j) o[j] = (f16)gelu_tanh((float)av[j]);
     }
     reinterpret_cast<f16x8*>(y)[i] = o;
 }
-
-unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // ---- y = a + b[i mod period] on f16 (a may be f32): the decoder's "queries + query_pe", "keys + key_pe" and
 // "image_embeddings + no_mask_embed" adds (mobile-sam.cpp:331-358, 437-440)

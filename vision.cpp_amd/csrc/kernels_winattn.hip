@@ -20,15 +20,7 @@ namespace {
 constexpr int WA_HD = 32;
 constexpr float WA_LOG2E = 1.44269504088896340736f;
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __fp16 hv4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-__device__ __forceinline__ float wa_other_half(float v) { // value of the lane that owns the same query in the other 32-lane half
-    const unsigned u = __float_as_uint(v);
-    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
 
 template <int QB>
 __global__ __launch_bounds__(QB * 64) void window_attention_kernel(const f16* __restrict__ qkv, const f16* __restrict__ bias, f16* __restrict__ out,
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(QB * 64) void window_attention_kernel(const f16* __
     }
     const f16* bp = bias + ((long)(head * QB + wave) * QB * 64 + lane) * 16;
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
 
     // loop-invariant LDS offsets: K fragment of d-step s at k_off[s] + kb * 32 rows; V^T transposed reads as in kernels_attn.hip
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(QB * 64) void window_attention_kernel(const f16* __
             s[e] = fmaf(s[e], scale, (float)(e < 8 ? b0[e & 7] : b1[e & 7])); // -inf on keys >= N
             mloc = fmaxf(mloc, s[e]);
         }
-        mloc = fmaxf(mloc, wa_other_half(mloc));
+        mloc = fmaxf(mloc, other_half(mloc));
         const float m_new = fmaxf(m_run, mloc * WA_LOG2E);
         if (__any(m_new > m_run)) {
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -135,7 +127,7 @@ __global__ __launch_bounds__(QB * 64) void window_attention_kernel(const f16* __
         }
     }
 
-    const float inv = 1.0f / (l_run + wa_other_half(l_run));
+    const float inv = 1.0f / (l_run + other_half(l_run));
     if (q < N) {
         f16* orow = out + ((long)win * N + q) * (heads * WA_HD) + head * WA_HD;
 #pragma unroll

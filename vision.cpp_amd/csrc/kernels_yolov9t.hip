@@ -180,17 +180,13 @@ __global__ __launch_bounds__(256) void decode_kernel(const f16* __restrict__ raw
     }
 }
 
-unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 } // namespace
 
 extern "C" int vx_yolo_preprocess(const uint8_t* img_u8, int channels, const float* img_f32, void* out8, int64_t n_pixels, void* stream) {
     VX_REQUIRE(out8 && (img_u8 != nullptr) != (img_f32 != nullptr), "vx_yolo_preprocess: exactly one of the u8 and f32 inputs, and an output");
     VX_REQUIRE(!img_u8 || channels == 3 || channels == 4, "vx_yolo_preprocess: %d channels (3 or 4)", channels);
     VX_REQUIRE(n_pixels > 0 && aligned16(out8), "vx_yolo_preprocess: empty or misaligned");
-    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks(n_pixels)), dim3(256), 0, as_stream(stream), img_u8, channels, img_f32, static_cast<f16*>(out8), (long)n_pixels);
+    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks_for(n_pixels)), dim3(256), 0, as_stream(stream), img_u8, channels, img_f32, static_cast<f16*>(out8), (long)n_pixels);
     VX_LAUNCH_CHECK();
     return 1;
 }
@@ -198,7 +194,7 @@ extern "C" int vx_yolo_preprocess(const uint8_t* img_u8, int channels, const flo
 extern "C" int vx_yolo_avgpool2_f16(const void* x, int64_t x_pix, void* y, int B, int H, int W, int C, void* stream) {
     VX_REQUIRE(x && y && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0 && x_pix >= C && x_pix % 8 == 0 && aligned16(x) && aligned16(y),
                "vx_yolo_avgpool2_f16: bad shape B=%d H=%d W=%d C=%d pix=%ld", B, H, W, C, (long)x_pix);
-    hipLaunchKernelGGL(avgpool2_kernel, dim3(blocks((long)B * (H - 1) * (W - 1) * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(x),
+    hipLaunchKernelGGL(avgpool2_kernel, dim3(blocks_for((long)B * (H - 1) * (W - 1) * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(x),
                        (long)x_pix, static_cast<f16*>(y), B, H, W, C);
     VX_LAUNCH_CHECK();
     return 1;
@@ -207,7 +203,7 @@ extern "C" int vx_yolo_avgpool2_f16(const void* x, int64_t x_pix, void* y, int B
 extern "C" int vx_yolo_spp_f16(void* buf, int64_t pix, int B, int H, int W, int C, void* stream) {
     VX_REQUIRE(buf && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && pix >= 4 * C && pix % 8 == 0 && aligned16(buf),
                "vx_yolo_spp_f16: bad shape B=%d H=%d W=%d C=%d pix=%ld", B, H, W, C, (long)pix);
-    hipLaunchKernelGGL(spp_kernel, dim3(blocks((long)B * H * W * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<f16*>(buf), (long)pix, B, H, W, C);
+    hipLaunchKernelGGL(spp_kernel, dim3(blocks_for((long)B * H * W * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<f16*>(buf), (long)pix, B, H, W, C);
     VX_LAUNCH_CHECK();
     return 1;
 }
@@ -216,7 +212,7 @@ extern "C" int vx_yolo_upsample2_f16(const void* x, int64_t x_pix, void* y, int6
     VX_REQUIRE(x && y && B > 0 && h > 0 && w > 0 && C > 0 && C % 8 == 0 && x_pix >= C && y_pix >= C && x_pix % 8 == 0 && y_pix % 8 == 0 && aligned16(x) &&
                    aligned16(y),
                "vx_yolo_upsample2_f16: bad shape B=%d h=%d w=%d C=%d", B, h, w, C);
-    hipLaunchKernelGGL(upsample2_kernel, dim3(blocks((long)B * 4 * h * w * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(x), (long)x_pix,
+    hipLaunchKernelGGL(upsample2_kernel, dim3(blocks_for((long)B * 4 * h * w * (C / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(x), (long)x_pix,
                        static_cast<f16*>(y), (long)y_pix, B, h, w, C);
     VX_LAUNCH_CHECK();
     return 1;
@@ -230,7 +226,7 @@ extern "C" int vx_yolo_decode(const void* raw0, const void* raw1, const void* ra
     VX_REQUIRE((cand_count != nullptr) == (cand_idx != nullptr) && (cand_idx != nullptr) == (cand_score != nullptr),
                "vx_yolo_decode: the candidate list needs count, index and score buffers");
     const long A = (long)(S / 8) * (S / 8) + (long)(S / 16) * (S / 16) + (long)(S / 32) * (S / 32);
-    hipLaunchKernelGGL(decode_kernel, dim3(blocks((long)B * A * (4 + nc / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(raw0),
+    hipLaunchKernelGGL(decode_kernel, dim3(blocks_for((long)B * A * (4 + nc / 8))), dim3(256), 0, as_stream(stream), static_cast<const f16*>(raw0),
                        static_cast<const f16*>(raw1), static_cast<const f16*>(raw2), B, S, nc, boxes, scores, conf, cand_count, cand_idx, cand_score);
     VX_LAUNCH_CHECK();
     return 1;
