@@ -1,0 +1,130 @@
+"""Fingerprints of what the graph lowering produces, for comparing two builds of the library (a refactor of csrc/lower_*.cpp must not move
+any of them). One line per case: the sha256 of `describe()` (launch list + launches / nodes / buffers / arena_bytes / unshared_bytes /
+constant_bytes) of a planning-only graph, or the error text where a graph does not lower. No device is needed for these.
+
+With --device the weight arenas of Depth-Anything SMALL and ESRGAN_TINY (fixed seeds) are copied back and hashed -- pack order and pack
+contents -- and so are the two models' outputs on fixed inputs.
+
+Usage: python tools/lowering_fingerprint.py [--device] [--out FILE] [substring of the case names to run ...]
+       VISP_LIBRARY=/path/to/other/libvisioncpp.so selects the build."""
+import argparse
+import hashlib
+import sys
+import tempfile
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+from __graft_entry__ import load_package  # noqa: E402
+
+load_package()
+import numpy as np  # noqa: E402
+from visioncpp_amd import _lib as L  # noqa: E402
+from visioncpp_amd import graph as G  # noqa: E402
+from visioncpp_amd import synth  # noqa: E402
+
+import graph_cases as GC  # noqa: E402
+
+
+def sha(data) -> str:
+    return hashlib.sha256(data if isinstance(data, (bytes, bytearray, memoryview)) else str(data).encode()).hexdigest()
+
+
+def planned(build) -> str:
+    try:
+        g = build()
+        g.allocate()
+        text = g.describe()
+        return f"{sha(text)} {text.strip().splitlines()[-1]}"
+    except L.Error as e:
+        return f"error: {e}"
+
+
+def cases(tmp: Path):
+    for cfg in (synth.MINI, synth.TINY, synth.SMALL, synth.BASE, synth.LARGE):
+        side = cfg.image_size - cfg.image_size % cfg.patch_size
+        path = None
+        for w, h in ((side, side), (518, 784)):  # 784 / 14 = 56 patches: the 1/7-level map is 112 px on that side
+            for fused in (True, False):
+                def build(cfg=cfg, w=w, h=h, fused=fused):
+                    nonlocal path
+                    path = path or synth.write_gguf(tmp / f"{cfg.name}.gguf", cfg, seed=0)
+                    g = G.Graph(None, G.Weights(path))
+                    g.set_fused_models(fused)
+                    G.depthany_predict(G.ModelRef(g), g.input((3, w, h, 2), G.F32, "image"), cfg.n_layers, cfg.n_heads, cfg.patch_size, cfg.feature_layers)
+                    return g
+                yield f"depthany_{cfg.name}_{w}x{h}_{'fused' if fused else 'per_node'}", build
+    for cfg in (synth.ESRGAN_TINY, synth.ESRGAN_X4):
+        def build(cfg=cfg):
+            g = G.Graph(None, G.Weights(synth.write_esrgan_gguf(tmp / f"esrgan_{cfg.name}.gguf", cfg, 7)))
+            G.esrgan_generate(G.ModelRef(g), g.input((3, 40, 56, 3), G.F32, "image"), cfg.scale, cfg.num_blocks)
+            return g
+        yield f"esrgan_{cfg.name}_40x56", build
+
+    def case(fn, *args):
+        def build():
+            g = G.Graph(None)
+            fn(g, np.random.default_rng(0), *args)
+            return g
+        return build
+    yield "conv_relu_add_64", case(GC.conv_relu_add, 64)
+    yield "conv_relu_add_32", case(GC.conv_relu_add, 32)
+    yield "residual_unit_on_planes", case(GC.residual_unit_on_planes)
+    yield "relu_into_output_conv_nhwc", case(GC.relu_into_output_conv, False)
+    yield "relu_into_output_conv_planar", case(GC.relu_into_output_conv, True)
+    yield "conv_leaky_0.2", case(GC.conv_leaky, 0.2)
+    yield "conv_leaky_0.1", case(GC.conv_leaky, 0.1)
+    yield "encoder_chain_equal_scales", case(GC.encoder_chain, [0.125, 0.125])
+    yield "encoder_chain_differing_scales", case(GC.encoder_chain, [0.125, 0.25])
+
+
+def device_cases(tmp: Path):
+    from visioncpp_amd import vision
+
+    dev = vision.Device.init(vision.Backend.gpu)
+
+    def arena(model):
+        ptr, n = model.weights_arena()
+        host = np.empty(n, np.uint8)
+        L.vx_check(L.get_lib().vx_memcpy_d2h(host.ctypes.data, ptr, n, None))
+        L.vx_check(L.get_lib().vx_stream_sync(None))
+        return f"{sha(host.tobytes())} bytes={n}"
+
+    model = vision.Model.load(synth.write_gguf(tmp / "dev_small.gguf", synth.SMALL, seed=0), dev)
+    yield "device_depthany_small_arena", arena(model)
+    out, raw = model.compute_batch(synth.images(2, 518, 518, seed=12), return_raw=True)
+    yield "device_depthany_small_output_518x518", sha(np.ascontiguousarray(out).tobytes()) + " raw " + sha(np.ascontiguousarray(raw).tobytes())
+    out = model.compute_batch(synth.images(2, 784, 518, seed=13))
+    yield "device_depthany_small_output_784x518", sha(np.ascontiguousarray(out).tobytes())
+    emodel = vision.Model.load(synth.write_esrgan_gguf(tmp / "dev_esrgan_tiny.gguf", synth.ESRGAN_TINY, seed=7), dev)
+    yield "device_esrgan_tiny_arena", arena(emodel)
+    yield "device_esrgan_tiny_output_72x56", sha(np.ascontiguousarray(emodel.upscale_batch(synth.images(1, 72, 56, seed=5))).tobytes())
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--device", action="store_true", help="also hash the weight arenas and outputs of two models on the GPU")
+    ap.add_argument("--out", help="write the lines to this file as well")
+    ap.add_argument("only", nargs="*", help="run the cases whose name contains one of these")
+    args = ap.parse_args()
+    lines = []
+
+    def put(name, value):
+        lines.append(f"{name}: {value}")
+        print(lines[-1], flush=True)
+
+    with tempfile.TemporaryDirectory() as td:
+        for name, build in cases(Path(td)):
+            if not args.only or any(s in name for s in args.only):
+                put(name, planned(build))
+        if args.device:
+            for name, value in device_cases(Path(td)):
+                put(name, value)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

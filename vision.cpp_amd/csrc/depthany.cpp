@@ -391,9 +391,9 @@ void depthany_weights_ready(depthany_model& m) {
         auto t = ws.tensors.find(name);
         if (t == ws.tensors.end()) throw except("depthany: tensor %s is missing", name);
         std::vector<float>& host = t->second.data;
-        if (auto p = ws.packs.find({name, 0}); p != ws.packs.end()) { // its f32 image
+        if (auto p = ws.packs.find({name, role_f32}); p != ws.packs.end()) { // its f32 image
             VX(vx_memcpy_d2h(host.data(), p->second, host.size() * 4, m.backend->stream));
-        } else if (auto q = ws.packs.find({name, 1}); q != ws.packs.end()) { // its f16 image (what the per-node lowering concatenates into the tokens)
+        } else if (auto q = ws.packs.find({name, role_f16}); q != ws.packs.end()) { // its f16 image (what the per-node lowering concatenates into the tokens)
             std::vector<uint16_t> h(host.size());
             VX(vx_memcpy_d2h(h.data(), q->second, h.size() * 2, m.backend->stream));
             for (size_t i = 0; i < h.size(); ++i) host[i] = f16_to_f32(h[i]);

@@ -93,6 +93,30 @@ struct graph_launch {
     double flops = 0, bytes = 0; // algorithmic work of the launch (2 x MACs; operand bytes), for the roofline lines
 };
 
+// Which device image of a weight a (name, role) key of weight_store::packs holds. The numbers are part of the store's keys: two
+// kinds that shared one would silently alias two different images of a weight, so a new kind gets a new number.
+enum pack_role : int {
+    role_f32 = 0,            // the values as they are, f32 (vectors, position embeddings, the one-channel head's kernel)
+    role_f16 = 1,            // the values as f16 (constants a copy launch concatenates into activations)
+    role_rows = 2,           // GEMM operand: f16 rows [N pad][K pad 64] of a linear / conv weight
+    role_conv_transpose = 3, // GEMM operand of conv_transpose: rows in pixel-shuffle order
+    role_qkv = 4,            // q | k | v rows of three linears as one operand (keyed on q's weight)
+    role_head_frag = 5,      // the DPT head's 3x3 kernel as the head kernel's MFMA fragments
+    role_dconv = 6,          // LDS-ring conv slabs [cin / 32][9][cout][32]
+    role_rcu = 7,            // residual-unit kernel operand [taps][64][64], swizzled
+    role_dconv_ex = 8,       // LDS-ring conv slabs with repeated input columns / padded outputs
+    role_bias_padded = 9,    // f32 bias zero-padded to a kernel's channel count
+    role_bias_base = 16,     // 16..24: bias_of_role(r), the f32 bias [N pad] that goes with the operand of role r (0..8)
+    role_block_mlp = 40,     // block kernel: out-proj | fc1 | fc2 fragments, LayerScale folded (keyed on the out-proj weight)
+    role_block_qkv = 41,     // block kernel: q | k | v fragments
+    role_block_mlp_vec = 42, // block kernel: biases, lambdas and LN2 of the MLP half as one f32 vector
+    role_block_qkv_vec = 43, // block kernel: LN1 and the q | k | v biases as one f32 vector
+    role_tap_vec = 44,       // block kernel: the taps' final LayerNorm weight | bias
+};
+constexpr pack_role bias_of_role(pack_role r) { return static_cast<pack_role>(role_bias_base + r); }
+static_assert(bias_of_role(role_rows) == 18 && bias_of_role(role_qkv) == 20 && bias_of_role(role_dconv_ex) == 24 && role_bias_padded < role_bias_base,
+              "16..24 are reserved for the biases of roles 0..8");
+
 // model_weights (ml.h:126-149): the tensors of a model by name, f32 on the host, and -- once a graph over them has been allocated on a
 // device -- their packed device images per consumer role (GEMM operand, pixel-shuffle rows, f32 vector, ...). Shared by every graph built
 // over the model: rebuilding the graph for another input extent (the reference's lazy graph build, vision.cpp:150-158) uploads nothing.

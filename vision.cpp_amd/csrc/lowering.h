@@ -1,0 +1,194 @@
+// The lowering of a graph into its launch list (graph_allocate, graph.h): internal to the graph layer. One struct, its state gathered
+// here, its member functions defined by concern in
+//   lower_weights.cpp  device images of weights and constants (cached / upload / pack_*)
+//   lower_conv.cpp     matrix products and convolutions with their fused epilogues, the planar maps, the DPT neck / head patterns
+//   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
+//   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
+// Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
+// a `return false` leaves the lowering's state as it was.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/visp_hip_kernels.h"
+#include "graph.h"
+#include "visp_util.h"
+
+namespace visp {
+
+std::string shape_str(const int64_t ne[4]); // graph.cpp
+
+struct packed_operand {
+    void* w = nullptr;
+    float* bias = nullptr;
+    int N = 0, K = 0, n_real = 0, k_real = 0;
+};
+
+struct lowering {
+    graph& g;
+
+    // ---- liveness and fusion marks (run): which nodes any output needs, who reads them; skip: computed by another node's launch
+    std::vector<char> needed, skip;
+    std::vector<int> uses;
+    std::vector<std::vector<int>> consumers;
+    std::vector<char> relu_on_load; // conv node -> the ReLU in front of it is applied by its loader
+
+    // ---- the launch list's buffer traffic (emit; read by plan_arena)
+    std::vector<std::pair<std::vector<int>, std::vector<int>>> io; // per launch: buffers read, buffers written
+
+    // ---- weight images (lower_weights.cpp)
+    std::map<std::pair<std::pair<int, int>, std::string>, void*> const_cache; // (node, role, derived-from) -> device copy made for this graph
+
+    // ---- inputs that a consumer reads in place instead of through a copy / a resize launch (g.fused_models)
+    struct sliced_rows { int src; int64_t begin, rows, stride; };  // rows [begin, begin + rows) of every group of `stride` rows of src
+    std::map<int, sliced_rows> sliced_in;                           // slice node -> what its (sole, plain-GEMM) reader addresses directly
+    struct resized_map { int buf; int hs, ws; };                    // the bilinear (align_corners) resize of [.., ws, hs, B] in `buf`
+    std::map<int, resized_map> resized_in;                          // interpolate / projected node -> what its (sole) conv reader interpolates itself
+    std::map<int, int> row_stride;                                  // node -> elements between rows when its buffer is padded for a GEMM reader
+    std::map<int, int> preprojected; // interpolate node -> buffer that already holds the 1x1 projection of its SOURCE (written by the residual-unit launch)
+
+    // ---- maps kept as 32-channel PLANES ([plane][B * H * W][32] f16) -- the layout the LDS-ring conv was built on for the ESRGAN dense blocks
+    // (kernels_dconv.hip; profiles/r04_esrgan_layout_experiment.txt: 5 % faster than NHWC). Layout is this lowering's choice: a map is planar when
+    // the conv that writes it read a planar map (or the f32 image), every reader that is such a conv takes it as it is, and any other reader gets
+    // an NHWC copy made on first use. A channel concat of planar maps is then no launch at all: the dense block [x | x1 | x2 | x3 | x4] of
+    // esrgan.cpp:27-41 is six planes of ONE buffer, x written by its producer into planes 0-1, every conv_block into the plane behind its input.
+    struct planar_map { int buf; int plane0; int n_planes; int64_t plane_elems; };
+    std::map<int, planar_map> planar;                 // ROOT node -> where it lives
+    std::map<int, std::pair<int, int>> placed;        // node a concat chain will read -> (buffer, first plane) reserved for it
+    std::map<int, int> up2_of;                        // interpolate(NEAREST, x2) node -> its (planar) source, resized by the reading conv's loader
+    std::map<int, int> image_plane;                   // f32 image input -> buffer of its value | residue plane
+
+    // ---- attention and the encoder chain (lower_encoder.cpp)
+    std::map<int, int> qkv_first;                 // first of the three linears (node order) -> attention node
+    std::map<int, std::array<int, 3>> qkv_lin;    // attention node -> its three linears
+    std::map<int, std::array<int, 3>> qkv_bufs;   // attention node -> head-major buffers, once the fused launch is emitted
+    struct enc_layer {
+        int ln1 = -1, lin[3] = {-1, -1, -1}, att = -1, o = -1, s1 = -1, x1 = -1, ln2 = -1, f1 = -1, ge = -1, f2 = -1, s2 = -1, x2 = -1;
+        int lam1 = -1, lam2 = -1;
+        std::vector<int> taps;
+    };
+    struct enc_chain {
+        bool ok = false;
+        int img = -1, u8 = -1, pe = -1, resh = -1, cat = -1, tok = -1, cls = -1, pos = -1, first = -1;
+        std::vector<int> views;
+        std::vector<enc_layer> layers;
+    } enc;
+
+    explicit lowering(graph& gr) : g(gr) {}
+    void run(); // the whole lowering: fills g.launches / g.buffers / the arena plan
+
+    // ---- nodes, buffers, launches
+    int root(int t) const {
+        while (g.nodes[t].alias_of >= 0) t = g.nodes[t].alias_of;
+        return t;
+    }
+    int root_view(int v) const { // the node behind reshape / cont views (before aliases are assigned)
+        while (g.nodes[v].op == gop_reshape || g.nodes[v].op == gop_cont) v = g.nodes[v].src[0];
+        return v;
+    }
+    // the sole reader of t, if it is not an output
+    int sole_consumer(int t) const { return uses[t] == 1 && !g.nodes[t].is_output && consumers[t].size() == 1 ? consumers[t][0] : -1; }
+    int buf_of(int t) {
+        const int r = root(t);
+        if (g.nodes[r].buffer < 0 && planar.count(r)) planar_to_nhwc(r); // a reader outside the LDS-ring conv: the map as NHWC, once
+        const int b = g.nodes[r].buffer;
+        if (b < 0) throw except("graph: tensor %d (%s) is read before it is computed", t, graph_op_name(g.nodes[t].op));
+        return b;
+    }
+    int new_buffer(size_t bytes, bool persistent = false) {
+        graph_buffer b;
+        b.bytes = round_up<size_t>(bytes, 256) + 256;
+        b.persistent = persistent;
+        b.first = b.last = (int)g.launches.size();
+        g.buffers.push_back(b);
+        return (int)g.buffers.size() - 1;
+    }
+    void materialise(int t) {
+        graph_node& n = g.nodes[t];
+        n.buffer = new_buffer(n.n_bytes(), n.is_output || n.op == gop_input);
+    }
+    void emit(std::string desc, std::vector<int> reads, std::vector<int> writes, std::function<void(void*)> run) {
+        graph_launch l;
+        l.desc = std::move(desc);
+        l.run = std::move(run);
+        g.launches.push_back(std::move(l));
+        io.emplace_back(std::move(reads), std::move(writes));
+    }
+    void tag(const char* group, double flops = 0, double bytes = 0) { // timing group and algorithmic work of the launch emitted last
+        graph_launch& l = g.launches.back();
+        l.group = group;
+        l.flops = flops;
+        l.bytes = bytes;
+    }
+    // device pointer of a buffer at run time (offsets are assigned after the launch list is complete)
+    std::function<char*()> ptr(int buf) {
+        graph* gp = &g;
+        return [gp, buf]() {
+            graph_buffer const& b = gp->buffers[buf];
+            return b.external ? static_cast<char*>(b.external) : static_cast<char*>(gp->arena.ptr) + b.offset;
+        };
+    }
+    // src[0]'s buffer in, a freshly materialised buffer of t out (and `scratch_bytes` of a further buffer the launch writes): one launch
+    void map_launch(int t, std::string desc, std::function<void(char* x, char* out, char* scratch, void* stream)> run, size_t scratch_bytes = 0);
+
+    // ---- lower_weights.cpp
+    void* cached(int t, pack_role role, std::function<void*(bool)> make, std::string const& with = {});
+    void* upload(const void* host, size_t bytes, bool to_store);
+    float* const_f32(int t);
+    void* const_f16(int t);
+    float* vec_cached(int key_node, pack_role role, std::string const& with, std::function<std::vector<float>()> make_host);
+    float* bias_padded(int bt, int n_pad);
+    packed_operand pack_matrix(int wt, pack_role role, int n, int k, std::function<float(int, int)> at, int bias_t, int bias_period, int scale_t = -1);
+    packed_operand pack_rows(int wt, int bias_t, int n, int scale_t = -1);
+    packed_operand pack_qkv(const int lin[3]);
+    packed_operand pack_conv_transpose(int wt, int bias_t, int s);
+    void* pack_head_fragments(int wt, int cin);
+    void* pack_dconv(int wt, int cin, int cout, int* d_cin);
+    void* pack_dconv_ex(int wt, int cin, int dup, int cout, int cout_pad, int* d_cin);
+    void* pack_rcu(int wt, int taps);
+
+    // ---- lower_conv.cpp
+    // What a product's launch takes over from the nodes behind it: [* LayerScale] [gelu | relu | leaky_relu] [(* s1) + res] [(* s2) + res2].
+    // A matcher fills it and changes nothing; absorb() applies exactly what was matched.
+    struct epilogue {
+        int act = 0; // 1 gelu (the planar conv: leaky_relu 0.2), 2 relu
+        int res = -1, res2 = -1, last = -1, scale = -1;
+        float s1 = 1.0f, s2 = 1.0f; // the planar conv's factors in front of its residual steps
+        std::vector<int> absorbed;  // the nodes this launch computes besides its own
+    };
+    epilogue match_epilogue(int t, bool allow_gelu, bool allow_scale = false, bool allow_two = false, bool res_after_relu = true) const;
+    epilogue match_planar_epilogue(int t) const;
+    void absorb(epilogue const& e, int into);
+    bool residual_ready(int other, int t) const;
+    struct residual_ptrs { std::function<char*()> res1, res2; };
+    residual_ptrs read_residuals(epilogue const& e, std::vector<int>& reads);
+    int padded_rows(int t, int K, int Kp, int64_t M, std::string const& who);
+    int plain_gemm_reader(int t) const;
+    bool dconv_shape(graph_node const& n, graph_node const& x, graph_node const& w) const;
+    void gemm_like(int t);
+    void dconv(int t, std::string const& who);
+    bool residual_unit(int t, std::string const& who);
+    bool planar_conv(int t, std::string const& who);
+    void planar_to_nhwc(int r);
+    bool nearest_into_reader(int t);
+    bool resize_into_reader(int t);
+    bool head_tail(int t);
+    void one_channel_head(int t);
+
+    // ---- lower_encoder.cpp
+    void find_qkv_groups();
+    void fused_qkv(int att);
+    void attention(int t);
+    void patch_embed(int t);
+    bool match_layer(int att, enc_layer& L) const;
+    void find_encoder_chain();
+    void emit_encoder();
+
+    // ---- lower_run.cpp
+    void copy_op(int t);
+    void plan_arena();
+};
+
+} // namespace visp
