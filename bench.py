@@ -3,7 +3,7 @@
 (`--workload esrgan` measures the next row to the same contract: Real-ESRGAN-4x f16, 256^2 -> 1024^2, batch 16,
 BASELINE.json configs[2].)
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: started without RANK in the environment, `--gpus N` launches the second form itself as a
@@ -15,9 +15,13 @@ pre-process, DINOv2-S encoder, DPT neck/head, min-max normalise) over one batch 
 batch is sharded across ranks with no data-path collective (weak scaling: 32 images per GPU);
 RCCL is used once, at load, to broadcast the packed weight arena from rank 0.
 
-Rank 0 prints ONE JSON line. `roofline` is measured live with HIP events on the compute stream
-(per kernel group, non-graph pass); `cpu_baseline` times the CPU oracle (oracle/, a port of the
-reference's ggml CPU path) on a bounded sample on this box's host cores.
+Rank 0 prints ONE JSON line. A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps,
+the `--dump-outputs` arrays, the line. `--full` adds everything else the benchmark measures, each in a pass of its own
+outside the timed steps: `roofline` and the per-kernel-group tables, measured live with HIP events on the compute stream
+(non-graph passes before the warm-up); the soak (`value_soak`); the upload + compute + download figure
+(`value_incl_h2d_d2h`); `cpu_baseline`, which times the CPU oracle (oracle/, a port of the reference's ggml CPU path) on a
+bounded sample of the host's cores and reports the parity of the timed output against it; for `--workload sam` also the
+single-image latencies and the error of `--fp8`. `value` and `ms_per_step` mean the same with and without it.
 """
 from __future__ import annotations
 
@@ -159,15 +163,19 @@ def main():
     ap.add_argument("--workload", choices=["depthany", "esrgan", "sam", "swin", "birefnet"], default="depthany",
                     help="depthany = the headline metric (BASELINE.json configs[1]); esrgan = configs[2], the next SURVEY section 8 row")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default 32 for depthany, 16 for esrgan, 128 for sam, 8 for swin and birefnet)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="next to the headline figure also measure the per-kernel-group tables and the roofline, the soak, the host-pipeline figure and the CPU baseline "
+                         "(off: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--min-seconds", type=float, default=10.0, help="soak: after the K timed steps keep stepping for this long and report that rate too (0 = skip)")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the upload + compute + download (host pipeline) figure")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="with --full, soak: after the K timed steps keep stepping for this long and report that rate too (default 10, 0 = skip)")
+    ap.add_argument("--no-pipeline", action="store_true", help="with --full: skip the upload + compute + download (host pipeline) figure")
     ap.add_argument("--schedule", type=int, default=-1, help="depthany encoder schedule: -1 = the library's default (block kernel), 0 = GEMM launches, 1 = token-stationary block kernel")
     ap.add_argument("--fp8", action="store_true", help="sam workload only, opt-in: the transformer stages' MLPs on the e4m3 matrix instruction (BASELINE.json configs[4]); reports the embedding error next to the rate")
     ap.add_argument("--cpu-images", type=int, default=32, help="bounded CPU-baseline sample (about 10 s at 16 threads)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="OpenMP threads of the CPU baseline (one GPU's share of the host)")
-    ap.add_argument("--profile-groups", action="store_true", help="print the per-kernel-group table to stderr")
+    ap.add_argument("--profile-groups", action="store_true", help="with --full: print the per-kernel-group table to stderr")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path on one GPU)")
     ap.add_argument("--device", type=int, default=None, help="force this HIP device for every rank (gloo rehearsal only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -180,6 +188,13 @@ def main():
         ap.error("--dump-outputs is implemented for the depthany workload only")
     if args.pipeline_child:
         return pipeline_child(args)
+    if args.full:
+        if args.min_seconds is None:
+            args.min_seconds = 10.0
+    else:  # a plain run: nothing next to the headline figure
+        if args.profile_groups or (args.min_seconds or 0) > 0:
+            ap.error("--profile-groups and --min-seconds measure next to the headline figure: add --full")
+        args.min_seconds, args.no_pipeline, args.no_cpu_baseline = 0.0, True, True
 
     import torch
 
@@ -241,9 +256,9 @@ def main():
     def step():
         model.compute_batch_device(rgb.data_ptr(), B, W, H, out.data_ptr(), None, stream)
 
-    # ---- per-kernel-group timing (direct launches, HIP events on the compute stream), untimed
+    # ---- --full: per-kernel-group timing (direct launches, HIP events on the compute stream), untimed
     groups = []
-    if rank == 0:
+    if args.full and rank == 0:
         step()
         torch.cuda.synchronize()
         model.enable_timing(True)
@@ -365,7 +380,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f16",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": "Depth-Anything-V2-Small f16 (DINOv2-S ViT) 518x518 batch=32 per MI355X (BASELINE.json configs[1])",
                        "images_per_gpu_per_step": B, "global_batch": world * B, "weights": "random-init synthetic GGUF (seed 0)",
                        "parallelism": f"dp{world} (image shards, no data-path collective)", "hip_graph": not args.no_graph,
@@ -501,7 +516,7 @@ def run_esrgan(args, torch, dist, rank, world, device_index, barrier, api):
         model.upscale_batch_device(src.data_ptr(), B, W, H, out.data_ptr(), vision.ImageFormat.rgb_u8, stream)
 
     groups = []
-    if rank == 0:
+    if args.full and rank == 0:
         step()
         torch.cuda.synchronize()
         model.enable_timing(True)
@@ -547,7 +562,7 @@ def run_esrgan(args, torch, dist, rank, world, device_index, barrier, api):
         "step_ms_device": {"mean": round(float(np.mean(step_ms)), 3), "std": round(float(np.std(step_ms)), 3), "min": round(float(np.min(step_ms)), 3),
                            "note": "rank 0, HIP events at the step boundaries of the same timed region"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16", "data": "synthetic",
+        "dtype": "f16", "data": "synthetic", "full": args.full,
         "config": {"workload": "Real-ESRGAN-4x f16 (RRDB conv stack) 256x256 -> 1024x1024 batch=16 per MI355X (BASELINE.json configs[2])",
                    "images_per_gpu_per_step": B, "global_batch": world * B, "weights": "random-init synthetic GGUF (seed 1)",
                    "tiling": "224 max / overlap 16 / align 16 as the reference: 4 tiles of 144x144 per image, 64 tiles per step",
@@ -615,15 +630,17 @@ def run_sam(args, torch, dist, rank, world, device_index, barrier, api):
 
     fp8_err = None
     if args.fp8:  # opt-in (configs[4] "fp8 GGUF weights on CDNA4 fp8 MFMA"): the stage MLPs on the e4m3 matrix instruction; the f16 result first, for the error
-        step()
-        torch.cuda.synchronize()
-        ref = out[:8].clone()
+        if args.full:
+            step()
+            torch.cuda.synchronize()
+            ref = out[:8].clone()
         model.sam_set_fp8_mlp(True)
-        step()
-        torch.cuda.synchronize()
-        fp8_err = float((out[:8] - ref).abs().mean() / ref.abs().mean())
+        if args.full:
+            step()
+            torch.cuda.synchronize()
+            fp8_err = float((out[:8] - ref).abs().mean() / ref.abs().mean())
     groups = []
-    if rank == 0:
+    if args.full and rank == 0:
         step()
         torch.cuda.synchronize()
         model.enable_timing(True)
@@ -667,7 +684,7 @@ def run_sam(args, torch, dist, rank, world, device_index, barrier, api):
         "step_ms_device": {"mean": round(float(np.mean(step_ms)), 3), "std": round(float(np.std(step_ms)), 3), "min": round(float(np.min(step_ms)), 3),
                            "note": "rank 0, HIP events at the step boundaries of the same timed region"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16 (stage MLPs e4m3)" if args.fp8 else "f16", "data": "synthetic",
+        "dtype": "f16 (stage MLPs e4m3)" if args.fp8 else "f16", "data": "synthetic", "full": args.full,
         "config": {"workload": f"MobileSAM TinyViT encoder 1024x1024 f16, batch={B} per MI355X (BASELINE.json configs[4] names fp8 weights and a "
                                "1k-image batch over 8 GPUs: this row is the f16 encoder, image shards per rank)" + (
                                    " -- with --fp8: the transformer stages' MLPs on the block-scaled e4m3 matrix instruction (opt-in, never the default)" if args.fp8 else ""),
@@ -705,21 +722,22 @@ def run_sam(args, torch, dist, rank, world, device_index, barrier, api):
                 res["roofline"]["traffic"] = round(k["hbm_bytes_per_launch"] * B / 16)
                 res["roofline"]["traffic_source"] = "profiles/r01_pmc/traffic_sam.json (FETCH_SIZE x2 + WRITE_SIZE, collected at batch 16, scaled by batch)"
         res["kernel_groups_ms"] = {g["name"]: round(g["ms"], 3) for g in groups}
-    # configs[0] of BASELINE.json (encode + decode of one 1024x1024 image), outside the timed region: latency of the reference
+    # --full: configs[0] of BASELINE.json (encode + decode of one 1024x1024 image), outside the timed region: latency of the reference
     # API calls sam_encode / sam_compute from host buffers (decode = prompt encoder + mask decoder on the GPU + the reference's
     # host-side mask resize / threshold)
-    model.sam_encode(imgs[0])
-    model.sam_compute([300, 300])  # first calls allocate the staging / decoder scratch
-    t0 = time.perf_counter()
-    for k in range(5):
-        model.sam_encode(imgs[k % len(imgs)])
-    t1 = time.perf_counter()
-    for k in range(10):
-        mask = model.sam_compute([400 + 40 * k, 500])
-    t2 = time.perf_counter()
-    assert mask.shape == (S, S) and set(np.unique(mask)) <= {0, 255}
-    res["single_image_latency_ms"] = {"sam_encode": round(1e3 * (t1 - t0) / 5, 2), "sam_compute": round(1e3 * (t2 - t1) / 10, 2),
-                                      "note": "steady state, host buffers in, u8 mask out; batch 1; not part of value"}
+    if args.full:
+        model.sam_encode(imgs[0])
+        model.sam_compute([300, 300])  # first calls allocate the staging / decoder scratch
+        t0 = time.perf_counter()
+        for k in range(5):
+            model.sam_encode(imgs[k % len(imgs)])
+        t1 = time.perf_counter()
+        for k in range(10):
+            mask = model.sam_compute([400 + 40 * k, 500])
+        t2 = time.perf_counter()
+        assert mask.shape == (S, S) and set(np.unique(mask)) <= {0, 255}
+        res["single_image_latency_ms"] = {"sam_encode": round(1e3 * (t1 - t0) / 5, 2), "sam_compute": round(1e3 * (t2 - t1) / 10, 2),
+                                          "note": "steady state, host buffers in, u8 mask out; batch 1; not part of value"}
     if world == 1 and not args.no_cpu_baseline:
         from oracle import oracle
 
@@ -766,7 +784,7 @@ def run_swin(args, torch, dist, rank, world, device_index, barrier, api):
         model.encode_batch_device(src.data_ptr(), B, S, S, ptrs, stream)
 
     groups = []
-    if rank == 0:
+    if args.full and rank == 0:
         step()
         torch.cuda.synchronize()
         model.enable_timing(True)
@@ -810,7 +828,7 @@ def run_swin(args, torch, dist, rank, world, device_index, barrier, api):
         "step_ms_device": {"mean": round(float(np.mean(step_ms)), 3), "std": round(float(np.std(step_ms)), 3), "min": round(float(np.min(step_ms)), 3),
                            "note": "rank 0, HIP events at the step boundaries of the same timed region"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16", "data": "synthetic",
+        "dtype": "f16", "data": "synthetic", "full": args.full,
         "config": {"workload": f"SWIN-T encoder (the backbone of BiRefNet-lite, BASELINE.json configs[3]) 1024x1024 f16, batch={B} per MI355X; "
                                "encoder only (the whole BiRefNet is --workload birefnet)",
                    "images_per_gpu_per_step": B, "global_batch": world * B, "weights": "random-init synthetic GGUF (seed 4)",
@@ -879,7 +897,7 @@ def run_birefnet(args, torch, dist, rank, world, device_index, barrier, api):
         model.segment_batch_device(src.data_ptr(), B, S, S, out.data_ptr(), stream)
 
     groups = []
-    if rank == 0:
+    if args.full and rank == 0:
         step()
         torch.cuda.synchronize()
         model.enable_timing(True)
@@ -923,7 +941,7 @@ def run_birefnet(args, torch, dist, rank, world, device_index, barrier, api):
         "step_ms_device": {"mean": round(float(np.mean(step_ms)), 3), "std": round(float(np.std(step_ms)), 3), "min": round(float(np.min(step_ms)), 3),
                            "note": "rank 0, HIP events at the step boundaries of the same timed region"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16", "data": "synthetic",
+        "dtype": "f16", "data": "synthetic", "full": args.full,
         "config": {"workload": f"BiRefNet-lite f16 (SWIN-T shifted-window attention, deformable-conv decoder) 1024x1024, batch={B} per MI355X "
                                "(BASELINE.json configs[3]: batch 64 over 8 GPUs)",
                    "images_per_gpu_per_step": B, "global_batch": world * B, "weights": "random-init synthetic GGUF (seed 4)",

@@ -6,7 +6,7 @@ tag=${1:-r02}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - > /dev/null
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --min-seconds 0 --no-pipeline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --min-seconds 0 --no-pipeline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
 db=$(ls $out/trace/*/*.db $out/trace/*.db 2>/dev/null | head -1)
 echo "db: $db"
 python3 tools/rocpd_stats.py "$db" $out/kernel_stats.csv
