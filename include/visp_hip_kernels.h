@@ -88,7 +88,8 @@ typedef struct {
     /* implicit-GEMM conv (conv_kh > 0): A is [B, H, W, Cin] f16, m = (b, oy, ox), k = (ky, kx, c) */
     int conv_kh, conv_kw, conv_stride, conv_pad;
     int conv_H, conv_W, conv_Cin, conv_OH, conv_OW;
-    int a_relu;         /* apply ReLU to A elements while loading (depth-anything.cpp:17,19)    */
+    int a_relu;         /* implicit conv only: apply ReLU to A elements while loading (depth-anything.cpp:17,19);
+                           refused in plain mode, whose loader has no ReLU                       */
 
     const void* W;      /* f16 [N, K], K padded to a multiple of 64 with zeros                   */
     const float* bias;  /* f32 [N] or NULL                                                      */
@@ -109,7 +110,8 @@ typedef struct {
     int ps_s, ps_Cout, ps_H, ps_W; /* stride, real Cout, input H, W; ldo = output channel stride */
     /* VX_EPI_F16_ADD */
     const void* res1; const void* res2; /* f16 [M, ldo] or NULL */
-    int n_valid;        /* columns >= n_valid are not stored (N padded for tiling); 0 = N        */
+    int n_valid;        /* f16 outputs: columns >= n_valid are not stored (N padded for tiling); 0 = N. The f32 epilogues
+                           (RESID_F32, TOKENS) store all N columns and refuse 0 < n_valid < N    */
     int stages;         /* LDS ring depth of the k-loop: 0 = kernel default (tuning knob for benches) */
     float head_bias, head_scale; /* VX_EPI_HEAD_OUT: conv3 bias, max_depth; lambda = conv3 weights f32 [N] */
     /* VX_EPI_F16_ADD extras (TinyViT): post_gelu: out = gelu(acc + bias + res1 [+ res2]) (mb_conv tail, mobile-sam.cpp:88-90).
@@ -122,7 +124,8 @@ typedef struct {
     int win_res_h, win_shift;
     /* split-K for deep reductions on few output tiles (3x3 convs with thousands of input channels on small maps): k_splits > 1
      * cuts the k-loop into that many ranges, one workgroup each, partial sums f32 in k_partial [k_splits][M][N] (caller's scratch),
-     * summed in a fixed order by a second launch that applies bias / ReLU / res1 -- deterministic. Epilogues F16, F16_RELU, F16_ADD. */
+     * summed in a fixed order by a second launch that applies bias / ReLU / res1 -- deterministic. Epilogues F16, F16_RELU, and F16_ADD
+     * with `relu` and res1 only (no res2, post_gelu or window order). */
     int k_splits; float* k_partial;
     void* debug_stamps; /* diagnostics only: u64 [blocks][8] s_memtime stamps per phase, NULL in product */
     const float* noise; /* VX_EPI_LRELU_AGC: f32 [noise_hw] (noise_const * noise_strength) added at row m % noise_hw, or NULL */

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+from window_ref import windows as _windows
 from visioncpp_amd import _lib as L
 from visioncpp_amd import synth, vision
 
@@ -34,19 +35,6 @@ def _release_buffers():
 
 def _pre(img_u8):  # birefnet_process_input (birefnet.cpp:259-270)
     return ((img_u8.astype(np.float32) / 255.0 - MEAN) / STD).astype(np.float32)
-
-
-def _windows(x, ws, shift):
-    """numpy pad + roll(-shift) + window_partition of [B, H, W, C] -> ([B*nwy*nwx*N, C], validity of each row)."""
-    B, H, W, Cc = x.shape
-    hp, wp = -(-H // ws) * ws, -(-W // ws) * ws
-    p = np.zeros((B, hp, wp, Cc), x.dtype)
-    p[:, :H, :W] = x
-    valid = np.zeros((B, hp, wp), bool)
-    valid[:, :H, :W] = True
-    p, valid = np.roll(p, (-shift, -shift), (1, 2)), np.roll(valid, (-shift, -shift), (1, 2))
-    part = lambda a: a.reshape(B, hp // ws, ws, wp // ws, ws, -1).transpose(0, 1, 3, 2, 4, 5).reshape(-1, a.shape[-1] if a.ndim == 4 else 1)  # noqa: E731
-    return part(p), part(valid[..., None])[:, 0]
 
 
 @pytest.mark.parametrize("H,W,Cc,ws,shift", [(9, 8, 256, 7, 3), (18, 16, 96, 7, 0), (20, 27, 768, 7, 3), (14, 14, 32, 7, 3)])

@@ -551,8 +551,9 @@ int dispatch_epi(const vx_gemm_args& a, hipStream_t s) {
     return 0;
 }
 
-// second launch of a split-K GEMM: out[m, n] = act(sum_s partial[s][m][n] + bias[n]) (+ res1), 8 columns per thread, fixed order
-__global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ part, int S, long M, int N, const float* __restrict__ bias, int epi,
+// second launch of a split-K GEMM: out[m, n] = act(sum_s partial[s][m][n] + bias[n]) (+ res1), 8 columns per thread, fixed order;
+// act is the ReLU of F16_RELU, or of F16_ADD with args.relu (applied before res1, as in the one-launch epilogue)
+__global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ part, int S, long M, int N, const float* __restrict__ bias, int epi, int relu,
                                                             f16* __restrict__ out, long ldo, int n_valid, const f16* __restrict__ res1) {
     const int c8 = n_valid / 8;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -568,13 +569,17 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
         v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
     }
     f16x8 o;
+    if (epi == VX_EPI_F16_RELU || (epi == VX_EPI_F16_ADD && relu)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.0f);
+    }
     if (epi == VX_EPI_F16_ADD && res1) {
         const f16x8 rr = *reinterpret_cast<const f16x8*>(res1 + m * ldo + n);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] += (float)rr[j];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (f16)(epi == VX_EPI_F16_RELU ? fmaxf(v[j], 0.0f) : v[j]);
+    for (int j = 0; j < 8; ++j) o[j] = (f16)v[j];
     *reinterpret_cast<f16x8*>(out + m * ldo + n) = o;
 }
 
@@ -610,7 +615,7 @@ extern "C" int vx_gemm_f16(const vx_gemm_args* args, void* stream) {
         g.k_splits = args->k_splits;
         if (!vx_gemm_f16_raw(&g, stream)) return 0;
         const long items = (long)a.M * (nv / 8);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, as_stream(stream), a.k_partial, args->k_splits, (long)a.M, a.N, a.bias, epi,
+        hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, as_stream(stream), a.k_partial, args->k_splits, (long)a.M, a.N, a.bias, epi, a.relu,
                            reinterpret_cast<f16*>(a.out), (long)a.ldo, nv, reinterpret_cast<const f16*>(res1));
         VX_LAUNCH_CHECK();
         return 1;
@@ -625,6 +630,8 @@ extern "C" int vx_gemm_f16_raw(const vx_gemm_args* args, void* stream) {
     VX_REQUIRE(a.N % 32 == 0, "vx_gemm_f16: N=%d must be a multiple of 32", a.N);
     VX_REQUIRE(a.A && a.W, "vx_gemm_f16: null operand");
     const int nv = a.n_valid > 0 ? a.n_valid : a.N;
+    if (a.epi == VX_EPI_RESID_F32 || a.epi == VX_EPI_TOKENS)
+        VX_REQUIRE(nv >= a.N, "vx_gemm_f16: n_valid=%d < N=%d: the f32 epilogues store all N columns", nv, a.N);
     if (epi_is_f16_tile(a.epi)) {
         VX_REQUIRE(nv % 8 == 0, "vx_gemm_f16: n_valid=%d must be a multiple of 8 for f16 outputs", nv);
         VX_REQUIRE(a.epi == VX_EPI_QKV || a.epi == VX_EPI_HEAD_OUT || a.ldo % 8 == 0, "vx_gemm_f16: ldo=%ld must be a multiple of 8", (long)a.ldo);
@@ -649,6 +656,7 @@ extern "C" int vx_gemm_f16_raw(const vx_gemm_args* args, void* stream) {
         return dispatch_epi<true>(a, as_stream(stream));
     }
     VX_REQUIRE(a.conv_pix == 0, "vx_gemm_f16: conv_pix is an implicit-conv field");
+    VX_REQUIRE(!a.a_relu, "vx_gemm_f16: a_relu is an implicit-conv field (the plain A loader has no ReLU)");
     VX_REQUIRE(a.lda % 8 == 0, "vx_gemm_f16: lda=%ld must be a multiple of 8", (long)a.lda);
     return dispatch_epi<false>(a, as_stream(stream));
 }
