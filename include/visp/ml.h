@@ -33,7 +33,7 @@ using i64x2 = std::array<int64_t, 2>;
 using i64x4 = std::array<int64_t, 4>;
 
 // the two ggml names the reference's callers spell out (compute_graph_input(m, GGML_TYPE_F32, ...)) and its interpolate modes
-constexpr int32_t GGML_TYPE_F32 = 0, GGML_TYPE_F16 = 1;
+constexpr int32_t GGML_TYPE_F32 = 0, GGML_TYPE_F16 = 1, GGML_TYPE_I32 = 26;
 constexpr int32_t GGML_SCALE_MODE_NEAREST = 0, GGML_SCALE_MODE_BILINEAR = 1, GGML_SCALE_MODE_BICUBIC = 2, GGML_SCALE_FLAG_ALIGN_CORNERS = 1 << 8;
 
 enum class model_build_flag : uint32_t { cwhn = 1 << 0, conv_2d_direct_cwhn = 1 << 1, concat_n = 1 << 2, f16_conv_transpose = 1 << 3, window_partition = 1 << 4, flash_attention = 1 << 5 };
@@ -221,6 +221,13 @@ inline tensor get_tensor(model_ref const& m, char const* name) { // ggml_get_ten
     int32_t id = -1;
     detail::check(visp_graph_get_tensor(m.handle(), name, &id));
     return id < 0 ? tensor() : tensor(m.handle(), id);
+}
+// a named constant that is not a file weight, found again with get_tensor: what the reference's callers precompute and upload (swin_precompute:
+// the relative position index, GGML_TYPE_I32 with int32 data; the shift masks, f32 data with -inf entries)
+inline tensor compute_graph_constant(model_ref const& m, char const* name, int32_t type, i64x4 ne, void const* data) {
+    int32_t id = -1;
+    detail::check(visp_graph_add_weight(m.handle(), name, type, ne.data(), static_cast<float const*>(data), &id));
+    return tensor(m.handle(), id);
 }
 inline tensor compute_graph_input(model_ref const& m, int32_t type, i64x4 ne, tensor_name name = "input") {
     int32_t id = -1;

@@ -41,7 +41,7 @@ inline tensor conv_transpose_2d(model_ref m, tensor x, int stride) { // nn.cpp:1
 }
 // image [C, W, H, N] f32 -> [D, W / p, H / p, N]: the projection conv with kernel == stride (nn.cpp:166-180; DINOv2 has no norm)
 inline tensor patch_embed(model_ref m, tensor x, int patch_size) {
-    model_ref p = m["projection"];
+    model_ref p = m[m.find("proj.weight") ? "proj" : "projection"]; // nn.cpp:168
     tensor b = p.find("bias");
     tensor out = b ? detail::op(m, VISP_OP_PATCH_EMBED, {x, p.weights("weight"), b}, {patch_size}) : detail::op(m, VISP_OP_PATCH_EMBED, {x, p.weights("weight")}, {patch_size});
     if (m.find("norm.weight")) out = layer_norm(m["norm"], out);
@@ -60,12 +60,39 @@ inline tensor reshape_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, i
 inline tensor reshape_3d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2) { return reshape_4d(m, x, n0, n1, n2, 1); }
 inline tensor repeat_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2, int64_t n3) { return detail::op(m, VISP_OP_REPEAT, {x}, {n0, n1, n2, n3}); }
 
+inline tensor permute(model_ref const& m, tensor x, int a0, int a1, int a2, int a3) { return detail::op(m, VISP_OP_PERMUTE, {x}, {a0, a1, a2, a3}); } // ggml_permute's axes
+inline tensor roll(model_ref const& m, tensor x, int s0, int s1, int s2, int s3) { return detail::op(m, VISP_OP_ROLL, {x}, {s0, s1, s2, s3}); }
+inline tensor pad(model_ref const& m, tensor x, int p0, int p1, int p2, int p3) { return detail::op(m, VISP_OP_PAD, {x}, {p0, p1, p2, p3}); }
+inline tensor get_rows(model_ref const& m, tensor table, tensor index) { return detail::op(m, VISP_OP_GET_ROWS, {table, index}); }
+inline tensor cast(model_ref const& m, tensor x, int32_t type) { return detail::op(m, VISP_OP_CAST, {x}, {type}); }
+
 struct attention_qkv { tensor q, k, v; };
-// attention with an optional output linear layer; q, k, v [head_dim, n_heads, n_tokens, batch] (nn.cpp:210-244). Masks belong to the
-// window-attention families, which this layer does not express.
+// one linear to 3 C channels, split into q, k, v [head_dim, n_heads, n_tokens, batch] (nn.cpp:182-208). split_dim says how the 3 C outputs are
+// ordered: 1 = (head, q|k|v, head_dim), 2 = (q|k|v, head, head_dim)
+inline attention_qkv split_qkv(model_ref m, tensor x, int n_heads, int split_dim) {
+    auto [c, n, b, _] = nelements(x);
+    tensor qkv = linear(m, x);
+    switch (split_dim) {
+        case 1:
+            qkv = reshape_4d(m, qkv, c / n_heads, 3, n_heads * n, b);
+            qkv = cont(m, permute(m, qkv, 0, 3, 1, 2));
+            break;
+        case 2:
+            qkv = reshape_4d(m, qkv, c / n_heads, n_heads, 3, n * b);
+            qkv = cont(m, permute(m, qkv, 0, 1, 3, 2));
+            break;
+        default: throw exception("split_qkv: split_dim is 1 or 2");
+    }
+    auto split = [&](tensor t, int64_t index) {
+        t = slice(m, t, {}, {}, {}, index);
+        return reshape_4d(m, t, c / n_heads, n_heads, n, b);
+    };
+    return {split(qkv, 0), split(qkv, 1), split(qkv, 2)};
+}
+// attention with an optional mask [n_keys, n_queries, 1 | n_heads, a divisor of batch] and an output linear layer; q, k, v
+// [head_dim, n_heads, n_tokens, batch] (nn.cpp:210-244). Without a mask: the head_dim-64 kernel; with one: head_dim 32 and 64.
 inline tensor attention(model_ref m, tensor q, tensor k, tensor v, tensor mask, float scale_, model_ref m_out) {
-    if (mask) throw exception("attention: masks are not built in the graph layer");
-    tensor x = detail::op(m, VISP_OP_ATTENTION, {q, k, v}, {}, {scale_});
+    tensor x = mask ? detail::op(m, VISP_OP_ATTENTION_MASKED, {q, k, v, mask}, {}, {scale_}) : detail::op(m, VISP_OP_ATTENTION, {q, k, v}, {}, {scale_});
     return linear(m_out, x);
 }
 
@@ -96,6 +123,13 @@ inline tensor ggml_cont(model_ref const& m, tensor x) { return cont(m, x); }
 inline tensor ggml_reshape_3d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2) { return reshape_3d(m, x, n0, n1, n2); }
 inline tensor ggml_reshape_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2, int64_t n3) { return reshape_4d(m, x, n0, n1, n2, n3); }
 inline tensor ggml_repeat_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2, int64_t n3) { return repeat_4d(m, x, n0, n1, n2, n3); }
+inline tensor ggml_permute(model_ref const& m, tensor x, int a0, int a1, int a2, int a3) { return permute(m, x, a0, a1, a2, a3); }
+inline tensor ggml_roll(model_ref const& m, tensor x, int s0, int s1, int s2, int s3) { return roll(m, x, s0, s1, s2, s3); }
+inline tensor ggml_pad(model_ref const& m, tensor x, int p0, int p1, int p2, int p3) { return pad(m, x, p0, p1, p2, p3); }
+inline tensor ggml_get_rows(model_ref const& m, tensor table, tensor index) { return get_rows(m, table, index); }
+inline tensor ggml_cast(model_ref const& m, tensor x, int32_t type) { return cast(m, x, type); }
+inline tensor ggml_gelu_inplace(model_ref const& m, tensor x) { return gelu(m, x); }
+inline tensor ggml_get_tensor(model_ref const& m, char const* name) { return get_tensor(m, name); }
 #endif
 
 } // namespace visp

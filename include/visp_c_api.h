@@ -334,7 +334,17 @@ enum visp_graph_op {
     /* extensions for callers that keep images in HBM (the reference does both steps on the host): */
     VISP_OP_IMAGE_U8_TO_F32 = 19,  /* src x u8 input [3,W,H,N]; f0..f2 mean, f3..f5 1/std: (x / 255 - mean) / std        image.cpp:215-255 */
     VISP_OP_IMAGE_NORMALIZE = 20,  /* src x f32 [1,W,H,N]: per-image min-max to [0, 1]                                   image.cpp:537-582 */
-    VISP_OP_LEAKY_RELU = 21        /* f0 negative slope                                                                    ggml_leaky_relu, esrgan.cpp:17, 24 */
+    VISP_OP_LEAKY_RELU = 21,       /* f0 negative slope                                                                    ggml_leaky_relu, esrgan.cpp:17, 24 */
+    /* the window ops of a SWIN block (swin.cpp:48-141); all of them are folded on the host when every operand is a constant */
+    VISP_OP_PERMUTE = 22,          /* i0..i3 ggml_permute's axes (source dimension d becomes dimension i_d); the result is contiguous, cont behind it a view */
+    VISP_OP_ROLL = 23,             /* i0..i3 cyclic shifts, negative allowed                                               ggml_roll, swin.cpp:116, 124 */
+    VISP_OP_PAD = 24,              /* i0..i3 zeros appended at the end of each dimension                                   ggml_pad, swin.cpp:111 */
+    VISP_OP_GET_ROWS = 25,         /* src table [C, rows], index i32 constant -> f32 [C, idx ne0, ne1, ne2]; constants only  ggml_get_rows, swin.cpp:75 */
+    VISP_OP_CAST = 26,             /* i0 type (0 f32, 1 f16): rounds constants, a view on activations that have the type   ggml_cast, swin.cpp:78 */
+    /* src q, k, v [head_dim, heads, T, B], mask [T_k, T_q, Hm, Bm] f16 / f32, constant or activation; f0 scale. Hm is 1 or heads, Bm divides B (batch b
+     * reads mask b % Bm). softmax(scale q k^T + mask) v as the 3-source op. head_dim 32 and 64, T_q == T_k. head_dim 32 exists through THIS op only:
+     * VISP_OP_ATTENTION keeps its head_dim-64 kernel and its refusal of everything else.                         nn.cpp:210-244, swin.cpp:69-97 */
+    VISP_OP_ATTENTION_MASKED = 27
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is
@@ -356,6 +366,8 @@ VISP_API void visp_weights_destroy(visp_weights* w); /* graphs over the weights 
 /* compute_graph_init (ml.cpp:531-543). weights == NULL: the graph starts with an empty store of its own (visp_graph_add_weight) */
 VISP_API int32_t visp_graph_create(visp_weights* weights, visp_graph** out);
 VISP_API void visp_graph_destroy(visp_graph* g);
+/* dtype 0 f32 / 1 f16: `data` f32 values. dtype 26 (i32): `data` points at int32 values -- an index constant for VISP_OP_GET_ROWS. Also how a caller adds
+ * a constant that is not a file weight (the shift mask of swin.cpp:165-221, -inf entries included); visp_graph_get_tensor finds it by name. */
 VISP_API int32_t visp_graph_add_weight(visp_graph* g, char const* name, int32_t dtype, int64_t const ne[4], float const* data, int32_t* out);
 VISP_API int32_t visp_graph_find_weight(visp_graph* g, char const* name, int32_t* out); /* *out = -1 when absent (model_ref::find) */
 VISP_API int32_t visp_graph_input(visp_graph* g, int32_t dtype /* 0 f32, 1 f16, 24 u8 image bytes */, int64_t const ne[4], char const* name, int32_t* out);

@@ -291,6 +291,12 @@ VX_API int vx_add_gelu_f16(const void* a, const void* b, void* y, int64_t n, voi
 #define VX_ATTN_Q_SCALE 0.18033688011112042f
 VX_API int vx_attention_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int T,
                             void* stream);
+/* attention with an additive mask, head_dim 32 or 64, any T (kernels_attn_mask.hip; nn.cpp:210-244 with a mask, swin.cpp:69-97):
+ * q, k, v f16 head-major [B,H,T,head_dim], q pre-scaled by scale * log2(e) (for 1 / sqrt(head_dim): VX_ATTN_Q_SCALE at 64);
+ * mask f16 (or f32: mask_is_f32) [Bm][Hm][T queries][T keys], Hm = 1 or H, Bm divides B, batch b reads image b % Bm; -inf entries
+ * allowed, a row that is -inf on every key is unspecified; out f16 [B*T, H*head_dim] = softmax(scale q k^T + mask) v */
+VX_API int vx_attention_masked_f16(const void* q, const void* k, const void* v, const void* mask, void* out, int B, int H, int T, int head_dim,
+                                   int Hm, int Bm, int mask_is_f32, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);
@@ -405,6 +411,10 @@ VX_API int vx_f32_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream)
 /* dst[i . dst_stride] = scale * src[i . src_stride], i over ne (element strides, 0 = broadcast a source dimension) */
 VX_API int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[4], const int64_t src_stride[4], const int64_t dst_stride[4], float scale,
                                void* stream);
+/* ggml_roll: dst[i] = src[(i - shift) mod ne] in every dimension (negative shifts wrap); f16, contiguous, dst != src */
+VX_API int vx_roll_f16(const void* src, void* dst, const int64_t ne[4], const int64_t shift[4], void* stream);
+/* ggml_pad: src [src_ne] in the low corner of dst [dst_ne >= src_ne], zeros behind it; f16, contiguous */
+VX_API int vx_pad_f16(const void* src, void* dst, const int64_t src_ne[4], const int64_t dst_ne[4], void* stream);
 /* y[i] = a[i] (op) b[i mod b_period]; op 0 add, 1 mul; each operand f16 or f32 */
 VX_API int vx_binary_rows(int op, const void* a, int a_f32, const void* b, int b_f32, int64_t b_period, void* y, int y_f32, int64_t n, void* stream);
 /* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s, 3 leaky ReLU x > 0 ? x : s x (ggml_leaky_relu, any slope); f16, 16-byte aligned */

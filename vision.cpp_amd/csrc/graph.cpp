@@ -18,7 +18,8 @@ namespace {
 
 const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_norm", "gelu", "relu", "scale", "add", "mul", "conv_2d",
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
-                                         "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu"};
+                                         "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
+                                         "cast", "attention_masked"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -160,13 +161,50 @@ void fold_constant(graph& g, graph_node& n) {
             else if ((mode & 255) == 1 && (mode & 256)) host_bilinear_ac(src(0).values(), src(0).ne, out, n.ip[0], n.ip[1]);
             else throw except("interpolate: mode %d is not built (bicubic, and bilinear | align_corners, are)", mode);
         } break;
+        case gop_permute: { // source dimension d is destination dimension ip[d]
+            host_view v{src(0).values(), src(0).ne};
+            int64_t o = 0, idx[4];
+            for (idx[3] = 0; idx[3] < n.ne[3]; ++idx[3])
+                for (idx[2] = 0; idx[2] < n.ne[2]; ++idx[2])
+                    for (idx[1] = 0; idx[1] < n.ne[1]; ++idx[1])
+                        for (idx[0] = 0; idx[0] < n.ne[0]; ++idx[0]) out[o++] = v.at(idx[n.ip[0]], idx[n.ip[1]], idx[n.ip[2]], idx[n.ip[3]]);
+        } break;
+        case gop_roll: {
+            host_view v{src(0).values(), src(0).ne};
+            auto from = [&](int64_t i, int d) { return ((i - n.ip[d]) % n.ne[d] + n.ne[d]) % n.ne[d]; };
+            int64_t o = 0;
+            for (int64_t i3 = 0; i3 < n.ne[3]; ++i3)
+                for (int64_t i2 = 0; i2 < n.ne[2]; ++i2)
+                    for (int64_t i1 = 0; i1 < n.ne[1]; ++i1)
+                        for (int64_t i0 = 0; i0 < n.ne[0]; ++i0) out[o++] = v.at(from(i0, 0), from(i1, 1), from(i2, 2), from(i3, 3));
+        } break;
+        case gop_pad: {
+            host_view v{src(0).values(), src(0).ne};
+            int64_t o = 0;
+            for (int64_t i3 = 0; i3 < n.ne[3]; ++i3)
+                for (int64_t i2 = 0; i2 < n.ne[2]; ++i2)
+                    for (int64_t i1 = 0; i1 < n.ne[1]; ++i1)
+                        for (int64_t i0 = 0; i0 < n.ne[0]; ++i0)
+                            out[o++] = i0 < v.ne[0] && i1 < v.ne[1] && i2 < v.ne[2] && i3 < v.ne[3] ? v.at(i0, i1, i2, i3) : 0.0f;
+        } break;
+        case gop_get_rows: {
+            const int64_t C = src(0).ne[0], rows = src(0).ne[1], cnt = src(1).n_elements();
+            for (int64_t i = 0; i < cnt; ++i) {
+                const int64_t row = (int64_t)src(1).values()[i];
+                if (row < 0 || row >= rows) throw except("get_rows: index %lld at position %lld is outside the table's %lld rows", (long long)row, (long long)i, (long long)rows);
+                std::copy(src(0).values() + row * C, src(0).values() + (row + 1) * C, out + i * C);
+            }
+        } break;
+        case gop_cast:
+            for (int64_t i = 0; i < total; ++i) out[i] = n.dtype == gdt_f16 ? f16_to_f32(f32_to_f16(src(0).values()[i])) : src(0).values()[i];
+            break;
         default: throw except("graph: %s on constants is not folded", graph_op_name(n.op));
     }
 }
 
 bool foldable(int32_t op) {
     return op == gop_reshape || op == gop_cont || op == gop_scale || op == gop_add || op == gop_mul || op == gop_slice || op == gop_repeat ||
-           op == gop_concat || op == gop_interpolate;
+           op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast;
 }
 
 void check_tensor(graph const& g, int t, const char* what) {
@@ -191,14 +229,21 @@ void weights_add(weight_store& ws, char const* name, int32_t dtype, const int64_
     if (ws.tensors.count(name)) throw except("weights: '%s' exists already", name);
     if (ws.dev) throw except("weights: '%s' added after a graph over these weights was allocated", name);
     weight_store::entry e;
-    e.dtype = dtype == gdt_f32 ? gdt_f32 : gdt_f16;
+    e.dtype = dtype == gdt_f32 ? gdt_f32 : (dtype == gdt_i32 ? gdt_i32 : gdt_f16);
     int64_t n = 1;
     for (int i = 0; i < 4; ++i) {
         if (ne[i] <= 0) throw except("weights: '%s' has a non-positive extent", name);
         e.ne[i] = ne[i];
         n *= ne[i];
     }
-    if (data) e.data.assign(data, data + n);
+    if (data && dtype == gdt_i32) { // `data` points at int32 values: index constants (ggml_get_rows), kept as floats -- exact below 2^24
+        const int32_t* idx = reinterpret_cast<const int32_t*>(data);
+        e.data.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            if (idx[i] < -(1 << 24) || idx[i] > (1 << 24)) throw except("weights: i32 tensor '%s' holds %d (magnitudes up to 2^24)", name, idx[i]);
+            e.data[(size_t)i] = (float)idx[i];
+        }
+    } else if (data) e.data.assign(data, data + n);
     else e.data.assign((size_t)n, 0.0f);
     ws.tensors.emplace(name, std::move(e));
 }
@@ -476,6 +521,63 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             same_shape();
             n.dtype = gdt_f32;
         } break;
+        case gop_permute: {
+            need_src(1, 1);
+            bool seen[4] = {false, false, false, false};
+            for (int d = 0; d < 4; ++d) {
+                if (n_ip != 4 || n.ip[d] < 0 || n.ip[d] > 3 || seen[n.ip[d]]) throw except("permute: the axes must be a permutation of 0..3 (ggml_permute: source dimension d becomes dimension axes[d])");
+                seen[n.ip[d]] = true;
+                n.ne[n.ip[d]] = S(0).ne[d];
+            }
+            n.dtype = S(0).dtype;
+        } break;
+        case gop_roll:
+            need_src(1, 1);
+            if (n_ip != 4) throw except("roll: four shifts");
+            same_shape();
+            n.dtype = S(0).dtype;
+            break;
+        case gop_pad:
+            need_src(1, 1);
+            for (int d = 0; d < 4; ++d) {
+                if (n_ip != 4 || n.ip[d] < 0) throw except("pad: four non-negative paddings (zeros are appended at the end of a dimension)");
+                n.ne[d] = S(0).ne[d] + n.ip[d];
+            }
+            n.dtype = S(0).dtype;
+            break;
+        case gop_get_rows: {
+            need_src(2, 2);
+            graph_node const &tab = S(0), &idx = S(1);
+            if (idx.dtype != gdt_i32 || !idx.constant) throw except("get_rows: the index is an i32 constant (visp_graph_add_weight with dtype 26)");
+            if (tab.ne[2] != 1 || tab.ne[3] != 1 || idx.ne[3] != 1) throw except("get_rows: table %s must be a matrix, index %s at most 3-dimensional", shape_str(tab.ne).c_str(), shape_str(idx.ne).c_str());
+            if (tab.dtype == gdt_i32) throw except("get_rows: the table is an f16 / f32 tensor");
+            n.ne[0] = tab.ne[0]; n.ne[1] = idx.ne[0]; n.ne[2] = idx.ne[1]; n.ne[3] = idx.ne[2];
+            n.dtype = gdt_f32; // ggml: the result of get_rows is always f32
+        } break;
+        case gop_cast:
+            need_src(1, 1);
+            if (n_ip != 1 || (n.ip[0] != gdt_f32 && n.ip[0] != gdt_f16)) throw except("cast: the target type is 0 (f32) or 1 (f16)");
+            if (S(0).dtype == gdt_i32) throw except("cast: an i32 tensor is an index, not a value");
+            if (!S(0).constant && S(0).dtype != n.ip[0]) throw except("cast: an %s activation to %s is not built (activations of this layer are f16; a cast to the type they have is a view)", S(0).dtype == gdt_f16 ? "f16" : "f32", n.ip[0] == gdt_f16 ? "f16" : "f32");
+            same_shape();
+            n.dtype = (int32_t)n.ip[0];
+            break;
+        case gop_attention_masked: {
+            need_src(4, 4);
+            graph_node const &q = S(0), &k = S(1), &v = S(2), &mk = S(3);
+            for (int i = 0; i < 4; ++i)
+                if (k.ne[i] != v.ne[i] || (i != 2 && q.ne[i] != k.ne[i])) throw except("attention_masked: q %s, k %s, v %s do not match ([head_dim, heads, tokens, batch])", shape_str(q.ne).c_str(), shape_str(k.ne).c_str(), shape_str(v.ne).c_str());
+            if (q.ne[2] != k.ne[2]) throw except("attention_masked: %lld queries on %lld keys; cross-attention (T_q != T_k) is not built", (long long)q.ne[2], (long long)k.ne[2]);
+            if (q.ne[0] != 32 && q.ne[0] != 64) throw except("attention_masked: head_dim %lld; the masked kernel is built for head_dim 32 and 64", (long long)q.ne[0]);
+            if (mk.dtype != gdt_f16 && mk.dtype != gdt_f32) throw except("attention_masked: the mask is an f16 or f32 tensor");
+            if (mk.ne[0] != k.ne[2] || mk.ne[1] != q.ne[2]) throw except("attention_masked: mask %s does not match %lld keys x %lld queries ([T_k, T_q, Hm, Bm])", shape_str(mk.ne).c_str(), (long long)k.ne[2], (long long)q.ne[2]);
+            if (mk.ne[2] != 1 && mk.ne[2] != q.ne[1]) throw except("attention_masked: the mask has %lld heads; 1 (broadcast) or %lld", (long long)mk.ne[2], (long long)q.ne[1]);
+            if (q.ne[3] % mk.ne[3]) throw except("attention_masked: the mask's batch %lld does not divide the batch %lld (batch b reads mask b %% Bm)", (long long)mk.ne[3], (long long)q.ne[3]);
+            n.ne[0] = q.ne[0] * q.ne[1];
+            n.ne[1] = q.ne[2];
+            n.ne[2] = q.ne[3];
+            n.ne[3] = 1;
+        } break;
         default: throw except("graph_add: op %d", op);
     }
     // f32 tensors exist as inputs only; an f32 operand anywhere else would need kernels this executor does not have
@@ -484,7 +586,8 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             const bool head_tail = (op == gop_relu || op == gop_scale) && S(i).op != gop_input;
             // (a 3x3 conv on the f32 image of <= 16 channels: the first conv of an image-to-image network, esrgan.cpp:58)
             const bool image_conv = op == gop_conv_2d && i == 0 && S(0).op == gop_input && S(0).ne[0] <= 16 && S(1).ne[1] == 3 && S(1).ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1;
-            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv)
+            const bool f32_mask = op == gop_attention_masked && i == 3; // the masked attention reads an f32 mask in place
+            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !f32_mask)
                 throw except("%s: operand %d is f32; only patch_embed and an image's first 3x3 conv read the f32 input tensor", nm, i);
         }
 

@@ -52,11 +52,18 @@ enum graph_op : int32_t {
     gop_image_u8_to_f32,  // x u8 [3, W, H, N] -> f32: (x / 255 - f0..f2) * f3..f5     image.cpp:215-255 as depthany_process_input calls it
     gop_image_normalize,  // x f32 [1, W, H, N] -> f32: per-image min-max to [0, 1]     image.cpp:537-582 (depthany_process_output)
     gop_leaky_relu,       // f0 = negative slope                         ggml_leaky_relu (esrgan.cpp:17, 24)
+    // the window ops of a SWIN block (swin.cpp:48-141) and the masked attention behind them
+    gop_permute,          // x; i0..i3 = ggml_permute's axes: source dimension d becomes dimension i_d; the result is contiguous (cont behind it: a view)
+    gop_roll,             // x; i0..i3 = cyclic shifts (negative allowed)  ggml_roll (swin.cpp:116, 124)
+    gop_pad,              // x; i0..i3 = zeros appended per dimension       ggml_pad (swin.cpp:111)
+    gop_get_rows,         // table [C, rows], idx i32 constant -> f32 [C, idx.ne0, idx.ne1, idx.ne2]; constants only (folded)   swin.cpp:75
+    gop_cast,             // x; i0 = type (0 f32, 1 f16): a view on activations of that type, a rounding on constants           swin.cpp:78
+    gop_attention_masked, // q, k, v [hd, heads, T, B], mask [T_k, T_q, Hm, Bm]; f0 = scale; hd 32 / 64 -> [hd * heads, T, B]   nn.cpp:210-244 with a mask
     gop_count
 };
 const char* graph_op_name(int32_t op);
 
-constexpr int32_t gdt_f32 = 0, gdt_f16 = 1, gdt_u8 = 24; // ggml type ids (24 = I8: one byte per element; image inputs)
+constexpr int32_t gdt_f32 = 0, gdt_f16 = 1, gdt_u8 = 24, gdt_i32 = 26; // ggml type ids (24 = I8: one byte per element; image inputs. 26 = I32: index constants, held as exact floats on the host)
 
 struct graph_node {
     int32_t op = gop_input;

@@ -52,6 +52,51 @@ __global__ __launch_bounds__(256) void copy_strided8_kernel(const f16* __restric
     }
 }
 
+// ggml_roll: dst[i] = src[(i - shift) mod ne] per dimension (shifts already reduced to [0, ne)). V = 8: rows of 8-element groups, ne[0] and
+// shift[0] count groups (the vector path: ne[0] and the first shift multiples of 8); V = 1: one element per thread-iteration
+struct roll_shape { long ne[4]; long shift[4]; };
+template <int V>
+__global__ __launch_bounds__(256) void roll_kernel(const f16* __restrict__ src, f16* __restrict__ dst, roll_shape s, long n) {
+    typedef _Float16 vec_t __attribute__((ext_vector_type(V)));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        long r = i, idx[4];
+        idx[0] = r % s.ne[0]; r /= s.ne[0];
+        idx[1] = r % s.ne[1]; r /= s.ne[1];
+        idx[2] = r % s.ne[2];
+        idx[3] = r / s.ne[2];
+        long from = 0;
+#pragma unroll
+        for (int d = 3; d >= 0; --d) {
+            long j = idx[d] - s.shift[d];
+            if (j < 0) j += s.ne[d];
+            from = from * s.ne[d] + j;
+        }
+        if constexpr (V == 1) dst[i] = src[from];
+        else *reinterpret_cast<vec_t*>(dst + i * V) = *reinterpret_cast<const vec_t*>(src + from * V);
+    }
+}
+// ggml_pad: the source in the low corner of the destination, zeros behind it in every dimension. V as for roll_kernel (sne[0] and dne[0] in groups)
+struct pad_shape { long sne[4]; long dne[4]; };
+template <int V>
+__global__ __launch_bounds__(256) void pad_kernel(const f16* __restrict__ src, f16* __restrict__ dst, pad_shape s, long n) {
+    typedef _Float16 vec_t __attribute__((ext_vector_type(V)));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        long r = i;
+        const long i0 = r % s.dne[0]; r /= s.dne[0];
+        const long i1 = r % s.dne[1]; r /= s.dne[1];
+        const long i2 = r % s.dne[2];
+        const long i3 = r / s.dne[2];
+        const bool inside = i0 < s.sne[0] && i1 < s.sne[1] && i2 < s.sne[2] && i3 < s.sne[3];
+        const long from = ((i3 * s.sne[2] + i2) * s.sne[1] + i1) * s.sne[0] + i0;
+        if constexpr (V == 1) dst[i] = inside ? src[from] : (f16)0;
+        else {
+            vec_t v = {};
+            if (inside) v = *reinterpret_cast<const vec_t*>(src + from * V);
+            *reinterpret_cast<vec_t*>(dst + i * V) = v;
+        }
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ float ld(const T* p, long i) { return (float)p[i]; }
 
@@ -213,6 +258,47 @@ extern "C" int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[
         hipLaunchKernelGGL(copy_strided8_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
     } else {
         hipLaunchKernelGGL(copy_strided_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n, scale, scaled);
+    }
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_roll_f16(const void* src, void* dst, const int64_t ne[4], const int64_t shift[4], void* stream) {
+    VX_REQUIRE(src && dst && src != dst, "vx_roll_f16: null or aliased operands");
+    roll_shape s;
+    long n = 1;
+    for (int i = 0; i < 4; ++i) {
+        VX_REQUIRE(ne[i] > 0, "vx_roll_f16: non-positive extent in dimension %d", i);
+        s.ne[i] = ne[i];
+        s.shift[i] = ((shift[i] % ne[i]) + ne[i]) % ne[i]; // negative shifts wrap
+        n *= ne[i];
+    }
+    const bool vec = ne[0] % 8 == 0 && s.shift[0] % 8 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    if (vec) {
+        s.ne[0] /= 8; s.shift[0] /= 8; n /= 8;
+        hipLaunchKernelGGL(roll_kernel<8>, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n);
+    } else {
+        hipLaunchKernelGGL(roll_kernel<1>, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n);
+    }
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_pad_f16(const void* src, void* dst, const int64_t src_ne[4], const int64_t dst_ne[4], void* stream) {
+    VX_REQUIRE(src && dst && src != dst, "vx_pad_f16: null or aliased operands");
+    pad_shape s;
+    long n = 1;
+    for (int i = 0; i < 4; ++i) {
+        VX_REQUIRE(src_ne[i] > 0 && dst_ne[i] >= src_ne[i], "vx_pad_f16: dimension %d shrinks or is empty", i);
+        s.sne[i] = src_ne[i]; s.dne[i] = dst_ne[i];
+        n *= dst_ne[i];
+    }
+    const bool vec = src_ne[0] % 8 == 0 && dst_ne[0] % 8 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    if (vec) {
+        s.sne[0] /= 8; s.dne[0] /= 8; n /= 8;
+        hipLaunchKernelGGL(pad_kernel<8>, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n);
+    } else {
+        hipLaunchKernelGGL(pad_kernel<1>, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), s, n);
     }
     VX_LAUNCH_CHECK();
     return 1;

@@ -89,26 +89,33 @@ void lowering::fused_qkv(int att) {
     qkv_bufs[att] = hb;
 }
 
+// q, k, v of an attention node, [hd, H, T, B] -> head-major [hd, T, H, B] copies, q multiplied by q_scale on the way
+std::array<int, 3> lowering::heads_major(graph_node const& n, float q_scale) {
+    graph_node const& q = g.nodes[n.src[0]];
+    const int64_t hd = q.ne[0], H = q.ne[1], T = q.ne[2], B = q.ne[3];
+    std::array<int, 3> hb;
+    for (int i = 0; i < 3; ++i) {
+        const int sb = buf_of(n.src[i]);
+        hb[i] = new_buffer((size_t)(hd * H * T * B) * 2);
+        auto sp = ptr(sb), dp = ptr(hb[i]);
+        const float s = i == 0 ? q_scale : 1.0f;
+        emit(std::string("heads_major ") + "qkv"[i] + (i == 0 ? " (scaled)" : ""), {sb}, {hb[i]}, [=](void* st) {
+            const int64_t ne[4] = {hd, T, H, B}, ss[4] = {1, H * hd, hd, T * H * hd}, ds[4] = {1, hd, T * hd, H * T * hd};
+            VX(vx_copy_strided_f16(sp(), dp(), ne, ss, ds, s, st));
+        });
+    }
+    return hb;
+}
+
 void lowering::attention(int t) {
     graph_node& n = g.nodes[t];
     graph_node const &q = g.nodes[n.src[0]], &k = g.nodes[n.src[1]];
     const int64_t hd = q.ne[0], H = q.ne[1], Tq = q.ne[2], Tk = k.ne[2], B = q.ne[3];
     if (hd != 64 || Tq != Tk) throw except("attention: head_dim %lld, %lld queries on %lld keys; the fused kernel is built for head_dim 64 self-attention", (long long)hd, (long long)Tq, (long long)Tk);
     const float q_scale = n.fp[0] * 1.4426950408889634f; // the kernel works in the exp2 domain (VX_ATTN_Q_SCALE)
-    int hb[3];
-    if (auto it = qkv_bufs.find(t); it != qkv_bufs.end()) {
-        for (int i = 0; i < 3; ++i) hb[i] = it->second[i];
-    } else
-    for (int i = 0; i < 3; ++i) { // [hd, H, T, B] -> head-major [hd, T, H, B]
-        const int sb = buf_of(n.src[i]);
-        hb[i] = new_buffer((size_t)(hd * H * Tq * B) * 2);
-        auto sp = ptr(sb), dp = ptr(hb[i]);
-        const float s = i == 0 ? q_scale : 1.0f;
-        emit(std::string("heads_major ") + "qkv"[i] + (i == 0 ? " (scaled)" : ""), {sb}, {hb[i]}, [=](void* st) {
-            const int64_t ne[4] = {hd, Tq, H, B}, ss[4] = {1, H * hd, hd, Tq * H * hd}, ds[4] = {1, hd, Tq * hd, H * Tq * hd};
-            VX(vx_copy_strided_f16(sp(), dp(), ne, ss, ds, s, st));
-        });
-    }
+    std::array<int, 3> hb;
+    if (auto it = qkv_bufs.find(t); it != qkv_bufs.end()) hb = it->second;
+    else hb = heads_major(n, q_scale);
     materialise(t);
     const int obuf = n.buffer;
     auto qp = ptr(hb[0]), kp = ptr(hb[1]), vp = ptr(hb[2]), op = ptr(obuf);
@@ -116,6 +123,45 @@ void lowering::attention(int t) {
     snprintf(d, sizeof d, "attention B=%lld heads=%lld T=%lld", (long long)B, (long long)H, (long long)Tq);
     emit(d, {hb[0], hb[1], hb[2]}, {obuf}, [=](void* st) { VX(vx_attention_f16(qp(), kp(), vp(), op(), (int)B, (int)H, (int)Tq, st)); });
     tag("attention", 4.0 * B * H * (double)Tq * Tq * 64, (double)B * H * Tq * 64 * 2 * 4);
+}
+
+// softmax(scale q k^T + mask) v at head_dim 32 / 64 (the window-attention families: swin.cpp:69-97). q, k, v head-major as above, the scale
+// folded into q; a constant mask (bias table [+ shift mask], folded on the host) becomes one f16 device image [Bm][Hm][T_q][T_k] -- ggml's
+// [T_k, T_q, Hm, Bm] is that layout already --, cut to its shortest period over the batch; an activation mask is read where it is, f16 or f32.
+void lowering::attention_masked(int t) {
+    graph_node& n = g.nodes[t];
+    graph_node const &q = g.nodes[n.src[0]], &mk = g.nodes[n.src[3]];
+    const int64_t hd = q.ne[0], H = q.ne[1], T = q.ne[2], B = q.ne[3], Hm = mk.ne[2];
+    int64_t Bm = mk.ne[3];
+    const float q_scale = n.fp[0] * 1.4426950408889634f; // the kernel works in the exp2 domain
+    // a constant mask that repeats over its batch (swin.cpp:83-88 repeats the layer's windows once per image) is kept once, the kernel's b % Bm does the
+    // rest: at SWIN-T stage 0, 1024^2, batch 8 that is 20 MB per block on the device instead of 158 MB
+    const int64_t image = mk.ne[0] * mk.ne[1] * mk.ne[2];
+    if (mk.constant)
+        for (int64_t p = 1; p < Bm; ++p)
+            if (Bm % p == 0 && memcmp(mk.values(), mk.values() + p * image, (size_t)((Bm - p) * image) * 4) == 0) { Bm = p; break; }
+    const std::array<int, 3> hb = heads_major(n, q_scale);
+    std::vector<int> reads = {hb[0], hb[1], hb[2]};
+    void* mconst = nullptr;
+    std::function<char*()> mp;
+    const int mask_f32 = !mk.constant && mk.dtype == gdt_f32;
+    if (mk.constant)
+        mconst = cached(n.src[3], role_f16, [&](bool st) {
+            std::vector<uint16_t> h((size_t)(Bm * image));
+            for (size_t i = 0; i < h.size(); ++i) h[i] = f32_to_f16(mk.values()[i]);
+            return upload(h.data(), h.size() * 2, st);
+        }, "images:" + std::to_string(Bm));
+    else { reads.push_back(buf_of(n.src[3])); mp = ptr(buf_of(n.src[3])); }
+    materialise(t);
+    const int obuf = n.buffer;
+    auto qp = ptr(hb[0]), kp = ptr(hb[1]), vp = ptr(hb[2]), op = ptr(obuf);
+    char d[160];
+    snprintf(d, sizeof d, "attention_masked B=%lld heads=%lld T=%lld hd=%lld mask=[%lld, %lld] %s", (long long)B, (long long)H, (long long)T, (long long)hd, (long long)Hm, (long long)Bm,
+             mk.constant ? "(constant)" : (mask_f32 ? "f32" : "f16"));
+    emit(d, reads, {obuf}, [=](void* st) {
+        VX(vx_attention_masked_f16(qp(), kp(), vp(), mp ? static_cast<const void*>(mp()) : mconst, op(), (int)B, (int)H, (int)T, (int)hd, (int)Hm, (int)Bm, mask_f32, st));
+    });
+    tag("attention", 4.0 * B * H * (double)T * T * hd, (double)B * H * T * hd * 2 * 4 + (double)B * H * T * T * (mask_f32 ? 4 : 2));
 }
 
 // ---- fused model group 1: the DINOv2 encoder (dino.cpp:10-110) -----------------------------------------------------------------------

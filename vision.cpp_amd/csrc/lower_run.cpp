@@ -109,6 +109,36 @@ void lowering::run() {
             case gop_conv_transpose_2d: gemm_like(t); break;
             case gop_patch_embed: patch_embed(t); break;
             case gop_attention: attention(t); break;
+            case gop_attention_masked: attention_masked(t); break;
+            case gop_cast: n.alias_of = n.src[0]; break; // an activation already has the type (graph_add refuses the rest): a view
+            case gop_get_rows:
+                throw except("get_rows: a non-constant operand; get_rows is folded on the host from a constant table and a constant index (get_rows on activations is not built)");
+            case gop_permute: { // one strided copy: destination dimension ip[d] walks source dimension d
+                graph_node const& x = g.nodes[n.src[0]];
+                const int xbuf = buf_of(n.src[0]);
+                materialise(t);
+                const int obuf = n.buffer;
+                auto xp = ptr(xbuf), op = ptr(obuf);
+                std::array<int64_t, 4> A{n.ne[0], n.ne[1], n.ne[2], n.ne[3]}, D{1, n.ne[0], n.ne[0] * n.ne[1], n.ne[0] * n.ne[1] * n.ne[2]}, S{};
+                const int64_t xs[4] = {1, x.ne[0], x.ne[0] * x.ne[1], x.ne[0] * x.ne[1] * x.ne[2]};
+                for (int d = 0; d < 4; ++d) S[n.ip[d]] = xs[d];
+                emit("permute " + shape_str(x.ne) + " -> " + shape_str(n.ne), {xbuf}, {obuf}, [=](void* st) { VX(vx_copy_strided_f16(xp(), op(), A.data(), S.data(), D.data(), 1.0f, st)); });
+                tag("glue", 0, (double)n.n_elements() * 4);
+            } break;
+            case gop_roll: {
+                graph_node const& x = g.nodes[n.src[0]];
+                std::array<int64_t, 4> A{x.ne[0], x.ne[1], x.ne[2], x.ne[3]}, Sh{n.ip[0], n.ip[1], n.ip[2], n.ip[3]};
+                char d[160];
+                snprintf(d, sizeof d, "roll %s by [%lld, %lld, %lld, %lld]", shape_str(x.ne).c_str(), (long long)Sh[0], (long long)Sh[1], (long long)Sh[2], (long long)Sh[3]);
+                map_launch(t, d, [=](char* xp, char* o, char*, void* st) { VX(vx_roll_f16(xp, o, A.data(), Sh.data(), st)); });
+                tag("glue", 0, (double)n.n_elements() * 4);
+            } break;
+            case gop_pad: {
+                graph_node const& x = g.nodes[n.src[0]];
+                std::array<int64_t, 4> A{x.ne[0], x.ne[1], x.ne[2], x.ne[3]}, D{n.ne[0], n.ne[1], n.ne[2], n.ne[3]};
+                map_launch(t, "pad " + shape_str(x.ne) + " -> " + shape_str(n.ne), [=](char* xp, char* o, char*, void* st) { VX(vx_pad_f16(xp, o, A.data(), D.data(), st)); });
+                tag("glue", 0, (double)(x.n_elements() + n.n_elements()) * 2);
+            } break;
             case gop_relu: {
                 const int c = sole_consumer(t);
                 if (c >= 0 && g.nodes[c].op == gop_conv_2d && g.nodes[c].src[0] == t && !(g.nodes[g.nodes[c].src[1]].ne[1] == 1 && g.nodes[g.nodes[c].src[1]].ne[2] == 1)) {

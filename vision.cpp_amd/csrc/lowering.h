@@ -180,7 +180,9 @@ struct lowering {
     // ---- lower_encoder.cpp
     void find_qkv_groups();
     void fused_qkv(int att);
+    std::array<int, 3> heads_major(graph_node const& n, float q_scale);
     void attention(int t);
+    void attention_masked(int t);
     void patch_embed(int t);
     bool match_layer(int att, enc_layer& L) const;
     void find_encoder_chain();

@@ -18,9 +18,10 @@ import numpy as np
 from . import _lib as lib
 from ._lib import check, get_lib
 
-F32, F16, U8 = 0, 1, 24
+F32, F16, U8, I32 = 0, 1, 24, 26
 (OP_LINEAR, OP_LAYER_NORM, OP_GELU, OP_RELU, OP_SCALE, OP_ADD, OP_MUL, OP_CONV_2D, OP_CONV_TRANSPOSE_2D, OP_INTERPOLATE, OP_ATTENTION,
- OP_CONCAT, OP_SLICE, OP_RESHAPE, OP_REPEAT, OP_PATCH_EMBED, OP_CONT, OP_IMAGE_U8_TO_F32, OP_IMAGE_NORMALIZE, OP_LEAKY_RELU) = range(2, 22)
+ OP_CONCAT, OP_SLICE, OP_RESHAPE, OP_REPEAT, OP_PATCH_EMBED, OP_CONT, OP_IMAGE_U8_TO_F32, OP_IMAGE_NORMALIZE, OP_LEAKY_RELU,
+ OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED) = range(2, 28)
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
 
@@ -93,8 +94,9 @@ class Graph:
 
     # ---- weights
     def add_weight(self, name: str, array: np.ndarray, dtype: int = F16) -> Tensor:
-        """`array` in torch / numpy index order (slowest first): its reversed shape is the ggml ne."""
-        a = np.ascontiguousarray(array, dtype=np.float32)
+        """`array` in torch / numpy index order (slowest first): its reversed shape is the ggml ne. Also how a constant that is not a file
+        weight enters the graph (a precomputed mask or index); `get_tensor(name)` finds it again."""
+        a = np.ascontiguousarray(array, dtype=np.int32 if dtype == I32 else np.float32)  # I32: an index constant (get_rows)
         ne = (c_int64 * 4)(*_ne(a.shape[::-1]))
         out = c_int32()
         check(self._api.visp_graph_add_weight(self._handle, name.encode(), dtype, ne, a.ctypes.data_as(c_void_p), byref(out)))
@@ -242,18 +244,37 @@ def conv_transpose_2d(m: ModelRef, x: Tensor, stride: int) -> Tensor:  # nn.cpp:
     return m.graph.op(OP_CONV_TRANSPOSE_2D, src, [stride])
 
 
-def patch_embed(m: ModelRef, x: Tensor, patch_size: int) -> Tensor:  # nn.cpp:166-180 (DINOv2: no norm)
-    p = m["projection"]
+def patch_embed(m: ModelRef, x: Tensor, patch_size: int) -> Tensor:  # nn.cpp:166-180 (DINOv2: "projection", no norm; SWIN: "proj" + norm)
+    p = m["proj" if m.find("proj.weight") is not None else "projection"]
     src = [x, p.weights("weight")]
     if (b := p.find("bias")) is not None:
         src.append(b)
-    return m.graph.op(OP_PATCH_EMBED, src, [patch_size])
+    out = m.graph.op(OP_PATCH_EMBED, src, [patch_size])
+    if m.find("norm.weight") is not None:
+        out = layer_norm(m["norm"], out)
+    return out
+
+
+def split_qkv(m: ModelRef, x: Tensor, n_heads: int, split_dim: int):  # nn.cpp:182-208
+    c, n, b, _ = x.ne
+    qkv = linear(m, x)
+    if split_dim == 1:
+        qkv = reshape(m, qkv, c // n_heads, 3, n_heads * n, b)
+        qkv = cont(m, permute(m, qkv, 0, 3, 1, 2))
+    elif split_dim == 2:
+        qkv = reshape(m, qkv, c // n_heads, n_heads, 3, n * b)
+        qkv = cont(m, permute(m, qkv, 0, 1, 3, 2))
+    else:
+        raise ValueError("split_qkv: split_dim is 1 or 2")
+    return tuple(reshape(m, slice_(m, qkv, SLICE_ALL, SLICE_ALL, SLICE_ALL, i), c // n_heads, n_heads, n, b) for i in range(3))
 
 
 def attention(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, mask, scale: float, m_out: ModelRef) -> Tensor:  # nn.cpp:210-244
+    """mask: None, or [n_keys, n_queries, 1 | n_heads, a divisor of batch] added to the scaled scores (head_dim 32 and 64)."""
     if mask is not None:
-        raise NotImplementedError("attention masks are built for the window-attention families only")
-    x = m.graph.op(OP_ATTENTION, [q, k, v], fparams=[scale])
+        x = m.graph.op(OP_ATTENTION_MASKED, [q, k, v, mask], fparams=[scale])
+    else:
+        x = m.graph.op(OP_ATTENTION, [q, k, v], fparams=[scale])
     return linear(m_out, x)
 
 
@@ -289,6 +310,11 @@ def reshape(m, x, *ne): return m.graph.op(OP_RESHAPE, [x], list(_ne(ne)))
 def repeat(m, x, *ne): return m.graph.op(OP_REPEAT, [x], list(_ne(ne)))
 def cont(m, x): return m.graph.op(OP_CONT, [x])
 def leaky_relu(m, x, slope): return m.graph.op(OP_LEAKY_RELU, [x], fparams=[slope])  # ggml_leaky_relu
+def permute(m, x, a0, a1, a2, a3): return m.graph.op(OP_PERMUTE, [x], [a0, a1, a2, a3])  # ggml_permute: source dimension d becomes dimension a_d
+def roll(m, x, s0, s1, s2, s3): return m.graph.op(OP_ROLL, [x], [s0, s1, s2, s3])  # ggml_roll
+def pad(m, x, p0, p1, p2, p3): return m.graph.op(OP_PAD, [x], [p0, p1, p2, p3])  # ggml_pad
+def get_rows(m, table, index): return m.graph.op(OP_GET_ROWS, [table, index])  # ggml_get_rows (constants only: folded)
+def cast(m, x, dtype): return m.graph.op(OP_CAST, [x], [dtype])  # ggml_cast
 
 
 # ---- Depth-Anything-V2 against this layer (the structure of src/visp/arch/dino.cpp + depth-anything.cpp) -----------------------
@@ -449,3 +475,141 @@ def esrgan_generate(m: ModelRef, x: Tensor, scale_factor: int, n_blocks: int) ->
     x = leaky_relu(m, conv_2d(m[seq], x, 1, 1), 0.2)
     x = conv_2d(m[seq + 2], x, 1, 1)
     return m.graph.output(x, "result")
+
+
+# ---- SWIN transformer encoder against this layer (the structure of src/visp/arch/swin.cpp) --------------------------------------------------
+
+def swin_relative_position_index(window: int) -> np.ndarray:  # swin.cpp:26-37
+    n = window
+    i = np.arange(n ** 4)
+    x0, y0, x1, y1 = i % n, (i // n) % n, (i // (n * n)) % n, (i // (n * n) // n) % n
+    return ((y1 - y0 + n - 1) * (2 * n - 1) + (x1 - x0 + n - 1)).astype(np.int32)
+
+
+def swin_attention_mask(w: int, h: int, window: int) -> np.ndarray:  # swin.cpp:165-210: [n_windows, n^2, n^2] of 0 / -inf
+    n, shift = window, window // 2
+    nw_x, nw_y = (w + n - 1) // n, (h + n - 1) // n
+    w_pad, h_pad = nw_x * n, nw_y * n
+    out = np.zeros((nw_y, nw_x, n * n, n * n), np.float32)
+    y, x = np.divmod(np.arange(n * n), n)
+    for iw_y in range(nw_y):
+        for iw_x in range(nw_x):
+            if iw_y < nw_y - 1 and iw_x < nw_x - 1:  # only the windows at the right and bottom edges carry a mask
+                continue
+            zone_y, zone_x = (iw_y * n + y) < h_pad - shift, (iw_x * n + x) < w_pad - shift
+            match = (zone_y[:, None] == zone_y[None, :]) & (zone_x[:, None] == zone_x[None, :])
+            out[iw_y, iw_x][~match] = -np.inf
+    return out.reshape(nw_y * nw_x, n * n, n * n)
+
+
+def swin_precompute(m: ModelRef, image_extent, window: int, n_layers: int = 4):  # swin.cpp:303-314
+    """The constants the reference's caller uploads: the relative position index and one shift mask per map extent, under the names
+    window_attention and layer look them up by."""
+    g = m.graph
+    width, height = image_extent[0] // 4, image_extent[1] // 4
+    out = [g.add_weight(f"window_attention_{window}.rel_pos_index", swin_relative_position_index(window), I32)]
+    for i in range(n_layers + 1):
+        w, h = width >> i, height >> i
+        name = f"swin_layer_{w}x{h}.attn_mask"
+        out.append(g.get_tensor(name) or g.add_weight(name, swin_attention_mask(w, h, window), F16))
+    return out
+
+
+def swin_mlp(m: ModelRef, x: Tensor) -> Tensor:  # swin.cpp:11-16
+    return named(m, linear(m["fc2"], gelu(m, linear(m["fc1"], x))))
+
+
+def swin_window_partition(m: ModelRef, x: Tensor, window: int) -> Tensor:  # swin.cpp:48-56
+    c, w, h, b = x.ne
+    assert w % window == 0 and h % window == 0, "expecting padded input"
+    x = reshape(m, x, c * window, w // window, window, (h // window) * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    return reshape(m, x, c, window * window, (w // window) * (h // window) * b)
+
+
+def swin_window_reverse(m: ModelRef, x: Tensor, w: int, h: int, window: int) -> Tensor:  # swin.cpp:58-67
+    c = x.ne[0]
+    b = x.ne[2] // (w // window) // (h // window)
+    x = reshape(m, x, c * window, window, w // window, (h // window) * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    return reshape(m, x, c, w, h, b)
+
+
+def swin_window_attention(m: ModelRef, x: Tensor, mask: Tensor | None, n_heads: int, window: int) -> Tensor:  # swin.cpp:69-97
+    c, n, b, _ = x.ne
+    rel_pos_index = m.graph.get_tensor(f"window_attention_{window}.rel_pos_index")
+    rel_pos_bias = get_rows(m, m.weights("relative_position_bias_table"), rel_pos_index)
+    rel_pos_bias = reshape(m, rel_pos_bias, n_heads, n, n, 1)
+    rel_pos_bias = permute(m, rel_pos_bias, 2, 0, 1, 3)  # [n, n, n_heads, 1]
+    rel_pos_bias = cast(m, rel_pos_bias, F16)  # get_rows gives f32
+    attn_mask = rel_pos_bias
+    if mask is not None:
+        n_windows = mask.ne[2]
+        if b > n_windows:  # several images in the batch
+            mask = reshape(m, mask, n, n, n_windows, 1)
+            mask = repeat(m, mask, n, n, n_windows, b // n_windows)
+        mask = reshape(m, mask, n, n, 1, b)
+        mask = repeat(m, mask, n, n, n_heads, b)
+        attn_mask = add(m, mask, attn_mask)  # [n, n, n_heads, b] + [n, n, n_heads, 1]
+    q, k, v = split_qkv(m["qkv"], x, n_heads, 2)
+    x = attention(m, q, k, v, attn_mask, 1.0 / math.sqrt(c // n_heads), m["proj"])
+    return named(m, x)
+
+
+def swin_block(m: ModelRef, x: Tensor, mask: Tensor | None, n_heads: int, window: int, w: int, h: int, shift: int) -> Tensor:  # swin.cpp:99-141
+    c, n, b, _ = x.ne
+    assert n == w * h, "spatial dimensions do not match"
+    shortcut = x
+    x = layer_norm(m["norm1"], x)
+    x = reshape(m, x, c, w, h, b)
+    pad_r, pad_b = (window - w % window) % window, (window - h % window) % window
+    if pad_r > 0 or pad_b > 0:
+        x = pad(m, x, 0, pad_r, pad_b, 0)
+    assert shift == 0 or mask is not None
+    if shift > 0:
+        x = roll(m, x, 0, -shift, -shift, 0)
+    x = swin_window_partition(m, x, window)
+    x = swin_window_attention(m["attn"], x, mask, n_heads, window)
+    x = swin_window_reverse(m, x, w + pad_r, h + pad_b, window)
+    if shift > 0:  # undo the shift
+        x = roll(m, x, 0, shift, shift, 0)
+    if pad_r > 0 or pad_b > 0:  # undo the padding
+        x = reshape(m, x, c, w + pad_r, h + pad_b, b)
+        x = cont(m, slice_(m, x, SLICE_ALL, (0, w), (0, h), SLICE_ALL))
+    x = reshape(m, x, c, n, b)
+    x = add(m, x, shortcut)
+    x = add(m, x, swin_mlp(m["mlp"], layer_norm(m["norm2"], x)))
+    return named(m, x)
+
+
+def swin_patch_merging(m: ModelRef, x: Tensor, w: int, h: int) -> Tensor:  # swin.cpp:143-161
+    c, n, b, _ = x.ne
+    assert n == w * h and w % 2 == 0 and h % 2 == 0
+    x = reshape(m, x, c, w, h, b)
+    x = concat(m, [slice_(m, x, SLICE_ALL, (0, w, 2), (0, h, 2)), slice_(m, x, SLICE_ALL, (0, w, 2), (1, h, 2)),
+                   slice_(m, x, SLICE_ALL, (1, w, 2), (0, h, 2)), slice_(m, x, SLICE_ALL, (1, w, 2), (1, h, 2))], 0)
+    x = reshape(m, x, c * 4, n // 4, b)
+    return named(m, linear(m["reduction"], layer_norm(m["norm"], x)))
+
+
+def swin_layer(m: ModelRef, x: Tensor, w: int, h: int, depth: int, n_heads: int, window: int, down: bool):  # swin.cpp:223-244
+    """Returns (x_out, w, h, x_down, w_down, h_down). The layer's mask goes to EVERY block, as the reference passes it."""
+    attn_mask = m.graph.get_tensor(f"swin_layer_{w}x{h}.attn_mask")
+    blocks = m["blocks"]
+    for i in range(depth):
+        x = swin_block(blocks[i], x, attn_mask, n_heads, window, w, h, 0 if i % 2 == 0 else window // 2)
+    if down:
+        return x, w, h, swin_patch_merging(m["downsample"], x, w, h), (w + 1) // 2, (h + 1) // 2
+    return x, w, h, x, w, h
+
+
+def swin_encode(m: ModelRef, x: Tensor, window: int, depths, n_heads):  # swin.cpp:246-266; x = the normalised f32 image [3, W, H, N]
+    x = patch_embed(m["patch_embed"], x, 4)
+    c, w, h, b = x.ne
+    x = reshape(m, x, c, w * h, b)
+    outs = []
+    for i in range(len(depths)):
+        x_out, w_out, h_out, x, w, h = swin_layer(m["layers"][i], x, w, h, depths[i], n_heads[i], window, i < len(depths) - 1)
+        out = layer_norm(m[f"norm{i}"], x_out)
+        outs.append(reshape(m, out, out.ne[0], w_out, h_out, b))
+    return outs
