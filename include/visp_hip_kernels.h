@@ -152,14 +152,18 @@ VX_API int vx_conv3x3_f16(const vx_gemm_args* args, void* stream);
  * reads the first cin/32 planes and writes its 32 (or 64) outputs as the next plane(s), so concat
  * (esrgan.cpp:29-36) is never materialised.
  *   v = conv(x) + bias;  act: v = max(v, 0.2 v);  res1: v = v*s1 + res1;  res2: v = v*s2 + res2.
+ *   The order is fixed: activation first, then res1, then res2. s1 / s2 apply only together with their residual.
  *   x_residual (cout = 64): v = v*s1 + x[planes 0,1] with x taken from the halo already in LDS (no second read);
- *   mutually exclusive with res1, res2 still applies afterwards.
+ *   mutually exclusive with res1, res2 still applies afterwards. The fold adds x * f16(1/s1) to the accumulators, so it is
+ *   refused with act != 0, with a_relu and for an s1 whose f16 reciprocal times s1 is not 1 (vx_dconv_x_residual_supported);
+ *   pass x as res1 there.
  * up2: the source is [B, H/2, W/2, 32] per plane and is nearest-upsampled on the fly (esrgan.cpp:13-19).
  * w: packed by the host as [cin/32][9 taps][cout][32] f16 with the four 16-byte groups of every (tap, n) row
  *    stored at position g ^ ((n >> 2) & 3)  (see pack_dconv in csrc/graph.cpp).
  * VX_DC_RGB_F32: cout = 32 (3 real), out = f32 [B, H, W, 3], no activation / residuals.
  * VX_DC_HEAD_F32: cout = 32, out = f32 [B, H, W] = head_scale * relu(sum_n relu(v)[n] * head_w[n] + head_bias)
  *   (head.conv2 + ReLU + head.conv3 1x1 + ReLU of the DPT head, depth-anything.cpp:87-94).
+ *   Both f32 epilogues refuse act != 0, res1, res2 and x_residual (they have no place to apply them).
  * The same kernel serves NHWC maps: *_pix = elements between pixels (0 = 32 = planar), *_plane = elements between
  *   consecutive 32-channel groups (32 for NHWC). act: 0 none, 1 LeakyReLU 0.2, 2 ReLU. a_relu: convolve relu(x). */
 enum { VX_DC_F16 = 0, VX_DC_RGB_F32 = 1, VX_DC_HEAD_F32 = 2 };
@@ -188,6 +192,15 @@ VX_API int vx_dconv_bilinear_supported(int cout, int H, int W, int hs, int ws);
 VX_API int vx_dconv3x3_f16(const vx_dconv_args* args, void* stream);
 /* sets the kernels' dynamic-LDS attribute (call once per process before capturing launches into a hipGraph) */
 VX_API int vx_dconv_prepare(void);
+/* may the "+ x" of x_residual be folded into the accumulators for this s1 / act / a_relu (see above) */
+VX_API int vx_dconv_x_residual_supported(float s1, int act, int a_relu);
+/* test hooks (process-global, host side only; the device code is the product's):
+ * vx_dconv_set_block_cap(n): the launcher sizes its persistent grid as on a device with n CUs (n a multiple of 8, >= 8), so that a small
+ *   problem walks several tiles per block; n <= 0 restores the device's CU count. Returns 0 for any other n.
+ * vx_dconv_set_resident_mode(mode): overrides VISP_DCONV_RES (0 never resident, 1 cin 64, 2 cin <= 128); mode < 0 = the environment
+ *   variable or, without one, the default. */
+VX_API int vx_dconv_set_block_cap(int n);
+VX_API void vx_dconv_set_resident_mode(int mode);
 
 /* ---- one launch per DPT residual unit on small maps (depth-anything.cpp:15-33; kernels_rcu.hip) -------------
  *   out = P( conv2( relu( conv1( relu(x) ) + b1 ) ) + b2 + x [+ res2] ),  P = identity or the 1x1 projection wp (+ bp)

@@ -77,6 +77,16 @@ def conv_leaky(g, rng, slope, W=20, H=18, B=2):
     return {"x": x, "y": y, "w": w, "b": b}
 
 
+def conv_narrow_input(g, rng, cin, cout=32, W=20, H=18, B=2):
+    """conv3x3 (cin 16 or 48 -> 32, stride 1, pad 1) on a 20-wide NHWC map: the LDS-ring conv's output widths and map size with an input narrower
+    than its 32-channel pixel stride (16: the GEMM family's conv) or no multiple of its chunk (48: run as 64 with zero weights)."""
+    m = G.ModelRef(g)
+    w, b = conv_weight(g, "c", rng, cout, cin)
+    x = g.input((cin, W, H, B), G.F16, "x")
+    y = g.output(G.conv_2d(m["c"], x, 1, 1), "y")
+    return {"x": x, "y": y, "w": w, "b": b}
+
+
 def encoder_chain(g, rng, scales, ps=14, side=2, B=2):
     """dino::prepare_tokens (dino.cpp:32-46) and len(scales) encoder layers of width 384 / MLP 1536 / 6 heads written out like dino_layer
     (dino.cpp:48-90), each attention with its own explicit scale; the last residual stream goes through a final LayerNorm (a tap) to the output."""

@@ -49,6 +49,18 @@ def assert_f16_ulp(got, want64, ulps=1.0, what=""):
                              f"got {[g[tuple(i)] for i in idx]} want {[w[tuple(i)] for i in idx]}")
 
 
+def conv3x3(x, w, b=None):
+    """x (B, H, W, Cin), w OHWI (Cout, 3, 3, Cin), stride 1, zero padding 1 -> float64 (B, H, W, Cout)"""
+    x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    B, H, W, _ = x.shape
+    xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    out = np.zeros((B, H, W, w.shape[0]))
+    for ky in range(3):
+        for kx in range(3):
+            out += xp[:, ky:ky + H, kx:kx + W] @ w[:, ky, kx].T
+    return out if b is None else out + np.asarray(b, np.float64)
+
+
 # ---- element-wise ------------------------------------------------------------------------------------------------------------
 
 def broadcast_period(a_shape, b_shape) -> int:

@@ -123,7 +123,9 @@ def test_dconv_bilinear_input(cin, hs, ws, H, W, B):
     """Round 3: ggml_interpolate(BILINEAR | ALIGN_CORNERS) fused into the consumer conv (depth-anything.cpp:36-38 -> head.conv1,
     :84-85 -> head.conv2; ml.cpp:782-788): the conv of the resized map, resized in the halo loader, against
     conv(oracle.interpolate(x)) -- both head forms (f16 map out, fused depth head) and both tile shapes (widths with a
-    remainder <= 16 take the 32x16 strip), several batch images so that persistent blocks cross image boundaries."""
+    remainder <= 16 take the 32x16 strip) and several batch images. Only the 518 x 518 case (in both forms) has more tiles than an MI355X has CUs;
+    the others run one tile per block (70 x 105 x 2 is 36 tiles). Persistent blocks that cross tile shapes and image boundaries are checked by
+    the capped runs of tests/test_gpu_dconv_matrix.py."""
     from tests import gpu_util as G
     rng = np.random.default_rng(cin + hs + W)
     assert G.api().vx_dconv_bilinear_supported(32, H, W, hs, ws) == 1

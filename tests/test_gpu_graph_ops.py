@@ -250,6 +250,22 @@ def test_conv_leaky_numbers(device, slope):
     assert np.abs(got - want).max() <= 4e-3 * np.abs(want).max()
 
 
+@pytest.mark.parametrize("cin", [16, 48])
+def test_conv_narrow_input_numbers(device, cin):
+    """Cin = 16 (below the LDS-ring conv's pixel stride: the GEMM family's conv) and Cin = 48 (the LDS-ring conv on weights padded to 64, the
+    last pixel's missing channels zero-filled by its loader) against the float64 conv: the f32 sum of K = 9 cin f16 products in any order is within
+    (K + 8) 2^-24 of the sum of magnitudes, then one f16 rounding."""
+    rng = np.random.default_rng(cin)
+    g = G.Graph(device)
+    c = GC.conv_narrow_input(g, rng, cin)
+    x = R.f16(rng.standard_normal((2, 18, 20, cin)))
+    (got,) = run(g, {c["x"]: x}, [c["y"]])
+    want = R.conv3x3(x, c["w"], c["b"])
+    mag = R.conv3x3(np.abs(x), np.abs(c["w"]), np.abs(c["b"]))
+    assert got.shape == want.shape and np.isfinite(got).all()
+    assert (np.abs(got - want) <= (9 * cin + 8) * 2.0 ** -24 * mag + np.maximum(2.0 ** -11 * np.abs(want), 2.0 ** -25)).all()
+
+
 @pytest.mark.parametrize("scales", [(0.125, 0.125), (0.125, 0.5)])
 def test_encoder_chain_matches_the_per_node_lowering(device, scales):
     """The two-layer chain lowered with the model kernels (dino_block when the scales agree) and node by node agree to f16 rounding of the

@@ -255,7 +255,7 @@ import graph_cases as GC  # noqa: E402
 @pytest.mark.parametrize("cout", [64, 32])
 def test_conv_relu_add_is_not_a_dconv_epilogue(cout):
     """conv3x3 to 32 / 64 channels on a 20-wide map (the LDS-ring conv's shape) -> relu -> + another map: the conv keeps the relu in its epilogue,
-    the add is a launch of its own (the conv adds its residuals before its activation)."""
+    the add is a launch of its own (the kernel applies the activation first and could take the add; this lowering does not ask it to)."""
     g = _g()
     GC.conv_relu_add(g, np.random.default_rng(1), cout)
     g.allocate()
@@ -286,6 +286,17 @@ def test_relu_into_a_conv_that_is_an_output(planar):
         assert lines == ["image_planes [3, 20, 18, 2]", "dconv3x3(planes)[f32 image]", "planes_to_nhwc [64, 20, 18, 2]", "dconv3x3[relu-in]"]
     else:
         assert lines == ["dconv3x3[relu-in]"]
+
+
+@pytest.mark.parametrize("cin", [16, 48])
+def test_conv_with_a_narrow_input(cin):
+    """conv3x3 to 32 channels on a 20-wide map with Cin = 16 is the GEMM family's conv (the LDS-ring conv's pixel stride is 32 channels at least,
+    its launcher refuses less); Cin = 48 is the LDS-ring conv on weights padded to 64."""
+    g = _g()
+    GC.conv_narrow_input(g, np.random.default_rng(9), cin)
+    g.allocate()
+    lines = g.describe().strip().splitlines()[:-1]
+    assert len(lines) == 1 and lines[0].startswith(f"dconv3x3 M=720 N=32 K={9 * cin}" if cin == 48 else "conv3x3 M=720 N=32 K=144"), lines
 
 
 @pytest.mark.parametrize("slope", [0.1, 1.5, -0.5])

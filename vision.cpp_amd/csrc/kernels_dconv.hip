@@ -878,8 +878,12 @@ __global__ __launch_bounds__(512) void dconv3x3_kernel(const vx_dconv_args p) {
     }
 }
 
+int g_block_cap = 0;  // test hook (vx_dconv_set_block_cap): > 0 stands in for the CU count
+int g_res_mode = -1;  // test hook (vx_dconv_set_resident_mode): >= 0 overrides VISP_DCONV_RES
+
 int dconv_grid_blocks() {
     static int n_cu = 0;
+    if (g_block_cap > 0) return g_block_cap;
     if (!n_cu) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
@@ -936,7 +940,8 @@ int launch_dconv(const vx_dconv_args& a, hipStream_t s) {
             // launches, streamed -> resident): cin 64 with 3 halo stages 6.62 -> 6.72, cin 96 with 2 stages 7.79 ->
             // 7.75, cin 128 with 2 stages 9.47 -> 9.04. Default: resident at cin = 128 only. VISP_DCONV_RES: 0 = never,
             // 1 = cin 64, 2 = cin <= 128, unset = cin 128.
-            static const int res_mode = getenv("VISP_DCONV_RES") ? atoi(getenv("VISP_DCONV_RES")) : -1;
+            static const int env_mode = getenv("VISP_DCONV_RES") ? atoi(getenv("VISP_DCONV_RES")) : -1;
+            const int res_mode = g_res_mode >= 0 ? g_res_mode : env_mode;
             if (res_mode >= 1 && a.cin == 64) return launch_variant<32, EPI, false, false, 2, 3>(a, s);   // 120 + 36 KB
             if ((res_mode >= 2 && a.cin <= 128) || (res_mode < 0 && a.cin == 128)) return launch_variant<32, EPI, false, false, 4, 2>(a, s); // 80 + 72 KB
         }
@@ -1069,6 +1074,25 @@ extern "C" int vx_dconv_bilinear_supported(int cout, int H, int W, int hs, int w
     return rows(ry, 18) <= 12 && rows(rx, 34) <= 21 && rows(ry, 34) <= 21 && rows(rx, 18) <= 12;
 }
 
+extern "C" int vx_dconv_set_block_cap(int n) {
+    if (n > 0 && (n < 8 || n % 8 != 0)) {
+        vx_set_error("vx_dconv_set_block_cap: %d is not a multiple of 8 (one block per XCD at least)", n);
+        return 0;
+    }
+    g_block_cap = n > 0 ? n : 0;
+    return 1;
+}
+
+extern "C" void vx_dconv_set_resident_mode(int mode) { g_res_mode = mode < 0 ? -1 : mode; }
+
+// the identity fold adds x * f16(1/s1) to the accumulators BEFORE the activation and the * s1, and takes x from the fragments AFTER
+// a_relu: it is "+ x" only without either and where f16(1/s1) * s1 is 1
+extern "C" int vx_dconv_x_residual_supported(float s1, int act, int a_relu) {
+    if (act != 0 || a_relu || s1 == 0.0f || !std::isfinite(s1)) return 0;
+    const float inv = (float)(f16)(1.0f / s1);
+    return std::isfinite(inv) && inv * s1 == 1.0f;
+}
+
 extern "C" int vx_dconv3x3_f16(const vx_dconv_args* args, void* stream) {
     const vx_dconv_args& a = *args;
     VX_REQUIRE(a.x && a.w && a.out, "vx_dconv3x3_f16: null operand");
@@ -1094,16 +1118,21 @@ extern "C" int vx_dconv3x3_f16(const vx_dconv_args* args, void* stream) {
     hipStream_t s = as_stream(stream);
     if (a.epi == VX_DC_RGB_F32) {
         VX_REQUIRE(a.cout == 32 && !a.a_relu, "vx_dconv3x3_f16: the rgb head takes weights padded to 32 outputs");
+        VX_REQUIRE(a.act == 0 && !a.res1 && !a.res2 && !a.x_residual, "vx_dconv3x3_f16: the rgb head has no activation and no residuals");
         return launch_dconv<32, VX_DC_RGB_F32>(a, s);
     }
     if (a.epi == VX_DC_HEAD_F32) {
         VX_REQUIRE(a.cout == 32 && a.head_w && !a.a_relu, "vx_dconv3x3_f16: the fused depth head is a 32-channel epilogue with head_w set");
+        VX_REQUIRE(a.act == 0 && !a.res1 && !a.res2 && !a.x_residual, "vx_dconv3x3_f16: the fused depth head applies its own ReLUs and takes no residuals");
         return launch_dconv<32, VX_DC_HEAD_F32>(a, s);
     }
     VX_REQUIRE(a.epi == VX_DC_F16, "vx_dconv3x3_f16: unknown epilogue %d", a.epi);
     VX_REQUIRE(a.out_plane % 8 == 0 && a.res1_plane % 8 == 0 && a.res2_plane % 8 == 0, "vx_dconv3x3_f16: plane strides must be multiples of 8");
     VX_REQUIRE(!a.x_residual || (a.cout == 64 && a.cin >= 64 && !a.res1 && !a.up2 && a.s1 != 0.0f),
                "vx_dconv3x3_f16: x_residual needs cout = 64 <= cin, no res1, no upsampling");
+    VX_REQUIRE(!a.x_residual || vx_dconv_x_residual_supported(a.s1, a.act, a.a_relu),
+               "vx_dconv3x3_f16: x_residual needs act = 0, no a_relu and an s1 = %g whose reciprocal is exact in f16; pass x as res1", (double)a.s1);
+    VX_REQUIRE(a.act >= 0 && a.act <= 2, "vx_dconv3x3_f16: unknown activation %d", a.act);
     if (a.cout == 32) return launch_dconv<32, VX_DC_F16>(a, s);
     if (a.cout == 64) return launch_dconv<64, VX_DC_F16>(a, s);
     vx_set_error("vx_dconv3x3_f16: Cout %d not in {32, 64}", a.cout);

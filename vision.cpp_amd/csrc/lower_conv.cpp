@@ -197,7 +197,7 @@ int lowering::plain_gemm_reader(int t) const { // the sole reader of t (through 
     return -1;
 }
 bool lowering::dconv_shape(graph_node const& n, graph_node const& x, graph_node const& w) const {
-    return g.fused_models && !env().no_dconv && n.op == gop_conv_2d && n.dtype == gdt_f16 && w.ne[1] == 3 && w.ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1 && x.ne[0] % 16 == 0 &&
+    return g.fused_models && !env().no_dconv && n.op == gop_conv_2d && n.dtype == gdt_f16 && w.ne[1] == 3 && w.ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1 && x.ne[0] % 16 == 0 && x.ne[0] >= 32 &&
            (w.ne[3] == 32 || w.ne[3] == 64) && n.ne[1] >= env().dconv_min_w;
 }
 
@@ -309,7 +309,7 @@ bool lowering::planar_conv(int t, std::string const& who) {
     for (int i = 0; i < 2; ++i) {
         if (res[i] < 0) continue;
         planar_map const& rm = planar.at(res[i]);
-        if (i == 0 && !up2 && cout == 64 && rm.buf == in.buf && rm.plane0 == in.plane0 && in.n_planes >= 2 && s1 != 0.0f) { d.x_residual = 1; continue; } // x = the halo's first two planes
+        if (i == 0 && !up2 && cout == 64 && rm.buf == in.buf && rm.plane0 == in.plane0 && in.n_planes >= 2 && vx_dconv_x_residual_supported(s1, act, 0)) { d.x_residual = 1; continue; } // x = the halo's first two planes (else: an ordinary res1)
         reads.push_back(rm.buf);
         rp[i] = ptr(rm.buf);
         r_off[i] = (int64_t)rm.plane0 * rm.plane_elems;
@@ -574,7 +574,7 @@ void lowering::gemm_like(int t) {
     tag(group_of(who, n, stride).c_str(), 2.0 * a.M * (double)p.n_real * p.k_real, (double)a.M * (p.k_real + n.ne[0]) * 2 + (double)p.N * p.K * 2);
 }
 
-// 3x3 / stride 1 / pad 1 with Cin % 16 == 0 and 32 or 64 output channels: the persistent LDS-ring conv (kernels_dconv.hip), with the
+// 3x3 / stride 1 / pad 1 with Cin % 16 == 0, Cin >= 32 (the kernel's pixel stride; a narrower map goes to the GEMM family's conv) and 32 or 64 output channels: the persistent LDS-ring conv (kernels_dconv.hip), with the
 // ReLU of a relu -> conv chain applied to the fragments, ReLU or up to two residual maps in the epilogue, and -- where the input is the
 // bilinear (align_corners) resize of a smaller map read by this conv only -- the resize done by the conv's halo loader
 void lowering::dconv(int t, std::string const& who) {
@@ -583,7 +583,7 @@ void lowering::dconv(int t, std::string const& who) {
     const int xs = n.src[0], wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
     graph_node const& x = g.nodes[xs];
     const int cin = (int)x.ne[0], cout = (int)n.ne[0], H = (int)n.ne[2], W = (int)n.ne[1], B = (int)n.ne[3];
-    const epilogue e = match_epilogue(t, false, false, true, false); // the LDS-ring conv adds its residuals before the activation: an add behind a relu is a launch
+    const epilogue e = match_epilogue(t, false, false, true, false); // the LDS-ring conv applies the activation, then the residuals (tests/test_gpu_dconv_matrix.py), so it could take an add behind a relu; this lowering does not ask for one yet: it stays a launch
     absorb(e, t);
     vx_dconv_args d;
     memset(&d, 0, sizeof d);
