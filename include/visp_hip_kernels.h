@@ -289,7 +289,7 @@ VX_API int vx_bf_sigmoid_out_f32(const void* a, int lda, float* out, int64_t n, 
 /* y f16 = a + b[i mod b_period]; a f16 or f32 (SAM decoder: queries + query_pe, keys + key_pe, embedding + no_mask_embed) */
 VX_API int vx_add_rows_f16(const void* a, int a_is_f32, const void* b, int64_t b_period, void* y, int64_t n, void* stream);
 /* attention with few queries or few keys (SAM mask decoder, mobile-sam.cpp:306-320): q [Nq][heads*hd], k, v [Nk][heads*hd]
- * -> out [Nq][heads*hd]; hd in {8, 16, 32}, Nk <= 4096; scale = 1/sqrt(hd) */
+ * -> out [Nq][heads*hd]; hd a power of two <= 32 (1, 2, 4, 8, 16, 32), Nk <= 4096; scale = 1/sqrt(hd) */
 VX_API int vx_small_attention_f16(const void* q, const void* k, const void* v, void* out, int Nq, int Nk, int heads, int hd, void* stream);
 /* sam::interpolate_bilinear (mobile-sam.cpp:485-516) for sam_process_mask (:556-583): source element (x, y) at
  * src[(y * sstride + x) * step], f16 or f32; dst f32 [dh][dw], or u8 thresholded at 0 (0 / 255) when out_u8 */
@@ -313,6 +313,9 @@ VX_API int vx_attention_masked_f16(const void* q, const void* k, const void* v, 
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);
+/* test hook (host side only): 4 or 8 forces vx_attention_f16's waves per block (128 / 256 queries), whatever T and VISP_ATTN_WAVES say;
+ * anything else restores the default rule (VISP_ATTN_WAVES, else 8 above T = 512 and 4 up to it) */
+VX_API void vx_attention_set_waves(int waves);
 /* diagnostics (tools/attn_stamps.py): u64 [blocks][waves][4] = cycles in {wait + barrier, scores + softmax, PV, lifetime}; NULL = off */
 VX_API void vx_attention_set_stamps(void* stamps);
 

@@ -1,0 +1,190 @@
+"""-m gpu: the four attention entry points over their argument space (tests/attn_cases.py) against the float64 references and the derived
+per-element allowance of tests/attn_ref.py. Every output buffer starts zeroed and is compared in full, GUARD_ROWS zeroed rows behind the last row
+the call owns included (one full query block, so a store from any row of a tail block lands inside the buffer and is compared): an element the
+call must not write has allowance 0 and must still hold zero bits. Nothing here is built to fault; the refusals return before any launch."""
+import time
+from collections import defaultdict
+
+import numpy as np
+import pytest
+
+import attn_cases as T
+import attn_ref as R
+from visioncpp_amd import _lib as L
+
+pytestmark = pytest.mark.gpu
+
+from gpu_util import api, dev, empty, release, sync  # noqa: E402
+
+GUARD_ROWS = 256  # the largest query block of the four kernels
+RATIO = defaultdict(float)  # (entry point, case group) -> largest error / allowance seen; reported, not asserted
+WAVE_BITS = {"equal": 0, "compared": 0}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
+    L.vx_check(api().vx_set_device(0))
+    t0 = time.perf_counter()
+    yield
+    print(f"\n{len(T.ALL)} cases in {time.perf_counter() - t0:.1f} s; largest |got - want| / allowance per entry point and group:")
+    for (entry, grp), ratio in sorted(RATIO.items()):
+        print(f"  {entry:34s} {grp:10s} {ratio:.3f}")
+    print(f"vx_attention_f16, 4 waves against 8 waves: {WAVE_BITS['equal']} of {WAVE_BITS['compared']} outputs bit-identical")
+
+
+@pytest.fixture(autouse=True)
+def _release_buffers():
+    yield
+    release()
+
+
+def _out(want):
+    return empty(want.size * 2)
+
+
+def launch_attention(a, want, waves=0, limit=-1.0):
+    out = _out(want)
+    try:
+        api().vx_attention_set_waves(waves)
+        api().vx_attention_set_fast_limit(limit)
+        L.vx_check(api().vx_attention_f16(dev(a["q"]).ptr, dev(a["k"]).ptr, dev(a["v"]).ptr, out.ptr, a["B"], a["H"], a["T"], None))
+        sync()
+    finally:
+        api().vx_attention_set_waves(0)
+        api().vx_attention_set_fast_limit(-1.0)
+    return out.to_numpy(np.float16, want.shape)
+
+
+def launch_masked(a, want):
+    out = _out(want)
+    L.vx_check(api().vx_attention_masked_f16(dev(a["q"]).ptr, dev(a["k"]).ptr, dev(a["v"]).ptr, dev(a["mask"]).ptr, out.ptr, a["B"], a["H"], a["T"], a["head_dim"],
+                                             a["Hm"], a["Bm"], a["mask_is_f32"], None))
+    sync()
+    return out.to_numpy(np.float16, want.shape)
+
+
+def launch_window(a, want):
+    """the plain form through vx_window_attention_f16 and its packer, the shifted form through vx_swin_attention_pack_bias and the masked entry point"""
+    N, heads = a["N"], a["heads"]
+    img = api().vx_window_attention_bias_bytes(N, heads) // 2
+    out = _out(want)
+    if a["ws"]:
+        packed = np.zeros(4 * img, np.uint16)
+        L.vx_check(api().vx_swin_attention_pack_bias(a["table"].ctypes.data, a["ws"], heads, packed.ctypes.data))
+        L.vx_check(api().vx_window_attention_masked_f16(dev(a["qkv"]).ptr, dev(packed).ptr, out.ptr, a["n_windows"], N, heads, a["nwx"], a["nwy"], None))
+    else:
+        packed = np.zeros(img, np.uint16)
+        bias = np.ascontiguousarray(a["bias"], np.float32)
+        L.vx_check(api().vx_window_attention_pack_bias(bias.ctypes.data, N, heads, packed.ctypes.data))
+        L.vx_check(api().vx_window_attention_f16(dev(a["qkv"]).ptr, dev(packed).ptr, out.ptr, a["n_windows"], N, heads, None))
+    sync()
+    return out.to_numpy(np.float16, want.shape)
+
+
+def launch_small(a, want):
+    out = _out(want)
+    L.vx_check(api().vx_small_attention_f16(dev(a["q"]).ptr, dev(a["k"]).ptr, dev(a["v"]).ptr, out.ptr, a["Nq"], a["Nk"], a["heads"], a["hd"], None))
+    sync()
+    return out.to_numpy(np.float16, want.shape)
+
+
+LAUNCH = {"attention": launch_attention, "masked": launch_masked, "window": launch_window, "small": launch_small}
+ENTRY = {"attention": "vx_attention_f16", "masked": "vx_attention_masked_f16", "window": "vx_window_attention_f16", "shifted": "vx_window_attention_masked_f16",
+         "small": "vx_small_attention_f16"}
+
+
+def compare(got, ref, key, what=""):
+    want, allow, written = ref
+    bits = got.view(np.uint16)
+    assert not bits[~written].any(), f"{what}: {int((bits[~written] != 0).sum())} elements written that the call must leave alone"
+    assert np.isfinite(got).all(), what
+    err = np.abs(got.astype(np.float64) - want)
+    ratio = float((err[written] / allow[written]).max())
+    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
+    RATIO[key] = max(RATIO[key], ratio)
+    worst = np.unravel_index(np.argmax(err - allow), err.shape)
+    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
+                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
+
+
+def check(case, group):
+    a = T.materialize(case)
+    ref = R.evaluate(a["entry"], a, GUARD_ROWS)
+    key = (ENTRY[group], case.get("data") or case.get("content") or "random")
+    if a["entry"] != "attention":
+        compare(LAUNCH[a["entry"]](a, ref[0]), ref, key, case["id"])
+        return
+    # both block shapes through the hook, and the default rule; from three key tiles on also with every tile on the full path
+    for limit in (-1.0, 0.0) if a["T"] > 128 else (-1.0,):
+        got = {w: launch_attention(a, ref[0], w, limit) for w in (4, 8, 0)}
+        for w, g in got.items():
+            compare(g, ref, key, f"{case['id']} waves {w} limit {limit}")
+        # the two block shapes walk the same 32-query groups over the same tile stream: the same bits
+        WAVE_BITS["compared"] += 1
+        WAVE_BITS["equal"] += int(np.array_equal(got[4].view(np.uint16), got[8].view(np.uint16)))
+        np.testing.assert_array_equal(got[4].view(np.uint16), got[8].view(np.uint16))
+        np.testing.assert_array_equal(got[0].view(np.uint16), got[T.attention_default_waves(a["T"])].view(np.uint16))
+
+
+def _ids(cases):
+    return [c["id"] for c in cases]
+
+
+@pytest.mark.parametrize("case", T.group("attention"), ids=_ids(T.group("attention")))
+def test_attention(case):
+    check(case, "attention")
+
+
+@pytest.mark.parametrize("case", T.group("masked"), ids=_ids(T.group("masked")))
+def test_attention_masked(case):
+    check(case, "masked")
+
+
+@pytest.mark.parametrize("case", T.group("window"), ids=_ids(T.group("window")))
+def test_window_attention(case):
+    check(case, "window")
+
+
+@pytest.mark.parametrize("case", T.group("shifted"), ids=_ids(T.group("shifted")))
+def test_window_attention_shifted(case):
+    check(case, "shifted")
+
+
+@pytest.mark.parametrize("case", T.group("small"), ids=_ids(T.group("small")))
+def test_small_attention(case):
+    check(case, "small")
+
+
+# ---- refusals: 0 and the message, before any launch ------------------------------------------------------------------------------------------
+
+def _refusals(table, base, call):
+    scratch = empty(1 << 16)
+    for fields, message in table:
+        args = dict(base, **fields)
+        args = {k: (scratch.ptr if v == "ptr" else v) for k, v in args.items()}
+        assert call(args) == 0, f"accepted: {fields}"
+        assert message.encode() in api().vx_last_error(), (fields, api().vx_last_error())
+
+
+def test_attention_refusals():
+    base = dict(q="ptr", k="ptr", v="ptr", out="ptr", B=1, H=1, T=64)
+    _refusals(T.ATTENTION_REFUSALS, base, lambda a: api().vx_attention_f16(a["q"], a["k"], a["v"], a["out"], a["B"], a["H"], a["T"], None))
+
+
+def test_attention_masked_refusals():
+    base = dict(q="ptr", k="ptr", v="ptr", mask="ptr", out="ptr", B=4, H=2, T=32, head_dim=32, Hm=2, Bm=2)
+    _refusals(T.MASKED_REFUSALS, base,
+              lambda a: api().vx_attention_masked_f16(a["q"], a["k"], a["v"], a["mask"], a["out"], a["B"], a["H"], a["T"], a["head_dim"], a["Hm"], a["Bm"], 0, None))
+
+
+def test_window_attention_refusals():
+    base = dict(qkv="ptr", bias="ptr", out="ptr", n_windows=4, N=49, heads=1, nwx=0, nwy=0)
+    _refusals(T.WINDOW_REFUSALS, base,
+              lambda a: api().vx_window_attention_masked_f16(a["qkv"], a["bias"], a["out"], a["n_windows"], a["N"], a["heads"], a["nwx"], a["nwy"], None))
+    assert api().vx_window_attention_f16(None, None, None, 1, 49, 1, None) == 0 and b"bad operands" in api().vx_last_error()
+
+
+def test_small_attention_refusals():
+    base = dict(q="ptr", k="ptr", v="ptr", out="ptr", Nq=4, Nk=16, heads=1, hd=8)
+    _refusals(T.SMALL_REFUSALS, base, lambda a: api().vx_small_attention_f16(a["q"], a["k"], a["v"], a["out"], a["Nq"], a["Nk"], a["heads"], a["hd"], None))

@@ -148,7 +148,7 @@ KERNEL_SYMBOLS = [
     "vx_memcpy_h2d", "vx_memcpy_d2h", "vx_memcpy_d2d", "vx_malloc_host", "vx_free_host", "vx_memcpy_h2d_async", "vx_memcpy_d2h_async", "vx_event_sync", "vx_stream_create", "vx_stream_destroy", "vx_stream_sync",
     "vx_event_create", "vx_event_destroy", "vx_event_record", "vx_event_elapsed_ms", "vx_stream_wait_event", "vx_graph_begin_capture",
     "vx_graph_end_capture", "vx_graph_launch", "vx_graph_destroy", "vx_gemm_f16", "vx_gemm_pick_k_splits", "vx_gemm_fp8_supported", "vx_gemm_fp8", "vx_quantize_rows_e4m3", "vx_quantize_rows_e4m3_host", "vx_conv3x3_supported", "vx_conv3x3_f16", "vx_rcu_supported", "vx_rcu_fused_f16", "vx_nearest_f16", "vx_image_planes_f32", "vx_esrgan_tiles_in_f32",
-    "vx_attention_f16", "vx_attention_set_fast_limit", "vx_attention_set_stamps", "vx_attention_masked_f16", "vx_roll_f16", "vx_pad_f16",
+    "vx_attention_f16", "vx_attention_set_fast_limit", "vx_attention_set_waves", "vx_attention_set_stamps", "vx_attention_masked_f16", "vx_roll_f16", "vx_pad_f16",
     "vx_layernorm_f32_f16", "vx_preprocess_patches", "vx_preprocess_f32", "vx_write_cls_rows", "vx_bilinear_ac_f16",
     "vx_head_out_f32", "vx_minmax_normalize", "vx_f32_to_u8",
     "vx_dconv3x3_f16", "vx_dconv_bilinear_supported", "vx_dconv_prepare", "vx_dconv_x_residual_supported", "vx_dconv_set_block_cap", "vx_dconv_set_resident_mode", "vx_tv_preprocess", "vx_dwconv3x3_f16", "vx_layernorm_f16", "vx_window_attention_f16", "vx_window_attention_bias_bytes", "vx_window_attention_pack_bias",
@@ -357,6 +357,7 @@ def init() -> ctypes.CDLL:
     lib.vx_conv3x3_f16.argtypes = [POINTER(GemmArgs), c_void_p]
     lib.vx_attention_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     lib.vx_attention_set_fast_limit.argtypes = [c_float]
+    lib.vx_attention_set_waves.argtypes = [c_int]
     lib.vx_attention_set_stamps.argtypes = [c_void_p]
     lib.vx_headconv_frag_bytes.restype = c_size_t
     lib.vx_headconv_set_stamps.argtypes = [c_void_p]
@@ -437,6 +438,7 @@ def init() -> ctypes.CDLL:
     for name in KERNEL_SYMBOLS[1:]:
         getattr(lib, name).restype = c_int
     lib.vx_attention_set_fast_limit.restype = None
+    lib.vx_attention_set_waves.restype = None
     lib.vx_dconv_set_resident_mode.restype = None
     lib.vx_dino_block_supported.argtypes = [c_int, c_int, c_int]
     lib.vx_dino_block_mlp_bytes.argtypes = []

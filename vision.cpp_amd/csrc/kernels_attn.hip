@@ -317,16 +317,25 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VISP_AT
 static float g_fast_limit = FAST_LIMIT_DEFAULT;
 extern "C" void vx_attention_set_fast_limit(float limit) { g_fast_limit = limit < 0.0f ? FAST_LIMIT_DEFAULT : limit; }
 
+// test hook: 4 or 8 forces the block shape (both kernels at every T), anything else restores the default rule
+static int g_attn_waves = 0;
+extern "C" void vx_attention_set_waves(int waves) { g_attn_waves = waves == 4 || waves == 8 ? waves : 0; }
+
 // diagnostics: u64 [blocks][waves][4] = {wait, softmax, pv, lifetime} cycles of the next launches; NULL = the product kernel
 static void* g_attn_stamps = nullptr;
 extern "C" void vx_attention_set_stamps(void* stamps) { g_attn_stamps = stamps; }
 
 extern "C" int vx_attention_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int T, void* stream) {
     VX_REQUIRE(B > 0 && H > 0 && T > 0, "vx_attention_f16: empty problem");
+    VX_REQUIRE(q && k && v && out, "vx_attention_f16: null operand");
+    // a head's K / V go through a buffer descriptor whose size and per-lane byte offsets are 32-bit ints
+    VX_REQUIRE((long)T * (HD * 2) < (1L << 31), "vx_attention_f16: T = %d: a head of %ld bytes does not fit the buffer descriptor", T, (long)T * (HD * 2));
     static const int nw_env = getenv("VISP_ATTN_WAVES") ? atoi(getenv("VISP_ATTN_WAVES")) : 0;
-    const int nw = nw_env == 4 || nw_env == 8 ? nw_env : (T > 512 ? 8 : 4); // short sequences: smaller blocks fill the chip better
+    const int nw = g_attn_waves ? g_attn_waves : nw_env == 4 || nw_env == 8 ? nw_env : (T > 512 ? 8 : 4); // short sequences: smaller blocks fill the chip better
     const int qpb = Q_PER_WAVE * nw;
-    dim3 grid(((T + qpb - 1) / qpb) * B * H);
+    const long n_blocks = (long)((T + qpb - 1) / qpb) * B * H;
+    VX_REQUIRE(n_blocks < (1L << 31), "vx_attention_f16: too many blocks (%ld)", n_blocks);
+    dim3 grid((unsigned)n_blocks);
     if (g_attn_stamps)
         hipLaunchKernelGGL((nw == 8 ? attention_kernel<8, true> : attention_kernel<4, true>), grid, dim3(64 * nw), 0, as_stream(stream), reinterpret_cast<const f16*>(q),
                            reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v), reinterpret_cast<f16*>(out), H, T, g_fast_limit,
