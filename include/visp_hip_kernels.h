@@ -206,7 +206,9 @@ VX_API void vx_dconv_set_resident_mode(int mode);
  *   out = P( conv2( relu( conv1( relu(x) ) + b1 ) ) + b2 + x [+ res2] ),  P = identity or the 1x1 projection wp (+ bp)
  * x, res2, out: f16 NHWC [B, H, W, 64]; biases f32 [64] or NULL. w1, w2: f16 [9 taps][64 n][64 c], wp: f16 [64 n][64 c], every (tap, n) row of
  * 128 bytes with its eight 16-byte groups stored at position g ^ ((n >> 1) & 7) (the linear LDS image of a tap's slab).
- * The intermediate map stays in LDS. H, W <= 96 (vx_rcu_supported); larger maps are the LDS-ring conv's. */
+ * The intermediate map stays in LDS. Supported (vx_rcu_supported): H, W in 1..96 whose tile (chosen from H and W) has an input region of at
+ * most 512 pixels and fits 160 KB of LDS -- 148 of the 9216 extents are refused for that, most of them narrow and tall (29 x 11, 29 x 21,
+ * 57 x 21, 96 x 2 as H x W). Everything else, larger maps included, is the LDS-ring conv's. */
 typedef struct {
     const void* x; const void* w1; const float* b1; const void* w2; const float* b2;
     const void* res2; const void* wp; const float* bp;
@@ -401,6 +403,10 @@ VX_API int vx_head_out_f32(const void* x, const float* w, float bias, float max_
  * is held in registers: `wfrag` = vx_headconv_pack (host code) of the GEMM-family rows [32][Kp], k = (ky, kx, c); vx_headconv_frag_bytes()
  * bytes. Supported: cin = cout = 32 and a resize whose 18 x 34 halo fits a 12 x 21 source patch (scale up to about 0.58). */
 VX_API size_t vx_headconv_frag_bytes(void);
+/* test hook (process-global, host side only; the device code is the product's): the 32-channel launcher starts at most n persistent blocks
+ * (n a multiple of 8: one block per XCD at least), so that a small problem walks several tiles per block; n <= 0 restores the default of
+ * two blocks per CU. Returns 0 for any other n. */
+VX_API int vx_headconv_set_block_cap(int n);
 VX_API int vx_headconv_pack(const void* w_rows, int Kp, void* out_frag);
 VX_API int vx_headconv_supported(int cin, int cout, int H, int W, int hs, int ws);
 /* diagnostics (tools/headconv_stamps.py): u64 [blocks][4][8] per-phase cycles of the next launches; NULL = off */

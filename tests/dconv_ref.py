@@ -56,6 +56,33 @@ def round16(x):
     return np.maximum(U16 * np.abs(x), TINY16)
 
 
+def accumulation_term(K: int, mag):
+    """an f32 sum of K exact f16 x f16 products in any order, plus the 8 spare units (bias, ...): on the sum of magnitudes `mag`"""
+    return (K + 8) * U32 * mag
+
+
+def bilinear_term(big, n_src: int, value_roundings: int = BIL_ROUNDINGS - 2):
+    """the interpolated input value's error: `value_roundings` f16 roundings of magnitudes <= big (4 with two fused lerp2 in a row), 2 units
+    for the two weights rounded to f16, the f32 coordinate"""
+    return ((value_roundings + 2) * U16 + 12 * U32 * n_src) * big + value_roundings * TINY16
+
+
+def head_epilogue(z, e, mag, K, hw, hb, hs, exact_clip=False):
+    """HEAD: hs * relu(sum_n relu(z)[n] hw[n] + hb) from conv sums z with input-error term e and magnitudes mag -> (want, allowance).
+    exact_clip: a ReLU whose argument is below zero by more than its own error bound gives exactly 0 on the device too -- such a channel
+    carries no error into the dot product, and such an output has allowance 0 (with it off, ReLU only has Lipschitz constant 1)."""
+    t = np.maximum(z, 0.0)
+    ez = e + accumulation_term(K, mag)
+    if exact_clip:
+        ez = np.where(z + ez < 0, 0.0, ez)
+    dot = t @ hw + hb
+    err = ez @ np.abs(hw) + (32 + 8) * U32 * (np.abs(t) @ np.abs(hw) + abs(hb))
+    allow = err * abs(hs) + U32 * np.abs(dot * hs)
+    if exact_clip:
+        allow = np.where(dot + err < 0, 0.0, allow)
+    return np.maximum(dot, 0.0) * hs, allow
+
+
 def pack_w(w: np.ndarray, cin_pad: int | None = None, cout_pad: int | None = None) -> np.ndarray:
     """[cout, cin, 3, 3] -> the flat f16 weight buffer of the header (zero padded to cin_pad / cout_pad, multiples of 32)"""
     co, ci = w.shape[:2]
@@ -127,7 +154,7 @@ def input_map(args):
         a, b, c, d = src[:, y0][:, :, x0], src[:, y0][:, :, x1], src[:, y1][:, :, x0], src[:, y1][:, :, x1]
         xin = (a * (1 - fx) + b * fx) * (1 - fy) + (c * (1 - fx) + d * fx) * fy
         big = np.maximum(np.maximum(np.abs(a), np.abs(b)), np.maximum(np.abs(c), np.abs(d)))
-        dx = (BIL_ROUNDINGS * U16 + 12 * U32 * max(hs, ws)) * big + 4 * TINY16
+        dx = bilinear_term(big, max(hs, ws))
     else:
         up = 1 if _get(args, "up2") else 0
         xin = src[:, np.arange(H) >> up][:, :, np.arange(W) >> up]
@@ -177,19 +204,17 @@ def evaluate(args):
 
     if epi == DC_RGB_F32:
         idx = p[..., None] * 3 + np.arange(3)
-        want[idx], allow[idx], written[idx] = z[..., :3], (e + (K + 8) * U32 * mag)[..., :3], True
+        want[idx], allow[idx], written[idx] = z[..., :3], (e + accumulation_term(K, mag))[..., :3], True
     elif epi == DC_HEAD_F32:
         hw = np.asarray(args["head_w"], np.float64)
         hb, hs = float(_get(args, "head_bias", 0.0)), float(_get(args, "head_scale", 0.0))
-        t = np.maximum(z, 0.0)
-        dot = t @ hw + hb
-        err = (e + (K + 8) * U32 * mag) @ np.abs(hw) + (32 + 8) * U32 * (np.abs(t) @ np.abs(hw) + abs(hb))
-        want[p], allow[p], written[p] = np.maximum(dot, 0.0) * hs, err * abs(hs) + U32 * np.abs(dot * hs), True
+        want[p], allow[p] = head_epilogue(z, e, mag, K, hw, hb, hs)
+        written[p] = True
     else:
         assert epi == DC_F16
         s1, s2 = float(_get(args, "s1", 1.0)), float(_get(args, "s2", 1.0))
         v = activation(z, _get(args, "act"))
-        e = e + (K + 8) * U32 * mag
+        e = e + accumulation_term(K, mag)
         if _get(args, "x_residual"):
             assert cout == 64 and args.get("res1") is None
             x64 = input_map(dict(args, a_relu=0))[0][..., :64]  # the header's x, not relu(x)

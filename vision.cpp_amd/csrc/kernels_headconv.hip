@@ -17,8 +17,9 @@
 //     exactly the LDS port's rate;
 //   * with pixels in the lanes, conv3's reduction over channels is 16 in-lane FMAs and one v_permlane32_swap; a lane then owns one
 //     output pixel and the 32 lanes of a row store 128 contiguous bytes.
-// The interpolation is the arithmetic of kernels_dconv.hip's resizing loader and of vx_bilinear_ac_f16: src = i / sf with
-// sf = (out - 1) / (in - 1), weights rounded to f16, v + f (w - v) evaluated as f w + (v - f v) on packed halves, x then y.
+// The interpolation is the arithmetic of kernels_dconv.hip's resizing loader: src = i / sf with sf = (out - 1) / (in - 1), weights
+// rounded to f16, v + f (w - v) evaluated as f w + (v - f v) on packed halves, x then y. vx_bilinear_ac_f16 (the unfused resize)
+// shares the coordinates only: it blends in f32, with four f32 weights, and rounds to f16 once.
 #include <algorithm>
 
 #include "vx_common.h"
@@ -590,6 +591,17 @@ extern "C" int vx_headconv_wide_bil_f16(const void* x, int cin, const void* wfra
 static void* g_headconv_stamps = nullptr;
 extern "C" void vx_headconv_set_stamps(void* stamps) { g_headconv_stamps = stamps; }
 
+// test hook (host side only): > 0 is the most blocks the 32-channel launcher starts, so that a small problem walks several tiles per block
+static int g_headconv_block_cap = 0;
+extern "C" int vx_headconv_set_block_cap(int n) {
+    if (n > 0 && n % 8 != 0) {
+        vx_set_error("vx_headconv_set_block_cap: %d is not a multiple of 8 (one block per XCD at least)", n);
+        return 0;
+    }
+    g_headconv_block_cap = n > 0 ? n : 0;
+    return 1;
+}
+
 extern "C" int vx_headconv_bil_f16(const void* x, const void* wfrag, const float* bias, const float* w3, float b3, float scale, float* out, int B, int H, int W,
                                    int hs, int ws, void* stream) {
     VX_REQUIRE(x && wfrag && bias && w3 && out && B > 0, "vx_headconv_bil_f16: null operand");
@@ -605,7 +617,8 @@ extern "C" int vx_headconv_bil_f16(const void* x, const void* wfrag, const float
         return n;
     }();
     static const int bpc = getenv("VISP_HEADCONV_BPC") ? atoi(getenv("VISP_HEADCONV_BPC")) : 2; // experiments
-    const int blocks = (int)std::min<long>(n_tiles, (long)std::max(1, bpc) * n_cu); // two persistent blocks per CU
+    const long most = g_headconv_block_cap > 0 ? g_headconv_block_cap : (long)std::max(1, bpc) * n_cu; // two persistent blocks per CU
+    const int blocks = (int)std::min<long>(n_tiles, most);
     hipLaunchKernelGGL(headconv_kernel, dim3(blocks), dim3(256), SMEM_BYTES, as_stream(stream), reinterpret_cast<const f16*>(x), reinterpret_cast<const f16*>(wfrag), bias,
                        w3, b3, scale, out, B, H, W, hs, ws, tiles_x, tiles_y, static_cast<unsigned long long*>(g_headconv_stamps));
     VX_LAUNCH_CHECK();

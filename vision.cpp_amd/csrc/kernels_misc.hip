@@ -284,7 +284,10 @@ int vx_write_cls_rows(float* x, const float* cls, const float* pos, int B, int T
 }
 
 int vx_bilinear_ac_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream) {
+    VX_REQUIRE(x && y, "vx_bilinear_ac_f16: null operand");
+    VX_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0, "vx_bilinear_ac_f16: empty extent");
     VX_REQUIRE(C % 8 == 0, "vx_bilinear_ac_f16: C=%d must be a multiple of 8", C);
+    VX_REQUIRE(OH <= 65535 && B <= 65535, "vx_bilinear_ac_f16: %d rows x %d images do not fit the grid (65535 each)", OH, B);
     float sfy = (OH > 1 && H > 1) ? (float)(OH - 1) / (float)(H - 1) : (float)OH / (float)H;
     float sfx = (OW > 1 && W > 1) ? (float)(OW - 1) / (float)(W - 1) : (float)OW / (float)W;
     VX_REQUIRE((long)H * W * C < 0x7fffffffL, "vx_bilinear_ac_f16: image too large for 32-bit offsets");

@@ -290,7 +290,9 @@ extern "C" int vx_rcu_supported(int H, int W) {
 
 extern "C" int vx_rcu_fused_f16(const vx_rcu_args* args, void* stream) {
     const vx_rcu_args& a = *args;
-    VX_REQUIRE(a.B > 0 && vx_rcu_supported(a.H, a.W), "vx_rcu_fused_f16: map %d x %d is not built (1..96 per side)", a.W, a.H);
+    VX_REQUIRE(a.B > 0, "vx_rcu_fused_f16: empty batch");
+    VX_REQUIRE(vx_rcu_supported(a.H, a.W),
+               "vx_rcu_fused_f16: map %d x %d is not built (1..96 per side, and a tile whose three regions hold at most 512 pixels and fit 160 KB of LDS)", a.W, a.H);
     VX_REQUIRE(a.x && a.w1 && a.w2 && a.out, "vx_rcu_fused_f16: missing operands");
     const rcu_geom g = rcu_geometry(a.H, a.W);
     const long blocks = (long)a.B * g.ncx * g.ncy;
