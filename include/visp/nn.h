@@ -48,6 +48,17 @@ inline tensor patch_embed(model_ref m, tensor x, int patch_size) {
     return out;
 }
 
+// deformable convolution (nn.cpp:131-148): weight [Cin, k, k, Cout], offset [2 k k, OW, OH, N] (dy, dx per tap), mask [k k, OW, OH, N] or null; stride 1
+inline tensor conv_2d_deform(model_ref m, tensor x, tensor weight, tensor offset, tensor mask, int stride, int pad) {
+    return mask ? detail::op(m, VISP_OP_CONV_2D_DEFORM, {x, weight, offset, mask}, {stride, pad}) : detail::op(m, VISP_OP_CONV_2D_DEFORM, {x, weight, offset}, {stride, pad});
+}
+// x * weight + bias per channel: the form a batch norm has once model conversion folded its statistics (nn.cpp:150-164)
+inline tensor batch_norm_2d(model_ref m, tensor x) {
+    if (m.find("running_mean") || m.find("running_var")) throw exception("Batch norm was not fused");
+    x = detail::op(m, VISP_OP_MUL, {x, m.weights("weight")});
+    return named(m, detail::op(m, VISP_OP_ADD, {x, m.weights("bias")}));
+}
+
 // element-wise and shape ops
 inline tensor add(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_ADD, {a, b}); }
 inline tensor mul(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_MUL, {a, b}); }
@@ -55,6 +66,9 @@ inline tensor gelu(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_
 inline tensor relu(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_RELU, {x}); }
 inline tensor scale(model_ref const& m, tensor x, float s) { return detail::op(m, VISP_OP_SCALE, {x}, {}, {s}); }
 inline tensor leaky_relu(model_ref const& m, tensor x, float negative_slope) { return detail::op(m, VISP_OP_LEAKY_RELU, {x}, {}, {negative_slope}); }
+inline tensor sigmoid(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SIGMOID, {x}); }
+// [C, W, H, N] -> [C, 1, 1, N] (mean_2d, birefnet.cpp:93-100; not ggml_mean, which reduces ne[0])
+inline tensor mean_2d(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_MEAN_2D, {x}); }
 inline tensor cont(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_CONT, {x}); }
 inline tensor reshape_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2, int64_t n3) { return detail::op(m, VISP_OP_RESHAPE, {x}, {n0, n1, n2, n3}); }
 inline tensor reshape_3d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2) { return reshape_4d(m, x, n0, n1, n2, 1); }
@@ -118,6 +132,8 @@ inline tensor ggml_relu(model_ref const& m, tensor x) { return relu(m, x); }
 inline tensor ggml_relu_inplace(model_ref const& m, tensor x) { return relu(m, x); }
 inline tensor ggml_scale(model_ref const& m, tensor x, float s) { return scale(m, x, s); }
 inline tensor ggml_scale_inplace(model_ref const& m, tensor x, float s) { return scale(m, x, s); }
+inline tensor ggml_sigmoid(model_ref const& m, tensor x) { return sigmoid(m, x); }
+inline tensor ggml_sigmoid_inplace(model_ref const& m, tensor x) { return sigmoid(m, x); }
 inline tensor ggml_leaky_relu(model_ref const& m, tensor x, float negative_slope, bool /*inplace*/) { return leaky_relu(m, x, negative_slope); }
 inline tensor ggml_cont(model_ref const& m, tensor x) { return cont(m, x); }
 inline tensor ggml_reshape_3d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2) { return reshape_3d(m, x, n0, n1, n2); }

@@ -344,7 +344,18 @@ enum visp_graph_op {
     /* src q, k, v [head_dim, heads, T, B], mask [T_k, T_q, Hm, Bm] f16 / f32, constant or activation; f0 scale. Hm is 1 or heads, Bm divides B (batch b
      * reads mask b % Bm). softmax(scale q k^T + mask) v as the 3-source op. head_dim 32 and 64, T_q == T_k. head_dim 32 exists through THIS op only:
      * VISP_OP_ATTENTION keeps its head_dim-64 kernel and its refusal of everything else.                         nn.cpp:210-244, swin.cpp:69-97 */
-    VISP_OP_ATTENTION_MASKED = 27
+    VISP_OP_ATTENTION_MASKED = 27,
+    /* the nodes of a BiRefNet decoder block (birefnet.cpp:79-145) */
+    /* src x [Cin, W, H, N] f16, w [Cin, kw, kh, Cout] (a constant, stored as conv_2d stores it), offset [2 kh kw, OW, OH, N], (mask [kh kw, OW, OH, N]); i0 stride,
+     * i1 pad. Offset channel 2t is dy, 2t + 1 is dx of tap t = ky kw + kx. A sample at (py, px) counts only inside (-1, H) x (-1, W), corners outside the map are
+     * zero: the convention of the oracle's vo_deform_conv2d_nhwc, pinned on grid_sample and NOT on torchvision (the parity caveat of
+     * tests/test_oracle_birefnet.py:1-10 carries over). Built for stride 1, kw == kh <= 7, Cin % 16 == 0, Cout % 8 == 0 and <= 256; anything else is refused
+     * when the node is made. With the default fused models the group conv_2d(offset, x), scale(sigmoid(conv_2d(modulator, x)), s), conv_2d_deform [, mul(c),
+     * add(c), relu] is two launches (kernels_deform.hip).                                                                  nn.cpp:131-148, birefnet.cpp:83-92 */
+    VISP_OP_CONV_2D_DEFORM = 28,
+    VISP_OP_SIGMOID = 29,          /* element-wise on f16 activations; folded on the host on constants                     ggml_sigmoid, birefnet.cpp:86 */
+    VISP_OP_MEAN_2D = 30           /* x [C, W, H, N] -> [C, 1, 1, N]: f32 sums in a fixed order, no atomics (the same bits every launch). NOT ggml_mean, which
+                                      reduces ne[0] -- here the channel                                                    mean_2d, birefnet.cpp:93-100 */
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

@@ -283,6 +283,21 @@ VX_API int vx_bf_resize_f16(const void* src, int lds, void* dst, int ldd, int B,
 /* sampling half of deformable_conv_2d (birefnet.cpp:83-92 = torchvision deform_conv2d, stride 1, pad k/2): x f16 [B,h,w,C]; offmod
  * [B*h*w, ldom] = per pixel 2 k^2 offsets (dy, dx per tap) then k^2 modulator logits; cols [B*h*w, k*k*C] = 2 sigmoid(mod) * sample */
 VX_API int vx_bf_deform_cols_f16(const void* x, const void* offmod, int ldom, void* cols, int B, int h, int w, int C, int k, void* stream);
+/* ---- deformable convolution as one implicit GEMM whose A loader samples (kernels_deform.hip; nn.cpp:131-148, stride 1) ----
+ * x f16 [B,H,W,Cin], Cin % 16 == 0; w f16 [Cout pad 32][k*k*Cin] (row n = the kernel of output n, taps (ky, kx) then channels; pad rows
+ * zero); Cout % 8 == 0, <= 256; k 1..7. Output extent OH = H + 2 pad - k + 1 (OW alike). offset f16 [B*OH*OW][ld_offset]: element 2t = dy,
+ * 2t+1 = dx of tap t = ky*k + kx. mask f16 [B*OH*OW][ld_mask], element t: mask_mode 0 none, 1 the factor as it is, 2 a logit (factor =
+ * mask_scale * sigmoid(logit)). A sample at (py, px) counts only inside (-1, H) x (-1, W); corners outside the map are zero. out f16
+ * [B*OH*OW][ldo] = relu?(scale[n] * conv + bias[n]) (scale, bias f32 [Cout], NULL = none). */
+typedef struct {
+    const void* x; int B, H, W, Cin;
+    const void* w; int Cout, k, pad;
+    const void* offset; int ld_offset;
+    const void* mask; int ld_mask; int mask_mode; float mask_scale;
+    const float* scale; const float* bias; int relu;
+    void* out; int ldo;
+} vx_deform_conv_args;
+VX_API int vx_deform_conv_f16(const vx_deform_conv_args* args, void* stream);
 /* per-image pixel mean [B, n, C] (row stride ld) -> [B, C]; broadcast of [B, C] rows to every pixel of a slice; y *= sigmoid(a); final mask */
 VX_API int vx_bf_mean_f16(const void* x, int ld, void* y, float* acc_scratch /*f32 [B*C]*/, int B, int64_t n, int C, void* stream);
 VX_API int vx_bf_broadcast_f16(const void* g, int ldg, void* dst, int ldd, int B, int64_t n, int C, void* stream);
@@ -441,6 +456,11 @@ VX_API int vx_pad_f16(const void* src, void* dst, const int64_t src_ne[4], const
 VX_API int vx_binary_rows(int op, const void* a, int a_f32, const void* b, int b_f32, int64_t b_period, void* y, int y_f32, int64_t n, void* stream);
 /* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s, 3 leaky ReLU x > 0 ? x : s x (ggml_leaky_relu, any slope); f16, 16-byte aligned */
 VX_API int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, void* stream);
+/* ggml_sigmoid: y f16 = 1 / (1 + exp(-x)); x f16, or f32 (x_f32: the map of a 1x1 convolution to one channel); 16-byte aligned */
+VX_API int vx_sigmoid_f16(const void* x, int x_f32, void* y, int64_t n, void* stream);
+/* mean_2d (birefnet.cpp:93-100) on an NHWC map: x f16 [B, n pixels, C] -> y f16 [B, C]. f32 sums in a fixed order (four pixel slices of four chains
+ * each, combined pairwise), no atomics: the same bits on every launch (kernels_birefnet.hip:137-142) */
+VX_API int vx_mean_2d_f16(const void* x, void* y, int B, int64_t n, int C, void* stream);
 /* y = x, f32 -> f16 (round to nearest even) or f16 -> f32 */
 VX_API int vx_convert(const void* x, int x_f32, void* y, int y_f32, int64_t n, void* stream);
 /* ggml_interpolate(NEAREST) of an NHWC f16 map (ml.cpp:782-788; esrgan.cpp:15) */

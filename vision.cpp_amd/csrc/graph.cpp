@@ -19,7 +19,7 @@ namespace {
 const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_norm", "gelu", "relu", "scale", "add", "mul", "conv_2d",
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
-                                         "cast", "attention_masked"};
+                                         "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -195,6 +195,9 @@ void fold_constant(graph& g, graph_node& n) {
                 std::copy(src(0).values() + row * C, src(0).values() + (row + 1) * C, out + i * C);
             }
         } break;
+        case gop_sigmoid:
+            for (int64_t i = 0; i < total; ++i) out[i] = (float)(1.0 / (1.0 + std::exp(-(double)src(0).values()[i])));
+            break;
         case gop_cast:
             for (int64_t i = 0; i < total; ++i) out[i] = n.dtype == gdt_f16 ? f16_to_f32(f32_to_f16(src(0).values()[i])) : src(0).values()[i];
             break;
@@ -204,7 +207,7 @@ void fold_constant(graph& g, graph_node& n) {
 
 bool foldable(int32_t op) {
     return op == gop_reshape || op == gop_cont || op == gop_scale || op == gop_add || op == gop_mul || op == gop_slice || op == gop_repeat ||
-           op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast;
+           op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid;
 }
 
 void check_tensor(graph const& g, int t, const char* what) {
@@ -578,12 +581,47 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             n.ne[2] = q.ne[3];
             n.ne[3] = 1;
         } break;
+        case gop_sigmoid:
+            need_src(1, 1);
+            same_shape();
+            break;
+        case gop_mean_2d:
+            need_src(1, 1);
+            n.ne[0] = S(0).ne[0]; n.ne[1] = 1; n.ne[2] = 1; n.ne[3] = S(0).ne[3];
+            break;
+        case gop_conv_2d_deform: {
+            need_src(3, 4);
+            graph_node const &x = S(0), &w = S(1), &off = S(2);
+            const int64_t stride = n.ip[0] > 0 ? n.ip[0] : 1, pad = n.ip[1];
+            n.ip[0] = stride;
+            if (!w.constant) throw except("conv_2d_deform: the kernel must be a model weight");
+            if (stride != 1) throw except("conv_2d_deform: stride %lld is not built (stride 1 is)", (long long)stride);
+            if (w.ne[1] != w.ne[2]) throw except("conv_2d_deform: kernel %lldx%lld; square kernels only", (long long)w.ne[1], (long long)w.ne[2]);
+            if (w.ne[1] > 7 || pad < 0) throw except("conv_2d_deform: kernel %lld, pad %lld (kernels up to 7x7, pad >= 0)", (long long)w.ne[1], (long long)pad);
+            if (w.ne[0] != x.ne[0]) throw except("conv_2d_deform: kernel %s (ne = [Cin, kw, kh, Cout]) does not match input %s (CWHN)", shape_str(w.ne).c_str(), shape_str(x.ne).c_str());
+            if (x.ne[0] % 16) throw except("conv_2d_deform: Cin = %lld must be a multiple of 16", (long long)x.ne[0]);
+            if (w.ne[3] > 256) throw except("conv_2d_deform: Cout = %lld; one block computes every output channel of its pixels, at most 256", (long long)w.ne[3]);
+            if (w.ne[3] % 8) throw except("conv_2d_deform: Cout = %lld must be a multiple of 8", (long long)w.ne[3]);
+            const int64_t taps = w.ne[1] * w.ne[2];
+            n.ne[0] = w.ne[3];
+            n.ne[1] = x.ne[1] + 2 * pad - w.ne[1] + 1;
+            n.ne[2] = x.ne[2] + 2 * pad - w.ne[2] + 1;
+            n.ne[3] = x.ne[3];
+            if (n.ne[1] <= 0 || n.ne[2] <= 0) throw except("conv_2d_deform: the kernel does not fit the input");
+            auto matches = [&](graph_node const& t, int64_t ch) { return t.ne[0] == ch && t.ne[1] == n.ne[1] && t.ne[2] == n.ne[2] && t.ne[3] == n.ne[3] && t.dtype != gdt_i32; };
+            if (!matches(off, 2 * taps))
+                throw except("conv_2d_deform: offset %s does not match a %lldx%lld kernel on a %lldx%lld output ([2 kh kw, OW, OH, N] = [%lld, %lld, %lld, %lld])", shape_str(off.ne).c_str(),
+                             (long long)w.ne[1], (long long)w.ne[2], (long long)n.ne[1], (long long)n.ne[2], (long long)(2 * taps), (long long)n.ne[1], (long long)n.ne[2], (long long)n.ne[3]);
+            if (n_src == 4 && !matches(S(3), taps))
+                throw except("conv_2d_deform: mask %s does not match a %lldx%lld kernel on a %lldx%lld output ([kh kw, OW, OH, N] = [%lld, %lld, %lld, %lld])", shape_str(S(3).ne).c_str(),
+                             (long long)w.ne[1], (long long)w.ne[2], (long long)n.ne[1], (long long)n.ne[2], (long long)taps, (long long)n.ne[1], (long long)n.ne[2], (long long)n.ne[3]);
+        } break;
         default: throw except("graph_add: op %d", op);
     }
     // f32 tensors exist as inputs only; an f32 operand anywhere else would need kernels this executor does not have
     if (op != gop_patch_embed && op != gop_image_u8_to_f32 && op != gop_image_normalize)
         for (int i = 0; i < n_src; ++i) {
-            const bool head_tail = (op == gop_relu || op == gop_scale) && S(i).op != gop_input;
+            const bool head_tail = (op == gop_relu || op == gop_scale || op == gop_sigmoid) && S(i).op != gop_input; // (sigmoid: f32 in, f16 out)
             // (a 3x3 conv on the f32 image of <= 16 channels: the first conv of an image-to-image network, esrgan.cpp:58)
             const bool image_conv = op == gop_conv_2d && i == 0 && S(0).op == gop_input && S(0).ne[0] <= 16 && S(1).ne[1] == 3 && S(1).ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1;
             const bool f32_mask = op == gop_attention_masked && i == 3; // the masked attention reads an f32 mask in place

@@ -59,6 +59,10 @@ enum graph_op : int32_t {
     gop_get_rows,         // table [C, rows], idx i32 constant -> f32 [C, idx.ne0, idx.ne1, idx.ne2]; constants only (folded)   swin.cpp:75
     gop_cast,             // x; i0 = type (0 f32, 1 f16): a view on activations of that type, a rounding on constants           swin.cpp:78
     gop_attention_masked, // q, k, v [hd, heads, T, B], mask [T_k, T_q, Hm, Bm]; f0 = scale; hd 32 / 64 -> [hd * heads, T, B]   nn.cpp:210-244 with a mask
+    // the nodes of a BiRefNet decoder block (birefnet.cpp:79-145)
+    gop_conv_2d_deform,   // x CWHN, w [Cin, k, k, Cout], offset [2 k k, OW, OH, N], (mask [k k, OW, OH, N]); i0 = stride (1), i1 = pad   nn.cpp:131-148
+    gop_sigmoid,          // ggml_sigmoid                              birefnet.cpp:86
+    gop_mean_2d,          // x [C, W, H, N] -> [C, 1, 1, N]: the pixel mean, f32 sums in a fixed order   birefnet.cpp:93-100
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -113,6 +117,9 @@ enum pack_role : int {
     role_rcu = 7,            // residual-unit kernel operand [taps][64][64], swizzled
     role_dconv_ex = 8,       // LDS-ring conv slabs with repeated input columns / padded outputs
     role_bias_padded = 9,    // f32 bias zero-padded to a kernel's channel count
+    role_deform = 10,        // deformable conv operand: f16 rows [Cout pad 32][taps * Cin]
+    role_deform_offsets = 11,// offset | modulator kernels of a deformable conv as one GEMM operand (keyed on the offset kernel)
+    role_deform_offsets_bias = 12, // ... and their biases, f32 [N pad]
     role_bias_base = 16,     // 16..24: bias_of_role(r), the f32 bias [N pad] that goes with the operand of role r (0..8)
     role_block_mlp = 40,     // block kernel: out-proj | fc1 | fc2 fragments, LayerScale folded (keyed on the out-proj weight)
     role_block_qkv = 41,     // block kernel: q | k | v fragments

@@ -183,6 +183,48 @@ __global__ __launch_bounds__(256) void image_planes_kernel(const float* __restri
     }
 }
 
+// ggml_sigmoid on f16: 8 elements per thread-iteration, a scalar tail
+__global__ __launch_bounds__(256) void sigmoid_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n) {
+    const long n8 = n >> 3;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        f16x8 v = *reinterpret_cast<const f16x8*>(x + i * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (f16)(1.0f / (1.0f + __expf(-(float)v[j])));
+        *reinterpret_cast<f16x8*>(y + i * 8) = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+        const long i = (n8 << 3) + threadIdx.x;
+        y[i] = (f16)(1.0f / (1.0f + __expf(-(float)x[i])));
+    }
+}
+// ... of the f32 map a 1x1 convolution to one channel leaves (the modulator of a 1x1 deformable conv)
+__global__ __launch_bounds__(256) void sigmoid_f32_kernel(const float* __restrict__ x, f16* __restrict__ y, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = (f16)(1.0f / (1.0f + __expf(-x[i])));
+}
+
+// mean_2d: x [B, n, C] -> y [B, C]. The arithmetic of bf_mean_partial_kernel (kernels_birefnet.hip): one block per (image, 64-channel group), four
+// pixel slices of 64 channels, each adding its pixels p = slice, slice + 4, ... on four chains in a FIXED order; no atomics, so the bits do not
+// depend on the launch. The block divides and rounds itself: one launch, no f32 scratch.
+__global__ __launch_bounds__(256) void mean_2d_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n, int C) {
+    __shared__ float part[4][64];
+    const int b = blockIdx.y, c = blockIdx.x * 64 + (threadIdx.x & 63), slice = threadIdx.x >> 6;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    if (c < C) {
+        const f16* xb = x + (long)b * n * C + c;
+        long p = slice;
+        for (; p + 12 < n; p += 16) {
+            s0 += (float)xb[p * C];
+            s1 += (float)xb[(p + 4) * C];
+            s2 += (float)xb[(p + 8) * C];
+            s3 += (float)xb[(p + 12) * C];
+        }
+        for (; p < n; p += 4) s0 += (float)xb[p * C];
+    }
+    part[slice][threadIdx.x & 63] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (slice == 0 && c < C) y[(long)b * C + c] = (f16)(((part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x])) / (float)n);
+}
+
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void convert_kernel(const TS* __restrict__ x, TD* __restrict__ y, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = (TD)(float)x[i];
@@ -348,6 +390,22 @@ extern "C" int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, 
         case 3: hipLaunchKernelGGL(unary_kernel<3>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
         default: VX_REQUIRE(false, "vx_unary_f16: op %d (0 gelu, 1 relu, 2 scale, 3 leaky relu)", op);
     }
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_sigmoid_f16(const void* x, int x_f32, void* y, int64_t n, void* stream) {
+    VX_REQUIRE(x && y && n > 0, "vx_sigmoid_f16: bad operands");
+    VX_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "vx_sigmoid_f16: operands must be 16-byte aligned");
+    if (x_f32) hipLaunchKernelGGL(sigmoid_f32_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const float*)x, (f16*)y, (long)n);
+    else hipLaunchKernelGGL(sigmoid_kernel, dim3(grid_stride_blocks(n / 8 + 1, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n);
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_mean_2d_f16(const void* x, void* y, int B, int64_t n, int C, void* stream) {
+    VX_REQUIRE(x && y && B > 0 && B <= 65535 && n > 0 && C > 0, "vx_mean_2d_f16: bad operands (B = %d, n = %ld, C = %d)", B, (long)n, C);
+    hipLaunchKernelGGL(mean_2d_kernel, dim3((C + 63) / 64, B), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, C);
     VX_LAUNCH_CHECK();
     return 1;
 }

@@ -533,12 +533,16 @@ void lowering::gemm_like(int t) {
         xbuf = plain_rows(p.k_real, p.K);
         a.ps_s = s; a.ps_Cout = (int)n.ne[0]; a.ps_H = (int)x.ne[2]; a.ps_W = (int)x.ne[1];
     }
-    if (n.ne[0] % 8) throw except("%s %s: %lld output channels; the f16 epilogues store 8 at a time", graph_op_name(n.op), who.c_str(), (long long)n.ne[0]);
+    // a channel count that is no multiple of 8 (the 2 k^2 offsets and k^2 modulator logits of a deformable conv on their own): the f16 epilogues store
+    // 8 at a time, so the product writes rows padded to 8 and one strided copy compacts them
+    const bool ragged = n.ne[0] % 8 != 0;
+    if (ragged && n.op == gop_conv_transpose_2d) throw except("%s %s: %lld output channels; the f16 epilogues store 8 at a time", graph_op_name(n.op), who.c_str(), (long long)n.ne[0]);
     a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.n_valid = n.op == gop_conv_transpose_2d ? p.n_real : (int)n.ne[0];
     a.ldo = n.ne[0];
     if (n.op == gop_conv_transpose_2d) a.epi = VX_EPI_PIXSHUF;
     else {
         if (n.op != gop_linear) e = match_epilogue(t, true, false, true);
+        if (ragged && e.res >= 0) throw except("%s %s: %lld output channels with a residual; rows that are no multiple of 8 channels take no residual epilogue", graph_op_name(n.op), who.c_str(), (long long)n.ne[0]);
         absorb(e, t); // (no way back to another lowering from here)
         a.epi = e.res >= 0 ? VX_EPI_F16_ADD : (e.act == 1 ? VX_EPI_F16_GELU : (e.act == 2 ? VX_EPI_F16_RELU : VX_EPI_F16));
         a.relu = e.res >= 0 && e.act == 2;
@@ -546,7 +550,7 @@ void lowering::gemm_like(int t) {
     // rows of a width that is no multiple of the GEMM's 64-wide k tile, read by one plain product only: written with the padded row
     // stride that reader wants (the pad columns are exact zeros: zero weights, zero bias), no pad_rows copy in between
     size_t out_bytes = n.n_bytes();
-    if (g.fused_models && a.epi == VX_EPI_F16 && n.op != gop_conv_transpose_2d && n.ne[0] % 64 != 0 && !n.is_output && p.N >= round_up((int)n.ne[0], 64) && plain_gemm_reader(t) >= 0) {
+    if (g.fused_models && !ragged && a.epi == VX_EPI_F16 && n.op != gop_conv_transpose_2d && n.ne[0] % 64 != 0 && !n.is_output && p.N >= round_up((int)n.ne[0], 64) && plain_gemm_reader(t) >= 0) {
         const int Kp = round_up((int)n.ne[0], 64);
         row_stride[t] = Kp;
         a.ldo = Kp;
@@ -554,7 +558,10 @@ void lowering::gemm_like(int t) {
         out_bytes = (size_t)(n.n_elements() / n.ne[0]) * Kp * 2;
     }
     n.buffer = new_buffer(out_bytes, n.is_output || n.op == gop_input);
-    const int obuf = n.buffer;
+    const int ld8 = round_up((int)n.ne[0], 8);
+    const int64_t rows = n.n_elements() / n.ne[0];
+    if (ragged) { a.ldo = ld8; a.n_valid = ld8; }
+    const int obuf = ragged ? new_buffer((size_t)rows * ld8 * 2) : n.buffer;
     std::vector<int> reads = {xbuf};
     const residual_ptrs rp = read_residuals(e, reads);
     const bool halo = conv && a.conv_kh == 3 && a.conv_kw == 3 && a.conv_stride == 1 && a.conv_pad == 1 && a.conv_W >= env().halo_min_w;
@@ -572,6 +579,16 @@ void lowering::gemm_like(int t) {
         else VX(vx_gemm_f16(&r, st));
     });
     tag(group_of(who, n, stride).c_str(), 2.0 * a.M * (double)p.n_real * p.k_real, (double)a.M * (p.k_real + n.ne[0]) * 2 + (double)p.N * p.K * 2);
+    if (ragged) {
+        const int dst = n.buffer;
+        auto sp = ptr(obuf), dp = ptr(dst);
+        const int64_t c = n.ne[0];
+        emit("unpad_rows N=" + std::to_string(ld8) + "->" + std::to_string(c) + " <- " + who, {obuf}, {dst}, [=](void* st) {
+            const int64_t ne[4] = {c, rows, 1, 1}, ss[4] = {1, ld8, 0, 0}, ds[4] = {1, c, 0, 0};
+            VX(vx_copy_strided_f16(sp(), dp(), ne, ss, ds, 1.0f, st));
+        });
+        tag("glue", 0, (double)rows * c * 4);
+    }
 }
 
 // 3x3 / stride 1 / pad 1 with Cin % 16 == 0, Cin >= 32 (the kernel's pixel stride; a narrower map goes to the GEMM family's conv) and 32 or 64 output channels: the persistent LDS-ring conv (kernels_dconv.hip), with the
@@ -694,5 +711,165 @@ bool lowering::resize_into_reader(int t) {
     return true;
 }
 
+
+// ---- deformable convolution (nn.cpp:131-148) -----------------------------------------------------------------------------------------------
+
+// deformable_conv_2d + the branch's batch norm and ReLU as the reference writes them (birefnet.cpp:83-92, 110-115): offset and modulator convs over
+// the same x, stride and pad as the deformable conv, each link read by the next one only
+bool lowering::match_deform_group(int t, deform_group& G) const {
+    graph_node const& n = g.nodes[t];
+    if (n.op != gop_conv_2d_deform || n.n_src != 4) return false;
+    const int x = n.src[0];
+    auto conv_on_x = [&](int c) {
+        graph_node const& cn = g.nodes[c];
+        return cn.op == gop_conv_2d && !cn.constant && cn.src[0] == x && cn.ip[0] == 1 && cn.ip[1] == n.ip[1] &&
+               g.nodes[cn.src[1]].ne[1] == g.nodes[n.src[1]].ne[1] && g.nodes[cn.src[1]].ne[2] == g.nodes[n.src[1]].ne[2] && sole_consumer(c) >= 0;
+    };
+    G.off = n.src[2];
+    G.scl = n.src[3];
+    if (!conv_on_x(G.off) || sole_consumer(G.off) != t) return false;
+    if (g.nodes[G.scl].op != gop_scale || g.nodes[G.scl].constant || sole_consumer(G.scl) != t) return false;
+    G.s = g.nodes[G.scl].fp[0];
+    G.sig = g.nodes[G.scl].src[0];
+    if (g.nodes[G.sig].op != gop_sigmoid || g.nodes[G.sig].constant || sole_consumer(G.sig) != G.scl) return false;
+    G.mod = g.nodes[G.sig].src[0];
+    if (!conv_on_x(G.mod) || sole_consumer(G.mod) != G.sig || G.mod == G.off) return false;
+    // [mul(c)] [add(c)] [relu] on per-channel constants behind it
+    auto per_channel = [&](int c, int32_t op, int from) {
+        graph_node const& cn = g.nodes[c];
+        return cn.op == op && cn.src[0] == from && g.nodes[cn.src[1]].constant && g.nodes[cn.src[1]].n_elements() == n.ne[0];
+    };
+    int last = t, c = sole_consumer(t);
+    if (c >= 0 && per_channel(c, gop_mul, last)) { G.mul = c; last = c; c = sole_consumer(c); }
+    if (c >= 0 && per_channel(c, gop_add, last)) { G.add = c; last = c; c = sole_consumer(c); }
+    if (c >= 0 && g.nodes[c].op == gop_relu && g.nodes[c].src[0] == last) G.relu = c;
+    return true;
+}
+// before the node loop: the convs of a group come before their deformable conv in node order and must not be lowered on their own
+void lowering::find_deform_groups() {
+    if (!g.fused_models) return;
+    for (int t = 0; t < (int)g.nodes.size(); ++t) {
+        deform_group G;
+        if (!needed[t] || !match_deform_group(t, G)) continue;
+        deform_groups[t] = G;
+        for (int c : {G.off, G.mod, G.sig, G.scl}) skip[c] = 1;
+    }
+}
+
+static std::string deform_who(graph const& g, graph_node const& n) {
+    graph_node const& w = g.nodes[n.src[1]];
+    return w.op == gop_weight && !w.name.empty() ? w.name : n.name;
+}
+
+// any use of the op: offsets and mask are read where they are, the mask as it is
+void lowering::deform_conv(int t) {
+    if (auto it = deform_groups.find(t); it != deform_groups.end()) return deform_fused(t, it->second);
+    graph_node& n = g.nodes[t];
+    graph_node const &x = g.nodes[n.src[0]], &w = g.nodes[n.src[1]];
+    vx_deform_conv_args a;
+    memset(&a, 0, sizeof a);
+    a.B = (int)x.ne[3]; a.H = (int)x.ne[2]; a.W = (int)x.ne[1]; a.Cin = (int)x.ne[0];
+    a.Cout = (int)n.ne[0]; a.k = (int)w.ne[1]; a.pad = (int)n.ip[1];
+    const int taps = a.k * a.k;
+    a.ld_offset = 2 * taps; a.ld_mask = taps; a.mask_mode = n.n_src == 4 ? 1 : 0; a.mask_scale = 1.0f;
+    a.ldo = a.Cout;
+    int n_pad = 0;
+    a.w = pack_deform(n.src[1], &n_pad);
+    std::vector<int> reads = {buf_of(n.src[0])};
+    auto xp = ptr(reads[0]);
+    // offsets and mask: activations in their buffers, or constants uploaded as f16
+    std::function<char*()> op_, mp_;
+    void *oc = nullptr, *mc = nullptr;
+    if (g.nodes[n.src[2]].constant) oc = const_f16(n.src[2]);
+    else { reads.push_back(buf_of(n.src[2])); op_ = ptr(reads.back()); }
+    if (n.n_src == 4) {
+        if (g.nodes[n.src[3]].constant) mc = const_f16(n.src[3]);
+        else { reads.push_back(buf_of(n.src[3])); mp_ = ptr(reads.back()); }
+    }
+    materialise(t);
+    const int obuf = n.buffer;
+    auto outp = ptr(obuf);
+    const std::string who = deform_who(g, n);
+    const int M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
+    char d[320];
+    snprintf(d, sizeof d, "deform_conv%s M=%d N=%d K=%d k=%d <- %s", n.n_src == 4 ? "[mask]" : "", M, a.Cout, taps * a.Cin, a.k, who.c_str());
+    emit(d, reads, {obuf}, [=](void* st) {
+        vx_deform_conv_args r = a;
+        r.x = xp();
+        r.offset = oc ? oc : op_();
+        r.mask = r.mask_mode ? (mc ? mc : mp_()) : nullptr;
+        r.out = outp();
+        VX(vx_deform_conv_f16(&r, st));
+    });
+    tag("deform_conv", 2.0 * M * (double)a.Cout * taps * a.Cin, (double)M * (a.Cin + a.Cout + 3.0 * taps) * 2);
+}
+
+// the matched group: ONE conv / GEMM computes offsets and modulator logits side by side, ONE deform_conv launch reads them in logits mode and applies the
+// per-channel scale, bias and ReLU
+void lowering::deform_fused(int t, deform_group const& G) {
+    graph_node& n = g.nodes[t];
+    graph_node const &x = g.nodes[n.src[0]], &w = g.nodes[n.src[1]];
+    graph_node const &on = g.nodes[G.off], &mn = g.nodes[G.mod];
+    const int k = (int)w.ne[1], taps = k * k, pad = (int)n.ip[1], Cin = (int)x.ne[0];
+    const int M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
+    const std::string who = deform_who(g, n);
+    const packed_operand p = pack_deform_offsets(on.src[1], on.n_src == 3 ? on.src[2] : -1, mn.src[1], mn.n_src == 3 ? mn.src[2] : -1);
+    const int ldom = round_up(3 * taps, 8);
+    const int xbuf = buf_of(n.src[0]);
+    const int ombuf = new_buffer((size_t)M * ldom * 2);
+    auto xp = ptr(xbuf), omp = ptr(ombuf);
+    {
+        vx_gemm_args a;
+        memset(&a, 0, sizeof a);
+        a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.M = M;
+        a.n_valid = ldom; a.ldo = ldom; a.epi = VX_EPI_F16;
+        const bool plain = k == 1 && pad == 0 && Cin % 64 == 0; // a plain product on the pixel rows; every other shape through the conv loader
+        if (plain) a.lda = Cin;
+        else {
+            a.conv_kh = a.conv_kw = k; a.conv_stride = 1; a.conv_pad = pad;
+            a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = Cin; a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
+        }
+        char d[320];
+        snprintf(d, sizeof d, "deform_offsets %s M=%d N=%d K=%d <- %s", plain ? "gemm" : ("conv" + std::to_string(k) + "x" + std::to_string(k)).c_str(), M, p.n_real, p.k_real,
+                 deform_who(g, on).c_str());
+        emit(d, {xbuf}, {ombuf}, [=](void* st) {
+            vx_gemm_args r = a;
+            r.A = xp();
+            r.out = omp();
+            VX(vx_gemm_f16(&r, st));
+        });
+        tag("deform_offsets", 2.0 * M * (double)p.n_real * p.k_real, (double)M * (Cin + p.n_real) * 2 + (double)p.N * p.K * 2);
+    }
+    vx_deform_conv_args a;
+    memset(&a, 0, sizeof a);
+    a.B = (int)x.ne[3]; a.H = (int)x.ne[2]; a.W = (int)x.ne[1]; a.Cin = Cin;
+    a.Cout = (int)n.ne[0]; a.k = k; a.pad = pad;
+    a.ld_offset = ldom; a.ld_mask = ldom; a.mask_mode = 2; a.mask_scale = G.s;
+    a.ldo = a.Cout;
+    int n_pad = 0;
+    a.w = pack_deform(n.src[1], &n_pad);
+    if (G.mul >= 0) a.scale = const_f32(g.nodes[G.mul].src[1]);
+    if (G.add >= 0) a.bias = const_f32(g.nodes[G.add].src[1]);
+    a.relu = G.relu >= 0;
+    epilogue e;
+    for (int c : {G.mul, G.add, G.relu})
+        if (c >= 0) e.absorbed.push_back(c);
+    absorb(e, t);
+    materialise(t);
+    const int obuf = n.buffer;
+    auto outp = ptr(obuf);
+    char d[320];
+    snprintf(d, sizeof d, "deform_conv[logits x%g]%s%s%s M=%d N=%d K=%d k=%d <- %s", G.s, G.mul >= 0 ? "[*scale]" : "", G.add >= 0 ? "[+bias]" : "", G.relu >= 0 ? "[relu]" : "", M,
+             a.Cout, taps * Cin, k, who.c_str());
+    emit(d, {xbuf, ombuf}, {obuf}, [=](void* st) {
+        vx_deform_conv_args r = a;
+        r.x = xp();
+        r.offset = omp();
+        r.mask = omp() + (size_t)2 * taps * 2;
+        r.out = outp();
+        VX(vx_deform_conv_f16(&r, st));
+    });
+    tag("deform_conv", 2.0 * M * (double)a.Cout * taps * Cin, (double)M * (Cin + a.Cout + ldom) * 2);
+}
 
 } // namespace visp

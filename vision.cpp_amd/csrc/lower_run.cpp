@@ -81,6 +81,7 @@ void lowering::run() {
             consumers[n.src[i]].push_back(t);
         }
     }
+    find_deform_groups();
     find_qkv_groups();
     find_encoder_chain();
     for (int t = 0; t < N; ++t) {
@@ -110,6 +111,20 @@ void lowering::run() {
             case gop_patch_embed: patch_embed(t); break;
             case gop_attention: attention(t); break;
             case gop_attention_masked: attention_masked(t); break;
+            case gop_conv_2d_deform: deform_conv(t); break;
+            case gop_sigmoid: {
+                const int64_t cnt = n.n_elements();
+                const int x_f32 = g.nodes[n.src[0]].dtype == gdt_f32;
+                map_launch(t, "sigmoid n=" + std::to_string(cnt), [=](char* x, char* o, char*, void* st) { VX(vx_sigmoid_f16(x, x_f32, o, cnt, st)); });
+                tag("glue", 0, (double)cnt * 4);
+            } break;
+            case gop_mean_2d: {
+                graph_node const& x = g.nodes[n.src[0]];
+                const int B = (int)x.ne[3], C = (int)x.ne[0];
+                const int64_t px = x.ne[1] * x.ne[2];
+                map_launch(t, "mean_2d " + shape_str(x.ne), [=](char* xp, char* o, char*, void* st) { VX(vx_mean_2d_f16(xp, o, B, px, C, st)); });
+                tag("mean", 0, (double)x.n_elements() * 2);
+            } break;
             case gop_cast: n.alias_of = n.src[0]; break; // an activation already has the type (graph_add refuses the rest): a view
             case gop_get_rows:
                 throw except("get_rows: a non-constant operand; get_rows is folded on the host from a constant table and a constant index (get_rows on activations is not built)");

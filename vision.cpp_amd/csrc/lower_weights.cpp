@@ -199,6 +199,46 @@ void* lowering::pack_rcu(int wt, int taps) {
     });
 }
 
+// the deformable conv's operand: the kernel's rows [cout][ky][kx][cin] as they are, f16, zero rows up to a multiple of 32 (kernels_deform.hip)
+void* lowering::pack_deform(int wt, int* n_pad) {
+    graph_node const& w = g.nodes[wt];
+    const int cout = (int)w.ne[3], np = round_up(cout, 32);
+    const size_t k = (size_t)(w.n_elements() / cout);
+    *n_pad = np;
+    return cached(wt, role_deform, [&](bool st) {
+        std::vector<uint16_t> h((size_t)np * k, 0);
+        for (size_t i = 0; i < (size_t)cout * k; ++i) h[i] = f32_to_f16(w.values()[i]);
+        return upload(h.data(), h.size() * 2, st);
+    });
+}
+// offset and modulator kernels over the same input as ONE operand: rows 0 .. 2 k^2 - 1 the offsets, then k^2 modulator logits, biases alike
+// (what pack_deform of csrc/birefnet.cpp does for the hand schedule)
+packed_operand lowering::pack_deform_offsets(int w_off, int b_off, int w_mod, int b_mod) {
+    graph_node const &wo = g.nodes[w_off], &wm = g.nodes[w_mod];
+    const int n_off = (int)wo.ne[3], n_mod = (int)wm.ne[3], k = (int)(wo.n_elements() / n_off);
+    auto id = [&](int t) { return t < 0 ? std::string("-") : (g.nodes[t].op == gop_weight && !g.nodes[t].name.empty() ? g.nodes[t].name : "#" + std::to_string(t)); };
+    const std::string with = id(w_mod) + "|" + id(b_off) + "|" + id(b_mod);
+    packed_operand p;
+    p.n_real = n_off + n_mod; p.k_real = k;
+    p.N = round_up(p.n_real, p.n_real > 64 ? 64 : 32);
+    p.K = round_up(k, 64);
+    p.w = cached(w_off, role_deform_offsets, [&](bool st) {
+        std::vector<uint16_t> h((size_t)p.N * p.K, 0);
+        for (int r = 0; r < p.n_real; ++r) {
+            const float* row = r < n_off ? wo.values() + (size_t)r * k : wm.values() + (size_t)(r - n_off) * k;
+            for (int c = 0; c < k; ++c) h[(size_t)r * p.K + c] = f32_to_f16(row[c]);
+        }
+        return upload(h.data(), h.size() * 2, st);
+    }, with);
+    p.bias = vec_cached(w_off, role_deform_offsets_bias, with, [&] {
+        std::vector<float> b((size_t)p.N, 0.0f);
+        for (int r = 0; r < n_off && b_off >= 0; ++r) b[(size_t)r] = g.nodes[b_off].values()[r];
+        for (int r = 0; r < n_mod && b_mod >= 0; ++r) b[(size_t)n_off + r] = g.nodes[b_mod].values()[r];
+        return b;
+    });
+    return p;
+}
+
 float* lowering::vec_cached(int key_node, pack_role role, std::string const& with, std::function<std::vector<float>()> make_host) {
     return static_cast<float*>(cached(key_node, role, [&](bool st) { std::vector<float> v = make_host(); return upload(v.data(), v.size() * 4, st); }, with));
 }

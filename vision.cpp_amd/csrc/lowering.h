@@ -148,6 +148,8 @@ struct lowering {
     void* pack_dconv(int wt, int cin, int cout, int* d_cin);
     void* pack_dconv_ex(int wt, int cin, int dup, int cout, int cout_pad, int* d_cin);
     void* pack_rcu(int wt, int taps);
+    void* pack_deform(int wt, int* n_pad);
+    packed_operand pack_deform_offsets(int w_off, int b_off, int w_mod, int b_mod);
 
     // ---- lower_conv.cpp
     // What a product's launch takes over from the nodes behind it: [* LayerScale] [gelu | relu | leaky_relu] [(* s1) + res] [(* s2) + res2].
@@ -176,6 +178,17 @@ struct lowering {
     bool resize_into_reader(int t);
     bool head_tail(int t);
     void one_channel_head(int t);
+    // conv_2d(offset, x), scale(sigmoid(conv_2d(modulator, x)), s), conv_2d_deform(x, W, ., .) [-> mul(c) -> add(c) -> relu] (birefnet.cpp:83-92, 110-115)
+    struct deform_group {
+        int off = -1, mod = -1, sig = -1, scl = -1; // the offset conv, the modulator conv, its sigmoid and scale nodes
+        int mul = -1, add = -1, relu = -1;          // the per-channel epilogue behind the deformable conv
+        float s = 1.0f;
+    };
+    std::map<int, deform_group> deform_groups;      // conv_2d_deform node -> its group (g.fused_models)
+    bool match_deform_group(int t, deform_group& G) const;
+    void find_deform_groups();
+    void deform_conv(int t);
+    void deform_fused(int t, deform_group const& G);
 
     // ---- lower_encoder.cpp
     void find_qkv_groups();

@@ -21,7 +21,7 @@ from ._lib import check, get_lib
 F32, F16, U8, I32 = 0, 1, 24, 26
 (OP_LINEAR, OP_LAYER_NORM, OP_GELU, OP_RELU, OP_SCALE, OP_ADD, OP_MUL, OP_CONV_2D, OP_CONV_TRANSPOSE_2D, OP_INTERPOLATE, OP_ATTENTION,
  OP_CONCAT, OP_SLICE, OP_RESHAPE, OP_REPEAT, OP_PATCH_EMBED, OP_CONT, OP_IMAGE_U8_TO_F32, OP_IMAGE_NORMALIZE, OP_LEAKY_RELU,
- OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED) = range(2, 28)
+ OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED, OP_CONV_2D_DEFORM, OP_SIGMOID, OP_MEAN_2D) = range(2, 31)
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
 
@@ -255,6 +255,17 @@ def patch_embed(m: ModelRef, x: Tensor, patch_size: int) -> Tensor:  # nn.cpp:16
     return out
 
 
+def conv_2d_deform(m: ModelRef, x: Tensor, weight: Tensor, offset: Tensor, mask: Tensor | None, stride: int, pad: int) -> Tensor:  # nn.cpp:131-148
+    """weight [Cin, k, k, Cout]; offset [2 k k, OW, OH, N] (channel 2t = dy, 2t + 1 = dx of tap t); mask [k k, OW, OH, N] or None. stride 1."""
+    return m.graph.op(OP_CONV_2D_DEFORM, [x, weight, offset] + ([mask] if mask is not None else []), [stride, pad])
+
+
+def batch_norm_2d(m: ModelRef, x: Tensor) -> Tensor:  # nn.cpp:150-164: the statistics were folded into weight and bias at conversion
+    if m.find("running_mean") is not None or m.find("running_var") is not None:
+        raise ValueError("Batch norm was not fused")
+    return named(m, add(m, mul(m, x, m.weights("weight")), m.weights("bias")))
+
+
 def split_qkv(m: ModelRef, x: Tensor, n_heads: int, split_dim: int):  # nn.cpp:182-208
     c, n, b, _ = x.ne
     qkv = linear(m, x)
@@ -314,6 +325,8 @@ def permute(m, x, a0, a1, a2, a3): return m.graph.op(OP_PERMUTE, [x], [a0, a1, a
 def roll(m, x, s0, s1, s2, s3): return m.graph.op(OP_ROLL, [x], [s0, s1, s2, s3])  # ggml_roll
 def pad(m, x, p0, p1, p2, p3): return m.graph.op(OP_PAD, [x], [p0, p1, p2, p3])  # ggml_pad
 def get_rows(m, table, index): return m.graph.op(OP_GET_ROWS, [table, index])  # ggml_get_rows (constants only: folded)
+def sigmoid(m, x): return m.graph.op(OP_SIGMOID, [x])  # ggml_sigmoid
+def mean_2d(m, x): return m.graph.op(OP_MEAN_2D, [x])  # birefnet.cpp:93-100: [C, W, H, N] -> [C, 1, 1, N] (not ggml_mean, which reduces ne[0])
 def cast(m, x, dtype): return m.graph.op(OP_CAST, [x], [dtype])  # ggml_cast
 
 
@@ -613,3 +626,46 @@ def swin_encode(m: ModelRef, x: Tensor, window: int, depths, n_heads):  # swin.c
         out = layer_norm(m[f"norm{i}"], x_out)
         outs.append(reshape(m, out, out.ne[0], w_out, h_out, b))
     return outs
+
+
+# ---- BiRefNet decoder block against this layer (the structure of src/visp/arch/birefnet.cpp:79-145) ------------------------------------------
+
+def birefnet_conv_2d_batch_norm(m: ModelRef, x: Tensor, stride: int = 1, pad: int = 0) -> Tensor:  # birefnet.cpp:79-81
+    return conv_2d(m, x, stride, pad)  # batch_norm is fused into conv_2d at model conversion
+
+
+def birefnet_deformable_conv_2d(m: ModelRef, x: Tensor, stride: int, pad: int) -> Tensor:  # birefnet.cpp:83-91
+    offset = conv_2d(m["offset"], x, stride, pad)
+    modulator = conv_2d(m["modulator"], x, stride, pad)
+    modulator = scale(m, sigmoid(m, modulator), 2.0)
+    x = conv_2d_deform(m, x, m.weights("conv.weight"), offset, modulator, stride, pad)
+    return named(m, x)
+
+
+def birefnet_global_avg_pool(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.cpp:93-107
+    x = mean_2d(m, x)
+    x = relu(m, birefnet_conv_2d_batch_norm(m[1], x))
+    return named(m, x)
+
+
+def birefnet_aspp_module_deformable(m: ModelRef, x: Tensor, padding: int = 0) -> Tensor:  # birefnet.cpp:109-114
+    x = birefnet_deformable_conv_2d(m["conv"], x, 1, padding)
+    x = batch_norm_2d(m["bn"], x)
+    return named(m, relu(m, x))
+
+
+def birefnet_aspp_deformable(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.cpp:116-137
+    x1 = birefnet_aspp_module_deformable(m["aspp1"], x)
+    x_deforms = [birefnet_aspp_module_deformable(m["aspp_deforms"][i], x, k // 2) for i, k in enumerate((1, 3, 7))]
+    x5 = birefnet_global_avg_pool(m["global_avg_pool"], x)
+    x5 = interpolate(m, x5, (x1.ne[1], x1.ne[2]), BILINEAR_AC)
+    x = concat(m, [x1, *x_deforms, x5], 0)
+    x = relu(m, birefnet_conv_2d_batch_norm(m["conv1"], x))
+    return named(m, x)
+
+
+def birefnet_basic_decoder_block(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.cpp:139-145
+    x = relu(m, birefnet_conv_2d_batch_norm(m["conv_in"], x, 1, 1))
+    x = birefnet_aspp_deformable(m["dec_att"], x)
+    x = birefnet_conv_2d_batch_norm(m["conv_out"], x, 1, 1)
+    return named(m, x)
