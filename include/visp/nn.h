@@ -35,6 +35,11 @@ inline tensor conv_2d(model_ref m, tensor x, int stride = 1, int pad = 0) { // n
     tensor b = m.find("bias");
     return b ? detail::op(m, VISP_OP_CONV_2D, {x, m.weights("weight"), b}, {stride, pad}) : detail::op(m, VISP_OP_CONV_2D, {x, m.weights("weight")}, {stride, pad});
 }
+// depthwise: weight [C, 1, kw, kh] (written NHWC: local_conv of mobile-sam.cpp:152-155) or [1, kw, kh, C] (OIHW, listed in conv2d_weights); nn.cpp:102-115
+inline tensor conv_2d_depthwise(model_ref m, tensor x, int stride = 1, int pad = 0) {
+    tensor b = m.find("bias");
+    return b ? detail::op(m, VISP_OP_CONV_2D_DEPTHWISE, {x, m.weights("weight"), b}, {stride, pad}) : detail::op(m, VISP_OP_CONV_2D_DEPTHWISE, {x, m.weights("weight")}, {stride, pad});
+}
 inline tensor conv_transpose_2d(model_ref m, tensor x, int stride) { // nn.cpp:117-129; weight [kw, kh, Cout, Cin], kernel == stride
     tensor b = m.find("bias");
     return b ? detail::op(m, VISP_OP_CONV_TRANSPOSE_2D, {x, m.weights("weight"), b}, {stride}) : detail::op(m, VISP_OP_CONV_TRANSPOSE_2D, {x, m.weights("weight")}, {stride});

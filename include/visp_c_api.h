@@ -354,8 +354,14 @@ enum visp_graph_op {
      * add(c), relu] is two launches (kernels_deform.hip).                                                                  nn.cpp:131-148, birefnet.cpp:83-92 */
     VISP_OP_CONV_2D_DEFORM = 28,
     VISP_OP_SIGMOID = 29,          /* element-wise on f16 activations; folded on the host on constants                     ggml_sigmoid, birefnet.cpp:86 */
-    VISP_OP_MEAN_2D = 30           /* x [C, W, H, N] -> [C, 1, 1, N]: f32 sums in a fixed order, no atomics (the same bits every launch). NOT ggml_mean, which
+    VISP_OP_MEAN_2D = 30,          /* x [C, W, H, N] -> [C, 1, 1, N]: f32 sums in a fixed order, no atomics (the same bits every launch). NOT ggml_mean, which
                                       reduces ne[0] -- here the channel                                                    mean_2d, birefnet.cpp:93-100 */
+    /* src x [C, W, H, N] f16, kernel (a constant) as [C, 1, kw, kh] (the NHWC form of TinyViT's local_conv) or [1, kw, kh, C] (a depthwise OIHW kernel listed in
+     * conv2d_weights), (bias [C], a constant); i0 stride (1 or 2), i1 pad. -> [C, (W + 2 pad - kw) / stride + 1, (H + 2 pad - kh) / stride + 1, N], floor division,
+     * even kernels like odd ones (4x4 at pad 2 gives W + 1 columns). Built for kw == kh <= 7, pad <= k - 1, C % 8 == 0; anything else is refused when the node is
+     * made. One launch (kernels_dwconv.hip); with the default fused models a gelu / leaky_relu that is its only reader joins it.
+     *                                                                                                        nn.cpp:102-115, mobile-sam.cpp:20-23, migan.cpp:28-57 */
+    VISP_OP_CONV_2D_DEPTHWISE = 31
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

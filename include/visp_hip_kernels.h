@@ -467,6 +467,15 @@ VX_API int vx_convert(const void* x, int x_f32, void* y, int y_f32, int64_t n, v
 VX_API int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream);
 /* f32 image [pixels][C <= 16] -> one 32-channel f16 plane: values, then what the f16 rounding dropped, then zeros (input of an image's first conv) */
 VX_API int vx_image_planes_f32(const float* x, void* y, int64_t n_pix, int C, void* stream);
+/* f32 image [pixels][3] -> f16 [pixels][8]: the values in channels 0..2, what the f16 rounding dropped in 3..5, zeros in 6..7 (the arithmetic of
+ * vx_tv_preprocess without the normalisation): the input of a 3-channel conv whose GEMM operand repeats taps 0..2 on 3..5 */
+VX_API int vx_image_pad8_f32(const float* x, void* y, int64_t n_pix, void* stream);
+/* ---- depthwise convolution, any square kernel (kernels_dwconv.hip; conv_2d_depthwise + add_bias_2d, nn.cpp:102-115) ----
+ * x f16 [B,H,W,C], C % 8 == 0; w f16 [k*k][C] (tap-major, tap = ky*k + kx); bias f32 [C] or NULL; y f16 [B,OH,OW,C] with OH = (H + 2 pad - k) / stride + 1
+ * (OW alike; even kernels like odd ones). k 1..7, stride 1 or 2, pad 0..k-1. Taps outside the map are zeros. act 0 none, 1 tanh GELU (ggml_gelu),
+ * 2 leaky ReLU with slope act_param. 16-byte aligned operands. */
+VX_API int vx_dwconv_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride, int pad, int act, float act_param,
+                         void* stream);
 /* patch_embed's im2col (nn.cpp:166-180) on the f32 image tensor [B,H,W,C]: rows (b,py,px), k = (ky,kx,c), zero padded to Kp, f16 */
 /* 1x1 convolution to one channel: out f32 [M] = scale * act(sum_c x[m,c] w[c] + bias), x f16 [M][C] (depth-anything.cpp:91-95) */
 VX_API int vx_conv1x1_to1_f32(const void* x, const float* w, float bias, int relu, float scale, float* out, int64_t M, int C, void* stream);

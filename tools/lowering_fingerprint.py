@@ -77,6 +77,18 @@ def cases(tmp: Path):
     yield "conv_leaky_0.1", case(GC.conv_leaky, 0.1)
     yield "encoder_chain_equal_scales", case(GC.encoder_chain, [0.125, 0.125])
     yield "encoder_chain_differing_scales", case(GC.encoder_chain, [0.125, 0.25])
+    for cfg, batch in ((synth.TINYVIT_MINI, 2), (synth.TINYVIT_5M, 1)):
+        path = None
+        for fused in (True, False):
+            def build(cfg=cfg, batch=batch, fused=fused):
+                nonlocal path
+                path = path or synth.write_tinyvit_gguf(tmp / f"tinyvit_{cfg.name}.gguf", cfg, seed=3)
+                g = G.Graph(None, G.Weights(path))
+                g.set_fused_models(fused)
+                out = G.tinyvit_encode(G.ModelRef(g, "enc"), g.input((3, cfg.img_size, cfg.img_size, batch), G.F32, "image"), cfg.layers())
+                g.output(out, "output")
+                return g
+            yield f"tinyvit_{cfg.name}_b{batch}_{'fused' if fused else 'per_node'}", build
 
 
 def device_cases(tmp: Path):

@@ -159,7 +159,7 @@ KERNEL_SYMBOLS = [
     "vx_head_out_f32", "vx_minmax_normalize", "vx_f32_to_u8",
     "vx_dconv3x3_f16", "vx_dconv_bilinear_supported", "vx_dconv_prepare", "vx_dconv_x_residual_supported", "vx_dconv_set_block_cap", "vx_dconv_set_resident_mode", "vx_tv_preprocess", "vx_dwconv3x3_f16", "vx_layernorm_f16", "vx_window_attention_f16", "vx_window_attention_bias_bytes", "vx_window_attention_pack_bias",
     "vx_window_reverse_add_f16", "vx_add_gelu_f16", "vx_add_rows_f16", "vx_small_attention_f16", "vx_sam_interpolate", "vx_mbconv_dw_pw_supported", "vx_mbconv_pack_w3", "vx_mbconv_dw_pw_f16", "vx_esrgan_tiles_in", "vx_esrgan_tiles_out",
-    "vx_bf_preprocess_half", "vx_bf_patches", "vx_bf_resize_f16", "vx_bf_deform_cols_f16", "vx_bf_mean_f16", "vx_bf_broadcast_f16", "vx_bf_mul_sigmoid_f16", "vx_bf_sigmoid_out_f32", "vx_deform_conv_f16", "vx_sigmoid_f16", "vx_mean_2d_f16",
+    "vx_bf_preprocess_half", "vx_bf_patches", "vx_bf_resize_f16", "vx_bf_deform_cols_f16", "vx_bf_mean_f16", "vx_bf_broadcast_f16", "vx_bf_mul_sigmoid_f16", "vx_bf_sigmoid_out_f32", "vx_deform_conv_f16", "vx_sigmoid_f16", "vx_mean_2d_f16", "vx_dwconv_f16", "vx_image_pad8_f32",
     "vx_swin_attention_pack_bias", "vx_window_attention_masked_f16", "vx_swin_layernorm_f16", "vx_swin_layernorm_strided_f16", "vx_swin_merge_layernorm_f16", "vx_swin_window_reverse_add_f16",
     "vx_headconv_frag_bytes", "vx_headconv_pack", "vx_headconv_supported", "vx_headconv_bil_f16", "vx_headconv_set_stamps", "vx_headconv_set_block_cap",
     "vx_headconv_wide_supported", "vx_headconv_wide_frag_bytes", "vx_headconv_wide_pack", "vx_headconv_wide_bil_f16",
@@ -435,6 +435,8 @@ def init() -> ctypes.CDLL:
     lib.vx_sigmoid_f16.argtypes = [c_void_p, c_int, c_void_p, c_int64, c_void_p]
     lib.vx_mean_2d_f16.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]
     lib.vx_deform_conv_f16.argtypes = [POINTER(DeformConvArgs), c_void_p]
+    lib.vx_dwconv_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]
+    lib.vx_image_pad8_f32.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
     lib.vx_convert.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]
     lib.vx_nearest_f16.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.vx_image_planes_f32.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p]

@@ -19,7 +19,7 @@ namespace {
 const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_norm", "gelu", "relu", "scale", "add", "mul", "conv_2d",
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
-                                         "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d"};
+                                         "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -616,6 +616,30 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
                 throw except("conv_2d_deform: mask %s does not match a %lldx%lld kernel on a %lldx%lld output ([kh kw, OW, OH, N] = [%lld, %lld, %lld, %lld])", shape_str(S(3).ne).c_str(),
                              (long long)w.ne[1], (long long)w.ne[2], (long long)n.ne[1], (long long)n.ne[2], (long long)taps, (long long)n.ne[1], (long long)n.ne[2], (long long)n.ne[3]);
         } break;
+        case gop_conv_2d_depthwise: {
+            need_src(2, 3);
+            graph_node const &x = S(0), &w = S(1);
+            const int64_t stride = n.ip[0] > 0 ? n.ip[0] : 1, pad = n.ip[1], C = x.ne[0];
+            n.ip[0] = stride;
+            if (!w.constant) throw except("conv_2d_depthwise: the kernel must be a model weight (a constant)");
+            // the two forms the weight store hands over: [C, 1, kw, kh] (written NHWC, nn.cpp:106 permutes it) and [1, kw, kh, C] (a depthwise OIHW kernel
+            // listed in conv2d_weights)
+            int64_t kw, kh;
+            if (w.ne[0] == C && w.ne[1] == 1) { kw = w.ne[2]; kh = w.ne[3]; }
+            else if (w.ne[0] == 1 && w.ne[3] == C) { kw = w.ne[1]; kh = w.ne[2]; }
+            else throw except("conv_2d_depthwise: kernel %s is neither [C, 1, kw, kh] nor [1, kw, kh, C] for input %s (CWHN)", shape_str(w.ne).c_str(), shape_str(x.ne).c_str());
+            if (stride != 1 && stride != 2) throw except("conv_2d_depthwise: stride %lld is not built (1 and 2 are)", (long long)stride);
+            if (kw != kh) throw except("conv_2d_depthwise: kernel %lldx%lld; square kernels only", (long long)kw, (long long)kh);
+            if (kw > 7) throw except("conv_2d_depthwise: kernel %lldx%lld; kernels up to 7x7", (long long)kw, (long long)kh);
+            if (pad < 0 || pad > kw - 1) throw except("conv_2d_depthwise: pad %lld with a %lldx%lld kernel (0 .. k - 1)", (long long)pad, (long long)kw, (long long)kh);
+            if (C % 8) throw except("conv_2d_depthwise: C = %lld must be a multiple of 8", (long long)C);
+            if (n_src == 3 && (!S(2).constant || S(2).n_elements() != C)) throw except("conv_2d_depthwise: bias has %lld elements, expected %lld (a constant)", (long long)S(2).n_elements(), (long long)C);
+            n.ne[0] = C;
+            n.ne[1] = x.ne[1] + 2 * pad - kw < 0 ? 0 : (x.ne[1] + 2 * pad - kw) / stride + 1;
+            n.ne[2] = x.ne[2] + 2 * pad - kh < 0 ? 0 : (x.ne[2] + 2 * pad - kh) / stride + 1;
+            n.ne[3] = x.ne[3];
+            if (n.ne[1] < 1 || n.ne[2] < 1) throw except("conv_2d_depthwise: a %lldx%lld kernel at pad %lld does not fit the %lldx%lld input", (long long)kw, (long long)kh, (long long)pad, (long long)x.ne[1], (long long)x.ne[2]);
+        } break;
         default: throw except("graph_add: op %d", op);
     }
     // f32 tensors exist as inputs only; an f32 operand anywhere else would need kernels this executor does not have
@@ -625,7 +649,9 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             // (a 3x3 conv on the f32 image of <= 16 channels: the first conv of an image-to-image network, esrgan.cpp:58)
             const bool image_conv = op == gop_conv_2d && i == 0 && S(0).op == gop_input && S(0).ne[0] <= 16 && S(1).ne[1] == 3 && S(1).ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1;
             const bool f32_mask = op == gop_attention_masked && i == 3; // the masked attention reads an f32 mask in place
-            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !f32_mask)
+            // (any conv on a 3-channel f32 image: image_pad8 in front of the GEMM family's conv, mobile-sam.cpp:71-73)
+            const bool image8_conv = op == gop_conv_2d && i == 0 && S(0).dtype == gdt_f32 && S(0).ne[0] == 3;
+            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask)
                 throw except("%s: operand %d is f32; only patch_embed and an image's first 3x3 conv read the f32 input tensor", nm, i);
         }
 

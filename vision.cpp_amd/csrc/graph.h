@@ -63,6 +63,8 @@ enum graph_op : int32_t {
     gop_conv_2d_deform,   // x CWHN, w [Cin, k, k, Cout], offset [2 k k, OW, OH, N], (mask [k k, OW, OH, N]); i0 = stride (1), i1 = pad   nn.cpp:131-148
     gop_sigmoid,          // ggml_sigmoid                              birefnet.cpp:86
     gop_mean_2d,          // x [C, W, H, N] -> [C, 1, 1, N]: the pixel mean, f32 sums in a fixed order   birefnet.cpp:93-100
+    // the one nn.h function TinyViT (mobile-sam.cpp:15-208) and MI-GAN (migan.cpp:28-57) need beyond the above
+    gop_conv_2d_depthwise,// x CWHN, w [C, 1, kw, kh] or [1, kw, kh, C], (b [C]); i0 = stride (1 | 2), i1 = pad   nn.cpp:102-115
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -120,7 +122,10 @@ enum pack_role : int {
     role_deform = 10,        // deformable conv operand: f16 rows [Cout pad 32][taps * Cin]
     role_deform_offsets = 11,// offset | modulator kernels of a deformable conv as one GEMM operand (keyed on the offset kernel)
     role_deform_offsets_bias = 12, // ... and their biases, f32 [N pad]
-    role_bias_base = 16,     // 16..24: bias_of_role(r), the f32 bias [N pad] that goes with the operand of role r (0..8)
+    role_depthwise = 13,     // depthwise conv operand: f16 [k * k][C], tap-major, from either stored form
+    role_image8 = 14,        // GEMM operand of a conv on a 3-channel f32 image read as 8-channel value | residue pixels: taps 0..2 repeated on 3..5
+    role_winattn_bias = 15,  // attention bias [T, T, heads, 1] in the window-attention kernel's accumulator order (vx_window_attention_pack_bias)
+    role_bias_base = 16,     // 16..24: bias_of_role(r), the f32 bias [N pad] that goes with the operand of role r (0..8); 30: that of role_image8
     role_block_mlp = 40,     // block kernel: out-proj | fc1 | fc2 fragments, LayerScale folded (keyed on the out-proj weight)
     role_block_qkv = 41,     // block kernel: q | k | v fragments
     role_block_mlp_vec = 42, // block kernel: biases, lambdas and LN2 of the MLP half as one f32 vector

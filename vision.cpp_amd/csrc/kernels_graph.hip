@@ -183,6 +183,15 @@ __global__ __launch_bounds__(256) void image_planes_kernel(const float* __restri
     }
 }
 
+// An f32 image [pixels][3] as 8-channel f16 pixels for the GEMM family's conv loader: value | rounding residue | zeros (residue_pixel, vx_device.h) --
+// tv_preprocess_kernel's arithmetic (kernels_tinyvit.hip) on an image that is normalised already
+__global__ __launch_bounds__(256) void image_pad8_kernel(const float* __restrict__ x, f16* __restrict__ y, long n_pix) {
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n_pix; p += (long)gridDim.x * 256) {
+        const float v[3] = {x[p * 3], x[p * 3 + 1], x[p * 3 + 2]};
+        reinterpret_cast<f16x8*>(y)[p] = residue_pixel(v);
+    }
+}
+
 // ggml_sigmoid on f16: 8 elements per thread-iteration, a scalar tail
 __global__ __launch_bounds__(256) void sigmoid_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n) {
     const long n8 = n >> 3;
@@ -414,6 +423,14 @@ extern "C" int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C
     VX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 8 == 0, "vx_nearest_f16: bad operands (C a multiple of 8)");
     const long n = (long)B * OH * OW * (C / 8);
     hipLaunchKernelGGL(nearest_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, H, W, C / 8, OH, OW, (float)OH / (float)H, (float)OW / (float)W, n);
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_image_pad8_f32(const float* x, void* y, int64_t n_pix, void* stream) {
+    VX_REQUIRE(x && y && n_pix > 0, "vx_image_pad8_f32: bad operands");
+    VX_REQUIRE(aligned16(y), "vx_image_pad8_f32: the output must be 16-byte aligned");
+    hipLaunchKernelGGL(image_pad8_kernel, dim3(grid_stride_blocks(n_pix, GRID_CAP)), dim3(256), 0, as_stream(stream), x, (f16*)y, (long)n_pix);
     VX_LAUNCH_CHECK();
     return 1;
 }

@@ -509,17 +509,19 @@ void lowering::gemm_like(int t) {
         const int kw = (int)w.ne[1], kh = (int)w.ne[2], pad = (int)n.ip[1];
         stride = (int)n.ip[0];
         a.M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
-        if (kw == 1 && kh == 1 && stride == 1 && pad == 0) { // 1x1: a plain product on the pixel rows (nn.cpp:76-81)
+        // a 3-channel f32 image (patch_embed of mobile-sam.cpp:71-76): read as 8-channel value | residue pixels by the conv loader
+        const bool image8_in = x.dtype == gdt_f32 && x.ne[0] == 3;
+        if (!image8_in && kw == 1 && kh == 1 && stride == 1 && pad == 0) { // 1x1: a plain product on the pixel rows (nn.cpp:76-81)
             p = pack_rows(wt, bt, (int)n.ne[0]);
             kind = "gemm(conv1x1)";
             xbuf = plain_rows(p.k_real, p.K);
         } else {
-            if (x.ne[0] % 8) throw except("conv_2d %s: Cin = %lld must be a multiple of 8", who.c_str(), (long long)x.ne[0]);
-            if (dconv_shape(n, x, w)) return dconv(t, who);
-            p = pack_rows(wt, bt, (int)n.ne[0]);
-            xbuf = buf_of(xs);
+            if (!image8_in && x.ne[0] % 8) throw except("conv_2d %s: Cin = %lld must be a multiple of 8", who.c_str(), (long long)x.ne[0]);
+            if (!image8_in && dconv_shape(n, x, w)) return dconv(t, who);
+            p = image8_in ? pack_image8(wt, bt, (int)n.ne[0]) : pack_rows(wt, bt, (int)n.ne[0]);
+            xbuf = image8_in ? image_pad8(xs) : buf_of(xs);
             a.conv_kh = kh; a.conv_kw = kw; a.conv_stride = stride; a.conv_pad = pad;
-            a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = (int)x.ne[0];
+            a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = image8_in ? 8 : (int)x.ne[0];
             a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
             a.a_relu = relu_on_load[t];
             conv = true;
@@ -870,6 +872,57 @@ void lowering::deform_fused(int t, deform_group const& G) {
         VX(vx_deform_conv_f16(&r, st));
     });
     tag("deform_conv", 2.0 * M * (double)a.Cout * taps * Cin, (double)M * (Cin + a.Cout + ldom) * 2);
+}
+
+// ---- depthwise convolution (nn.cpp:102-115) and the 3-channel image in front of a model's first conv ---------------------------------------------
+
+// the 8-channel f16 pixels of a 3-channel f32 image, made once per image whoever reads it
+int lowering::image_pad8(int xs) {
+    const int r = root(xs);
+    if (auto it = image8.find(r); it != image8.end()) return it->second;
+    graph_node const& x = g.nodes[r];
+    const int64_t px = x.ne[1] * x.ne[2] * x.ne[3];
+    const int src = buf_of(r), dst = new_buffer((size_t)px * 16);
+    auto sp = ptr(src), dp = ptr(dst);
+    emit("image_pad8 " + shape_str(x.ne), {src}, {dst}, [=](void* st) { VX(vx_image_pad8_f32(reinterpret_cast<const float*>(sp()), dp(), px, st)); });
+    tag("preprocess", 0, (double)px * 28);
+    image8[r] = dst;
+    return dst;
+}
+
+// one launch of a depthwise kernel (kernels_dwconv.hip, or kernels_tinyvit.hip's for 3x3 / pad 1); with fused models a gelu / leaky_relu that is its only reader joins it
+void lowering::depthwise_conv(int t) {
+    graph_node& n = g.nodes[t];
+    graph_node const &x = g.nodes[n.src[0]], &w = g.nodes[n.src[1]];
+    const int C = (int)x.ne[0], k = (int)(w.ne[0] == C && w.ne[1] == 1 ? w.ne[2] : w.ne[1]);
+    const int B = (int)x.ne[3], H = (int)x.ne[2], W = (int)x.ne[1], stride = (int)n.ip[0], pad = (int)n.ip[1];
+    void* wp = pack_depthwise(n.src[1], C, k);
+    const float* bp = n.n_src == 3 ? const_f32(n.src[2]) : nullptr;
+    int act = 0;
+    float act_param = 0.0f;
+    if (const int c = sole_consumer(t); g.fused_models && c >= 0 && (g.nodes[c].op == gop_gelu || g.nodes[c].op == gop_leaky_relu)) {
+        act = g.nodes[c].op == gop_gelu ? 1 : 2;
+        act_param = g.nodes[c].fp[0];
+        epilogue e;
+        e.absorbed.push_back(c);
+        absorb(e, t);
+    }
+    const std::string who = w.op == gop_weight && !w.name.empty() ? w.name : n.name;
+    const int xbuf = buf_of(n.src[0]);
+    materialise(t);
+    const int obuf = n.buffer;
+    auto xp = ptr(xbuf), op = ptr(obuf);
+    char d[320];
+    snprintf(d, sizeof d, "dwconv%dx%d%s%s B=%d %dx%d -> %lldx%lld C=%d pad=%d <- %s", k, k, stride > 1 ? "s2" : "", act == 1 ? "[gelu]" : (act == 2 ? "[leaky_relu]" : ""), B, W, H,
+             (long long)n.ne[1], (long long)n.ne[2], C, pad, who.c_str());
+    // 3x3 / pad 1 with a bias and no activation but GELU is what the hand schedule's kernel computes, to the same bits and measurably faster at stride 1
+    // (tools/bench_dwconv.py): those launches go to it, everything else to the generic kernel
+    const bool hand3x3 = k == 3 && pad == 1 && bp && act != 2;
+    emit(d, {xbuf}, {obuf}, [=](void* st) {
+        if (hand3x3) VX(vx_dwconv3x3_f16(xp(), wp, bp, op(), B, H, W, C, stride, act == 1, st));
+        else VX(vx_dwconv_f16(xp(), wp, bp, op(), B, H, W, C, k, stride, pad, act, act_param, st));
+    });
+    tag("dwconv", 2.0 * (double)n.n_elements() * k * k, (double)(x.n_elements() + n.n_elements()) * 2 + (double)k * k * C * 2);
 }
 
 } // namespace visp

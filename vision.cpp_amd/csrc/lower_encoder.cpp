@@ -1,6 +1,8 @@
 // Graph lowering: attention, patch embedding and the DINOv2 encoder chain (see lowering.h).
 #include "lowering.h"
 
+#include <cmath>
+
 namespace visp {
 
 void lowering::patch_embed(int t) {
@@ -129,6 +131,7 @@ void lowering::attention(int t) {
 // folded into q; a constant mask (bias table [+ shift mask], folded on the host) becomes one f16 device image [Bm][Hm][T_q][T_k] -- ggml's
 // [T_k, T_q, Hm, Bm] is that layout already --, cut to its shortest period over the batch; an activation mask is read where it is, f16 or f32.
 void lowering::attention_masked(int t) {
+    if (auto it = window_groups.find(t); it != window_groups.end()) return window_attention(t, it->second);
     graph_node& n = g.nodes[t];
     graph_node const &q = g.nodes[n.src[0]], &mk = g.nodes[n.src[3]];
     const int64_t hd = q.ne[0], H = q.ne[1], T = q.ne[2], B = q.ne[3], Hm = mk.ne[2];
@@ -162,6 +165,81 @@ void lowering::attention_masked(int t) {
         VX(vx_attention_masked_f16(qp(), kp(), vp(), mp ? static_cast<const void*>(mp()) : mconst, op(), (int)B, (int)H, (int)T, (int)hd, (int)Hm, (int)Bm, mask_f32, st));
     });
     tag("attention", 4.0 * B * H * (double)T * T * hd, (double)B * H * T * hd * 2 * 4 + (double)B * H * T * T * (mask_f32 ? 4 : 2));
+}
+
+// ---- the packed-bias window attention (mobile-sam.cpp:124-132) ---------------------------------------------------------------------------
+// split_qkv(.., 1) leaves every token row of the q|k|v product as heads x (q | k | v) of 32 channels each -- the operand layout of
+// vx_window_attention_f16 (kernels_winattn.hip). When the views between the product and the attention are read by nothing else, the attention runs on
+// the product's rows where they are: two launches instead of permute, three slices, three heads_major copies and the masked attention. SWIN splits with
+// split_dim 2 (its rows are q | k | v of ALL heads): its permute has other axes and does not match.
+bool lowering::match_window_group(int att, window_group& G) const {
+    graph_node const& n = g.nodes[att];
+    if (n.op != gop_attention_masked) return false;
+    graph_node const &q = g.nodes[n.src[0]], &mk = g.nodes[n.src[3]];
+    const int64_t hd = q.ne[0], H = q.ne[1], T = q.ne[2], B = q.ne[3];
+    if (hd != 32 || T > 256 || fabsf(n.fp[0] - 1.0f / sqrtf(32.0f)) > 1e-6f) return false; // (the kernel's own scale is 1 / sqrt(32))
+    if (!mk.constant || mk.ne[0] != T || mk.ne[1] != T || mk.ne[2] != H || mk.ne[3] != 1) return false;
+    int cn = -1;
+    for (int i = 0; i < 3; ++i) {
+        const int r = n.src[i];
+        graph_node const& rn = g.nodes[r];
+        if (rn.op != gop_reshape || rn.constant || sole_consumer(r) != att || rn.ne[0] != 32 || rn.ne[1] != H || rn.ne[2] != T || rn.ne[3] != B) return false;
+        const int sl = rn.src[0];
+        graph_node const& sn = g.nodes[sl];
+        if (sn.op != gop_slice || sole_consumer(sl) != r) return false;
+        graph_node const& c = g.nodes[sn.src[0]];
+        // part i of the last dimension, everything of the others
+        if (sn.ip[9] != i || sn.ne[3] != 1 || sn.ip[11] != 1 || sn.ip[0] != 0 || sn.ip[3] != 0 || sn.ip[6] != 0 || sn.ip[2] != 1 || sn.ip[5] != 1 || sn.ip[8] != 1 ||
+            sn.ne[0] != c.ne[0] || sn.ne[1] != c.ne[1] || sn.ne[2] != c.ne[2])
+            return false;
+        if (i == 0) cn = sn.src[0];
+        else if (sn.src[0] != cn) return false;
+        G.views.push_back(r);
+        G.views.push_back(sl);
+    }
+    graph_node const& c = g.nodes[cn];
+    if (c.op != gop_cont || c.is_output || uses[cn] != 3 || c.ne[0] != 32 || c.ne[1] != H * T || c.ne[2] != B || c.ne[3] != 3) return false;
+    const int pm = c.src[0];
+    graph_node const& p = g.nodes[pm];
+    if (p.op != gop_permute || sole_consumer(pm) != cn || p.ip[0] != 0 || p.ip[1] != 3 || p.ip[2] != 1 || p.ip[3] != 2) return false;
+    const int r0 = p.src[0];
+    graph_node const& r = g.nodes[r0];
+    if (r.op != gop_reshape || sole_consumer(r0) != pm || r.ne[0] != 32 || r.ne[1] != 3 || r.ne[2] != H * T || r.ne[3] != B) return false;
+    const int lin = r.src[0];
+    graph_node const& l = g.nodes[lin];
+    if (l.op != gop_linear || l.constant || sole_consumer(lin) != r0 || l.ne[0] != 96 * H || l.ne[1] != T || l.ne[2] != B || l.ne[3] != 1) return false;
+    G.lin = lin;
+    for (int v : {cn, pm, r0}) G.views.push_back(v);
+    return true;
+}
+// before the node loop: the views come before their attention in node order and must not be lowered on their own
+void lowering::find_window_groups() {
+    if (!g.fused_models) return;
+    for (int t = 0; t < (int)g.nodes.size(); ++t) {
+        window_group G;
+        if (!needed[t] || !match_window_group(t, G)) continue;
+        for (int v : G.views) skip[v] = 1;
+        window_groups[t] = std::move(G);
+    }
+}
+void lowering::window_attention(int t, window_group const& G) {
+    graph_node& n = g.nodes[t];
+    graph_node const &q = g.nodes[n.src[0]], &mk = g.nodes[n.src[3]];
+    const int H = (int)q.ne[1], T = (int)q.ne[2], B = (int)q.ne[3];
+    void* bias = cached(n.src[3], role_winattn_bias, [&](bool st) {
+        std::vector<char> h(vx_window_attention_bias_bytes(T, H));
+        VX(vx_window_attention_pack_bias(mk.values(), T, H, h.data())); // ggml's [T_k, T_q, heads, 1] is [heads][T_q][T_k] in memory
+        return upload(h.data(), h.size(), st);
+    });
+    const int qbuf = buf_of(G.lin);
+    materialise(t);
+    const int obuf = n.buffer;
+    auto qp = ptr(qbuf), op = ptr(obuf);
+    graph_node const& w = g.nodes[g.nodes[G.lin].src[1]];
+    char d[240];
+    snprintf(d, sizeof d, "window_attention windows=%d heads=%d T=%d hd=32 <- %s", B, H, T, w.name.c_str());
+    emit(d, {qbuf}, {obuf}, [=](void* st) { VX(vx_window_attention_f16(qp(), bias, op(), B, T, H, st)); });
+    tag("attention", 4.0 * B * H * (double)T * T * 32, (double)B * H * T * 32 * 2 * 4 + (double)H * T * T * 2);
 }
 
 // ---- fused model group 1: the DINOv2 encoder (dino.cpp:10-110) -----------------------------------------------------------------------

@@ -83,6 +83,7 @@ void lowering::run() {
     }
     find_deform_groups();
     find_qkv_groups();
+    find_window_groups();
     find_encoder_chain();
     for (int t = 0; t < N; ++t) {
         graph_node& n = g.nodes[t];
@@ -112,6 +113,7 @@ void lowering::run() {
             case gop_attention: attention(t); break;
             case gop_attention_masked: attention_masked(t); break;
             case gop_conv_2d_deform: deform_conv(t); break;
+            case gop_conv_2d_depthwise: depthwise_conv(t); break;
             case gop_sigmoid: {
                 const int64_t cnt = n.n_elements();
                 const int x_f32 = g.nodes[n.src[0]].dtype == gdt_f32;

@@ -239,6 +239,27 @@ packed_operand lowering::pack_deform_offsets(int w_off, int b_off, int w_mod, in
     return p;
 }
 
+// the depthwise conv's operand: f16 [k * k][C], tap = ky * k + kx, from either stored form -- [C, 1, kw, kh] (channel fastest: the rows as they
+// are) or [1, kw, kh, C] (a depthwise OIHW kernel listed in conv2d_weights: channel slowest)
+void* lowering::pack_depthwise(int wt, int C, int k) {
+    graph_node const& w = g.nodes[wt];
+    const bool channel_first = w.ne[0] == C && w.ne[1] == 1;
+    return cached(wt, role_depthwise, [&](bool st) {
+        std::vector<uint16_t> h((size_t)k * k * C);
+        for (int tap = 0; tap < k * k; ++tap)
+            for (int c = 0; c < C; ++c) h[(size_t)tap * C + c] = f32_to_f16(w.values()[channel_first ? (size_t)tap * C + c : (size_t)c * k * k + tap]);
+        return upload(h.data(), h.size() * 2, st);
+    });
+}
+// conv [3, kw, kh, Cout] on 8-channel value | residue pixels (image_pad8): every tap's three columns repeated on channels 3..5, zeros on 6..7, so the f32
+// accumulator adds w * hi + w * lo = w * (the f32 pixel up to the residue's own rounding)
+packed_operand lowering::pack_image8(int wt, int bias_t, int n) {
+    graph_node const& w = g.nodes[wt];
+    const int k3 = (int)(w.n_elements() / n), taps = k3 / 3;
+    const float* h = w.values();
+    return pack_matrix(wt, role_image8, n, taps * 8, [h, k3](int r, int c) { return c % 8 < 6 ? h[(size_t)r * k3 + (c / 8) * 3 + (c % 8) % 3] : 0.0f; }, bias_t, n);
+}
+
 float* lowering::vec_cached(int key_node, pack_role role, std::string const& with, std::function<std::vector<float>()> make_host) {
     return static_cast<float*>(cached(key_node, role, [&](bool st) { std::vector<float> v = make_host(); return upload(v.data(), v.size() * 4, st); }, with));
 }

@@ -59,6 +59,7 @@ struct lowering {
     std::map<int, std::pair<int, int>> placed;        // node a concat chain will read -> (buffer, first plane) reserved for it
     std::map<int, int> up2_of;                        // interpolate(NEAREST, x2) node -> its (planar) source, resized by the reading conv's loader
     std::map<int, int> image_plane;                   // f32 image input -> buffer of its value | residue plane
+    std::map<int, int> image8;                        // 3-channel f32 image -> buffer of its 8-channel value | residue pixels (image_pad8)
 
     // ---- attention and the encoder chain (lower_encoder.cpp)
     std::map<int, int> qkv_first;                 // first of the three linears (node order) -> attention node
@@ -150,6 +151,8 @@ struct lowering {
     void* pack_rcu(int wt, int taps);
     void* pack_deform(int wt, int* n_pad);
     packed_operand pack_deform_offsets(int w_off, int b_off, int w_mod, int b_mod);
+    void* pack_depthwise(int wt, int C, int k);
+    packed_operand pack_image8(int wt, int bias_t, int n);
 
     // ---- lower_conv.cpp
     // What a product's launch takes over from the nodes behind it: [* LayerScale] [gelu | relu | leaky_relu] [(* s1) + res] [(* s2) + res2].
@@ -189,6 +192,8 @@ struct lowering {
     void find_deform_groups();
     void deform_conv(int t);
     void deform_fused(int t, deform_group const& G);
+    int image_pad8(int xs);
+    void depthwise_conv(int t);
 
     // ---- lower_encoder.cpp
     void find_qkv_groups();
@@ -196,6 +201,13 @@ struct lowering {
     std::array<int, 3> heads_major(graph_node const& n, float q_scale);
     void attention(int t);
     void attention_masked(int t);
+    // split_qkv(.., 1) of nn.cpp:182-208 feeding a masked attention at head_dim 32 with a constant per-head bias (mobile-sam.cpp:124-132):
+    // linear -> reshape -> permute(0, 3, 1, 2) -> cont -> 3 x (slice -> reshape) -> attention_masked
+    struct window_group { int lin = -1; std::vector<int> views; }; // the q|k|v linear; the nodes between it and the attention, computed by nobody
+    std::map<int, window_group> window_groups;      // attention_masked node -> its group (g.fused_models)
+    bool match_window_group(int att, window_group& G) const;
+    void find_window_groups();
+    void window_attention(int t, window_group const& G);
     void patch_embed(int t);
     bool match_layer(int att, enc_layer& L) const;
     void find_encoder_chain();

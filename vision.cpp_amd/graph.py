@@ -21,7 +21,7 @@ from ._lib import check, get_lib
 F32, F16, U8, I32 = 0, 1, 24, 26
 (OP_LINEAR, OP_LAYER_NORM, OP_GELU, OP_RELU, OP_SCALE, OP_ADD, OP_MUL, OP_CONV_2D, OP_CONV_TRANSPOSE_2D, OP_INTERPOLATE, OP_ATTENTION,
  OP_CONCAT, OP_SLICE, OP_RESHAPE, OP_REPEAT, OP_PATCH_EMBED, OP_CONT, OP_IMAGE_U8_TO_F32, OP_IMAGE_NORMALIZE, OP_LEAKY_RELU,
- OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED, OP_CONV_2D_DEFORM, OP_SIGMOID, OP_MEAN_2D) = range(2, 31)
+ OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED, OP_CONV_2D_DEFORM, OP_SIGMOID, OP_MEAN_2D, OP_CONV_2D_DEPTHWISE) = range(2, 32)
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
 
@@ -235,6 +235,14 @@ def conv_2d(m: ModelRef, x: Tensor, stride: int = 1, pad: int = 0) -> Tensor:  #
     if (b := m.find("bias")) is not None:
         src.append(b)
     return m.graph.op(OP_CONV_2D, src, [stride, pad])
+
+
+def conv_2d_depthwise(m: ModelRef, x: Tensor, stride: int = 1, pad: int = 0) -> Tensor:  # nn.cpp:102-115
+    """weight [C, 1, kw, kh] (written NHWC: TinyViT's local_conv) or [1, kw, kh, C] (a depthwise OIHW kernel listed in conv2d_weights)."""
+    src = [x, m.weights("weight")]
+    if (b := m.find("bias")) is not None:
+        src.append(b)
+    return m.graph.op(OP_CONV_2D_DEPTHWISE, src, [stride, pad])
 
 
 def conv_transpose_2d(m: ModelRef, x: Tensor, stride: int) -> Tensor:  # nn.cpp:117-129
@@ -669,3 +677,131 @@ def birefnet_basic_decoder_block(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.
     x = birefnet_aspp_deformable(m["dec_att"], x)
     x = birefnet_conv_2d_batch_norm(m["conv_out"], x, 1, 1)
     return named(m, x)
+
+
+# ---- TinyViT (the MobileSAM image encoder) against this layer (the structure of src/visp/arch/mobile-sam.cpp:15-208) ---------------------------
+# Written after the branch WITHOUT model_build_flag::window_partition (ggml_win_part is not an op here). Where it departs from the reference: the
+# literal 64 of mobile-sam.cpp:195 is the last layer's resolution (a small configuration can be built), the two GGML_ASSERTs of tiny_vit_block are
+# exceptions, window_reverse takes the batch from the window count (the reference reads ne[3] of a 3-D tensor: batch 1 only), and patch_merging
+# reads its width from conv1's output instead of from dimension 0 of the depthwise kernel (which is 1 in the [1, kw, kh, C] form).
+
+def sam_conv_2d_batch_norm(m: ModelRef, x: Tensor, stride: int = 1, pad: int = 0) -> Tensor:  # mobile-sam.cpp:15-18
+    return conv_2d(m["c"], x, stride, pad)  # batch_norm is fused into conv_2d at model conversion
+
+
+def sam_conv_2d_depthwise_batch_norm(m: ModelRef, x: Tensor, stride: int = 1, pad: int = 0) -> Tensor:  # mobile-sam.cpp:20-23
+    return conv_2d_depthwise(m["c"], x, stride, pad)
+
+
+def sam_window_partition(m: ModelRef, x: Tensor, window: int) -> Tensor:  # mobile-sam.cpp:25-44
+    c, w, h, b = x.ne
+    px, py = (window - w % window) % window, (window - h % window) % window
+    npw, nph = (w + px) // window, (h + py) // window
+    if px > 0 or py > 0:
+        x = pad(m, x, 0, px, py, 0)
+    x = reshape(m, x, c * window, npw, window, nph * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    return reshape(m, x, c, window * window, npw * nph * b)
+
+
+def sam_window_reverse(m: ModelRef, x: Tensor, w: int, h: int, window: int) -> Tensor:  # mobile-sam.cpp:46-65
+    c = x.ne[0]
+    px, py = (window - w % window) % window, (window - h % window) % window
+    npw, nph = (w + px) // window, (h + py) // window
+    b = x.ne[2] // (npw * nph)
+    x = reshape(m, x, c * window, window, npw, nph * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    x = reshape(m, x, c, w + px, h + py, b)
+    x = slice_(m, x, SLICE_ALL, (0, w), (0, h))
+    return cont(m, x)
+
+
+def tinyvit_patch_embed(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:71-76; x = the normalised f32 image [3, W, H, N]
+    x = sam_conv_2d_batch_norm(m["seq.0"], x, 2, 1)
+    x = gelu(m, x)
+    x = sam_conv_2d_batch_norm(m["seq.2"], x, 2, 1)
+    return named(m, x)
+
+
+def tinyvit_mb_conv(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:78-92
+    shortcut = x
+    x = gelu(m, sam_conv_2d_batch_norm(m["conv1"], x))
+    x = gelu(m, sam_conv_2d_depthwise_batch_norm(m["conv2"], x, 1, 1))
+    x = sam_conv_2d_batch_norm(m["conv3"], x)
+    x = gelu(m, add(m, x, shortcut))
+    return named(m, x)
+
+
+def tinyvit_patch_merging(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:94-113
+    x = gelu(m, sam_conv_2d_batch_norm(m["conv1"], x))
+    c_out = x.ne[0]
+    stride = 1 if c_out in (320, 448, 576) else 2
+    x = gelu(m, sam_conv_2d_depthwise_batch_norm(m["conv2"], x, stride, 1))
+    c, w, h, b = x.ne
+    x = sam_conv_2d_batch_norm(m["conv3"], x)
+    return named(m, reshape(m, x, c, w * h, b))  # always [c, wh, b]
+
+
+def tinyvit_mlp(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:115-122
+    x = layer_norm(m["norm"], x)
+    x = gelu(m, linear(m["fc1"], x))
+    return named(m, linear(m["fc2"], x))
+
+
+def tinyvit_attention_rel_bias(m: ModelRef, x: Tensor, dim: int, n_heads: int) -> Tensor:  # mobile-sam.cpp:124-132
+    scale_ = 1.0 / math.sqrt(float(dim // n_heads))
+    mask = m.weights("attention_biases_indexed")  # [T, T, heads, 1]
+    x = layer_norm(m["norm"], x)
+    q, k, v = split_qkv(m["qkv"], x, n_heads, 1)
+    return attention(m, q, k, v, mask, scale_, m["proj"])
+
+
+def tinyvit_block(m: ModelRef, x: Tensor, input_resolution: int, dim: int, num_heads: int, window_size: int) -> Tensor:  # mobile-sam.cpp:134-161
+    h = w = input_resolution
+    c, spatial, b, _ = x.ne
+    if spatial != h * w:
+        raise ValueError(f"tinyvit_block: {spatial} tokens do not form a {w}x{h} map")
+    if h == window_size or w == window_size:
+        raise ValueError(f"tinyvit_block: a {w}x{h} map that is one {window_size}x{window_size} window is not built (the reference asserts the same)")
+    res_x = x
+    x = reshape(m, x, c, w, h, b)
+    x = sam_window_partition(m, x, window_size)
+    x = tinyvit_attention_rel_bias(m["attn"], x, dim, num_heads)
+    x = sam_window_reverse(m, x, w, h, window_size)
+    x = reshape(m, x, c, spatial, b)
+    x = add(m, x, res_x)
+    x = reshape(m, x, c, w, h, b)
+    x = sam_conv_2d_depthwise_batch_norm(m["local_conv"], x, 1, 1)  # (its kernel is stored NHWC whatever the file's layout: [C, 1, kw, kh])
+    x = reshape(m, x, c, spatial, b)
+    x = add(m, x, tinyvit_mlp(m["mlp"], x))
+    return named(m, x)
+
+
+def tinyvit_conv_layer(m: ModelRef, x: Tensor, layer) -> Tensor:  # mobile-sam.cpp:163-170; layer = (resolution, dim, depth, heads, window, downsample)
+    for i in range(layer[2]):
+        x = tinyvit_mb_conv(m["blocks"][i], x)
+    x = tinyvit_patch_merging(m["downsample"], x)
+    return named(m, x)
+
+
+def tinyvit_basic_layer(m: ModelRef, x: Tensor, layer) -> Tensor:  # mobile-sam.cpp:172-183
+    resolution, dim, depth, heads, window, downsample = layer
+    for i in range(depth):
+        x = tinyvit_block(m["blocks"][i], x, resolution, dim, heads, window)
+    if downsample:
+        x = reshape(m, x, x.ne[0], resolution, resolution, x.ne[2])
+        x = tinyvit_patch_merging(m["downsample"], x)
+    return named(m, x)
+
+
+def tinyvit_encode(m: ModelRef, x: Tensor, layers) -> Tensor:  # mobile-sam.cpp:185-208; layers as synth.TinyVitConfig.layers() gives them
+    x = tinyvit_patch_embed(m["patch_embed"], x)
+    x = tinyvit_conv_layer(m["layers.0"], x, layers[0])
+    for i in range(1, len(layers)):
+        x = tinyvit_basic_layer(m["layers"][i], x, layers[i])
+    res = layers[-1][0]
+    x = reshape(m, x, x.ne[0], res, res, x.ne[2])
+    x = conv_2d(m["neck.0"], x)
+    x = layer_norm(m["neck.1"], x)
+    x = conv_2d(m["neck.2"], x, 1, 1)
+    return layer_norm(m["neck.3"], x)

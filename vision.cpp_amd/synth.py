@@ -307,6 +307,9 @@ class TinyVitConfig:
 
 
 TINYVIT_5M = TinyVitConfig()
+# the smallest TinyViT that still walks every path of the encoder: maps 64 / 32 / 16 / 16, every windowed stage pads its windows (32 -> 35, 16 -> 28,
+# 16 -> 21), window lengths 49 and 196, head_dim 32 throughout, and a last merging of stride 1 (width 320, mobile-sam.cpp:100)
+TINYVIT_MINI = TinyVitConfig(img_size=256, embed_dims=(32, 64, 96, 320), depths=(1, 1, 2, 1), num_heads=(1, 2, 3, 10), window_sizes=(7, 7, 14, 7), name="mini")
 
 
 def attention_bias_idxs(ws: int) -> np.ndarray:
