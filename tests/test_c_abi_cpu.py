@@ -9,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from visioncpp_amd import _cdecl
 from visioncpp_amd import _lib as L
 from visioncpp_amd import gguf, synth
 
@@ -26,6 +27,9 @@ def test_library_exports_every_declared_symbol():
     for sym in sorted(declared):
         assert hasattr(api, sym), f"{sym} declared in include/ but not exported"
     assert declared <= set(L.C_API_SYMBOLS + L.KERNEL_SYMBOLS), declared - set(L.C_API_SYMBOLS + L.KERNEL_SYMBOLS)
+    # the bindings are derived by _cdecl's reader: this regular expression is the independent count of what it must have found
+    assert declared == set(L.C_API_SYMBOLS + L.KERNEL_SYMBOLS), declared ^ set(L.C_API_SYMBOLS + L.KERNEL_SYMBOLS)
+    assert len(L.C_API_SYMBOLS + L.KERNEL_SYMBOLS) == len(declared)  # and no name twice
 
 
 def test_reference_symbol_set_is_complete():
@@ -167,30 +171,102 @@ def test_esrgan_converter_accepts_both_key_layouts(tmp_path):
         convert.convert_esrgan({"foo.weight": np.zeros(3, np.float32)}, tmp_path / "x.gguf")
 
 
-def test_ctypes_structs_match_the_c_headers(tmp_path):
-    """The Python mirrors of the argument blocks must have the C layout: compile a probe against include/*.h with gcc
-    and compare sizeof / offsetof of the last field (catches a field added on one side only)."""
+def _layout_by_gcc(include_dir, structs, tmp_path):
+    """{"struct": "sizeof", "struct.field": "offsetof,sizeof"} of `structs` {C name: field names}, printed by a C probe compiled against include_dir."""
     import subprocess
 
-    root = Path(__file__).resolve().parents[1]
+    lines = []
+    for cname, fields in structs.items():
+        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    printf("{cname}.{f} %zu,%zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f in fields]
     probe = tmp_path / "probe.c"
-    probe.write_text('''
-#include <stddef.h>
-#include <stdio.h>
-#include "visp_hip_kernels.h"
-#include "visp_c_api.h"
-int main(void) {
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vx_gemm_args), offsetof(vx_gemm_args, debug_stamps), sizeof(vx_dconv_args),
-           offsetof(vx_dconv_args, stamps), sizeof(vx_tile_layout), sizeof(visp_image_view), sizeof(visp_timing), sizeof(visp_esrgan_info));
-    return 0;
-}
-''')
+    probe.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "visp_hip_kernels.h"\n#include "visp_c_api.h"\n'
+                     "int main(void) {\n" + "\n".join(lines) + "\n    return 0;\n}\n")
     exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-I", str(root / "include"), str(probe), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    want = [C.sizeof(L.GemmArgs), L.GemmArgs.debug_stamps.offset, C.sizeof(L.DconvArgs), L.DconvArgs.stamps.offset, C.sizeof(L.TileLayout),
-            C.sizeof(L.ImageView), C.sizeof(L.Timing), C.sizeof(L.EsrganInfo)]
-    assert got == want, (got, want)
+    subprocess.run(["gcc", "-I", str(include_dir), str(probe), "-o", str(exe)], check=True)
+    return dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+
+
+def test_ctypes_structs_match_the_c_headers(tmp_path):
+    """The ctypes structures must have the C layout. They are derived from the headers by _cdecl's reader, so the judge is gcc: a
+    probe generated from the parsed field names prints sizeof of every struct and offsetof / sizeof of every field, compiled against
+    include/*.h, and the output is compared with the ctypes classes (catches a misread, reordered or dropped field anywhere)."""
+    structs = {cname: [name for _, _, _, name, _ in fields] for cname, fields in (*L.C_API_DECLS.structs.items(), *L.KERNEL_DECLS.structs.items())}
+    assert set(structs) == set(L.STRUCT_NAMES) and len(structs) == 15
+    got = _layout_by_gcc(ROOT / "include", structs, tmp_path)
+    want = {}
+    for cname, fields in structs.items():
+        cls = getattr(L, L.STRUCT_NAMES[cname])
+        assert cls is L.STRUCTS[cname] and [n for n, _ in cls._fields_] == [f + "_" * (f == "lambda") for f in fields]
+        want[cname] = str(C.sizeof(cls))
+        want.update({f"{cname}.{f}": f"{getattr(cls, n).offset},{getattr(cls, n).size}" for f, (n, _) in zip(fields, cls._fields_)})
+    assert len(want) == 15 + sum(len(f) for f in structs.values()) > 200
+    assert got == want, {k: (got.get(k), want.get(k)) for k in got.keys() | want.keys() if got.get(k) != want.get(k)}
+    # field types where size and offset cannot tell: arrays, and the keyword field
+    assert L.Timing.name.size == 32 and L.DepthAnyInfo.feature_layers.size == 16 and L.MiganInfo.channels.size == 36
+    assert dict(L.GemmArgs._fields_)["lambda_"] is C.c_void_p and dict(L.GemmArgs._fields_)["q_scale"] is C.c_float
+    assert dict(L.GemmArgs._fields_)["lda"] is C.c_int64 and dict(L.Timing._fields_)["flops"] is C.c_double
+
+
+def test_prototypes_are_derived_from_the_declarations():
+    """Exact argtypes / restype for one declaration of each construct the reader handles (the mapping of _cdecl.ctype)."""
+    api = L.get_lib()
+    P, vp, cp, i32, i64, f32 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_float
+    for name, argtypes, restype in [
+        ("visp_weights_add", [vp, cp, i32, vp, vp], i32),                            # array parameter `int64_t const ne[4]`
+        ("visp_yolov9t_last_split", [vp, vp], i32),                                  # array parameter `float out_ms[3]`
+        ("visp_depthany_compute_sharded", [vp, i32, vp, i32, i32, i32, vp], i32),    # `visp_model* const*`
+        ("visp_device_init", [i32, vp], i32),                                        # pointer to pointer
+        ("vx_gemm_f16", [P(L.GemmArgs), vp], C.c_int),                               # struct pointer
+        ("visp_yolov9t_nms", [vp, vp, i32, i32, P(L.Yolov9tNmsParams), P(L.Detection), i32, vp], i32),
+        ("visp_file_get_string", [vp, cp, cp, i64, vp], i32),                        # `char const*` in, `char*` out
+        ("vx_device_info", [C.c_int, cp, C.c_int, cp, C.c_int, vp, vp, vp], C.c_int),  # ... and a declaration spanning lines
+        ("visp_get_last_error", [], cp),                                             # returns `char const*`, `(void)`
+        ("vx_window_attention_bias_bytes", [C.c_int, C.c_int], C.c_size_t),          # size_t return
+        ("vx_headconv_frag_bytes", [], C.c_size_t),
+        ("vx_attention_set_stamps", [vp], None),                                     # void return
+        ("visp_model_compute", [vp, i32, P(L.ImageView), i32, vp, i32, P(L.ImageView), vp], i32),  # three lines
+        ("visp_graph_input", [vp, i32, vp, cp, vp], i32),                            # comment inside the parameter list
+        ("vx_swin_attention_pack_bias", [vp, C.c_int, C.c_int, vp], C.c_int),        # comments inside the parameter list
+        ("vx_memcpy_h2d_async", [vp, vp, C.c_size_t, vp], C.c_int),                  # size_t parameter
+        ("vx_set_device", [C.c_int], C.c_int),
+        ("visp_yolov9t_scale_boxes", [P(L.Detection), i32, i32, i32, f32, f32, f32], i32),
+    ]:
+        fn = getattr(api, name)
+        assert (list(fn.argtypes), fn.restype) == (argtypes, restype), (name, fn.argtypes, fn.restype)
+    for name, (_, params) in (*L.C_API_DECLS.functions.items(), *L.KERNEL_DECLS.functions.items()):  # every declared function is bound, none by default
+        assert len(getattr(api, name).argtypes) == len(params), name
+    # enumerators: explicit and implicit values, named and anonymous enums
+    enums = L.C_API_DECLS.enums
+    assert enums["visp_backend_type"] == {"VISP_BACKEND_AUTO": 0, "VISP_BACKEND_CPU": 1, "VISP_BACKEND_GPU": 2, "VISP_BACKEND_VULKAN": 258}
+    assert enums["visp_model_family"]["VISP_FAMILY_COUNT"] == 5 and enums[""] == {"VISP_LOAD_DEFAULT": 0, "VISP_LOAD_NO_UPLOAD": 1}
+    assert (L.EPI_F16, L.EPI_PIXSHUF, L.EPI_SILU, L.DC_F16, L.DC_RGB_F32, L.DC_HEAD_F32) == (0, 6, 10, 0, 1, 2)
+    from visioncpp_amd import graph
+    assert (graph.OP_LINEAR, graph.OP_RELU, graph.OP_CONT, graph.OP_ATTENTION_MASKED, graph.OP_CONV_2D_DEPTHWISE) == (2, 5, 18, 27, 31)
+    assert L.C_API_DECLS.opaque >= {"visp_model", "visp_device", "visp_graph"}
+
+
+def test_the_declaration_reader_refuses_what_it_cannot_read():
+    """_cdecl.parse is strict: a declaration it does not understand completely is an error that quotes the text, never skipped."""
+    ok = "typedef struct { int a, b; float* p; char name[8]; } vx_t;\nVX_API int vx_f(const vx_t* t, int64_t const ne[4]);\n"
+    d = _cdecl.parse(ok)
+    assert [v[1:] for v in d.structs["vx_t"]] == [("int", "", "a", ""), ("int", "", "b", ""), ("float", "*", "p", ""), ("char", "", "name", "[8]")]
+    assert [v[1:] for v in d.functions["vx_f"][1]] == [("vx_t", "*", "t", ""), ("int64_t", " const", "ne", "[4]")] and d.functions["vx_f"][0][1:] == ("int", "", "", "")
+    for bad, quoted in [
+        ("VX_API int vx_f(half_t* x, int n);", "half_t* x"),                          # unknown base type
+        ("typedef struct { int a; unsigned b; } vx_t;", "unsigned b"),
+        ("VISP_API wchar_t const* visp_f(void);", "wchar_t const*"),
+        (ok + "typedef struct {\n    int a;\n    int b;\nVX_API int vx_g(void);\n", "typedef struct { int a; int b;"),  # unterminated struct
+        ("VX_API int vx_f(int a, int (*callback)(int));", "VX_API int vx_f(int a"),  # not the C the headers use
+        ("VX_API int vx_f(int a)\nVX_API int vx_g(void);", "VX_API int vx_f(int a)"),  # missing semicolon
+        ("enum vx_e { VX_A = 1 << 2 };", "VX_A = 1 << 2"),
+        ("int vx_f(int a);", "int vx_f(int a);"),                                     # not behind the API macro
+    ]:
+        with pytest.raises(_cdecl.DeclError) as e:
+            _cdecl.parse(bad)
+        assert quoted in str(e.value), (bad, str(e.value))
+    with pytest.raises(_cdecl.DeclError, match="vx_new_args"):  # a struct the bindings have no Python name for
+        _cdecl.structures(_cdecl.parse("typedef struct { int a; } vx_new_args;"), L.STRUCT_NAMES)
 
 
 def test_mobile_sam_gguf_is_detected_and_bias_packing_is_host_code(tmp_path):

@@ -19,9 +19,8 @@ from . import _lib as lib
 from ._lib import check, get_lib
 
 F32, F16, U8, I32 = 0, 1, 24, 26
-(OP_LINEAR, OP_LAYER_NORM, OP_GELU, OP_RELU, OP_SCALE, OP_ADD, OP_MUL, OP_CONV_2D, OP_CONV_TRANSPOSE_2D, OP_INTERPOLATE, OP_ATTENTION,
- OP_CONCAT, OP_SLICE, OP_RESHAPE, OP_REPEAT, OP_PATCH_EMBED, OP_CONT, OP_IMAGE_U8_TO_F32, OP_IMAGE_NORMALIZE, OP_LEAKY_RELU,
- OP_PERMUTE, OP_ROLL, OP_PAD, OP_GET_ROWS, OP_CAST, OP_ATTENTION_MASKED, OP_CONV_2D_DEFORM, OP_SIGMOID, OP_MEAN_2D, OP_CONV_2D_DEPTHWISE) = range(2, 32)
+# OP_LINEAR ... OP_CONV_2D_DEPTHWISE: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
+globals().update({k.removeprefix("VISP_"): v for k, v in lib.C_API_DECLS.enums["visp_graph_op"].items()})
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
 

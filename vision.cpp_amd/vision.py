@@ -487,6 +487,10 @@ DETECTION_DTYPE = np.dtype([("x1", np.float32), ("y1", np.float32), ("x2", np.fl
 assert DETECTION_DTYPE.itemsize == ctypes.sizeof(lib.Detection)
 
 
+def _dets_p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(lib.Detection))
+
+
 def _nms_params(conf=None, iou=None, max_det=None, max_nms=None, max_wh=None) -> lib.Yolov9tNmsParams:
     """visp_yolov9t_nms_defaults (conf 0.25, iou 0.45, max_det 300, max_nms 30000, max_wh 640) with the given fields replaced."""
     p = lib.Yolov9tNmsParams()
@@ -523,14 +527,14 @@ def yolov9t_nms(boxes: np.ndarray, scores: np.ndarray, **nms) -> np.ndarray:
     assert b.shape == (a, 4), (b.shape, s.shape)
     p = _nms_params(**nms)
     out, n = np.empty(p.max_det, DETECTION_DTYPE), c_int32()
-    check(get_lib().visp_yolov9t_nms(b.ctypes.data, s.ctypes.data, a, nc, byref(p), out.ctypes.data, p.max_det, byref(n)))
+    check(get_lib().visp_yolov9t_nms(b.ctypes.data, s.ctypes.data, a, nc, byref(p), _dets_p(out), p.max_det, byref(n)))
     return out[: n.value].copy()
 
 
 def yolov9t_scale_boxes(dets: np.ndarray, width: int, height: int, gain: float, pad_w: float, pad_h: float) -> np.ndarray:
     """scale_boxes (yolov9t.cpp:1255-1281) on the host: DETECTION_DTYPE boxes in letterbox pixels -> a copy in image pixels."""
     out = np.ascontiguousarray(dets, DETECTION_DTYPE).copy()
-    check(get_lib().visp_yolov9t_scale_boxes(out.ctypes.data, out.size, width, height, gain, pad_w, pad_h))
+    check(get_lib().visp_yolov9t_scale_boxes(_dets_p(out), out.size, width, height, gain, pad_w, pad_h))
     return out
 
 
@@ -559,7 +563,7 @@ class Yolov9t(Model):
         img, view = _image_view(image)
         p = _nms_params(**nms)
         out, n = np.empty(p.max_det, DETECTION_DTYPE), c_int32()
-        check(self._api.visp_yolov9t_detect(self._handle, byref(view), byref(p), out.ctypes.data, p.max_det, byref(n)))
+        check(self._api.visp_yolov9t_detect(self._handle, byref(view), byref(p), _dets_p(out), p.max_det, byref(n)))
         return out[: min(n.value, p.max_det)].copy()
 
     def detect_batch(self, images: np.ndarray, **nms) -> list[np.ndarray]:
@@ -569,14 +573,14 @@ class Yolov9t(Model):
         assert h == w, imgs.shape
         p = _nms_params(**nms)
         out, counts = np.empty((b, p.max_det), DETECTION_DTYPE), np.zeros(b, np.int32)
-        check(self._api.visp_yolov9t_detect_batch_host(self._handle, imgs.ctypes.data, c, b, h, byref(p), out.ctypes.data,
+        check(self._api.visp_yolov9t_detect_batch_host(self._handle, imgs.ctypes.data, c, b, h, byref(p), _dets_p(out),
                                                        counts.ctypes.data_as(ctypes.POINTER(c_int32))))
         return [out[i, : counts[i]].copy() for i in range(b)]
 
     def detect_batch_device(self, img_dev: int, channels: int, batch: int, size: int, stream: int | None = None, **nms) -> list[np.ndarray]:
         p = _nms_params(**nms)
         out, counts = np.empty((batch, p.max_det), DETECTION_DTYPE), np.zeros(batch, np.int32)
-        check(self._api.visp_yolov9t_detect_batch_device(self._handle, img_dev, channels, batch, size, byref(p), out.ctypes.data,
+        check(self._api.visp_yolov9t_detect_batch_device(self._handle, img_dev, channels, batch, size, byref(p), _dets_p(out),
                                                          counts.ctypes.data_as(ctypes.POINTER(c_int32)), stream))
         return [out[i, : counts[i]].copy() for i in range(batch)]
 
