@@ -74,6 +74,15 @@ inline tensor leaky_relu(model_ref const& m, tensor x, float negative_slope) { r
 inline tensor sigmoid(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SIGMOID, {x}); }
 // [C, W, H, N] -> [C, 1, 1, N] (mean_2d, birefnet.cpp:93-100; not ggml_mean, which reduces ne[0])
 inline tensor mean_2d(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_MEAN_2D, {x}); }
+// the ggml calls of yolov9t.cpp beyond the above
+inline tensor silu(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SILU, {x}); }
+inline tensor sub(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_SUB, {a, b}); } // a - b, b broadcast as for add
+// x [C, W, H, N]; kind 0 max, 1 average (ggml's values); kernel, stride and pad per dimension as ggml_pool_2d takes them
+inline tensor pool_2d(model_ref const& m, tensor x, int kind, int k0, int k1, int s0, int s1, int p0, int p1) { return detail::op(m, VISP_OP_POOL_2D, {x}, {kind, k0, k1, s0, s1, p0, p1}); }
+inline tensor soft_max(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SOFT_MAX, {x}); } // over dimension 0
+inline tensor sum_rows(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SUM_ROWS, {x}); } // [n, a, b, c] -> [1, a, b, c]
+// ggml_upscale: both extents times `factor` (NEAREST: the existing interpolate at mode 0)
+inline tensor upscale(model_ref const& m, tensor x, int factor, int32_t mode) { return interpolate(m, x, {x->ne[1] * factor, x->ne[2] * factor}, mode); }
 inline tensor cont(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_CONT, {x}); }
 inline tensor reshape_4d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2, int64_t n3) { return detail::op(m, VISP_OP_RESHAPE, {x}, {n0, n1, n2, n3}); }
 inline tensor reshape_3d(model_ref const& m, tensor x, int64_t n0, int64_t n1, int64_t n2) { return reshape_4d(m, x, n0, n1, n2, 1); }
@@ -151,6 +160,15 @@ inline tensor ggml_get_rows(model_ref const& m, tensor table, tensor index) { re
 inline tensor ggml_cast(model_ref const& m, tensor x, int32_t type) { return cast(m, x, type); }
 inline tensor ggml_gelu_inplace(model_ref const& m, tensor x) { return gelu(m, x); }
 inline tensor ggml_get_tensor(model_ref const& m, char const* name) { return get_tensor(m, name); }
+constexpr int GGML_OP_POOL_MAX = 0, GGML_OP_POOL_AVG = 1;
+inline tensor ggml_silu(model_ref const& m, tensor x) { return silu(m, x); }
+inline tensor ggml_silu_inplace(model_ref const& m, tensor x) { return silu(m, x); }
+inline tensor ggml_pool_2d(model_ref const& m, tensor x, int kind, int k0, int k1, int s0, int s1, int p0, int p1) { return pool_2d(m, x, kind, k0, k1, s0, s1, p0, p1); }
+inline tensor ggml_soft_max(model_ref const& m, tensor x) { return soft_max(m, x); }
+inline tensor ggml_sum_rows(model_ref const& m, tensor x) { return sum_rows(m, x); }
+inline tensor ggml_sub(model_ref const& m, tensor a, tensor b) { return sub(m, a, b); }
+inline tensor ggml_upscale(model_ref const& m, tensor x, int factor, int32_t mode) { return upscale(m, x, factor, mode); }
+inline tensor ggml_concat(model_ref const& m, tensor a, tensor b, int dim) { return concat(m, {a, b}, dim); }
 #endif
 
 } // namespace visp

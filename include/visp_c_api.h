@@ -361,7 +361,18 @@ enum visp_graph_op {
      * even kernels like odd ones (4x4 at pad 2 gives W + 1 columns). Built for kw == kh <= 7, pad <= k - 1, C % 8 == 0; anything else is refused when the node is
      * made. One launch (kernels_dwconv.hip); with the default fused models a gelu / leaky_relu that is its only reader joins it.
      *                                                                                                        nn.cpp:102-115, mobile-sam.cpp:20-23, migan.cpp:28-57 */
-    VISP_OP_CONV_2D_DEPTHWISE = 31
+    VISP_OP_CONV_2D_DEPTHWISE = 31,
+    /* the ggml calls of YOLOv9t (yolov9t.cpp) beyond nn.h. With the default fused models a silu that is the only reader of a conv_2d / linear is that launch's
+     * epilogue, silu(add(conv3x3(x), conv1x1(x))) is one 3x3 launch on folded weights, channel slices and channel concats of such maps are read and written
+     * in place, and slice -> reshape [n, 4, A, N] -> soft_max -> mul(c [n]) -> sum_rows is one launch. */
+    VISP_OP_SILU = 32,             /* x / (1 + exp(-x)), element-wise on f16 activations; folded on the host on constants          ggml_silu, yolov9t.cpp:124 */
+    /* x [C, W, H, N] f16; i0 kind (ggml's values: 0 max, 1 avg), i1, i2 kernel w, h, i3, i4 stride w, h, i5, i6 pad w, h -> [C, (W + 2 pad - k) / stride + 1, .., N],
+     * floor division. Max: positions outside the map never win. Built: square kernels 1..13, equal strides 1 or 2, pad <= k / 2, C % 8 == 0; average with
+     * pad > 0 is refused (the reference never builds it, and ggml's divisor there is a convention of its own).      ggml_pool_2d, yolov9t.cpp:171-177, 461 */
+    VISP_OP_POOL_2D = 33,
+    VISP_OP_SOFT_MAX = 34,         /* over dimension 0, the row maximum subtracted; ne[0] a multiple of 8, at most 1024             ggml_soft_max, yolov9t.cpp:681 */
+    VISP_OP_SUM_ROWS = 35,         /* [n, a, b, c] -> [1, a, b, c]: f32 sum in a fixed order                                        ggml_sum_rows, yolov9t.cpp:687 */
+    VISP_OP_SUB = 36               /* a - b, b broadcast as for ADD (the operands are not swapped)                                  ggml_sub, yolov9t.cpp:644 */
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

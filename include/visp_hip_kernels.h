@@ -452,9 +452,10 @@ VX_API int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[4], 
 VX_API int vx_roll_f16(const void* src, void* dst, const int64_t ne[4], const int64_t shift[4], void* stream);
 /* ggml_pad: src [src_ne] in the low corner of dst [dst_ne >= src_ne], zeros behind it; f16, contiguous */
 VX_API int vx_pad_f16(const void* src, void* dst, const int64_t src_ne[4], const int64_t dst_ne[4], void* stream);
-/* y[i] = a[i] (op) b[i mod b_period]; op 0 add, 1 mul; each operand f16 or f32 */
+/* y[i] = a[i] (op) b[i mod b_period]; op 0 add, 1 mul, 2 sub (a - b); each operand f16 or f32 */
 VX_API int vx_binary_rows(int op, const void* a, int a_f32, const void* b, int b_f32, int64_t b_period, void* y, int y_f32, int64_t n, void* stream);
-/* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s, 3 leaky ReLU x > 0 ? x : s x (ggml_leaky_relu, any slope); f16, 16-byte aligned */
+/* op 0 tanh-GELU (ggml_gelu), 1 ReLU, 2 x * s, 3 leaky ReLU x > 0 ? x : s x (ggml_leaky_relu, any slope), 4 SiLU x / (1 + exp(-x)) (ggml_silu);
+ * f16, 16-byte aligned */
 VX_API int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, void* stream);
 /* ggml_sigmoid: y f16 = 1 / (1 + exp(-x)); x f16, or f32 (x_f32: the map of a 1x1 convolution to one channel); 16-byte aligned */
 VX_API int vx_sigmoid_f16(const void* x, int x_f32, void* y, int64_t n, void* stream);
@@ -465,6 +466,8 @@ VX_API int vx_mean_2d_f16(const void* x, void* y, int B, int64_t n, int C, void*
 VX_API int vx_convert(const void* x, int x_f32, void* y, int y_f32, int64_t n, void* stream);
 /* ggml_interpolate(NEAREST) of an NHWC f16 map (ml.cpp:782-788; esrgan.cpp:15) */
 VX_API int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream);
+/* ... x and y pixels x_pix / y_pix elements apart (multiples of 8, >= C): an upsample that reads a channel slice and writes into a slice of a concat's buffer */
+VX_API int vx_nearest_pix_f16(const void* x, int64_t x_pix, void* y, int64_t y_pix, int B, int H, int W, int C, int OH, int OW, void* stream);
 /* f32 image [pixels][C <= 16] -> one 32-channel f16 plane: values, then what the f16 rounding dropped, then zeros (input of an image's first conv) */
 VX_API int vx_image_planes_f32(const float* x, void* y, int64_t n_pix, int C, void* stream);
 /* f32 image [pixels][3] -> f16 [pixels][8]: the values in channels 0..2, what the f16 rounding dropped in 3..5, zeros in 6..7 (the arithmetic of
@@ -476,6 +479,20 @@ VX_API int vx_image_pad8_f32(const float* x, void* y, int64_t n_pix, void* strea
  * 2 leaky ReLU with slope act_param. 16-byte aligned operands. */
 VX_API int vx_dwconv_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride, int pad, int act, float act_param,
                          void* stream);
+/* ---- pooling, row softmax and row sums (kernels_pool.hip; ggml_pool_2d, ggml_soft_max, ggml_sum_rows as yolov9t.cpp:165-185, 449-483, 657-691 use them) ----
+ * x f16 [B,H,W] pixels of x_pix elements, the C pooled channels first (x points at the slice's first channel); y f16 [B,OH,OW] pixels of y_pix elements,
+ * OH = (H + 2 pad - k) / stride + 1 (OW alike). kind 0 max (taken in f16: exact; positions outside the map never win), 1 average (f32 sum, one rounding;
+ * pad 0 only). k 1..13, stride 1 or 2, pad 0..k/2, C % 8 == 0, pixel strides multiples of 8 and >= C, 16-byte aligned operands. Channels of a y pixel
+ * beyond C are not touched. */
+VX_API int vx_pool2d_f16(const void* x, int64_t x_pix, void* y, int64_t y_pix, int B, int H, int W, int C, int kind, int k, int stride, int pad, void* stream);
+/* y[r, :n] = softmax(x[r, :n]) for rows of n f16 (n % 8 == 0, n <= 1024) x_ld / y_ld elements apart: f32 arithmetic, the row maximum subtracted */
+VX_API int vx_softmax_rows_f16(const void* x, int64_t x_ld, void* y, int64_t y_ld, int64_t rows, int n, void* stream);
+/* y f16 [rows][group]: y[r, g] = sum_i softmax(x[r, g n .. g n + n))_i * proj[i], proj f32 [n]; n % 8 == 0, n <= 64, x_ld >= group * n: the DFL decode
+ * (dfl_forward, yolov9t.cpp:657-691) on the box logits where they lie, inside rows of 64 + nc channels */
+VX_API int vx_softmax_expect_f16(const void* x, int64_t x_ld, int group, const float* proj, void* y, int64_t rows, int n, void* stream);
+/* y f16 [rows] = the sum of each row of n f16, f32, left to right (ggml_sum_rows). One thread per row with scalar loads: not a hot-path kernel (long rows are
+ * read uncoalesced); with fused models the one chain that uses it, the DFL decode, is vx_softmax_expect_f16 instead */
+VX_API int vx_sum_rows_f16(const void* x, void* y, int64_t rows, int n, void* stream);
 /* patch_embed's im2col (nn.cpp:166-180) on the f32 image tensor [B,H,W,C]: rows (b,py,px), k = (ky,kx,c), zero padded to Kp, f16 */
 /* 1x1 convolution to one channel: out f32 [M] = scale * act(sum_c x[m,c] w[c] + bias), x f16 [M][C] (depth-anything.cpp:91-95) */
 VX_API int vx_conv1x1_to1_f32(const void* x, const float* w, float bias, int relu, float scale, float* out, int64_t M, int C, void* stream);

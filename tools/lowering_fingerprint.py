@@ -89,6 +89,19 @@ def cases(tmp: Path):
                 g.output(out, "output")
                 return g
             yield f"tinyvit_{cfg.name}_b{batch}_{'fused' if fused else 'per_node'}", build
+    ypath = None
+    for size, batch in ((96, 2), (640, 1)):
+        for fused in (True, False):
+            def build(size=size, batch=batch, fused=fused):
+                nonlocal ypath
+                ypath = ypath or synth.write_yolov9t_gguf(tmp / "yolov9t.gguf", seed=1)
+                g = G.Graph(None, G.Weights(ypath))
+                g.set_fused_models(fused)
+                boxes, scores, raw, _ = G.yolov9t_forward(G.ModelRef(g), g.input((3, size, size, batch), G.F32, "image"))
+                for i, t in enumerate([boxes, scores, *raw]):
+                    g.output(t, f"out{i}")
+                return g
+            yield f"yolov9t_{size}_b{batch}_{'fused' if fused else 'per_node'}", build
 
 
 def device_cases(tmp: Path):

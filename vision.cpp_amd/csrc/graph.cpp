@@ -19,7 +19,8 @@ namespace {
 const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_norm", "gelu", "relu", "scale", "add", "mul", "conv_2d",
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
-                                         "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise"};
+                                         "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
+                                         "sum_rows", "sub"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -120,11 +121,15 @@ void fold_constant(graph& g, graph_node& n) {
             for (int64_t i = 0; i < total; ++i) out[i] = src(0).values()[i] * n.fp[0];
             break;
         case gop_add:
-        case gop_mul: {
+        case gop_mul:
+        case gop_sub: {
             const int64_t period = src(1).n_elements();
             const float *a = src(0).values(), *b = src(1).values();
-            for (int64_t i = 0; i < total; ++i) out[i] = n.op == gop_add ? a[i] + b[i % period] : a[i] * b[i % period];
+            for (int64_t i = 0; i < total; ++i) out[i] = n.op == gop_add ? a[i] + b[i % period] : (n.op == gop_mul ? a[i] * b[i % period] : a[i] - b[i % period]);
         } break;
+        case gop_silu:
+            for (int64_t i = 0; i < total; ++i) out[i] = (float)((double)src(0).values()[i] / (1.0 + std::exp(-(double)src(0).values()[i])));
+            break;
         case gop_slice: {
             host_view v{src(0).values(), src(0).ne};
             int64_t o = 0;
@@ -207,7 +212,8 @@ void fold_constant(graph& g, graph_node& n) {
 
 bool foldable(int32_t op) {
     return op == gop_reshape || op == gop_cont || op == gop_scale || op == gop_add || op == gop_mul || op == gop_slice || op == gop_repeat ||
-           op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid;
+           op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid ||
+           op == gop_silu || op == gop_sub;
 }
 
 void check_tensor(graph const& g, int t, const char* what) {
@@ -582,9 +588,44 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             n.ne[3] = 1;
         } break;
         case gop_sigmoid:
+        case gop_silu:
             need_src(1, 1);
             same_shape();
             break;
+        case gop_sub: // not commutative: the operands stay where they are, so the first one is the larger
+            need_src(2, 2);
+            broadcast_period(S(0).ne, S(1).ne, nm);
+            same_shape();
+            break;
+        case gop_soft_max:
+            need_src(1, 1);
+            if (S(0).ne[0] % 8 || S(0).ne[0] > 1024) throw except("soft_max: rows of %lld elements (a multiple of 8, at most 1024)", (long long)S(0).ne[0]);
+            same_shape();
+            break;
+        case gop_sum_rows:
+            need_src(1, 1);
+            same_shape();
+            n.ne[0] = 1;
+            break;
+        case gop_pool_2d: {
+            need_src(1, 1);
+            graph_node const& x = S(0);
+            const int64_t kind = n.ip[0], kw = n.ip[1], kh = n.ip[2], sw = n.ip[3], sh = n.ip[4], pw = n.ip[5], ph = n.ip[6], C = x.ne[0];
+            if (n_ip != 7) throw except("pool_2d: seven integer parameters (kind, kernel w h, stride w h, pad w h)");
+            if (kind != 0 && kind != 1) throw except("pool_2d: kind %lld (0 max, 1 average)", (long long)kind);
+            if (kw != kh) throw except("pool_2d: kernel %lldx%lld; square kernels only", (long long)kw, (long long)kh);
+            if (sw != sh) throw except("pool_2d: strides %lld and %lld; equal strides only", (long long)sw, (long long)sh);
+            if (sw != 1 && sw != 2) throw except("pool_2d: stride %lld is not built (1 and 2 are)", (long long)sw);
+            if (kw < 1 || kw > 13) throw except("pool_2d: kernel %lldx%lld; kernels 1x1 up to 13x13", (long long)kw, (long long)kh);
+            if (pw != ph || pw < 0 || pw > kw / 2) throw except("pool_2d: pad %lld, %lld with a %lldx%lld kernel (equal, 0 .. k / 2)", (long long)pw, (long long)ph, (long long)kw, (long long)kh);
+            if (kind == 1 && pw > 0) throw except("pool_2d: average pooling with pad %lld is not built (pad 0 is; the divisor at the border would be a convention)", (long long)pw);
+            if (C % 8) throw except("pool_2d: C = %lld must be a multiple of 8", (long long)C);
+            n.ne[0] = C;
+            n.ne[1] = x.ne[1] + 2 * pw - kw < 0 ? 0 : (x.ne[1] + 2 * pw - kw) / sw + 1;
+            n.ne[2] = x.ne[2] + 2 * pw - kh < 0 ? 0 : (x.ne[2] + 2 * pw - kh) / sw + 1;
+            n.ne[3] = x.ne[3];
+            if (n.ne[1] < 1 || n.ne[2] < 1) throw except("pool_2d: a %lldx%lld kernel at pad %lld does not fit the %lldx%lld input", (long long)kw, (long long)kh, (long long)pw, (long long)x.ne[1], (long long)x.ne[2]);
+        } break;
         case gop_mean_2d:
             need_src(1, 1);
             n.ne[0] = S(0).ne[0]; n.ne[1] = 1; n.ne[2] = 1; n.ne[3] = S(0).ne[3];

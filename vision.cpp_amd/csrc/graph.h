@@ -65,6 +65,12 @@ enum graph_op : int32_t {
     gop_mean_2d,          // x [C, W, H, N] -> [C, 1, 1, N]: the pixel mean, f32 sums in a fixed order   birefnet.cpp:93-100
     // the one nn.h function TinyViT (mobile-sam.cpp:15-208) and MI-GAN (migan.cpp:28-57) need beyond the above
     gop_conv_2d_depthwise,// x CWHN, w [C, 1, kw, kh] or [1, kw, kh, C], (b [C]); i0 = stride (1 | 2), i1 = pad   nn.cpp:102-115
+    // the ggml calls of YOLOv9t beyond nn.h (yolov9t.cpp:124, 171-177, 461, 644, 681, 687)
+    gop_silu,             // ggml_silu
+    gop_pool_2d,          // x CWHN; i0 = kind (0 max, 1 avg), i1 i2 = kernel, i3 i4 = stride, i5 i6 = pad   ggml_pool_2d
+    gop_soft_max,         // over ne[0], the row maximum subtracted           ggml_soft_max
+    gop_sum_rows,         // [n, a, b, c] -> [1, a, b, c]                      ggml_sum_rows
+    gop_sub,              // a - b, b broadcast as for add                     ggml_sub
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -131,6 +137,8 @@ enum pack_role : int {
     role_block_mlp_vec = 42, // block kernel: biases, lambdas and LN2 of the MLP half as one f32 vector
     role_block_qkv_vec = 43, // block kernel: LN1 and the q | k | v biases as one f32 vector
     role_tap_vec = 44,       // block kernel: the taps' final LayerNorm weight | bias
+    role_rep_conv = 45,      // GEMM operand of a RepConv: the 3x3 kernel with the 1x1 kernel added into its centre tap (keyed on the 3x3 kernel)
+    role_rep_conv_bias = 46, // ... and the two biases summed in f32, [N pad]
 };
 constexpr pack_role bias_of_role(pack_role r) { return static_cast<pack_role>(role_bias_base + r); }
 static_assert(bias_of_role(role_rows) == 18 && bias_of_role(role_qkv) == 20 && bias_of_role(role_dconv_ex) == 24 && role_bias_padded < role_bias_base,

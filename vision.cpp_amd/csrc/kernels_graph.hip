@@ -100,12 +100,12 @@ __global__ __launch_bounds__(256) void pad_kernel(const f16* __restrict__ src, f
 template <typename T>
 __device__ __forceinline__ float ld(const T* p, long i) { return (float)p[i]; }
 
-// y = a (op) b[i mod period]; f16 or f32 on every side
+// y = a (op) b[i mod period], op 0 add, 1 mul, 2 sub; f16 or f32 on every side
 template <int OP, typename TA, typename TB, typename TY>
 __global__ __launch_bounds__(256) void binary_kernel(const TA* __restrict__ a, const TB* __restrict__ b, long period, TY* __restrict__ y, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float av = ld(a, i), bv = ld(b, period == n ? i : i % period);
-        y[i] = (TY)f32_rounded(OP == 0 ? av + bv : av * bv);
+        y[i] = (TY)f32_rounded(OP == 0 ? av + bv : (OP == 1 ? av * bv : av - bv));
     }
 }
 // the common case: f16 (op) f16 -> f16, n and period multiples of 8
@@ -118,13 +118,17 @@ __global__ __launch_bounds__(256) void binary8_kernel(const f16* __restrict__ a,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float bv = (float)b[bo + j];
-            o[j] = (f16)f32_rounded(OP == 0 ? (float)av[j] + bv : (float)av[j] * bv);
+            o[j] = (f16)f32_rounded(OP == 0 ? (float)av[j] + bv : (OP == 1 ? (float)av[j] * bv : (float)av[j] - bv));
         }
         *reinterpret_cast<f16x8*>(y + i * 8) = o;
     }
 }
 
-// 0 gelu, 1 relu, 2 scale, 3 leaky relu (ggml_leaky_relu: x > 0 ? x : s x, for any slope)
+// 0 gelu, 1 relu, 2 scale, 3 leaky relu (ggml_leaky_relu: x > 0 ? x : s x, for any slope), 4 SiLU (ggml_silu)
+template <int OP>
+__device__ __forceinline__ float unary_of(float f, float s) {
+    return OP == 0 ? gelu_tanh(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : (OP == 4 ? silu(f) : f * s)));
+}
 template <int OP>
 __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n, float s) {
     const long n8 = n >> 3;
@@ -133,14 +137,14 @@ __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float f = (float)v[j];
-            v[j] = (f16)(OP == 0 ? gelu_tanh(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
+            v[j] = (f16)unary_of<OP>(f, s);
         }
         *reinterpret_cast<f16x8*>(y + i * 8) = v;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) { // tail
         const long i = (n8 << 3) + threadIdx.x;
         const float f = (float)x[i];
-        y[i] = (f16)(OP == 0 ? gelu_tanh(f) : (OP == 1 ? fmaxf(f, 0.0f) : (OP == 3 ? (f > 0.0f ? f : f * s) : f * s)));
+        y[i] = (f16)unary_of<OP>(f, s);
     }
 }
 
@@ -155,6 +159,20 @@ __global__ __launch_bounds__(256) void nearest_kernel(const f16* __restrict__ x,
         const long b = p / OH;
         const int iy = min((int)floorf((float)oy / sy), H - 1), ix = min((int)floorf((float)ox / sx), W - 1);
         *reinterpret_cast<f16x8*>(y + i * 8) = *reinterpret_cast<const f16x8*>(x + (((b * H + iy) * W + ix) * C8 + c) * 8);
+    }
+}
+
+// ... with pixel strides of its own on both sides: reads a channel slice of a wider map, writes into a slice of a concat's buffer (yolov9t.cpp:486-493 + 495-503)
+__global__ __launch_bounds__(256) void nearest_pix_kernel(const f16* __restrict__ x, long x_pix, f16* __restrict__ y, long y_pix, int H, int W, int C8, int OH, int OW, float sy, float sx, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C8);
+        long p = i / C8;
+        const int ox = (int)(p % OW);
+        p /= OW;
+        const int oy = (int)(p % OH);
+        const long b = p / OH;
+        const int iy = min((int)floorf((float)oy / sy), H - 1), ix = min((int)floorf((float)ox / sx), W - 1);
+        *reinterpret_cast<f16x8*>(y + ((b * OH + oy) * OW + ox) * y_pix + c * 8) = *reinterpret_cast<const f16x8*>(x + ((b * H + iy) * W + ix) * x_pix + c * 8);
     }
 }
 
@@ -381,8 +399,9 @@ static int launch_binary(const void* a, int a_f32, const void* b, int b_f32, int
 
 extern "C" int vx_binary_rows(int op, const void* a, int a_f32, const void* b, int b_f32, int64_t b_period, void* y, int y_f32, int64_t n, void* stream) {
     VX_REQUIRE(a && b && y && n > 0 && b_period > 0 && n % b_period == 0, "vx_binary_rows: bad operands (n = %ld, period = %ld)", (long)n, (long)b_period);
-    VX_REQUIRE(op == 0 || op == 1, "vx_binary_rows: op %d (0 add, 1 mul)", op);
+    VX_REQUIRE(op >= 0 && op <= 2, "vx_binary_rows: op %d (0 add, 1 mul, 2 sub)", op);
     if (op == 0) launch_binary<0>(a, a_f32, b, b_f32, b_period, y, y_f32, n, as_stream(stream));
+    else if (op == 2) launch_binary<2>(a, a_f32, b, b_f32, b_period, y, y_f32, n, as_stream(stream));
     else launch_binary<1>(a, a_f32, b, b_f32, b_period, y, y_f32, n, as_stream(stream));
     VX_LAUNCH_CHECK();
     return 1;
@@ -397,7 +416,8 @@ extern "C" int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, 
         case 1: hipLaunchKernelGGL(unary_kernel<1>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
         case 2: hipLaunchKernelGGL(unary_kernel<2>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
         case 3: hipLaunchKernelGGL(unary_kernel<3>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
-        default: VX_REQUIRE(false, "vx_unary_f16: op %d (0 gelu, 1 relu, 2 scale, 3 leaky relu)", op);
+        case 4: hipLaunchKernelGGL(unary_kernel<4>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
+        default: VX_REQUIRE(false, "vx_unary_f16: op %d (0 gelu, 1 relu, 2 scale, 3 leaky relu, 4 silu)", op);
     }
     VX_LAUNCH_CHECK();
     return 1;
@@ -423,6 +443,17 @@ extern "C" int vx_nearest_f16(const void* x, void* y, int B, int H, int W, int C
     VX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 8 == 0, "vx_nearest_f16: bad operands (C a multiple of 8)");
     const long n = (long)B * OH * OW * (C / 8);
     hipLaunchKernelGGL(nearest_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, H, W, C / 8, OH, OW, (float)OH / (float)H, (float)OW / (float)W, n);
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_nearest_pix_f16(const void* x, int64_t x_pix, void* y, int64_t y_pix, int B, int H, int W, int C, int OH, int OW, void* stream) {
+    VX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 8 == 0, "vx_nearest_pix_f16: bad operands (C a multiple of 8)");
+    VX_REQUIRE(x_pix >= C && y_pix >= C && x_pix % 8 == 0 && y_pix % 8 == 0 && aligned16(x) && aligned16(y), "vx_nearest_pix_f16: pixel strides %ld / %ld (multiples of 8, at least C = %d; operands 16-byte aligned)",
+               (long)x_pix, (long)y_pix, C);
+    const long n = (long)B * OH * OW * (C / 8);
+    hipLaunchKernelGGL(nearest_pix_kernel, dim3(grid_stride_blocks(n, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (long)x_pix, (f16*)y, (long)y_pix, H, W, C / 8, OH, OW,
+                       (float)OH / (float)H, (float)OW / (float)W, n);
     VX_LAUNCH_CHECK();
     return 1;
 }

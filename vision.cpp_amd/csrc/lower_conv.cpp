@@ -466,6 +466,7 @@ bool lowering::residual_unit(int t, std::string const& who) {
 
 void lowering::gemm_like(int t) {
     graph_node& n = g.nodes[t];
+    if (yolo_takes(t)) return yolo_product(t); // a SiLU group, a conv that reads or writes inside a wider map: never the LDS-ring kernels (lower_yolo.cpp)
     {
         std::string w0 = g.nodes[n.src[1]].op == gop_weight && !g.nodes[n.src[1]].name.empty() ? g.nodes[n.src[1]].name : n.name;
         if (n.op == gop_conv_2d && planar_conv(t, w0)) return;

@@ -50,6 +50,12 @@ void lowering::copy_op(int t) {
         if (x.constant) {
             void* cp = const_f16(n.src[i]);
             emit(d + " (constant)", {}, {obuf}, [=](void* st) { VX(vx_copy_strided_f16(cp, op() + off * 2, A.data(), S.data(), D.data(), 1.0f, st)); });
+        } else if (lives_in_place(n.src[i])) { // a channel slice read in its source, or a map that lives in another concat's buffer
+            const located L = locate(n.src[i]);
+            auto xp = ptr(L.buf);
+            const int64_t x_off = L.off;
+            std::array<int64_t, 4> SP{1, L.pix, L.pix * x.ne[1], L.pix * x.ne[1] * x.ne[2]};
+            emit(d, {L.buf}, {obuf}, [=](void* st) { VX(vx_copy_strided_f16(xp() + x_off * 2, op() + off * 2, A.data(), SP.data(), D.data(), 1.0f, st)); });
         } else {
             const int xbuf = buf_of(n.src[i]);
             auto xp = ptr(xbuf);
@@ -85,6 +91,7 @@ void lowering::run() {
     find_qkv_groups();
     find_window_groups();
     find_encoder_chain();
+    find_yolo_groups();
     for (int t = 0; t < N; ++t) {
         graph_node& n = g.nodes[t];
         if (enc.ok && t == enc.first) emit_encoder();
@@ -114,6 +121,9 @@ void lowering::run() {
             case gop_attention_masked: attention_masked(t); break;
             case gop_conv_2d_deform: deform_conv(t); break;
             case gop_conv_2d_depthwise: depthwise_conv(t); break;
+            case gop_pool_2d: pool_2d(t); break;
+            case gop_soft_max: soft_max(t); break;
+            case gop_sum_rows: sum_rows(t); break;
             case gop_sigmoid: {
                 const int64_t cnt = n.n_elements();
                 const int x_f32 = g.nodes[n.src[0]].dtype == gdt_f32;
@@ -167,20 +177,22 @@ void lowering::run() {
                 [[fallthrough]];
             case gop_gelu:
             case gop_leaky_relu:
+            case gop_silu:
             case gop_scale: {
                 if (n.dtype != gdt_f16) throw except("%s on the f32 map of a one-channel head that has other readers is not built", graph_op_name(n.op));
                 const int64_t cnt = n.n_elements();
-                const int uop = n.op == gop_gelu ? 0 : (n.op == gop_relu ? 1 : (n.op == gop_leaky_relu ? 3 : 2));
+                const int uop = n.op == gop_gelu ? 0 : (n.op == gop_relu ? 1 : (n.op == gop_leaky_relu ? 3 : (n.op == gop_silu ? 4 : 2)));
                 const float s = n.fp[0];
                 map_launch(t, std::string(graph_op_name(n.op)) + " n=" + std::to_string(cnt), [=](char* x, char* o, char*, void* st) { VX(vx_unary_f16(uop, x, o, cnt, s, st)); });
             } break;
             case gop_add:
-            case gop_mul: {
+            case gop_mul:
+            case gop_sub: {
                 graph_node const& b = g.nodes[n.src[1]];
                 if (g.nodes[n.src[0]].constant) throw except("%s: the larger operand is a constant; broadcast of an activation onto it is not built", graph_op_name(n.op));
                 const int abuf = buf_of(n.src[0]);
                 const int64_t period = b.n_elements(), cnt = n.n_elements();
-                const int bop = n.op == gop_add ? 0 : 1;
+                const int bop = n.op == gop_add ? 0 : (n.op == gop_mul ? 1 : 2);
                 std::vector<int> reads = {abuf};
                 std::function<char*()> bp;
                 float* bc = nullptr;
@@ -212,6 +224,7 @@ void lowering::run() {
                 if (!nearest && ((n.ip[2] & 255) != 1 || !(n.ip[2] & 256))) throw except("interpolate: mode %lld on activations is not built (bilinear | align_corners is; bicubic on constants)", (long long)n.ip[2]);
                 if (x.ne[0] % 8) throw except("interpolate: %lld channels (a multiple of 8)", (long long)x.ne[0]);
                 const int B = (int)x.ne[3], H = (int)x.ne[2], W = (int)x.ne[1], C = (int)x.ne[0], OH = (int)n.ne[2], OW = (int)n.ne[1];
+                if (nearest && g.fused_models && (lives_in_place(n.src[0]) || cat_slot.count(t))) { nearest_in_place(t); break; }
                 char d[128];
                 snprintf(d, sizeof d, "%s %dx%d -> %dx%d C=%d", nearest ? "nearest" : "bilinear_ac", W, H, OW, OH, C);
                 map_launch(t, d, [=](char* xp, char* o, char*, void* st) {
@@ -239,6 +252,7 @@ void lowering::run() {
                 tag("normalize", 0, (double)B * px * 12);
             } break;
             case gop_slice:
+                if (chan_slice.count(t)) break; // channels [c0, c1) only: its readers address it in its source (lower_yolo.cpp)
                 // rows [b, e) of every image's token block, read by one plain product only (dpt::neck drops the cls token, depth-anything.cpp:50):
                 // the GEMM's A rows are addressed in the source, no copy
                 if (g.fused_models && !n.is_output && plain_gemm_reader(t) >= 0 && n.ip[0] == 0 && n.ne[0] == g.nodes[n.src[0]].ne[0] && n.ne[0] % 64 == 0 && n.ip[5] == 1 &&
@@ -251,10 +265,14 @@ void lowering::run() {
                 copy_op(t);
                 break;
             case gop_concat:
+                if (cat_sources.count(t)) { concat_in_place(t); break; }
+                [[fallthrough]];
             case gop_repeat: copy_op(t); break;
             default: throw except("graph_allocate: %s is not lowered", graph_op_name(n.op));
         }
     }
+    for (auto const& sl : cat_slot)
+        if (!lives_in_place(sl.first)) throw except("graph: internal: the slice of concat %d reserved for tensor %d was never written", sl.second.first, sl.first);
     if (!placed.empty()) throw except("graph: internal: a plane reserved for tensor %d of a dense block was never written", placed.begin()->first);
     plan_arena();
 }

@@ -260,6 +260,35 @@ packed_operand lowering::pack_image8(int wt, int bias_t, int n) {
     return pack_matrix(wt, role_image8, n, taps * 8, [h, k3](int r, int c) { return c % 8 < 6 ? h[(size_t)r * k3 + (c / 8) * 3 + (c % 8) % 3] : 0.0f; }, bias_t, n);
 }
 
+// RepConv (yolov9t.cpp:256-300): conv3x3(x) + conv1x1(x) at the same stride is one 3x3 conv whose centre tap holds the 1x1 kernel as well. Rows [Cout][9 Cin],
+// k = (ky, kx, c); the sums are made in f32 before the one f16 rounding, the biases summed in f32
+packed_operand lowering::pack_rep_conv(int w3, int b3, int w1, int b1) {
+    graph_node const &a = g.nodes[w3], &b = g.nodes[w1];
+    const int n = (int)a.ne[3], cin = (int)a.ne[0], k = 9 * cin;
+    const std::string with = "+" + (b.op == gop_weight && !b.name.empty() ? b.name : "#" + std::to_string(w1));
+    packed_operand p;
+    p.n_real = n; p.k_real = k;
+    p.N = round_up(n, n > 64 ? 64 : 32);
+    p.K = round_up(k, 64);
+    p.w = cached(w3, role_rep_conv, [&](bool st) {
+        std::vector<uint16_t> h((size_t)p.N * p.K, 0);
+        for (int r = 0; r < n; ++r)
+            for (int c = 0; c < k; ++c) {
+                float v = a.values()[(size_t)r * k + c];
+                if (c / cin == 4) v += b.values()[(size_t)r * cin + c % cin];
+                h[(size_t)r * p.K + c] = f32_to_f16(v);
+            }
+        return upload(h.data(), h.size() * 2, st);
+    }, with);
+    if (b3 >= 0 || b1 >= 0)
+        p.bias = static_cast<float*>(cached(w3, role_rep_conv_bias, [&](bool st) {
+            std::vector<float> v((size_t)p.N, 0.0f);
+            for (int r = 0; r < n; ++r) v[r] = (b3 >= 0 ? g.nodes[b3].values()[r] : 0.0f) + (b1 >= 0 ? g.nodes[b1].values()[r] : 0.0f);
+            return upload(v.data(), v.size() * 4, st);
+        }, with));
+    return p;
+}
+
 float* lowering::vec_cached(int key_node, pack_role role, std::string const& with, std::function<std::vector<float>()> make_host) {
     return static_cast<float*>(cached(key_node, role, [&](bool st) { std::vector<float> v = make_host(); return upload(v.data(), v.size() * 4, st); }, with));
 }

@@ -3,6 +3,7 @@
 //   lower_weights.cpp  device images of weights and constants (cached / upload / pack_*)
 //   lower_conv.cpp     matrix products and convolutions with their fused epilogues, the planar maps, the DPT neck / head patterns
 //   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
+//   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
 // a `return false` leaves the lowering's state as it was.
@@ -212,6 +213,40 @@ struct lowering {
     bool match_layer(int att, enc_layer& L) const;
     void find_encoder_chain();
     void emit_encoder();
+
+    // ---- lower_yolo.cpp: the patterns of SiLU-conv / channel-split / channel-concat networks (yolov9t.cpp; all of it g.fused_models only)
+    struct located { int buf; int64_t off, pix; };  // a map inside a wider one: buffer, first channel, elements between pixels
+    // conv_2d / linear -> silu [-> add(map computed before)], or silu(add(conv3x3(x), conv1x1(x))) keyed on the 3x3 conv: one GEMM-family launch
+    struct silu_group { int silu = -1, add = -1, res = -1, rep1 = -1, rep_add = -1; };
+    std::map<int, silu_group> silu_convs;              // product node -> what its launch computes besides
+    std::map<int, int> rep_member;                     // the 1x1 conv of a folded RepConv -> its 3x3 conv
+    std::map<int, int> launch_of_last;                 // last node of a silu group -> its product node
+    std::map<int, std::pair<int, int>> chan_slice;     // slice of channels [c0, c1) only -> (source, c0): no launch, its readers address the source
+    struct cat_source { int node; int c0; bool placed; };
+    std::map<int, std::vector<cat_source>> cat_sources; // top concat of a dimension-0 chain with a placeable source -> its flattened sources
+    std::map<int, std::pair<int, int>> cat_slot;       // last node of a launch -> (top concat, first channel) it writes into
+    std::map<int, located> in_place;                   // node without a buffer of its own -> where it lives (set when its launch is emitted)
+    struct dfl_group { int map = -1, c0 = 0, n = 0, groups = 0, proj = -1; std::vector<int> absorbed; };
+    std::map<int, dfl_group> dfl_groups;               // sum_rows node -> slice -> [cont] -> reshape -> soft_max -> mul(constant) in front of it
+    bool channels_only(graph_node const& s) const;
+    std::vector<int> readers_through_conts(int t) const;
+    bool gemm_family_reader(int c, int view) const;
+    bool in_place_readers_ok(int t, std::vector<int> const& chain) const;
+    bool match_silu_group(int t, silu_group& G) const;
+    bool match_dfl_group(int t, dfl_group& G) const;
+    bool placeable_launch(int s) const;
+    void find_yolo_groups();
+    bool lives_in_place(int t) const;
+    located locate(int t);
+    located output_slot(int t, int last);
+    bool yolo_takes(int t) const;
+    void yolo_product(int t);
+    void pool_2d(int t);
+    void nearest_in_place(int t);
+    void concat_in_place(int t);
+    void soft_max(int t);
+    void sum_rows(int t);
+    packed_operand pack_rep_conv(int w3, int b3, int w1, int b1);
 
     // ---- lower_run.cpp
     void copy_op(int t);

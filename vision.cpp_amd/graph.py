@@ -19,7 +19,7 @@ from . import _lib as lib
 from ._lib import check, get_lib
 
 F32, F16, U8, I32 = 0, 1, 24, 26
-# OP_LINEAR ... OP_CONV_2D_DEPTHWISE: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
+# OP_LINEAR ... OP_SUB: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
 globals().update({k.removeprefix("VISP_"): v for k, v in lib.C_API_DECLS.enums["visp_graph_op"].items()})
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
@@ -335,6 +335,21 @@ def get_rows(m, table, index): return m.graph.op(OP_GET_ROWS, [table, index])  #
 def sigmoid(m, x): return m.graph.op(OP_SIGMOID, [x])  # ggml_sigmoid
 def mean_2d(m, x): return m.graph.op(OP_MEAN_2D, [x])  # birefnet.cpp:93-100: [C, W, H, N] -> [C, 1, 1, N] (not ggml_mean, which reduces ne[0])
 def cast(m, x, dtype): return m.graph.op(OP_CAST, [x], [dtype])  # ggml_cast
+def silu(m, x): return m.graph.op(OP_SILU, [x])  # ggml_silu
+def sub(m, a, b): return m.graph.op(OP_SUB, [a, b])  # ggml_sub: a - b, b broadcast as for add
+def soft_max(m, x): return m.graph.op(OP_SOFT_MAX, [x])  # ggml_soft_max: over dimension 0
+def sum_rows(m, x): return m.graph.op(OP_SUM_ROWS, [x])  # ggml_sum_rows: [n, a, b, c] -> [1, a, b, c]
+
+
+POOL_MAX, POOL_AVG = 0, 1  # ggml_op_pool
+
+
+def pool_2d(m, x, kind, k0, k1, s0, s1, p0, p1):  # ggml_pool_2d on a CWHN map
+    return m.graph.op(OP_POOL_2D, [x], [kind, k0, k1, s0, s1, p0, p1])
+
+
+def upscale(m, x, factor, mode):  # ggml_upscale: NEAREST is interpolate at mode 0
+    return interpolate(m, x, (x.ne[1] * factor, x.ne[2] * factor), mode)
 
 
 # ---- Depth-Anything-V2 against this layer (the structure of src/visp/arch/dino.cpp + depth-anything.cpp) -----------------------
@@ -804,3 +819,181 @@ def tinyvit_encode(m: ModelRef, x: Tensor, layers) -> Tensor:  # mobile-sam.cpp:
     x = layer_norm(m["neck.1"], x)
     x = conv_2d(m["neck.2"], x, 1, 1)
     return layer_norm(m["neck.3"], x)
+
+
+# ---- YOLOv9t against this layer (the structure of src/visp/arch/yolov9t.cpp) ------------------------------------------------------------------
+# Node for node, with `m` the model's root and tensor names as the reference builds them (BatchNorm is folded into the conv at conversion, so Conv's
+# batch_norm_2d branch has nothing to do). Four departures, because the reference's detect head holds for one image only:
+# reshape_2d keeps the batch ([C, w h, 1, N]); ggml_view_4d / ggml_dup are channel slices; sub(anchor_points, lt) is add(scale(lt, -1), anchors), since a
+# constant cannot be the larger operand; and the stride constant is [4, A] made on the host, since mul does not broadcast along dimension 0.
+
+YOLO_REG_MAX = 16
+
+
+def _yolo_at(m: ModelRef, name: str) -> ModelRef:
+    return m.with_prefix(m._full(name))
+
+
+def yolo_conv(m: ModelRef, x: Tensor, name: str, k: int, s: int = 1, act: bool = True) -> Tensor:  # yolov9t.cpp:78-130
+    """Conv: conv_2d at autopad k // 2 under `name` (".conv" appended when it is missing), then SiLU."""
+    x = conv_2d(_yolo_at(m, name if ".conv" in name else name + ".conv"), x, s, k // 2)
+    return silu(m, x) if act else x
+
+
+def yolo_aconv(m: ModelRef, x: Tensor, name: str) -> Tensor:  # yolov9t.cpp:165-185
+    pooled = pool_2d(m, x, POOL_AVG, 2, 2, 1, 1, 0, 0)
+    return yolo_conv(m, pooled, name + ".cv1.conv", 3, 2)
+
+
+def yolo_concat(m: ModelRef, tensors, dim: int = 0) -> Tensor:  # yolov9t.cpp:495-503 and yolo_concat: channels are dimension 0 of a CWHN map
+    return concat(m, list(tensors), dim)
+
+
+def yolo_upsample(m: ModelRef, x: Tensor, scale_factor: int = 2) -> Tensor:  # yolov9t.cpp:486-493
+    return upscale(m, x, scale_factor, SCALE_MODE_NEAREST)
+
+
+def yolo_elan1(m: ModelRef, x: Tensor, name: str, c1: int, c2: int, c3: int, c4: int) -> Tensor:  # yolov9t.cpp:187-234
+    assert c3 % 2 == 0, "ELAN1: c3 must be even for chunk(2)"
+    cv1 = yolo_conv(m, x, name + ".cv1.conv", 1)
+    split1 = slice_(m, cv1, (0, c3 // 2))
+    split2 = slice_(m, cv1, (c3 // 2, c3))
+    cv2 = yolo_conv(m, split2, name + ".cv2.conv", 3)
+    cv3 = yolo_conv(m, cv2, name + ".cv3.conv", 3)
+    cat = yolo_concat(m, [yolo_concat(m, [yolo_concat(m, [split1, split2]), cv2]), cv3])
+    return yolo_conv(m, cat, name + ".cv4.conv", 1)
+
+
+def yolo_rep_conv(m: ModelRef, x: Tensor, name: str, s: int = 1, act: bool = True) -> Tensor:  # yolov9t.cpp:256-300, the non-deploy branch (k = 3, p = 1)
+    out = add(m, yolo_conv(m, x, name + ".conv1.conv", 3, s, False), yolo_conv(m, x, name + ".conv2.conv", 1, s, False))
+    return silu(m, out) if act else out
+
+
+def yolo_rep_bottleneck(m: ModelRef, x: Tensor, name: str, c1: int, c2: int, shortcut: bool = True) -> Tensor:  # yolov9t.cpp:304-332
+    cv2 = yolo_conv(m, yolo_rep_conv(m, x, name + ".cv1"), name + ".cv2", 3)
+    return add(m, x, cv2) if shortcut and c1 == c2 else cv2
+
+
+def yolo_rep_csp(m: ModelRef, x: Tensor, name: str, c1: int, c2: int, n: int, shortcut: bool = True, e: float = 0.5) -> Tensor:  # yolov9t.cpp:370-402
+    c_ = int(c2 * e)
+    cv1 = yolo_conv(m, x, name + ".cv1", 1)
+    cv2 = yolo_conv(m, x, name + ".cv2", 1)
+    m_out = cv1
+    for i in range(n):
+        m_out = yolo_rep_bottleneck(m, m_out, f"{name}.m.{i}", c_, c_, shortcut)
+    return yolo_conv(m, cont(m, concat(m, [m_out, cv2], 0)), name + ".cv3", 1)
+
+
+def yolo_rep_ncsp_elan4(m: ModelRef, x: Tensor, name: str, c1: int, c2: int, c3: int, c4: int, n: int) -> Tensor:  # yolov9t.cpp:406-445
+    c = c3 // 2
+    cv1 = yolo_conv(m, x, name + ".cv1", 1)
+    h0 = slice_(m, cv1, (0, c))
+    h1 = slice_(m, cv1, (c, c3))
+
+    def rep_conv(x, name, c_in, c_out):
+        return yolo_conv(m, yolo_rep_csp(m, x, name + ".0", c_in, c_out, n), name + ".1", 3)
+
+    cv2 = rep_conv(h1, name + ".cv2", c3 // 2, c4)
+    cv3 = rep_conv(cv2, name + ".cv3", c4, c4)
+    return yolo_conv(m, yolo_concat(m, [h0, h1, cv2, cv3]), name + ".cv4", 1)
+
+
+def yolo_sppelan(m: ModelRef, x: Tensor, name: str, c1: int, c2: int, c3: int, k: int = 5) -> Tensor:  # yolov9t.cpp:449-483
+    cv1 = yolo_conv(m, x, name + ".cv1", 1)
+    cv2 = pool_2d(m, cv1, POOL_MAX, k, k, 1, 1, k // 2, k // 2)
+    cv3 = pool_2d(m, cv2, POOL_MAX, k, k, 1, 1, k // 2, k // 2)
+    cv4 = pool_2d(m, cv3, POOL_MAX, k, k, 1, 1, k // 2, k // 2)
+    return yolo_conv(m, cont(m, yolo_concat(m, [cv1, cv2, cv3, cv4])), name + ".cv5", 1)
+
+
+def yolov9t_backbone(m: ModelRef, x: Tensor) -> dict[int, Tensor]:  # yolov9t.cpp:507-628; x = the f32 image [3, S, S, N]
+    f: dict[int, Tensor] = {}
+    f[0] = yolo_conv(m, x, "model.0", 3, 2)
+    f[1] = yolo_conv(m, f[0], "model.1", 3, 2)
+    f[2] = yolo_elan1(m, f[1], "model.2", 32, 32, 32, 16)
+    f[3] = yolo_aconv(m, f[2], "model.3")
+    f[4] = yolo_rep_ncsp_elan4(m, f[3], "model.4", 64, 64, 64, 32, 3)
+    f[5] = yolo_aconv(m, f[4], "model.5")
+    f[6] = yolo_rep_ncsp_elan4(m, f[5], "model.6", 96, 96, 96, 48, 3)
+    f[7] = yolo_aconv(m, f[6], "model.7")
+    f[8] = yolo_rep_ncsp_elan4(m, f[7], "model.8", 128, 128, 128, 64, 3)
+    f[9] = yolo_sppelan(m, f[8], "model.9", 128, 128, 64, 5)
+    f[10] = yolo_upsample(m, f[9], 2)
+    f[11] = yolo_concat(m, [f[10], f[6]])
+    f[12] = yolo_rep_ncsp_elan4(m, f[11], "model.12", 224, 96, 96, 48, 3)
+    f[13] = yolo_upsample(m, f[12], 2)
+    f[14] = yolo_concat(m, [f[13], f[4]])
+    f[15] = yolo_rep_ncsp_elan4(m, f[14], "model.15", 160, 64, 64, 32, 3)
+    f[16] = yolo_aconv(m, f[15], "model.16")
+    f[17] = yolo_concat(m, [f[16], f[12]])
+    f[18] = yolo_rep_ncsp_elan4(m, f[17], "model.18", 144, 96, 96, 48, 3)
+    f[19] = yolo_aconv(m, f[18], "model.19")
+    f[20] = yolo_concat(m, [f[19], f[9]])
+    f[21] = yolo_rep_ncsp_elan4(m, f[20], "model.21", 192, 128, 128, 64, 3)
+    return f
+
+
+def yolo_dist2bbox(m: ModelRef, distance: Tensor, anchor_points: Tensor) -> Tensor:  # yolov9t.cpp:631-655, xyxy; distance [1, 4, A, N], anchors [2, A]
+    distance = cont(m, permute(m, cont(m, distance), 2, 0, 1, 3))  # [4, A, 1, N]
+    lt = slice_(m, distance, (0, 2))
+    rb = slice_(m, distance, (2, 4))
+    x1y1 = add(m, scale(m, lt, -1.0), anchor_points)  # anchor_points - lt
+    x2y2 = add(m, rb, anchor_points)
+    return concat(m, [x1y1, x2y2], 0)
+
+
+def yolo_dfl_forward(m: ModelRef, proj: Tensor, x: Tensor, reg_max: int) -> Tensor:  # yolov9t.cpp:657-691; x [4 reg_max, A, 1, N] -> [1, 4, A, N]
+    anchors, batch = x.ne[1] * x.ne[2], x.ne[3]
+    soft = soft_max(m, reshape(m, cont(m, x), reg_max, 4, anchors, batch))
+    return sum_rows(m, mul(m, soft, reshape(m, proj, reg_max, 1, 1, 1)))
+
+
+def yolo_make_anchors(levels, strides, offset: float = 0.5):  # yolov9t.cpp:875-925: (x + 0.5, y + 0.5) y-major per level, and each anchor's stride
+    pts, st = [], []
+    for (w, h), s in zip(levels, strides):
+        gy, gx = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        pts.append(np.stack([gx.ravel() + offset, gy.ravel() + offset], -1))
+        st.append(np.full(w * h, s))
+    return np.concatenate(pts).astype(np.float32), np.concatenate(st).astype(np.float32)
+
+
+def yolo_inference(m: ModelRef, raw, features, reg_max: int, nc: int):  # yolov9t.cpp:693-768 -> boxes [4, A, 1, N], scores [nc, A, 1, N]
+    g = m.graph
+    x_cat = yolo_concat(m, features, 1)  # [4 reg_max + nc, A, 1, N]
+    total = x_cat.ne[1]
+    anchors, strides = yolo_make_anchors([(r.ne[1], r.ne[2]) for r in raw], [8.0 * 2 ** i for i in range(len(raw))])
+    tag = "x".join(str(r.ne[1]) for r in raw)
+    anchor_points = g.get_tensor(f"anchor_points_{tag}") or g.add_weight(f"anchor_points_{tag}", anchors, F32)
+    stride_tensor = g.get_tensor(f"stride_points_{tag}") or g.add_weight(f"stride_points_{tag}", np.repeat(strides[:, None], 4, 1), F32)  # [4, A]
+    box = cont(m, slice_(m, x_cat, (0, reg_max * 4)))
+    cls = cont(m, slice_(m, x_cat, (reg_max * 4, reg_max * 4 + nc)))
+    proj = g.get_tensor("dfl_proj") or g.add_weight("dfl_proj", np.arange(reg_max, dtype=np.float32), F32)
+    dbox = yolo_dist2bbox(m, yolo_dfl_forward(m, proj, box, reg_max), anchor_points)
+    dbox = mul(m, dbox, stride_tensor)
+    assert dbox.ne[1] == total
+    return dbox, g.set_name(sigmoid(m, cls), "cls_prob")
+
+
+def yolo_detect_forward(m: ModelRef, features, ch, nc: int, training: bool = False):  # yolov9t.cpp:770-824
+    """-> (boxes, scores, raw maps); boxes and scores are None when `training` (the convs alone)."""
+    reg_max = YOLO_REG_MAX
+    raw, flat = [], []
+    for i, x in enumerate(features):
+        r = yolo_conv(m, yolo_conv(m, x, f"detect.cv2.{i}.0.conv", 3), f"detect.cv2.{i}.1.conv", 3)
+        r = conv_2d(_yolo_at(m, f"detect.cv2.{i}.2"), r, 1, 0)
+        c = yolo_conv(m, yolo_conv(m, x, f"detect.cv3.{i}.0.conv", 3), f"detect.cv3.{i}.1.conv", 3)
+        c = conv_2d(_yolo_at(m, f"detect.cv3.{i}.2"), c, 1, 0)
+        combined = yolo_concat(m, [r, c])
+        raw.append(combined)
+        flat.append(reshape(m, combined, combined.ne[0], combined.ne[1] * combined.ne[2], 1, combined.ne[3]))
+    if training:
+        return None, None, raw
+    boxes, scores = yolo_inference(m, raw, flat, reg_max, nc)
+    return boxes, scores, raw
+
+
+def yolov9t_forward(m: ModelRef, image: Tensor, nc: int = 80):  # yolov9t.cpp:827-840; image f32 [3, S, S, N]
+    """-> (boxes [4, A, 1, N] xyxy in pixels, scores [nc, A, 1, N], the per-level raw maps [64 + nc, S / s, S / s, N], the backbone's features by index)."""
+    f = yolov9t_backbone(m, image)
+    boxes, scores, raw = yolo_detect_forward(m, [f[15], f[18], f[21]], [64, 96, 128], nc)
+    return boxes, scores, raw, f
