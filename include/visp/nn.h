@@ -81,6 +81,8 @@ inline tensor sub(model_ref const& m, tensor a, tensor b) { return detail::op(m,
 inline tensor pool_2d(model_ref const& m, tensor x, int kind, int k0, int k1, int s0, int s1, int p0, int p1) { return detail::op(m, VISP_OP_POOL_2D, {x}, {kind, k0, k1, s0, s1, p0, p1}); }
 inline tensor soft_max(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SOFT_MAX, {x}); } // over dimension 0
 inline tensor sum_rows(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SUM_ROWS, {x}); } // [n, a, b, c] -> [1, a, b, c]
+// the ggml call of migan.cpp beyond the above: min(max(x, lo), hi) (migan.cpp:23); add / mul / sub also take a plane [1, W, H, 1] on [C, W, H, N] (migan.cpp:40, 76)
+inline tensor clamp(model_ref const& m, tensor x, float lo, float hi) { return detail::op(m, VISP_OP_CLAMP, {x}, {}, {lo, hi}); }
 // ggml_upscale: both extents times `factor` (NEAREST: the existing interpolate at mode 0)
 inline tensor upscale(model_ref const& m, tensor x, int factor, int32_t mode) { return interpolate(m, x, {x->ne[1] * factor, x->ne[2] * factor}, mode); }
 inline tensor cont(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_CONT, {x}); }
@@ -169,6 +171,8 @@ inline tensor ggml_sum_rows(model_ref const& m, tensor x) { return sum_rows(m, x
 inline tensor ggml_sub(model_ref const& m, tensor a, tensor b) { return sub(m, a, b); }
 inline tensor ggml_upscale(model_ref const& m, tensor x, int factor, int32_t mode) { return upscale(m, x, factor, mode); }
 inline tensor ggml_concat(model_ref const& m, tensor a, tensor b, int dim) { return concat(m, {a, b}, dim); }
+inline tensor ggml_clamp(model_ref const& m, tensor x, float lo, float hi) { return clamp(m, x, lo, hi); }
+inline tensor ggml_mul_inplace(model_ref const& m, tensor a, tensor b) { return mul(m, a, b); }
 #endif
 
 } // namespace visp

@@ -320,7 +320,7 @@ enum visp_graph_op {
     VISP_OP_LAYER_NORM = 3,        /* src x, w, b; f0 eps                                  nn.cpp:14-19 */
     VISP_OP_GELU = 4, VISP_OP_RELU = 5,
     VISP_OP_SCALE = 6,             /* f0 factor */
-    VISP_OP_ADD = 7, VISP_OP_MUL = 8, /* second operand broadcast over trailing dimensions */
+    VISP_OP_ADD = 7, VISP_OP_MUL = 8, /* second operand broadcast over trailing dimensions, or a plane [1, W, H, 1] on [C, W, H, N] */
     VISP_OP_CONV_2D = 9,           /* src x [C,W,H,N], w [Cin,kw,kh,Cout], (b); i0 stride, i1 pad        nn.cpp:72-100 */
     VISP_OP_CONV_TRANSPOSE_2D = 10,/* src x, w [kw,kh,Cout,Cin], (b); i0 stride (== kernel)               nn.cpp:117-129 */
     VISP_OP_INTERPOLATE = 11,      /* i0 w, i1 h, i2 mode: 1 bilinear, 2 bicubic, | 256 align_corners     ml.cpp:782-788 */
@@ -372,7 +372,13 @@ enum visp_graph_op {
     VISP_OP_POOL_2D = 33,
     VISP_OP_SOFT_MAX = 34,         /* over dimension 0, the row maximum subtracted; ne[0] a multiple of 8, at most 1024             ggml_soft_max, yolov9t.cpp:681 */
     VISP_OP_SUM_ROWS = 35,         /* [n, a, b, c] -> [1, a, b, c]: f32 sum in a fixed order                                        ggml_sum_rows, yolov9t.cpp:687 */
-    VISP_OP_SUB = 36               /* a - b, b broadcast as for ADD (the operands are not swapped)                                  ggml_sub, yolov9t.cpp:644 */
+    VISP_OP_SUB = 36,              /* a - b, b broadcast as for ADD (the operands are not swapped)                                  ggml_sub, yolov9t.cpp:644 */
+    /* the nodes of MI-GAN (migan.cpp) beyond the above. f0 lower bound, f1 upper bound: min(max(x, f0), f1) on f16 activations, folded on the host on
+     * constants; refused when f0 > f1 or a bound is not finite. ADD / MUL / SUB also take a second operand [1, W, H, 1] on a first operand [C, W, H, N] (one value
+     * per pixel, for every channel and image: migan.cpp:40, 76), and CONV_2D reads an f32 image of 4 channels as it reads one of 3. With the default fused
+     * models leaky_relu -> scale -> clamp joins the convolution in front of it, and interpolate(x2 NEAREST) -> mul(zero-insertion tile) -> depthwise 4x4 pad 2 ->
+     * slice -> cont is one polyphase FIR launch.                                          ggml_clamp, migan.cpp:23 */
+    VISP_OP_CLAMP = 37
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

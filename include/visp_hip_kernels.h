@@ -479,6 +479,24 @@ VX_API int vx_image_pad8_f32(const float* x, void* y, int64_t n_pix, void* strea
  * 2 leaky ReLU with slope act_param. 16-byte aligned operands. */
 VX_API int vx_dwconv_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride, int pad, int act, float act_param,
                          void* stream);
+/* ggml_clamp: y = x < lo ? lo : (x > hi ? hi : x) on f16 (a NaN stays one); lo <= hi, both finite; 16-byte aligned */
+VX_API int vx_clamp_f16(const void* x, void* y, int64_t n, float lo, float hi, void* stream);
+/* y[b, p, c] = a[b, p, c] (op) plane[p] for a f16 [B, HW, C], C % 8 == 0: one value per pixel for every channel and image (migan.cpp:40, 76).
+ * op 0 add, 1 mul, 2 sub; plane f16 or f32 (b_f32) [HW]; f32 arithmetic, one rounding; a and y 16-byte aligned */
+VX_API int vx_binary_plane_f16(int op, const void* a, const void* b, int b_f32, void* y, int B, int64_t HW, int C, void* stream);
+/* f32 image [pixels][4] -> f16 [pixels][8]: the values in channels 0..3, what the f16 rounding dropped in 4..7 (vx_image_pad8_f32 for 4 channels) */
+VX_API int vx_image4_pad8_f32(const float* x, void* y, int64_t n_pix, void* stream);
+/* ---- x2 FIR upsample and the depthwise conv with MI-GAN's activation (kernels_fir.hip; migan.cpp:17-26, 32-51) ----
+ * out[Y, X, c] = sum_{i,j} fir[i * 4 + j][c] z[Y + i - 2, X + j - 2, c] with z[2a, 2b] = x[a, b] and zero elsewhere and outside 2h x 2w: zero insertion, a 4x4
+ * depthwise FIR at pad 2, last row and column dropped, computed polyphase (each output parity reads 2 x 2 input pixels and 4 taps; no x2 intermediate).
+ * x f16 [B,h,w] pixels of x_pix elements, fir f16 [16][C], y f16 [B,2h,2w] pixels of y_pix elements; channels of a y pixel beyond C are not touched.
+ * Epilogue in f32 before the one f16 rounding: + plane[Y * 2w + X] (f32 [2h * 2w] or NULL); if agc: leaky ReLU 0.2, * gain, clamp to +-clamp (clamp 0: none);
+ * + res (f16 [B,2h,2w] pixels of res_pix elements, or NULL). C % 8 == 0, pixel strides multiples of 8 and >= C, 16-byte aligned operands. */
+VX_API int vx_upfirdn2x_f16(const void* x, int64_t x_pix, const void* fir, void* y, int64_t y_pix, const float* plane, const void* res, int64_t res_pix, int agc,
+                            float gain, float clamp, int B, int h, int w, int C, void* stream);
+/* vx_dwconv_f16 with lrelu_agc behind it: y = clamp((v > 0 ? v : slope v) * gain, +-clamp) of v = conv + bias, in f32 before the rounding (clamp 0: none) */
+VX_API int vx_dwconv_agc_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride, int pad, float slope, float gain,
+                             float clamp, void* stream);
 /* ---- pooling, row softmax and row sums (kernels_pool.hip; ggml_pool_2d, ggml_soft_max, ggml_sum_rows as yolov9t.cpp:165-185, 449-483, 657-691 use them) ----
  * x f16 [B,H,W] pixels of x_pix elements, the C pooled channels first (x points at the slice's first channel); y f16 [B,OH,OW] pixels of y_pix elements,
  * OH = (H + 2 pad - k) / stride + 1 (OW alike). kind 0 max (taken in f16: exact; positions outside the map never win), 1 average (f32 sum, one rounding;

@@ -102,6 +102,17 @@ def cases(tmp: Path):
                     g.output(t, f"out{i}")
                 return g
             yield f"yolov9t_{size}_b{batch}_{'fused' if fused else 'per_node'}", build
+    for res, kw in ((32, dict(ch_base=256, ch_max=24)), (512, {})):  # widths 8 .. 24 (no multiple of 64), and the full-size generator
+        mpath = None
+        for fused in (True, False):
+            def build(res=res, kw=kw, fused=fused):
+                nonlocal mpath
+                mpath = mpath or synth.write_migan_gguf(tmp / f"migan_{res}.gguf", res, seed=1, **kw)
+                g = G.Graph(None, G.Weights(mpath))
+                g.set_fused_models(fused)
+                G.migan_generate(G.ModelRef(g), g.input((4, res, res, 2), G.F32, "image"), res)
+                return g
+            yield f"migan_{res}_{'fused' if fused else 'per_node'}", build
 
 
 def device_cases(tmp: Path):

@@ -20,7 +20,7 @@ const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_nor
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
                                          "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
-                                         "sum_rows", "sub"};
+                                         "sum_rows", "sub", "clamp"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -96,14 +96,16 @@ void host_bilinear_ac(const float* src, const int64_t sne[4], float* dst, int64_
         }
 }
 
-// b broadcast over the trailing dimensions of a: b.ne[i] == a.ne[i] up to some dimension, 1 from there on. Returns b's period.
+// b broadcast over the trailing dimensions of a: b.ne[i] == a.ne[i] up to some dimension, 1 from there on. Returns b's period. The one other form
+// admitted is a plane (plane_broadcast, graph.h): b [1, W, H, 1] on a [C, W, H, N], one value per pixel; its period is W * H pixels, not elements.
 int64_t broadcast_period(const int64_t a[4], const int64_t b[4], const char* what) {
+    if (plane_broadcast(a, b)) return b[1] * b[2];
     bool ones = false;
     int64_t period = 1;
     for (int i = 0; i < 4; ++i) {
         if (!ones && b[i] == a[i]) { period *= b[i]; continue; }
         if (b[i] == 1) { ones = ones || a[i] != 1; continue; }
-        throw except("%s: cannot broadcast %s onto %s (the second operand must equal the first in its leading dimensions and be 1 in the rest)", what,
+        throw except("%s: cannot broadcast %s onto %s (the second operand must equal the first in its leading dimensions and be 1 in the rest, or be a plane [1, W, H, 1] on [C, W, H, N])", what,
                      shape_str(b).c_str(), shape_str(a).c_str());
     }
     return period;
@@ -123,12 +125,25 @@ void fold_constant(graph& g, graph_node& n) {
         case gop_add:
         case gop_mul:
         case gop_sub: {
-            const int64_t period = src(1).n_elements();
-            const float *a = src(0).values(), *b = src(1).values();
-            for (int64_t i = 0; i < total; ++i) out[i] = n.op == gop_add ? a[i] + b[i % period] : (n.op == gop_mul ? a[i] * b[i % period] : a[i] - b[i % period]);
+            const bool plane = plane_broadcast(src(0).ne, src(1).ne); // b's index is then the pixel's, not the element's
+            const int64_t period = src(1).n_elements(), C = plane ? n.ne[0] : 1;
+            const float *a = src(0).values(), *bv = src(1).values();
+            std::vector<float> spread;
+            if (plane) {
+                spread.resize((size_t)(period * C));
+                for (int64_t i = 0; i < period * C; ++i) spread[(size_t)i] = bv[i / C];
+            }
+            const float* b = plane ? spread.data() : bv;
+            for (int64_t i = 0; i < total; ++i) out[i] = n.op == gop_add ? a[i] + b[i % (period * C)] : (n.op == gop_mul ? a[i] * b[i % (period * C)] : a[i] - b[i % (period * C)]);
         } break;
         case gop_silu:
             for (int64_t i = 0; i < total; ++i) out[i] = (float)((double)src(0).values()[i] / (1.0 + std::exp(-(double)src(0).values()[i])));
+            break;
+        case gop_clamp: // ggml_clamp's comparisons: a NaN stays one, -0.0 stays -0.0
+            for (int64_t i = 0; i < total; ++i) {
+                const float v = src(0).values()[i];
+                out[i] = v < n.fp[0] ? n.fp[0] : (v > n.fp[1] ? n.fp[1] : v);
+            }
             break;
         case gop_slice: {
             host_view v{src(0).values(), src(0).ne};
@@ -213,7 +228,7 @@ void fold_constant(graph& g, graph_node& n) {
 bool foldable(int32_t op) {
     return op == gop_reshape || op == gop_cont || op == gop_scale || op == gop_add || op == gop_mul || op == gop_slice || op == gop_repeat ||
            op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid ||
-           op == gop_silu || op == gop_sub;
+           op == gop_silu || op == gop_sub || op == gop_clamp;
 }
 
 void check_tensor(graph const& g, int t, const char* what) {
@@ -592,6 +607,13 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             need_src(1, 1);
             same_shape();
             break;
+        case gop_clamp:
+            need_src(1, 1);
+            if (n_fp != 2) throw except("clamp: two float parameters (lower bound, upper bound)");
+            if (!std::isfinite(n.fp[0]) || !std::isfinite(n.fp[1])) throw except("clamp: bounds %g .. %g; both must be finite", (double)n.fp[0], (double)n.fp[1]);
+            if (n.fp[0] > n.fp[1]) throw except("clamp: lower bound %g above upper bound %g", (double)n.fp[0], (double)n.fp[1]);
+            same_shape();
+            break;
         case gop_sub: // not commutative: the operands stay where they are, so the first one is the larger
             need_src(2, 2);
             broadcast_period(S(0).ne, S(1).ne, nm);
@@ -690,8 +712,8 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             // (a 3x3 conv on the f32 image of <= 16 channels: the first conv of an image-to-image network, esrgan.cpp:58)
             const bool image_conv = op == gop_conv_2d && i == 0 && S(0).op == gop_input && S(0).ne[0] <= 16 && S(1).ne[1] == 3 && S(1).ne[2] == 3 && n.ip[0] == 1 && n.ip[1] == 1;
             const bool f32_mask = op == gop_attention_masked && i == 3; // the masked attention reads an f32 mask in place
-            // (any conv on a 3-channel f32 image: image_pad8 in front of the GEMM family's conv, mobile-sam.cpp:71-73)
-            const bool image8_conv = op == gop_conv_2d && i == 0 && S(0).dtype == gdt_f32 && S(0).ne[0] == 3;
+            // (any conv on a 3- or 4-channel f32 image: image_pad8 in front of the GEMM family's conv, mobile-sam.cpp:71-73, migan.cpp:84-86)
+            const bool image8_conv = op == gop_conv_2d && i == 0 && S(0).dtype == gdt_f32 && (S(0).ne[0] == 3 || S(0).ne[0] == 4);
             if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask)
                 throw except("%s: operand %d is f32; only patch_embed and an image's first 3x3 conv read the f32 input tensor", nm, i);
         }

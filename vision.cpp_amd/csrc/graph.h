@@ -71,6 +71,8 @@ enum graph_op : int32_t {
     gop_soft_max,         // over ne[0], the row maximum subtracted           ggml_soft_max
     gop_sum_rows,         // [n, a, b, c] -> [1, a, b, c]                      ggml_sum_rows
     gop_sub,              // a - b, b broadcast as for add                     ggml_sub
+    // MI-GAN's node beyond the above (migan.cpp:23); add / mul / sub also take a plane [1, W, H, 1] on [C, W, H, N] (migan.cpp:40, 76)
+    gop_clamp,            // f0 = lower, f1 = upper bound: min(max(x, f0), f1)   ggml_clamp
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -139,7 +141,14 @@ enum pack_role : int {
     role_tap_vec = 44,       // block kernel: the taps' final LayerNorm weight | bias
     role_rep_conv = 45,      // GEMM operand of a RepConv: the 3x3 kernel with the 1x1 kernel added into its centre tap (keyed on the 3x3 kernel)
     role_rep_conv_bias = 46, // ... and the two biases summed in f32, [N pad]
+    role_plane_f32 = 47,     // a [1, W, H, 1] constant as the f32 plane a fused epilogue adds per pixel (MI-GAN's folded noise)
 };
+// the second form of broadcast add / mul / sub admit next to the trailing-dimension one: b [1, W, H, 1] on a [C, W, H, N], one value per pixel for every
+// channel and image (ggml_mul_inplace(x, filter), ggml_add_inplace(x, noise): migan.cpp:40, 76). Where C == 1 or W H == 1 the trailing rule holds already.
+inline bool plane_broadcast(const int64_t a[4], const int64_t b[4]) {
+    return b[0] == 1 && b[3] == 1 && b[1] == a[1] && b[2] == a[2] && a[0] > 1 && b[1] * b[2] > 1;
+}
+
 constexpr pack_role bias_of_role(pack_role r) { return static_cast<pack_role>(role_bias_base + r); }
 static_assert(bias_of_role(role_rows) == 18 && bias_of_role(role_qkv) == 20 && bias_of_role(role_dconv_ex) == 24 && role_bias_padded < role_bias_base,
               "16..24 are reserved for the biases of roles 0..8");

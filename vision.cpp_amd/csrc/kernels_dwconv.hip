@@ -9,6 +9,7 @@
 // gets a contiguous run of the row-major sequence and the K output rows that read one input row fetch it through one L2.
 // The kernel is memory bound: loads per output are K ((P - 1) S + K) / P instead of K^2 (3.75 instead of 9 at 3x3 / P = 8).
 // Taps outside the map are zeros; a strip's tail past OW is computed and not stored.
+// kernels_fir.hip holds a copy of this kernel with another tail (dwconv_agc_kernel: lrelu_agc): a change to the loop here belongs there as well.
 #include "vx_common.h"
 
 namespace {

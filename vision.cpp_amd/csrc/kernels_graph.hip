@@ -148,6 +148,52 @@ __global__ __launch_bounds__(256) void unary_kernel(const f16* __restrict__ x, f
     }
 }
 
+// 5 clamp (ggml_clamp: x < lo ? lo : (x > hi ? hi : x), so a NaN stays one); unary_kernel's form with the second bound as a parameter of its own
+__device__ __forceinline__ float clamp_of(float f, float lo, float hi) { return f < lo ? lo : (f > hi ? hi : f); }
+__global__ __launch_bounds__(256) void clamp_kernel(const f16* __restrict__ x, f16* __restrict__ y, long n, float lo, float hi) {
+    const long n8 = n >> 3;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        f16x8 v = *reinterpret_cast<const f16x8*>(x + i * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (f16)clamp_of((float)v[j], lo, hi);
+        *reinterpret_cast<f16x8*>(y + i * 8) = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) { // tail
+        const long i = (n8 << 3) + threadIdx.x;
+        y[i] = (f16)clamp_of((float)x[i], lo, hi);
+    }
+}
+
+// y[b, p, c] = a[b, p, c] (op) plane[p]: one value per pixel for every channel and image (ggml_mul / ggml_add with a [1, W, H, 1] operand, migan.cpp:40, 76);
+// 8 channels per thread, lanes over the channel groups first
+template <int OP, typename TB>
+__global__ __launch_bounds__(256) void binary_plane_kernel(const f16* __restrict__ a, const TB* __restrict__ b, f16* __restrict__ y, long HW, int C8, long n8) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        const float bv = (float)b[(i / C8) % HW];
+        const f16x8 av = *reinterpret_cast<const f16x8*>(a + i * 8);
+        f16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (f16)f32_rounded(OP == 0 ? (float)av[j] + bv : (OP == 1 ? (float)av[j] * bv : (float)av[j] - bv));
+        *reinterpret_cast<f16x8*>(y + i * 8) = o;
+    }
+}
+
+// image_pad8_kernel for an f32 image [pixels][4] (MI-GAN's mask | rgb input, migan.cpp:84-86): value | rounding residue fill the 8 channels
+__global__ __launch_bounds__(256) void image4_pad8_kernel(const float* __restrict__ x, f16* __restrict__ y, long n_pix) {
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n_pix; p += (long)gridDim.x * 256) {
+        const float4 v4 = reinterpret_cast<const float4*>(x)[p];
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        f16x8 o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f16 hi = (f16)v[c];
+            o[c] = hi;
+            o[4 + c] = (f16)(v[c] - (float)hi);
+        }
+        reinterpret_cast<f16x8*>(y)[p] = o;
+    }
+}
+
 // ggml_interpolate(NEAREST) on an NHWC f16 map (ml.cpp:782-788 -> ggml upscale: source index = floor(i / (out / in))); 8 channels per thread
 __global__ __launch_bounds__(256) void nearest_kernel(const f16* __restrict__ x, f16* __restrict__ y, int H, int W, int C8, int OH, int OW, float sy, float sx, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
@@ -419,6 +465,43 @@ extern "C" int vx_unary_f16(int op, const void* x, void* y, int64_t n, float s, 
         case 4: hipLaunchKernelGGL(unary_kernel<4>, g, t, 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, s); break;
         default: VX_REQUIRE(false, "vx_unary_f16: op %d (0 gelu, 1 relu, 2 scale, 3 leaky relu, 4 silu)", op);
     }
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_clamp_f16(const void* x, void* y, int64_t n, float lo, float hi, void* stream) {
+    VX_REQUIRE(x && y && n > 0, "vx_clamp_f16: bad operands");
+    VX_REQUIRE(lo <= hi && lo - lo == 0.0f && hi - hi == 0.0f, "vx_clamp_f16: bounds %g .. %g (finite, lower <= upper)", (double)lo, (double)hi);
+    VX_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "vx_clamp_f16: operands must be 16-byte aligned");
+    hipLaunchKernelGGL(clamp_kernel, dim3(grid_stride_blocks(n / 8 + 1, GRID_CAP)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)y, (long)n, lo, hi);
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+template <int OP>
+static void launch_binary_plane(const void* a, const void* b, int b_f32, void* y, int64_t HW, int C8, long n8, hipStream_t st) {
+    const dim3 g(grid_stride_blocks(n8, GRID_CAP)), t(256);
+    if (b_f32) hipLaunchKernelGGL((binary_plane_kernel<OP, float>), g, t, 0, st, (const f16*)a, (const float*)b, (f16*)y, (long)HW, C8, n8);
+    else hipLaunchKernelGGL((binary_plane_kernel<OP, f16>), g, t, 0, st, (const f16*)a, (const f16*)b, (f16*)y, (long)HW, C8, n8);
+}
+
+extern "C" int vx_binary_plane_f16(int op, const void* a, const void* b, int b_f32, void* y, int B, int64_t HW, int C, void* stream) {
+    VX_REQUIRE(a && b && y && B > 0 && HW > 0 && C > 0, "vx_binary_plane_f16: bad operands");
+    VX_REQUIRE(op >= 0 && op <= 2, "vx_binary_plane_f16: op %d (0 add, 1 mul, 2 sub)", op);
+    VX_REQUIRE(C % 8 == 0, "vx_binary_plane_f16: C = %d must be a multiple of 8", C);
+    VX_REQUIRE(aligned16(a) && aligned16(y), "vx_binary_plane_f16: operands must be 16-byte aligned");
+    const long n8 = (long)B * HW * (C / 8);
+    if (op == 0) launch_binary_plane<0>(a, b, b_f32, y, HW, C / 8, n8, as_stream(stream));
+    else if (op == 1) launch_binary_plane<1>(a, b, b_f32, y, HW, C / 8, n8, as_stream(stream));
+    else launch_binary_plane<2>(a, b, b_f32, y, HW, C / 8, n8, as_stream(stream));
+    VX_LAUNCH_CHECK();
+    return 1;
+}
+
+extern "C" int vx_image4_pad8_f32(const float* x, void* y, int64_t n_pix, void* stream) {
+    VX_REQUIRE(x && y && n_pix > 0, "vx_image4_pad8_f32: bad operands");
+    VX_REQUIRE(aligned16(x) && aligned16(y), "vx_image4_pad8_f32: operands must be 16-byte aligned");
+    hipLaunchKernelGGL(image4_pad8_kernel, dim3(grid_stride_blocks(n_pix, GRID_CAP)), dim3(256), 0, as_stream(stream), x, (f16*)y, (long)n_pix);
     VX_LAUNCH_CHECK();
     return 1;
 }

@@ -511,7 +511,7 @@ void lowering::gemm_like(int t) {
         stride = (int)n.ip[0];
         a.M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
         // a 3-channel f32 image (patch_embed of mobile-sam.cpp:71-76): read as 8-channel value | residue pixels by the conv loader
-        const bool image8_in = x.dtype == gdt_f32 && x.ne[0] == 3;
+        const bool image8_in = x.dtype == gdt_f32 && (x.ne[0] == 3 || x.ne[0] == 4); // (4: MI-GAN's mask | rgb, migan.cpp:84-86)
         if (!image8_in && kw == 1 && kh == 1 && stride == 1 && pad == 0) { // 1x1: a plain product on the pixel rows (nn.cpp:76-81)
             p = pack_rows(wt, bt, (int)n.ne[0]);
             kind = "gemm(conv1x1)";
@@ -877,7 +877,7 @@ void lowering::deform_fused(int t, deform_group const& G) {
 
 // ---- depthwise convolution (nn.cpp:102-115) and the 3-channel image in front of a model's first conv ---------------------------------------------
 
-// the 8-channel f16 pixels of a 3-channel f32 image, made once per image whoever reads it
+// the 8-channel f16 pixels of a 3- or 4-channel f32 image, made once per image whoever reads it
 int lowering::image_pad8(int xs) {
     const int r = root(xs);
     if (auto it = image8.find(r); it != image8.end()) return it->second;
@@ -885,8 +885,13 @@ int lowering::image_pad8(int xs) {
     const int64_t px = x.ne[1] * x.ne[2] * x.ne[3];
     const int src = buf_of(r), dst = new_buffer((size_t)px * 16);
     auto sp = ptr(src), dp = ptr(dst);
-    emit("image_pad8 " + shape_str(x.ne), {src}, {dst}, [=](void* st) { VX(vx_image_pad8_f32(reinterpret_cast<const float*>(sp()), dp(), px, st)); });
-    tag("preprocess", 0, (double)px * 28);
+    if (x.ne[0] == 4) {
+        emit("image4_pad8 " + shape_str(x.ne), {src}, {dst}, [=](void* st) { VX(vx_image4_pad8_f32(reinterpret_cast<const float*>(sp()), dp(), px, st)); });
+        tag("preprocess", 0, (double)px * 32);
+    } else {
+        emit("image_pad8 " + shape_str(x.ne), {src}, {dst}, [=](void* st) { VX(vx_image_pad8_f32(reinterpret_cast<const float*>(sp()), dp(), px, st)); });
+        tag("preprocess", 0, (double)px * 28);
+    }
     image8[r] = dst;
     return dst;
 }

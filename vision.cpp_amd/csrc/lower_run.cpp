@@ -92,6 +92,7 @@ void lowering::run() {
     find_window_groups();
     find_encoder_chain();
     find_yolo_groups();
+    find_migan_groups();
     for (int t = 0; t < N; ++t) {
         graph_node& n = g.nodes[t];
         if (enc.ok && t == enc.first) emit_encoder();
@@ -101,6 +102,7 @@ void lowering::run() {
             if (n.is_output) throw except("graph_allocate: output '%s' is a constant", n.name.c_str());
             continue;
         }
+        if (migan_emits(t)) continue; // the last node of an lrelu_agc / FIR upsample group: the group's one launch
         std::string who = n.name;
         switch (n.op) {
             case gop_input: materialise(t); break;
@@ -185,10 +187,12 @@ void lowering::run() {
                 const float s = n.fp[0];
                 map_launch(t, std::string(graph_op_name(n.op)) + " n=" + std::to_string(cnt), [=](char* x, char* o, char*, void* st) { VX(vx_unary_f16(uop, x, o, cnt, s, st)); });
             } break;
+            case gop_clamp: clamp_op(t); break;
             case gop_add:
             case gop_mul:
             case gop_sub: {
                 graph_node const& b = g.nodes[n.src[1]];
+                if (plane_broadcast(n.ne, b.ne)) { plane_binary(t); break; }
                 if (g.nodes[n.src[0]].constant) throw except("%s: the larger operand is a constant; broadcast of an activation onto it is not built", graph_op_name(n.op));
                 const int abuf = buf_of(n.src[0]);
                 const int64_t period = b.n_elements(), cnt = n.n_elements();

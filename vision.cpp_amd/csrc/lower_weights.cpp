@@ -251,13 +251,13 @@ void* lowering::pack_depthwise(int wt, int C, int k) {
         return upload(h.data(), h.size() * 2, st);
     });
 }
-// conv [3, kw, kh, Cout] on 8-channel value | residue pixels (image_pad8): every tap's three columns repeated on channels 3..5, zeros on 6..7, so the f32
+// conv [C, kw, kh, Cout], C = 3 or 4, on 8-channel value | residue pixels (image_pad8): every tap's C columns repeated on channels C..2C-1, zeros behind them, so the f32
 // accumulator adds w * hi + w * lo = w * (the f32 pixel up to the residue's own rounding)
 packed_operand lowering::pack_image8(int wt, int bias_t, int n) {
     graph_node const& w = g.nodes[wt];
-    const int k3 = (int)(w.n_elements() / n), taps = k3 / 3;
+    const int C = (int)w.ne[0], kc = (int)(w.n_elements() / n), taps = kc / C;
     const float* h = w.values();
-    return pack_matrix(wt, role_image8, n, taps * 8, [h, k3](int r, int c) { return c % 8 < 6 ? h[(size_t)r * k3 + (c / 8) * 3 + (c % 8) % 3] : 0.0f; }, bias_t, n);
+    return pack_matrix(wt, role_image8, n, taps * 8, [h, kc, C](int r, int c) { return c % 8 < 2 * C ? h[(size_t)r * kc + (c / 8) * C + (c % 8) % C] : 0.0f; }, bias_t, n);
 }
 
 // RepConv (yolov9t.cpp:256-300): conv3x3(x) + conv1x1(x) at the same stride is one 3x3 conv whose centre tap holds the 1x1 kernel as well. Rows [Cout][9 Cin],

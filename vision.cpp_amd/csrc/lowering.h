@@ -4,6 +4,7 @@
 //   lower_conv.cpp     matrix products and convolutions with their fused epilogues, the planar maps, the DPT neck / head patterns
 //   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
 //   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
+//   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
 // a `return false` leaves the lowering's state as it was.
@@ -60,7 +61,7 @@ struct lowering {
     std::map<int, std::pair<int, int>> placed;        // node a concat chain will read -> (buffer, first plane) reserved for it
     std::map<int, int> up2_of;                        // interpolate(NEAREST, x2) node -> its (planar) source, resized by the reading conv's loader
     std::map<int, int> image_plane;                   // f32 image input -> buffer of its value | residue plane
-    std::map<int, int> image8;                        // 3-channel f32 image -> buffer of its 8-channel value | residue pixels (image_pad8)
+    std::map<int, int> image8;                        // 3- or 4-channel f32 image -> buffer of its 8-channel value | residue pixels (image_pad8)
 
     // ---- attention and the encoder chain (lower_encoder.cpp)
     std::map<int, int> qkv_first;                 // first of the three linears (node order) -> attention node
@@ -247,6 +248,35 @@ struct lowering {
     void soft_max(int t);
     void sum_rows(int t);
     packed_operand pack_rep_conv(int w3, int b3, int w1, int b1);
+
+    // ---- lower_migan.cpp: the node groups of MI-GAN (migan.cpp; the groups with g.fused_models only), clamp and plane-broadcast launches
+    // what a launch takes over from the nodes behind it: [+ plane constant] [leaky_relu [scale] [clamp(-c, c)]] [+ map]
+    struct agc_tail {
+        int plane = -1, res = -1, last = -1;
+        bool act = false;
+        float slope = 0.0f, gain = 1.0f, clamp = 0.0f;
+        std::vector<int> absorbed;
+    };
+    struct upfir_group { int src = -1, fir = -1; std::vector<int> members; agc_tail tail; }; // the map upsampled, the 4x4 kernel, interpolate .. [cont]
+    std::map<int, upfir_group> upfir_at;                      // LAST node of a group -> the group its launch computes
+    std::map<int, std::pair<int, agc_tail>> dw_agc_at;        // last node -> (conv_2d_depthwise node, its tail)
+    std::map<int, std::pair<int, agc_tail>> conv_agc_at;      // last node -> (1x1 conv_2d node, its tail)
+    std::vector<char> migan_claimed;                          // node -> a group computes it: one of this file's found so far (its last node included), or one
+                                                              // another lowering decided on before (SiLU groups, folded RepConvs, deformable-conv epilogues)
+    std::map<int, double> bound_memo;                         // value_bound's results
+    double value_bound(int v);                                // a proven bound of |values| of map v from the graph alone, or infinity
+    bool will_live_in_place(int v) const;                     // v (through cont / reshape views) is a channel slice read in its source or a map placed in a concat
+    bool free_node(int c) const { return c >= 0 && !skip[c] && !migan_claimed[c]; } // c may still join a group: no other pattern or group computes it
+    agc_tail match_agc_tail(int from, bool allow_plane, bool allow_add) const;
+    bool match_upfir_group(int t, upfir_group& G) const;
+    void find_migan_groups();
+    bool migan_emits(int t);
+    float* plane_f32(int t);
+    void migan_upfir(int last, upfir_group const& G);
+    void migan_depthwise(int last, int t, agc_tail const& T);
+    void migan_product(int last, int t, agc_tail const& T);
+    void clamp_op(int t);
+    void plane_binary(int t);
 
     // ---- lower_run.cpp
     void copy_op(int t);

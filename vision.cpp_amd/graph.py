@@ -19,7 +19,7 @@ from . import _lib as lib
 from ._lib import check, get_lib
 
 F32, F16, U8, I32 = 0, 1, 24, 26
-# OP_LINEAR ... OP_SUB: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
+# OP_LINEAR ... OP_CLAMP: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
 globals().update({k.removeprefix("VISP_"): v for k, v in lib.C_API_DECLS.enums["visp_graph_op"].items()})
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
@@ -339,6 +339,7 @@ def silu(m, x): return m.graph.op(OP_SILU, [x])  # ggml_silu
 def sub(m, a, b): return m.graph.op(OP_SUB, [a, b])  # ggml_sub: a - b, b broadcast as for add
 def soft_max(m, x): return m.graph.op(OP_SOFT_MAX, [x])  # ggml_soft_max: over dimension 0
 def sum_rows(m, x): return m.graph.op(OP_SUM_ROWS, [x])  # ggml_sum_rows: [n, a, b, c] -> [1, a, b, c]
+def clamp(m, x, lo, hi): return m.graph.op(OP_CLAMP, [x], fparams=[lo, hi])  # ggml_clamp: min(max(x, lo), hi)
 
 
 POOL_MAX, POOL_AVG = 0, 1  # ggml_op_pool
@@ -997,3 +998,117 @@ def yolov9t_forward(m: ModelRef, image: Tensor, nc: int = 80):  # yolov9t.cpp:82
     f = yolov9t_backbone(m, image)
     boxes, scores, raw = yolo_detect_forward(m, [f[15], f[18], f[21]], [64, 96, 128], nc)
     return boxes, scores, raw, f
+
+
+# ---- MI-GAN against this layer (the structure of src/visp/arch/migan.cpp, its CWHN branch) ------------------------------------------------------
+# Node for node. One departure, in the manner of the four of the YOLO builders: the image path (torgb, upsample_2d(img), add) has 3
+# channels and every map kernel here works on multiples of 8, so torgb's weight and bias and the image upsample's filter enter as named host constants 8
+# channels wide, channels 3..7 exactly zero; the image is carried 8 wide and migan_generate ends with a channel slice 0..3.
+
+MIGAN_SQRT2 = 1.4142135623  # migan.cpp:15
+
+
+def _migan_pad8(m: ModelRef, name: str, axis: int) -> Tensor:
+    """The constant `name` under m with numpy axis `axis` (the channel) zero-padded from 3 to 8, as the named host constant '<name>.pad8'."""
+    g, full = m.graph, m._full(name) + ".pad8"
+    if (t := g.get_tensor(full)) is not None:
+        return t
+    a = g.read_constant(m.weights(name))
+    width = [(0, 0)] * a.ndim
+    width[axis] = (0, 8 - a.shape[axis])
+    return g.add_weight(full, np.pad(a, width), F16)
+
+
+def migan_lrelu_agc(m: ModelRef, x: Tensor, alpha: float, gain: float, clamp_: float) -> Tensor:  # migan.cpp:17-26
+    x = leaky_relu(m, x, alpha)
+    if gain != 1:
+        x = scale(m, x, gain)
+    if clamp_ != 0:
+        x = clamp(m, x, -clamp_, clamp_)
+    return named(m, x)
+
+
+def migan_downsample_2d(m: ModelRef, x: Tensor) -> Tensor:  # migan.cpp:28-30
+    return conv_2d_depthwise(m["filter"], x, 2, 1)
+
+
+def migan_upsample_2d(m: ModelRef, x: Tensor, fir: Tensor | None = None) -> Tensor:  # migan.cpp:32-51; `fir`: the 4x4 kernel, where it is not m["filter"]'s weight
+    filt = m.weights("filter_const")
+    filt = reshape(m, filt, 1, filt.ne[0], filt.ne[1], 1)
+    c, w, h, n = x.ne
+    x = interpolate(m, x, (w * 2, h * 2), SCALE_MODE_NEAREST)
+    x = mul(m, x, filt)
+    x = conv_2d_depthwise(m["filter"], x, 1, 2) if fir is None else m.graph.op(OP_CONV_2D_DEPTHWISE, [x, fir], [1, 2])  # 4x4 filter
+    x = slice_(m, x, SLICE_ALL, (0, -1), (0, -1), SLICE_ALL)  # remove padding from right and bottom
+    x = cont(m, x)
+    return named(m, x)
+
+
+def migan_separable_conv_2d(m: ModelRef, x: Tensor, activation: bool = False, downsample: bool = False, upsample: bool = False, noise: bool = False) -> Tensor:  # migan.cpp:53-82
+    pad_ = m["conv1"].weights("weight").ne[2] // 2
+    x = conv_2d_depthwise(m["conv1"], x, 1, pad_)
+    if activation:
+        x = migan_lrelu_agc(m, x, 0.2, MIGAN_SQRT2, 256)
+    if downsample:
+        x = migan_downsample_2d(m["downsample"], x)
+    x = conv_2d(m["conv2"], x)
+    if upsample:
+        x = migan_upsample_2d(m["upsample"], x)
+    if noise:
+        nz = mul(m, m.weights("noise_const"), m.weights("noise_strength"))
+        nz = reshape(m, nz, 1, nz.ne[0], nz.ne[1], 1)
+        x = add(m, x, nz)
+    if activation:
+        x = migan_lrelu_agc(m, x, 0.2, MIGAN_SQRT2, 256)
+    return named(m, x)
+
+
+def migan_from_rgb(m: ModelRef, x: Tensor) -> Tensor:  # migan.cpp:84-89; x = the f32 image [4, W, H, N]
+    x = conv_2d(m["fromrgb"], x)
+    x = migan_lrelu_agc(m, x, 0.2, MIGAN_SQRT2, 256)
+    return named(m, x)
+
+
+def migan_encoder_block(m: ModelRef, x: Tensor, downsample: bool = False):  # migan.cpp:91-95
+    feat = migan_separable_conv_2d(m["conv1"], x, activation=True)
+    x = migan_separable_conv_2d(m["conv2"], feat, activation=True, downsample=downsample)
+    return x, feat
+
+
+def migan_encode(m: ModelRef, x: Tensor, res: int):  # migan.cpp:99-112
+    assert res == x.ne[1]
+    n = int(math.log2(res)) - 1
+    assert (1 << (n + 1)) == res
+    x = migan_from_rgb(m[f"b{res}"], x)
+    feats = [None] * n
+    for i in range(n - 1):
+        x, feats[i] = migan_encoder_block(m[f"b{res >> i}"], x, downsample=True)
+    x, feats[n - 1] = migan_encoder_block(m["b4"], x)
+    return x, feats
+
+
+def migan_synthesis_block(m: ModelRef, x: Tensor, feat: Tensor, img: Tensor | None, upsample: bool = False, noise: bool = False):  # migan.cpp:114-127
+    """`img` and the returned image are 8 channels wide, channels 3..7 zero (the departure above)."""
+    x = migan_separable_conv_2d(m["conv1"], x, activation=True, noise=noise, upsample=upsample)
+    x = add(m, x, feat)
+    x = migan_separable_conv_2d(m["conv2"], x, activation=True, noise=noise)
+    if img is not None:
+        img = migan_upsample_2d(m["upsample"], img, _migan_pad8(m["upsample.filter"], "weight", 0))
+    y = m.graph.op(OP_CONV_2D, [x, _migan_pad8(m["torgb"], "weight", 0), _migan_pad8(m["torgb"], "bias", -1)], [1, 0])
+    img = add(m, img, y) if img is not None else y
+    return x, img
+
+
+def migan_synthesis(m: ModelRef, x: Tensor, feats, res: int) -> Tensor:  # migan.cpp:129-140
+    n = int(math.log2(res)) - 1
+    assert (1 << (n + 1)) == res
+    x, img = migan_synthesis_block(m["b4"], x, feats[n - 1], None)
+    for i in range(n - 2, -1, -1):
+        x, img = migan_synthesis_block(m[f"b{res >> i}"], x, feats[i], img, upsample=True, noise=True)
+    return img
+
+
+def migan_generate(m: ModelRef, image: Tensor, res: int) -> Tensor:  # migan.cpp:161-165; image f32 [4, res, res, N] -> f16 [3, res, res, N]
+    x, feats = migan_encode(m["encoder"], image, res)
+    img = migan_synthesis(m["synthesis"], x, feats, res)
+    return m.graph.output(slice_(m, img, (0, 3)), "output")
