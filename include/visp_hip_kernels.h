@@ -346,8 +346,8 @@ VX_API void vx_attention_set_stamps(void* stamps);
  * in by the caller: wo / w2 rows and bo / b2 scaled by lambda1 / lambda2 -- the residual stream then stays in the MFMA accumulators from
  * the attention output to the next layer's q, k, v (x read once, written once per launch).
  * vec_mlp f32 = bo' | (unused) | ln2.w | ln2.b | b1[1536] | b2' | (unused) (3840 floats), vec_qkv f32 = ln1.w | ln1.b | bqkv[1152]
- * (1920 floats), vec_tap f32 = lnf.w | lnf.b (768 floats). M % T == 0 when q != NULL. 16 tokens per wave on v_mfma_f32_16x16x32_f16,
- * two waves per SIMD. */
+ * (1920 floats), vec_tap f32 = lnf.w | lnf.b (768 floats). When q != NULL: M % T == 0 and H == 6 -- the kernel writes embed_dim / 64 heads
+ * per token and uses H only as the image stride, so any other H is refused. 16 tokens per wave on v_mfma_f32_16x16x32_f16, two waves per SIMD. */
 typedef struct {
     const void* att; float* x;
     const void* w_mlp; const float* vec_mlp;

@@ -692,6 +692,9 @@ int vx_dino_block16_f16(const vx_dino_block_args* args, void* stream) {
     VX_REQUIRE(mlp || qkv, "vx_dino_block16_f16: nothing to do (neither att nor q given)");
     if (mlp) VX_REQUIRE(a.w_mlp && a.vec_mlp, "vx_dino_block16_f16: the MLP half needs w_mlp and vec_mlp");
     if (qkv) VX_REQUIRE(a.w_qkv && a.vec_qkv && a.k && a.v && a.T > 0 && a.H > 0 && a.M % a.T == 0, "vx_dino_block16_f16: the QKV half needs w_qkv, vec_qkv, k, v, T, H and M %% T == 0");
+    // the kernel always produces D / 64 heads; H only enters the image stride of the scatter ((b * H * T + tok) * 128 bytes): with any other H
+    // the images overlap or land behind the buffers
+    if (qkv) VX_REQUIRE(a.H == D / 64, "vx_dino_block16_f16: H = %d, but the kernel writes embed_dim / 64 = %d heads per token", a.H, D / 64);
     if (tap) VX_REQUIRE(a.vec_tap, "vx_dino_block16_f16: the tap needs vec_tap");
     VX_REQUIRE((long)a.M * D * 4 < 0x7fffffffL, "vx_dino_block16_f16: M = %d rows exceed the 2 GiB buffer range", a.M);
     if (mlp && qkv && tap) return launch16<true, true, true>(a, stream);
