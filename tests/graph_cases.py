@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 from visioncpp_amd import graph as G
+from visioncpp_amd import synth
 
 
 def h(a):
@@ -129,3 +130,53 @@ def encoder_chain(g, rng, scales, ps=14, side=2, B=2):
     last = m["l"][len(scales) - 1]
     y = g.output(G.layer_norm(last["final"], x, 1e-6), "y")
     return {"image": img, "y": y}
+
+
+# ---- one aspp_module_deformable (birefnet.cpp:109-114): the planning tests, the C++ face and tools/lowering_fingerprint.py build the same module
+
+DEFORM_C_IN, DEFORM_PLANES, DEFORM_KERNEL, DEFORM_W, DEFORM_H, DEFORM_B = 64, 256, 3, 13, 9, 2
+
+
+def deform_module_weights(seed=3):
+    """name -> (numpy array in torch order of the graph layer's layout, dtype): kernels [Cout, kh, kw, Cin]"""
+    rng = np.random.default_rng(seed)
+    t = DEFORM_KERNEL * DEFORM_KERNEL
+    out = {}
+    for name, co, bias in (("offset", 2 * t, True), ("modulator", t, True), ("conv", DEFORM_PLANES, False)):
+        out[f"aspp.conv.{name}.weight"] = ((rng.standard_normal((co, DEFORM_KERNEL, DEFORM_KERNEL, DEFORM_C_IN)) * 0.05).astype(np.float32), G.F16)
+        if bias:
+            out[f"aspp.conv.{name}.bias"] = ((rng.standard_normal(co) * 0.05).astype(np.float32), G.F32)
+    out["aspp.bn.weight"] = ((1 + 0.1 * rng.standard_normal(DEFORM_PLANES)).astype(np.float32), G.F32)
+    out["aspp.bn.bias"] = ((0.1 * rng.standard_normal(DEFORM_PLANES)).astype(np.float32), G.F32)
+    return out
+
+
+def deform_module(g, add_weights=True):
+    """The module on a [64, 13, 9, 2] map; `add_weights` False: the graph was made on a file that holds them."""
+    if add_weights:
+        for name, (a, dt) in deform_module_weights().items():
+            g.add_weight(name, a, dt)
+    x = g.input((DEFORM_C_IN, DEFORM_W, DEFORM_H, DEFORM_B), G.F16, "x")
+    y = g.output(G.birefnet_aspp_module_deformable(G.ModelRef(g, "aspp"), x, DEFORM_KERNEL // 2), "branch")
+    return {"x": x, "y": y}
+
+
+# ---- SWIN_MINI (graphs made on the file synth.write_swin_gguf(path, synth.SWIN_MINI, seed=5) writes)
+
+def swin_block_mini(g):
+    """bb.layers.0.blocks.1 of SWIN_MINI (C = 32, one head, shift 3) on a 14 x 14 map, two images."""
+    m = G.ModelRef(g, "bb")
+    G.swin_precompute(m, (56, 56), 7, 0)
+    x = g.input((32, 196, 2), G.F16, "tokens")
+    y = g.output(G.swin_block(m["layers"][0]["blocks"][1], x, g.get_tensor("swin_layer_14x14.attn_mask"), 1, 7, 14, 14, 3), "block")
+    return {"x": x, "y": y}
+
+
+def swin_encode_mini(g):
+    """swin_encode of SWIN_MINI at 256 x 288 (maps 64x72 .. 8x9: every stage pads)."""
+    cfg = synth.SWIN_MINI
+    m = G.ModelRef(g, "bb")
+    image = g.input((3, 256, 288, 2), G.F32, "image")
+    G.swin_precompute(m, (256, 288), cfg.window_size)
+    outs = G.swin_encode(m, image, cfg.window_size, cfg.depths, cfg.n_heads)
+    return {"image": image, "outs": [g.output(o, f"out{i}") for i, o in enumerate(outs)]}

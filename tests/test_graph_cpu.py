@@ -320,3 +320,22 @@ def test_encoder_chain_needs_one_attention_scale(scales, fused):
     assert (d.count("dino_block[") == 3) == fused and ("dino_block[" in d) == fused
     if not fused:
         assert d.count("attention B=2 heads=6 T=5") == 2 and d.count("gemm[qkv heads-major]") == 2
+
+
+def test_lowering_fingerprints_did_not_move(tmp_path):
+    """tests/golden/lowering_fingerprint.txt: every line tools/lowering_fingerprint.py prints (the sha256 of a planning-only graph's launch list and
+    buffer plan, or the refusal's text), recorded before the product emitter and the claim table replaced their copies. Line for line, names included."""
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parents[1]
+    want = (root / "tests" / "golden" / "lowering_fingerprint.txt").read_text().strip().splitlines()
+    out = tmp_path / "now.txt"
+    r = subprocess.run([sys.executable, str(root / "tools" / "lowering_fingerprint.py"), "--out", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr
+    got = out.read_text().strip().splitlines()
+    assert len(want) == 51 and [l.split(": ", 1)[0] for l in got] == [l.split(": ", 1)[0] for l in want]
+    for g_, w_ in zip(got, want):
+        assert g_ == w_, w_.split(": ", 1)[0]
+    assert [l.split(": ", 1)[0] for l in want if l.split(": ", 1)[1].startswith("error")] == [f"depthany_tiny_{s}_{f}" for s in ("70x70", "518x784") for f in ("fused", "per_node")]

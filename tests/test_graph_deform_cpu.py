@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import deform_ref as R
+import graph_cases as GC
 from visioncpp_amd import _lib as L
 from visioncpp_amd import graph as G
 
@@ -91,30 +92,13 @@ def test_batch_norm_2d_refuses_unfused_statistics():
 
 # ---- the planned launch list of one aspp_module_deformable ----------------------------------------------------------------------------------
 
-C_IN, PLANES, KERNEL, W, H, B = 64, 256, 3, 13, 9, 2
-
-
-def _module_weights(seed=3):
-    """name -> (numpy array in torch order of the graph layer's layout, dtype): kernels [Cout, kh, kw, Cin]"""
-    rng = np.random.default_rng(seed)
-    t = KERNEL * KERNEL
-    out = {}
-    for name, co, bias in (("offset", 2 * t, True), ("modulator", t, True), ("conv", PLANES, False)):
-        out[f"aspp.conv.{name}.weight"] = ((rng.standard_normal((co, KERNEL, KERNEL, C_IN)) * 0.05).astype(np.float32), G.F16)
-        if bias:
-            out[f"aspp.conv.{name}.bias"] = ((rng.standard_normal(co) * 0.05).astype(np.float32), G.F32)
-    out["aspp.bn.weight"] = ((1 + 0.1 * rng.standard_normal(PLANES)).astype(np.float32), G.F32)
-    out["aspp.bn.bias"] = ((0.1 * rng.standard_normal(PLANES)).astype(np.float32), G.F32)
-    return out
+C_IN, PLANES, KERNEL, W, H, B = GC.DEFORM_C_IN, GC.DEFORM_PLANES, GC.DEFORM_KERNEL, GC.DEFORM_W, GC.DEFORM_H, GC.DEFORM_B
+_module_weights = GC.deform_module_weights
 
 
 def _module_graph(fused: bool, weights=None):
     g = G.Graph(None, weights)
-    if weights is None:
-        for name, (a, dt) in _module_weights().items():
-            g.add_weight(name, a, dt)
-    x = g.input((C_IN, W, H, B), G.F16, "x")
-    g.output(G.birefnet_aspp_module_deformable(G.ModelRef(g, "aspp"), x, KERNEL // 2), "branch")
+    GC.deform_module(g, add_weights=weights is None)
     g.set_fused_models(fused)
     g.allocate()
     return g

@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import graph_cases as GC
 import graph_window_ref as R
 from oracle import oracle
 from visioncpp_amd import _lib as L
@@ -135,11 +136,7 @@ def _block_graph(tmp_path):
     """bb.layers.0.blocks.1 of SWIN_MINI (C = 32, one head, shift 3) on a 14 x 14 map, two images."""
     path = synth.write_swin_gguf(tmp_path / "mini.gguf", synth.SWIN_MINI, seed=5)
     g = G.Graph(None, G.Weights(path))
-    m = G.ModelRef(g, "bb")
-    G.swin_precompute(m, (56, 56), 7, 0)
-    x = g.input((32, 196, 2), G.F16, "tokens")
-    out = G.swin_block(m["layers"][0]["blocks"][1], x, g.get_tensor("swin_layer_14x14.attn_mask"), 1, 7, 14, 14, 3)
-    g.output(out, "block")
+    GC.swin_block_mini(g)
     g.allocate()
     return path, g
 
@@ -173,13 +170,8 @@ def test_swin_encode_plans_with_padding_and_masks_at_every_stage(tmp_path):
     cfg = synth.SWIN_MINI
     path = synth.write_swin_gguf(tmp_path / "mini.gguf", cfg, seed=5)
     g = G.Graph(None, G.Weights(path))
-    m = G.ModelRef(g, "bb")
-    image = g.input((3, 256, 288, 2), G.F32, "image")
-    G.swin_precompute(m, (256, 288), cfg.window_size)
-    outs = G.swin_encode(m, image, cfg.window_size, cfg.depths, cfg.n_heads)
+    outs = GC.swin_encode_mini(g)["outs"]
     assert [o.ne for o in outs] == [(32, 64, 72, 2), (64, 32, 36, 2), (128, 16, 18, 2), (256, 8, 9, 2)]
-    for i, o in enumerate(outs):
-        g.output(o, f"out{i}")
     g.allocate()
     lines = g.describe().strip().splitlines()[:-1]
     att = [l for l in lines if l.startswith("attention")]

@@ -19,11 +19,55 @@ switches const& env() {
 }
 
 const char* act_name(int a) { return a == 1 ? "gelu" : (a == 2 ? "relu" : ""); }
+
+} // namespace
+
 bool is_conv3x3(graph_node const& c, graph_node const& w) {
     return c.op == gop_conv_2d && w.constant && w.ne[1] == 3 && w.ne[2] == 3 && c.ip[0] == 1 && c.ip[1] == 1;
 }
+bool same_shape(graph_node const& a, graph_node const& b) { return a.ne[0] == b.ne[0] && a.ne[1] == b.ne[1] && a.ne[2] == b.ne[2] && a.ne[3] == b.ne[3]; }
 
-} // namespace
+// ---- the one launch of the GEMM family ---------------------------------------------------------------------------------------------------------
+
+// The plan as a launch: its reads and writes (A's buffer among the writes where its slack is zeroed first), the closure that puts the run-time
+// addresses into a copy of the arguments, its timing group and work. Every behaviour comes from a field of the plan.
+void lowering::emit_product(product const& P) {
+    std::vector<int> reads = {P.in.buf}, writes;
+    std::function<char*()> xp = ptr(P.in.buf), op, r1, r2, qp, kp, vp;
+    if (P.out.buf >= 0) { writes.push_back(P.out.buf); op = ptr(P.out.buf); }
+    if (P.qkv[0] >= 0) {
+        writes.insert(writes.end(), P.qkv.begin(), P.qkv.end());
+        qp = ptr(P.qkv[0]); kp = ptr(P.qkv[1]); vp = ptr(P.qkv[2]);
+    }
+    if (P.zero_at) writes.push_back(P.in.buf);
+    if (P.res1.buf >= 0) { reads.push_back(P.res1.buf); r1 = ptr(P.res1.buf); }
+    if (P.res2 >= 0) { reads.push_back(P.res2); r2 = ptr(P.res2); }
+    emit(P.desc, reads, writes, [=](void* st) { // (the closure keeps its own copy of the plan)
+        vx_gemm_args r = P.a;
+        r.A = xp() + P.in.off * 2;
+        if (op) r.out = op() + P.out.off * 2;
+        if (r1) r.res1 = r1() + P.res1.off * 2;
+        if (r2) r.res2 = r2();
+        if (qp) { r.q = qp(); r.k = kp(); r.vt = vp(); }
+        if (P.zero_at) VX(vx_memset(xp() + P.zero_at, 0, 128, st));
+        if (P.halo && vx_conv3x3_supported(&r)) VX(vx_conv3x3_f16(&r, st));
+        else VX(vx_gemm_f16(&r, st));
+    });
+    tag(P.group.c_str(), P.flops, P.bytes);
+}
+// the implicit conv's geometry: conv node n (conv_2d, or a conv_2d_deform whose offsets are computed with its kernel's extent) on x with kernel w
+void lowering::conv_geometry(vx_gemm_args& a, graph_node const& n, graph_node const& x, graph_node const& w) const {
+    a.conv_kh = (int)w.ne[2]; a.conv_kw = (int)w.ne[1]; a.conv_stride = (int)n.ip[0]; a.conv_pad = (int)n.ip[1];
+    a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = image8_input(x) ? 8 : (int)x.ne[0];
+    a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
+}
+// the operand of conv / linear / patch_embed node n: its kernel's rows (LayerScale scale_t folded in), laid out for 8-channel image pixels, or folded
+// with the 1x1 conv rep1 of a RepConv
+void lowering::pack_conv_rows(product& P, graph_node const& n, bool image8_in, int rep1, int scale_t) {
+    const int wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
+    if (rep1 >= 0) P.operand(pack_rep_conv(wt, bt, g.nodes[rep1].src[1], g.nodes[rep1].n_src == 3 ? g.nodes[rep1].src[2] : -1));
+    else P.operand(image8_in ? pack_image8(wt, bt, (int)n.ne[0]) : pack_rows(wt, bt, (int)n.ne[0], scale_t));
+}
 
 // the epilogue behind a matrix product: [* LayerScale] [gelu | relu] then up to two [+ residual]; `res_after_relu` false: an add behind a
 // relu stays a launch
@@ -57,9 +101,10 @@ lowering::epilogue lowering::match_epilogue(int t, bool allow_gelu, bool allow_s
     }
     return e;
 }
-// the matched nodes are computed by `into`'s launch: they share its buffer, and an output among them keeps it
-void lowering::absorb(epilogue const& e, int into) {
-    for (int c : e.absorbed) {
+// the matched nodes (entries < 0 are left out) are computed by `into`'s launch: they share its buffer, and an output among them keeps it
+void lowering::absorb(std::vector<int> const& nodes, int into) {
+    for (int c : nodes) {
+        if (c < 0) continue;
         skip[c] = 1;
         g.nodes[c].alias_of = into;
         if (g.nodes[c].is_output) g.nodes[into].is_output = true;
@@ -68,9 +113,8 @@ void lowering::absorb(epilogue const& e, int into) {
 // `other` can be the residual operand of the epilogue of t's launch: an f16 map of t's shape, in an NHWC buffer before that launch runs
 bool lowering::residual_ready(int other, int t) const {
     graph_node const& o = g.nodes[other];
-    bool same = !o.constant && o.dtype == gdt_f16 && root(other) != root(t) && root(other) < t; // already computed when this launch runs
-    for (int i = 0; i < 4; ++i) same = same && o.ne[i] == g.nodes[t].ne[i];
-    return same && g.nodes[root(other)].buffer >= 0;
+    return !o.constant && o.dtype == gdt_f16 && root(other) != root(t) && root(other) < t /* already computed when this launch runs */ && same_shape(o, g.nodes[t]) &&
+           g.nodes[root(other)].buffer >= 0;
 }
 // the residual operands of an epilogue: their buffers join `reads`, their addresses are taken when the launch runs
 lowering::residual_ptrs lowering::read_residuals(epilogue const& e, std::vector<int>& reads) {
@@ -116,11 +160,10 @@ bool lowering::head_tail(int t) {
     if (cin == 32 ? !vx_headconv_supported(32, 32, H, W, hs, ws) || (size_t)B * hs * ws * 64 >= ((size_t)1 << 31)
                   : !vx_headconv_wide_supported(cin, 32, H, W, hs, ws) || (size_t)B * hs * ws * cin >= ((size_t)1 << 32))
         return false;
-    epilogue tail; // what c3's launch computes behind c3
-    tail.absorbed = {r2};
+    std::vector<int> tail = {r2}; // what c3's launch computes behind c3
     float scale = 1.0f;
     const int sc = sole_consumer(r2);
-    if (sc >= 0 && g.nodes[sc].op == gop_scale) { scale = g.nodes[sc].fp[0]; tail.absorbed.push_back(sc); }
+    if (sc >= 0 && g.nodes[sc].op == gop_scale) { scale = g.nodes[sc].fp[0]; tail.push_back(sc); }
     const int wt = g.nodes[c2].src[1];
     void* frag = pack_head_fragments(wt, cin);
     const float* bias2 = const_f32(g.nodes[c2].src[2]);
@@ -150,13 +193,12 @@ void lowering::one_channel_head(int t) {
     graph_node const& x = g.nodes[n.src[0]];
     const int C = (int)x.ne[0];
     if (C % 8) throw except("conv_2d to one channel: Cin = %d must be a multiple of 8", C);
-    epilogue e; // [relu] [scale] behind the conv
+    std::vector<int> tail; // [relu] [scale] behind the conv
     float scale = 1.0f;
-    int c = sole_consumer(t);
-    if (c >= 0 && g.nodes[c].op == gop_relu) { e.act = 2; e.absorbed.push_back(c); c = sole_consumer(c); }
-    if (c >= 0 && g.nodes[c].op == gop_scale) { scale = g.nodes[c].fp[0]; e.absorbed.push_back(c); }
-    const int relu = e.act == 2;
-    absorb(e, t); // (an output anywhere in the fused chain keeps the buffer)
+    int relu = 0, c = sole_consumer(t);
+    if (c >= 0 && g.nodes[c].op == gop_relu) { relu = 1; tail.push_back(c); c = sole_consumer(c); }
+    if (c >= 0 && g.nodes[c].op == gop_scale) { scale = g.nodes[c].fp[0]; tail.push_back(c); }
+    absorb(tail, t); // (an output anywhere in the fused chain keeps the buffer)
     const float* w = const_f32(n.src[1]);
     const float bias = n.n_src == 3 ? g.nodes[n.src[2]].values()[0] : 0.0f;
     if (n.n_src == 3) (void)const_f32(n.src[2]);
@@ -165,7 +207,7 @@ void lowering::one_channel_head(int t) {
     const int obuf = n.buffer;
     auto xp = ptr(xbuf), op = ptr(obuf);
     const int64_t M = n.n_elements();
-    std::string who = n.name.empty() ? g.nodes[n.src[1]].name : n.name;
+    std::string who = n.name.empty() ? g.nodes[n.src[1]].name : n.name; // (not weight_name: the node's own name comes first here)
     emit(std::string("conv1x1_to_1") + (relu ? "[relu]" : "") + (scale != 1.0f ? "[scale]" : "") + " M=" + std::to_string(M) + " C=" + std::to_string(C) + " <- " + who, {xbuf}, {obuf},
          [=](void* st) { VX(vx_conv1x1_to1_f32(xp(), w, bias, relu, scale, reinterpret_cast<float*>(op()), M, C, st)); });
     tag("head_out", 2.0 * M * C, (double)M * (C * 2 + 4));
@@ -467,28 +509,23 @@ bool lowering::residual_unit(int t, std::string const& who) {
 void lowering::gemm_like(int t) {
     graph_node& n = g.nodes[t];
     if (yolo_takes(t)) return yolo_product(t); // a SiLU group, a conv that reads or writes inside a wider map: never the LDS-ring kernels (lower_yolo.cpp)
-    {
-        std::string w0 = g.nodes[n.src[1]].op == gop_weight && !g.nodes[n.src[1]].name.empty() ? g.nodes[n.src[1]].name : n.name;
-        if (n.op == gop_conv_2d && planar_conv(t, w0)) return;
-    }
+    if (n.op == gop_conv_2d && planar_conv(t, weight_name(g, n))) return;
     if (n.op == gop_conv_2d && n.dtype == gdt_f32 && n.ne[0] != 1) throw except("conv_2d %s to an f32 image of %lld channels is lowered onto the LDS-ring conv only (3x3 / stride 1 / pad 1 behind planar maps)", n.name.c_str(), (long long)n.ne[0]);
     if (n.op == gop_conv_2d && n.dtype == gdt_f32) return one_channel_head(t);
     const int xs = n.src[0], wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
     graph_node const& x = g.nodes[xs];
+    // groups are keyed on the weight's name. (Not weight_name: a conv without a name on a kernel that is no named weight takes the kernel node's name)
     std::string who = n.name.empty() ? g.nodes[wt].name : n.name;
-    if (g.nodes[wt].op == gop_weight && !g.nodes[wt].name.empty()) who = g.nodes[wt].name; // groups are keyed on the weight's name
-    vx_gemm_args a;
-    memset(&a, 0, sizeof a);
-    packed_operand p;
-    int xbuf = -1;
+    if (g.nodes[wt].op == gop_weight && !g.nodes[wt].name.empty()) who = g.nodes[wt].name;
+    product P;
+    vx_gemm_args& a = P.a;
     std::string kind;
-    bool conv = false;
     epilogue e;
     e.last = t;
     int stride = 1;
     // the A rows of a plain product: in place from a sliced source, from a padded producer, or padded by a copy
-    auto plain_rows = [&](int K, int Kp) {
-        const int v = root_view(xs);
+    auto plain_rows = [&] {
+        const int v = root_view(xs), K = P.p.k_real, Kp = P.p.K;
         if (auto it = sliced_in.find(v); it != sliced_in.end()) {
             a.a_group = (int)it->second.rows; a.a_group_stride = (int)it->second.stride; a.a_row_off = (int)it->second.begin;
             a.lda = K;
@@ -501,46 +538,45 @@ void lowering::gemm_like(int t) {
     };
     if (n.op == gop_linear) {
         e = match_epilogue(t, true, true);
-        p = pack_rows(wt, bt, (int)n.ne[0], e.scale);
+        pack_conv_rows(P, n, false, -1, e.scale);
         a.M = (int)(x.n_elements() / x.ne[0]);
         kind = "gemm";
-        xbuf = plain_rows(p.k_real, p.K);
+        P.in.buf = plain_rows();
     } else if (n.op == gop_conv_2d) {
         graph_node const& w = g.nodes[wt];
         const int kw = (int)w.ne[1], kh = (int)w.ne[2], pad = (int)n.ip[1];
         stride = (int)n.ip[0];
         a.M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
-        // a 3-channel f32 image (patch_embed of mobile-sam.cpp:71-76): read as 8-channel value | residue pixels by the conv loader
-        const bool image8_in = x.dtype == gdt_f32 && (x.ne[0] == 3 || x.ne[0] == 4); // (4: MI-GAN's mask | rgb, migan.cpp:84-86)
+        // a 3-channel f32 image (patch_embed of mobile-sam.cpp:71-76) or MI-GAN's mask | rgb (migan.cpp:84-86): read as 8-channel pixels by the conv loader
+        const bool image8_in = image8_input(x);
         if (!image8_in && kw == 1 && kh == 1 && stride == 1 && pad == 0) { // 1x1: a plain product on the pixel rows (nn.cpp:76-81)
-            p = pack_rows(wt, bt, (int)n.ne[0]);
+            pack_conv_rows(P, n, false);
             kind = "gemm(conv1x1)";
-            xbuf = plain_rows(p.k_real, p.K);
+            P.in.buf = plain_rows();
         } else {
             if (!image8_in && x.ne[0] % 8) throw except("conv_2d %s: Cin = %lld must be a multiple of 8", who.c_str(), (long long)x.ne[0]);
             if (!image8_in && dconv_shape(n, x, w)) return dconv(t, who);
-            p = image8_in ? pack_image8(wt, bt, (int)n.ne[0]) : pack_rows(wt, bt, (int)n.ne[0]);
-            xbuf = image8_in ? image_pad8(xs) : buf_of(xs);
-            a.conv_kh = kh; a.conv_kw = kw; a.conv_stride = stride; a.conv_pad = pad;
-            a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = image8_in ? 8 : (int)x.ne[0];
-            a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
+            pack_conv_rows(P, n, image8_in);
+            P.in.buf = image8_in ? image_pad8(xs) : buf_of(xs);
+            conv_geometry(a, n, x, w);
             a.a_relu = relu_on_load[t];
-            conv = true;
+            P.halo = kh == 3 && kw == 3 && stride == 1 && pad == 1 && a.conv_W >= env().halo_min_w;
             kind = "conv" + std::to_string(kw) + "x" + std::to_string(kh) + (stride > 1 ? "s" + std::to_string(stride) : "") + (a.a_relu ? "[relu-in]" : "");
         }
     } else { // conv_transpose_2d with kernel == stride: a product + pixel shuffle
         const int s = (int)n.ip[0];
-        p = pack_conv_transpose(wt, bt, s);
+        P.operand(pack_conv_transpose(wt, bt, s));
         a.M = (int)(x.ne[1] * x.ne[2] * x.ne[3]);
         kind = "gemm+pixel_shuffle(s" + std::to_string(s) + ")";
-        xbuf = plain_rows(p.k_real, p.K);
+        P.in.buf = plain_rows();
         a.ps_s = s; a.ps_Cout = (int)n.ne[0]; a.ps_H = (int)x.ne[2]; a.ps_W = (int)x.ne[1];
     }
+    packed_operand const& p = P.p;
     // a channel count that is no multiple of 8 (the 2 k^2 offsets and k^2 modulator logits of a deformable conv on their own): the f16 epilogues store
     // 8 at a time, so the product writes rows padded to 8 and one strided copy compacts them
     const bool ragged = n.ne[0] % 8 != 0;
     if (ragged && n.op == gop_conv_transpose_2d) throw except("%s %s: %lld output channels; the f16 epilogues store 8 at a time", graph_op_name(n.op), who.c_str(), (long long)n.ne[0]);
-    a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.n_valid = n.op == gop_conv_transpose_2d ? p.n_real : (int)n.ne[0];
+    a.n_valid = n.op == gop_conv_transpose_2d ? p.n_real : (int)n.ne[0];
     a.ldo = n.ne[0];
     if (n.op == gop_conv_transpose_2d) a.epi = VX_EPI_PIXSHUF;
     else {
@@ -564,26 +600,18 @@ void lowering::gemm_like(int t) {
     const int ld8 = round_up((int)n.ne[0], 8);
     const int64_t rows = n.n_elements() / n.ne[0];
     if (ragged) { a.ldo = ld8; a.n_valid = ld8; }
-    const int obuf = ragged ? new_buffer((size_t)rows * ld8 * 2) : n.buffer;
-    std::vector<int> reads = {xbuf};
-    const residual_ptrs rp = read_residuals(e, reads);
-    const bool halo = conv && a.conv_kh == 3 && a.conv_kw == 3 && a.conv_stride == 1 && a.conv_pad == 1 && a.conv_W >= env().halo_min_w;
+    P.out.buf = ragged ? new_buffer((size_t)rows * ld8 * 2) : n.buffer;
+    if (e.res >= 0) P.res1.buf = buf_of(e.res);
+    if (e.res2 >= 0) P.res2 = buf_of(e.res2);
     char d[320];
     snprintf(d, sizeof d, "%s%s%s%s%s%s%s M=%d N=%d K=%d <- %s", kind.c_str(), e.scale >= 0 ? "[*scale]" : "", e.act ? "[" : "", act_name(e.act), e.act ? "]" : "",
              e.res >= 0 ? "[+res]" : "", e.res2 >= 0 ? "[+res]" : "", a.M, (int)n.ne[0], p.k_real, who.c_str());
-    auto xp = ptr(xbuf), op = ptr(obuf);
-    emit(d, reads, {obuf}, [=](void* st) {
-        vx_gemm_args r = a;
-        r.A = xp();
-        r.out = op();
-        if (rp.res1) r.res1 = rp.res1();
-        if (rp.res2) r.res2 = rp.res2();
-        if (halo && vx_conv3x3_supported(&r)) VX(vx_conv3x3_f16(&r, st));
-        else VX(vx_gemm_f16(&r, st));
-    });
-    tag(group_of(who, n, stride).c_str(), 2.0 * a.M * (double)p.n_real * p.k_real, (double)a.M * (p.k_real + n.ne[0]) * 2 + (double)p.N * p.K * 2);
+    P.desc = d;
+    P.group = group_of(who, n, stride);
+    P.work(p.k_real, (double)n.ne[0]); // (the residuals' rows are not counted here)
+    emit_product(P);
     if (ragged) {
-        const int dst = n.buffer;
+        const int obuf = P.out.buf, dst = n.buffer;
         auto sp = ptr(obuf), dp = ptr(dst);
         const int64_t c = n.ne[0];
         emit("unpad_rows N=" + std::to_string(ld8) + "->" + std::to_string(c) + " <- " + who, {obuf}, {dst}, [=](void* st) {
@@ -672,25 +700,24 @@ bool lowering::resize_into_reader(int t) {
     }
     if (!(w.ne[1] == 1 && w.ne[2] == 1 && cn.ip[0] == 1 && cn.ip[1] == 0) || cn.ne[0] % 8 || x.ne[0] % 64) return false;
     // the projection on the small map (where the residual unit in front of the resize has not applied it already)
-    const int bt = cn.n_src == 3 ? cn.src[2] : -1, cout = (int)cn.ne[0];
+    const int cout = (int)cn.ne[0];
     const int64_t M = (int64_t)B * hs * ws;
     int sbuf;
     if (auto it = preprojected.find(t); it != preprojected.end()) sbuf = it->second;
     else {
-        packed_operand p = pack_rows(cn.src[1], bt, cout);
+        product P;
+        pack_conv_rows(P, cn, false);
         sbuf = new_buffer((size_t)M * cout * 2);
-        const int xbuf = buf_of(up.src[0]);
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
-        a.lda = p.K; a.W = p.w; a.bias = p.bias; a.M = (int)M; a.N = p.N; a.K = p.K; a.n_valid = cout; a.ldo = cout; a.epi = VX_EPI_F16;
-        auto xp = ptr(xbuf), sp0 = ptr(sbuf);
+        P.in.buf = buf_of(up.src[0]);
+        P.out.buf = sbuf;
+        vx_gemm_args& a = P.a;
+        a.lda = P.p.K; a.M = (int)M; a.n_valid = cout; a.ldo = cout; a.epi = VX_EPI_F16;
         std::string who = g.nodes[cn.src[1]].name;
-        emit("gemm(conv1x1 before its resize) M=" + std::to_string(M) + " N=" + std::to_string(cout) + " K=" + std::to_string(p.k_real) + " <- " + who, {xbuf}, {sbuf}, [=](void* st) {
-            vx_gemm_args r = a;
-            r.A = xp(); r.out = sp0();
-            VX(vx_gemm_f16(&r, st));
-        });
-        tag(group_of(who, cn, 1).c_str(), 2.0 * M * (double)cout * p.k_real, (double)M * (p.k_real + cout) * 2);
+        P.desc = "gemm(conv1x1 before its resize) M=" + std::to_string(M) + " N=" + std::to_string(cout) + " K=" + std::to_string(P.p.k_real) + " <- " + who;
+        P.group = group_of(who, cn, 1);
+        P.flops = 2.0 * M * (double)cout * P.p.k_real;
+        P.bytes = (double)M * (P.p.k_real + cout) * 2; // (without the operand's image)
+        emit_product(P);
     }
     auto sp = ptr(sbuf);
     skip[t] = 1;
@@ -756,12 +783,8 @@ void lowering::find_deform_groups() {
         if (!needed[t] || !match_deform_group(t, G)) continue;
         deform_groups[t] = G;
         for (int c : {G.off, G.mod, G.sig, G.scl}) skip[c] = 1;
+        claim(t, {G.off, G.mod, G.sig, G.scl, G.mul, G.add, G.relu}); // (the tail is absorbed when the launch is emitted)
     }
-}
-
-static std::string deform_who(graph const& g, graph_node const& n) {
-    graph_node const& w = g.nodes[n.src[1]];
-    return w.op == gop_weight && !w.name.empty() ? w.name : n.name;
 }
 
 // any use of the op: offsets and mask are read where they are, the mask as it is
@@ -792,7 +815,7 @@ void lowering::deform_conv(int t) {
     materialise(t);
     const int obuf = n.buffer;
     auto outp = ptr(obuf);
-    const std::string who = deform_who(g, n);
+    const std::string who = weight_name(g, n);
     const int M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
     char d[320];
     snprintf(d, sizeof d, "deform_conv%s M=%d N=%d K=%d k=%d <- %s", n.n_src == 4 ? "[mask]" : "", M, a.Cout, taps * a.Cin, a.k, who.c_str());
@@ -815,33 +838,29 @@ void lowering::deform_fused(int t, deform_group const& G) {
     graph_node const &on = g.nodes[G.off], &mn = g.nodes[G.mod];
     const int k = (int)w.ne[1], taps = k * k, pad = (int)n.ip[1], Cin = (int)x.ne[0];
     const int M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
-    const std::string who = deform_who(g, n);
+    const std::string who = weight_name(g, n);
     const packed_operand p = pack_deform_offsets(on.src[1], on.n_src == 3 ? on.src[2] : -1, mn.src[1], mn.n_src == 3 ? mn.src[2] : -1);
     const int ldom = round_up(3 * taps, 8);
     const int xbuf = buf_of(n.src[0]);
     const int ombuf = new_buffer((size_t)M * ldom * 2);
     auto xp = ptr(xbuf), omp = ptr(ombuf);
     {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
-        a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.M = M;
-        a.n_valid = ldom; a.ldo = ldom; a.epi = VX_EPI_F16;
+        product P;
+        P.operand(p);
+        P.in.buf = xbuf;
+        P.out.buf = ombuf;
+        vx_gemm_args& a = P.a;
+        a.M = M; a.n_valid = ldom; a.ldo = ldom; a.epi = VX_EPI_F16;
         const bool plain = k == 1 && pad == 0 && Cin % 64 == 0; // a plain product on the pixel rows; every other shape through the conv loader
         if (plain) a.lda = Cin;
-        else {
-            a.conv_kh = a.conv_kw = k; a.conv_stride = 1; a.conv_pad = pad;
-            a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = Cin; a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
-        }
+        else conv_geometry(a, n, x, w);
         char d[320];
         snprintf(d, sizeof d, "deform_offsets %s M=%d N=%d K=%d <- %s", plain ? "gemm" : ("conv" + std::to_string(k) + "x" + std::to_string(k)).c_str(), M, p.n_real, p.k_real,
-                 deform_who(g, on).c_str());
-        emit(d, {xbuf}, {ombuf}, [=](void* st) {
-            vx_gemm_args r = a;
-            r.A = xp();
-            r.out = omp();
-            VX(vx_gemm_f16(&r, st));
-        });
-        tag("deform_offsets", 2.0 * M * (double)p.n_real * p.k_real, (double)M * (Cin + p.n_real) * 2 + (double)p.N * p.K * 2);
+                 weight_name(g, on).c_str());
+        P.desc = d;
+        P.group = "deform_offsets";
+        P.work(Cin, p.n_real); // (one read of x, not of its k^2 taps)
+        emit_product(P);
     }
     vx_deform_conv_args a;
     memset(&a, 0, sizeof a);
@@ -854,10 +873,7 @@ void lowering::deform_fused(int t, deform_group const& G) {
     if (G.mul >= 0) a.scale = const_f32(g.nodes[G.mul].src[1]);
     if (G.add >= 0) a.bias = const_f32(g.nodes[G.add].src[1]);
     a.relu = G.relu >= 0;
-    epilogue e;
-    for (int c : {G.mul, G.add, G.relu})
-        if (c >= 0) e.absorbed.push_back(c);
-    absorb(e, t);
+    absorb(std::vector<int>{G.mul, G.add, G.relu}, t);
     materialise(t);
     const int obuf = n.buffer;
     auto outp = ptr(obuf);
@@ -909,11 +925,9 @@ void lowering::depthwise_conv(int t) {
     if (const int c = sole_consumer(t); g.fused_models && c >= 0 && (g.nodes[c].op == gop_gelu || g.nodes[c].op == gop_leaky_relu)) {
         act = g.nodes[c].op == gop_gelu ? 1 : 2;
         act_param = g.nodes[c].fp[0];
-        epilogue e;
-        e.absorbed.push_back(c);
-        absorb(e, t);
+        absorb(std::vector<int>{c}, t);
     }
-    const std::string who = w.op == gop_weight && !w.name.empty() ? w.name : n.name;
+    const std::string who = weight_name(g, n);
     const int xbuf = buf_of(n.src[0]);
     materialise(t);
     const int obuf = n.buffer;

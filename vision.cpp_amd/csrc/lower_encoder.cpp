@@ -9,27 +9,23 @@ void lowering::patch_embed(int t) {
     graph_node& n = g.nodes[t];
     graph_node const& x = g.nodes[n.src[0]];
     const int ps = (int)n.ip[0], C = (int)x.ne[0], W = (int)x.ne[1], H = (int)x.ne[2], B = (int)x.ne[3];
-    packed_operand p = pack_rows(n.src[1], n.n_src == 3 ? n.src[2] : -1, (int)n.ne[0]);
+    product P;
+    pack_conv_rows(P, n, false);
+    packed_operand const& p = P.p;
     const int64_t M = (int64_t)B * (H / ps) * (W / ps);
     const int xbuf = buf_of(n.src[0]), pbuf = new_buffer((size_t)M * p.K * 2);
-    std::string who = n.name.empty() ? g.nodes[n.src[1]].name : n.name;
+    std::string who = n.name.empty() ? g.nodes[n.src[1]].name : n.name; // (not weight_name: the node's own name comes first here)
     auto xp = ptr(xbuf), pp = ptr(pbuf);
     const int Kp = p.K;
     emit("im2col_patches " + std::to_string(ps) + "x" + std::to_string(ps) + " M=" + std::to_string(M) + " <- " + who, {xbuf}, {pbuf},
          [=](void* st) { VX(vx_im2col_patches_f32(reinterpret_cast<const float*>(xp()), pp(), B, H, W, C, ps, Kp, st)); });
     if (n.ne[0] % 8) throw except("patch_embed %s: %lld output channels", who.c_str(), (long long)n.ne[0]);
     materialise(t);
-    const int obuf = n.buffer;
-    vx_gemm_args a;
-    memset(&a, 0, sizeof a);
-    a.lda = p.K; a.W = p.w; a.bias = p.bias; a.M = (int)M; a.N = p.N; a.K = p.K; a.n_valid = (int)n.ne[0]; a.ldo = n.ne[0]; a.epi = VX_EPI_F16;
-    auto op = ptr(obuf);
-    emit("gemm M=" + std::to_string(M) + " N=" + std::to_string(n.ne[0]) + " K=" + std::to_string(p.k_real) + " <- " + who, {pbuf}, {obuf}, [=](void* st) {
-        vx_gemm_args r = a;
-        r.A = pp();
-        r.out = op();
-        VX(vx_gemm_f16(&r, st));
-    });
+    P.in.buf = pbuf;
+    P.out.buf = n.buffer;
+    P.a.lda = p.K; P.a.M = (int)M; P.a.n_valid = (int)n.ne[0]; P.a.ldo = n.ne[0]; P.a.epi = VX_EPI_F16;
+    P.desc = "gemm M=" + std::to_string(M) + " N=" + std::to_string(n.ne[0]) + " K=" + std::to_string(p.k_real) + " <- " + who;
+    emit_product(P); // (no timing group of its own)
 }
 
 // q, k, v of an attention that are views of three linears over ONE input, read by nothing else: the three products become one GEMM
@@ -57,6 +53,10 @@ void lowering::find_qkv_groups() {
         if (!ok) continue;
         qkv_lin[t] = lin;
         qkv_first[std::min({lin[0], lin[1], lin[2]})] = t;
+        for (int i = 0; i < 3; ++i) { // the linears and their views are computed by the attention's q|k|v launch (fused_qkv, or the encoder chain's block launch)
+            claim(t, {lin[i]});
+            for (int v = n.src[i]; v != lin[i]; v = g.nodes[v].src[0]) claim(t, {v});
+        }
     }
 }
 void lowering::fused_qkv(int att) {
@@ -64,30 +64,27 @@ void lowering::fused_qkv(int att) {
     graph_node const& q = g.nodes[n.src[0]];
     const int64_t H = q.ne[1], T = q.ne[2], B = q.ne[3];
     auto const& lin = qkv_lin[att];
-    packed_operand p = pack_qkv(lin.data());
+    product P;
+    P.operand(pack_qkv(lin.data()));
+    packed_operand const& p = P.p;
     const int xs = g.nodes[lin[0]].src[0];
-    const int xbuf = buf_of(xs);
-    std::array<int, 3> hb;
+    P.in.buf = buf_of(xs);
+    std::array<int, 3>& hb = P.qkv;
     for (int i = 0; i < 3; ++i) hb[i] = new_buffer((size_t)(64 * H * T * B) * 2);
-    for (int i = 0; i < 3; ++i) { // the linears and their views are computed by this launch
-        skip[lin[i]] = 1;
-        for (int v = n.src[i]; v != lin[i]; v = g.nodes[v].src[0]) skip[v] = 1;
-    }
-    vx_gemm_args a;
-    memset(&a, 0, sizeof a);
-    a.lda = p.K; a.W = p.w; a.bias = p.bias; a.M = (int)(B * T); a.N = p.N; a.K = p.K; a.n_valid = p.N;
+    for (size_t c = 0; c < claimed_by.size(); ++c) // the linears and their views, as find_qkv_groups claimed them, are computed by this launch
+        if (claimed_by[c] == att) skip[c] = 1;
+    auto& a = P.a;
+    a.lda = p.K; a.M = (int)(B * T); a.n_valid = p.N;
     a.epi = VX_EPI_QKV;
     a.qkv_T = (int)T; a.qkv_H = (int)H;
     a.q_scale = n.fp[0] * 1.4426950408889634f; // the attention kernel works in the exp2 domain (VX_ATTN_Q_SCALE)
-    auto xp = ptr(xbuf), qp = ptr(hb[0]), kp = ptr(hb[1]), vp = ptr(hb[2]);
     char d[200];
     snprintf(d, sizeof d, "gemm[qkv heads-major] M=%d N=%d K=%d <- %s", a.M, p.N, p.k_real, g.nodes[g.nodes[lin[0]].src[1]].name.c_str());
-    emit(d, {xbuf}, {hb[0], hb[1], hb[2]}, [=](void* st) {
-        vx_gemm_args r = a;
-        r.A = xp(); r.q = qp(); r.k = kp(); r.vt = vp();
-        VX(vx_gemm_f16(&r, st));
-    });
-    tag("gemm_qkv", 2.0 * a.M * (double)p.N * p.k_real, (double)a.M * (p.k_real + p.N) * 2);
+    P.desc = d;
+    P.group = "gemm_qkv";
+    P.flops = 2.0 * a.M * (double)p.N * p.k_real;
+    P.bytes = (double)a.M * (p.k_real + p.N) * 2; // (without the operand's image)
+    emit_product(P);
     qkv_bufs[att] = hb;
 }
 
@@ -219,6 +216,7 @@ void lowering::find_window_groups() {
         window_group G;
         if (!needed[t] || !match_window_group(t, G)) continue;
         for (int v : G.views) skip[v] = 1;
+        claim(t, G.views);
         window_groups[t] = std::move(G);
     }
 }
@@ -360,7 +358,7 @@ static void put(std::vector<float>& v, const float* src, size_t n) { // n floats
 
 void lowering::emit_encoder() {
     auto values_or_null = [&](int t) -> const float* { return t >= 0 ? g.nodes[t].values() : nullptr; };
-    auto wname = [&](int t) { return t >= 0 ? (g.nodes[t].op == gop_weight && !g.nodes[t].name.empty() ? g.nodes[t].name : "#" + std::to_string(t)) : std::string("-"); };
+    auto wname = [&](int t) { return const_id(g, t); };
     enc_chain const& e = enc;
     graph_node const& tok = g.nodes[e.tok];
     graph_node const& pe = g.nodes[e.pe];
@@ -376,7 +374,9 @@ void lowering::emit_encoder() {
 
     // ---- tokens: patches (u8 -> f16 with the normalisation folded in, or from the f32 image), cls rows, patch GEMM whose epilogue adds
     // bias + position embedding and writes f32 token rows
-    packed_operand p = pack_rows(pe.src[1], pe.n_src == 3 ? pe.src[2] : -1, D);
+    product tokens;
+    pack_conv_rows(tokens, pe, false); // (pe.ne[0] == D: find_encoder_chain)
+    packed_operand const& p = tokens.p;
     const int Kp = p.K;
     const int pbuf = new_buffer((size_t)MP * Kp * 2), xbuf = new_buffer((size_t)M * D * 4);
     auto pp = ptr(pbuf), xp = ptr(xbuf);
@@ -402,16 +402,16 @@ void lowering::emit_encoder() {
     emit("cls_rows B=" + std::to_string(B), {}, {xbuf}, [=](void* st) { VX(vx_write_cls_rows(reinterpret_cast<float*>(xp()), cls, pos, B, T, D, st)); });
     tag("preprocess");
     {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
-        a.lda = Kp; a.W = p.w; a.bias = p.bias; a.M = (int)MP; a.N = p.N; a.K = p.K; a.n_valid = D;
+        auto& a = tokens.a;
+        a.lda = Kp; a.M = (int)MP; a.n_valid = D;
         a.epi = VX_EPI_TOKENS; a.ldo = D; a.pos = pos; a.tokens_P = Pn;
-        emit("gemm[tokens f32: + bias + pos] M=" + std::to_string(MP) + " N=384 K=" + std::to_string(p.k_real) + " <- " + g.nodes[pe.src[1]].name, {pbuf}, {xbuf}, [=](void* st) {
-            vx_gemm_args r = a;
-            r.A = pp(); r.out = xp();
-            VX(vx_gemm_f16(&r, st));
-        });
-        tag("patch_embed", 2.0 * MP * D * p.k_real, (double)MP * Kp * 2 + (double)M * D * 4);
+        tokens.in.buf = pbuf;
+        tokens.out.buf = xbuf;
+        tokens.desc = "gemm[tokens f32: + bias + pos] M=" + std::to_string(MP) + " N=384 K=" + std::to_string(p.k_real) + " <- " + g.nodes[pe.src[1]].name;
+        tokens.group = "patch_embed";
+        tokens.flops = 2.0 * MP * D * p.k_real;
+        tokens.bytes = (double)MP * Kp * 2 + (double)M * D * 4;
+        emit_product(tokens);
     }
     auto copy_out = [&](int node, const char* what) { // a graph output inside the group: the residual stream as it stands, f32
         graph_node& n = g.nodes[node];

@@ -19,12 +19,6 @@ namespace visp {
 
 namespace {
 
-std::string weight_name(graph const& g, graph_node const& n) {
-    graph_node const& w = g.nodes[n.src[1]];
-    return w.op == gop_weight && !w.name.empty() ? w.name : n.name;
-}
-bool same_shape(graph_node const& a, graph_node const& b) { return a.ne[0] == b.ne[0] && a.ne[1] == b.ne[1] && a.ne[2] == b.ne[2] && a.ne[3] == b.ne[3]; }
-
 constexpr float AGC_SLOPE = 0.2f, AGC_GAIN = 1.41421356f, AGC_CLAMP = 256.0f; // what VX_EPI_LRELU_AGC computes (kernels_gemm.hip)
 
 } // namespace
@@ -97,47 +91,35 @@ bool lowering::match_upfir_group(int t, upfir_group& G) const {
 void lowering::find_migan_groups() {
     if (!g.fused_models) return;
     const int N = (int)g.nodes.size();
-    migan_claimed.assign(N, 0);
-    // what other lowerings decided to compute inside a launch of theirs without marking it in skip[] (they absorb it when the launch is emitted)
-    for (auto const& sc : silu_convs)
-        for (int c : {sc.second.silu, sc.second.add, sc.second.rep1, sc.second.rep_add})
-            if (c >= 0) migan_claimed[c] = 1;
-    for (auto const& l : launch_of_last) migan_claimed[l.first] = 1;
-    for (auto const& d : deform_groups)
-        for (int c : {d.second.mul, d.second.add, d.second.relu})
-            if (c >= 0) migan_claimed[c] = 1;
-    std::vector<char> ours(N, 0); // ... as against the nodes of this file's groups
-    auto claim = [&](std::vector<int> const& nodes, int last) {
-        for (int c : nodes) {
-            migan_claimed[c] = 1;
-            ours[c] = 1;
-            if (c != last) skip[c] = 1;
-        }
-    };
+    // a group is keyed on its LAST node, where its launch is emitted; the nodes in front of it are computed by nobody
     std::vector<char> group_last(N, 0);
+    auto accept = [&](std::vector<int> const& nodes, int last) {
+        claim(last, nodes);
+        group_last[last] = 1;
+        for (int c : nodes)
+            if (c != last) skip[c] = 1;
+    };
     for (int t = 0; t < N; ++t) {
-        if (!needed[t] || skip[t] || migan_claimed[t] || g.nodes[t].constant) continue;
+        if (!free_node(t) || g.nodes[t].constant) continue;
         graph_node const& n = g.nodes[t];
         if (n.op == gop_interpolate) { // (c)
             upfir_group G;
             if (!match_upfir_group(t, G)) continue;
             std::vector<int> all = G.members;
             all.insert(all.end(), G.tail.absorbed.begin(), G.tail.absorbed.end());
-            claim(all, G.tail.last);
-            group_last[G.tail.last] = 1;
+            accept(all, G.tail.last);
             upfir_at[G.tail.last] = G;
         } else if (n.op == gop_conv_2d_depthwise && n.dtype == gdt_f16) { // (a): only with a scale or a clamp; a bare leaky_relu is depthwise_conv's own epilogue
             agc_tail T = match_agc_tail(t, false, false);
             if (!T.act || (T.gain == 1.0f && T.clamp == 0.0f)) continue;
             std::vector<int> all = T.absorbed;
             all.push_back(t);
-            claim(all, T.last);
-            group_last[T.last] = 1;
+            accept(all, T.last);
             dw_agc_at[T.last] = {t, T};
         } else if (n.op == gop_conv_2d && n.dtype == gdt_f16 && n.ne[0] % 8 == 0) { // (b)
             graph_node const &w = g.nodes[n.src[1]], &x = g.nodes[n.src[0]];
             if (w.ne[1] != 1 || w.ne[2] != 1 || n.ip[0] != 1 || n.ip[1] != 0 || (n.n_src == 3 && !g.nodes[n.src[2]].constant) || x.constant) continue;
-            const bool image = x.dtype == gdt_f32 && x.op == gop_input && (x.ne[0] == 3 || x.ne[0] == 4);
+            const bool image = x.op == gop_input && image8_input(x);
             if (!image) {
                 // an f16 map in a buffer of its own, as wide as its pixels: not one a product may have written with padded rows, nor a view another pattern reads in place
                 const int32_t xop = g.nodes[root_view(n.src[0])].op;
@@ -153,10 +135,10 @@ void lowering::find_migan_groups() {
             // without the epilogue's exact constants: a bare conv, taken only behind a group's map (its rows then need no padded copy either)
             if (!agc) {
                 if (!group_last[root_view(n.src[0])]) continue;
-                // ... and only where no other lowering has plans for it: a SiLU group or a RepConv member, a conv that writes into its slice of a concat
-                // (lower_yolo.cpp), or one whose reader the generic product would take into its epilogue (gelu / relu / LayerScale / a residual add)
-                if (silu_convs.count(t) || rep_member.count(t) || cat_slot.count(t)) continue;
-                if (const int c = sole_consumer(t); c >= 0 && !ours[c] &&
+                // ... and only where no other lowering has plans for it: a SiLU group, a conv that writes into its slice of a concat (lower_yolo.cpp), or
+                // one whose reader the generic product would take into its epilogue (gelu / relu / LayerScale / a residual add)
+                if (silu_convs.count(t) || cat_slot.count(t)) continue;
+                if (const int c = sole_consumer(t); c >= 0 && !(claimed_by[c] >= 0 && group_last[claimed_by[c]]) && // (a reader in a group of this file's takes t as it is)
                     (g.nodes[c].op == gop_gelu || g.nodes[c].op == gop_relu || g.nodes[c].op == gop_add || g.nodes[c].op == gop_mul))
                     continue;
                 T = agc_tail{};
@@ -164,8 +146,7 @@ void lowering::find_migan_groups() {
             }
             std::vector<int> all = T.absorbed;
             all.push_back(t);
-            claim(all, T.last);
-            group_last[T.last] = 1;
+            accept(all, T.last);
             conv_agc_at[T.last] = {t, T};
         }
     }
@@ -285,16 +266,13 @@ void lowering::migan_depthwise(int last, int t, agc_tail const& T) {
 
 void lowering::migan_product(int last, int t, agc_tail const& T) {
     graph_node const& n = g.nodes[t];
-    const int xs = n.src[0], wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
+    const int xs = n.src[0];
     graph_node const& x = g.nodes[xs];
     const std::string who = weight_name(g, n);
-    vx_gemm_args a;
-    memset(&a, 0, sizeof a);
-    packed_operand p;
-    const bool image8_in = x.dtype == gdt_f32;
-    int xbuf;
+    product P;
+    auto& a = P.a;
+    const bool image8_in = image8_input(x); // (the only f32 input find_migan_groups admits)
     std::string kind;
-    size_t tail_at = 0; // where the zeroed slack behind the A rows begins (0: none needed)
     a.M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
     if (T.act) {
         // VX_EPI_LRELU_AGC exists on the plain product only, whose loader reads whole 64-wide k tiles. Where the rows are narrower (Cin % 64 != 0, the 8-channel
@@ -303,48 +281,38 @@ void lowering::migan_product(int last, int t, agc_tail const& T) {
         // launch zeroes first (the buffer is among the launch's writes for that). 0 * inf is a NaN, so this is done only where the graph proves the map finite
         // (value_bound: every map MI-GAN feeds here is clamped or a FIR of a clamped map); any other map is copied into padded rows, as per node, and so is a
         // graph input or output, which may be bound to a caller's buffer that has no slack. (The 8-channel pixels of the f32 image are as finite as the image.)
-        p = image8_in ? pack_image8(wt, bt, (int)n.ne[0]) : pack_rows(wt, bt, (int)n.ne[0]);
-        const int cin = image8_in ? 8 : (int)x.ne[0];
-        bool copy = !image8_in && cin != p.K && !(value_bound(xs) < 65504.0);
-        for (int v = xs; !image8_in && cin != p.K && v >= 0; v = g.nodes[v].alias_of) copy = copy || g.nodes[v].op == gop_input || g.nodes[v].is_output; // xs and every view down to its root
+        pack_conv_rows(P, n, image8_in);
+        const int cin = image8_in ? 8 : (int)x.ne[0], Kp = P.p.K;
+        bool copy = !image8_in && cin != Kp && !(value_bound(xs) < 65504.0);
+        for (int v = xs; !image8_in && cin != Kp && v >= 0; v = g.nodes[v].alias_of) copy = copy || g.nodes[v].op == gop_input || g.nodes[v].is_output; // xs and every view down to its root
         if (copy) {
-            xbuf = padded_rows(xs, cin, p.K, a.M, who);
-            a.lda = p.K;
+            P.in.buf = padded_rows(xs, cin, Kp, a.M, who);
+            a.lda = Kp;
         } else {
-            xbuf = image8_in ? image_pad8(xs) : buf_of(xs);
+            P.in.buf = image8_in ? image_pad8(xs) : buf_of(xs);
             a.lda = cin;
-            if (cin != p.K) tail_at = (size_t)a.M * cin * 2;
+            if (cin != Kp) P.zero_at = (size_t)a.M * cin * 2; // the slack behind the A rows
         }
         kind = "gemm(conv1x1)";
     } else { // the plain f16 epilogue: the implicit conv reads rows of any width % 8
-        p = pack_rows(wt, bt, (int)n.ne[0]);
-        xbuf = buf_of(xs);
-        a.conv_kh = 1; a.conv_kw = 1; a.conv_stride = 1; a.conv_pad = 0;
-        a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = (int)x.ne[0];
-        a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
+        pack_conv_rows(P, n, false);
+        P.in.buf = buf_of(xs);
+        conv_geometry(a, n, x, g.nodes[n.src[1]]);
         kind = "conv1x1";
     }
-    a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.n_valid = (int)n.ne[0];
+    a.n_valid = (int)n.ne[0];
     a.ldo = n.ne[0];
     a.epi = T.act ? VX_EPI_LRELU_AGC : VX_EPI_F16;
     if (T.plane >= 0) { a.noise = plane_f32(T.plane); a.noise_hw = (int)(n.ne[1] * n.ne[2]); }
-    std::vector<int> reads = {xbuf};
-    std::function<char*()> rp;
-    if (T.res >= 0) { reads.push_back(buf_of(T.res)); rp = ptr(reads.back()); }
+    if (T.res >= 0) P.res1.buf = buf_of(T.res);
     materialise(last);
-    const int obuf = g.nodes[last].buffer;
-    auto xp = ptr(xbuf), op = ptr(obuf);
+    P.out.buf = g.nodes[last].buffer;
     char d[360];
-    snprintf(d, sizeof d, "%s%s M=%d N=%d K=%d <- %s", kind.c_str(), tail_tag(T).c_str(), a.M, (int)n.ne[0], p.k_real, who.c_str());
-    emit(d, reads, tail_at ? std::vector<int>{obuf, xbuf} : std::vector<int>{obuf}, [=](void* st) {
-        vx_gemm_args r = a;
-        r.A = xp();
-        r.out = op();
-        if (rp) r.res1 = rp();
-        if (tail_at) VX(vx_memset(xp() + tail_at, 0, 128, st));
-        VX(vx_gemm_f16(&r, st));
-    });
-    tag("conv", 2.0 * a.M * (double)p.n_real * p.k_real, (double)a.M * (p.k_real + n.ne[0] * (T.res >= 0 ? 2 : 1)) * 2 + (double)p.N * p.K * 2);
+    snprintf(d, sizeof d, "%s%s M=%d N=%d K=%d <- %s", kind.c_str(), tail_tag(T).c_str(), a.M, (int)n.ne[0], P.p.k_real, who.c_str());
+    P.desc = d;
+    P.group = "conv";
+    P.work(P.p.k_real + (T.res >= 0 ? (double)n.ne[0] : 0.0), (double)n.ne[0]);
+    emit_product(P);
 }
 
 // ggml_clamp on an f16 activation

@@ -70,6 +70,7 @@ void lowering::run() {
     skip.assign(N, 0);
     uses.assign(N, 0);
     relu_on_load.assign(N, 0);
+    claimed_by.assign(N, -1);
     consumers.assign(N, {});
     bool any_out = false;
     for (int t = N - 1; t >= 0; --t) {

@@ -3,6 +3,15 @@
 
 namespace visp {
 
+std::string weight_name(graph const& g, graph_node const& n) {
+    graph_node const& w = g.nodes[n.src[1]];
+    return w.op == gop_weight && !w.name.empty() ? w.name : n.name;
+}
+std::string const_id(graph const& g, int t) {
+    if (t < 0) return "-";
+    return g.nodes[t].op == gop_weight && !g.nodes[t].name.empty() ? g.nodes[t].name : "#" + std::to_string(t);
+}
+
 // device image of constant t in `role`: model weights are cached in the weight store (shared by every graph over the model),
 // constants folded inside this graph belong to the graph
 // `with`: names of the other weights a derived image was made from (a folded LayerScale vector, the k and v parts of a fused
@@ -67,7 +76,7 @@ packed_operand lowering::pack_matrix(int wt, pack_role role, int n, int k, std::
     // LayerScale folded into the operand: W' = f16(lambda[n] * W[n, :]), b' = lambda[n] * b[n] (what csrc/depthany.cpp does for the
     // block kernel: the product's epilogue can then take the residual)
     const float* lam = scale_t >= 0 ? g.nodes[scale_t].values() : nullptr;
-    const std::string with = scale_t >= 0 ? "*" + (g.nodes[scale_t].op == gop_weight && !g.nodes[scale_t].name.empty() ? g.nodes[scale_t].name : "#" + std::to_string(scale_t)) : std::string();
+    const std::string with = scale_t >= 0 ? "*" + const_id(g, scale_t) : std::string();
     p.n_real = n; p.k_real = k;
     p.N = round_up(n, n > 64 ? 64 : 32);
     p.K = round_up(k, 64);
@@ -216,8 +225,7 @@ void* lowering::pack_deform(int wt, int* n_pad) {
 packed_operand lowering::pack_deform_offsets(int w_off, int b_off, int w_mod, int b_mod) {
     graph_node const &wo = g.nodes[w_off], &wm = g.nodes[w_mod];
     const int n_off = (int)wo.ne[3], n_mod = (int)wm.ne[3], k = (int)(wo.n_elements() / n_off);
-    auto id = [&](int t) { return t < 0 ? std::string("-") : (g.nodes[t].op == gop_weight && !g.nodes[t].name.empty() ? g.nodes[t].name : "#" + std::to_string(t)); };
-    const std::string with = id(w_mod) + "|" + id(b_off) + "|" + id(b_mod);
+    const std::string with = const_id(g, w_mod) + "|" + const_id(g, b_off) + "|" + const_id(g, b_mod);
     packed_operand p;
     p.n_real = n_off + n_mod; p.k_real = k;
     p.N = round_up(p.n_real, p.n_real > 64 ? 64 : 32);
@@ -265,7 +273,7 @@ packed_operand lowering::pack_image8(int wt, int bias_t, int n) {
 packed_operand lowering::pack_rep_conv(int w3, int b3, int w1, int b1) {
     graph_node const &a = g.nodes[w3], &b = g.nodes[w1];
     const int n = (int)a.ne[3], cin = (int)a.ne[0], k = 9 * cin;
-    const std::string with = "+" + (b.op == gop_weight && !b.name.empty() ? b.name : "#" + std::to_string(w1));
+    const std::string with = "+" + const_id(g, w1);
     packed_operand p;
     p.n_real = n; p.k_real = k;
     p.N = round_up(n, n > 64 ? 64 : 32);

@@ -13,16 +13,6 @@
 
 namespace visp {
 
-namespace {
-
-bool is_3x3_s1_p1(graph_node const& c, graph_node const& w) { return w.ne[1] == 3 && w.ne[2] == 3 && c.ip[0] == 1 && c.ip[1] == 1; }
-std::string weight_name(graph const& g, graph_node const& n) {
-    graph_node const& w = g.nodes[n.src[1]];
-    return w.op == gop_weight && !w.name.empty() ? w.name : n.name;
-}
-
-} // namespace
-
 bool lowering::channels_only(graph_node const& s) const {
     graph_node const& x = g.nodes[s.src[0]];
     if (s.op != gop_slice || s.constant || s.is_output || x.dtype != gdt_f16 || s.ip[2] != 1) return false;
@@ -47,7 +37,7 @@ bool lowering::gemm_family_reader(int c, int view) const {
     while (v != view && g.nodes[v].op == gop_cont) v = g.nodes[v].src[0];
     if (n.op != gop_conv_2d || n.constant || n.dtype != gdt_f16 || n.ne[0] % 8 || v != view) return false;
     if (silu_convs.count(c) || rep_member.count(c)) return true;
-    return !is_3x3_s1_p1(n, g.nodes[n.src[1]]); // (those may go to the LDS-ring kernels)
+    return !is_conv3x3(n, g.nodes[n.src[1]]); // (those may go to the LDS-ring kernels)
 }
 // every reader of t (outside `chain`, the concat nodes it is placed by) can address it inside a wider map
 bool lowering::in_place_readers_ok(int t, std::vector<int> const& chain) const {
@@ -93,9 +83,7 @@ bool lowering::match_silu_group(int t, silu_group& G) const {
     if (a >= 0 && g.nodes[a].op == gop_add) { // the shortcut of a RepBottleneck, added after the activation
         const int o = g.nodes[a].src[0] == c ? g.nodes[a].src[1] : g.nodes[a].src[0];
         graph_node const& on = g.nodes[o];
-        bool same = o != c && !on.constant && on.dtype == gdt_f16 && o < std::min(t, G.rep1 >= 0 ? G.rep1 : t);
-        for (int i = 0; i < 4; ++i) same = same && on.ne[i] == n.ne[i];
-        if (same) { G.add = a; G.res = o; }
+        if (o != c && !on.constant && on.dtype == gdt_f16 && o < std::min(t, G.rep1 >= 0 ? G.rep1 : t) && same_shape(on, n)) { G.add = a; G.res = o; }
     }
     return true;
 }
@@ -135,7 +123,7 @@ bool lowering::placeable_launch(int s) const {
     if (n.op == gop_pool_2d) return true;
     if (n.op == gop_interpolate) return (n.ip[2] & 255) == 0; // nearest (a planar source read by one 3x3 conv never feeds a concat: nearest_into_reader)
     if (auto it = launch_of_last.find(s); it != launch_of_last.end()) return g.nodes[it->second].op == gop_conv_2d;
-    if (n.op != gop_conv_2d || silu_convs.count(s) || rep_member.count(s) || is_3x3_s1_p1(n, g.nodes[n.src[1]])) return false;
+    if (n.op != gop_conv_2d || silu_convs.count(s) || rep_member.count(s) || is_conv3x3(n, g.nodes[n.src[1]])) return false;
     graph_node const& x = g.nodes[n.src[0]];
     if (x.op == gop_interpolate || x.op == gop_relu || x.dtype != gdt_f16 || (n.n_src == 3 && !g.nodes[n.src[2]].constant)) return false;
     for (int c : consumers[s])
@@ -152,12 +140,14 @@ void lowering::find_yolo_groups() {
         silu_convs[t] = G;
         if (G.rep1 >= 0) { rep_member[G.rep1] = t; skip[G.rep1] = 1; } // (wherever it stands in node order, the 3x3 conv's launch computes it)
         launch_of_last[G.add >= 0 ? G.add : G.silu] = t;
+        claim(t, {G.rep1, G.rep_add, G.silu, G.add}); // (absorbed when the launch is emitted)
     }
     for (int t = 0; t < N; ++t) { // (e)
         dfl_group G;
         if (!needed[t] || !match_dfl_group(t, G)) continue;
         dfl_groups[t] = G;
         for (int c : G.absorbed) skip[c] = 1;
+        claim(t, G.absorbed);
     }
     // (c): in node order, so that a slice of a slice sees its source's decision; readers that are slices themselves are looked at once every
     // candidate is known (a candidate whose reader fails is dropped, which may drop others: repeat until nothing changes)
@@ -298,70 +288,47 @@ void lowering::yolo_product(int t) {
     graph_node& n = g.nodes[t];
     silu_group G;
     if (auto it = silu_convs.find(t); it != silu_convs.end()) G = it->second;
-    const int xs = n.src[0], wt = n.src[1], bt = n.n_src == 3 ? n.src[2] : -1;
+    const int xs = n.src[0];
     graph_node const& x = g.nodes[xs];
     const std::string who = weight_name(g, n);
-    vx_gemm_args a;
-    memset(&a, 0, sizeof a);
-    packed_operand p;
-    located in;
+    product P;
+    auto& a = P.a;
     std::string kind;
     if (n.op == gop_linear) {
-        p = pack_rows(wt, bt, (int)n.ne[0]);
+        pack_conv_rows(P, n, false);
         a.M = (int)(x.n_elements() / x.ne[0]);
-        a.lda = p.K;
-        in = {padded_rows(xs, p.k_real, p.K, a.M, who), 0, p.K};
+        a.lda = P.p.K;
+        P.in = {padded_rows(xs, P.p.k_real, P.p.K, a.M, who), 0, P.p.K};
         kind = "gemm";
     } else {
-        graph_node const& w = g.nodes[wt];
-        const int kw = (int)w.ne[1], kh = (int)w.ne[2], stride = (int)n.ip[0], pad = (int)n.ip[1];
-        const bool image8_in = x.dtype == gdt_f32 && x.ne[0] == 3;
+        graph_node const& w = g.nodes[n.src[1]];
+        const bool image8_in = image8_input(x); // (the SiLU matcher admits the 3-channel image only; nothing else of f32 gets here)
         if (!image8_in && x.ne[0] % 8) throw except("conv_2d %s: Cin = %lld must be a multiple of 8", who.c_str(), (long long)x.ne[0]);
-        if (G.rep1 >= 0) {
-            graph_node const& o = g.nodes[G.rep1];
-            p = pack_rep_conv(wt, bt, o.src[1], o.n_src == 3 ? o.src[2] : -1);
-        } else p = image8_in ? pack_image8(wt, bt, (int)n.ne[0]) : pack_rows(wt, bt, (int)n.ne[0]);
-        in = image8_in ? located{image_pad8(xs), 0, 8} : locate(xs);
+        pack_conv_rows(P, n, image8_in, G.rep1);
+        P.in = image8_in ? located{image_pad8(xs), 0, 8} : locate(xs);
         a.M = (int)(n.ne[1] * n.ne[2] * n.ne[3]);
-        a.conv_kh = kh; a.conv_kw = kw; a.conv_stride = stride; a.conv_pad = pad;
-        a.conv_H = (int)x.ne[2]; a.conv_W = (int)x.ne[1]; a.conv_Cin = image8_in ? 8 : (int)x.ne[0];
-        a.conv_OH = (int)n.ne[2]; a.conv_OW = (int)n.ne[1];
-        a.conv_pix = in.pix;
-        kind = "conv" + std::to_string(kw) + "x" + std::to_string(kh) + (stride > 1 ? "s" + std::to_string(stride) : "") + (G.rep1 >= 0 ? "[+conv1x1 folded]" : "") +
-               place_tag("in", in, a.conv_Cin);
+        conv_geometry(a, n, x, w);
+        a.conv_pix = P.in.pix;
+        kind = "conv" + std::to_string(a.conv_kw) + "x" + std::to_string(a.conv_kh) + (a.conv_stride > 1 ? "s" + std::to_string(a.conv_stride) : "") + (G.rep1 >= 0 ? "[+conv1x1 folded]" : "") +
+               place_tag("in", P.in, a.conv_Cin);
     }
-    // the nodes this launch computes besides its own
-    epilogue e;
-    for (int c : {G.rep1, G.rep_add, G.silu, G.add})
-        if (c >= 0) e.absorbed.push_back(c);
-    absorb(e, t);
+    absorb(std::vector<int>{G.rep1, G.rep_add, G.silu, G.add}, t); // the nodes this launch computes besides its own
     const int last = G.add >= 0 ? G.add : (G.silu >= 0 ? G.silu : t);
-    std::vector<int> reads = {in.buf};
-    located res{-1, 0, 0};
     if (G.res >= 0) {
-        res = locate(G.res);
-        reads.push_back(res.buf);
-        a.ld_res1 = res.pix;
+        P.res1 = locate(G.res);
+        a.ld_res1 = P.res1.pix;
     }
-    const located out = output_slot(t, last);
-    a.W = p.w; a.bias = p.bias; a.N = p.N; a.K = p.K; a.n_valid = (int)n.ne[0];
-    a.ldo = out.pix;
+    P.out = output_slot(t, last);
+    a.n_valid = (int)n.ne[0];
+    a.ldo = P.out.pix;
     a.epi = G.silu >= 0 ? VX_EPI_SILU : VX_EPI_F16;
     char d[360];
-    snprintf(d, sizeof d, "%s%s%s%s M=%d N=%d K=%d <- %s", kind.c_str(), G.silu >= 0 ? "[silu]" : "", G.res >= 0 ? "[+res]" : "", place_tag("out", out, n.ne[0]).c_str(), a.M, (int)n.ne[0],
-             p.k_real, who.c_str());
-    auto xp = ptr(in.buf), op = ptr(out.buf);
-    std::function<char*()> rp;
-    if (G.res >= 0) rp = ptr(res.buf);
-    const int64_t in_off = in.off, out_off = out.off, res_off = res.off;
-    emit(d, reads, {out.buf}, [=](void* st) {
-        vx_gemm_args r = a;
-        r.A = xp() + in_off * 2;
-        r.out = op() + out_off * 2;
-        if (rp) r.res1 = rp() + res_off * 2;
-        VX(vx_gemm_f16(&r, st));
-    });
-    tag(n.op == gop_linear ? "gemm" : "conv", 2.0 * a.M * (double)p.n_real * p.k_real, (double)a.M * (p.k_real + n.ne[0] * (G.res >= 0 ? 2 : 1)) * 2 + (double)p.N * p.K * 2);
+    snprintf(d, sizeof d, "%s%s%s%s M=%d N=%d K=%d <- %s", kind.c_str(), G.silu >= 0 ? "[silu]" : "", G.res >= 0 ? "[+res]" : "", place_tag("out", P.out, n.ne[0]).c_str(), a.M, (int)n.ne[0],
+             P.p.k_real, who.c_str());
+    P.desc = d;
+    P.group = n.op == gop_linear ? "gemm" : "conv";
+    P.work(P.p.k_real + (G.res >= 0 ? (double)n.ne[0] : 0.0), (double)n.ne[0]);
+    emit_product(P);
 }
 
 // ggml_pool_2d: one launch of kernels_pool.hip; with fused models it reads a channel slice where it lies and writes into its slice of a concat

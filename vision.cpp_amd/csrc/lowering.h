@@ -1,13 +1,15 @@
 // The lowering of a graph into its launch list (graph_allocate, graph.h): internal to the graph layer. One struct, its state gathered
 // here, its member functions defined by concern in
 //   lower_weights.cpp  device images of weights and constants (cached / upload / pack_*)
-//   lower_conv.cpp     matrix products and convolutions with their fused epilogues, the planar maps, the DPT neck / head patterns
+//   lower_conv.cpp     the one emitter of a GEMM-family launch (product, emit_product), matrix products and convolutions with their fused epilogues,
+//                      the planar maps, the DPT neck / head patterns
 //   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
 //   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
 //   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
-// a `return false` leaves the lowering's state as it was.
+// a `return false` leaves the lowering's state as it was. A finder that accepts a group says so in ONE table (claim): a matcher asks free_node()
+// whether a node may still join a group of its own and needs to know nothing about the other families.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -28,6 +30,11 @@ struct packed_operand {
     int N = 0, K = 0, n_real = 0, k_real = 0;
 };
 
+std::string weight_name(graph const& g, graph_node const& n); // of the node's second operand if that is a named weight, else the node's own name
+std::string const_id(graph const& g, int t);                   // a key for the constant t: its name, "#index" if it has none, "-" for t < 0
+bool is_conv3x3(graph_node const& c, graph_node const& w);     // conv_2d on a constant 3x3 kernel, stride 1, pad 1
+bool same_shape(graph_node const& a, graph_node const& b);
+
 struct lowering {
     graph& g;
 
@@ -36,6 +43,9 @@ struct lowering {
     std::vector<int> uses;
     std::vector<std::vector<int>> consumers;
     std::vector<char> relu_on_load; // conv node -> the ReLU in front of it is applied by its loader
+    // node -> the anchor node of the group whose launch will compute it, or -1: written by claim() when a finder accepts a group. skip[] keeps its own
+    // meaning and timing (some groups set it when they match, others when their launch is emitted); this table is what matchers ask besides
+    std::vector<int> claimed_by;
 
     // ---- the launch list's buffer traffic (emit; read by plan_arena)
     std::vector<std::pair<std::vector<int>, std::vector<int>>> io; // per launch: buffers read, buffers written
@@ -78,6 +88,50 @@ struct lowering {
         std::vector<int> views;
         std::vector<enc_layer> layers;
     } enc;
+
+    // ---- deformable-conv groups (lower_conv.cpp)
+    // conv_2d(offset, x), scale(sigmoid(conv_2d(modulator, x)), s), conv_2d_deform(x, W, ., .) [-> mul(c) -> add(c) -> relu] (birefnet.cpp:83-92, 110-115)
+    struct deform_group {
+        int off = -1, mod = -1, sig = -1, scl = -1; // the offset conv, the modulator conv, its sigmoid and scale nodes
+        int mul = -1, add = -1, relu = -1;          // the per-channel epilogue behind the deformable conv
+        float s = 1.0f;
+    };
+    std::map<int, deform_group> deform_groups;      // conv_2d_deform node -> its group (g.fused_models)
+
+    // ---- the packed-bias window attention (lower_encoder.cpp)
+    // split_qkv(.., 1) of nn.cpp:182-208 feeding a masked attention at head_dim 32 with a constant per-head bias (mobile-sam.cpp:124-132):
+    // linear -> reshape -> permute(0, 3, 1, 2) -> cont -> 3 x (slice -> reshape) -> attention_masked
+    struct window_group { int lin = -1; std::vector<int> views; }; // the q|k|v linear; the nodes between it and the attention, computed by nobody
+    std::map<int, window_group> window_groups;      // attention_masked node -> its group (g.fused_models)
+
+    // ---- SiLU-conv / channel-split / channel-concat networks (lower_yolo.cpp; all of it g.fused_models only)
+    struct located { int buf; int64_t off, pix; };  // a map inside a wider one: buffer, first channel, elements between pixels; a buffer of its own is {buf, 0, width}
+    // conv_2d / linear -> silu [-> add(map computed before)], or silu(add(conv3x3(x), conv1x1(x))) keyed on the 3x3 conv: one GEMM-family launch
+    struct silu_group { int silu = -1, add = -1, res = -1, rep1 = -1, rep_add = -1; };
+    std::map<int, silu_group> silu_convs;              // product node -> what its launch computes besides
+    std::map<int, int> rep_member;                     // the 1x1 conv of a folded RepConv -> its 3x3 conv
+    std::map<int, int> launch_of_last;                 // last node of a silu group -> its product node
+    std::map<int, std::pair<int, int>> chan_slice;     // slice of channels [c0, c1) only -> (source, c0): no launch, its readers address the source
+    struct cat_source { int node; int c0; bool placed; };
+    std::map<int, std::vector<cat_source>> cat_sources; // top concat of a dimension-0 chain with a placeable source -> its flattened sources
+    std::map<int, std::pair<int, int>> cat_slot;       // last node of a launch -> (top concat, first channel) it writes into
+    std::map<int, located> in_place;                   // node without a buffer of its own -> where it lives (set when its launch is emitted)
+    struct dfl_group { int map = -1, c0 = 0, n = 0, groups = 0, proj = -1; std::vector<int> absorbed; };
+    std::map<int, dfl_group> dfl_groups;               // sum_rows node -> slice -> [cont] -> reshape -> soft_max -> mul(constant) in front of it
+
+    // ---- the node groups of MI-GAN (lower_migan.cpp; g.fused_models only)
+    // what a launch takes over from the nodes behind it: [+ plane constant] [leaky_relu [scale] [clamp(-c, c)]] [+ map]
+    struct agc_tail {
+        int plane = -1, res = -1, last = -1;
+        bool act = false;
+        float slope = 0.0f, gain = 1.0f, clamp = 0.0f;
+        std::vector<int> absorbed;
+    };
+    struct upfir_group { int src = -1, fir = -1; std::vector<int> members; agc_tail tail; }; // the map upsampled, the 4x4 kernel, interpolate .. [cont]
+    std::map<int, upfir_group> upfir_at;                      // LAST node of a group -> the group its launch computes
+    std::map<int, std::pair<int, agc_tail>> dw_agc_at;        // last node -> (conv_2d_depthwise node, its tail)
+    std::map<int, std::pair<int, agc_tail>> conv_agc_at;      // last node -> (1x1 conv_2d node, its tail)
+    std::map<int, double> bound_memo;                         // value_bound's results
 
     explicit lowering(graph& gr) : g(gr) {}
     void run(); // the whole lowering: fills g.launches / g.buffers / the arena plan
@@ -133,6 +187,16 @@ struct lowering {
             return b.external ? static_cast<char*>(b.external) : static_cast<char*>(gp->arena.ptr) + b.offset;
         };
     }
+    // a finder accepted a group: `anchor`'s launch will compute `nodes` (entries < 0 are left out). Two groups never share a node
+    void claim(int anchor, std::vector<int> const& nodes) {
+        for (int c : nodes) {
+            if (c < 0) continue;
+            if (claimed_by[c] >= 0 && claimed_by[c] != anchor)
+                throw except("graph: internal: node %d (%s) is claimed by the group of node %d and by the group of node %d", c, graph_op_name(g.nodes[c].op), claimed_by[c], anchor);
+            claimed_by[c] = anchor;
+        }
+    }
+    bool free_node(int c) const { return c >= 0 && needed[c] && !skip[c] && claimed_by[c] < 0; } // c may still join a group: no launch computes it yet
     // src[0]'s buffer in, a freshly materialised buffer of t out (and `scratch_bytes` of a further buffer the launch writes): one launch
     void map_launch(int t, std::string desc, std::function<void(char* x, char* out, char* scratch, void* stream)> run, size_t scratch_bytes = 0);
 
@@ -157,6 +221,29 @@ struct lowering {
     packed_operand pack_image8(int wt, int bias_t, int n);
 
     // ---- lower_conv.cpp
+    // One launch of the GEMM family (vx_gemm_f16, or vx_conv3x3_f16 where `halo` allows and the arguments fit), planned as data: everything but the
+    // run-time addresses. The planners (gemm_like, yolo_product, migan_product, ..) decide and fill it; emit_product turns it into the launch.
+    struct product {
+        vx_gemm_args a;                                   // zeroed; A / out / res1 / res2 / q / k / vt are set when the launch runs
+        packed_operand p;
+        located in{-1, 0, 0}, out{-1, 0, 0}, res1{-1, 0, 0}; // where A, the output and the first residual lie (buf < 0: none; pix is the planner's to put into `a`)
+        int res2 = -1;                                    // the second residual's buffer
+        std::array<int, 3> qkv{-1, -1, -1};               // VX_EPI_QKV: the head-major q, k, v buffers it writes
+        size_t zero_at = 0;                               // byte offset into A's buffer of 128 bytes of slack to zero first (0: none)
+        bool halo = false;                                // vx_conv3x3_f16 may take the launch
+        std::string desc, group;
+        double flops = 0, bytes = 0;
+        product() { memset(&a, 0, sizeof a); }
+        void operand(packed_operand const& q) { p = q; a.W = q.w; a.bias = q.bias; a.N = q.N; a.K = q.K; }
+        void work(double reads_per_row, double writes_per_row) { // 2 M N K, and the rows read and written plus the operand's image
+            flops = 2.0 * a.M * (double)p.n_real * p.k_real;
+            bytes = (double)a.M * (reads_per_row + writes_per_row) * 2 + (double)p.N * p.K * 2;
+        }
+    };
+    void emit_product(product const& P);
+    static bool image8_input(graph_node const& x) { return x.dtype == gdt_f32 && (x.ne[0] == 3 || x.ne[0] == 4); } // read as 8-channel value | residue pixels (image_pad8)
+    void conv_geometry(vx_gemm_args& a, graph_node const& n, graph_node const& x, graph_node const& w) const;
+    void pack_conv_rows(product& P, graph_node const& n, bool image8_in, int rep1 = -1, int scale_t = -1);
     // What a product's launch takes over from the nodes behind it: [* LayerScale] [gelu | relu | leaky_relu] [(* s1) + res] [(* s2) + res2].
     // A matcher fills it and changes nothing; absorb() applies exactly what was matched.
     struct epilogue {
@@ -167,7 +254,8 @@ struct lowering {
     };
     epilogue match_epilogue(int t, bool allow_gelu, bool allow_scale = false, bool allow_two = false, bool res_after_relu = true) const;
     epilogue match_planar_epilogue(int t) const;
-    void absorb(epilogue const& e, int into);
+    void absorb(std::vector<int> const& nodes, int into);
+    void absorb(epilogue const& e, int into) { absorb(e.absorbed, into); }
     bool residual_ready(int other, int t) const;
     struct residual_ptrs { std::function<char*()> res1, res2; };
     residual_ptrs read_residuals(epilogue const& e, std::vector<int>& reads);
@@ -183,13 +271,6 @@ struct lowering {
     bool resize_into_reader(int t);
     bool head_tail(int t);
     void one_channel_head(int t);
-    // conv_2d(offset, x), scale(sigmoid(conv_2d(modulator, x)), s), conv_2d_deform(x, W, ., .) [-> mul(c) -> add(c) -> relu] (birefnet.cpp:83-92, 110-115)
-    struct deform_group {
-        int off = -1, mod = -1, sig = -1, scl = -1; // the offset conv, the modulator conv, its sigmoid and scale nodes
-        int mul = -1, add = -1, relu = -1;          // the per-channel epilogue behind the deformable conv
-        float s = 1.0f;
-    };
-    std::map<int, deform_group> deform_groups;      // conv_2d_deform node -> its group (g.fused_models)
     bool match_deform_group(int t, deform_group& G) const;
     void find_deform_groups();
     void deform_conv(int t);
@@ -203,10 +284,6 @@ struct lowering {
     std::array<int, 3> heads_major(graph_node const& n, float q_scale);
     void attention(int t);
     void attention_masked(int t);
-    // split_qkv(.., 1) of nn.cpp:182-208 feeding a masked attention at head_dim 32 with a constant per-head bias (mobile-sam.cpp:124-132):
-    // linear -> reshape -> permute(0, 3, 1, 2) -> cont -> 3 x (slice -> reshape) -> attention_masked
-    struct window_group { int lin = -1; std::vector<int> views; }; // the q|k|v linear; the nodes between it and the attention, computed by nobody
-    std::map<int, window_group> window_groups;      // attention_masked node -> its group (g.fused_models)
     bool match_window_group(int att, window_group& G) const;
     void find_window_groups();
     void window_attention(int t, window_group const& G);
@@ -216,19 +293,6 @@ struct lowering {
     void emit_encoder();
 
     // ---- lower_yolo.cpp: the patterns of SiLU-conv / channel-split / channel-concat networks (yolov9t.cpp; all of it g.fused_models only)
-    struct located { int buf; int64_t off, pix; };  // a map inside a wider one: buffer, first channel, elements between pixels
-    // conv_2d / linear -> silu [-> add(map computed before)], or silu(add(conv3x3(x), conv1x1(x))) keyed on the 3x3 conv: one GEMM-family launch
-    struct silu_group { int silu = -1, add = -1, res = -1, rep1 = -1, rep_add = -1; };
-    std::map<int, silu_group> silu_convs;              // product node -> what its launch computes besides
-    std::map<int, int> rep_member;                     // the 1x1 conv of a folded RepConv -> its 3x3 conv
-    std::map<int, int> launch_of_last;                 // last node of a silu group -> its product node
-    std::map<int, std::pair<int, int>> chan_slice;     // slice of channels [c0, c1) only -> (source, c0): no launch, its readers address the source
-    struct cat_source { int node; int c0; bool placed; };
-    std::map<int, std::vector<cat_source>> cat_sources; // top concat of a dimension-0 chain with a placeable source -> its flattened sources
-    std::map<int, std::pair<int, int>> cat_slot;       // last node of a launch -> (top concat, first channel) it writes into
-    std::map<int, located> in_place;                   // node without a buffer of its own -> where it lives (set when its launch is emitted)
-    struct dfl_group { int map = -1, c0 = 0, n = 0, groups = 0, proj = -1; std::vector<int> absorbed; };
-    std::map<int, dfl_group> dfl_groups;               // sum_rows node -> slice -> [cont] -> reshape -> soft_max -> mul(constant) in front of it
     bool channels_only(graph_node const& s) const;
     std::vector<int> readers_through_conts(int t) const;
     bool gemm_family_reader(int c, int view) const;
@@ -250,23 +314,8 @@ struct lowering {
     packed_operand pack_rep_conv(int w3, int b3, int w1, int b1);
 
     // ---- lower_migan.cpp: the node groups of MI-GAN (migan.cpp; the groups with g.fused_models only), clamp and plane-broadcast launches
-    // what a launch takes over from the nodes behind it: [+ plane constant] [leaky_relu [scale] [clamp(-c, c)]] [+ map]
-    struct agc_tail {
-        int plane = -1, res = -1, last = -1;
-        bool act = false;
-        float slope = 0.0f, gain = 1.0f, clamp = 0.0f;
-        std::vector<int> absorbed;
-    };
-    struct upfir_group { int src = -1, fir = -1; std::vector<int> members; agc_tail tail; }; // the map upsampled, the 4x4 kernel, interpolate .. [cont]
-    std::map<int, upfir_group> upfir_at;                      // LAST node of a group -> the group its launch computes
-    std::map<int, std::pair<int, agc_tail>> dw_agc_at;        // last node -> (conv_2d_depthwise node, its tail)
-    std::map<int, std::pair<int, agc_tail>> conv_agc_at;      // last node -> (1x1 conv_2d node, its tail)
-    std::vector<char> migan_claimed;                          // node -> a group computes it: one of this file's found so far (its last node included), or one
-                                                              // another lowering decided on before (SiLU groups, folded RepConvs, deformable-conv epilogues)
-    std::map<int, double> bound_memo;                         // value_bound's results
     double value_bound(int v);                                // a proven bound of |values| of map v from the graph alone, or infinity
     bool will_live_in_place(int v) const;                     // v (through cont / reshape views) is a channel slice read in its source or a map placed in a concat
-    bool free_node(int c) const { return c >= 0 && !skip[c] && !migan_claimed[c]; } // c may still join a group: no other pattern or group computes it
     agc_tail match_agc_tail(int from, bool allow_plane, bool allow_add) const;
     bool match_upfir_group(int t, upfir_group& G) const;
     void find_migan_groups();
