@@ -142,7 +142,11 @@ VX_API int vx_gemm_pick_k_splits(int M, int N, int K);
 
 /* 3x3 / stride 1 / pad 1 NHWC convolution with the input halo staged once in LDS (Cin, Cout in {32, 64};
  * epilogues F16, F16_RELU, F16_ADD, HEAD_OUT). Same argument block as the implicit-GEMM form (conv_* fields,
- * W = [Cout][Kp] with k = (ky,kx,c)); used for the DPT fusion / head convs at >= 96 px (depth-anything.cpp:15-23, 81-94). */
+ * W = [Cout][Kp] with k = (ky,kx,c)); used for the DPT fusion / head convs at >= 96 px (depth-anything.cpp:15-23, 81-94).
+ * It reads whole pixels of conv_Cin channels and addresses out, res1 and res2 at pixel * ldo (ldo % 8 == 0, >= N), in pixel order, over
+ * the whole k range. What it does not implement it refuses: vx_conv3x3_supported answers 0 and vx_conv3x3_f16 returns 0 with a message for
+ * conv_pix other than 0 or conv_Cin, non-zero post_gelu, win_ws, win_res_h, ld_res1 or a_group, k_splits above 1, and res2 without res1
+ * -- vx_gemm_f16 implements those. */
 VX_API int vx_conv3x3_supported(const vx_gemm_args* args);
 VX_API int vx_conv3x3_f16(const vx_gemm_args* args, void* stream);
 

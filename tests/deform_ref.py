@@ -36,39 +36,59 @@ def conv2d(x, w, b=None, pad=0):
     return y if b is None else y + np.asarray(b, np.float64)
 
 
-def deform_sample(x, py, px):
-    """x [B, H, W, C]; py, px [B, OH, OW] -> [B, OH, OW, C]: bilinear, zero outside (-1, H) x (-1, W), corners outside the map zero."""
+def deform_sample(x, py, px, with_big=False):
+    """x [B, H, W, C]; py, px [B, OH, OW] -> [B, OH, OW, C]: bilinear, zero outside (-1, H) x (-1, W), corners outside the map zero.
+    with_big: also the largest magnitude among the corners that count (what an error bound of the blend is linear in)."""
     B, H, W, _ = x.shape
     inside = (py > -1) & (py < H) & (px > -1) & (px < W)
     y0, x0 = np.floor(py).astype(np.int64), np.floor(px).astype(np.int64)
     ly, lx = py - y0, px - x0
     bi = np.arange(B)[:, None, None]
     out = np.zeros(py.shape + (x.shape[3],))
+    big = np.zeros_like(out)
     for yy, xx, wgt in ((y0, x0, (1 - ly) * (1 - lx)), (y0, x0 + 1, (1 - ly) * lx), (y0 + 1, x0, ly * (1 - lx)), (y0 + 1, x0 + 1, ly * lx)):
         ok = inside & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
         v = x[bi, np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]
         out += np.where(ok, wgt, 0.0)[..., None] * v
-    return out
+        big = np.maximum(big, np.where(ok[..., None], np.abs(v), 0.0))
+    return (out, big) if with_big else out
+
+
+def deform_positions(offset, kh, kw, pad):
+    """offset [B, OH, OW, 2 kh kw] -> py, px [taps, B, OH, OW] (float64): the f32 sum f32(integer) + f32(offset) every implementation forms"""
+    off32 = np.asarray(offset, np.float32)
+    OH, OW = off32.shape[1:3]
+    oy, ox = np.meshgrid(np.arange(OH), np.arange(OW), indexing="ij")
+    py, px = [], []
+    for t in range(kh * kw):
+        ky, kx = divmod(t, kw)
+        py.append(((oy - pad + ky).astype(np.float32)[None] + off32[..., 2 * t]).astype(np.float64))
+        px.append(((ox - pad + kx).astype(np.float32)[None] + off32[..., 2 * t + 1]).astype(np.float64))
+    return np.stack(py), np.stack(px)
+
+
+def deform_columns(x, offset, kh, kw, pad, mask=None):
+    """The A operand of the deformable conv as a product: -> (cols, big) [B, OH, OW, taps, C], cols = mask * sample, big = |mask| times the
+    largest corner magnitude of the sample."""
+    x = np.asarray(x, np.float64)
+    py, px = deform_positions(offset, kh, kw, pad)
+    cols, bigs = [], []
+    for t in range(kh * kw):
+        s, big = deform_sample(x, py[t], px[t], with_big=True)
+        if mask is not None:
+            m = np.asarray(mask, np.float64)[..., t:t + 1]
+            s, big = s * m, big * np.abs(m)
+        cols.append(s)
+        bigs.append(big)
+    return np.stack(cols, axis=3), np.stack(bigs, axis=3)
 
 
 def deform_conv2d(x, w, offset, mask=None, pad=0):
     """stride 1, dilation 1, one offset group (nn.cpp:131-148 / torchvision deform_conv2d with the convention above)."""
-    x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
-    B, H, W, C = x.shape
+    w = np.asarray(w, np.float64)
     co, kh, kw, _ = w.shape
-    OH, OW = H + 2 * pad - kh + 1, W + 2 * pad - kw + 1
-    off32 = np.asarray(offset, np.float32)
-    oy, ox = np.meshgrid(np.arange(OH), np.arange(OW), indexing="ij")
-    y = np.zeros((B, OH, OW, co))
-    for t in range(kh * kw):
-        ky, kx = divmod(t, kw)
-        py = ((oy - pad + ky).astype(np.float32)[None] + off32[..., 2 * t]).astype(np.float64)  # the f32 sum every implementation forms
-        px = ((ox - pad + kx).astype(np.float32)[None] + off32[..., 2 * t + 1]).astype(np.float64)
-        s = deform_sample(x, py, px)
-        if mask is not None:
-            s = s * np.asarray(mask, np.float64)[..., t:t + 1]
-        y += s @ w[:, ky, kx].T
-    return y
+    cols, _ = deform_columns(x, offset, kh, kw, pad, mask)
+    return cols.reshape(cols.shape[:3] + (-1,)) @ w.reshape(co, -1).T
 
 
 def bilinear_ac(x, oh, ow):

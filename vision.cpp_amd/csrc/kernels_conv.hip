@@ -218,19 +218,35 @@ int dispatch_conv_epi(const vx_gemm_args& a, hipStream_t s) {
     return 0;
 }
 
+// Why this kernel does not take the argument block (NULL: it does). The fields of vx_gemm_args that the kernel does not read are refused where
+// they are set: it indexes the input at (iy * W + ix) * Cin and both residuals at pixel * ldo, in pixel order, over the whole k range.
+const char* conv3x3_refusal(const vx_gemm_args* a) {
+    if (!(a->conv_kh == 3 && a->conv_kw == 3 && a->conv_stride == 1 && a->conv_pad == 1 && (a->conv_Cin == 32 || a->conv_Cin == 64) &&
+          (a->N == 32 || a->N == 64) && (a->n_valid == 0 || a->n_valid == a->N) && a->conv_OH == a->conv_H && a->conv_OW == a->conv_W &&
+          (a->epi == VX_EPI_F16 || a->epi == VX_EPI_F16_RELU || a->epi == VX_EPI_F16_ADD || (a->epi == VX_EPI_HEAD_OUT && a->N == 32))))
+        return "unsupported shape (3x3 s1 p1, Cin/Cout in {32,64} only)";
+    if (a->conv_pix != 0 && a->conv_pix != a->conv_Cin) return "conv_pix: the halo loader reads whole pixels of conv_Cin channels, no channel slice";
+    if (a->post_gelu) return "post_gelu is not built into this kernel";
+    if (a->win_ws || a->win_res_h) return "window-order output (win_ws, win_res_h) is not built into this kernel";
+    if (a->k_splits > 1) return "k_splits > 1 is not built into this kernel";
+    if (a->ld_res1) return "ld_res1: res1 is addressed with ldo";
+    if (a->a_group) return "a_group is a plain-GEMM field";
+    if (a->epi == VX_EPI_F16_ADD && a->res2 && !a->res1) return "res2 without res1: the epilogue adds res2 only next to res1";
+    return nullptr;
+}
+
 } // namespace
 
-extern "C" int vx_conv3x3_supported(const vx_gemm_args* a) {
-    return a->conv_kh == 3 && a->conv_kw == 3 && a->conv_stride == 1 && a->conv_pad == 1 && (a->conv_Cin == 32 || a->conv_Cin == 64) &&
-           (a->N == 32 || a->N == 64) && (a->n_valid == 0 || a->n_valid == a->N) && a->conv_OH == a->conv_H && a->conv_OW == a->conv_W &&
-           (a->epi == VX_EPI_F16 || a->epi == VX_EPI_F16_RELU || a->epi == VX_EPI_F16_ADD || (a->epi == VX_EPI_HEAD_OUT && a->N == 32));
-}
+extern "C" int vx_conv3x3_supported(const vx_gemm_args* a) { return conv3x3_refusal(a) == nullptr; }
 
 extern "C" int vx_conv3x3_f16(const vx_gemm_args* args, void* stream) {
     const vx_gemm_args& a = *args;
-    VX_REQUIRE(vx_conv3x3_supported(args), "vx_conv3x3_f16: unsupported shape (3x3 s1 p1, Cin/Cout in {32,64} only)");
-    VX_REQUIRE(a.K >= 9 * a.conv_Cin && a.A && a.W && a.out, "vx_conv3x3_f16: bad operands");
-    VX_REQUIRE(a.M % (a.conv_OH * a.conv_OW) == 0, "vx_conv3x3_f16: M is not a whole number of images");
+    const char* const why = conv3x3_refusal(args);
+    VX_REQUIRE(why == nullptr, "vx_conv3x3_f16: %s", why);
+    VX_REQUIRE(a.K >= 9 * a.conv_Cin && a.A && a.W && a.out && a.conv_H > 0 && a.conv_W > 0, "vx_conv3x3_f16: bad operands");
+    VX_REQUIRE(a.M > 0 && a.M % (a.conv_OH * a.conv_OW) == 0, "vx_conv3x3_f16: M is not a whole number of images");
+    VX_REQUIRE(a.epi == VX_EPI_HEAD_OUT ? a.lambda != nullptr : (a.ldo >= a.N && a.ldo % 8 == 0),
+               "vx_conv3x3_f16: ldo=%ld must be a multiple of 8 and >= N (f16 epilogues); the head epilogue needs conv3 weights", (long)a.ldo);
     hipStream_t s = as_stream(stream);
     if (a.conv_Cin == 64 && a.N == 64) return dispatch_conv_epi<64, 64>(a, s);
     if (a.conv_Cin == 64 && a.N == 32) return dispatch_conv_epi<64, 32>(a, s);
