@@ -126,6 +126,17 @@ inline tensor attention(model_ref m, tensor q, tensor k, tensor v, tensor mask, 
     return linear(m_out, x);
 }
 
+// attention WITHOUT a mask for any number of queries and keys at head_dim 16, 32 and 64, with an output linear layer: q [head_dim, n_heads, n_queries, batch],
+// k, v [head_dim, n_heads, n_keys, batch] (nn.cpp:210-244 with mask == nullptr, as the SAM mask decoder calls it: mobile-sam.cpp:307-319). A builder of its
+// own next to attention(), whose mask-less form keeps the head_dim-64 self-attention kernel and its refusals.
+inline tensor attention_cross(model_ref m, tensor q, tensor k, tensor v, float scale_, model_ref m_out) {
+    return linear(m_out, detail::op(m, VISP_OP_ATTENTION_CROSS, {q, k, v}, {}, {scale_}));
+}
+// the ggml calls of the SAM prompt encoder and mask decoder beyond the above (mobile-sam.cpp:243-246, 471)
+inline tensor mul_mat(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_MUL_MAT, {a, b}); } // a [K, M, Ba], b [K, N, B] -> [M, N, B]
+inline tensor sin(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SIN, {x}); }
+inline tensor cos(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_COS, {x}); }
+
 #ifdef VISP_GGML_NAMES
 // the two calls the reference's arch code makes without a context (dino.cpp:104-105): the tensor knows its graph
 inline tensor ggml_format_name(tensor t, char const* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -173,6 +184,9 @@ inline tensor ggml_upscale(model_ref const& m, tensor x, int factor, int32_t mod
 inline tensor ggml_concat(model_ref const& m, tensor a, tensor b, int dim) { return concat(m, {a, b}, dim); }
 inline tensor ggml_clamp(model_ref const& m, tensor x, float lo, float hi) { return clamp(m, x, lo, hi); }
 inline tensor ggml_mul_inplace(model_ref const& m, tensor a, tensor b) { return mul(m, a, b); }
+inline tensor ggml_mul_mat(model_ref const& m, tensor a, tensor b) { return mul_mat(m, a, b); }
+inline tensor ggml_sin(model_ref const& m, tensor x) { return sin(m, x); }
+inline tensor ggml_cos(model_ref const& m, tensor x) { return cos(m, x); }
 #endif
 
 } // namespace visp

@@ -378,7 +378,21 @@ enum visp_graph_op {
      * per pixel, for every channel and image: migan.cpp:40, 76), and CONV_2D reads an f32 image of 4 channels as it reads one of 3. With the default fused
      * models leaky_relu -> scale -> clamp joins the convolution in front of it, and interpolate(x2 NEAREST) -> mul(zero-insertion tile) -> depthwise 4x4 pad 2 ->
      * slice -> cont is one polyphase FIR launch.                                          ggml_clamp, migan.cpp:23 */
-    VISP_OP_CLAMP = 37
+    VISP_OP_CLAMP = 37,
+    /* the nodes of the SAM prompt encoder and mask decoder (mobile-sam.cpp:210-478) beyond the above.
+     * src q [head_dim, heads, T_q, B], k, v [head_dim, heads, T_k, B], f16 activations; f0 scale -> [head_dim * heads, T_q, B] = softmax(scale q k^T) v, what
+     * nn.cpp:210-244 computes without a mask. head_dim 16, 32 and 64, any T_q, T_k >= 1; other head_dims, shapes that do not match and non-f16 operands are
+     * refused when the node is made. One launch on q, k, v where they are (no head-major copies); with T_q <= 32 and T_k >= 256 the keys are split over blocks
+     * and a second launch folds the parts in a fixed order. VISP_OP_ATTENTION and VISP_OP_ATTENTION_MASKED keep their kernels and
+     * their refusals. */
+    VISP_OP_ATTENTION_CROSS = 38,
+    /* ggml_mul_mat: a [K, M, Ba], b [K, N, B] -> [M, N, B], Ba 1 or B. Folded on the host when both are constants. On the device: two f16 activations with
+     * K % 8 == 0, K <= 256, N <= 16 (one launch), and a constant a with K == 2 on an f32 graph input b as the head of mul_mat -> scale -> {sin, cos} ->
+     * concat(dim 0), which is one launch (position_embedding_random, mobile-sam.cpp:238-248). Everything else is refused; with a constant a, LINEAR is the
+     * op to use.                                                                                                            mobile-sam.cpp:243, 471 */
+    VISP_OP_MUL_MAT = 39,
+    VISP_OP_SIN = 40,              /* element-wise on f16 activations, f32 inside; folded on the host on constants             ggml_sin, mobile-sam.cpp:245 */
+    VISP_OP_COS = 41               /* likewise                                                                                 ggml_cos, mobile-sam.cpp:246 */
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

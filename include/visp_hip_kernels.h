@@ -331,6 +331,27 @@ VX_API int vx_attention_f16(const void* q, const void* k, const void* v, void* o
  * allowed, a row that is -inf on every key is unspecified; out f16 [B*T, H*head_dim] = softmax(scale q k^T + mask) v */
 VX_API int vx_attention_masked_f16(const void* q, const void* k, const void* v, const void* mask, void* out, int B, int H, int T, int head_dim,
                                    int Hm, int Bm, int mask_is_f32, void* stream);
+/* attention without a mask for any T_q, T_k >= 1, head_dim 16, 32 or 64 (kernels_attn_cross.hip; nn.cpp:210-244 with mask == nullptr as
+ * mobile-sam.cpp:307-319 calls it): q f16 [B][T_q][H][head_dim], k, v f16 [B][T_k][H][head_dim] -- token-major rows of H * head_dim, NOT head-major and
+ * NOT pre-scaled: the kernel multiplies the f32 scores by scale * log2(e). out f16 [B][T_q][H * head_dim] = softmax(scale q k^T) v.
+ * With T_q <= 32 and T_k >= 256 the keys are split into parts of 128 over blocks; the parts' (m, l, O) triples go through `partial`
+ * (vx_attention_cross_partial_bytes, 0 when there is one part; NULL is then fine) and a second launch folds them in part order: no atomics, the same
+ * bits on every run. vx_attention_cross_parts: the number of parts (1: a single launch). */
+VX_API int vx_attention_cross_parts(int Tq, int Tk);
+VX_API size_t vx_attention_cross_partial_bytes(int B, int H, int Tq, int Tk, int head_dim);
+VX_API int vx_attention_cross_f16(const void* q, const void* k, const void* v, void* out, void* partial, size_t partial_bytes, int B, int H, int Tq, int Tk,
+                                  int head_dim, float scale, void* stream);
+/* the two launches of a split one by one (the graph layer lists them as two): step 1 the attention launch, step 2 the combine launch (nothing when parts == 1) */
+VX_API int vx_attention_cross_step_f16(int step, const void* q, const void* k, const void* v, void* out, void* partial, size_t partial_bytes, int B, int H, int Tq,
+                                       int Tk, int head_dim, float scale, void* stream);
+/* ggml_mul_mat of two f16 activations (kernels_samdec.hip; mobile-sam.cpp:471): a [Ba][M][K], b [B][N][K] -> out [B][N][M], out[b][n][m] = sum_k a[b or 0][m][k]
+ * b[b][n][k], f32 sums with k ascending, one f16 rounding. K a multiple of 8 and <= 256, N <= 16, Ba 1 or B; a 16-byte aligned. One thread per row m. */
+VX_API int vx_mul_mat_f16(const void* a, const void* b, void* out, int64_t M, int N, int K, int B, int Ba, void* stream);
+/* ggml_sin (mode 0) / ggml_cos (mode 1): y f16 = sin(x) / cos(x), x f16 in radians, f32 inside (x / 2 pi reduced to [-0.5, 0.5] revolutions); 16-byte aligned */
+VX_API int vx_sincos_f16(int mode, const void* x, void* y, int64_t n, void* stream);
+/* position_embedding_random (mobile-sam.cpp:238-248): coords f32 [n_points][2] (x, y), gauss f32 [F][2] (g0[f], g1[f]) -> out f16 [n_points][2 F] =
+ * sin | cos of 2 pi (x g0 + y g1); product, scale and argument reduction in f32 */
+VX_API int vx_fourier_features_f32(const float* coords, const float* gauss, void* out, int64_t n_points, int F, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -20,7 +20,7 @@ const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_nor
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
                                          "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
-                                         "sum_rows", "sub", "clamp"};
+                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -218,6 +218,23 @@ void fold_constant(graph& g, graph_node& n) {
         case gop_sigmoid:
             for (int64_t i = 0; i < total; ++i) out[i] = (float)(1.0 / (1.0 + std::exp(-(double)src(0).values()[i])));
             break;
+        case gop_sin:
+            for (int64_t i = 0; i < total; ++i) out[i] = (float)std::sin((double)src(0).values()[i]);
+            break;
+        case gop_cos:
+            for (int64_t i = 0; i < total; ++i) out[i] = (float)std::cos((double)src(0).values()[i]);
+            break;
+        case gop_mul_mat: { // out[m, n, b] = sum_k a[k, m, b or 0] b[k, n, b], in double
+            const int64_t K = src(0).ne[0], M = n.ne[0], N = n.ne[1], Ba = src(0).ne[2];
+            const float *a = src(0).values(), *bv = src(1).values();
+            for (int64_t b = 0; b < n.ne[2]; ++b)
+                for (int64_t j = 0; j < N; ++j)
+                    for (int64_t m = 0; m < M; ++m) {
+                        double acc = 0.0;
+                        for (int64_t k = 0; k < K; ++k) acc += (double)a[((Ba == 1 ? 0 : b) * M + m) * K + k] * (double)bv[(b * N + j) * K + k];
+                        out[(b * N + j) * M + m] = (float)acc;
+                    }
+        } break;
         case gop_cast:
             for (int64_t i = 0; i < total; ++i) out[i] = n.dtype == gdt_f16 ? f16_to_f32(f32_to_f16(src(0).values()[i])) : src(0).values()[i];
             break;
@@ -228,7 +245,7 @@ void fold_constant(graph& g, graph_node& n) {
 bool foldable(int32_t op) {
     return op == gop_reshape || op == gop_cont || op == gop_scale || op == gop_add || op == gop_mul || op == gop_slice || op == gop_repeat ||
            op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid ||
-           op == gop_silu || op == gop_sub || op == gop_clamp;
+           op == gop_silu || op == gop_sub || op == gop_clamp || op == gop_mul_mat || op == gop_sin || op == gop_cos;
 }
 
 void check_tensor(graph const& g, int t, const char* what) {
@@ -604,9 +621,45 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
         } break;
         case gop_sigmoid:
         case gop_silu:
+        case gop_sin:
+        case gop_cos:
             need_src(1, 1);
             same_shape();
             break;
+        case gop_attention_cross: {
+            need_src(3, 3);
+            graph_node const &q = S(0), &k = S(1), &v = S(2);
+            for (int i = 0; i < 4; ++i)
+                if (k.ne[i] != v.ne[i] || (i != 2 && q.ne[i] != k.ne[i]))
+                    throw except("attention_cross: q %s, k %s, v %s do not match (q [head_dim, heads, T_q, batch]; k, v [head_dim, heads, T_k, batch])", shape_str(q.ne).c_str(), shape_str(k.ne).c_str(), shape_str(v.ne).c_str());
+            if (q.ne[0] != 16 && q.ne[0] != 32 && q.ne[0] != 64) throw except("attention_cross: head_dim %lld; the kernel is built for head_dim 16, 32 and 64", (long long)q.ne[0]);
+            for (int i = 0; i < 3; ++i)
+                if (S(i).constant || S(i).dtype != gdt_f16) throw except("attention_cross: operand %d (%s) is %s; q, k and v are f16 activations", i, i == 0 ? "q" : (i == 1 ? "k" : "v"), S(i).constant ? "a constant" : "f32");
+            n.ne[0] = q.ne[0] * q.ne[1];
+            n.ne[1] = q.ne[2];
+            n.ne[2] = q.ne[3];
+            n.ne[3] = 1;
+        } break;
+        case gop_mul_mat: {
+            need_src(2, 2);
+            graph_node const &a = S(0), &b = S(1);
+            const int64_t K = a.ne[0], M = a.ne[1], Ba = a.ne[2], N = b.ne[1], B = b.ne[2];
+            if (b.ne[0] != K || a.ne[3] != 1 || b.ne[3] != 1) throw except("mul_mat: a %s and b %s do not match (a [K, M, Ba], b [K, N, B] -> [M, N, B])", shape_str(a.ne).c_str(), shape_str(b.ne).c_str());
+            if (Ba != 1 && Ba != B) throw except("mul_mat: the first operand's batch %lld is neither 1 nor the second's %lld", (long long)Ba, (long long)B);
+            if (a.dtype == gdt_i32 || b.dtype == gdt_i32) throw except("mul_mat: an i32 tensor is an index, not a value");
+            n.ne[0] = M; n.ne[1] = N; n.ne[2] = B; n.ne[3] = 1;
+            if (a.constant && b.constant) break; // folded on the host
+            if (!a.constant && b.constant) throw except("mul_mat: the second operand is a constant and the first an activation; this product is not built (swap the roles: LINEAR takes the constant as its weight)");
+            if (a.constant) {
+                // a constant [2, F] on the f32 coordinates: the head of position_embedding_random's chain (mobile-sam.cpp:243), lowered with it as one launch
+                if (K == 2 && b.op == gop_input && b.dtype == gdt_f32) break;
+                if (K == 2) throw except("mul_mat: a constant first operand with K = 2 is built on an f32 graph input only (the coordinates of position_embedding_random), not on an f16 activation");
+                throw except("mul_mat: the first operand is a constant; use LINEAR (linear(x, w) is mul_mat(w, x) with w as the layer's weight) -- mul_mat is built for two activations, and for a constant [2, F] on f32 coordinates");
+            }
+            if (a.dtype != gdt_f16 || b.dtype != gdt_f16) throw except("mul_mat: operands of two activations are f16 (a is %s, b is %s)", a.dtype == gdt_f16 ? "f16" : "f32", b.dtype == gdt_f16 ? "f16" : "f32");
+            if (K % 8 || K > 256) throw except("mul_mat: K = %lld; two activations are multiplied for K a multiple of 8, at most 256", (long long)K);
+            if (N > 16) throw except("mul_mat: N = %lld columns in the second operand; at most 16 (one thread per row of the first keeps them in registers)", (long long)N);
+        } break;
         case gop_clamp:
             need_src(1, 1);
             if (n_fp != 2) throw except("clamp: two float parameters (lower bound, upper bound)");
@@ -714,7 +767,8 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             const bool f32_mask = op == gop_attention_masked && i == 3; // the masked attention reads an f32 mask in place
             // (any conv on a 3- or 4-channel f32 image: image_pad8 in front of the GEMM family's conv, mobile-sam.cpp:71-73, migan.cpp:84-86)
             const bool image8_conv = op == gop_conv_2d && i == 0 && S(0).dtype == gdt_f32 && (S(0).ne[0] == 3 || S(0).ne[0] == 4);
-            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask)
+            const bool fourier_head = op == gop_mul_mat && i == 1 && S(0).constant && S(0).ne[0] == 2 && S(1).op == gop_input; // (checked above)
+            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask && !fourier_head)
                 throw except("%s: operand %d is f32; only patch_embed and an image's first 3x3 conv read the f32 input tensor", nm, i);
         }
 

@@ -73,6 +73,11 @@ enum graph_op : int32_t {
     gop_sub,              // a - b, b broadcast as for add                     ggml_sub
     // MI-GAN's node beyond the above (migan.cpp:23); add / mul / sub also take a plane [1, W, H, 1] on [C, W, H, N] (migan.cpp:40, 76)
     gop_clamp,            // f0 = lower, f1 = upper bound: min(max(x, f0), f1)   ggml_clamp
+    // the nodes of the SAM prompt encoder and mask decoder beyond the above (mobile-sam.cpp:238-248, 307-319, 471)
+    gop_attention_cross,  // q [hd, heads, T_q, B], k, v [hd, heads, T_k, B]; f0 = scale; hd 16 / 32 / 64, any T_q, T_k -> [hd * heads, T_q, B]   nn.cpp:210-244 without a mask
+    gop_mul_mat,          // a [K, M, Ba], b [K, N, B] -> [M, N, B], Ba 1 or B     ggml_mul_mat
+    gop_sin,              // ggml_sin
+    gop_cos,              // ggml_cos
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -142,6 +147,7 @@ enum pack_role : int {
     role_rep_conv = 45,      // GEMM operand of a RepConv: the 3x3 kernel with the 1x1 kernel added into its centre tap (keyed on the 3x3 kernel)
     role_rep_conv_bias = 46, // ... and the two biases summed in f32, [N pad]
     role_plane_f32 = 47,     // a [1, W, H, 1] constant as the f32 plane a fused epilogue adds per pixel (MI-GAN's folded noise)
+    role_fourier = 48,       // the [2, F] gaussian matrix of position_embedding_random, rounded to f16, as f32 pairs [F][2]
 };
 // the second form of broadcast add / mul / sub admit next to the trailing-dimension one: b [1, W, H, 1] on a [C, W, H, N], one value per pixel for every
 // channel and image (ggml_mul_inplace(x, filter), ggml_add_inplace(x, noise): migan.cpp:40, 76). Where C == 1 or W H == 1 the trailing rule holds already.

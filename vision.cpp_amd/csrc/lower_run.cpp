@@ -94,6 +94,7 @@ void lowering::run() {
     find_encoder_chain();
     find_yolo_groups();
     find_migan_groups();
+    find_sam_groups();
     for (int t = 0; t < N; ++t) {
         graph_node& n = g.nodes[t];
         if (enc.ok && t == enc.first) emit_encoder();
@@ -122,6 +123,10 @@ void lowering::run() {
             case gop_patch_embed: patch_embed(t); break;
             case gop_attention: attention(t); break;
             case gop_attention_masked: attention_masked(t); break;
+            case gop_attention_cross: attention_cross(t); break;
+            case gop_mul_mat: mul_mat(t); break;
+            case gop_sin:
+            case gop_cos: sincos(t); break;
             case gop_conv_2d_deform: deform_conv(t); break;
             case gop_conv_2d_depthwise: depthwise_conv(t); break;
             case gop_pool_2d: pool_2d(t); break;
@@ -270,9 +275,22 @@ void lowering::run() {
                 copy_op(t);
                 break;
             case gop_concat:
+                if (auto it = fourier_groups.find(t); it != fourier_groups.end()) { fourier_features(t, it->second); break; }
                 if (cat_sources.count(t)) { concat_in_place(t); break; }
-                [[fallthrough]];
-            case gop_repeat: copy_op(t); break;
+                copy_op(t);
+                break;
+            case gop_repeat:
+                if (same_shape(n, g.nodes[n.src[0]])) { // to its own shape (mobile-sam.cpp:439 at batch 1): a view
+                    n.alias_of = n.src[0];
+                    if (n.is_output) {
+                        graph_node& r = g.nodes[root(t)];
+                        r.is_output = true;
+                        if (r.buffer >= 0) g.buffers[r.buffer].persistent = true;
+                    }
+                    break;
+                }
+                copy_op(t);
+                break;
             default: throw except("graph_allocate: %s is not lowered", graph_op_name(n.op));
         }
     }

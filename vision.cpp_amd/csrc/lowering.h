@@ -6,6 +6,7 @@
 //   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
 //   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
 //   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
+//   lower_sam.cpp      attention without a mask on token-major q / k / v, mul_mat of activations, sin / cos, the Fourier-feature group
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
 // a `return false` leaves the lowering's state as it was. A finder that accepts a group says so in ONE table (claim): a matcher asks free_node()
@@ -132,6 +133,10 @@ struct lowering {
     std::map<int, std::pair<int, agc_tail>> dw_agc_at;        // last node -> (conv_2d_depthwise node, its tail)
     std::map<int, std::pair<int, agc_tail>> conv_agc_at;      // last node -> (1x1 conv_2d node, its tail)
     std::map<int, double> bound_memo;                         // value_bound's results
+
+    // ---- the nodes of the SAM prompt encoder and mask decoder (lower_sam.cpp; the Fourier group in BOTH lowering modes)
+    struct fourier_group { int mm = -1, scale = -1, sin = -1, cos = -1; };  // mul_mat(constant [2, F], f32 input) -> scale(2 pi) -> {sin, cos}
+    std::map<int, fourier_group> fourier_groups;              // concat(sin, cos, dim 0) node -> the group its one launch computes
 
     explicit lowering(graph& gr) : g(gr) {}
     void run(); // the whole lowering: fills g.launches / g.buffers / the arena plan
@@ -326,6 +331,15 @@ struct lowering {
     void migan_product(int last, int t, agc_tail const& T);
     void clamp_op(int t);
     void plane_binary(int t);
+
+    // ---- lower_sam.cpp
+    bool match_fourier_group(int cat, fourier_group& G) const;
+    void find_sam_groups();
+    void fourier_features(int t, fourier_group const& G);
+    int token_rows(int t, const char* who);
+    void attention_cross(int t);
+    void mul_mat(int t);
+    void sincos(int t);
 
     // ---- lower_run.cpp
     void copy_op(int t);

@@ -19,7 +19,7 @@ from . import _lib as lib
 from ._lib import check, get_lib
 
 F32, F16, U8, I32 = 0, 1, 24, 26
-# OP_LINEAR ... OP_CLAMP: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
+# OP_LINEAR ... OP_COS: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
 globals().update({k.removeprefix("VISP_"): v for k, v in lib.C_API_DECLS.enums["visp_graph_op"].items()})
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
@@ -82,6 +82,8 @@ class Graph:
         self._api = get_lib()
         self._device = device  # kept alive; bound when the graph is allocated (compute_graph_allocate(graph, backend))
         self._weights = weights
+        if weights is not None and device is not None:
+            weights._device = device  # the weights' device images are freed on the device they were made on: it outlives a Weights that outlives its graphs
         h = c_void_p()
         check(self._api.visp_graph_create(weights._handle if weights is not None else None, byref(h)))
         self._handle = h
@@ -296,6 +298,12 @@ def attention(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, mask, scale: float, 
     return linear(m_out, x)
 
 
+def attention_cross(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, scale: float, m_out: ModelRef) -> Tensor:  # nn.cpp:210-244 with mask == nullptr
+    """q [head_dim, n_heads, n_queries, batch], k, v [head_dim, n_heads, n_keys, batch]; head_dim 16, 32 and 64, any number of queries and keys. A builder of its own:
+    attention(mask=None) keeps the head_dim-64 self-attention kernel and its refusals."""
+    return linear(m_out, m.graph.op(OP_ATTENTION_CROSS, [q, k, v], fparams=[scale]))
+
+
 # ---- ml.h tensor operations + the ggml ops the arch code uses directly ----------------------------------------------------------
 
 def slice_(m: ModelRef, x: Tensor, s0=SLICE_ALL, s1=SLICE_ALL, s2=SLICE_ALL, s3=SLICE_ALL) -> Tensor:  # ml.cpp:746-768
@@ -340,6 +348,11 @@ def sub(m, a, b): return m.graph.op(OP_SUB, [a, b])  # ggml_sub: a - b, b broadc
 def soft_max(m, x): return m.graph.op(OP_SOFT_MAX, [x])  # ggml_soft_max: over dimension 0
 def sum_rows(m, x): return m.graph.op(OP_SUM_ROWS, [x])  # ggml_sum_rows: [n, a, b, c] -> [1, a, b, c]
 def clamp(m, x, lo, hi): return m.graph.op(OP_CLAMP, [x], fparams=[lo, hi])  # ggml_clamp: min(max(x, lo), hi)
+
+
+def mul_mat(m, a, b): return m.graph.op(OP_MUL_MAT, [a, b])  # ggml_mul_mat: a [K, M, Ba], b [K, N, B] -> [M, N, B]
+def sin(m, x): return m.graph.op(OP_SIN, [x])  # ggml_sin
+def cos(m, x): return m.graph.op(OP_COS, [x])  # ggml_cos
 
 
 POOL_MAX, POOL_AVG = 0, 1  # ggml_op_pool
@@ -1112,3 +1125,128 @@ def migan_generate(m: ModelRef, image: Tensor, res: int) -> Tensor:  # migan.cpp
     x, feats = migan_encode(m["encoder"], image, res)
     img = migan_synthesis(m["synthesis"], x, feats, res)
     return m.graph.output(slice_(m, img, (0, 3)), "output")
+
+
+# ---- MobileSAM prompt encoder and mask decoder against this layer (the structure of src/visp/arch/mobile-sam.cpp:210-478) ------------------------------
+# Node for node, with three departures. The reference writes into views (ggml_cpy into a slice, :256 and :468; ggml_add_inplace on a slice, :261, :275, :279);
+# this layer is functional, so those are concat(add(slice(..), w), ..) and a concat of the four hypernetwork rows. attention() with a null mask is
+# attention_cross(): the builder of the op that takes any head_dim in {16, 32, 64} and T_q != T_k. And pos_src is repeated to the batch of the tokens (the
+# reference repeats it to tokens->ne[3], which is 1, and its reshape_3d to b then holds for one prompt only); several prompts are batch entries here.
+
+def sam_position_embedding_random(m: ModelRef, coords: Tensor) -> Tensor:  # mobile-sam.cpp:238-248; coords f32 [2, n, B] in [-1, 1]
+    pe = m.weights("positional_encoding_gaussian_matrix")  # [F, 2]
+    pe = cont(m, permute(m, pe, 1, 0, 2, 3))  # ggml_transpose
+    coords = mul_mat(m, pe, coords)
+    coords = scale(m, coords, 2.0 * math.pi)
+    return concat(m, [sin(m, coords), cos(m, coords)], 0)
+
+
+def sam_embed_points(m: ModelRef, coords: Tensor) -> Tensor:  # mobile-sam.cpp:250-266; the last point is the sentinel
+    count, b = coords.ne[1] - 1, coords.ne[2]
+    x = sam_position_embedding_random(m["pe_layer"], coords)
+    c = x.ne[0]
+    label_end = repeat(m, m.weights("not_a_point_embed.weight"), c, 1, b, 1)  # :255-256: the sentinel's row IS not_a_point_embed
+    label_one = add(m, slice_(m, x, SLICE_ALL, (0, count)), m.weights("point_embeddings.1.weight"))  # :260-261: foreground points
+    return concat(m, [label_one, label_end], 1)
+
+
+def sam_embed_box(m: ModelRef, coords: Tensor) -> Tensor:  # mobile-sam.cpp:268-284; coords f32 [2, 2, B]: the two corners
+    x = sam_position_embedding_random(m["pe_layer"], coords)
+    corner1 = add(m, slice_(m, x, SLICE_ALL, 0), m.weights("point_embeddings.2.weight"))
+    corner2 = add(m, slice_(m, x, SLICE_ALL, 1), m.weights("point_embeddings.3.weight"))
+    return m.graph.set_name(concat(m, [corner1, corner2], 1), "box_embed")
+
+
+def sam_no_mask_embed(m: ModelRef) -> Tensor:  # mobile-sam.cpp:286-288
+    return m.weights("no_mask_embed.weight")
+
+
+def sam_mlp_block(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:294-299
+    return linear(m["lin2"], relu(m, linear(m["lin1"], x)))
+
+
+def sam_decoder_attention(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, n_heads: int) -> Tensor:  # mobile-sam.cpp:307-319
+    q, k, v = linear(m["q_proj"], q), linear(m["k_proj"], k), linear(m["v_proj"], v)
+    q, k, v = (reshape(m, t, t.ne[0] // n_heads, n_heads, t.ne[1], t.ne[2]) for t in (q, k, v))
+    return attention_cross(m, q, k, v, 1.0 / math.sqrt(float(q.ne[0])), m["out_proj"])
+
+
+def sam_two_way_attention_block(m: ModelRef, queries: Tensor, keys: Tensor, query_pe: Tensor, key_pe: Tensor, num_heads: int, skip_first_layer_pe: bool):  # mobile-sam.cpp:321-362
+    if skip_first_layer_pe:  # self attention block
+        queries = sam_decoder_attention(m["self_attn"], queries, queries, queries, num_heads)
+    else:
+        q = add(m, queries, query_pe)
+        queries = add(m, queries, sam_decoder_attention(m["self_attn"], q, q, queries, num_heads))
+    queries = layer_norm(m["norm1"], queries)
+    q = add(m, queries, query_pe)  # cross attention block, tokens attending to image embedding
+    k = add(m, keys, key_pe)
+    queries = add(m, queries, sam_decoder_attention(m["cross_attn_t2i"], q, k, keys, num_heads))
+    queries = layer_norm(m["norm2"], queries)
+    queries = add(m, queries, sam_mlp_block(m["mlp"], queries))  # MLP block
+    queries = cont(m, layer_norm(m["norm3"], queries))
+    q = add(m, queries, query_pe)  # cross attention block, image embedding attending to tokens
+    keys = add(m, keys, sam_decoder_attention(m["cross_attn_i2t"], k, q, queries, num_heads))
+    keys = layer_norm(m["norm4"], keys)
+    return queries, keys
+
+
+def sam_two_way_transformer(m: ModelRef, image_embedding: Tensor, image_pe: Tensor, point_embedding: Tensor, depth: int, num_heads: int):  # mobile-sam.cpp:364-395
+    c, w, h, b = image_embedding.ne
+    image_embedding = reshape(m, image_embedding, c, w * h, b)
+    image_pe = reshape(m, image_pe, c, w * h, b)
+    queries, keys = point_embedding, image_embedding
+    for i in range(depth):
+        queries, keys = sam_two_way_attention_block(m["layers"][i], queries, keys, point_embedding, image_pe, num_heads, i == 0)
+    q = add(m, queries, point_embedding)  # the final attention layer from the points to the image
+    k = add(m, keys, image_pe)
+    queries = add(m, queries, sam_decoder_attention(m["final_attn_t2i"], q, k, keys, num_heads))
+    return layer_norm(m["norm_final_attn"], queries), keys
+
+
+def sam_upscale_outputs(m: ModelRef, x: Tensor) -> Tensor:  # mobile-sam.cpp:397-405
+    x = conv_transpose_2d(m[0], x, 2)
+    x = gelu(m, layer_norm(m[1], x))
+    return gelu(m, conv_transpose_2d(m[3], x, 2))
+
+
+def sam_hypernetwork_mlp(m: ModelRef, x: Tensor, num_layers: int) -> Tensor:  # mobile-sam.cpp:407-416
+    for i in range(num_layers):
+        x = linear(m["layers"][i], x)
+        if i < num_layers - 1:
+            x = relu(m, x)
+    return x
+
+
+def sam_predict_masks(m: ModelRef, image_embeddings: Tensor, sparse_prompt: Tensor, dense_prompt: Tensor):  # mobile-sam.cpp:418-478
+    """image_embeddings [C, W, H, 1], sparse_prompt [C, n, B] (B prompts), dense_prompt [C] -> masks [4 W, 4 H, 4, B], iou [4, B]."""
+    num_heads, transformer_depth, num_mask_tokens = 8, 2, 4
+    b = sparse_prompt.ne[2]
+    output_tokens = concat(m, [m.weights("iou_token.weight"), m.weights("mask_tokens.weight")], 1)
+    output_tokens = repeat(m, output_tokens, output_tokens.ne[0], output_tokens.ne[1], b, 1)
+    tokens = concat(m, [output_tokens, sparse_prompt], 1)
+    ie0, ie1, ie2, _ = image_embeddings.ne
+    src = repeat(m, image_embeddings, ie0, ie1, ie2, b)  # per-image data in batch direction to be per-mask
+    src = add(m, src, dense_prompt)
+    image_pe = m.weights("dense_positional_embedding")
+    pos_src = repeat(m, image_pe, image_pe.ne[0], image_pe.ne[1], image_pe.ne[2], b)
+    c_low, w_low, h_low, _ = src.ne
+    hs, out = sam_two_way_transformer(m["transformer"], src, pos_src, tokens, transformer_depth, num_heads)
+    iou_token_out = reshape(m, slice_(m, hs, SLICE_ALL, 0), hs.ne[0], b)  # ggml_view_2d(hs, ne0, ne2, nb2, 0): token 0 of every prompt
+    mask_tokens_out = slice_(m, hs, SLICE_ALL, (1, num_mask_tokens + 1))
+    out = reshape(m, out, c_low, w_low, h_low, b)
+    upscaled_embedding = sam_upscale_outputs(m["output_upscaling"], out)
+    c, w, h, _ = upscaled_embedding.ne
+    upscaled_embedding = reshape(m, upscaled_embedding, c, w * h, b)
+    mlps = m["output_hypernetworks_mlps"]
+    rows = [sam_hypernetwork_mlp(mlps[i], slice_(m, mask_tokens_out, SLICE_ALL, i), 3) for i in range(num_mask_tokens)]
+    hyper_in = concat(m, rows, 1)  # :462-470 writes the rows into a new tensor
+    masks = mul_mat(m, upscaled_embedding, hyper_in)
+    masks = reshape(m, masks, w, h, masks.ne[1], b)
+    iou_pred = sam_hypernetwork_mlp(m["iou_prediction_head"], iou_token_out, 3)
+    return masks, iou_pred
+
+
+def sam_predict_mask(m: ModelRef, image_embed: Tensor, prompt_embed: Tensor):  # mobile-sam.cpp:597-602; m = the model's root
+    dense_prompt = sam_no_mask_embed(m["prompt_encoder"])
+    masks, iou = sam_predict_masks(m["dec"], image_embed, prompt_embed, dense_prompt)
+    return m.graph.output(masks, "masks"), m.graph.output(iou, "iou")

@@ -540,6 +540,27 @@ def write_mobile_sam_gguf(path: str | Path, cfg: TinyVitConfig = TINYVIT_5M, see
     return Path(path)
 
 
+def sam_decoder_tensors_at(sd: dict[str, np.ndarray], size: int) -> dict[str, np.ndarray]:
+    """sam_decoder_gguf_tensors with the dense positional embedding rebuilt for a size x size embedding (from the f16-rounded gaussian matrix, as the
+    reference's converter sees it after its own rounding)."""
+    tensors = sam_decoder_gguf_tensors(sd)
+    gauss = sd["prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"].astype(np.float16).astype(np.float32)
+    tensors["dec.dense_positional_embedding"] = sam_dense_positional_embedding(gauss, size)
+    return tensors
+
+
+def write_sam_decoder_gguf(path: str | Path, sd: dict[str, np.ndarray], size: int = 64) -> Path:
+    """The prompt encoder and mask decoder alone (no image encoder), for a size x size embedding."""
+    w = GGUFWriter(path, "mobile-sam")
+    w.add_string("mobile-sam.tensor_data_layout", "whcn")
+    w.add_uint32("general.quantization_version", 2)
+    w.add_uint32("general.file_type", 1)
+    for name, t in sam_decoder_tensors_at(sd, size).items():
+        w.add_tensor(name, t)
+    w.write()
+    return Path(path)
+
+
 # ---- SWIN transformer encoder, the BiRefNet backbone (reference src/visp/arch/swin.cpp, scripts/convert.py:358-419) ----
 
 @dataclass(frozen=True)
