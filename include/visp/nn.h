@@ -136,6 +136,11 @@ inline tensor attention_cross(model_ref m, tensor q, tensor k, tensor v, float s
 inline tensor mul_mat(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_MUL_MAT, {a, b}); } // a [K, M, Ba], b [K, N, B] -> [M, N, B]
 inline tensor sin(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SIN, {x}); }
 inline tensor cos(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_COS, {x}); }
+// the ggml call of the SAM3 vision encoder beyond the above (sam3.h:413-438): ggml_rope_ext in GGML_ROPE_TYPE_NORMAL. x [n, heads, T, B] f16, pos an i32 constant
+// [T]; n_dims == n. Pair i of token t is rotated by pos[t] * freq_scale * freq_base^(-2 i / n).
+inline tensor rope(model_ref const& m, tensor x, tensor pos, int n_dims, float freq_base, float freq_scale) {
+    return detail::op(m, VISP_OP_ROPE, {x, pos}, {n_dims, 0}, {freq_base, freq_scale});
+}
 
 #ifdef VISP_GGML_NAMES
 // the two calls the reference's arch code makes without a context (dino.cpp:104-105): the tensor knows its graph
@@ -187,6 +192,16 @@ inline tensor ggml_mul_inplace(model_ref const& m, tensor a, tensor b) { return 
 inline tensor ggml_mul_mat(model_ref const& m, tensor a, tensor b) { return mul_mat(m, a, b); }
 inline tensor ggml_sin(model_ref const& m, tensor x) { return sin(m, x); }
 inline tensor ggml_cos(model_ref const& m, tensor x) { return cos(m, x); }
+constexpr int GGML_ROPE_TYPE_NORMAL = 0, GGML_ROPE_TYPE_NEOX = 2;
+// ggml's full argument list. Built: no frequency factors, GGML_ROPE_TYPE_NORMAL (any other mode is refused by the op), and the defaults of the YaRN
+// arguments (ext_factor 0, attn_factor 1, beta_fast / beta_slow 0, as sam3.h:423-427 passes them); n_ctx_orig is not read without YaRN.
+inline tensor ggml_rope_ext(model_ref const& m, tensor a, tensor b, tensor c, int n_dims, int mode, int /*n_ctx_orig*/, float freq_base, float freq_scale, float ext_factor,
+                            float attn_factor, float beta_fast, float beta_slow) {
+    if (c) throw exception("rope: frequency factors are not built (pass a null tensor)");
+    if (ext_factor != 0.0f || attn_factor != 1.0f || beta_fast != 0.0f || beta_slow != 0.0f)
+        throw exception("rope: ext_factor / attn_factor / beta_fast / beta_slow other than 0, 1, 0, 0 (YaRN) are not built");
+    return detail::op(m, VISP_OP_ROPE, {a, b}, {n_dims, mode}, {freq_base, freq_scale});
+}
 #endif
 
 } // namespace visp

@@ -328,7 +328,8 @@ enum visp_graph_op {
     VISP_OP_CONCAT = 13,           /* src a, b; i0 dim                                                      ml.cpp:770-780 */
     VISP_OP_SLICE = 14,            /* i[3d], i[3d+1], i[3d+2] = begin, end, step of dimension d            ml.cpp:746-768 */
     VISP_OP_RESHAPE = 15,          /* i0..i3 ne */
-    VISP_OP_REPEAT = 16,           /* i0..i3 ne */
+    VISP_OP_REPEAT = 16,           /* i0..i3 ne: a source dimension is 1 or equal; a CONSTANT source may be tiled (every target extent a multiple of the
+                                    * source's, out[i] = src[i mod ne_src] as ggml_repeat defines it), folded on the host          dino.cpp:38-40, sam3.h:331-334 */
     VISP_OP_PATCH_EMBED = 17,      /* src x f32 [C,W,H,N], w, (b); i0 patch size                           nn.cpp:166-180 */
     VISP_OP_CONT = 18,
     /* extensions for callers that keep images in HBM (the reference does both steps on the host): */
@@ -339,7 +340,10 @@ enum visp_graph_op {
     VISP_OP_PERMUTE = 22,          /* i0..i3 ggml_permute's axes (source dimension d becomes dimension i_d); the result is contiguous, cont behind it a view */
     VISP_OP_ROLL = 23,             /* i0..i3 cyclic shifts, negative allowed                                               ggml_roll, swin.cpp:116, 124 */
     VISP_OP_PAD = 24,              /* i0..i3 zeros appended at the end of each dimension                                   ggml_pad, swin.cpp:111 */
-    VISP_OP_GET_ROWS = 25,         /* src table [C, rows], index i32 constant -> f32 [C, idx ne0, ne1, ne2]; constants only  ggml_get_rows, swin.cpp:75 */
+    /* src table [C, rows] (a constant, f16 / f32), index i32 -> [C, idx ne0, ne1, ne2]. A constant index is folded on the host and gives f32, as ggml says. An
+     * index that is an i32 GRAPH INPUT (the token ids of clip_text_embed) is gathered on the device and gives an f16 ACTIVATION -- ggml says f32 there too, but
+     * activations of this layer are f16; C a multiple of 8. An index outside the table reads nothing and gives a row of zeros.   ggml_get_rows, swin.cpp:75, sam3.h:225 */
+    VISP_OP_GET_ROWS = 25,
     VISP_OP_CAST = 26,             /* i0 type (0 f32, 1 f16): rounds constants, a view on activations that have the type   ggml_cast, swin.cpp:78 */
     /* src q, k, v [head_dim, heads, T, B], mask [T_k, T_q, Hm, Bm] f16 / f32, constant or activation; f0 scale. Hm is 1 or heads, Bm divides B (batch b
      * reads mask b % Bm). softmax(scale q k^T + mask) v as the 3-source op. head_dim 32 and 64, T_q == T_k. head_dim 32 exists through THIS op only:
@@ -392,7 +396,13 @@ enum visp_graph_op {
      * op to use.                                                                                                            mobile-sam.cpp:243, 471 */
     VISP_OP_MUL_MAT = 39,
     VISP_OP_SIN = 40,              /* element-wise on f16 activations, f32 inside; folded on the host on constants             ggml_sin, mobile-sam.cpp:245 */
-    VISP_OP_COS = 41               /* likewise                                                                                 ggml_cos, mobile-sam.cpp:246 */
+    VISP_OP_COS = 41,              /* likewise                                                                                 ggml_cos, mobile-sam.cpp:246 */
+    /* the node of the SAM3 vision encoder beyond the above: ggml_rope_ext in GGML_ROPE_TYPE_NORMAL (sam3.h:413-438). src x [n, heads, T, B] (an f16 activation),
+     * pos i32 CONSTANT [T] (visp_graph_add_weight with dtype 26, like a get_rows index); i0 n_dims (== n, a multiple of 8), i1 mode (0, NORMAL, only); f0
+     * freq_base, f1 freq_scale. For pair i in [0, n / 2): theta = pos[t] * freq_scale * freq_base^(-2 i / n); out[2i] = x[2i] cos - x[2i+1] sin, out[2i+1] =
+     * x[2i] sin + x[2i+1] cos. The result has x's shape, f16. The angles never go through device transcendentals: the lowering makes a cos | sin table in double
+     * from the constant positions, once per (positions, n_dims, base, scale). apply_rope_2d is two ROPE nodes on the two halves of a head. */
+    VISP_OP_ROPE = 42
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is
@@ -418,7 +428,7 @@ VISP_API void visp_graph_destroy(visp_graph* g);
  * a constant that is not a file weight (the shift mask of swin.cpp:165-221, -inf entries included); visp_graph_get_tensor finds it by name. */
 VISP_API int32_t visp_graph_add_weight(visp_graph* g, char const* name, int32_t dtype, int64_t const ne[4], float const* data, int32_t* out);
 VISP_API int32_t visp_graph_find_weight(visp_graph* g, char const* name, int32_t* out); /* *out = -1 when absent (model_ref::find) */
-VISP_API int32_t visp_graph_input(visp_graph* g, int32_t dtype /* 0 f32, 1 f16, 24 u8 image bytes */, int64_t const ne[4], char const* name, int32_t* out);
+VISP_API int32_t visp_graph_input(visp_graph* g, int32_t dtype /* 0 f32, 1 f16, 24 u8 image bytes, 26 i32 indices */, int64_t const ne[4], char const* name, int32_t* out);
 VISP_API int32_t visp_graph_op(visp_graph* g, int32_t op, int32_t const* src, int32_t n_src, int64_t const* iparams, int32_t n_iparams,
                                float const* fparams, int32_t n_fparams, int32_t* out);
 VISP_API int32_t visp_graph_set_name(visp_graph* g, int32_t tensor, char const* name);

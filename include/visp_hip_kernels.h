@@ -473,6 +473,27 @@ VX_API int vx_f32_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream)
 /* dst[i . dst_stride] = scale * src[i . src_stride], i over ne (element strides, 0 = broadcast a source dimension) */
 VX_API int vx_copy_strided_f16(const void* src, void* dst, const int64_t ne[4], const int64_t src_stride[4], const int64_t dst_stride[4], float scale,
                                void* stream);
+/* ---- rotary position embedding and the token gather of the SAM3 encoders (kernels_rope.hip; sam3.h:221-231, 413-438). Memory-bound passes next to
+ * vx_copy_strided_f16: 16 bytes per lane and access, no LDS, no scratch.
+ * vx_rope_f16: ggml_rope_ext in GGML_ROPE_TYPE_NORMAL on rows of n f16 channels. Row (h, t, b) of x lies at x + h si[0] + t si[1] + b si[2] elements (so: out),
+ * which serves token-major [B][T][heads][n] and head-major [B][heads][T][n] alike. table f32 [T][n]: cos of pair i at [t][i], sin at [t][n / 2 + i], computed
+ * on the host (the kernel only multiplies): out[2i] = (x[2i] cos - x[2i+1] sin) q_scale, out[2i+1] = (x[2i] sin + x[2i+1] cos) q_scale, f32 arithmetic, one
+ * f16 rounding. out == x (in place) is legal with equal strides: a lane reads and writes the same four pairs. Refused (0, vx_last_error, no launch): null or
+ * misaligned (16 bytes) pointers, n % 8 != 0, strides that are no multiples of 8, an empty problem, extents past the kernel's 32-bit indexing, and an output
+ * whose extent overlaps an input's (or the other output's) in any way but being that input's own in-place buffer.
+ * vx_rope_supported / vx_rope2d_supported answer the shape part of that (rows of n, rows of head_dim) without launching. */
+VX_API int vx_rope2d_supported(int head_dim, int heads, int T, int B, const int64_t strides_in[3], const int64_t strides_out[3]);
+VX_API int vx_rope_supported(int n, int heads, int T, int B, const int64_t strides_in[3], const int64_t strides_out[3]);
+VX_API int vx_rope_f16(const void* x, void* out, const float* table, int n, int heads, int T, int B, const int64_t strides_in[3], const int64_t strides_out[3],
+                       float q_scale, void* stream);
+/* apply_rope_2d (sam3.h:413-438) on whole heads of head_dim channels (a multiple of 16): channels [0, hd / 2) are rotated by table_x, [hd / 2, hd) by table_y
+ * (each f32 [T][hd / 2] as above). q and k in ONE launch (blockIdx.y selects; k and k_out NULL: q alone), both with the same strides; q_scale is multiplied
+ * into q only. The launch that replaces 2 x (2 slices + 2 ropes + 1 concat). */
+VX_API int vx_rope2d_f16(const void* q, void* q_out, const void* k, void* k_out, const float* table_x, const float* table_y, int head_dim, int heads, int T, int B,
+                         const int64_t strides_in[3], const int64_t strides_out[3], float q_scale, void* stream);
+/* ggml_get_rows with an index known at run time only: out f16 [n_idx][C] = table f16 [rows][C] at idx i32 [n_idx] (device memory), C % 8 == 0. The guard is
+ * part of the kernel: an index outside [0, rows) gives a row of zeros and reads nothing. */
+VX_API int vx_get_rows_f16(const void* table, const int32_t* idx, void* out, int64_t rows, int C, int64_t n_idx, void* stream);
 /* ggml_roll: dst[i] = src[(i - shift) mod ne] in every dimension (negative shifts wrap); f16, contiguous, dst != src */
 VX_API int vx_roll_f16(const void* src, void* dst, const int64_t ne[4], const int64_t shift[4], void* stream);
 /* ggml_pad: src [src_ne] in the low corner of dst [dst_ne >= src_ne], zeros behind it; f16, contiguous */

@@ -20,7 +20,7 @@ const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_nor
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
                                          "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
-                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos"};
+                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos", "rope"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -361,7 +361,7 @@ int graph_add_weight(graph& g, char const* name, int32_t dtype, const int64_t ne
 
 int graph_input(graph& g, int32_t dtype, const int64_t ne[4], char const* name) {
     require_building(g, "graph_input");
-    if (dtype != gdt_f32 && dtype != gdt_f16 && dtype != gdt_u8) throw except("graph_input: dtype %d (0 = f32, 1 = f16, 24 = u8 image bytes)", dtype);
+    if (dtype != gdt_f32 && dtype != gdt_f16 && dtype != gdt_u8 && dtype != gdt_i32) throw except("graph_input: dtype %d (0 = f32, 1 = f16, 24 = u8 image bytes, 26 = i32 indices)", dtype);
     graph_node n;
     n.op = gop_input;
     n.dtype = dtype;
@@ -532,7 +532,8 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             need_src(1, 1);
             for (int i = 0; i < 4; ++i) {
                 n.ne[i] = n.ip[i];
-                if (n.ip[i] <= 0 || (S(0).ne[i] != 1 && S(0).ne[i] != n.ip[i])) throw except("repeat: %s to %s (source dimensions must be 1 or already equal)", shape_str(S(0).ne).c_str(), shape_str(n.ip).c_str());
+                const bool tiles = S(0).constant && n.ip[i] > 0 && n.ip[i] % S(0).ne[i] == 0; // a constant is tiled on the host (ggml_repeat: out[i] = src[i mod ne_src])
+                if (n.ip[i] <= 0 || (S(0).ne[i] != 1 && S(0).ne[i] != n.ip[i] && !tiles)) throw except("repeat: %s to %s (source dimensions must be 1 or already equal)", shape_str(S(0).ne).c_str(), shape_str(n.ip).c_str());
             }
             break;
         case gop_patch_embed: {
@@ -589,11 +590,16 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
         case gop_get_rows: {
             need_src(2, 2);
             graph_node const &tab = S(0), &idx = S(1);
-            if (idx.dtype != gdt_i32 || !idx.constant) throw except("get_rows: the index is an i32 constant (visp_graph_add_weight with dtype 26)");
+            const bool runtime_idx = idx.dtype == gdt_i32 && idx.op == gop_input; // the token ids of clip_text_embed (sam3.h:225): gathered on the device
+            if (idx.dtype != gdt_i32 || (!idx.constant && !runtime_idx)) throw except("get_rows: the index is an i32 constant (visp_graph_add_weight with dtype 26)");
             if (tab.ne[2] != 1 || tab.ne[3] != 1 || idx.ne[3] != 1) throw except("get_rows: table %s must be a matrix, index %s at most 3-dimensional", shape_str(tab.ne).c_str(), shape_str(idx.ne).c_str());
             if (tab.dtype == gdt_i32) throw except("get_rows: the table is an f16 / f32 tensor");
             n.ne[0] = tab.ne[0]; n.ne[1] = idx.ne[0]; n.ne[2] = idx.ne[1]; n.ne[3] = idx.ne[2];
             n.dtype = gdt_f32; // ggml: the result of get_rows is always f32
+            if (runtime_idx && tab.constant) { // ... but activations of this layer are f16: a gather at run time gives an f16 activation
+                if (tab.ne[0] % 8) throw except("get_rows: a table of %lld channels with a run-time index (a multiple of 8)", (long long)tab.ne[0]);
+                n.dtype = gdt_f16;
+            }
         } break;
         case gop_cast:
             need_src(1, 1);
@@ -659,6 +665,19 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             if (a.dtype != gdt_f16 || b.dtype != gdt_f16) throw except("mul_mat: operands of two activations are f16 (a is %s, b is %s)", a.dtype == gdt_f16 ? "f16" : "f32", b.dtype == gdt_f16 ? "f16" : "f32");
             if (K % 8 || K > 256) throw except("mul_mat: K = %lld; two activations are multiplied for K a multiple of 8, at most 256", (long long)K);
             if (N > 16) throw except("mul_mat: N = %lld columns in the second operand; at most 16 (one thread per row of the first keeps them in registers)", (long long)N);
+        } break;
+        case gop_rope: {
+            need_src(2, 2);
+            graph_node const &x = S(0), &pos = S(1);
+            if (n_ip < 1 || n_fp != 2) throw except("rope: one or two integer parameters (n_dims, mode) and two float parameters (freq_base, freq_scale)");
+            if (n_ip > 1 && n.ip[1] != 0) throw except("rope: mode %lld is not built (0, GGML_ROPE_TYPE_NORMAL: adjacent pairs, is)", (long long)n.ip[1]);
+            if (x.constant || x.dtype != gdt_f16) throw except("rope: x is %s; the operand is an f16 activation [n, heads, T, B]", x.constant ? "a constant" : "f32");
+            if (!pos.constant || pos.dtype != gdt_i32) throw except("rope: the positions are an i32 constant [T] (visp_graph_add_weight with dtype 26), not %s", pos.constant ? "an f16 / f32 constant" : "an activation");
+            if (pos.ne[0] != x.ne[2] || pos.n_elements() != pos.ne[0]) throw except("rope: positions %s do not match the %lld tokens of x %s", shape_str(pos.ne).c_str(), (long long)x.ne[2], shape_str(x.ne).c_str());
+            if (n.ip[0] != x.ne[0]) throw except("rope: n_dims %lld on rows of %lld channels; the op is built for n_dims == ne[0] (slice the part to rotate)", (long long)n.ip[0], (long long)x.ne[0]);
+            if (x.ne[0] % 8) throw except("rope: rows of %lld channels (a multiple of 8)", (long long)x.ne[0]);
+            if (!(n.fp[0] > 0.0f) || !std::isfinite(n.fp[0]) || !std::isfinite(n.fp[1])) throw except("rope: freq_base %g, freq_scale %g (a positive base, finite)", (double)n.fp[0], (double)n.fp[1]);
+            same_shape();
         } break;
         case gop_clamp:
             need_src(1, 1);
@@ -768,7 +787,9 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             // (any conv on a 3- or 4-channel f32 image: image_pad8 in front of the GEMM family's conv, mobile-sam.cpp:71-73, migan.cpp:84-86)
             const bool image8_conv = op == gop_conv_2d && i == 0 && S(0).dtype == gdt_f32 && (S(0).ne[0] == 3 || S(0).ne[0] == 4);
             const bool fourier_head = op == gop_mul_mat && i == 1 && S(0).constant && S(0).ne[0] == 2 && S(1).op == gop_input; // (checked above)
-            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask && !fourier_head)
+            const bool row_index = op == gop_get_rows && i == 1; // (an i32 graph input, checked above)
+            if (!S(i).constant && S(i).dtype == gdt_i32 && !row_index) throw except("%s: operand %d is an i32 graph input; an i32 tensor is an index, not a value (get_rows reads one)", nm, i);
+            if (!S(i).constant && S(i).dtype != gdt_f16 && !head_tail && !image_conv && !image8_conv && !f32_mask && !fourier_head && !row_index)
                 throw except("%s: operand %d is f32; only patch_embed and an image's first 3x3 conv read the f32 input tensor", nm, i);
         }
 

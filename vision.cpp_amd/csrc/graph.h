@@ -45,7 +45,7 @@ enum graph_op : int32_t {
     gop_concat,           // a, b; i0 = dim                            ml.cpp:770-780
     gop_slice,            // x; i[3d..3d+2] = begin, end, step         ml.cpp:746-768
     gop_reshape,          // x; i0..i3 = ne (a view)
-    gop_repeat,           // x; i0..i3 = ne (source dims 1 or equal)   dino.cpp:38-40
+    gop_repeat,           // x; i0..i3 = ne (source dims 1 or equal; a constant source may be tiled: folded)   dino.cpp:38-40, sam3.h:331-334
     gop_patch_embed,      // x f32 [C, W, H, N], w conv weight, (b); i0 = patch size            nn.cpp:166-180
     gop_cont,             // a view: every tensor of this executor is contiguous
     // extensions for callers that keep images in HBM (the batched entries of this library); the reference does both steps on the host
@@ -56,7 +56,7 @@ enum graph_op : int32_t {
     gop_permute,          // x; i0..i3 = ggml_permute's axes: source dimension d becomes dimension i_d; the result is contiguous (cont behind it: a view)
     gop_roll,             // x; i0..i3 = cyclic shifts (negative allowed)  ggml_roll (swin.cpp:116, 124)
     gop_pad,              // x; i0..i3 = zeros appended per dimension       ggml_pad (swin.cpp:111)
-    gop_get_rows,         // table [C, rows], idx i32 constant -> f32 [C, idx.ne0, idx.ne1, idx.ne2]; constants only (folded)   swin.cpp:75
+    gop_get_rows,         // table [C, rows] constant, idx i32: a constant -> f32 (folded); a graph input -> f16 activation [C, idx.ne0, idx.ne1, idx.ne2]   swin.cpp:75, sam3.h:225
     gop_cast,             // x; i0 = type (0 f32, 1 f16): a view on activations of that type, a rounding on constants           swin.cpp:78
     gop_attention_masked, // q, k, v [hd, heads, T, B], mask [T_k, T_q, Hm, Bm]; f0 = scale; hd 32 / 64 -> [hd * heads, T, B]   nn.cpp:210-244 with a mask
     // the nodes of a BiRefNet decoder block (birefnet.cpp:79-145)
@@ -78,6 +78,8 @@ enum graph_op : int32_t {
     gop_mul_mat,          // a [K, M, Ba], b [K, N, B] -> [M, N, B], Ba 1 or B     ggml_mul_mat
     gop_sin,              // ggml_sin
     gop_cos,              // ggml_cos
+    // the node of the SAM3 vision encoder beyond the above (sam3.h:413-438)
+    gop_rope,             // x [n, heads, T, B] f16, pos i32 constant [T]; i0 = n_dims (== n), i1 = mode (0: NORMAL); f0 = freq_base, f1 = freq_scale   ggml_rope_ext
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -148,6 +150,7 @@ enum pack_role : int {
     role_rep_conv_bias = 46, // ... and the two biases summed in f32, [N pad]
     role_plane_f32 = 47,     // a [1, W, H, 1] constant as the f32 plane a fused epilogue adds per pixel (MI-GAN's folded noise)
     role_fourier = 48,       // the [2, F] gaussian matrix of position_embedding_random, rounded to f16, as f32 pairs [F][2]
+    role_rope_table = 49,    // i32 positions [T] -> f32 [T][n]: cos | sin of pos * scale * base^(-2 i / n), computed in double (keyed with n, base, scale)
 };
 // the second form of broadcast add / mul / sub admit next to the trailing-dimension one: b [1, W, H, 1] on a [C, W, H, N], one value per pixel for every
 // channel and image (ggml_mul_inplace(x, filter), ggml_add_inplace(x, noise): migan.cpp:40, 76). Where C == 1 or W H == 1 the trailing rule holds already.

@@ -34,10 +34,19 @@ void lowering::find_qkv_groups() {
     for (int t = 0; t < (int)g.nodes.size(); ++t) {
         graph_node const& n = g.nodes[t];
         if (!needed[t] || n.op != gop_attention) continue;
-        std::array<int, 3> lin{-1, -1, -1};
+        std::array<int, 3> lin{-1, -1, -1}, top{n.src[0], n.src[1], n.src[2]}; // top: where the walk down to the linear starts
+        std::array<int, 2> ropes{-1, -1};
         bool ok = g.nodes[n.src[0]].ne[0] == 64 && g.nodes[n.src[0]].ne[2] == g.nodes[n.src[1]].ne[2];
         for (int i = 0; i < 3 && ok; ++i) {
             int v = n.src[i];
+            // q or k through a rope_2d group (sam3.h:452-453): the group is read by this attention alone, and the view r it rotates by its two slices alone
+            if (auto rg = rope2d_groups.find(v); i < 2 && rg != rope2d_groups.end()) {
+                const int r = rg->second.src;
+                ok = sole_consumer(v) == t && uses[r] == 2 && !g.nodes[r].is_output && g.nodes[r].op == gop_reshape;
+                ropes[i] = v;
+                top[i] = r;
+                if (ok) v = g.nodes[r].src[0];
+            }
             while (ok && (g.nodes[v].op == gop_reshape || g.nodes[v].op == gop_cont)) { // single-reader views only
                 ok = uses[v] == 1 && !g.nodes[v].is_output;
                 v = g.nodes[v].src[0];
@@ -46,6 +55,16 @@ void lowering::find_qkv_groups() {
             lin[i] = v;
         }
         ok = ok && lin[0] != lin[1] && lin[1] != lin[2] && lin[0] != lin[2];
+        if (ok && (ropes[0] >= 0 || ropes[1] >= 0)) { // q and k rotated alike (one launch takes both), or the chain is left to its nodes
+            ok = ropes[0] >= 0 && ropes[1] >= 0;
+            if (ok) {
+                auto const &A = rope2d_groups[ropes[0]], &K = rope2d_groups[ropes[1]];
+                for (int h = 0; h < 2 && ok; ++h) {
+                    graph_node const &a = g.nodes[A.rope[h]], &b = g.nodes[K.rope[h]];
+                    ok = a.src[1] == b.src[1] && a.fp[0] == b.fp[0] && a.fp[1] == b.fp[1];
+                }
+            }
+        }
         for (int i = 1; i < 3 && ok; ++i)
             ok = g.nodes[lin[i]].src[0] == g.nodes[lin[0]].src[0] && g.nodes[g.nodes[lin[i]].src[1]].ne[0] == g.nodes[g.nodes[lin[0]].src[1]].ne[0] &&
                  g.nodes[g.nodes[lin[i]].src[1]].ne[1] == g.nodes[g.nodes[lin[0]].src[1]].ne[1];
@@ -55,8 +74,9 @@ void lowering::find_qkv_groups() {
         qkv_first[std::min({lin[0], lin[1], lin[2]})] = t;
         for (int i = 0; i < 3; ++i) { // the linears and their views are computed by the attention's q|k|v launch (fused_qkv, or the encoder chain's block launch)
             claim(t, {lin[i]});
-            for (int v = n.src[i]; v != lin[i]; v = g.nodes[v].src[0]) claim(t, {v});
+            for (int v = top[i]; v != lin[i]; v = g.nodes[v].src[0]) claim(t, {v});
         }
+        if (ropes[0] >= 0) qkv_rope[t] = ropes; // (their nodes stay claimed by the groups themselves)
     }
 }
 void lowering::fused_qkv(int att) {
@@ -86,6 +106,7 @@ void lowering::fused_qkv(int att) {
     P.bytes = (double)a.M * (p.k_real + p.N) * 2; // (without the operand's image)
     emit_product(P);
     qkv_bufs[att] = hb;
+    if (qkv_rope.count(att)) rope2d_in_place(att, hb);
 }
 
 // q, k, v of an attention node, [hd, H, T, B] -> head-major [hd, T, H, B] copies, q multiplied by q_scale on the way
@@ -249,7 +270,7 @@ void lowering::window_attention(int t, window_group const& G) {
 // read inside the group only; the token tensor and the layer outputs may be graph outputs (they are copied out of the stream as f32).
 bool lowering::match_layer(int att, enc_layer& L) const {
     auto it = qkv_lin.find(att);
-    if (it == qkv_lin.end()) return false;
+    if (it == qkv_lin.end() || qkv_rope.count(att)) return false; // (the block kernel has no rotation in front of its attention)
     for (int i = 0; i < 3; ++i) L.lin[i] = it->second[i];
     L.att = att;
     L.ln1 = g.nodes[L.lin[0]].src[0];

@@ -89,6 +89,7 @@ void lowering::run() {
         }
     }
     find_deform_groups();
+    find_sam3_groups(); // (before find_qkv_groups: the q|k|v chain walks through a rope_2d group)
     find_qkv_groups();
     find_window_groups();
     find_encoder_chain();
@@ -146,8 +147,8 @@ void lowering::run() {
                 tag("mean", 0, (double)x.n_elements() * 2);
             } break;
             case gop_cast: n.alias_of = n.src[0]; break; // an activation already has the type (graph_add refuses the rest): a view
-            case gop_get_rows:
-                throw except("get_rows: a non-constant operand; get_rows is folded on the host from a constant table and a constant index (get_rows on activations is not built)");
+            case gop_get_rows: get_rows(t); break; // an i32 graph input on a constant table; a non-constant table is refused there
+            case gop_rope: rope(t); break;
             case gop_permute: { // one strided copy: destination dimension ip[d] walks source dimension d
                 graph_node const& x = g.nodes[n.src[0]];
                 const int xbuf = buf_of(n.src[0]);
@@ -276,6 +277,7 @@ void lowering::run() {
                 break;
             case gop_concat:
                 if (auto it = fourier_groups.find(t); it != fourier_groups.end()) { fourier_features(t, it->second); break; }
+                if (auto it = rope2d_groups.find(t); it != rope2d_groups.end()) { rope2d(t, it->second); break; }
                 if (cat_sources.count(t)) { concat_in_place(t); break; }
                 copy_op(t);
                 break;

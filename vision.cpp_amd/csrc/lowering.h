@@ -7,6 +7,7 @@
 //   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
 //   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
 //   lower_sam.cpp      attention without a mask on token-major q / k / v, mul_mat of activations, sin / cos, the Fourier-feature group
+//   lower_sam3.cpp     ROPE, the rope_2d group (alone, and in place behind the fused q|k|v product), get_rows with a run-time index
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
 // a `return false` leaves the lowering's state as it was. A finder that accepts a group says so in ONE table (claim): a matcher asks free_node()
@@ -137,6 +138,11 @@ struct lowering {
     // ---- the nodes of the SAM prompt encoder and mask decoder (lower_sam.cpp; the Fourier group in BOTH lowering modes)
     struct fourier_group { int mm = -1, scale = -1, sin = -1, cos = -1; };  // mul_mat(constant [2, F], f32 input) -> scale(2 pi) -> {sin, cos}
     std::map<int, fourier_group> fourier_groups;              // concat(sin, cos, dim 0) node -> the group its one launch computes
+
+    // ---- the nodes of the SAM3 encoders (lower_sam3.cpp; the groups with g.fused_models only)
+    struct rope2d_group { int src = -1, slice[2] = {-1, -1}, rope[2] = {-1, -1}; }; // r [hd, heads, T, B]; the slices of its two halves and their ropes
+    std::map<int, rope2d_group> rope2d_groups;               // concat(rope(slice(r, first half), px), rope(slice(r, second half), py), dim 0) node -> its group
+    std::map<int, std::array<int, 2>> qkv_rope;              // attention node of a fused q|k|v chain -> the rope_2d groups (concat nodes) q and k come through
 
     explicit lowering(graph& gr) : g(gr) {}
     void run(); // the whole lowering: fills g.launches / g.buffers / the arena plan
@@ -340,6 +346,15 @@ struct lowering {
     void attention_cross(int t);
     void mul_mat(int t);
     void sincos(int t);
+
+    // ---- lower_sam3.cpp
+    float* rope_table(int pos_t, int n, float base, float scale);
+    bool match_rope2d_group(int cat, rope2d_group& G) const;
+    void find_sam3_groups();
+    void rope2d(int t, rope2d_group const& G);
+    void rope2d_in_place(int att, std::array<int, 3> const& hb);
+    void rope(int t);
+    void get_rows(int t);
 
     // ---- lower_run.cpp
     void copy_op(int t);

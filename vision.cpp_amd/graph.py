@@ -19,7 +19,7 @@ from . import _lib as lib
 from ._lib import check, get_lib
 
 F32, F16, U8, I32 = 0, 1, 24, 26
-# OP_LINEAR ... OP_COS: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
+# OP_LINEAR ... OP_ROPE: enum visp_graph_op of include/visp_c_api.h, its names without the VISP_ prefix
 globals().update({k.removeprefix("VISP_"): v for k, v in lib.C_API_DECLS.enums["visp_graph_op"].items()})
 SCALE_MODE_NEAREST, SCALE_MODE_BILINEAR, SCALE_MODE_BICUBIC, SCALE_FLAG_ALIGN_CORNERS = 0, 1, 2, 256  # ggml's values (ml.cpp:782-788)
 SLICE_ALL = (0, 2**62, 1)
@@ -164,7 +164,7 @@ class Graph:
 
     def set(self, t: Tensor, array: np.ndarray):
         dtype, ne, _ = self.info(t)
-        a = np.ascontiguousarray(array, dtype={F32: np.float32, U8: np.uint8}.get(dtype, np.float16))
+        a = np.ascontiguousarray(array, dtype={F32: np.float32, U8: np.uint8, I32: np.int32}.get(dtype, np.float16))
         if a.size != int(np.prod(ne)):
             raise ValueError(f"tensor {t} takes {int(np.prod(ne))} elements, got {a.size}")
         check(self._api.visp_graph_tensor_set(self._handle, t.index, a.ctypes.data_as(c_void_p), a.nbytes))
@@ -339,7 +339,7 @@ def leaky_relu(m, x, slope): return m.graph.op(OP_LEAKY_RELU, [x], fparams=[slop
 def permute(m, x, a0, a1, a2, a3): return m.graph.op(OP_PERMUTE, [x], [a0, a1, a2, a3])  # ggml_permute: source dimension d becomes dimension a_d
 def roll(m, x, s0, s1, s2, s3): return m.graph.op(OP_ROLL, [x], [s0, s1, s2, s3])  # ggml_roll
 def pad(m, x, p0, p1, p2, p3): return m.graph.op(OP_PAD, [x], [p0, p1, p2, p3])  # ggml_pad
-def get_rows(m, table, index): return m.graph.op(OP_GET_ROWS, [table, index])  # ggml_get_rows (constants only: folded)
+def get_rows(m, table, index): return m.graph.op(OP_GET_ROWS, [table, index])  # ggml_get_rows: a constant index is folded (f32); an i32 graph input gathers on the device (f16)
 def sigmoid(m, x): return m.graph.op(OP_SIGMOID, [x])  # ggml_sigmoid
 def mean_2d(m, x): return m.graph.op(OP_MEAN_2D, [x])  # birefnet.cpp:93-100: [C, W, H, N] -> [C, 1, 1, N] (not ggml_mean, which reduces ne[0])
 def cast(m, x, dtype): return m.graph.op(OP_CAST, [x], [dtype])  # ggml_cast
@@ -1250,3 +1250,221 @@ def sam_predict_mask(m: ModelRef, image_embed: Tensor, prompt_embed: Tensor):  #
     dense_prompt = sam_no_mask_embed(m["prompt_encoder"])
     masks, iou = sam_predict_masks(m["dec"], image_embed, prompt_embed, dense_prompt)
     return m.graph.output(masks, "masks"), m.graph.output(iou, "iou")
+
+
+# ---- SAM3 vision encoder and CLIP text encoder against this layer (the structure of src/visp/arch/sam3.h) ----------------------------------------------
+# Node for node, with these departures. Maps are CWHN here, so the reference's WHCN reshape / permute / cont behind the patch conv (sam3.h:320-323) is one
+# reshape, and the conv itself (kernel == stride on the f32 image) is the PATCH_EMBED node. The rope positions are i32 CONSTANTS under the reference's names
+# (it fills graph inputs on the host, :391-411), and the sine position embedding is an f32 constant computed on the host, CWHN (:524-564 fills a WHCN input).
+# The causal mask [T, T, 1, 1] f16 and the token ids [T] (or [T, B]) i32 are graph inputs; the CLIP tokenizer is not part of this layer.
+
+ROPE_TYPE_NORMAL = 0  # GGML_ROPE_TYPE_NORMAL: adjacent pairs
+
+
+def rope(m, x, pos, n_dims, freq_base, freq_scale):  # ggml_rope_ext in GGML_ROPE_TYPE_NORMAL; pos an i32 constant [T]
+    return m.graph.op(OP_ROPE, [x, pos], [n_dims, ROPE_TYPE_NORMAL], [freq_base, freq_scale])
+
+
+class Sam3VitParams:  # sam3_vit_params, sam3.h:299-307
+    def __init__(self, image_size=1008, patch_size=14, window_size=24, n_layers=32, n_heads=16, global_attn_indexes=(7, 15, 23, 31)):
+        self.image_size, self.patch_size, self.window_size, self.n_layers, self.n_heads = image_size, patch_size, window_size, n_layers, n_heads
+        self.global_attn_indexes = tuple(global_attn_indexes)
+
+
+def clip_text_embed(m: ModelRef, ids: Tensor) -> Tensor:  # sam3.h:221-231; ids i32 [T] or [T, B], a graph input
+    seq_len = ids.ne[0]
+    token_embeds = get_rows(m, m.weights("token_embedding.weight"), ids)
+    pos_embeds = slice_(m, m.weights("position_embedding.weight"), SLICE_ALL, (0, seq_len))
+    return add(m, token_embeds, pos_embeds)
+
+
+def clip_attention(m: ModelRef, x: Tensor, attention_mask: Tensor, n_heads: int = 16) -> Tensor:  # sam3.h:233-247
+    head_dim = x.ne[0] // n_heads
+    q, k, v = (reshape(m, linear(m[name], x), head_dim, n_heads, x.ne[1], x.ne[2]) for name in ("q_proj", "k_proj", "v_proj"))
+    return attention(m, q, k, v, attention_mask, 1.0 / math.sqrt(float(head_dim)), m["out_proj"])
+
+
+def clip_mlp(m: ModelRef, x: Tensor) -> Tensor:  # sam3.h:249-254
+    return linear(m["fc2"], gelu(m, linear(m["fc1"], x)))
+
+
+def clip_encoder_layer(m: ModelRef, x: Tensor, attention_mask: Tensor, n_heads: int = 16) -> Tensor:  # sam3.h:256-267
+    x = add(m, clip_attention(m["self_attn"], layer_norm(m["layer_norm1"], x), attention_mask, n_heads), x)
+    return add(m, clip_mlp(m["mlp"], layer_norm(m["layer_norm2"], x)), x)
+
+
+def clip_text_encode(m: ModelRef, embeds: Tensor, attention_mask: Tensor, n_heads: int = 16) -> Tensor:  # sam3.h:269-275 (24 layers in SAM3: counted from the weights)
+    layers, i = m["layers"], 0
+    while layers[i].find("layer_norm1.weight") is not None:
+        embeds = clip_encoder_layer(layers[i], embeds, attention_mask, n_heads)
+        i += 1
+    return embeds
+
+
+def clip_encode_text(m: ModelRef, ids: Tensor, attention_mask: Tensor, n_heads: int = 16) -> Tensor:  # sam3.h:277-282
+    embeds = clip_text_embed(m["embeddings"], ids)
+    encoded = clip_text_encode(m["encoder"], embeds, attention_mask, n_heads)
+    return layer_norm(m["final_layer_norm"], encoded)
+
+
+def sam3_encode_text(m: ModelRef, ids: Tensor, attention_mask: Tensor, n_heads: int = 16) -> Tensor:  # sam3.h:284-288; m = "det"
+    return linear(m["text_projection"], clip_encode_text(m["te.text_model"], ids, attention_mask, n_heads))
+
+
+def clip_causal_mask(n_tokens: int, max_tokens: int) -> np.ndarray:
+    """The mask clip_tokenizer::tokenize builds (sam3.h:146-192) for a prompt of n_tokens ids (bos and eos included): causal on the prompt's rows, the
+    padding rows see the whole prompt. f16 [max_tokens, max_tokens] of 0 / -inf."""
+    mask = np.full((max_tokens, max_tokens), -np.inf, np.float16)
+    for row in range(max_tokens):
+        mask[row, : (row + 1 if row < n_tokens else n_tokens)] = 0
+    return mask
+
+
+def sam3_vision_embed(m: ModelRef, image: Tensor, patch_size: int) -> Tensor:  # sam3.h:313-338; image f32 [3, W, H, N]
+    c, w, h, b = image.ne
+    wp, hp = w // patch_size, h // patch_size
+    embed = patch_embed(m["patch_embeddings"], image, patch_size)
+    embed = reshape(m, embed, embed.ne[0], wp * hp, b)
+    pos_embed = m.weights("position_embeddings")
+    hidden_size = pos_embed.ne[0]
+    pretrain_size = int(math.sqrt(float(pos_embed.ne[1])) + 0.5)
+    if wp == pretrain_size and hp == pretrain_size:
+        pos_embed = reshape(m, pos_embed, hidden_size, wp * hp, 1)
+    else:  # tile the position embeddings to the image's grid
+        pos_embed = reshape(m, pos_embed, hidden_size, pretrain_size, pretrain_size, 1)
+        pos_embed = repeat(m, pos_embed, hidden_size, wp, hp, 1)
+        pos_embed = reshape(m, pos_embed, hidden_size, wp * hp, 1)
+    return named(m, add(m, embed, pos_embed))
+
+
+def sam3_mlp(m: ModelRef, x: Tensor) -> Tensor:  # sam3.h:340-345
+    return linear(m["fc2"], gelu(m, linear(m["fc1"], x)))
+
+
+def sam3_window_partition(m: ModelRef, x: Tensor, window: int) -> Tensor:  # sam3.h:347-366
+    c, w, h, b = x.ne
+    px, py = (window - w % window) % window, (window - h % window) % window
+    npw, nph = (w + px) // window, (h + py) // window
+    if px > 0 or py > 0:
+        x = pad(m, x, 0, px, py, 0)
+    x = reshape(m, x, c * window, npw, window, nph * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    return reshape(m, x, c, window * window, npw * nph * b)
+
+
+def sam3_window_reverse(m: ModelRef, x: Tensor, w: int, h: int, window: int, b: int) -> Tensor:  # sam3.h:368-389 (b: the reference reads ne[3] of a 3-D tensor)
+    c = x.ne[0]
+    px, py = (window - w % window) % window, (window - h % window) % window
+    npw, nph = (w + px) // window, (h + py) // window
+    x = reshape(m, x, c * window, window, npw, nph * b)
+    x = cont(m, permute(m, x, 0, 2, 1, 3))
+    x = reshape(m, x, c, w + px, h + py, b)
+    if px > 0 or py > 0:
+        x = cont(m, slice_(m, x, SLICE_ALL, (0, w), (0, h)))
+    return x
+
+
+class Rope2dPositions:  # rope_2d_positions, sam3.h:293-297
+    def __init__(self, x: Tensor, y: Tensor, scale: float):
+        self.x, self.y, self.scale = x, y, scale
+
+
+def sam3_rope_2d_positions(m: ModelRef, n_pos: int, n_rows: int, scale: float, name: str) -> Rope2dPositions:  # sam3.h:391-411: i32 constants "<name>.x", "<name>.y"
+    g, i = m.graph, np.arange(n_pos, dtype=np.int32)
+    px = g.get_tensor(f"{name}.x") or g.add_weight(f"{name}.x", i % n_rows, I32)
+    py = g.get_tensor(f"{name}.y") or g.add_weight(f"{name}.y", i // n_rows, I32)
+    return Rope2dPositions(px, py, scale)
+
+
+def sam3_apply_rope_2d(m: ModelRef, x: Tensor, pos: Rope2dPositions) -> Tensor:  # sam3.h:413-438: x positions on the first half of a head, y on the second
+    freq_base, dim = 10000.0, x.ne[0]
+    first = rope(m, slice_(m, x, (0, dim // 2)), pos.x, dim // 2, freq_base, pos.scale)
+    second = rope(m, slice_(m, x, (dim // 2, dim)), pos.y, dim // 2, freq_base, pos.scale)
+    return concat(m, [first, second], 0)
+
+
+def sam3_rope_attention(m: ModelRef, x: Tensor, n_heads: int, pos: Rope2dPositions) -> Tensor:  # sam3.h:440-455
+    head_dim = x.ne[0] // n_heads
+    q, k, v = (reshape(m, linear(m[name], x), head_dim, n_heads, x.ne[1], x.ne[2]) for name in ("q_proj", "k_proj", "v_proj"))
+    q, k = sam3_apply_rope_2d(m, q, pos), sam3_apply_rope_2d(m, k, pos)
+    return attention(m, q, k, v, None, 1.0 / math.sqrt(float(head_dim)), m["o_proj"])
+
+
+def sam3_vision_layer(m: ModelRef, x: Tensor, window_size: int, n_heads: int, rope_pos: Rope2dPositions) -> Tensor:  # sam3.h:457-483; x [C, W, H, B]
+    residual_attn = x
+    x = layer_norm(m["layer_norm1"], x)
+    c, w, h, b = x.ne
+    x = sam3_window_partition(m, x, window_size) if window_size > 0 else reshape(m, x, c, w * h, b)
+    x = sam3_rope_attention(m["attention"], x, n_heads, rope_pos)
+    x = sam3_window_reverse(m, x, w, h, window_size, b) if window_size > 0 else reshape(m, x, c, w, h, b)
+    x = add(m, x, residual_attn)
+    x = add(m, sam3_mlp(m["mlp"], layer_norm(m["layer_norm2"], x)), x)
+    return named(m, x)
+
+
+def sam3_vision_transformer(m: ModelRef, image: Tensor, p: Sam3VitParams) -> Tensor:  # sam3.h:485-515
+    x = sam3_vision_embed(m["embeddings"], image, p.patch_size)
+    c, w, h, b = x.ne[0], image.ne[1] // p.patch_size, image.ne[2] // p.patch_size, image.ne[3]
+    x = reshape(m, x, c, w, h, b)
+    pos_window = sam3_rope_2d_positions(m, p.window_size ** 2, p.window_size, 1.0, "_vit_rope_pos_window")
+    n_rows_global = p.image_size // p.patch_size
+    pos_global = sam3_rope_2d_positions(m, n_rows_global ** 2, n_rows_global, float(p.window_size) / float(n_rows_global), "_vit_rope_pos_global")
+    x = layer_norm(m["layer_norm"], x)
+    for i in range(p.n_layers):
+        is_global = i in p.global_attn_indexes
+        x = sam3_vision_layer(m["layers"][i], x, 0 if is_global else p.window_size, p.n_heads, pos_global if is_global else pos_window)
+    return reshape(m, x, c, w * h, b)
+
+
+def sam3_sine_position_values(width: int, height: int, n_pos_feats: int, normalize: bool) -> np.ndarray:
+    """sam3.h:537-561 in its f32 arithmetic: numpy [2 n_pos_feats, height, width] (y features first), the reference's WHCN tensor."""
+    f32 = np.float32
+    dim_t = np.power(f32(10000.0), (f32(2.0) * (np.arange(n_pos_feats) // 2).astype(f32) / f32(n_pos_feats))).astype(f32)
+    y, x = np.arange(1, height + 1, dtype=f32), np.arange(1, width + 1, dtype=f32)
+    if normalize:
+        y, x = y / (f32(height) + f32(1e-6)) * f32(2.0 * math.pi), x / (f32(width) + f32(1e-6)) * f32(2.0 * math.pi)
+    even = (np.arange(n_pos_feats) % 2 == 0)[:, None]
+    ay, ax = (y[None, :] / dim_t[:, None]).astype(f32), (x[None, :] / dim_t[:, None]).astype(f32)
+    fy, fx = np.where(even, np.sin(ay), np.cos(ay)).astype(f32), np.where(even, np.sin(ax), np.cos(ax)).astype(f32)
+    out = np.empty((2 * n_pos_feats, height, width), f32)
+    out[:n_pos_feats], out[n_pos_feats:] = fy[:, :, None], fx[:, None, :]
+    return out
+
+
+def sam3_sine_position_embedding(m: ModelRef, shape, n_pos_feats: int, normalize: bool) -> Tensor:  # sam3.h:524-564; shape = the map's (C, W, H, N)
+    _, width, height, _ = shape
+    name = f"_sine_pos_embed_{width}x{height}x{n_pos_feats}{'_norm' if normalize else ''}"
+    pe = m.graph.get_tensor(name)
+    if pe is None:  # CWHN: [2 F, W, H, 1]
+        pe = m.graph.add_weight(name, sam3_sine_position_values(width, height, n_pos_feats, normalize).transpose(1, 2, 0)[None], F32)
+    return pe
+
+
+def sam3_fpn_layer(m: ModelRef, x: Tensor, index: int) -> Tensor:  # sam3.h:566-587
+    if index == 0:  # scale factor 4
+        x = conv_transpose_2d(m["scale_layers.0"], x, 2)
+        x = gelu(m, x)
+        x = conv_transpose_2d(m["scale_layers.2"], x, 2)
+    elif index == 1:  # scale factor 2
+        x = conv_transpose_2d(m["scale_layers.0"], x, 2)
+    elif index == 3:  # scale factor 0.5
+        x = pool_2d(m, x, POOL_MAX, 2, 2, 2, 2, 0, 0)
+    elif index != 2:
+        raise ValueError(f"Invalid FPN layer index {index}")
+    x = conv_2d(m["proj1"], x, 1, 0)
+    return conv_2d(m["proj2"], x, 1, 1)
+
+
+def sam3_vision_neck(m: ModelRef, x: Tensor):  # sam3.h:589-602 -> (fpn_hidden_states, fpn_position_encoding), four each
+    hidden, pos = [], []
+    for i in range(4):
+        hidden.append(sam3_fpn_layer(m["fpn_layers"][i], x, i))
+        pos.append(sam3_sine_position_embedding(m, hidden[i].ne, hidden[i].ne[0] // 2, True))
+    return hidden, pos
+
+
+def sam3_encode_vision(m: ModelRef, image: Tensor, p: Sam3VitParams):  # sam3.h:604-613; m = "det.ve"; image f32 [3, W, H, N]
+    c, w, h, b = image.ne
+    x = sam3_vision_transformer(m["backbone"], image, p)
+    x = reshape(m, x, x.ne[0], w // p.patch_size, h // p.patch_size, b)
+    return sam3_vision_neck(m["neck"], x)

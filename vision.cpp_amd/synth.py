@@ -940,3 +940,174 @@ def write_yolov9t_gguf(path: str | Path, seed: int = 0, sd: dict[str, np.ndarray
     from .convert import convert_yolov9t
     sd = sd if sd is not None else yolov9t_state_dict(seed, **kw)
     return convert_yolov9t(sd, path)
+
+
+# ---- SAM3 vision encoder + CLIP text encoder (reference src/visp/arch/sam3.h, scripts/convert.py:288-351, tests/test_sam3.py::_convert_tensor_names) ----
+
+@dataclass
+class Sam3VitConfig:
+    """Sam3ViTConfig + the neck's width, with the reference's sam3_vit_params defaults (sam3.h:299-307)."""
+    hidden: int = 1024
+    heads: int = 16
+    mlp: int = 4736
+    patch: int = 14
+    window: int = 24
+    pretrain_grid: int = 24        # position embeddings of pretrain_grid x pretrain_grid patches, tiled to the image's grid
+    image_size: int = 1008
+    n_layers: int = 32
+    global_layers: tuple = (7, 15, 23, 31)
+    fpn_dim: int = 256
+    name: str = "sam3"
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch
+
+
+@dataclass
+class ClipTextConfig:
+    hidden: int = 1024
+    heads: int = 16
+    mlp: int = 4096
+    vocab: int = 49408
+    positions: int = 32
+    n_layers: int = 24
+    proj_dim: int = 256            # det.text_projection: CLIP's hidden size -> the detector's
+    name: str = "clip"
+
+
+SAM3_VIT = Sam3VitConfig()
+SAM3_VIT_MINI = Sam3VitConfig(hidden=128, heads=2, mlp=256, patch=2, window=4, pretrain_grid=4, image_size=16, n_layers=2, global_layers=(1,), fpn_dim=32, name="sam3_mini")
+CLIP_TEXT = ClipTextConfig()
+CLIP_TEXT_MINI = ClipTextConfig(hidden=128, heads=2, mlp=256, vocab=100, positions=8, n_layers=2, proj_dim=32, name="clip_mini")
+
+
+def _sam3_helpers(rng, sd):
+    def normal(shape, std):
+        return (rng.standard_normal(shape) * std).astype(np.float32)
+
+    def lin(name, out_f, in_f, gain=1.0):
+        sd[f"{name}.weight"] = normal((out_f, in_f), gain / np.sqrt(in_f))
+        sd[f"{name}.bias"] = normal((out_f,), 0.02)
+
+    def norm(name, c):
+        sd[f"{name}.weight"] = (1.0 + rng.standard_normal(c) * 0.05).astype(np.float32)
+        sd[f"{name}.bias"] = normal((c,), 0.02)
+
+    return normal, lin, norm
+
+
+def sam3_vision_state_dict(cfg: Sam3VitConfig = SAM3_VIT_MINI, seed: int = 0, prefix: str = "detector_model.vision_encoder.") -> dict[str, np.ndarray]:
+    """float32 tensors under the names of transformers' Sam3VisionModel inside Sam3Model, torch shapes: the ViT backbone and the FPN neck."""
+    rng = np.random.default_rng(seed)
+    sd: dict[str, np.ndarray] = {}
+    normal, lin, norm = _sam3_helpers(rng, sd)
+    C, bb = cfg.hidden, prefix + "backbone."
+    sd[bb + "embeddings.patch_embeddings.projection.weight"] = normal((C, 3, cfg.patch, cfg.patch), 1.0 / np.sqrt(3 * cfg.patch ** 2))
+    sd[bb + "embeddings.position_embeddings"] = normal((1, cfg.pretrain_grid ** 2, C), 0.5)
+    norm(bb + "layer_norm", C)
+    for i in range(cfg.n_layers):
+        p = f"{bb}layers.{i}"
+        norm(f"{p}.layer_norm1", C)
+        for name in ("q_proj", "k_proj", "v_proj"):
+            lin(f"{p}.attention.{name}", C, C, gain=1.5)
+        lin(f"{p}.attention.o_proj", C, C)
+        norm(f"{p}.layer_norm2", C)
+        lin(f"{p}.mlp.fc1", cfg.mlp, C, gain=1.4)
+        lin(f"{p}.mlp.fc2", C, cfg.mlp, gain=1.4)
+    for i in range(4):  # scale factors 4, 2, 1, 0.5 (Sam3FPNLayer)
+        p, mid = f"{prefix}neck.fpn_layers.{i}", C
+        if i == 0:
+            sd[f"{p}.scale_layers.0.weight"] = normal((C, C // 2, 2, 2), 1.0 / np.sqrt(C))
+            sd[f"{p}.scale_layers.0.bias"] = normal((C // 2,), 0.02)
+            sd[f"{p}.scale_layers.2.weight"] = normal((C // 2, C // 4, 2, 2), 1.0 / np.sqrt(C // 2))
+            sd[f"{p}.scale_layers.2.bias"] = normal((C // 4,), 0.02)
+            mid = C // 4
+        elif i == 1:
+            sd[f"{p}.scale_layers.0.weight"] = normal((C, C // 2, 2, 2), 1.0 / np.sqrt(C))
+            sd[f"{p}.scale_layers.0.bias"] = normal((C // 2,), 0.02)
+            mid = C // 2
+        sd[f"{p}.proj1.weight"] = normal((cfg.fpn_dim, mid, 1, 1), 1.0 / np.sqrt(mid))
+        sd[f"{p}.proj1.bias"] = normal((cfg.fpn_dim,), 0.02)
+        sd[f"{p}.proj2.weight"] = normal((cfg.fpn_dim, cfg.fpn_dim, 3, 3), 1.0 / np.sqrt(9 * cfg.fpn_dim))
+        sd[f"{p}.proj2.bias"] = normal((cfg.fpn_dim,), 0.02)
+    return sd
+
+
+def clip_text_state_dict(cfg: ClipTextConfig = CLIP_TEXT_MINI, seed: int = 0, prefix: str = "detector_model.") -> dict[str, np.ndarray]:
+    """float32 tensors under the names of Sam3Model's text side: CLIPTextModelWithProjection's text_model and the detector's text_projection."""
+    rng = np.random.default_rng(seed)
+    sd: dict[str, np.ndarray] = {}
+    normal, lin, norm = _sam3_helpers(rng, sd)
+    C, tm = cfg.hidden, prefix + "text_encoder.text_model."
+    sd[tm + "embeddings.token_embedding.weight"] = normal((cfg.vocab, C), 0.5)
+    sd[tm + "embeddings.position_embedding.weight"] = normal((cfg.positions, C), 0.5)
+    for i in range(cfg.n_layers):
+        p = f"{tm}encoder.layers.{i}"
+        norm(f"{p}.layer_norm1", C)
+        for name in ("q_proj", "k_proj", "v_proj"):
+            lin(f"{p}.self_attn.{name}", C, C, gain=1.5)
+        lin(f"{p}.self_attn.out_proj", C, C)
+        norm(f"{p}.layer_norm2", C)
+        lin(f"{p}.mlp.fc1", cfg.mlp, C, gain=1.4)
+        lin(f"{p}.mlp.fc2", C, cfg.mlp, gain=1.4)
+    norm(tm + "final_layer_norm", C)
+    lin(prefix + "text_projection", cfg.proj_dim, C)
+    return sd
+
+
+def sam3_tensor_name(key: str) -> str:
+    """convert_sam3's renaming (scripts/convert.py:342-349)."""
+    for a, b in (("detector_model", "det"), ("text_encoder", "te"), ("vision_encoder", "ve"), ("tracker_model", "trk"), ("mask_decoder.", "decoder."),
+                 ("_image_to_token.", "_i2t."), ("_token_to_image.", "_t2i.")):
+        key = key.replace(a, b)
+    return key
+
+
+def sam3_gguf_tensors(sd: dict[str, np.ndarray]):
+    """convert_sam3's rules (scripts/convert.py:338-351): every tensor renamed and written f16 in its torch layout, CLIP's own text_projection left out. The
+    reference runs SAM3 in WHCN and lists nothing; for this layer's CWHN maps the Conv2d kernels are listed in conv2d_weights (ConvTranspose2d kernels are
+    read as they are stored). Returns (name -> array as stored, conv2d_weights index list)."""
+    out: dict[str, np.ndarray] = {}
+    conv2d: list[int] = []
+    for key, t in sd.items():
+        if key.startswith("detector_model.text_encoder.text_projection"):
+            continue
+        if t.ndim == 4 and "scale_layers" not in key:
+            conv2d.append(len(out))
+        out[sam3_tensor_name(key)] = t.astype(np.float16)
+    return out, conv2d
+
+
+def sam3_graph_tensors(sd: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
+    """The same tensors as the weight store presents them after loading (conv kernels OHWI = ne [Cin, kw, kh, Cout]), f16-rounded f32: what a test adds to a
+    graph without going through a file."""
+    tensors, conv2d = sam3_gguf_tensors(sd)
+    out = {}
+    for i, (name, t) in enumerate(tensors.items()):
+        t = t.astype(np.float32)
+        out[name] = np.ascontiguousarray(t.transpose(0, 2, 3, 1)) if i in conv2d else t
+    return out
+
+
+def write_sam3_gguf(path: str | Path, vit: Sam3VitConfig | None = SAM3_VIT_MINI, text: ClipTextConfig | None = CLIP_TEXT_MINI, seed: int = 0, sd=None) -> Path:
+    """A 'sam3' GGUF with the vision encoder and / or the text encoder (no tokenizer vocabulary: ids are the caller's)."""
+    if sd is None:
+        sd = {}
+        if vit is not None:
+            sd.update(sam3_vision_state_dict(vit, seed))
+        if text is not None:
+            sd.update(clip_text_state_dict(text, seed + 1000))
+    tensors, conv2d = sam3_gguf_tensors(sd)
+    w = GGUFWriter(path, "sam3")
+    w.add_string("sam3.tensor_data_layout", "whcn")
+    if text is not None:
+        w.add_int32("sam3.tokenizer.max_length", text.positions)
+    w.add_uint32("general.quantization_version", 2)
+    w.add_uint32("general.file_type", 1)
+    if conv2d:
+        w.add_array_i32("sam3.conv2d_weights", conv2d)
+    for name, t in tensors.items():
+        w.add_tensor(name, t)
+    w.write()
+    return Path(path)
