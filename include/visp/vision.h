@@ -5,7 +5,8 @@
 // Header-only over the binary-stable C ABI (include/visp_c_api.h, lib/libvisioncpp.so): link with -lvisioncpp.
 //
 // Covered: backend_init / backend_device, image_view / image_data / image_alloc / image_clear / image_scale / image_u8_to_f32 /
-// image_normalize, per family *_load_model + *_compute for depth_anything, esrgan, birefnet and sam (sam_encode + sam_compute with a
+// image_normalize / image_span / image_to_mask / image_set_alpha / image_blur / image_erosion / image_estimate_foreground /
+// image_alpha_composite, birefnet_cutout, per family *_load_model + *_compute for depth_anything, esrgan, birefnet and sam (sam_encode + sam_compute with a
 // point or a box), and the Depth-Anything pipeline pieces depthany_params / depthany_detect_params / depthany_image_extent /
 // depthany_process_input / depthany_process_output (vision.h:236-252).
 // The ml.h layer -- model_file, model_weights, compute_graph, model_ref, tensor, transfer_* -- is visp/ml.h, the nn.h builders visp/nn.h.
@@ -130,6 +131,87 @@ inline image_data image_normalize(image_view const& img, float min = 0, float ma
     visp_image_data* owner = nullptr;
     detail::check(visp_image_normalize(&in, min, max, &out, &owner));
     return detail::take(out, owner);
+}
+
+// include/visp/image.h:68-88: mutable, non-owning; converts to an image_view
+struct image_span {
+    i32x2 extent;
+    int32_t stride = 0;
+    image_format format = image_format::rgba_u8;
+    void* data = nullptr;
+
+    image_span() = default;
+    image_span(image_data& img) : extent(img.extent), stride(img.extent[0] * n_bytes(img.format)), format(img.format), data(img.data.get()) {}
+    image_span(i32x2 e, image_format f, void* d) : extent(e), stride(e[0] * n_bytes(f)), format(f), data(d) {}
+    image_span(i32x2 e, std::span<float> d) : image_span(e, image_format::alpha_f32, d.data()) {} // one float per pixel
+    operator image_view() const { return image_view(extent, stride, format, data); }
+};
+namespace detail {
+inline void take_into(visp_image_view const& v, visp_image_data* owner, image_span const& dst, char const* who) { // the library-owned result into the caller's span
+    const bool fits = dst.extent == i32x2{v.width, v.height} && int32_t(dst.format) == v.format && dst.data;
+    const size_t row = size_t(v.width) * size_t(n_bytes(image_format(v.format)));
+    for (int y = 0; fits && y < v.height; ++y)
+        std::memcpy(static_cast<uint8_t*>(dst.data) + size_t(y) * size_t(dst.stride), static_cast<uint8_t const*>(v.data) + size_t(y) * size_t(v.stride), row);
+    visp_image_destroy(owner);
+    if (!fits) throw exception(std::string(who) + ": the destination's extent or format differs from the source's");
+}
+} // namespace detail
+
+// The matting ops (include/visp/image.h:141-170). They compute on the calling thread's current HIP device (the reference's run on the host and take no
+// device either); image_to_mask and image_set_alpha are host code.
+// image.cpp:304-308: the first channel of a u8 image as alpha_u8
+inline image_data image_to_mask(image_view const& src) {
+    visp_image_view in = detail::c_view(src), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_to_mask(&in, &out, &owner));
+    return detail::take(out, owner);
+}
+inline void image_to_mask(image_view const& src, image_span const& dst) {
+    visp_image_view in = detail::c_view(src), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_to_mask(&in, &out, &owner));
+    detail::take_into(out, owner, dst, "image_to_mask");
+}
+// image.cpp:310-323: writes `alpha` (alpha_u8) to the alpha channel of `img` (rgba_u8 / bgra_u8 / argb_u8), in place
+inline void image_set_alpha(image_span const& img, image_view const& alpha) {
+    visp_image_view in = detail::c_view(img), a = detail::c_view(alpha), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_set_alpha(&in, &a, &out, &owner));
+    detail::take_into(out, owner, img, "image_set_alpha");
+}
+// image.cpp:410-419: box filter of size 2 radius + 1, alpha_f32 / rgba_f32
+inline void image_blur(image_view const& src, image_span const& dst, int radius) {
+    visp_image_view in = detail::c_view(src), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_blur(nullptr, &in, radius, &out, &owner));
+    detail::take_into(out, owner, dst, "image_blur");
+}
+// image.cpp:527-535: minimum in the square neighbourhood, alpha_u8 / alpha_f32
+inline void image_erosion(image_view const& src, image_span const& dst, int radius) {
+    visp_image_view in = detail::c_view(src), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_erosion(nullptr, &in, radius, &out, &owner));
+    detail::take_into(out, owner, dst, "image_erosion");
+}
+// image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
+inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
+    visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_estimate_foreground(nullptr, &in, &mk, radius, &out, &owner));
+    return detail::take(out, owner);
+}
+// image.cpp:491-507: dst = fg * alpha + bg * (1 - alpha) as rgba_u8
+inline image_data image_alpha_composite(image_view const& fg, image_view const& bg, image_view const& mask) {
+    visp_image_view f = detail::c_view(fg), b = detail::c_view(bg), mk = detail::c_view(mask), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_alpha_composite(nullptr, &f, &b, &mk, &out, &owner));
+    return detail::take(out, owner);
+}
+inline void image_alpha_composite(image_view const& fg, image_view const& bg, image_view const& mask, image_span const& dst) {
+    visp_image_view f = detail::c_view(fg), b = detail::c_view(bg), mk = detail::c_view(mask), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_image_alpha_composite(nullptr, &f, &b, &mk, &out, &owner));
+    detail::take_into(out, owner, dst, "image_alpha_composite");
 }
 
 //
@@ -369,6 +451,14 @@ inline image_data esrgan_compute(esrgan_model& model, image_view image) { return
 using birefnet_model = detail::model_handle<VISP_BIREFNET>;
 inline birefnet_model birefnet_load_model(char const* filepath, backend_device const& dev) { return birefnet_model(detail::load<VISP_BIREFNET>(filepath, dev)); }
 inline image_data birefnet_compute(birefnet_model& model, image_view image) { return detail::compute<VISP_BIREFNET>(model.handle, image); }
+// not in the reference's header: what its `vision-cli birefnet --composite` makes (src/cli/cli.cpp:327-347) -- the image as an rgba_u8 cutout at its own
+// extent, colours from image_estimate_foreground on the network's mask, alpha = the mask -- without the mask leaving the device
+inline image_data birefnet_cutout(birefnet_model& model, image_view image, int radius = 30) {
+    visp_image_view in = detail::c_view(image), out{};
+    visp_image_data* owner = nullptr;
+    detail::check(visp_birefnet_cutout(model.handle, &in, radius, &out, &owner));
+    return detail::take(out, owner);
+}
 
 // MobileSAM (vision.h:139-160): sam_encode once per image, then any number of prompts (vision.cpp:26-92) -> alpha_u8 mask
 using sam_model = detail::model_handle<VISP_SAM>;

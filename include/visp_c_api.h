@@ -283,6 +283,40 @@ VISP_API int32_t visp_sam_read_timing(visp_model* m, visp_timing* out, int32_t c
 VISP_API int32_t visp_birefnet_image_extent(visp_model* m, int32_t w, int32_t h, int32_t* out_w, int32_t* out_h);
 VISP_API int32_t visp_birefnet_compute_batch_device(visp_model* m, void const* rgb_u8, int32_t batch, int32_t w, int32_t h, void* mask_f32, void* stream);
 VISP_API int32_t visp_birefnet_compute_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w, int32_t h, float* mask);
+/* The cutout: visp_birefnet_compute_batch_* as it stands, then the foreground estimator (visp_image_estimate_foreground_batch_device, below) on the mask
+ * where it lies on the device -- what the reference's `vision-cli birefnet --composite` makes on the host (src/cli/cli.cpp:327-347). rgb_u8 [batch, h, w, 3]
+ * at the model extent -> rgba_u8 [batch, h, w, 4], alpha = the mask; radius as for the estimator (the reference's default is 30). stream as above.
+ * visp_model_compute for the family keeps returning the mask. */
+VISP_API int32_t visp_birefnet_cutout_batch_device(visp_model* m, void const* rgb_u8, int32_t batch, int32_t w, int32_t h, int32_t radius, void* rgba_u8_out, void* stream);
+VISP_API int32_t visp_birefnet_cutout_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w, int32_t h, int32_t radius, uint8_t* rgba_u8_out);
+/* one 8-bit colour image of any extent -> rgba_u8 cutout at that extent: the mask as visp_model_compute makes it (kept in f32), then the estimator on the
+ * caller's own pixels; result owned by *out_data */
+VISP_API int32_t visp_birefnet_cutout(visp_model* m, visp_image_view const* image, int32_t radius, visp_image_view* out_image, visp_image_data** out_data);
+
+/* ---- matting image ops (reference include/visp/image.h:141-170, src/visp/image.cpp:290-323, 358-535) ------------------------------------------------
+ * Host views in (the row stride is honoured), a library-owned image out (visp_image_destroy). The four that compute run on `dev`; dev == NULL means the
+ * calling thread's current HIP device. Every argument check -- null, format, extent mismatch, radius -- happens before anything touches a device. */
+/* image_blur: box filter of size 2 radius + 1, edges replicated; alpha_f32 or rgba_f32; 1 <= radius <= min(w, h) / 2. Every output sums its own window:
+ * the reference's running sum along the whole row is not reproduced (its error grows with the row) */
+VISP_API int32_t visp_image_blur(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data);
+/* image_erosion: minimum over the clamped (2 radius + 1)^2 neighbourhood; alpha_u8 or alpha_f32; bit-exact; 1 <= radius <= 64 */
+VISP_API int32_t visp_image_erosion(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data);
+/* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
+ * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
+VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,
+                                                visp_image_view* out_image, visp_image_data** out_data);
+/* image_alpha_composite: fg rgba_u8, bg rgb_u8 or rgba_u8, mask alpha_u8 -> rgba_u8 = trunc((w fg + (1 - w) bg) * 255), w = mask / 255, alpha 255 */
+VISP_API int32_t visp_image_alpha_composite(visp_device const* dev, visp_image_view const* fg, visp_image_view const* bg, visp_image_view const* mask,
+                                            visp_image_view* out_image, visp_image_data** out_data);
+/* host only. image_set_alpha: a copy of img (rgba_u8 / bgra_u8 / argb_u8) with its alpha channel, by the format's channel map, taken from alpha (alpha_u8) */
+VISP_API int32_t visp_image_set_alpha(visp_image_view const* img, visp_image_view const* alpha, visp_image_view* out_image, visp_image_data** out_data);
+/* host only. image_to_mask: the first channel of every pixel of a u8 image as alpha_u8 */
+VISP_API int32_t visp_image_to_mask(visp_image_view const* src, visp_image_view* out_image, visp_image_data** out_data);
+/* the estimator on device-resident batches: img [batch, h, w] pixels of img_format (VISP_RGBA_F32, or VISP_RGB_U8 / VISP_RGBA_U8 read directly: no f32 copy
+ * of the image is made), mask f32 [batch, h, w] -> out [batch, h, w, 4] of out_format (VISP_RGBA_F32 or VISP_RGBA_U8). stream = hipStream_t or NULL (the
+ * device's stream). The workspace (64 bytes per pixel) lives for the call: the stream is synchronised before it returns. */
+VISP_API int32_t visp_image_estimate_foreground_batch_device(visp_device const* dev, void const* img, int32_t img_format, void const* mask_f32, int32_t batch,
+                                                             int32_t w, int32_t h, int32_t radius, void* out, int32_t out_format, void* stream);
 
 /* ---- SWIN encoder, the backbone of BiRefNet (reference src/visp/arch/swin.cpp, swin_encode) ---------
  * The encoder of a birefnet GGUF (tensors bb.*, KV swin.embed_dim) on its own: visp_swin_load reads only the backbone; the

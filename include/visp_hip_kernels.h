@@ -603,6 +603,30 @@ VX_API int vx_yolo_upsample2_f16(const void* x, int64_t x_pix, void* y, int64_t 
 VX_API int vx_yolo_decode(const void* raw0, const void* raw1, const void* raw2, int B, int S, int nc, float* boxes, float* scores, float conf,
                           int* cand_count, int* cand_idx, float* cand_score, void* stream);
 
+/* ---- matting image ops (kernels_matting.hip; image_blur, image_erosion, image_estimate_foreground, image_alpha_composite of the reference's
+ * src/visp/image.cpp:358-535). Images are [B, h, w] pixels, rows *_row ELEMENTS apart (image b starts h rows behind image b - 1), or
+ * contiguous where no row stride is given. Every launcher refuses null and misaligned pointers, an illegal radius, outputs that overlap
+ * inputs and batches whose element count passes 32-bit indexing. No atomics: the same bits every run, for every batch size. */
+/* box filter of size 2 radius + 1, edges replicated, horizontal pass into tmp (f32 [B, h, w, C] contiguous) then vertical pass into y.
+ * C = 1 (alpha_f32) or 4 (rgba_f32; 16-byte aligned pointers, row strides multiples of 4). 1 <= radius <= min(w, h) / 2. Every output
+ * is the sum of its own window, left to right / top to bottom, times fl(1 / (2 radius + 1)) per pass: the reference's running sum over
+ * the whole row is NOT reproduced. */
+VX_API int vx_box_blur_f32(const float* x, int64_t x_row, float* tmp, float* y, int64_t y_row, int B, int h, int w, int C, int radius, void* stream);
+/* minimum over the clamped (2 radius + 1)^2 neighbourhood and the format's one (1.0f / 255), bit-exact; 1 <= radius <= 64 */
+VX_API int vx_erode_f32(const float* x, int64_t x_row, float* y, int64_t y_row, int B, int h, int w, int radius, void* stream);
+VX_API int vx_erode_u8(const uint8_t* x, int64_t x_row, uint8_t* y, int64_t y_row, int B, int h, int w, int radius, void* stream);
+/* One stage of the blur-fusion foreground estimator (image.cpp:423-469) as two launches, all maps contiguous. img: the image, img_format one of
+ * enum visp_image_format: rgba_u8 or rgb_u8 (read directly, / 255 in the loader), or rgba_f32. fg, bg: rgba_f32 maps, or both NULL = the image
+ * itself (stage one). mask f32. planes: f32 workspace [B, h, w, 8], the horizontal window means of m, fg m, bg (1 - m). out: the
+ * foreground, alpha = clamp(mask, 0, 1), as out_format rgba_f32 or rgba_u8 (truncating, as image_store does). bg_out (nullable): the
+ * blurred background as rgba_f32 (its alpha is 0, nothing reads it). passes: 3 = both launches; 1 = the horizontal launch alone, 2 = the vertical launch alone
+ * on the planes an earlier horizontal launch left (per-launch timing, tools/bench_matting.py); 1 then 2 gives the bits of 3. */
+VX_API int vx_foreground_stage(const void* img, int img_format, const float* fg, const float* bg, const float* mask, float* planes, void* out, int out_format,
+                               float* bg_out, int B, int h, int w, int radius, int passes, void* stream);
+/* out rgba_u8 = trunc(clamp(w fg + (1 - w) bg, 0, 1) * 255), w = mask / 255, alpha 255; fg rgba_u8, bg rgb_u8 / rgba_u8 (bg_channels 3 / 4),
+ * mask u8. f32 arithmetic without fused multiply-adds: the bits of the reference's host code. */
+VX_API int vx_alpha_composite_u8(const uint8_t* fg_rgba, const uint8_t* bg, int bg_channels, const uint8_t* mask, uint8_t* out_rgba, int64_t n_pixels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ struct birefnet_model : swin_model { // vision.h birefnet_model counterpart; the
     birefnet_weights dec;
     device_buffer dec_arena;
     device_buffer dws; // decoder / feature workspace
+    device_buffer cutout_ws; // the mask and the foreground estimator's workspace of the cutout entries (matting.h)
 };
 
 birefnet_model* birefnet_load_model(char const* filepath, backend_device const& dev);

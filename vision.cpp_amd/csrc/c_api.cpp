@@ -21,6 +21,7 @@
 #include "tinyvit.h"
 #include "swin.h"
 #include "birefnet.h"
+#include "matting.h"
 #include "graph.h"
 #include "visp_util.h"
 
@@ -135,6 +136,15 @@ void return_image(image_data&& img, visp_image_view* out_image, visp_image_data*
     out_image->stride = owned->extent[0] * n_bytes(owned->format);
     out_image->format = int32_t(owned->format);
     out_image->data = owned->data.get();
+}
+
+// a caller's view as visp::image_view: present, with data, a format of the enum, a positive extent and rows no shorter than their pixels
+image_view host_view(char const* who, visp_image_view const* v) {
+    if (!v || !v->data) throw except("%s: null argument", who);
+    if (v->format < 0 || v->format > int32_t(image_format::alpha_f32)) throw except("Unsupported image format [%d]", v->format);
+    if (v->width < 1 || v->height < 1) throw except("%s: empty image (%dx%d)", who, v->width, v->height);
+    if ((int64_t)v->stride < (int64_t)v->width * n_bytes(image_format(v->format))) throw except("%s: row stride %d is shorter than a row", who, v->stride);
+    return image_view{i32x2{{v->width, v->height}}, v->stride, image_format(v->format), v->data};
 }
 
 } // namespace
@@ -808,6 +818,78 @@ int32_t visp_birefnet_compute_batch_device(visp_model* m, void const* rgb_u8, in
 
 int32_t visp_birefnet_compute_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w, int32_t h, float* mask) {
     return handle_errors([&]() { birefnet_compute_batch_host(as_birefnet(m), rgb_u8, batch, w, h, mask); });
+}
+
+int32_t visp_birefnet_cutout_batch_device(visp_model* m, void const* rgb_u8, int32_t batch, int32_t w, int32_t h, int32_t radius, void* rgba_u8_out, void* stream) {
+    return handle_errors([&]() { birefnet_cutout_batch_device(as_birefnet(m), rgb_u8, batch, w, h, radius, rgba_u8_out, stream); });
+}
+
+int32_t visp_birefnet_cutout_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w, int32_t h, int32_t radius, uint8_t* rgba_u8_out) {
+    return handle_errors([&]() { birefnet_cutout_batch_host(as_birefnet(m), rgb_u8, batch, w, h, radius, rgba_u8_out); });
+}
+
+int32_t visp_birefnet_cutout(visp_model* m, visp_image_view const* image, int32_t radius, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!image || !out_image || !out_data) throw except("visp_birefnet_cutout: null argument");
+        return_image(birefnet_cutout(as_birefnet(m), host_view("visp_birefnet_cutout", image), radius), out_image, out_data);
+    });
+}
+
+// ---- matting image ops (matting.h): the argument checks run inside the visp:: functions, before their first device call ----
+
+int32_t visp_image_blur(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_blur: null argument");
+        return_image(image_blur(dev, host_view("visp_image_blur", src), radius), out_image, out_data);
+    });
+}
+
+int32_t visp_image_erosion(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_erosion: null argument");
+        return_image(image_erosion(dev, host_view("visp_image_erosion", src), radius), out_image, out_data);
+    });
+}
+
+int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius, visp_image_view* out_image,
+                                       visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_estimate_foreground: null argument");
+        return_image(image_estimate_foreground(dev, host_view("visp_image_estimate_foreground", image), host_view("visp_image_estimate_foreground", mask), radius), out_image,
+                     out_data);
+    });
+}
+
+int32_t visp_image_alpha_composite(visp_device const* dev, visp_image_view const* fg, visp_image_view const* bg, visp_image_view const* mask, visp_image_view* out_image,
+                                   visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_alpha_composite: null argument");
+        char const* who = "visp_image_alpha_composite";
+        return_image(image_alpha_composite(dev, host_view(who, fg), host_view(who, bg), host_view(who, mask)), out_image, out_data);
+    });
+}
+
+int32_t visp_image_set_alpha(visp_image_view const* img, visp_image_view const* alpha, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_set_alpha: null argument");
+        return_image(image_set_alpha(host_view("visp_image_set_alpha", img), host_view("visp_image_set_alpha", alpha)), out_image, out_data);
+    });
+}
+
+int32_t visp_image_to_mask(visp_image_view const* src, visp_image_view* out_image, visp_image_data** out_data) {
+    return handle_errors([&]() {
+        if (!out_image || !out_data) throw except("visp_image_to_mask: null argument");
+        return_image(image_to_mask(host_view("visp_image_to_mask", src)), out_image, out_data);
+    });
+}
+
+int32_t visp_image_estimate_foreground_batch_device(visp_device const* dev, void const* img, int32_t img_format, void const* mask_f32, int32_t batch, int32_t w, int32_t h,
+                                                    int32_t radius, void* out, int32_t out_format, void* stream) {
+    return handle_errors([&]() {
+        if (img_format < 0 || img_format > int32_t(image_format::alpha_f32) || out_format < 0 || out_format > int32_t(image_format::alpha_f32))
+            throw except("Unsupported image format [%d]", img_format);
+        estimate_foreground_batch_device(dev, img, image_format(img_format), static_cast<float const*>(mask_f32), batch, w, h, radius, out, image_format(out_format), stream);
+    });
 }
 
 int32_t visp_birefnet_image_extent(visp_model* m, int32_t w, int32_t h, int32_t* out_w, int32_t* out_h) {

@@ -127,4 +127,35 @@ image_data image_to_rgb_u8(image_view const& img) {
     return dst;
 }
 
+image_data image_packed(image_view const& img) {
+    image_data dst = image_alloc(img.extent, img.format);
+    const size_t row = (size_t)img.extent[0] * n_bytes(img.format);
+    const uint8_t* s = static_cast<const uint8_t*>(img.data);
+    for (int y = 0; y < img.extent[1]; ++y) memcpy(dst.data.get() + y * row, s + (size_t)y * img.stride, row);
+    return dst;
+}
+
+image_data image_to_mask(image_view const& src) {
+    if (is_float(src.format)) throw except("image_to_mask: expected a u8 image, got format %d", int(src.format));
+    const int ch = n_channels(src.format);
+    image_data dst = image_alloc(src.extent, image_format::alpha_u8);
+    const uint8_t* s = static_cast<const uint8_t*>(src.data);
+    for (int y = 0; y < src.extent[1]; ++y)
+        for (int x = 0; x < src.extent[0]; ++x) dst.data[(size_t)y * src.extent[0] + x] = s[(size_t)y * src.stride + (size_t)x * ch];
+    return dst;
+}
+
+image_data image_set_alpha(image_view const& img, image_view const& alpha) {
+    if (is_float(img.format) || n_channels(img.format) != 4) throw except("image_set_alpha: expected a 4-channel u8 image, got format %d", int(img.format));
+    if (alpha.format != image_format::alpha_u8) throw except("image_set_alpha: expected an alpha_u8 mask, got format %d", int(alpha.format));
+    if (img.extent != alpha.extent) throw except("image_set_alpha: extents differ (%dx%d and %dx%d)", img.extent[0], img.extent[1], alpha.extent[0], alpha.extent[1]);
+    int map[4];
+    channel_map(img.format, map);
+    image_data dst = image_packed(img);
+    const uint8_t* a = static_cast<const uint8_t*>(alpha.data);
+    for (int y = 0; y < img.extent[1]; ++y)
+        for (int x = 0; x < img.extent[0]; ++x) dst.data[((size_t)y * img.extent[0] + x) * 4 + map[3]] = a[(size_t)y * alpha.stride + x];
+    return dst;
+}
+
 } // namespace visp

@@ -50,5 +50,11 @@ image_data image_normalize(image_view const& img, float min = 0, float max = 1);
 image_data image_scale(image_view const& img, i32x2 target);
 // converts any supported u8 format to tightly packed rgb_u8 (channel map of image.cpp get_channel_map)
 image_data image_to_rgb_u8(image_view const& img);
+// image.cpp:290-308: the first channel of every pixel as alpha_u8 (any u8 format)
+image_data image_to_mask(image_view const& src);
+// image.cpp:310-323: a copy of img (a 4-channel u8 format) whose alpha channel -- by the format's channel map -- is `alpha` (alpha_u8)
+image_data image_set_alpha(image_view const& img, image_view const& alpha);
+// the rows of a view, stride honoured, packed without gaps
+image_data image_packed(image_view const& img);
 
 } // namespace visp

@@ -226,6 +226,27 @@ class Model:
     def segment_batch_device(self, rgb_dev: int, batch: int, w: int, h: int, mask_dev: int, stream: int | None = None):
         check(self._api.visp_birefnet_compute_batch_device(self._handle, rgb_dev, batch, w, h, mask_dev, stream))
 
+    def birefnet_cutout_batch(self, images: np.ndarray, radius: int = 30) -> np.ndarray:
+        """images: uint8 [B, h, w, 3] at the model extent -> uint8 [B, h, w, 4]: foreground colours from the estimator on the network's mask, alpha = the mask."""
+        imgs = np.ascontiguousarray(images, dtype=np.uint8)
+        b, h, w, c = imgs.shape
+        assert c == 3
+        out = np.empty((b, h, w, 4), np.uint8)
+        check(self._api.visp_birefnet_cutout_batch_host(self._handle, imgs.ctypes.data, b, w, h, int(radius), out.ctypes.data))
+        return out
+
+    def birefnet_cutout_batch_device(self, rgb_dev: int, batch: int, w: int, h: int, rgba_dev: int, radius: int = 30, stream: int | None = None):
+        check(self._api.visp_birefnet_cutout_batch_device(self._handle, rgb_dev, batch, w, h, int(radius), rgba_dev, stream))
+
+    def birefnet_cutout(self, image: np.ndarray, format: ImageFormat = ImageFormat.rgb_u8, radius: int = 30) -> np.ndarray:
+        """One 8-bit colour image of any extent -> uint8 [h, w, 4] cutout at that extent."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = img.shape[:2]
+        view = lib.ImageView(w, h, w * _CHANNELS[format.value], format.value, img.ctypes.data)
+        out_view, out_data = lib.ImageView(), c_void_p()
+        check(self._api.visp_birefnet_cutout(self._handle, byref(view), int(radius), byref(out_view), byref(out_data)))
+        return self._take_image(out_view, out_data)
+
     # ---- ESRGAN (family 4): batched extension
     @property
     def esrgan_info(self) -> lib.EsrganInfo:
@@ -356,6 +377,84 @@ def image_scale(image: np.ndarray, width: int, height: int, format: ImageFormat 
     finally:
         api.visp_image_destroy(out_data)
     return res[..., 0] if ch == 1 else res
+
+
+# ---- the matting image ops (reference include/visp/image.h:141-170). Arrays are [h, w] or [h, w, ch]; a view of a wider array keeps its row stride.
+def _view_of(image: np.ndarray, format: ImageFormat):
+    """(ImageView, the array that owns its memory): uint8 or float32 by the format, rows may be strided, pixels are contiguous."""
+    dtype = np.float32 if format.value >= ImageFormat.rgba_f32.value else np.uint8
+    img = np.asarray(image, dtype=dtype)
+    ch = _CHANNELS[format.value]
+    if img.ndim == 2:
+        img = img[..., None]
+    if img.ndim != 3 or img.shape[2] != ch:
+        raise ValueError(f"expected an array of {ch} channel(s) for {format.name}, got shape {image.shape}")
+    if img.strides[2] != img.itemsize or img.strides[1] != ch * img.itemsize or img.strides[0] < img.shape[1] * ch * img.itemsize:
+        img = np.ascontiguousarray(img)
+    return lib.ImageView(img.shape[1], img.shape[0], img.strides[0], format.value, img.ctypes.data), img
+
+
+def _take(out_view, out_data) -> np.ndarray:
+    api = lib.get_lib()
+    try:
+        fmt = out_view.format
+        dtype, ch = (np.float32 if fmt >= ImageFormat.rgba_f32.value else np.uint8), _CHANNELS[fmt]
+        buf = (ctypes.c_uint8 * (out_view.height * out_view.stride)).from_address(out_view.data)
+        res = np.frombuffer(buf, dtype).reshape(out_view.height, out_view.width, ch).copy()
+    finally:
+        api.visp_image_destroy(out_data)
+    return res[..., 0] if ch == 1 else res
+
+
+def _image_op(name: str, views: list, *args, on: tuple = ()) -> np.ndarray:
+    """Calls the C entry `name`(*on, views..., *args, out_view, out_data) and takes the library-owned result; views: what _view_of returns."""
+    out_view, out_data = lib.ImageView(), c_void_p()
+    check(getattr(lib.get_lib(), name)(*on, *(byref(v) for v, _ in views), *args, byref(out_view), byref(out_data)))
+    return _take(out_view, out_data)
+
+
+def _on(device: "Device | None") -> tuple:
+    return (device._handle if device is not None else None,)  # NULL: the calling thread's current HIP device
+
+
+def image_blur(image: np.ndarray, radius: int, device: Device | None = None) -> np.ndarray:
+    """Box filter of size 2 radius + 1 with replicated edges: f32 [h, w] (alpha_f32) or [h, w, 4] (rgba_f32). device None: the current HIP device."""
+    fmt = ImageFormat.alpha_f32 if np.ndim(image) == 2 else ImageFormat.rgba_f32
+    return _image_op("visp_image_blur", [_view_of(image, fmt)], int(radius), on=_on(device))
+
+
+def image_erosion(mask: np.ndarray, radius: int, device: Device | None = None) -> np.ndarray:
+    """Minimum over the (2 radius + 1)^2 neighbourhood: [h, w] uint8 (alpha_u8) or float32 (alpha_f32), same type out."""
+    fmt = ImageFormat.alpha_u8 if np.asarray(mask).dtype == np.uint8 else ImageFormat.alpha_f32
+    return _image_op("visp_image_erosion", [_view_of(mask, fmt)], int(radius), on=_on(device))
+
+
+def image_estimate_foreground(image: np.ndarray, mask: np.ndarray, radius: int = 30, device: Device | None = None) -> np.ndarray:
+    """image f32 [h, w, 4] (rgba_f32), mask f32 [h, w] -> f32 [h, w, 4]: foreground colours, alpha = mask (blur-fusion, two stages)."""
+    return _image_op("visp_image_estimate_foreground", [_view_of(image, ImageFormat.rgba_f32), _view_of(mask, ImageFormat.alpha_f32)], int(radius), on=_on(device))
+
+
+def image_alpha_composite(fg: np.ndarray, bg: np.ndarray, mask: np.ndarray, device: Device | None = None) -> np.ndarray:
+    """fg uint8 [h, w, 4], bg uint8 [h, w, 3 or 4], mask uint8 [h, w] -> uint8 [h, w, 4] = fg * alpha + bg * (1 - alpha), alpha 255."""
+    bg_fmt = ImageFormat.rgb_u8 if np.shape(bg)[-1] == 3 else ImageFormat.rgba_u8
+    return _image_op("visp_image_alpha_composite", [_view_of(fg, ImageFormat.rgba_u8), _view_of(bg, bg_fmt), _view_of(mask, ImageFormat.alpha_u8)], on=_on(device))
+
+
+def image_set_alpha(image: np.ndarray, alpha: np.ndarray, format: ImageFormat = ImageFormat.rgba_u8) -> np.ndarray:
+    """A copy of image (uint8 [h, w, 4] in `format`: rgba / bgra / argb) with its alpha channel set from alpha (uint8 [h, w]). Host code."""
+    return _image_op("visp_image_set_alpha", [_view_of(image, format), _view_of(alpha, ImageFormat.alpha_u8)])
+
+
+def image_to_mask(image: np.ndarray, format: ImageFormat = ImageFormat.rgba_u8) -> np.ndarray:
+    """The first channel of a uint8 image as a mask uint8 [h, w]. Host code."""
+    return _image_op("visp_image_to_mask", [_view_of(image, format)])
+
+
+def estimate_foreground_batch_device(img_dev: int, img_format: ImageFormat, mask_dev: int, batch: int, w: int, h: int, out_dev: int,
+                                     out_format: ImageFormat = ImageFormat.rgba_u8, radius: int = 30, device: Device | None = None, stream: int | None = None):
+    """The estimator on device-resident batches: img [batch, h, w] pixels of rgba_f32 / rgb_u8 / rgba_u8, mask f32 [batch, h, w] -> out [batch, h, w, 4]."""
+    check(lib.get_lib().visp_image_estimate_foreground_batch_device(device._handle if device is not None else None, img_dev, img_format.value, mask_dev, batch, w, h,
+                                                                    int(radius), out_dev, out_format.value, stream))
 
 
 def esrgan_tile_layout(w: int, h: int, scale: int = 1) -> dict:
