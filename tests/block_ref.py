@@ -171,17 +171,21 @@ def f16_deviation(v, e):
     return r, np.maximum(f16(v + e) - r, r - f16(v - e))
 
 
-def layer_norm(x, e_x, g, b, eps):
-    """-> (LN(x) float64, the allowance of the device's f32 value before any rounding to f16)"""
+def layer_norm(x, e_x, g, b, eps, width=D, rsq_rel=RSQ_REL, info=None):
+    """-> (LN(x) float64, the allowance of the device's f32 value before any rounding to f16). `width`: the number of terms of the two row sums
+    (the row kernels of tests/rows_ref.py pass their own C); `rsq_rel`: the relative error of the reciprocal root as the kernel forms it;
+    `info`, a dict, receives t (per row) for callers that have to hold it inside the range the rstd bound is valid on."""
     mean = x.mean(axis=1, keepdims=True)
     d = x - mean
     var = (d * d).mean(axis=1, keepdims=True)
     a = g / np.sqrt(var + eps)
-    e_mean = (D + 8) * U32 * np.abs(x).mean(axis=1, keepdims=True) + e_x.mean(axis=1, keepdims=True)
+    e_mean = (width + 8) * U32 * np.abs(x).mean(axis=1, keepdims=True) + e_x.mean(axis=1, keepdims=True)
     e_d = e_x + e_mean
-    e_var = (D + 8) * U32 * var + 2 * (np.abs(d) * e_d).mean(axis=1, keepdims=True) + (e_d * e_d).mean(axis=1, keepdims=True)
+    e_var = (width + 8) * U32 * var + 2 * (np.abs(d) * e_d).mean(axis=1, keepdims=True) + (e_d * e_d).mean(axis=1, keepdims=True)
     t = e_var / (var + eps)
-    rel = RSQ_REL + t / 2 + t * t
+    if info is not None:
+        info["t"] = t
+    rel = rsq_rel + t / 2 + t * t
     allow = np.abs(a) * e_d + np.abs(d * a) * rel + 4 * U32 * (np.abs(x * a) + np.abs(mean * a) + np.abs(b))
     return d * a + b, allow
 

@@ -240,6 +240,7 @@ __global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict_
 extern "C" {
 
 int vx_layernorm_f32_f16(const float* x, const float* w, const float* b, void* y, int M, int C, float eps, void* stream) {
+    VX_REQUIRE(x && w && b && y, "vx_layernorm_f32_f16: null operand");
     VX_REQUIRE(M > 0 && C > 0, "vx_layernorm: empty problem");
     dim3 grid((M + 3) / 4), block(256);
     hipStream_t s = as_stream(stream);

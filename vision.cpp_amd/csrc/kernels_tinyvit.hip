@@ -435,7 +435,7 @@ int vx_tv_preprocess(const uint8_t* rgb, void* out, int64_t n_pixels, void* stre
 
 int vx_dwconv3x3_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int stride, int gelu, void* stream) {
     VX_REQUIRE(x && w && bias && y && B > 0 && H > 0 && W > 0, "vx_dwconv3x3_f16: bad operands");
-    VX_REQUIRE(C % 8 == 0 && (stride == 1 || stride == 2), "vx_dwconv3x3_f16: C %% 8 == 0 and stride 1 or 2 only (C = %d, stride = %d)", C, stride);
+    VX_REQUIRE(C > 0 && C % 8 == 0 && (stride == 1 || stride == 2), "vx_dwconv3x3_f16: C > 0, C %% 8 == 0 and stride 1 or 2 only (C = %d, stride = %d)", C, stride);
     const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
     const f16* xp = reinterpret_cast<const f16*>(x);
     const f16* wp = reinterpret_cast<const f16*>(w);
@@ -470,7 +470,7 @@ int vx_layernorm_f16(const void* x, const float* w, const float* b, void* y, int
 }
 
 int vx_window_reverse_add_f16(const void* a, const void* x, void* y, int B, int res, int ws, int C, void* stream) {
-    VX_REQUIRE(a && x && y && B > 0 && res > 0 && ws > 0 && C % 8 == 0, "vx_window_reverse_add_f16: bad operands");
+    VX_REQUIRE(a && x && y && B > 0 && res > 0 && ws > 0 && C > 0 && C % 8 == 0, "vx_window_reverse_add_f16: bad operands");
     const long n = (long)B * res * res * (C / 8);
     hipLaunchKernelGGL(tv_window_reverse_add_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), reinterpret_cast<const f16*>(a),
                        reinterpret_cast<const f16*>(x), reinterpret_cast<f16*>(y), B, res, ws, (res + ws - 1) / ws, C);
