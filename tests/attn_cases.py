@@ -3,7 +3,8 @@ smallest shape that reaches each code path. `materialize(case)` turns a case int
 head, window) has its own random data from default_rng(seed), rounded to f16. q and k have a standard deviation of 1; keys have one length and
 query i leans on key i (correlation 0.9) as the two projections of one token do, so whatever T is, every key carries visible weight for some
 query (the sensitivity condition of the CPU file: with independent q and k no scale reached it at T = 1370, the allowance's exponential term
-being 4e-3 of the largest output). No case holds a query that is masked on every key."""
+being 4e-3 of the largest output). No case holds a query that is masked on every key. The `cross` group has fewer queries than keys in places:
+_cross says who owns which key there."""
 from __future__ import annotations
 
 import itertools
@@ -228,9 +229,141 @@ def _small(c):
                 Nq=Nq, Nk=Nk, heads=c["heads"], hd=c["hd"])
 
 
-GROUPS = {"attention": ATTENTION, "masked": MASKED, "window": WINDOW, "shifted": SHIFTED, "small": SMALL}
+# ---- vx_attention_cross_f16 / vx_attention_cross_step_f16 --------------------------------------------------------------------------------------
+CROSS_HD = (16, 32, 64)
+CROSS_TQ = (1, 31, 32, 33, 64, 65, 96, 97, 128, 129, 257)     # NW 1, 2 and 4, the idle fourth wave (65 .. 96), several blocks, a last block with one live wave
+CROSS_TK = (1, 2, 31, 32, 33, 63, 64, 65, 100, 255)           # one part each
+CROSS_LONG = [(33, 256), (33, 300), (65, 256), (65, 300)]     # many keys, too many queries to split
+CROSS_SPLIT_TQ = (1, 7, 31, 32)
+CROSS_SPLIT_TK = (256, 257, 300, 383, 384, 385)               # 2, 3 and 4 parts; a last part of one key (257, 385), a full one (256, 384)
+CROSS_FEW = [(300, 1), (513, 7), (300, 32), (513, 1), (300, 7), (513, 32)]   # few keys, many queries: (Tq, Tk), rotated over the head dims
+
+
+def cross_waves(Tq):
+    """launch_cross's rule: a wave per 32 queries up to two, four from three query blocks on"""
+    qb = -(-Tq // 32)
+    return 4 if qb >= 3 else qb
+
+
+def cross_parts(Tq, Tk):
+    """cx_parts: at most 32 queries and at least 256 keys cut the keys into parts of 128"""
+    return -(-Tk // 128) if Tq <= 32 and Tk >= 256 else 1
+
+
+def cross_partial_bytes(B, H, Tq, Tk, hd):
+    """vx_attention_cross_partial_bytes: [B * H][parts][32][hd + 2] floats, nothing for one part"""
+    parts = cross_parts(Tq, Tk)
+    return B * H * parts * 32 * (hd + 2) * 4 if parts > 1 else 0
+
+
+def cross_idle_form(Tq):
+    """how a block of four waves comes to hold a wave without queries: 'short' (65 .. 96 queries: the fourth wave of the only block), 'last' (the last of
+    several blocks has fewer than 97 queries), None"""
+    if cross_waves(Tq) != 4 or (Tq - 1) % 128 >= 96:
+        return None
+    return "short" if Tq <= 128 else "last"
+
+
+def cross_edge_keys(Tq, Tk):
+    """where a defect of the key loop can sit: the first and last key of every 32-key block, of every 128-key part of a split, and key Tk - 1"""
+    edge = {Tk - 1}
+    for step in (32,) + ((128,) if cross_parts(Tq, Tk) > 1 else ()):
+        for k0 in range(0, Tk, step):
+            edge |= {k0, min(k0 + step, Tk) - 1}
+    return sorted(edge)
+
+
+def _cross_cases():
+    out = []
+
+    def add(hd, Tq, Tk, data="random", mul=1.0, min_bh=1):
+        n = len(out)
+        B = 1 + n % 3
+        H = 2 + n % 2
+        if Tq < Tk and data in ("random", "low", "vmax"):   # enough queries over the (b, h) problems to own every edge key once: see _cross
+            min_bh = max(min_bh, -(-len(cross_edge_keys(Tq, Tk)) // Tq))
+        H = max(H, -(-min_bh // B))
+        scale = {0.0: "-s0", 1.0: ""}.get(mul, f"-sx{mul}")
+        out.append(dict(id=f"hd{hd}-Tq{Tq}-Tk{Tk}-B{B}-H{H}{scale}{'' if data == 'random' else '-' + data}", entry="cross", hd=hd, Tq=Tq, Tk=Tk, B=B, H=H,
+                        mul=mul, data=data, seed=100000 * hd + 300 * Tq + Tk))
+
+    for hi, hd in enumerate(CROSS_HD):
+        for i, Tq in enumerate(CROSS_TQ):   # a rotation, not the product: every Tq and every Tk at every head_dim
+            add(hd, Tq, CROSS_TK[(i + 3 * hi) % len(CROSS_TK)])
+        for Tq, Tk in CROSS_LONG:
+            add(hd, Tq, Tk)
+        for j, Tk in enumerate(CROSS_SPLIT_TK):
+            add(hd, CROSS_SPLIT_TQ[(j + hi) % len(CROSS_SPLIT_TQ)], Tk, min_bh=4 if j == 2 else 1)
+    for i, (Tq, Tk) in enumerate(CROSS_FEW):
+        add(CROSS_HD[i % 3], Tq, Tk)
+    # scale 0: every P is 1, the output is the mean of v
+    for hd, Tq, Tk in [(16, 97, 31), (32, 33, 33), (64, 129, 2), (32, 1, 7)]:
+        add(hd, Tq, Tk, mul=0.0)
+    # another positive scale per head_dim, one of them split
+    for hd, Tq, Tk, mul in [(16, 65, 64, 1.7), (32, 7, 300, 0.6), (64, 128, 100, 1.7)]:
+        add(hd, Tq, Tk, mul=mul)
+    # the data kinds of _attention, each with one part and split
+    for hd, Tq, Tk, data in [(32, 100, 100, "spike"), (16, 65, 255, "ramp"), (64, 33, 100, "low"), (32, 97, 65, "vmax"),
+                             (16, 7, 300, "spike"), (64, 31, 385, "ramp"), (32, 7, 257, "low"), (16, 32, 384, "vmax"), (32, 7, 300, "cliff")]:
+        add(hd, Tq, Tk, data=data)
+    return out
+
+
+CROSS = _cross_cases()
+_PB = cross_partial_bytes(1, 2, 7, 300, 16)
+_NOTHING, _ALIGN, _SPLIT = "empty problem", "q, k, v must be 16-byte aligned, out 8-byte aligned", "7 queries on 300 keys split the keys into 3 parts and need"
+# against a valid base call (tests/test_gpu_attn_matrix.py); "ptr+n": the scratch buffer's address plus n bytes; step None: vx_attention_cross_f16
+CROSS_REFUSALS = [
+    (dict(head_dim=48), "head_dim 48 (16, 32 and 64 are built)"),
+    (dict(q=0), _NOTHING), (dict(k=0), _NOTHING), (dict(v=0), _NOTHING), (dict(out=0), _NOTHING),
+    (dict(B=0), _NOTHING), (dict(H=0), _NOTHING), (dict(Tq=0), _NOTHING), (dict(Tk=0), _NOTHING),
+    (dict(q="ptr+8"), _ALIGN), (dict(k="ptr+8"), _ALIGN), (dict(v="ptr+8"), _ALIGN), (dict(out="ptr+4"), _ALIGN),
+    (dict(Tk=300, partial=0), f"{_SPLIT} {_PB} bytes of partial results (vx_attention_cross_partial_bytes), got 0"),
+    (dict(Tk=300, partial_bytes=_PB - 1), f"{_SPLIT} {_PB} bytes of partial results (vx_attention_cross_partial_bytes), got {_PB - 1}"),
+    (dict(Tk=300, partial="ptr+2"), _SPLIT),
+    (dict(B=1 << 16, H=1 << 15, Tq=1, Tk=1), "too many blocks"),
+    (dict(step=0), "vx_attention_cross_step_f16: step 0"), (dict(step=3), "vx_attention_cross_step_f16: step 3"),
+]
+
+
+def _cross(c):
+    """Random data as _qk makes it: keys of one length, a query that leans on "its" key. With Tq >= Tk query i owns key i mod Tk. With fewer queries than
+    keys the queries of the successive (b, h) problems own successive keys of cross_edge_keys: a defect at a key position is the same in every (b, h), so
+    it is enough that every edge key is owned in one of them (the case's H is chosen so that B * H * Tq reaches the edge set)."""
+    rng = np.random.default_rng(c["seed"])
+    B, H, Tq, Tk, hd = c["B"], c["H"], c["Tq"], c["Tk"], c["hd"]
+    scale = np.float32(c["mul"] / np.sqrt(hd))
+    k = rng.standard_normal((B, H, Tk, hd)).astype(np.float32)
+    k /= np.sqrt((k ** 2).mean(-1, keepdims=True))
+    if Tq >= Tk:
+        own = np.broadcast_to(np.arange(Tq) % Tk, (B, H, Tq))
+    else:
+        edge = np.array(cross_edge_keys(Tq, Tk))
+        own = edge[np.arange(B * H * Tq) % len(edge)].reshape(B, H, Tq)
+    q = QK_RHO * np.take_along_axis(k, own[..., None], axis=2) + np.sqrt(1.0 - QK_RHO ** 2) * rng.standard_normal((B, H, Tq, hd)).astype(np.float32)
+    q, k = _h(q * QK_STD).astype(np.float32), _h(k * QK_STD).astype(np.float32)
+    v = rng.standard_normal((B, H, Tk, hd)).astype(np.float32)
+    if c["data"] in ("spike", "cliff"):
+        # a key of a late 32-key block and one of the last block (in a split: of the last part) beat everything before them for their query: natural-log score
+        # 12 (the running maximum jumps by 17 in the exp2 domain, the earlier parts' weights are 2^-17), or for "cliff" 112: every earlier P and part weight is 0
+        peak = 12.0 if c["data"] == "spike" else 112.0
+        for key in (2 * Tk // 3, Tk - 10):
+            qo = q[0, 0, key % Tq]
+            k[0, 0, key] = qo * (peak / float((qo ** 2).sum() * scale))
+    elif c["data"] == "ramp":   # +3 per 32-key block in the exp2 domain through feature 0, for a rising, a flat and a falling query
+        q[..., 0] = np.array([8.0, 0.0, -8.0, 0.0], np.float32)[np.arange(Tq) % 4]
+        k[..., 0] = (np.arange(Tk, dtype=np.float32) / 32.0 * 3.0 / LOG2E) / (8.0 * scale)
+    elif c["data"] == "low":    # scale * q . k near -28 -> -40.4 in the exp2 domain
+        q[..., 0], k[..., 0] = 16.0, -28.0 / (16.0 * scale)
+    elif c["data"] == "vmax":
+        v = np.where(rng.random(v.shape) < 0.5, np.float32(65504.0), np.float32(-65504.0))
+    tok = lambda x: np.ascontiguousarray(_h(x).transpose(0, 2, 1, 3))  # noqa: E731  [B, T, H, hd]: token-major rows, as the launcher takes them
+    return dict(entry="cross", q=tok(q), k=tok(k), v=tok(v), B=B, H=H, Tq=Tq, Tk=Tk, head_dim=hd, scale=float(scale))
+
+
+GROUPS = {"attention": ATTENTION, "masked": MASKED, "window": WINDOW, "shifted": SHIFTED, "small": SMALL, "cross": CROSS}
 ALL = [c for g in GROUPS.values() for c in g]
-_MAKE = {"attention": _attention, "masked": _masked, "window": _window, "small": _small}
+_MAKE = {"attention": _attention, "masked": _masked, "window": _window, "small": _small, "cross": _cross}
 
 
 def group(name):

@@ -1,4 +1,4 @@
-"""float64 references of the four attention entry points and a derived per-element error allowance. Plain numpy, nothing from the device side.
+"""float64 references of the five attention entry points and a derived per-element error allowance. Plain numpy, nothing from the device side.
 
 One `evaluate_*(args, guard_rows)` per entry point. `args` holds the launcher's own arguments, pointers replaced by numpy arrays that hold the
 WHOLE buffer behind the pointer, with the f16 values the kernel reads:
@@ -7,12 +7,14 @@ WHOLE buffer behind the pointer, with the f16 values the kernel reads:
   vx_window_attention_*     qkv f16 [n_windows * N, heads, 3, 32]; bias [heads, N, N]: the f16 values of the table, -inf allowed; mask None or
                             [nwx * nwy, N, N] of 0 / -inf: the class masks, window w of the call reads mask[w % (nwx * nwy)];  n_windows, N, heads, nwx, nwy
   vx_small_attention_f16    q f16 [Nq, heads * hd], k, v f16 [Nk, heads * hd];  Nq, Nk, heads, hd
+  vx_attention_cross_f16    q f16 [B, Tq, H, head_dim], k, v f16 [B, Tk, H, head_dim], token-major, q NOT pre-scaled;  B, H, Tq, Tk, head_dim, scale (the f32
+                            the launcher is given). Problem (b, h) owns rows b * Tq .. and columns h * head_dim .. of the [B * Tq + guard, H * head_dim] buffer.
 Each returns `want, allow, written` for the whole row-major output buffer [rows + guard_rows, heads * head_dim] as the call leaves a
 zero-initialised buffer. The guard rows sit behind the last row the call owns; `allow` is 0 wherever the call must not write, so the one
 comparison |got - want| <= allow also finds stray stores. A query whose mask is -inf on every key is unspecified by contract: `evaluate` refuses it.
 
-All four are softmax2(s) v with s, in the exp2 domain, = a * (q . k) + b * add  (a, b = 1, 0 | 1, log2e | log2e / sqrt(32), log2e | log2e / sqrt(hd), 0;
-add = the mask, or bias + class mask). p = the softmax weights of a query, l their sum before the division, A_d = sum_j p_j |v_jd|, out_d = sum_j p_j v_jd,
+All five are softmax2(s) v with s, in the exp2 domain, = a * (q . k) + b * add  (a, b = 1, 0 | 1, log2e | log2e / sqrt(32), log2e | log2e / sqrt(hd), 0 |
+scale * log2e, 0; add = the mask, or bias + class mask). p = the softmax weights of a query, l their sum before the division, A_d = sum_j p_j |v_jd|, out_d = sum_j p_j v_jd,
 u16 = 2^-11, u32 = 2^-24. The allowance of out_d is the sum of:
   scores        an f32 MFMA (or fma chain) sum of hd exact f16 x f16 products is within (hd - 1) u32 of the exact sum times sum_d |q_d| |k_d| in ANY
                 order; the scale, the mask / bias fma, the constant log2e and the subtraction of the reference point m round a few more times, each
@@ -35,7 +37,26 @@ u16 = 2^-11, u32 = 2^-24. The allowance of out_d is the sum of:
                 (1 + u16)^4 - 1, so 4 u16 |out_d| (plus second order, paid by the spare units of the next term).
   accumulation  O and l are f32 sums of T terms in n_tiles groups, each group followed by at most one rescale:  (T + n_tiles + 8) u32 A_d for O and the same
                 times |out_d| <= A_d for l:  2 (T + n_tiles + 8) u32 A_d. vx_small_attention_f16 sums in a fixed order with n_tiles = 0; any-order bounds hold.
-  output        max(u16 |out_d|, 2^-25) for the one rounding to f16; o * (1 / l) rounds twice in f32 (in the 8 spare units)."""
+  output        max(u16 |out_d|, 2^-25) for the one rounding to f16; o * (1 / l) rounds twice in f32 (in the 8 spare units).
+
+vx_attention_cross_f16 is the masked kernel's arithmetic (tile = 32, P in f16 and its subnormal term, the unrounded p summed into l: 2 u16 A_d and T_k 2^-25
+max|v_d|, accumulation with n_tiles = ceil(T_k / 32)) with these differences, none of them fitted to what the device returns:
+  scores        the kernel multiplies the f32 MFMA sum by the f32 qs = fl(fl(scale) fl(log2e)). Where the masked kernel has one fma (mask * log2e + acc) there
+                are three roundings relative to |s| here (the constant log2e, the product that makes qs, the product acc * qs) and the subtraction of the
+                reference point: one more than the four the header counts, so 5 u32 (|s| + |m|) in ds.
+  key split     (T_q <= 32 and T_k >= 256: parts of 128 keys) block (bh, part i) leaves its unrounded f32 triple (m_i, l_i, O_i), the masked kernel's sums over
+                its own <= 128 keys with m_i the part's largest score as the reference point: the terms above hold per part, and a sum over the parts of
+                per-part bounds is at most the bound over all T_k keys (the subnormal term: a P of part i is off by 2^-25 in the units of a running maximum
+                <= m_i <= m, and the rescales that follow only shrink it; in the units of m the key that holds m has P = 1, so l >= 1 up to rounding as before).
+                The combine takes m = max m_i exactly and then, per part in part order,
+                  w_i = exp2(m_i - m)   one subtraction, rounded relative to |m_i| + |m|: every p of part i is scaled by 2^(u32 (|m_i| + |m|)), which is a
+                                        score error of that size on the keys of the part. m_i is the score of a key of the part; a part all of whose keys
+                                        are dead (s - m <= -150) has w_i = 0 in f32 either way. One more unit: 6 u32 (|s| + |m|) in ds for a split. The
+                                        accuracy of the exp2 itself is what the F16_TOL term stands for, as it is for every p.
+                  l   = fma(l_i, w_i, l)     a chain of `parts` fma over positive terms: relative error at most parts u32 of the sum
+                  acc = fma(O_id, w_i, acc)  the same chain over terms of either sign: at most parts u32 sum_i |O_id| w_i <= parts u32 l A_d
+                so the division moves by parts u32 A_d through acc and parts u32 |out_d| <= parts u32 A_d through l:  2 parts u32 A_d on top of the
+                accumulation term; acc * (1 / l) rounds twice in f32, in the 8 spare units as before."""
 from __future__ import annotations
 
 import numpy as np
@@ -81,7 +102,8 @@ def solve(p):
     with np.errstate(invalid="ignore"):
         if p["add"] is not None:
             mag = mag + p["b"] * np.abs(np.where(live, p["add"], 0.0))
-        ds = np.where(live, (hd + 8) * U32 * mag + 4 * U32 * (np.abs(np.where(live, s, 0.0)) + np.abs(m)), 0.0)
+        n_round = 4 if p["kind"] != "cross" else (5 if p["parts"] == 1 else 6)   # the docstring: the cross kernel's qs product and its combine
+        ds = np.where(live, (hd + 8) * U32 * mag + n_round * U32 * (np.abs(np.where(live, s, 0.0)) + np.abs(m)), 0.0)
         # a key below the cut stays below it: its score error is far smaller than its distance to the cut
         dead_err = np.where(live, 0.0, (hd + 8) * U32 * np.abs(np.where(np.isfinite(s), s, 0.0)))
         assert (np.where(live, -np.inf, s - m + dead_err) < DEAD + 20).all()
@@ -92,6 +114,8 @@ def solve(p):
         allow = allow + 2 * U16 * A + Tk * TINY16 * np.abs(v).max(0)
     if p["kind"] == "dense":
         allow = allow + 4 * U16 * np.abs(out)
+    if p["kind"] == "cross" and p["parts"] > 1:   # the combine's two fma chains
+        allow = allow + 2 * p["parts"] * U32 * A
     return out, allow, w
 
 
@@ -153,7 +177,22 @@ def problems_small(a):
                    rows=slice(0, Nq), cols=c, b_idx=0, h_idx=h)
 
 
-PROBLEMS = {"attention": problems_attention, "masked": problems_masked, "window": problems_window, "small": problems_small}
+def cross_parts(Tq, Tk):
+    """the launcher's rule, restated: at most one query block and at least 256 keys split the keys into parts of 128"""
+    return -(-Tk // 128) if Tq <= 32 and Tk >= 256 else 1
+
+
+def problems_cross(a):
+    B, H, Tq, Tk, hd = a["B"], a["H"], a["Tq"], a["Tk"], a["head_dim"]
+    assert a["q"].shape == (B, Tq, H, hd) and a["k"].shape == a["v"].shape == (B, Tk, H, hd)
+    scale = np.float32(a["scale"])
+    for b in range(B):
+        for h in range(H):
+            yield dict(kind="cross", tile=32, a=float(scale) * LOG2E, b=0.0, add=None, q=f64(a["q"][b, :, h]), k=f64(a["k"][b, :, h]), v=f64(a["v"][b, :, h]),
+                       parts=cross_parts(Tq, Tk), qs=scale * np.float32(LOG2E), rows=slice(b * Tq, (b + 1) * Tq), cols=slice(h * hd, (h + 1) * hd), b_idx=b, h_idx=h)
+
+
+PROBLEMS = {"attention": problems_attention, "masked": problems_masked, "window": problems_window, "small": problems_small, "cross": problems_cross}
 
 
 def out_shape(entry, a):
@@ -164,6 +203,8 @@ def out_shape(entry, a):
         return a["B"] * a["T"], a["H"] * a["head_dim"]
     if entry == "window":
         return a["n_windows"] * a["N"], a["heads"] * 32
+    if entry == "cross":
+        return a["B"] * a["Tq"], a["H"] * a["head_dim"]
     return a["Nq"], a["heads"] * a["hd"]
 
 
@@ -187,3 +228,7 @@ def evaluate_window(a, guard_rows=0):
 
 def evaluate_small(a, guard_rows=0):
     return evaluate("small", a, guard_rows)
+
+
+def evaluate_cross(a, guard_rows=0):
+    return evaluate("cross", a, guard_rows)

@@ -1,4 +1,4 @@
-"""No device: the float64 references of the attention kernels (tests/attn_ref.py) are pinned to the CPU oracle and to graph_window_ref, numpy
+"""No device: the float64 references of the attention kernels (tests/attn_ref.py) are pinned to the CPU oracle, graph_window_ref and cross_attn_ref, numpy
 emulations of each kernel's arithmetic (f16 P, the packed-f16 add tree, f32 sums, the lagging reference point) lie inside the allowance on every
 case of tests/attn_cases.py, seeded corruptions of those emulations lie outside, every key of every case is visible through the allowance, the
 case table reaches what the launchers can select, and the two host packers lay the bias out in accumulator order."""
@@ -9,6 +9,7 @@ import pytest
 
 import attn_cases as T
 import attn_ref as R
+import cross_attn_ref as XR
 import graph_window_ref as GW
 from oracle import oracle as O
 from visioncpp_amd import _lib as L
@@ -60,6 +61,17 @@ def test_window_reference_matches_graph_window_ref(case_id):
     assert np.abs(ref.reshape(want.shape) - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
 
 
+@pytest.mark.parametrize("case", T.group("cross"), ids=_ids(T.group("cross")))
+def test_cross_reference_matches_the_independent_statement(case):
+    """cross_attn_ref.attention: natural exponent, einsum over all heads at once; evaluate_cross: exp2, per (b, h) problem. Both float64."""
+    a, (want, allow, written) = _made(case["id"])
+    ref = XR.attention(a["q"], a["k"], a["v"], float(np.float32(a["scale"]))).reshape(want.shape)
+    # the scores differ by a few float64 roundings of a value of at most max|s| (natural log), which moves a weight by that relative amount
+    smax = abs(a["scale"]) * np.einsum("bqhd,bkhd->bhqk", np.abs(a["q"].astype(np.float64)), np.abs(a["k"].astype(np.float64))).max()
+    assert np.abs(ref - want).max() <= 2.0 ** -52 * (16 + 8 * smax + a["Tk"]) * np.abs(a["v"].astype(np.float64)).max()
+    assert written.all() and (allow > 0).all()
+
+
 def test_small_reference_matches_the_cpu_oracle():
     rng = np.random.default_rng(1)
     for hd, heads in ((4, 3), (32, 1)):
@@ -95,8 +107,67 @@ def _exp2(x):
         return np.exp2(f32(x)).astype(np.float32)
 
 
+def _fma(a, b, c):
+    """f32 fma: the product of two f32 is exact in float64, the sum rounds once there and once to f32"""
+    return f32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+def _emulate_cross(p, corrupt):
+    """attention_cross_kernel and attention_cross_combine_kernel: f32 scores times the f32 qs, tail keys -inf, 32-key tiles, running maximum with floor
+    -1e30, unrounded p into l, f16 P into the PV product, queries beyond T_q on the clamped row; a split leaves (m, l, O) per 128-key part and the
+    combine folds them as written: m = max m_i, l and acc as fma chains in part order, acc * (1 / l)."""
+    q, k, v = f32(p["q"]), f32(p["k"]), f32(p["v"])
+    Tq, Tk, parts = q.shape[0], k.shape[0], p["parts"]
+    qs = f32(p["qs"] / LOG2E) if corrupt == "scale_log2e" else p["qs"]
+    s = f32(f32(q @ k.T) * qs)
+    if corrupt == "drop_key":
+        s[:, Tk // 2] = -np.inf
+    if corrupt == "double_key":
+        s[:, Tk // 2] += 1.0
+    s = np.concatenate([s, np.repeat(s[-1:], -Tq % 32, 0)])
+    n = s.shape[0]
+    gain = np.float32(1.02 if corrupt == "p_bias" else 1.0)
+    triples = []
+    for part in range(parts):
+        k0, k1 = (part * 128, min(Tk, part * 128 + 128)) if parts > 1 else (0, Tk)
+        sp, vp = s[:, k0:k1], v[k0:k1]
+        pad, fill = -(k1 - k0) % 32, -np.inf
+        if part == parts - 1 and corrupt == "tail_unmasked":
+            fill = 0.0
+        if part == parts - 1 and corrupt == "part_tail":   # the part runs to k_begin + 128: its zero-staged keys score 0
+            pad, fill = k0 + 128 - k1, 0.0
+        sp, vp = np.pad(sp, ((0, 0), (0, pad)), constant_values=fill), np.pad(vp, ((0, pad), (0, 0)))
+        o, l, m = np.zeros((n, vp.shape[1]), np.float32), np.zeros(n, np.float32), np.full(n, -1e30, np.float32)
+        for t in range(sp.shape[1] // 32):
+            st, vt = sp[:, t * 32:(t + 1) * 32], vp[t * 32:(t + 1) * 32]
+            m_new = np.maximum(m, st.max(1))
+            alpha = _exp2(m - m_new)
+            l, o, m = f32(l * alpha), f32(o * alpha[:, None]), m_new
+            pr = _exp2(st - m[:, None])
+            l = f32(l + pr.sum(1, dtype=np.float32))
+            o = f32(o + f32(r16(pr) * gain) @ vt)
+        triples.append((m, l, o))
+    if parts == 1:
+        m, l, o = triples[0]
+        return r16(o * f32(1.0 / l)[:, None])[:Tq].astype(np.float64)
+    used = triples[:-1] if corrupt == "drop_part" else triples
+    m = np.full(n, -1e30, np.float32)
+    for mi, _, _ in used:
+        m = np.maximum(m, mi)
+    if corrupt == "stale_max":
+        m = triples[0][0]
+    l, acc = np.zeros(n, np.float32), np.zeros((n, v.shape[1]), np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for mi, li, oi in used:
+            w = _exp2(mi - m)
+            l, acc = _fma(li, w, l), _fma(oi, w[:, None], acc)
+        return r16(acc * f32(1.0 / l)[:, None])[:Tq].astype(np.float64)
+
+
 def emulate(p, corrupt=None, limit=1024.0):
     """One problem of attn_ref.PROBLEMS on the kernel's own arithmetic -> the f16 output [Tq, hd] as float64. `corrupt` plants one defect."""
+    if p["kind"] == "cross":
+        return _emulate_cross(p, corrupt)
     q, k, v = f32(p["q"]), f32(p["k"]), f32(p["v"])
     Tq, Tk, kind = q.shape[0], k.shape[0], p["kind"]
     add = None if p["add"] is None else f32(p["add"])
@@ -172,6 +243,8 @@ ARG_CORRUPTIONS = {   # defects that pick the wrong operand slice: applied to th
     "mask_head": lambda a: dict(a, mask=np.roll(a["mask"], -1, axis=1)) if a["entry"] == "masked" and a["Hm"] > 1 else None,
     "mask_batch": lambda a: dict(a, mask=np.roll(a["mask"], -1, axis=0)) if a["entry"] == "masked" and a["Bm"] > 1 else None,
     "wrong_class": lambda a: dict(a, mask=np.roll(a["mask"], -1, axis=0)) if a["entry"] == "window" and a["nwx"] * a["nwy"] > 1 else None,
+    "kv_head": lambda a: dict(a, k=np.roll(a["k"], -1, axis=2), v=np.roll(a["v"], -1, axis=2)) if a["entry"] == "cross" and a["H"] > 1 else None,
+    "kv_batch": lambda a: dict(a, k=np.roll(a["k"], -1, axis=0), v=np.roll(a["v"], -1, axis=0)) if a["entry"] == "cross" and a["B"] > 1 else None,
 }
 
 
@@ -209,21 +282,32 @@ def _pick(group, pred=lambda c: True, n=6):
 
 
 _multi_q = lambda c: c.get("T", c.get("N", 0)) > 64  # noqa: E731
+_split = lambda c: T.cross_parts(c["Tq"], c["Tk"]) > 1  # noqa: E731
 CORRUPTIONS = {
     "drop_key": dict(attention=_pick("attention", lambda c: c["T"] > 1), masked=_pick("masked", lambda c: c["T"] > 1), window=_pick("window", lambda c: c["N"] > 1),
-                     shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1 and c["Nq"] >= c["Nk"])),
+                     shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1 and c["Nq"] >= c["Nk"]),
+                     cross=_pick("cross", lambda c: c["Tk"] > 1 and c["Tq"] >= c["Tk"])),
     "double_key": dict(attention=_pick("attention", lambda c: c["T"] > 1), masked=_pick("masked", lambda c: c["T"] > 1), window=_pick("window", lambda c: c["N"] > 1),
-                       shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1 and c["Nq"] >= c["Nk"])),
+                       shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1 and c["Nq"] >= c["Nk"]),
+                       cross=_pick("cross", lambda c: c["Tk"] > 1 and c["Tq"] >= c["Tk"])),
     "tail_unmasked": dict(attention=_pick("attention", lambda c: c["T"] % 64), masked=_pick("masked", lambda c: c["T"] % 32), window=_pick("window", lambda c: c["N"] % 32),
-                          shifted=_pick("shifted", lambda c: c["N"] % 32)),
+                          shifted=_pick("shifted", lambda c: c["N"] % 32), cross=_pick("cross", lambda c: c["Tk"] % 32)),
     "neighbour_mask_row": dict(masked=_pick("masked", lambda c: c["T"] > 1), window=_pick("window", lambda c: c["N"] > 1), shifted=_pick("shifted")),
     "mask_head": dict(masked=_pick("masked", lambda c: c["Hm"] > 1)),
     "mask_batch": dict(masked=_pick("masked", lambda c: c["Bm"] > 1)),
     "wrong_class": dict(shifted=_pick("shifted", lambda c: c["nwx"] * c["nwy"] > 1)),
     "scale_log2e": dict(attention=_pick("attention", lambda c: c["T"] > 1), masked=_pick("masked", lambda c: c["T"] > 1), window=_pick("window", lambda c: c["N"] > 1),
-                        shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1)),
-    "p_bias": dict(attention=_pick("attention"), masked=_pick("masked"), window=_pick("window"), shifted=_pick("shifted")),
-    "block_shift": dict(attention=_pick("attention", _multi_q), masked=_pick("masked", _multi_q), window=_pick("window", _multi_q), shifted=_pick("shifted", _multi_q)),
+                        shifted=_pick("shifted"), small=_pick("small", lambda c: c["Nk"] > 1), cross=_pick("cross", lambda c: c["Tk"] > 1)),
+    "p_bias": dict(attention=_pick("attention"), masked=_pick("masked"), window=_pick("window"), shifted=_pick("shifted"), cross=_pick("cross")),
+    "block_shift": dict(attention=_pick("attention", _multi_q), masked=_pick("masked", _multi_q), window=_pick("window", _multi_q), shifted=_pick("shifted", _multi_q),
+                        cross=_pick("cross", lambda c: c["Tq"] > 64)),
+    # the key split of vx_attention_cross_f16: the combine skips the last part; the last part runs to k_begin + 128 and its zero-staged keys score 0 instead
+    # of -inf; the combine takes part 0's maximum as the reference point (the same value as long as no weight overflows: the "cliff" data is what sees it)
+    "drop_part": dict(cross=_pick("cross", _split)),
+    "part_tail": dict(cross=_pick("cross", lambda c: _split(c) and c["Tk"] % 128)),
+    "stale_max": dict(cross=_pick("cross", lambda c: _split(c) and c["data"] in ("spike", "ramp", "cliff"))),
+    "kv_head": dict(cross=_pick("cross", lambda c: c["Tk"] > 1)),
+    "kv_batch": dict(cross=_pick("cross", lambda c: c["Tk"] > 1 and c["B"] > 1)),
 }
 PAIRS = [(name, fam) for name, fams in CORRUPTIONS.items() for fam in fams]
 
@@ -237,7 +321,7 @@ def test_seeded_corruption_leaves_the_allowance(name, family):
         a, (want, allow, _) = _made(case["id"])
         got = emulate_call(a, name)
         assert got is not None, case["id"]
-        if (np.abs(got - want) > allow).any():
+        if not (np.abs(got - want) <= allow).all():   # a NaN is outside too, as it is for the device comparison
             caught.append(case["id"])
     assert caught, f"{name} stays inside the allowance on every one of {_ids(cases)}"
 
@@ -251,16 +335,22 @@ WORST = {}
 def _sensitive(c):
     """Dropping key j changes row i by p_ij (v_j - out_i) / (1 - p_ij). For the three MFMA kernels every case takes part (a lone key cannot be dropped).
     vx_small_attention_f16 takes part where Nq >= Nk: a query has at most 1 / p keys of weight p, so with fewer queries than keys most keys weigh
-    less on every output than one f16 rounding of it, whatever the data."""
+    less on every output than one f16 rounding of it, whatever the data.
+    vx_attention_cross_f16 takes part with every key where Tq >= Tk. Where Tq < Tk the same counting holds, so the condition is asked of the keys of
+    attn_cases.cross_edge_keys only (the first and last key of every 32-key block and 128-key part, and the last key: where a defect of the key loop can
+    sit), each taken at the (b, h) problem that sees it best: the case's queries own those keys in turn over its problems, and a defect at a key position
+    is the same in every problem. The data kinds built to be peaked ("spike", "ramp", "cliff") hide most keys on purpose and are exempt."""
     if c["entry"] == "small":
         return c["Nk"] > 1 and c["Nq"] >= c["Nk"]
+    if c["entry"] == "cross":
+        return c["Tk"] > 1 and c["data"] not in ("spike", "ramp", "cliff")
     return c.get("T", c.get("N")) > 1
 
 
 @pytest.mark.parametrize("case", [c for c in T.ALL if _sensitive(c)], ids=_ids([c for c in T.ALL if _sensitive(c)]))
 def test_dropping_any_key_moves_some_output_by_four_allowances(case):
     a, (want, allow, _) = _made(case["id"])
-    worst = np.inf
+    worst, per_key = np.inf, None
     for p in R.PROBLEMS[a["entry"]](a):
         out, _, w = R.solve(p)
         al = allow[p["rows"], p["cols"]]
@@ -270,6 +360,10 @@ def test_dropping_any_key_moves_some_output_by_four_allowances(case):
         for d in range(out.shape[1]):
             ratio = np.maximum(ratio, (g * np.abs(p["v"][None, :, d] - out[:, d, None]) / al[:, d, None]).max(0))
         worst = min(worst, float(ratio.min()))
+        per_key = ratio if per_key is None else np.maximum(per_key, ratio)
+    if case["entry"] == "cross":   # per key position, the problem that sees it best; with fewer queries than keys the edge keys only: _sensitive
+        keys = slice(None) if case["Tq"] >= case["Tk"] else T.cross_edge_keys(case["Tq"], case["Tk"])
+        worst = float(per_key[keys].min())
     WORST[case["id"]] = worst
     print(f"smallest key-sensitivity ratio {worst:.2f}")
     assert worst >= SENSITIVITY, worst
@@ -309,6 +403,32 @@ def test_table_reaches_what_the_launchers_select():
     assert {T.window_qb(c["N"]) for c in T.WINDOW} == {1, 2, 4, 7, 8} == {T.window_qb(c["N"]) for c in T.SHIFTED}
     assert {c["N"] for c in T.WINDOW} == set(T.WINDOW_N) and {c["ws"] for c in T.SHIFTED} == set(T.SHIFT_WS)
     assert {(c["nwx"], c["nwy"]) for c in T.SHIFTED} == {(1, 1), (3, 1), (2, 3)} and {c["heads"] for c in T.WINDOW} == {1, 3} == {c["heads"] for c in T.SHIFTED}
+    # vx_attention_cross_f16: the nine (head_dim, waves) instances without a split, both idle-wave forms, the key-range edges, the parts of a split
+    one = [c for c in T.CROSS if T.cross_parts(c["Tq"], c["Tk"]) == 1]
+    split = [c for c in T.CROSS if T.cross_parts(c["Tq"], c["Tk"]) > 1]
+    assert {(c["hd"], T.cross_waves(c["Tq"])) for c in one} == {(hd, nw) for hd in T.CROSS_HD for nw in (1, 2, 4)}
+    assert [T.cross_waves(t) for t in (1, 32, 33, 64, 65, 96, 97, 129)] == [1, 1, 2, 2, 4, 4, 4, 4] and [T.cross_parts(*s) for s in ((32, 255), (32, 256), (33, 256), (1, 385))] == [1, 2, 1, 4]
+    assert [T.cross_idle_form(t) for t in (64, 65, 96, 97, 128, 129, 257)] == [None, "short", "short", None, None, "last", "last"]
+    for hd in T.CROSS_HD:
+        mine, mine_split = [c for c in one if c["hd"] == hd], [c for c in split if c["hd"] == hd]
+        assert {c["Tq"] for c in mine} >= set(T.CROSS_TQ) and {c["Tk"] for c in mine} >= set(T.CROSS_TK)
+        assert {T.cross_idle_form(c["Tq"]) for c in mine} >= {"short", "last"}
+        assert {c["Tk"] % 32 for c in mine} >= {0, 1, 31}
+        assert {(c["Tq"], c["Tk"]) for c in mine} >= set(T.CROSS_LONG)
+        assert {T.cross_parts(c["Tq"], c["Tk"]) for c in mine_split} == {2, 3, 4}
+        assert {c["Tk"] for c in mine_split} >= set(T.CROSS_SPLIT_TK) and {c["Tq"] for c in mine_split} >= set(T.CROSS_SPLIT_TQ)
+        assert any(c["Tk"] % 128 == 1 for c in mine_split) and any(c["Tk"] % 128 == 0 for c in mine_split)   # a last part of one key, a full last part
+        assert any(c["B"] * c["H"] >= 4 and c["B"] > 1 and c["H"] > 1 for c in mine_split)
+        assert any(c["mul"] not in (0.0, 1.0) for c in T.CROSS if c["hd"] == hd)
+    assert {(c["Tq"], c["Tk"]) for c in one} >= {(tq, tk) for tq in (300, 513) for tk in (1, 7, 32)}
+    assert all(c["H"] > 1 for c in T.CROSS) and {c["B"] for c in T.CROSS} == {1, 2, 3}
+    assert sum(c["mul"] == 0.0 for c in T.CROSS) >= 3
+    kinds = {"random", "spike", "ramp", "low", "vmax"}
+    assert {c["data"] for c in one} >= kinds and {c["data"] for c in split} >= kinds
+    for c in T.CROSS:   # with fewer queries than keys the queries of the case's problems reach every edge key: attn_cases._cross
+        if c["Tq"] < c["Tk"] and c["data"] in ("random", "low", "vmax"):
+            assert c["B"] * c["H"] * c["Tq"] >= len(T.cross_edge_keys(c["Tq"], c["Tk"])), c["id"]
+    assert T.cross_edge_keys(7, 257) == [0, 31, 32, 63, 64, 95, 96, 127, 128, 159, 160, 191, 192, 223, 224, 255, 256]
     # vx_small_attention_f16: both kernels, both sides of the dispatcher edge, every head_dim on each
     assert {(T.small_few_keys(c), c["hd"]) for c in T.SMALL} == {(f, hd) for f in (True, False) for hd in T.SMALL_HD}
     assert {(c["Nq"], c["Nk"]) for c in T.SMALL} >= set(T.SMALL_SHAPES) and {c["heads"] for c in T.SMALL} == {1, 3}

@@ -1,4 +1,4 @@
-"""-m gpu: the four attention entry points over their argument space (tests/attn_cases.py) against the float64 references and the derived
+"""-m gpu: the five attention entry points over their argument space (tests/attn_cases.py) against the float64 references and the derived
 per-element allowance of tests/attn_ref.py. Every output buffer starts zeroed and is compared in full, GUARD_ROWS zeroed rows behind the last row
 the call owns included (one full query block, so a store from any row of a tail block lands inside the buffer and is compared): an element the
 call must not write has allowance 0 and must still hold zero bits. Nothing here is built to fault; the refusals return before any launch."""
@@ -16,9 +16,10 @@ pytestmark = pytest.mark.gpu
 
 from gpu_util import api, dev, empty, release, sync  # noqa: E402
 
-GUARD_ROWS = 256  # the largest query block of the four kernels
+GUARD_ROWS = 256  # the largest query block of the five kernels
 RATIO = defaultdict(float)  # (entry point, case group) -> largest error / allowance seen; reported, not asserted
 WAVE_BITS = {"equal": 0, "compared": 0}
+SECONDS = defaultdict(float)  # case group -> wall time of its cases, references included
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -30,6 +31,7 @@ def _device():
     print(f"\n{len(T.ALL)} cases in {time.perf_counter() - t0:.1f} s; largest |got - want| / allowance per entry point and group:")
     for (entry, grp), ratio in sorted(RATIO.items()):
         print(f"  {entry:34s} {grp:10s} {ratio:.3f}")
+    print("wall time per group, float64 references included: " + ", ".join(f"{g} {t:.2f} s" for g, t in SECONDS.items()))
     print(f"vx_attention_f16, 4 waves against 8 waves: {WAVE_BITS['equal']} of {WAVE_BITS['compared']} outputs bit-identical")
 
 
@@ -89,9 +91,57 @@ def launch_small(a, want):
     return out.to_numpy(np.float16, want.shape)
 
 
-LAUNCH = {"attention": launch_attention, "masked": launch_masked, "window": launch_window, "small": launch_small}
+NAN16 = 0x7E00         # f16 quiet NaN: the 32 rows behind the last token of q, k and v, inside the allocation
+FILL32 = 0x7FC5A5A5    # f32 quiet NaN with a payload: what `partial` and its guard hold before a call
+PARTIAL_GUARD = 32 * 66 * 2   # floats behind `partial`: two whole part slots of the widest head
+
+
+def _nan_tail(x):
+    """[B, T, H, hd] f16 -> the rows [B * T + 32, H * hd] with 32 rows of NaN behind the last token: a tail key or a clamped query row that leaks is non-finite"""
+    rows = x.reshape(-1, x.shape[2] * x.shape[3]).view(np.uint16)
+    return np.concatenate([rows, np.full((32, rows.shape[1]), NAN16, np.uint16)])
+
+
+def launch_cross(a, want, step=None, state=None):
+    """One call of vx_attention_cross_f16 (step None) or vx_attention_cross_step_f16 on fresh buffers, or on those of `state` (a former call's).
+    -> out [rows + GUARD_ROWS, H * hd] f16, the state. `partial` and its guard are checked after every call that runs step 1."""
+    B, H, Tq, Tk, hd = a["B"], a["H"], a["Tq"], a["Tk"], a["head_dim"]
+    parts, need = api().vx_attention_cross_parts(Tq, Tk), api().vx_attention_cross_partial_bytes(B, H, Tq, Tk, hd)
+    assert parts == T.cross_parts(Tq, Tk) and need == T.cross_partial_bytes(B, H, Tq, Tk, hd)
+    if state is None:
+        state = dict(q=dev(_nan_tail(a["q"])), k=dev(_nan_tail(a["k"])), v=dev(_nan_tail(a["v"])), out=_out(want),
+                     partial=dev(np.full(need // 4 + PARTIAL_GUARD, FILL32, np.uint32)) if need else None)
+    part = state["partial"]
+    args = (state["q"].ptr, state["k"].ptr, state["v"].ptr, state["out"].ptr, part.ptr if part else None, need, B, H, Tq, Tk, hd, a["scale"], None)
+    L.vx_check(api().vx_attention_cross_f16(*args) if step is None else api().vx_attention_cross_step_f16(step, *args))
+    sync()
+    if part is not None:
+        bits = part.to_numpy(np.uint32, (need // 4 + PARTIAL_GUARD,))
+        assert (bits[need // 4:] == FILL32).all(), "stores behind vx_attention_cross_partial_bytes"
+        slots = bits[:need // 4].reshape(B * H, parts, 32, hd + 2)
+        assert np.isfinite(slots[:, :, :Tq].view(np.float32)).all(), "a (m, l, O) row of a live query is not finite, or was not written"
+        assert (slots[:, :, Tq:] == FILL32).all(), "a partial row at or beyond T_q was written"
+    return state["out"].to_numpy(np.float16, want.shape), state
+
+
+def check_cross(case, a, ref, key):
+    """The fused call twice (the same bits), then the two step calls the lowering makes for a split, against the fused call bit for bit."""
+    bits = lambda x: x.view(np.uint16)  # noqa: E731
+    got, _ = launch_cross(a, ref[0])
+    compare(got, ref, key, case["id"])
+    np.testing.assert_array_equal(bits(launch_cross(a, ref[0])[0]), bits(got))
+    if T.cross_parts(a["Tq"], a["Tk"]) > 1:
+        first, state = launch_cross(a, ref[0], step=1)
+        assert not bits(first).any(), "step 1 of a split wrote to out"
+        np.testing.assert_array_equal(bits(launch_cross(a, ref[0], step=2, state=state)[0]), bits(got))
+    else:
+        assert not bits(launch_cross(a, ref[0], step=2)[0]).any(), "step 2 of a single part wrote to out"
+        np.testing.assert_array_equal(bits(launch_cross(a, ref[0], step=1)[0]), bits(got))
+
+
+LAUNCH = {"cross": launch_cross, "attention": launch_attention, "masked": launch_masked, "window": launch_window, "small": launch_small}
 ENTRY = {"attention": "vx_attention_f16", "masked": "vx_attention_masked_f16", "window": "vx_window_attention_f16", "shifted": "vx_window_attention_masked_f16",
-         "small": "vx_small_attention_f16"}
+         "small": "vx_small_attention_f16", "cross": "vx_attention_cross_f16"}
 
 
 def compare(got, ref, key, what=""):
@@ -109,9 +159,19 @@ def compare(got, ref, key, what=""):
 
 
 def check(case, group):
+    t0 = time.perf_counter()
+    try:
+        _check(case, group)
+    finally:
+        SECONDS[group] += time.perf_counter() - t0
+
+
+def _check(case, group):
     a = T.materialize(case)
     ref = R.evaluate(a["entry"], a, GUARD_ROWS)
     key = (ENTRY[group], case.get("data") or case.get("content") or "random")
+    if a["entry"] == "cross":
+        return check_cross(case, a, ref, key)
     if a["entry"] != "attention":
         compare(LAUNCH[a["entry"]](a, ref[0]), ref, key, case["id"])
         return
@@ -156,15 +216,22 @@ def test_small_attention(case):
     check(case, "small")
 
 
+@pytest.mark.parametrize("case", T.group("cross"), ids=_ids(T.group("cross")))
+def test_attention_cross(case):
+    check(case, "cross")
+
+
 # ---- refusals: 0 and the message, before any launch ------------------------------------------------------------------------------------------
 
 def _refusals(table, base, call):
     scratch = empty(1 << 16)
     for fields, message in table:
         args = dict(base, **fields)
-        args = {k: (scratch.ptr if v == "ptr" else v) for k, v in args.items()}
+        args = {k: (scratch.ptr + int(v[3:] or 0) if isinstance(v, str) and v.startswith("ptr") else v) for k, v in args.items()}   # "ptr", "ptr+8"
         assert call(args) == 0, f"accepted: {fields}"
         assert message.encode() in api().vx_last_error(), (fields, api().vx_last_error())
+    sync()
+    assert not scratch.to_numpy(np.uint8, (1 << 16,)).any(), "a refused call wrote to an operand"
 
 
 def test_attention_refusals():
@@ -188,3 +255,13 @@ def test_window_attention_refusals():
 def test_small_attention_refusals():
     base = dict(q="ptr", k="ptr", v="ptr", out="ptr", Nq=4, Nk=16, heads=1, hd=8)
     _refusals(T.SMALL_REFUSALS, base, lambda a: api().vx_small_attention_f16(a["q"], a["k"], a["v"], a["out"], a["Nq"], a["Nk"], a["heads"], a["hd"], None))
+
+
+def test_attention_cross_refusals():
+    base = dict(step=None, q="ptr", k="ptr", v="ptr", out="ptr", partial="ptr", partial_bytes=1 << 15, B=1, H=2, Tq=7, Tk=7, head_dim=16, scale=0.25)
+
+    def call(a):
+        args = (a["q"], a["k"], a["v"], a["out"], a["partial"], a["partial_bytes"], a["B"], a["H"], a["Tq"], a["Tk"], a["head_dim"], a["scale"], None)
+        return api().vx_attention_cross_f16(*args) if a["step"] is None else api().vx_attention_cross_step_f16(a["step"], *args)
+
+    _refusals(T.CROSS_REFUSALS, base, call)
