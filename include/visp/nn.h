@@ -141,6 +141,9 @@ inline tensor cos(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_C
 inline tensor rope(model_ref const& m, tensor x, tensor pos, int n_dims, float freq_base, float freq_scale) {
     return detail::op(m, VISP_OP_ROPE, {x, pos}, {n_dims, 0}, {freq_base, freq_scale});
 }
+// image_to_patches (birefnet.cpp:153-162) as one op: the f32 image [C <= 4, W, H, N] (the graph input, or interpolate of it in bilinear | align_corners) ->
+// f16 [gw gh C, out_w, out_h, N] with gw = W / out_w, gh = H / out_h; channel gx + gw (gy + gh c) of pixel (py, px) is image (gy out_h + py, gx out_w + px, c)
+inline tensor image_patches(model_ref const& m, tensor image, int64_t out_w, int64_t out_h) { return detail::op(m, VISP_OP_IMAGE_PATCHES, {image}, {out_w, out_h}); }
 
 #ifdef VISP_GGML_NAMES
 // the two calls the reference's arch code makes without a context (dino.cpp:104-105): the tensor knows its graph

@@ -436,7 +436,12 @@ enum visp_graph_op {
      * freq_base, f1 freq_scale. For pair i in [0, n / 2): theta = pos[t] * freq_scale * freq_base^(-2 i / n); out[2i] = x[2i] cos - x[2i+1] sin, out[2i+1] =
      * x[2i] sin + x[2i+1] cos. The result has x's shape, f16. The angles never go through device transcendentals: the lowering makes a cos | sin table in double
      * from the constant positions, once per (positions, n_dims, base, scale). apply_rope_2d is two ROPE nodes on the two halves of a head. */
-    VISP_OP_ROPE = 42
+    VISP_OP_ROPE = 42,
+    /* the node of BiRefNet's decoder beyond the above: image_to_patches (birefnet.cpp:153-162) as ONE op, since the reference's reshape / permute chain lives in
+     * WHCN, which this layer keeps only as views. src an f32 image [C, W, H, N] with C <= 4 (the graph input, or INTERPOLATE of it: INTERPOLATE takes such an image
+     * in mode bilinear | align_corners and gives an f32 image every reader of the input takes); i0 = w, i1 = h. The result is f16 [gw gh C, w, h, N] with gw = W / w,
+     * gh = H / h: channel gx + gw (gy + gh c) of pixel (py, px) is image (gy h + py, gx w + px, c). w and h divide the image; gw gh C is a multiple of 8. */
+    VISP_OP_IMAGE_PATCHES = 43
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

@@ -627,6 +627,31 @@ VX_API int vx_foreground_stage(const void* img, int img_format, const float* fg,
  * mask u8. f32 arithmetic without fused multiply-adds: the bits of the reference's host code. */
 VX_API int vx_alpha_composite_u8(const uint8_t* fg_rgba, const uint8_t* bg, int bg_channels, const uint8_t* mask, uint8_t* out_rgba, int64_t n_pixels, void* stream);
 
+/* ---- image ops and pixel gates of BiRefNet on the graph layer (kernels_imgops.hip; birefnet.cpp:20-73, 147-260). Memory-bound passes, no atomics: the
+ * same bits on every launch. */
+/* bilinear | align_corners resize of an f32 image: x [B, H, W, C] -> y [B, OH, OW, C], C 1..4. Source coordinate o * fl((in - 1) / (out - 1)) in f32 (0 where
+ * out is 1), both taps clamped to the image, horizontal lerp v0 + (v1 - v0) t, then vertical: the arithmetic of vx_bf_preprocess_half */
+VX_API int vx_image_bilinear_ac_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, void* stream);
+/* image_to_patches (birefnet.cpp:153-162) of an f32 image x [B, IH, IW, C], C 1..4, as an f16 map y [B, h, w, gw gh C] with gw = IW / w, gh = IH / h:
+ * channel gx + gw (gy + gh c) of pixel (py, px) is x[gy h + py, gx w + px, c], rounded to nearest even. w and h divide the image; gw gh C % 8 == 0. form 1: one
+ * thread gathers 8 channels (8 loads w pixels apart); form 2: a block stages vx_image_patches_tile(gw gh C) output pixels in LDS from contiguous image-row
+ * segments and writes them as one contiguous run; form 0 takes form 2 where it was measured faster (tiles below 32 pixels: more than 888 channels) and form 1 otherwise.
+ * Both give the same bits. */
+VX_API int vx_image_patches_f16(const float* x, void* y, int B, int IH, int IW, int C, int h, int w, int form, void* stream);
+/* output pixels per block of form 2 for that many channels: the largest power of two <= 64 whose tile (channels + 8 halves per pixel) fits 56 KiB; 0 if none */
+VX_API int vx_image_patches_tile(int channels);
+/* the gdt gate (birefnet.cpp:189-192) per pixel: g = sigmoid(bias + sum_k a[r, k] w[k]) over the Cg channels of a (f32 sum, k ascending), rounded to f16 as
+ * vx_bf_mul_sigmoid_f16's operand is; y[r, c] = f16(p[r, c] * g) for the C channels of p. p, a, y f16 with rows ldp / lda / ldy elements apart (multiples of 8);
+ * w f32 [Cg]; C and Cg multiples of 8; 16-byte aligned; y overlaps neither p nor a. */
+VX_API int vx_pixel_gate_f16(const void* p, int64_t ldp, const void* a, int64_t lda, const float* w, float bias, void* y, int64_t ldy, int64_t rows, int C, int Cg, void* stream);
+/* vx_bilinear_ac_f16 with x and y pixels x_pix / y_pix elements apart (multiples of 8, >= C): a resize that reads a channel slice and writes its slice of a
+ * concat's buffer. The same bits as vx_bilinear_ac_f16 where both strides are C. */
+VX_API int vx_bilinear_ac_pix_f16(const void* x, int64_t x_pix, void* y, int64_t y_pix, int B, int H, int W, int C, int OH, int OW, void* stream);
+/* LayerNorm (nn.cpp:14-19) of contiguous f16 rows x [rows][C] with output rows y_pix elements apart (a multiple of 8, >= C): a norm that writes its slice of a
+ * concat's buffer. w, b f32 [C]; C % 8 == 0, C <= 1024. f32: mean, then the mean of squared deviations, 1 / sqrt(var + eps); one rounding to f16.
+ * 8, 16, 32 or 64 lanes per row by C. */
+VX_API int vx_layernorm_pix_f16(const void* x, const float* w, const float* b, void* y, int64_t y_pix, int64_t rows, int C, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_nor
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
                                          "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
-                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos", "rope"};
+                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos", "rope", "image_patches"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -247,6 +247,9 @@ bool foldable(int32_t op) {
            op == gop_concat || op == gop_interpolate || op == gop_permute || op == gop_roll || op == gop_pad || op == gop_get_rows || op == gop_cast || op == gop_sigmoid ||
            op == gop_silu || op == gop_sub || op == gop_clamp || op == gop_mul_mat || op == gop_sin || op == gop_cos;
 }
+
+// the f32 image the reference uploads, [C <= 4, W, H, N], or a resize of one: what interpolate and image_patches take besides f16 activations
+bool is_f32_image(graph_node const& x) { return !x.constant && x.dtype == gdt_f32 && x.ne[0] <= 4 && (x.op == gop_input || x.op == gop_interpolate); }
 
 void check_tensor(graph const& g, int t, const char* what) {
     if (t < 0 || t >= (int)g.nodes.size()) throw except("%s: tensor handle %d is not part of this graph", what, t);
@@ -485,7 +488,24 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             same_shape();
             n.ne[1] = n.ip[0];
             n.ne[2] = n.ip[1];
+            if (is_f32_image(S(0))) { // downscale_by(image, 2) (birefnet.cpp:36-41): an f32 image again, for every reader of the input image
+                if ((n.ip[2] & 255) != 1 || !(n.ip[2] & 256))
+                    throw except("interpolate: mode %lld (%s%s) on an f32 image is not built (bilinear | align_corners is)", (long long)n.ip[2],
+                                 (n.ip[2] & 255) == 0 ? "nearest" : ((n.ip[2] & 255) == 1 ? "bilinear" : ((n.ip[2] & 255) == 2 ? "bicubic" : "unknown")), n.ip[2] & 256 ? " | align_corners" : "");
+                n.dtype = gdt_f32;
+            }
             break;
+        case gop_image_patches: {
+            need_src(1, 1);
+            graph_node const& x = S(0);
+            const int64_t w = n.ip[0], h = n.ip[1];
+            if (!is_f32_image(x)) throw except("image_patches: the operand is an f32 image [C <= 4, W, H, N] (the graph input, or interpolate of it), not %s %s", x.constant ? "the constant" : (x.dtype == gdt_f32 ? "the f32 tensor" : "the f16 / integer tensor"), shape_str(x.ne).c_str());
+            if (n_ip != 2 || w <= 0 || h <= 0) throw except("image_patches: two positive integer parameters (w, h of the patch map)");
+            if (x.ne[1] % w || x.ne[2] % h) throw except("image_patches: Grid must divide image size (image %lldx%lld, patches %lldx%lld)", (long long)x.ne[1], (long long)x.ne[2], (long long)w, (long long)h);
+            const int64_t gw = x.ne[1] / w, gh = x.ne[2] / h;
+            if (gw * gh * x.ne[0] % 8) throw except("image_patches: grid %lldx%lld of a %lld-channel image gives %lld channels (a multiple of 8; at grid 1 a conv reads the image itself)", (long long)gw, (long long)gh, (long long)x.ne[0], (long long)(gw * gh * x.ne[0]));
+            n.ne[0] = gw * gh * x.ne[0]; n.ne[1] = w; n.ne[2] = h; n.ne[3] = x.ne[3];
+        } break;
         case gop_attention: {
             need_src(3, 3);
             graph_node const &q = S(0), &k = S(1), &v = S(2);
@@ -778,7 +798,7 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
         default: throw except("graph_add: op %d", op);
     }
     // f32 tensors exist as inputs only; an f32 operand anywhere else would need kernels this executor does not have
-    if (op != gop_patch_embed && op != gop_image_u8_to_f32 && op != gop_image_normalize)
+    if (op != gop_patch_embed && op != gop_image_u8_to_f32 && op != gop_image_normalize && op != gop_image_patches && !(op == gop_interpolate && is_f32_image(S(0))))
         for (int i = 0; i < n_src; ++i) {
             const bool head_tail = (op == gop_relu || op == gop_scale || op == gop_sigmoid) && S(i).op != gop_input; // (sigmoid: f32 in, f16 out)
             // (a 3x3 conv on the f32 image of <= 16 channels: the first conv of an image-to-image network, esrgan.cpp:58)

@@ -80,6 +80,8 @@ enum graph_op : int32_t {
     gop_cos,              // ggml_cos
     // the node of the SAM3 vision encoder beyond the above (sam3.h:413-438)
     gop_rope,             // x [n, heads, T, B] f16, pos i32 constant [T]; i0 = n_dims (== n), i1 = mode (0: NORMAL); f0 = freq_base, f1 = freq_scale   ggml_rope_ext
+    // the node of BiRefNet's decoder beyond the above (birefnet.cpp:153-162); interpolate also takes an f32 image [C <= 4, W, H, N] (birefnet.cpp:36-41)
+    gop_image_patches,    // f32 image [C <= 4, W, H, N]; i0 = w, i1 = h -> f16 [gw gh C, w, h, N], channel gx + gw (gy + gh c)   image_to_patches
     gop_count
 };
 const char* graph_op_name(int32_t op);

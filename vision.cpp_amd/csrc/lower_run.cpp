@@ -96,6 +96,7 @@ void lowering::run() {
     find_yolo_groups();
     find_migan_groups();
     find_sam_groups();
+    find_birefnet_groups();
     for (int t = 0; t < N; ++t) {
         graph_node& n = g.nodes[t];
         if (enc.ok && t == enc.first) emit_encoder();
@@ -198,6 +199,7 @@ void lowering::run() {
             case gop_add:
             case gop_mul:
             case gop_sub: {
+                if (auto it = gate_groups.find(t); it != gate_groups.end()) { pixel_gate(t, it->second); break; }
                 graph_node const& b = g.nodes[n.src[1]];
                 if (plane_broadcast(n.ne, b.ne)) { plane_binary(t); break; }
                 if (g.nodes[n.src[0]].constant) throw except("%s: the larger operand is a constant; broadcast of an activation onto it is not built", graph_op_name(n.op));
@@ -218,6 +220,7 @@ void lowering::run() {
                 });
             } break;
             case gop_layer_norm: {
+                if (g.fused_models && cat_slot.count(t)) { layer_norm_in_place(t); break; } // into its slice of a concat (lower_birefnet.cpp)
                 const int C = (int)n.ne[0];
                 if (C % 8 || C > 1024) throw except("layer_norm: %d channels (a multiple of 8, at most 1024)", C);
                 float *w = const_f32(n.src[1]), *b = const_f32(n.src[2]);
@@ -227,7 +230,10 @@ void lowering::run() {
                            [=](char* x, char* o, char*, void* st) { VX(vx_layernorm_f16(x, w, b, o, rows, C, eps, 0, 0, 0, st)); });
                 tag("layernorm", 0, (double)rows * C * 4);
             } break;
+            case gop_image_patches: image_patches(t); break;
             case gop_interpolate: {
+                if (n.dtype == gdt_f32) { image_resize(t); break; } // an f32 image (graph_add admits bilinear | align_corners only)
+                if (g.fused_models && (n.ip[2] & 255) == 1 && cat_slot.count(t)) { bilinear_in_place(t); break; }
                 if (nearest_into_reader(t)) break;
                 const bool nearest = (n.ip[2] & 255) == 0; // NEAREST on its own, or bilinear | align_corners
                 if (!nearest && ((!n.is_output && head_tail(t)) || resize_into_reader(t))) break;

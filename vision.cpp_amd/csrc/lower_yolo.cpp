@@ -121,7 +121,13 @@ bool lowering::placeable_launch(int s) const {
     graph_node const& n = g.nodes[s];
     if (n.constant || n.is_output || n.dtype != gdt_f16 || n.ne[0] % 8) return false;
     if (n.op == gop_pool_2d) return true;
-    if (n.op == gop_interpolate) return (n.ip[2] & 255) == 0; // nearest (a planar source read by one 3x3 conv never feeds a concat: nearest_into_reader)
+    if (n.op == gop_interpolate) {
+        if ((n.ip[2] & 255) == 0) return true; // nearest (a planar source read by one 3x3 conv never feeds a concat: nearest_into_reader)
+        // bilinear | align_corners of a map in a buffer of its own (vx_bilinear_ac_pix_f16; encode_concat, birefnet.cpp:50-57). A 1 x 1 source is a broadcast: it stays
+        // the launch it is (aspp_deformable's x5, birefnet.cpp:127-132)
+        graph_node const& x = g.nodes[n.src[0]];
+        return (n.ip[2] & 255) == 1 && (n.ip[2] & 256) && !x.constant && x.dtype == gdt_f16 && x.ne[1] * x.ne[2] > 1;
+    }
     if (auto it = launch_of_last.find(s); it != launch_of_last.end()) return g.nodes[it->second].op == gop_conv_2d;
     if (n.op != gop_conv_2d || silu_convs.count(s) || rep_member.count(s) || is_conv3x3(n, g.nodes[n.src[1]])) return false;
     graph_node const& x = g.nodes[n.src[0]];
@@ -211,6 +217,13 @@ void lowering::find_yolo_groups() {
                 for (size_t q = i; q < j; ++q) list[q].placed = true;
                 any = true;
                 i = j - 1;
+                continue;
+            }
+            // a LayerNorm read through one view by this concat alone (swin_encode's outputs in encode_concat, swin.cpp:262-264): its launch writes the slice
+            if (const int ln = v == srcs[i] ? norm_behind(v) : -1; ln >= 0 && !cat_slot.count(ln) && std::find(chain.begin(), chain.end(), sole_consumer(v)) != chain.end()) {
+                slots.emplace_back(ln, list[i].c0);
+                list[i].placed = true;
+                any = true;
                 continue;
             }
             if (!placeable_launch(v) || !in_place_readers_ok(v, chain)) continue;

@@ -8,6 +8,7 @@
 //   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
 //   lower_sam.cpp      attention without a mask on token-major q / k / v, mul_mat of activations, sin / cos, the Fourier-feature group
 //   lower_sam3.cpp     ROPE, the rope_2d group (alone, and in place behind the fused q|k|v product), get_rows with a run-time index
+//   lower_birefnet.cpp resize and patches of an f32 image, the pixel gate group, bilinear resizes and LayerNorms that write into a concat's buffer
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
 // Pattern functions MATCH first (const, nothing changes), and only when everything they need holds do they absorb nodes, pack and emit:
 // a `return false` leaves the lowering's state as it was. A finder that accepts a group says so in ONE table (claim): a matcher asks free_node()
@@ -143,6 +144,10 @@ struct lowering {
     struct rope2d_group { int src = -1, slice[2] = {-1, -1}, rope[2] = {-1, -1}; }; // r [hd, heads, T, B]; the slices of its two halves and their ropes
     std::map<int, rope2d_group> rope2d_groups;               // concat(rope(slice(r, first half), px), rope(slice(r, second half), py), dim 0) node -> its group
     std::map<int, std::array<int, 2>> qkv_rope;              // attention node of a fused q|k|v chain -> the rope_2d groups (concat nodes) q and k come through
+
+    // ---- the nodes of BiRefNet beyond a decoder block (lower_birefnet.cpp; the group with g.fused_models only)
+    struct gate_group { int p = -1, conv = -1, sig = -1, rep = -1; }; // the map gated; conv_2d(1x1 to one channel) -> sigmoid -> [repeat to p's shape]
+    std::map<int, gate_group> gate_groups;                   // mul(p, .) node -> the group its one launch computes
 
     explicit lowering(graph& gr) : g(gr) {}
     void run(); // the whole lowering: fills g.launches / g.buffers / the arena plan
@@ -355,6 +360,16 @@ struct lowering {
     void rope2d_in_place(int att, std::array<int, 3> const& hb);
     void rope(int t);
     void get_rows(int t);
+
+    // ---- lower_birefnet.cpp
+    void image_resize(int t);
+    void image_patches(int t);
+    bool match_gate_group(int t, gate_group& G) const;
+    void find_birefnet_groups();
+    void pixel_gate(int t, gate_group const& G);
+    int norm_behind(int v) const;
+    void bilinear_in_place(int t);
+    void layer_norm_in_place(int t);
 
     // ---- lower_run.cpp
     void copy_op(int t);

@@ -553,10 +553,12 @@ def swin_attention_mask(w: int, h: int, window: int) -> np.ndarray:  # swin.cpp:
 
 def swin_precompute(m: ModelRef, image_extent, window: int, n_layers: int = 4):  # swin.cpp:303-314
     """The constants the reference's caller uploads: the relative position index and one shift mask per map extent, under the names
-    window_attention and layer look them up by."""
+    window_attention and layer look them up by. Called again for another extent over the same weights (BiRefNet's half-scale pass, birefnet.cpp:67-73), it
+    finds the constants that exist already and adds the masks that do not."""
     g = m.graph
     width, height = image_extent[0] // 4, image_extent[1] // 4
-    out = [g.add_weight(f"window_attention_{window}.rel_pos_index", swin_relative_position_index(window), I32)]
+    name = f"window_attention_{window}.rel_pos_index"
+    out = [g.get_tensor(name) or g.add_weight(name, swin_relative_position_index(window), I32)]
     for i in range(n_layers + 1):
         w, h = width >> i, height >> i
         name = f"swin_layer_{w}x{h}.attn_mask"
@@ -705,6 +707,111 @@ def birefnet_basic_decoder_block(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.
     x = birefnet_aspp_deformable(m["dec_att"], x)
     x = birefnet_conv_2d_batch_norm(m["conv_out"], x, 1, 1)
     return named(m, x)
+
+
+# ---- the whole BiRefNet against this layer (the structure of src/visp/arch/birefnet.cpp:20-73, 147-260) -----------------------------------------
+# In CWHN: the reference's permutes to WHCN and back are views here, and its concats on dimension 2 are on dimension 0. Three departures. image_to_patches
+# is one op (OP_IMAGE_PATCHES), not the reshape / permute chain, which lives in WHCN. The gate of a decoder level is mul(p, repeat(gate, p's shape)) when the
+# batch is larger than 1 -- ggml_mul's broadcast written out -- since mul takes a plane [1, W, H, 1] only; with fused models either form is one pixel_gate launch.
+# And encode_concat's last feature is one left fold [d0, d1, d2, xs3, up3] instead of the reference's [d0, d1, d2, concat(xs3, up3)]: the same channels
+# in the same order, and one buffer that every part is written into.
+
+def birefnet_upscale_to(m: ModelRef, x: Tensor, target: Tensor) -> Tensor:  # birefnet.cpp:20-30
+    return interpolate(m, x, (target.ne[1], target.ne[2]), BILINEAR_AC)
+
+
+def birefnet_downscale_by(m: ModelRef, x: Tensor, f: int) -> Tensor:  # birefnet.cpp:32-41; x an f16 map, or the f32 image
+    return interpolate(m, x, (x.ne[1] // f, x.ne[2] // f), BILINEAR_AC)
+
+
+def birefnet_encode_concat(m: ModelRef, xs, xs_low):  # birefnet.cpp:43-65
+    ups = [birefnet_upscale_to(m, xs_low[i], xs[i]) for i in range(4)]
+    out = [concat(m, [xs[i], ups[i]], 0) for i in range(3)]
+    downs = [birefnet_downscale_by(m, out[i], 8 >> i) for i in range(3)]
+    out.append(concat(m, [*downs, xs[3], ups[3]], 0))
+    return out
+
+
+def birefnet_precompute(m: ModelRef, image_extent, window: int):  # birefnet.cpp:321-323, for both passes of encode
+    """The SWIN constants of the full-size and of the half-size pass (m = the model's root)."""
+    swin_precompute(m["bb"], image_extent, window)
+    swin_precompute(m["bb"], (image_extent[0] // 2, image_extent[1] // 2), window)
+
+
+def birefnet_encode(m: ModelRef, x: Tensor, window: int, depths, n_heads):  # birefnet.cpp:67-73; x = the normalised f32 image [3, W, H, N]
+    xs = swin_encode(m["bb"], x, window, depths, n_heads)
+    x_low = birefnet_downscale_by(m, x, 2)
+    xs_low = swin_encode(m["bb"], x_low, window, depths, n_heads)
+    return birefnet_encode_concat(m, xs, xs_low)
+
+
+def birefnet_simple_conv(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.cpp:147-151
+    x = conv_2d(m["conv1"], x, 1, 1)
+    x = conv_2d(m["conv_out"], x, 1, 1)
+    return named(m, x)
+
+
+def birefnet_image_to_patches(m: ModelRef, x: Tensor, out_w: int, out_h: int) -> Tensor:  # birefnet.cpp:153-162; x = the f32 image -> f16 [gw gh C, out_w, out_h, N]
+    return m.graph.op(OP_IMAGE_PATCHES, [x], [out_w, out_h])
+
+
+def birefnet_gdt_conv(m: ModelRef, x: Tensor) -> Tensor:  # birefnet.cpp:164-168
+    return relu(m, birefnet_conv_2d_batch_norm(m[0], x, 1, 1))
+
+
+def birefnet_decode(m: ModelRef, x: Tensor, features, captures: bool = False) -> Tensor:  # birefnet.cpp:170-248; x = the f32 image
+    g = m.graph
+    x1, x2, x3, x4 = features
+
+    def keep(t, name):
+        return g.output(t, name) if captures else t
+
+    def with_patches(blk, t):  # birefnet.cpp:181-187
+        patches = birefnet_image_to_patches(m, x, t.ne[1], t.ne[2])
+        patches = birefnet_simple_conv(m[blk], patches)
+        return concat(m, [t, patches], 0)
+
+    def gated(level, p):  # birefnet.cpp:189-192
+        p_gdt = birefnet_gdt_conv(m[f"gdt_convs_{level}"], p)
+        gdt_attn = sigmoid(m, conv_2d(m[f"gdt_convs_attn_{level}.0"], p_gdt))
+        if p.ne[3] > 1:
+            gdt_attn = repeat(m, gdt_attn, *p.ne)
+        return mul(m, p, gdt_attn)
+
+    p4 = keep(gated(4, birefnet_basic_decoder_block(m["block4"], with_patches("ipt_blk5", x4))), "p4")
+    x3 = conv_2d(m["lateral_block4.conv"], x3)
+    _p3 = add(m, birefnet_upscale_to(m, p4, x3), x3)
+
+    p3 = keep(gated(3, birefnet_basic_decoder_block(m["block3"], with_patches("ipt_blk4", _p3))), "p3")
+    _p3 = birefnet_upscale_to(m, p3, x2)
+    x2 = conv_2d(m["lateral_block3.conv"], x2)
+    _p2 = add(m, _p3, x2)
+
+    p2 = keep(gated(2, birefnet_basic_decoder_block(m["block2"], with_patches("ipt_blk3", _p2))), "p2")
+    _p2 = birefnet_upscale_to(m, p2, x1)
+    x1 = conv_2d(m["lateral_block2.conv"], x1)
+    _p1 = add(m, _p2, x1)
+
+    _p1 = keep(birefnet_basic_decoder_block(m["block1"], with_patches("ipt_blk2", _p1)), "p1")
+    _p1 = birefnet_upscale_to(m, _p1, x)
+    p1_ipt = birefnet_simple_conv(m["ipt_blk1"], x)
+    _p1 = concat(m, [_p1, p1_ipt], 0)
+    p1_out = sigmoid(m, conv_2d(m["conv_out1.0"], _p1))
+    return named(m, p1_out)
+
+
+def birefnet_predict(m: ModelRef, image: Tensor, window: int, depths, n_heads, captures: bool = False) -> Tensor:  # birefnet.cpp:252-260
+    """m = the model's root, after birefnet_precompute for the image's extent. captures: the encoder features, the squeeze block and the four decoder levels
+    are outputs too (feature_0 .. feature_3, squeeze, p4 .. p1), as the hand schedule's captures name them."""
+    g = m.graph
+    features = birefnet_encode(m, image, window, depths, n_heads)
+    if captures:
+        features = [g.output(f, f"feature_{i}") for i, f in enumerate(features)]
+    features[3] = birefnet_basic_decoder_block(m["squeeze_module.0"], features[3])
+    if captures:
+        g.output(features[3], "squeeze")
+    scaled_preds = birefnet_decode(m["decoder"], image, features, captures)
+    return g.output(scaled_preds, "output")
 
 
 # ---- TinyViT (the MobileSAM image encoder) against this layer (the structure of src/visp/arch/mobile-sam.cpp:15-208) ---------------------------
