@@ -3,8 +3,11 @@ over the vx_* C ABI (include/visp_hip_kernels.h)."""
 from __future__ import annotations
 
 import ctypes as C
+import time
+from collections import defaultdict
 
 import numpy as np
+import pytest
 
 from visioncpp_amd import _lib as L
 from visioncpp_amd.vision import DeviceBuffer
@@ -38,6 +41,71 @@ def release():
 
 def sync():
     L.vx_check(api().vx_stream_sync(None))
+
+
+def ptr(a):
+    """a host array as a device address (None stays NULL)"""
+    return None if a is None else dev(np.ascontiguousarray(a)).ptr
+
+
+def ids(cases):
+    return [c["id"] for c in cases]
+
+
+# ---- what the argument-space suites (test_gpu_*_matrix.py) share around buffer_check.assert_buffer ---------------------------------------
+
+class Report:
+    """One suite's table of the largest error / allowance per key, printed at module teardown: reported, not asserted. One instance per test
+    module. `headline` may hold {launches} and {seconds}; `row(key, ratio, count)` formats a line; `tail()` gives the lines behind the table."""
+
+    def __init__(self, headline, row, tail=None):
+        self.headline, self.row, self.tail = headline, row, tail
+        self.ratio, self.count = defaultdict(float), defaultdict(int)
+        self.launches, self.t0 = 0, time.time()
+
+    def add(self, key, ratio, launches=1):
+        self.ratio[key] = max(self.ratio[key], ratio)
+        self.count[key] += launches
+        self.launches += launches
+
+    def print(self):
+        print("\n" + self.headline.format(launches=self.launches, seconds=time.time() - self.t0))
+        for key, ratio in sorted(self.ratio.items()):
+            print(self.row(key, ratio, self.count[key]))
+        for line in self.tail() if self.tail else ():
+            print(line)
+
+
+def device_fixture(report, reset=None):
+    """-> the module-scoped autouse fixture of a suite (bind it to a name in the test module): a device is there and selected; at teardown
+    `reset` (the suite's own hooks), then the report"""
+    @pytest.fixture(scope="module", autouse=True)
+    def _device():
+        assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
+        L.vx_check(api().vx_set_device(0))
+        report.t0 = time.time()
+        yield
+        if reset:
+            reset()
+        report.print()
+    return _device
+
+
+def release_fixture(reset=None):
+    """-> the per-test autouse fixture of a suite: `reset`, then every buffer of the test is released"""
+    @pytest.fixture(autouse=True)
+    def _release_buffers():
+        yield
+        if reset:
+            reset()
+        release()
+    return _release_buffers
+
+
+def assert_nothing_launched(scratch, nbytes):
+    """the tail of a refusal table: the scratch all operands pointed at is still zero"""
+    sync()
+    assert not scratch.to_numpy(np.uint8, (nbytes,)).any(), "a refused call wrote to an operand"
 
 
 def pad_weight(w: np.ndarray, n_align=32, k_align=64):

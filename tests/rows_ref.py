@@ -7,7 +7,7 @@ elements behind the last row) as the call leaves a buffer that started filled wi
 so the buffer is not zero-initialised: CANARY = -24000 is finite, exact in f16 and f32, and nothing here comes near it (the LayerNorm, add and
 depthwise cases on ordinary data stay below 1e3, a GELU is never below -0.17 and the large-magnitude cases hold nothing between 40 and
 30000 in magnitude; tests/test_rows_ref_cpu.py asserts that every element a call writes lies further from it than its allowance plus 1000). An element the call must not
-write has `written` False, allowance 0 and must still hold the canary's bits. `min_guard` is one full block of the kernel's rows.
+write has `written` False, allowance 0 and must still hold the canary's bits (tests/buffer_check.py, with `untouched=CANARY`). `min_guard` is one full block of the kernel's rows.
 
 Entries (`args` holds the launcher's own arguments, numpy arrays for the whole operands, already rounded to the type the kernel reads):
   ln32          vx_layernorm_f32_f16             x f32 [M, C] -> f16 [M, C]
@@ -247,25 +247,8 @@ def out_dtype(entry, args):
 
 
 def canary_buffer(size, dtype):
+    """what an output buffer holds before the call: buffer_check.violations(got, ref, untouched=CANARY) is the comparison"""
     return np.full(size, CANARY, dtype)
-
-
-def violations(got, ref):
-    """The one comparison of a whole buffer (what the device left, or what an emulation says it would) with evaluate()'s result ->
-    dict(stray: elements the call must leave alone that no longer hold the canary's bits, nonfinite, outside: elements with
-    |got - want| > allow (a NaN is outside), ratio: the largest error / allowance, err: the largest error, worst: its index)"""
-    want, allow, written = ref
-    assert got.shape == want.shape and got.dtype in (np.float16, np.float32)
-    as_bits = np.uint32 if got.dtype == np.float32 else np.uint16
-    stray = (got.view(as_bits) != np.array(CANARY, got.dtype).view(as_bits)) & ~written
-    err = np.abs(got.astype(np.float64) - want)
-    outside = ~(err <= allow)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))
-    finite = np.isfinite(got)
-    return dict(stray=int(stray.sum()), first_stray=int(np.argmax(stray)), nonfinite=int((~finite).sum()), outside=int(outside.sum()),
-                ratio=float(np.max(np.where(finite, ratio, np.inf))), err=float(np.max(np.where(finite, err, np.inf))),
-                worst=int(np.argmax(np.where(finite, err - allow, np.inf))))
 
 
 def evaluate(entry: str, args, guard: int):

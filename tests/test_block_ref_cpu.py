@@ -9,6 +9,7 @@ import pytest
 
 import block_cases as T
 import block_ref as R
+from buffer_check import violations
 from visioncpp_amd import _lib as L
 
 D, HID, HEADS = R.D, R.HID, R.HEADS
@@ -288,7 +289,7 @@ def _reference(c):
 
 
 def _outside(c, mut=None, carried=False):
-    """per buffer: elements of the emulation outside the allowance, and the largest error / allowance. As the GPU test does it: x and cap_x1
+    """per buffer: elements of the emulation that buffer_check.violations rejects, and the largest error / allowance. As the GPU test does it: x and cap_x1
     against the reference of the inputs, feat / q / k / v against the reference of the stream that came back (`carried`: of the inputs as well,
     with the allowance of x carried into them)"""
     a, ref = _reference(c)
@@ -297,12 +298,8 @@ def _outside(c, mut=None, carried=False):
         ref = dict(ref, **R.evaluate(a, x_out=got["x"]))
     res = {}
     for n in BUFFERS:
-        want, allow, written = ref[n]
-        err = np.abs(got[n] - want)
-        bad = ~(err <= allow)  # (a NaN is outside)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))
-        res[n] = (int(bad.sum()), float(np.max(ratio)) if np.isfinite(err).all() else float("inf"))
+        v = violations(got[n], ref[n], untouched=a["x"] if n == "x" else 0.0)  # the GPU test's comparison (a NaN is outside)
+        res[n] = (v["stray"] + v["nonfinite"] + v["outside"], v["ratio"])
     return res
 
 

@@ -10,35 +10,28 @@ import pytest
 
 import attn_cases as T
 import attn_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, release, sync  # noqa: E402
+from gpu_util import Report, api, assert_nothing_launched, dev, device_fixture, empty, ids, release_fixture, sync  # noqa: E402
 
 GUARD_ROWS = 256  # the largest query block of the five kernels
-RATIO = defaultdict(float)  # (entry point, case group) -> largest error / allowance seen; reported, not asserted
 WAVE_BITS = {"equal": 0, "compared": 0}
 SECONDS = defaultdict(float)  # case group -> wall time of its cases, references included
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    t0 = time.perf_counter()
-    yield
-    print(f"\n{len(T.ALL)} cases in {time.perf_counter() - t0:.1f} s; largest |got - want| / allowance per entry point and group:")
-    for (entry, grp), ratio in sorted(RATIO.items()):
-        print(f"  {entry:34s} {grp:10s} {ratio:.3f}")
-    print("wall time per group, float64 references included: " + ", ".join(f"{g} {t:.2f} s" for g, t in SECONDS.items()))
-    print(f"vx_attention_f16, 4 waves against 8 waves: {WAVE_BITS['equal']} of {WAVE_BITS['compared']} outputs bit-identical")
+def _tail():
+    return ["wall time per group, float64 references included: " + ", ".join(f"{g} {t:.2f} s" for g, t in SECONDS.items()),
+            f"vx_attention_f16, 4 waves against 8 waves: {WAVE_BITS['equal']} of {WAVE_BITS['compared']} outputs bit-identical"]
 
 
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    release()
+# (entry point, case group) -> largest error / allowance seen; reported, not asserted
+REPORT = Report(f"{len(T.ALL)} cases in {{seconds:.1f}} s; largest |got - want| / allowance per entry point and group:",
+                lambda key, ratio, count: f"  {key[0]:34s} {key[1]:10s} {ratio:.3f}", tail=_tail)
+_device = device_fixture(REPORT)
+_release_buffers = release_fixture()
 
 
 def _out(want):
@@ -145,17 +138,7 @@ ENTRY = {"attention": "vx_attention_f16", "masked": "vx_attention_masked_f16", "
 
 
 def compare(got, ref, key, what=""):
-    want, allow, written = ref
-    bits = got.view(np.uint16)
-    assert not bits[~written].any(), f"{what}: {int((bits[~written] != 0).sum())} elements written that the call must leave alone"
-    assert np.isfinite(got).all(), what
-    err = np.abs(got.astype(np.float64) - want)
-    ratio = float((err[written] / allow[written]).max())
-    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
-    RATIO[key] = max(RATIO[key], ratio)
-    worst = np.unravel_index(np.argmax(err - allow), err.shape)
-    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
-                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
+    REPORT.add(key, assert_buffer(got, ref, what)["ratio"])
 
 
 def check(case, group):
@@ -187,36 +170,32 @@ def _check(case, group):
         np.testing.assert_array_equal(got[0].view(np.uint16), got[T.attention_default_waves(a["T"])].view(np.uint16))
 
 
-def _ids(cases):
-    return [c["id"] for c in cases]
-
-
-@pytest.mark.parametrize("case", T.group("attention"), ids=_ids(T.group("attention")))
+@pytest.mark.parametrize("case", T.group("attention"), ids=ids(T.group("attention")))
 def test_attention(case):
     check(case, "attention")
 
 
-@pytest.mark.parametrize("case", T.group("masked"), ids=_ids(T.group("masked")))
+@pytest.mark.parametrize("case", T.group("masked"), ids=ids(T.group("masked")))
 def test_attention_masked(case):
     check(case, "masked")
 
 
-@pytest.mark.parametrize("case", T.group("window"), ids=_ids(T.group("window")))
+@pytest.mark.parametrize("case", T.group("window"), ids=ids(T.group("window")))
 def test_window_attention(case):
     check(case, "window")
 
 
-@pytest.mark.parametrize("case", T.group("shifted"), ids=_ids(T.group("shifted")))
+@pytest.mark.parametrize("case", T.group("shifted"), ids=ids(T.group("shifted")))
 def test_window_attention_shifted(case):
     check(case, "shifted")
 
 
-@pytest.mark.parametrize("case", T.group("small"), ids=_ids(T.group("small")))
+@pytest.mark.parametrize("case", T.group("small"), ids=ids(T.group("small")))
 def test_small_attention(case):
     check(case, "small")
 
 
-@pytest.mark.parametrize("case", T.group("cross"), ids=_ids(T.group("cross")))
+@pytest.mark.parametrize("case", T.group("cross"), ids=ids(T.group("cross")))
 def test_attention_cross(case):
     check(case, "cross")
 
@@ -230,8 +209,7 @@ def _refusals(table, base, call):
         args = {k: (scratch.ptr + int(v[3:] or 0) if isinstance(v, str) and v.startswith("ptr") else v) for k, v in args.items()}   # "ptr", "ptr+8"
         assert call(args) == 0, f"accepted: {fields}"
         assert message.encode() in api().vx_last_error(), (fields, api().vx_last_error())
-    sync()
-    assert not scratch.to_numpy(np.uint8, (1 << 16,)).any(), "a refused call wrote to an operand"
+    assert_nothing_launched(scratch, 1 << 16)
 
 
 def test_attention_refusals():

@@ -7,44 +7,34 @@ feat, q, k, v against the reference of the residual stream that came back, so no
 The largest error / allowance per buffer -- split by instance, by row class and, in the hidden-unit probes, by GELU population -- is printed at
 module teardown: reported, not asserted (profiles/block16_matrix_ratios.txt holds the numbers a later kernel change is judged against)."""
 import ctypes as C
-import time
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 import block_cases as T
 import block_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 from visioncpp_amd.vision import DeviceBuffer
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, release, sync  # noqa: E402
+from gpu_util import Report, api, assert_nothing_launched, dev, device_fixture, empty, release_fixture, sync  # noqa: E402
 
 D, HEADS = R.D, R.HEADS
-RATIO = defaultdict(float)  # (buffer, split) -> largest error / allowance seen
-COUNT = defaultdict(int)
+# (buffer, split) -> largest error / allowance seen
+REPORT = Report("{launches} launches compared in {seconds:.1f} s; largest |got - want| / allowance per buffer and split:",
+                lambda key, ratio, count: f"  {key[0]:7s} {key[1]:22s} {ratio:.3f}")
 _WEIGHTS = {}               # weight set -> its device buffers, uploaded once
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    t0 = time.time()
-    yield
+def _drop_weights():
     sync()
     _WEIGHTS.clear()
-    print(f"\n{COUNT['launches']} launches compared in {time.time() - t0:.1f} s; largest |got - want| / allowance per buffer and split:")
-    for (buf, split), ratio in sorted(RATIO.items()):
-        print(f"  {buf:7s} {split:22s} {ratio:.3f}")
 
 
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    release()
+_device = device_fixture(REPORT, reset=_drop_weights)
+_release_buffers = release_fixture()
 
 
 def device_weights(name):
@@ -91,21 +81,9 @@ def per_row(v, M):
 
 
 def compare(name, got, ref, initial, case, splits):
-    want, allow, written = ref
-    what = f"{case['id']} {name}"
-    bits = np.uint32 if got.dtype == np.float32 else np.uint16
-    stray = got.view(bits)[~written] != np.asarray(initial, got.dtype).view(bits)[~written]
-    assert not stray.any(), f"{what}: {int(stray.sum())} elements written that the call must leave alone, the first at flat index {int(np.flatnonzero(~written.reshape(-1))[np.argmax(stray)])}"
-    assert np.isfinite(got[written]).all(), f"{what}: {int((~np.isfinite(got[written])).sum())} written elements are not finite"
-    err = np.where(written, np.abs(got.astype(np.float64) - want), 0.0)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))
-    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio.max():.3f}")
+    ratio = assert_buffer(got, ref, f"{case['id']} {name}", untouched=initial)["ratios"]
     for split, mask in splits.items():
-        RATIO[(name, split)] = max(RATIO[(name, split)], float(per_row(ratio, case["M"])[mask].max()) if mask.ndim == 1 else float(ratio[mask].max()))
-    worst = np.unravel_index(int(np.argmax(err - allow)), err.shape)
-    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
-                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
+        REPORT.add((name, split), float(per_row(ratio, case["M"])[mask].max()) if mask.ndim == 1 else float(ratio[mask].max()), launches=0)
 
 
 CASES = T.all_cases()
@@ -122,7 +100,7 @@ def test_block(case):
     cls = np.array(T.row_classes(M)) if case["data"] == "mixed" else np.array(["probe"] * M)
     splits = {"inst " + case["inst"]: np.ones(M, bool)}
     splits.update({"rows " + k: cls == k for k in set(cls.tolist())})
-    COUNT["launches"] += 1
+    REPORT.launches += 1
     for name in ("x", "cap_x1", "feat", "q", "k", "v"):
         if name not in got:
             continue
@@ -135,7 +113,7 @@ def test_block(case):
             s["gelu packed-f16 units"] = packed
             if f32.any():
                 s["gelu f32 units"] = f32
-        compare(name, got[name], ref[name], a["x"] if name == "x" else 0.0 * got[name], case, s)
+        compare(name, got[name], ref[name], a["x"] if name == "x" else 0.0, case, s)
     if case["inst"] == "FTF":
         np.testing.assert_array_equal(got["x"].view(np.uint32), np.ascontiguousarray(a["x"], np.float32).view(np.uint32))
     if case.get("exact_cap"):  # Wo' = I on small integers: x + att bit for bit
@@ -146,5 +124,4 @@ def test_refusals():
     lib = api()
     scratch = empty(T.REFUSAL_SCRATCH_BYTES)
     assert T.run_refusals(lib, scratch.ptr) == len(T.REFUSALS)
-    sync()
-    assert not scratch.to_numpy(np.uint8, (T.REFUSAL_SCRATCH_BYTES,)).any()  # nothing was launched
+    assert_nothing_launched(scratch, T.REFUSAL_SCRATCH_BYTES)

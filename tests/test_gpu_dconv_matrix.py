@@ -6,40 +6,30 @@ The stream cases run a 40-tile problem three times: with the launcher's grid cap
 tiles across tile-shape changes and image boundaries: the next tile's first chunk under the current tile's epilogue, the counted waits with
 stores in flight, a tile boundary at every position of the unrolled step loop), with 16 (stride 2), and uncapped (one tile per block)."""
 import ctypes as C
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 import dconv_cases as T
 import dconv_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, release, sync  # noqa: E402
+from gpu_util import Report, api, dev, device_fixture, empty, ids, release_fixture, sync  # noqa: E402
 
-RATIO = defaultdict(float)  # variant -> largest error / allowance seen; reported, not asserted
+# variant -> largest error / allowance seen; reported, not asserted
+REPORT = Report("largest |got - want| / allowance per variant:", lambda variant, ratio, count: f"  {variant:13s} {ratio:.3f}")
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    yield
+def _default_grid():
     api().vx_dconv_set_block_cap(0)
     api().vx_dconv_set_resident_mode(-1)
-    print("\nlargest |got - want| / allowance per variant:")
-    for v, ratio in sorted(RATIO.items()):
-        print(f"  {v:13s} {ratio:.3f}")
 
 
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    api().vx_dconv_set_block_cap(0)
-    api().vx_dconv_set_resident_mode(-1)
-    release()
+_device = device_fixture(REPORT, reset=_default_grid)
+_release_buffers = release_fixture(reset=_default_grid)
 
 
 def launch(a, cap=0, res_mode=-1, stamps=None):
@@ -75,17 +65,7 @@ def launch(a, cap=0, res_mode=-1, stamps=None):
 
 
 def compare(a, got, ref, variant, what=""):
-    want, allow, written = (r["out"] for r in ref)
-    bits = got.view(np.uint32 if got.dtype == np.float32 else np.uint16)
-    assert not bits[~written].any(), f"{what}: {int((bits[~written] != 0).sum())} elements written that the call must leave alone"
-    assert np.isfinite(got).all(), what
-    err = np.abs(got.astype(np.float64) - want)
-    ratio = float((err[written] / allow[written]).max())
-    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
-    RATIO[variant] = max(RATIO[variant], ratio)
-    worst = int(np.argmax(err - allow))
-    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
-                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
+    REPORT.add(variant, assert_buffer(got, tuple(r["out"] for r in ref), what)["ratio"])
 
 
 def check(case, cap=0):
@@ -96,11 +76,7 @@ def check(case, cap=0):
     return got
 
 
-def _ids(cases):
-    return [c["id"] for c in cases]
-
-
-@pytest.mark.parametrize("case", T.group("stream"), ids=_ids(T.group("stream")))
+@pytest.mark.parametrize("case", T.group("stream"), ids=ids(T.group("stream")))
 def test_stream(case):
     a = T.materialize(case)
     ref = R.evaluate(a)
@@ -116,7 +92,7 @@ def test_stream(case):
             np.testing.assert_array_equal(first.view(np.uint16 if got.dtype == np.float16 else np.uint32), got.view(np.uint16 if got.dtype == np.float16 else np.uint32))
 
 
-@pytest.mark.parametrize("case", T.group("stamps"), ids=_ids(T.group("stamps")))
+@pytest.mark.parametrize("case", T.group("stamps"), ids=ids(T.group("stamps")))
 def test_stream_with_stamps(case):
     """The diagnostics instantiation: bit-identical to the product one, and slot 6 of a block's row is the number of (tile, chunk) steps it owns."""
     a = T.materialize(case)
@@ -138,19 +114,19 @@ def test_stream_with_stamps(case):
         assert (s[:blocks, 7] != 0).all() and not s[blocks:].any()
 
 
-@pytest.mark.parametrize("case", T.group("epilogue"), ids=_ids(T.group("epilogue")))
+@pytest.mark.parametrize("case", T.group("epilogue"), ids=ids(T.group("epilogue")))
 def test_epilogue(case):
     check(case)
 
 
-@pytest.mark.parametrize("case", T.group("geometry"), ids=_ids(T.group("geometry")))
+@pytest.mark.parametrize("case", T.group("geometry"), ids=ids(T.group("geometry")))
 def test_geometry(case):
     check(case)
     if T.tile_count(case["H"], case["W"]) * case["B"] > 8:
         check(case, cap=8)
 
 
-@pytest.mark.parametrize("case", T.group("padded"), ids=_ids(T.group("padded")))
+@pytest.mark.parametrize("case", T.group("padded"), ids=ids(T.group("padded")))
 def test_padded_cin(case):
     """NHWC Cin = 48 run as cin = 64 with zero weights: channels 48..63 of a pixel are the next pixel's first 16 (times zero: finite even at
     +-65504) and, for an image's last pixel, past the buffer descriptor (zero-filled, whatever follows: here the next image, then NaNs)."""

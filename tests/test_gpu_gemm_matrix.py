@@ -4,38 +4,25 @@ must still hold zero bits (columns >= n_valid, the slack up to ldo, cls rows, dr
 every buffer carries GUARD_ROWS zeroed rows past the last one the call owns (whole extra images in the scattered layouts): one
 tallest block tile, so a store from any row of the tail tile lands inside the buffer and is compared."""
 import ctypes as C
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 import gemm_cases
 import gemm_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, gemm, release  # noqa: E402
+from gpu_util import Report, api, dev, device_fixture, empty, gemm, ids, release_fixture  # noqa: E402
 
 POINTERS = ("A", "W", "bias", "lambda_", "pos", "res1", "res2", "noise", "out0", "A_off")
 GUARD_ROWS = 256  # the tallest block tile
-RATIO = defaultdict(float)  # epilogue -> largest error / allowance seen; reported, not asserted
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    yield
-    print("\nlargest |got - want| / allowance per epilogue:")
-    for epi, ratio in sorted(RATIO.items()):
-        print(f"  {R.EPI_NAMES[epi]:10s} {ratio:.3f}")
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    release()
+# epilogue -> largest error / allowance seen; reported, not asserted
+REPORT = Report("largest |got - want| / allowance per epilogue:", lambda epi, ratio, count: f"  {R.EPI_NAMES[epi]:10s} {ratio:.3f}")
+_device = device_fixture(REPORT)
+_release_buffers = release_fixture()
 
 
 class _At:  # a device pointer into a buffer (gpu_util.gemm reads .ptr)
@@ -71,31 +58,17 @@ def launch(a, want):
 def check(a):
     want, allow, written = R.evaluate(a, GUARD_ROWS)
     got = launch(a, want)
-    for name in want:
-        g = got[name]
-        bits = g.view(np.uint32 if g.dtype == np.float32 else np.uint16)
-        assert not bits[~written[name]].any(), f"{name}: {int((bits[~written[name]] != 0).sum())} elements written that the call must leave alone"
-        assert np.isfinite(g).all(), name
-        err = np.abs(g.astype(np.float64) - want[name])
-        ratio = float((err[written[name]] / allow[name][written[name]]).max())
-        print(f"{name}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
-        RATIO[a["epi"]] = max(RATIO[a["epi"]], ratio)
-        worst = np.unravel_index(np.argmax(err - allow[name]), err.shape)
-        assert (err <= allow[name]).all(), (f"{name}: {int((err > allow[name]).sum())} of {err.size} elements outside the allowance; worst at {worst}: "
-                                            f"got {g[worst]}, want {want[name][worst]:.6g}, allowance {allow[name][worst]:.3g}")
+    for name in want:  # out, or q, k and vt
+        REPORT.add(a["epi"], assert_buffer(got[name], (want[name], allow[name], written[name]), name)["ratio"])
     return got
 
 
-def _ids(cases):
-    return [c["id"] for c in cases]
-
-
-@pytest.mark.parametrize("case", gemm_cases.group("a"), ids=_ids(gemm_cases.group("a")))
+@pytest.mark.parametrize("case", gemm_cases.group("a"), ids=ids(gemm_cases.group("a")))
 def test_epilogue_by_tile_form(case):
     check(gemm_cases.materialize(case))
 
 
-@pytest.mark.parametrize("case", gemm_cases.group("b"), ids=_ids(gemm_cases.group("b")))
+@pytest.mark.parametrize("case", gemm_cases.group("b"), ids=ids(gemm_cases.group("b")))
 def test_split_k(case):
     a = gemm_cases.materialize(case)
     first = check(a)
@@ -103,7 +76,7 @@ def test_split_k(case):
     np.testing.assert_array_equal(first["out"].view(np.uint16), again["out"].view(np.uint16))  # the fixed summation order: bit-identical
 
 
-@pytest.mark.parametrize("case", gemm_cases.group("c"), ids=_ids(gemm_cases.group("c")))
+@pytest.mark.parametrize("case", gemm_cases.group("c"), ids=ids(gemm_cases.group("c")))
 def test_conv_geometry(case):
     check(gemm_cases.materialize(case))
 

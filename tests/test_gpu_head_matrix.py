@@ -6,41 +6,30 @@ must not write has allowance 0 and must still hold zero bits (reported on its ow
 The walk case runs a 36-tile problem on 8 persistent blocks (vx_headconv_set_block_cap): five tiles per block across image boundaries, the
 double buffer's steady state -- and must give the bits of the default grid."""
 import ctypes as C
-import time
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 import head_cases as T
 import head_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, release, sync  # noqa: E402
+from gpu_util import Report, api, assert_nothing_launched, dev, device_fixture, empty, ids, release_fixture, sync  # noqa: E402
 
-RATIO = defaultdict(float)  # (entry point, data kind) -> largest error / allowance seen; reported, not asserted
-COUNT = defaultdict(int)
+# (entry point, data kind) -> largest error / allowance seen; reported, not asserted
+REPORT = Report("{launches} launches compared in {seconds:.1f} s; largest |got - want| / allowance per entry point and data kind:",
+                lambda key, ratio, count: f"  {key[0]:26s} {key[1]:9s} {ratio:.3f}  ({count} launches)")
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    t0 = time.time()
-    yield
+def _uncap():
     api().vx_headconv_set_block_cap(0)
-    print(f"\n{sum(COUNT.values())} launches compared in {time.time() - t0:.1f} s; largest |got - want| / allowance per entry point and data kind:")
-    for key, ratio in sorted(RATIO.items()):
-        print(f"  {key[0]:26s} {key[1]:9s} {ratio:.3f}  ({COUNT[key]} launches)")
 
 
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    api().vx_headconv_set_block_cap(0)
-    release()
+_device = device_fixture(REPORT, reset=_uncap)
+_release_buffers = release_fixture(reset=_uncap)
 
 
 def entry_point(a, entry):
@@ -85,45 +74,25 @@ def launch(entry, a, guard, cap=0):
     return out.to_numpy(np.float16, (n,))
 
 
-def compare(got, ref, key, what):
-    want, allow, written = ref
-    bits = got.view(np.uint32 if got.dtype == np.float32 else np.uint16)
-    stray = bits[~written] != 0
-    assert not stray.any(), f"{what}: {int(stray.sum())} elements written that the call must leave alone, the first at {int(np.flatnonzero(~written)[np.argmax(stray)])}"
-    assert np.isfinite(got).all(), f"{what}: {int((~np.isfinite(got)).sum())} elements are not finite"
-    err = np.abs(got.astype(np.float64) - want)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = float(np.max(np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))))
-    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
-    RATIO[key] = max(RATIO[key], ratio)
-    COUNT[key] += 1
-    worst = int(np.argmax(err - allow))
-    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
-                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
-
-
 def check(case, cap=0):
     a = T.materialize(case)
     guard = T.guard_of(case, a)
     got = launch(case["entry"], a, guard, cap)
-    compare(got, R.evaluate(case["entry"], a, guard), (entry_point(a, case["entry"]), case["kind"]), case["id"] + (f" cap {cap}" if cap else ""))
+    v = assert_buffer(got, R.evaluate(case["entry"], a, guard), case["id"] + (f" cap {cap}" if cap else ""))
+    REPORT.add((entry_point(a, case["entry"]), case["kind"]), v["ratio"])
     return got
-
-
-def _ids(cases):
-    return [c["id"] for c in cases]
 
 
 HEAD = [c for c in T.group("headconv") if "caps" not in c]
 WALKS = [c for c in T.group("headconv") if "caps" in c]
 
 
-@pytest.mark.parametrize("case", HEAD, ids=_ids(HEAD))
+@pytest.mark.parametrize("case", HEAD, ids=ids(HEAD))
 def test_headconv(case):
     check(case)
 
 
-@pytest.mark.parametrize("case", WALKS, ids=_ids(WALKS))
+@pytest.mark.parametrize("case", WALKS, ids=ids(WALKS))
 def test_headconv_capped_walk_gives_the_default_grid_s_bits(case):
     first = None
     for cap in case["caps"]:
@@ -134,12 +103,12 @@ def test_headconv_capped_walk_gives_the_default_grid_s_bits(case):
             np.testing.assert_array_equal(first.view(np.uint32), got.view(np.uint32))
 
 
-@pytest.mark.parametrize("case", T.group("rcu"), ids=_ids(T.group("rcu")))
+@pytest.mark.parametrize("case", T.group("rcu"), ids=ids(T.group("rcu")))
 def test_rcu(case):
     check(case)
 
 
-@pytest.mark.parametrize("case", T.group("bilinear"), ids=_ids(T.group("bilinear")))
+@pytest.mark.parametrize("case", T.group("bilinear"), ids=ids(T.group("bilinear")))
 def test_bilinear(case):
     got = check(case)
     if (case["H"], case["W"]) == (case["OH"], case["OW"]):  # the identity resize: the input's bits
@@ -152,7 +121,7 @@ BATCH = [dict(c, id=c["id"] + "-b3", B=3) for c in T.all_cases()
          if c["id"] in [f"head-second-tile-cin{cin}-pos" for cin in T.CINS] + ["rcu-{}x{}-rcu+res+proj".format(*T.RCU_FIXED[-1]), "bil-up2-c24"]]
 
 
-@pytest.mark.parametrize("case", BATCH, ids=_ids(BATCH))
+@pytest.mark.parametrize("case", BATCH, ids=ids(BATCH))
 def test_batch_position_does_not_show_in_the_bits(case):
     """an image's result at position 2 of B = 3 against the same image alone"""
     assert len(BATCH) == 5
@@ -173,6 +142,5 @@ def test_refusals():
     lib = api()
     scratch = empty(T.REFUSAL_SCRATCH_BYTES)
     assert T.run_refusals(lib, scratch.ptr) == len(T.HEAD_REFUSALS) + len(T.WIDE_REFUSALS) + len(T.RCU_REFUSALS) + len(T.BIL_REFUSALS) > 40
-    sync()
-    assert not scratch.to_numpy(np.uint8, (T.REFUSAL_SCRATCH_BYTES,)).any()  # nothing was launched
+    assert_nothing_launched(scratch, T.REFUSAL_SCRATCH_BYTES)
     assert lib.vx_headconv_set_block_cap(12) == 0 and b"multiple of 8" in lib.vx_last_error()

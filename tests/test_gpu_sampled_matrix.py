@@ -4,8 +4,6 @@ Every output buffer starts zeroed and is compared in full, what lies in front of
 the call must not write has allowance 0 and must still hold zero bits (reported on its own). One comparison per buffer, no element and no
 case exempt."""
 import ctypes as C
-import time
-from collections import defaultdict
 
 import numpy as np
 import pytest
@@ -13,36 +11,19 @@ import pytest
 import gemm_ref as G
 import sampled_cases as T
 import sampled_ref as R
+from buffer_check import assert_buffer
 from visioncpp_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import api, dev, empty, release, sync  # noqa: E402
+from gpu_util import Report, api, assert_nothing_launched, dev, device_fixture, empty, ids, ptr, release_fixture, sync  # noqa: E402
 
-RATIO = defaultdict(float)  # (entry point, data kind) -> largest error / allowance seen; reported, not asserted
-COUNT = defaultdict(int)
+# (entry point, data kind) -> largest error / allowance seen; reported, not asserted
+REPORT = Report("{launches} launches compared in {seconds:.1f} s; largest |got - want| / allowance per entry point and data kind:",
+                lambda key, ratio, count: f"  {key[0]:24s} {key[1]:12s} {ratio:.4f}  ({count} launches)")
 ENTRY_POINT = {"deform": "vx_deform_conv_f16", "cols": "vx_bf_deform_cols_f16", "mbconv": "vx_mbconv_dw_pw_f16", "halo": "vx_conv3x3_f16"}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert api().vx_device_count() > 0, "no HIP device visible: the product path has no CPU fallback"
-    L.vx_check(api().vx_set_device(0))
-    t0 = time.time()
-    yield
-    print(f"\n{sum(COUNT.values())} launches compared in {time.time() - t0:.1f} s; largest |got - want| / allowance per entry point and data kind:")
-    for key, ratio in sorted(RATIO.items()):
-        print(f"  {key[0]:24s} {key[1]:12s} {ratio:.4f}  ({COUNT[key]} launches)")
-
-
-@pytest.fixture(autouse=True)
-def _release_buffers():
-    yield
-    release()
-
-
-def _ptr(a):
-    return None if a is None else dev(a).ptr
+_device = device_fixture(REPORT)
+_release_buffers = release_fixture()
 
 
 def launch(entry, a, n):
@@ -54,7 +35,7 @@ def launch(entry, a, n):
         g = L.GemmArgs()
         for k, v in a.items():
             if k in ("A", "W", "bias", "lambda_", "res1", "res2"):
-                v = _ptr(v)
+                v = ptr(v)
             elif k == "A_off":
                 continue
             setattr(g, k, v)
@@ -67,36 +48,19 @@ def launch(entry, a, n):
     if entry == "deform":
         d = L.DeformConvArgs()
         om = dev(a["offset"])
-        d.x, d.w, d.offset, d.scale, d.bias = _ptr(a["x"]), _ptr(a["w"]), om.ptr, _ptr(a["scale"]), _ptr(a["bias"])
-        d.mask = om.ptr + 2 * a["mask_col"] if a["mask_mode"] == 2 else _ptr(a["mask"])
+        d.x, d.w, d.offset, d.scale, d.bias = ptr(a["x"]), ptr(a["w"]), om.ptr, ptr(a["scale"]), ptr(a["bias"])
+        d.mask = om.ptr + 2 * a["mask_col"] if a["mask_mode"] == 2 else ptr(a["mask"])
         for k in ("B", "H", "W", "Cin", "Cout", "k", "pad", "ld_offset", "ld_mask", "mask_mode", "mask_scale", "relu", "ldo"):
             setattr(d, k, a[k])
         d.out = out.ptr + 2 * a["out_off"]
         assert d.out % 8 == 0 and (a["out_off"] == 0 or d.out % 16 == 8)
         L.vx_check(lib.vx_deform_conv_f16(C.byref(d), None))
     elif entry == "cols":
-        L.vx_check(lib.vx_bf_deform_cols_f16(_ptr(a["x"]), _ptr(a["om"]), a["ldom"], out.ptr, a["B"], a["H"], a["W"], a["C"], a["k"], None))
+        L.vx_check(lib.vx_bf_deform_cols_f16(ptr(a["x"]), ptr(a["om"]), a["ldom"], out.ptr, a["B"], a["H"], a["W"], a["C"], a["k"], None))
     else:
-        L.vx_check(lib.vx_mbconv_dw_pw_f16(*(_ptr(a[k]) for k in ("h", "w2", "b2", "w3", "b3", "x")), out.ptr, a["B"], a["H"], a["W"], R.MB_C, R.MB_CO, None))
+        L.vx_check(lib.vx_mbconv_dw_pw_f16(*(ptr(a[k]) for k in ("h", "w2", "b2", "w3", "b3", "x")), out.ptr, a["B"], a["H"], a["W"], R.MB_C, R.MB_CO, None))
     sync()
     return out.to_numpy(np.float16, (n + 8,))[:n]
-
-
-def compare(got, ref, key, what):
-    want, allow, written = ref
-    bits = got.view(np.uint32 if got.dtype == np.float32 else np.uint16)
-    stray = bits[~written] != 0
-    assert not stray.any(), f"{what}: {int(stray.sum())} elements written that the call must leave alone, the first at {int(np.flatnonzero(~written)[np.argmax(stray)])}"
-    assert np.isfinite(got).all(), f"{what}: {int((~np.isfinite(got)).sum())} elements are not finite"
-    err = np.abs(got.astype(np.float64) - want)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = float(np.max(np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))))
-    print(f"{what}: max err {err.max():.3e}, max err / allowance {ratio:.3f}")
-    RATIO[key] = max(RATIO[key], ratio)
-    COUNT[key] += 1
-    worst = int(np.argmax(err - allow))
-    assert (err <= allow).all(), (f"{what}: {int((err > allow).sum())} of {err.size} elements outside the allowance; worst at {worst}: got {got[worst]}, "
-                                  f"want {want[worst]:.6g}, allowance {allow[worst]:.3g}")
 
 
 def check(case):
@@ -104,25 +68,21 @@ def check(case):
     ref = R.evaluate(case["entry"], a, T.guard_of(case, a))
     got = launch(case["entry"], a, ref[0].size)
     head = case["entry"] == "halo" and a["epi"] == G.HEAD_OUT  # the f32 head epilogue has an allowance of its own kind: reported on its own
-    compare(got, ref, (ENTRY_POINT[case["entry"]] + ("/head" if head else ""), case["kind"]), case["id"])
+    REPORT.add((ENTRY_POINT[case["entry"]] + ("/head" if head else ""), case["kind"]), assert_buffer(got, ref, case["id"])["ratio"])
     return a, got
 
 
-def _ids(cases):
-    return [c["id"] for c in cases]
-
-
-@pytest.mark.parametrize("case", T.group("deform"), ids=_ids(T.group("deform")))
+@pytest.mark.parametrize("case", T.group("deform"), ids=ids(T.group("deform")))
 def test_deform_conv(case):
     check(case)
 
 
-@pytest.mark.parametrize("case", T.group("cols"), ids=_ids(T.group("cols")))
+@pytest.mark.parametrize("case", T.group("cols"), ids=ids(T.group("cols")))
 def test_deform_cols(case):
     check(case)
 
 
-@pytest.mark.parametrize("case", T.group("mbconv"), ids=_ids(T.group("mbconv")))
+@pytest.mark.parametrize("case", T.group("mbconv"), ids=ids(T.group("mbconv")))
 def test_mbconv(case):
     a, got = check(case)
     if case["kind"] == "w3-probe":  # output channel n holds 12 + depthwise channel (37 n + 5) % 256 of its pixel (c / 64 plus the pixel's bit), exactly
@@ -130,7 +90,7 @@ def test_mbconv(case):
         np.testing.assert_array_equal(got[:h.size // 4].astype(np.float64).reshape(h.shape[:3] + (R.MB_CO,)), T.W3_PROBE_B2 + h[..., T.w3_probe_column(np.arange(R.MB_CO))])
 
 
-@pytest.mark.parametrize("case", T.group("halo"), ids=_ids(T.group("halo")))
+@pytest.mark.parametrize("case", T.group("halo"), ids=ids(T.group("halo")))
 def test_halo_conv(case):
     check(case)
 
@@ -140,5 +100,4 @@ def test_refusals():
     lib = api()
     scratch = empty(T.REFUSAL_SCRATCH_BYTES)
     assert T.run_refusals(lib, scratch.ptr) == len(T.DEFORM_REFUSALS) + len(T.MBCONV_REFUSALS) + len(T.HALO_REFUSALS) + len(T.COLS_REFUSALS) > 70
-    sync()
-    assert not scratch.to_numpy(np.uint8, (T.REFUSAL_SCRATCH_BYTES,)).any()  # nothing was launched
+    assert_nothing_launched(scratch, T.REFUSAL_SCRATCH_BYTES)

@@ -1,7 +1,7 @@
 """No device: the references of tests/rows_ref.py agree with the CPU oracle and the older numpy references, the tables of tests/rows_cases.py
 cover every dispatch class of every launcher, a float32 numpy emulation of the LayerNorm kernels' arithmetic (two-pass, per-lane partial sums,
 tree reduction) lies inside the allowance for EVERY LayerNorm case in two summation orders, and emulations with one seeded mistake each are
-rejected by the comparison the GPU test uses (rows_ref.violations). No element and no case is exempt anywhere in this file."""
+rejected by the comparison the GPU test uses (buffer_check.violations). No element and no case is exempt anywhere in this file."""
 import re
 from collections import defaultdict
 from pathlib import Path
@@ -13,6 +13,7 @@ import dwconv_ref
 import rows_cases as T
 import rows_ref as R
 import window_ref
+from buffer_check import rejected, violations
 from oracle import oracle
 from visioncpp_amd import _lib as L
 
@@ -353,8 +354,8 @@ def _reject(c, defect=None, order=0):
     guard = T.guard_of(c, a)
     ref = R.evaluate(c["entry"], a, guard)
     got = emulate_ln(c["entry"], a, guard, order, defect) if c["entry"] in LN_GROUPS else emulate_reverse(c["entry"], a, guard, defect)
-    v = R.violations(got, ref)
-    return bool(v["stray"] or v["nonfinite"] or v["outside"]), v
+    v = violations(got, ref, untouched=R.CANARY)
+    return rejected(v), v
 
 
 def test_emulated_layer_norm_is_inside_the_allowance_for_every_case_in_two_orders():
@@ -422,6 +423,15 @@ def test_seeded_defects_are_rejected_by_the_comparison_the_gpu_test_uses():
                 assert (c in rejecting) == (lanes * per > _width(c)), c["id"]
         if defect in ("eps_dropped", "eps_other"):
             assert {c["id"] for c in tried if c["kind"] == "tiny" and _width(c) > 1} <= {c["id"] for c in rejecting}  # (a row of one element is its own mean)
+        if defect == "last_row_into_guard":  # under its own keys: a row of stray stores in the guard; outside are those and the row left at the canary
+            for c in tried:
+                v = _reject(c, defect)[1]
+                assert v["stray"] == _width(c) and v["outside"] == 2 * _width(c) and v["first_stray"] >= v["ratios"].size - T.guard_of(c, T.materialize(c)) and v["nonfinite"] == 0, c["id"]
+        if defect == "eps_dropped":  # a constant row without eps is 0 x inf
+            for c in tried:
+                if c["kind"] == "constant":
+                    v = _reject(c, defect)[1]
+                    assert v["nonfinite"] > 0 and v["stray"] == 0 and v["ratio"] == np.inf, c["id"]
         if defect in ("shift_sign", "merge_parts_by_row", "last_row_into_guard", "pad_rows_zeroed_not_bias", "pad_rows_normalised_not_zeroed"):  # (a zero bias cannot tell the pad rows' two contents apart)
             assert not missed, missed
 

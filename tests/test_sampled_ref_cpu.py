@@ -13,6 +13,7 @@ import deform_ref as D
 import gemm_ref as G
 import sampled_cases as T
 import sampled_ref as R
+from buffer_check import violations
 from visioncpp_amd import _lib as L
 
 F32 = np.float32
@@ -357,13 +358,10 @@ def _reference(c):
 
 
 def _outside(c, corrupt=None):
-    """elements of the emulation outside the allowance, and the largest error / allowance"""
+    """elements of the emulation that buffer_check.violations rejects, and the largest error / allowance"""
     a, want, allow = _reference(c)
-    err = np.abs(EMULATE[c["entry"]](a, corrupt) - want)
-    bad = ~(err <= allow)  # (a NaN is outside)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(allow > 0, err / allow, np.where(err > 0, np.inf, 0.0))
-    return int(bad.sum()), float(np.nanmax(ratio)) if np.isfinite(err).all() else float("inf")
+    v = violations(EMULATE[c["entry"]](a, corrupt), (want, allow, np.ones(want.shape, bool)))  # the GPU test's comparison (a NaN is outside)
+    return v["nonfinite"] + v["outside"], v["ratio"]
 
 
 def test_emulated_arithmetic_is_inside_the_allowance_for_every_case():
