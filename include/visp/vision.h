@@ -483,5 +483,32 @@ inline image_data sam_compute(sam_model& model, box_2d box) {
     int32_t p[4] = {box.top_left[0], box.top_left[1], box.bottom_right[0], box.bottom_right[1]};
     return detail::sam_prompt(model, p, 4);
 }
+// not in the reference's header: many prompts on one sam_encode in one batched pass -> one alpha_u8 mask per prompt, in order
+namespace detail {
+inline std::vector<image_data> sam_prompts(sam_model& model, std::vector<int32_t> const& prompts, int32_t n_args) {
+    const int32_t n = int32_t(prompts.size() / 4);
+    int32_t w = 0, h = 0;
+    check(visp_sam_image_extent(model.handle, &w, &h));
+    std::vector<int32_t> counts(size_t(n), n_args);
+    std::vector<uint8_t> masks(size_t(n) * size_t(w) * size_t(h));
+    check(visp_sam_compute_batch_host(model.handle, prompts.data(), counts.data(), n, masks.data(), nullptr, nullptr));
+    std::vector<image_data> out;
+    for (int32_t i = 0; i < n; ++i) {
+        out.push_back(image_alloc({w, h}, image_format::alpha_u8));
+        std::memcpy(out.back().data.get(), masks.data() + size_t(i) * size_t(w) * size_t(h), size_t(w) * size_t(h));
+    }
+    return out;
+}
+} // namespace detail
+inline std::vector<image_data> sam_compute_batch(sam_model& model, span<i32x2 const> points) {
+    std::vector<int32_t> p;
+    for (i32x2 const& pt : points) p.insert(p.end(), {pt[0], pt[1], 0, 0});
+    return detail::sam_prompts(model, p, 2);
+}
+inline std::vector<image_data> sam_compute_batch(sam_model& model, span<box_2d const> boxes) {
+    std::vector<int32_t> p;
+    for (box_2d const& b : boxes) p.insert(p.end(), {b.top_left[0], b.top_left[1], b.bottom_right[0], b.bottom_right[1]});
+    return detail::sam_prompts(model, p, 4);
+}
 
 } // namespace visp

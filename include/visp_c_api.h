@@ -261,6 +261,26 @@ VISP_API int32_t visp_sam_read_embedding(visp_model* m, float* host_out, int64_t
 VISP_API int32_t visp_sam_compute(visp_model* m, int32_t const* prompt, int32_t n_prompt, visp_image_view* out_image, visp_image_data** out_data);
 /* test hook: mask logits [4][256][256] (f16-rounded; kept only while captures are enabled) and iou predictions [4] of the last sam_compute */
 VISP_API int32_t visp_sam_read_masks(visp_model* m, float* masks, int64_t capacity, float iou[4]);
+/* Many prompts on the embedding of the last visp_sam_encode in one batched pass (the prompt index folded into the rows of the decoder's launches).
+ * prompts: host i32 [n][4] in pixels of the encoded image, a point uses entries 0 and 1, a box all four; n_args: host i32 [n], each 2 or 4 (points and
+ * boxes may be mixed). Outputs are DEVICE pointers: masks_u8 [n][h][w] (0 / 255, h x w = the encoded image's extent), iou f32 [n][4] and chosen i32 [n]
+ * (best of the first three masks by predicted iou, vision.cpp:80-82); iou and chosen may be NULL. The prompts run in chunks (visp_sam_set_prompt_chunk);
+ * nothing in the call waits for the device, except that the first call (and one with a larger chunk or more prompts) allocates the workspace, and
+ * that stream = NULL means the device's stream, synchronised before returning. With captures enabled the call synchronises per chunk.
+ * All batch calls on one model share its workspace and its pinned token buffer: they must be ordered on ONE stream. A call on another stream while an
+ * earlier one may still run is the caller's to order (an event between the streams); the library does not. */
+VISP_API int32_t visp_sam_compute_batch_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, void* masks_u8_dev, void* iou_dev,
+                                               void* chosen_dev, void* stream);
+/* the same with host outputs (masks u8 [n][h][w], iou f32 [n][4], chosen i32 [n]; iou and chosen may be NULL); blocks */
+VISP_API int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, uint8_t* masks_u8, float* iou,
+                                             int32_t* chosen);
+/* extent in pixels of the image given to the last visp_sam_encode: what sizes the masks of the calls above */
+VISP_API int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height);
+/* prompts per internal chunk of the batch calls: 1 .. 256, default 64. It sizes the workspace: about 27 MB per prompt in flight. */
+VISP_API int32_t visp_sam_set_prompt_chunk(visp_model* m, int32_t n);
+/* test hook, the batch twin of visp_sam_read_masks: with captures enabled, the f16-rounded logit planes [n][4][256][256] and (iou nullable) the iou
+ * predictions [n][4] of the last batch call; capacity in floats of `logits` */
+VISP_API int32_t visp_sam_read_masks_batch(visp_model* m, float* logits, int64_t capacity, float* iou);
 /* rgb: u8 [B, 1024, 1024, 3] already at the model extent -> out f32 [B, 64, 64, 256]; device pointers;
  * stream = hipStream_t or NULL (NULL: the device's stream, synchronised before returning) */
 VISP_API int32_t visp_sam_encode_batch_device(visp_model* m, void const* rgb, int32_t batch, void* out, void* stream);

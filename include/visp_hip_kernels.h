@@ -352,6 +352,19 @@ VX_API int vx_sincos_f16(int mode, const void* x, void* y, int64_t n, void* stre
 /* position_embedding_random (mobile-sam.cpp:238-248): coords f32 [n_points][2] (x, y), gauss f32 [F][2] (g0[f], g1[f]) -> out f16 [n_points][2 F] =
  * sin | cos of 2 pi (x g0 + y g1); product, scale and argument reduction in f32 */
 VX_API int vx_fourier_features_f32(const float* coords, const float* gauss, void* out, int64_t n_points, int F, void* stream);
+/* ---- batched MobileSAM decode, many prompts per encoded image (kernels_samprompts.hip) ----
+ * iou_prediction_head (mobile-sam.cpp:476-481) on one f16 token per prompt (prompt p at tokens + p * row_stride elements): three linears K0 -> N0 -> N1 -> N2 with
+ * ReLU behind the first two, f32 weights [n][k] and biases on the device, f32 sums. iou f32 [P][N2]; chosen i32 [P] (nullable) = argmax of the first three
+ * predictions, the first index on ties (std::max_element, vision.cpp:80-82). Widths <= 1024, 3 <= N2 <= 64. */
+VX_API int vx_sam_iou_head_f32(const void* tokens, int64_t row_stride, int P, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                               const float* b2, int K0, int N0, int N1, int N2, float* iou, int32_t* chosen, void* stream);
+/* sam_process_mask (mobile-sam.cpp:556-583) for P prompts in two launches with the arithmetic of vx_sam_interpolate, bit for bit. Prompt p reads the f16 logit
+ * plane chosen[p] (clamped to 0 .. n_planes - 1): element (x, y) of plane c at planes[p * prompt_stride + c * plane_stride + (y * mask_size + x) * step].
+ * Step 1: mask_size^2 -> scaled f32 [P][image_size^2]; step 2: the top-left sw x sh of that -> out u8 [P][dh][dw], 0 / 255 by the sign. */
+VX_API int vx_sam_process_masks(const void* planes, int64_t prompt_stride, int64_t plane_stride, int step, int mask_size, int n_planes, const int32_t* chosen,
+                                float* scaled, int image_size, int sw, int sh, uint8_t* out, int dw, int dh, int P, void* stream);
+/* dst f16 [B][n] = B copies of src f16 [n]; n a multiple of 8, both 16-byte aligned */
+VX_API int vx_sam_tile_rows_f16(const void* src, int64_t n, void* dst, int B, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -775,6 +775,40 @@ int32_t visp_sam_read_masks(visp_model* m, float* masks, int64_t capacity, float
     });
 }
 
+int32_t visp_sam_compute_batch_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, void* masks_u8_dev, void* iou_dev, void* chosen_dev,
+                                      void* stream) {
+    return handle_errors([&]() { sam_compute_batch_device(as_sam(m), prompts, n_args, n, masks_u8_dev, iou_dev, chosen_dev, stream); });
+}
+
+int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, uint8_t* masks_u8, float* iou, int32_t* chosen) {
+    return handle_errors([&]() { sam_compute_batch_host(as_sam(m), prompts, n_args, n, masks_u8, iou, chosen); });
+}
+
+int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height) {
+    return handle_errors([&]() {
+        sam_model& sm = as_sam(m);
+        if (!width || !height) throw except("sam: null argument");
+        if (!sm.embed.ptr || sm.image_extent[0] <= 0) throw except("Missing image embeds, call sam_encode() first");
+        *width = sm.image_extent[0];
+        *height = sm.image_extent[1];
+    });
+}
+
+int32_t visp_sam_set_prompt_chunk(visp_model* m, int32_t n) {
+    return handle_errors([&]() { sam_set_prompt_chunk(as_sam(m), n); });
+}
+
+int32_t visp_sam_read_masks_batch(visp_model* m, float* logits, int64_t capacity, float* iou) {
+    return handle_errors([&]() {
+        sam_model& sm = as_sam(m);
+        if (!logits) throw except("sam: null argument");
+        if (sm.last_batch_masks.empty()) throw except("sam: no mask logits kept: enable captures, then call sam_compute_batch()");
+        if (capacity < (int64_t)sm.last_batch_masks.size()) throw except("sam: mask buffer too small (%lld < %zu)", (long long)capacity, sm.last_batch_masks.size());
+        memcpy(logits, sm.last_batch_masks.data(), sm.last_batch_masks.size() * sizeof(float));
+        if (iou) memcpy(iou, sm.last_batch_iou.data(), sm.last_batch_iou.size() * sizeof(float));
+    });
+}
+
 int32_t visp_sam_encode_batch_device(visp_model* m, void const* rgb, int32_t batch, void* out, void* stream) {
     return handle_errors([&]() { sam_encode_batch_device(as_sam(m), rgb, batch, out, stream); });
 }

@@ -173,8 +173,35 @@ void sam_weights_ready(sam_model& m) {
             D.iou_b[l].assign((size_t)g.n_real, 0.0f);
             if (g.b != SIZE_MAX) VX(vx_memcpy_d2h(D.iou_b[l].data(), wa + g.b, (size_t)g.n_real * 4, s));
         }
+        VX(vx_stream_sync(s));
+        // the same f32 values on the device for vx_sam_iou_head_f32 (the batched path ranks the masks there): [w0 | b0 | w1 | b1 | w2 | b2]
+        workspace_layout lay;
+        for (int l = 0; l < 3; ++l) {
+            m.iou_head_off[2 * l] = lay.take(D.iou_w[l].size() * 4);
+            m.iou_head_off[2 * l + 1] = lay.take(D.iou_b[l].size() * 4);
+        }
+        m.iou_head_dev = device_buffer(lay.top);
+        uint8_t* base = static_cast<uint8_t*>(m.iou_head_dev.ptr);
+        for (int l = 0; l < 3; ++l) {
+            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l], D.iou_w[l].data(), D.iou_w[l].size() * 4, s));
+            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l + 1], D.iou_b[l].data(), D.iou_b[l].size() * 4, s));
+        }
+        VX(vx_stream_sync(s));
     }
     m.weights_uploaded = true;
+}
+
+sam_model::~sam_model() {
+    if (!prompt_tokens_host && !prompt_tokens_event) return;
+    try {
+        device_turn turn(*backend);
+        if (prompt_tokens_event) {
+            vx_event_sync(prompt_tokens_event);
+            vx_event_destroy(prompt_tokens_event);
+        }
+        if (prompt_tokens_host) vx_free_host(prompt_tokens_host);
+    } catch (...) {
+    }
 }
 
 // e4m3 images of the stage MLPs' weights: read back from the packed f16 arena (what is on every rank), quantised on the host per output channel
@@ -424,26 +451,19 @@ float sam_transform_coord(int p, float scale, int image_size) { // mobile-sam.cp
     return 2.f * center_normalized - 1.f;
 }
 
-} // namespace
+constexpr int kSamTokens = 7; // [iou | 4 mask tokens | 2 prompt points]
 
-image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
+// prompt encoder on the host (two points of 256 sin/cos values; mobile-sam.cpp:219-286): the decoder's token rows of one prompt, f16 [7][dim].
+// Both sam_compute and the batched path call it: one prompt gives the same bits on either.
+void sam_prompt_tokens(sam_model const& m, int const* prompt, int n_prompt, uint16_t* out) {
     samdec_weights const& D = m.dec;
-    if (n_prompt != 2 && n_prompt != 4) throw except("sam: bad number of arguments (%d), must be 2 or 4", n_prompt);
-    if (!D.present) throw except("sam: this model file holds no prompt encoder / mask decoder (dec.* tensors)");
-    if (D.gaussian.empty()) throw except("sam: the decoder's host tables were not read (model loaded without data)");
-    if (!m.embed.ptr || m.image_extent[0] <= 0) throw except("Missing image embeds, call sam_encode() first");
-    device_turn turn(*m.backend);
-    void* s = m.backend->stream;
-    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = 7, F = dim / 2;
-    const int image_size = m.params.img_size, mask_size = 4 * res;
+    const int dim = D.dim, F = dim / 2, image_size = m.params.img_size;
     const bool is_box = n_prompt == 4;
-
-    // ---- prompt encoder on the host (two points of 256 sin/cos values; mobile-sam.cpp:219-286)
     const float scale = float(image_size) / float(std::max(m.image_extent[0], m.image_extent[1]));
     float coords[4] = {sam_transform_coord(prompt[0], scale, image_size), sam_transform_coord(prompt[1], scale, image_size), 0.f, 0.f};
     if (is_box) { coords[2] = sam_transform_coord(prompt[2], scale, image_size); coords[3] = sam_transform_coord(prompt[3], scale, image_size); }
     std::vector<float> tokens(D.output_tokens); // [iou | 4 mask tokens]
-    tokens.resize((size_t)Nt * dim);
+    tokens.resize((size_t)kSamTokens * dim);
     for (int i = 0; i < 2; ++i) {
         float* t = tokens.data() + (size_t)(5 + i) * dim;
         for (int f = 0; f < F; ++f) {
@@ -456,8 +476,29 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
         else if (i == 0) for (int c = 0; c < dim; ++c) t[c] += D.point_embed[1][c];
         else for (int c = 0; c < dim; ++c) t[c] = D.not_a_point[c];
     }
+    for (size_t i = 0; i < tokens.size(); ++i) out[i] = f32_to_f16(tokens[i]);
+}
+
+void sam_require_decoder(sam_model const& m) {
+    samdec_weights const& D = m.dec;
+    if (!D.present) throw except("sam: this model file holds no prompt encoder / mask decoder (dec.* tensors)");
+    if (D.gaussian.empty()) throw except("sam: the decoder's host tables were not read (model loaded without data)");
+    if (!m.embed.ptr || m.image_extent[0] <= 0) throw except("Missing image embeds, call sam_encode() first");
+}
+
+} // namespace
+
+image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
+    samdec_weights const& D = m.dec;
+    if (n_prompt != 2 && n_prompt != 4) throw except("sam: bad number of arguments (%d), must be 2 or 4", n_prompt);
+    sam_require_decoder(m);
+    device_turn turn(*m.backend);
+    void* s = m.backend->stream;
+    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = kSamTokens;
+    const int image_size = m.params.img_size, mask_size = 4 * res;
+
     std::vector<uint16_t> tokens_h((size_t)8 * dim, 0);
-    for (size_t i = 0; i < tokens.size(); ++i) tokens_h[i] = f32_to_f16(tokens[i]);
+    sam_prompt_tokens(m, prompt, n_prompt, tokens_h.data());
 
     // ---- scratch (f16 elements)
     const size_t big = (size_t)Nk * dim, tok = (size_t)8 * dim;
@@ -607,6 +648,237 @@ image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
     VX(vx_stream_sync(s));
     m.timing = timing;
     return out;
+}
+
+// ---- many prompts per embedding: the decoder above with the prompt index folded into the rows of its launches ---------------------
+
+void sam_set_prompt_chunk(sam_model& m, int n) {
+    if (n < 1 || n > 256) throw except("sam: prompt chunk %d is outside 1 .. 256", n);
+    m.prompt_chunk = n;
+}
+
+void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream) {
+    samdec_weights const& D = m.dec;
+    if (!prompts || !n_args || !masks_u8_dev) throw except("sam: null argument");
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
+    for (int i = 0; i < n; ++i)
+        if (n_args[i] != 2 && n_args[i] != 4) throw except("sam: bad number of arguments (%d) for prompt %d, must be 2 or 4", n_args[i], i);
+    sam_require_decoder(m);
+    if (!m.iou_head_dev.ptr) throw except("sam: weights have not been uploaded (load_no_upload without weights_ready)");
+    device_turn turn(*m.backend);
+    void* s = stream ? stream : m.backend->stream;
+    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = kSamTokens;
+    const int image_size = m.params.img_size, mask_size = 4 * res;
+    const int64_t n_px = (int64_t)mask_size * mask_size;
+    const int Bmax = std::min(n, m.prompt_chunk);
+    sam_twoway_weights const& L0 = D.layers.at(0);
+    const int ci = L0.t2i.q.n_real, cs = L0.self_attn.q.n_real; // widths inside the cross and the self attention
+    const int hd_c = ci / H, hd_s = cs / H;
+    auto built = [](int hd) { return hd == 16 || hd == 32 || hd == 64; };
+    if (!built(hd_c) || !built(hd_s)) throw except("sam: the batched decoder is built for attention head widths 16, 32 and 64 (got %d and %d)", hd_s, hd_c);
+    for (sam_twoway_weights const& L : D.layers)
+        if (L.t2i.q.n_real != ci || L.i2t.q.n_real != ci || L.self_attn.q.n_real != cs) throw except("sam: the decoder layers differ in their attention widths");
+    if (D.final_attn.q.n_real != ci) throw except("sam: the final attention's width differs from the layers'");
+    int tok_w = std::max({dim, cs, ci}), hyp_w = 0, mlp_w = 0;
+    for (sam_twoway_weights const& L : D.layers) mlp_w = std::max(mlp_w, L.lin1.n_real);
+    for (int i = 0; i < 4; ++i) hyp_w = std::max({hyp_w, D.hyper[i][0].n_real, D.hyper[i][1].n_real});
+
+    // ---- the prompt tokens of the whole call, encoded on the host into pinned memory and uploaded once
+    const size_t tok_bytes = (size_t)n * Nt * dim * 2;
+    if (m.prompt_tokens_event) VX(vx_event_sync(m.prompt_tokens_event)); // the previous call's upload has read them (long done in practice)
+    else VX(vx_event_create(&m.prompt_tokens_event));
+    if (m.prompt_tokens_bytes < tok_bytes) {
+        if (m.prompt_tokens_host) VX(vx_free_host(m.prompt_tokens_host));
+        m.prompt_tokens_host = nullptr;
+        m.prompt_tokens_bytes = 0;
+        VX(vx_malloc_host(&m.prompt_tokens_host, tok_bytes));
+        m.prompt_tokens_bytes = tok_bytes;
+    }
+    uint16_t* tok_host = static_cast<uint16_t*>(m.prompt_tokens_host);
+    for (int i = 0; i < n; ++i) sam_prompt_tokens(m, prompts + (size_t)i * 4, n_args[i], tok_host + (size_t)i * Nt * dim);
+
+    // ---- workspace: what every prompt shares, then the buffers of one chunk of Bmax prompts (f16 unless said otherwise)
+    const size_t R = (size_t)Bmax * Nt, big = (size_t)Bmax * Nk;
+    workspace_layout layout;
+    auto take = [&](size_t elems) { return layout.take(elems * 2, 256); };
+    const size_t o_tok = take((size_t)n * Nt * dim);
+    const size_t o_K0 = take((size_t)Nk * dim), o_k10 = take((size_t)Nk * dim), o_pk0 = take((size_t)Nk * ci), o_pv0 = take((size_t)Nk * ci), o_pq0 = take((size_t)Nk * ci);
+    const size_t o_Q = take(R * dim), o_t1 = take(R * dim), o_t2 = take(R * dim), o_h = take(R * mlp_w + 64);
+    const size_t o_tq = take(R * tok_w), o_tk = take(R * tok_w), o_tv = take(R * tok_w), o_ta = take(R * tok_w);
+    const size_t o_K = take(big * dim), o_k1 = take(big * dim), o_k2 = take(big * dim);
+    const size_t o_pq = take(big * ci), o_pk = take(big * ci), o_pv = take(big * ci), o_ao = take(big * ci);
+    const size_t o_u1 = take(4 * big * D.up_c1), o_u1n = take(4 * big * D.up_c1), o_u2p = take(16 * big * D.up_c2), o_u2 = take(16 * big * D.up_c2 + 64);
+    const size_t o_ha = take((size_t)Bmax * hyp_w + 64), o_hb = take((size_t)Bmax * hyp_w + 64), o_hy = take((size_t)Bmax * 4 * D.up_c2 + 64);
+    const size_t o_mask = take((size_t)Bmax * 4 * n_px);
+    const size_t o_iou = layout.take((size_t)Bmax * 4 * 4, 256), o_chosen = layout.take((size_t)Bmax * 4, 256);
+    const size_t o_scaled = layout.take((size_t)Bmax * image_size * image_size * 4, 256);
+    const size_t part_bytes = std::max(vx_attention_cross_partial_bytes(Bmax, H, Nt, Nk, hd_c), vx_attention_cross_partial_bytes(1, H, (int)R, Nk, hd_c));
+    const size_t o_part = layout.take(part_bytes, 256);
+    grow(m.batch_ws, layout.top, {m.backend->stream, s}, s); // zero-filled: GEMM rows are read up to K padded to 64, stale bytes must be finite
+    uint8_t* base = static_cast<uint8_t*>(m.batch_ws.ptr);
+    auto P = [&](size_t off) { return static_cast<void*>(base + off); };
+    void *tok_all = P(o_tok), *K0 = P(o_K0), *k10 = P(o_k10), *pk0 = P(o_pk0), *pv0 = P(o_pv0), *pq0 = P(o_pq0);
+    void *Q = P(o_Q), *t1 = P(o_t1), *t2 = P(o_t2), *hbuf = P(o_h), *tq = P(o_tq), *tk = P(o_tk), *tv = P(o_tv), *ta = P(o_ta);
+    void *K = P(o_K), *k1 = P(o_k1), *k2 = P(o_k2), *pq = P(o_pq), *pk = P(o_pk), *pv = P(o_pv), *ao = P(o_ao);
+    void *u1 = P(o_u1), *u1n = P(o_u1n), *u2p = P(o_u2p), *u2 = P(o_u2), *ha = P(o_ha), *hb = P(o_hb), *hy = P(o_hy), *masks_d = P(o_mask);
+    void *iou_ws = P(o_iou), *chosen_ws = P(o_chosen), *scaled = P(o_scaled), *part = part_bytes ? P(o_part) : nullptr;
+
+    tv_exec ex(m, s, m.weight_arena.ptr);
+    const bool timing = m.timing;
+    m.timing = false; // the per-group table belongs to the encoder
+    struct restore_timing { sam_model& m; bool v; ~restore_timing() { m.timing = v; } } restore{m, timing};
+    const uint8_t* wa = ex.wa;
+    VX(vx_memcpy_h2d_async(tok_all, tok_host, tok_bytes, s));
+    VX(vx_event_record(m.prompt_tokens_event, s));
+
+    auto linear = [&](packed_gemm const& g, const void* A, long M, void* out, int epi = VX_EPI_F16, const void* res1 = nullptr) {
+        ex.gemm(g, A, M, g.k_real, out, epi, res1, "decoder");
+    };
+    auto norm = [&](packed_vec const& w, packed_vec const& b, const void* x, void* y, long rows, int C) {
+        VX(vx_layernorm_f16(x, ex.vec(w), ex.vec(b), y, rows, C, 1e-5f, 0, 0, 0, s));
+    };
+    auto add = [&](const void* a, const void* b, void* y, long n_el) { VX(vx_add_rows_f16(a, 0, b, n_el, y, n_el, s)); };
+    auto cross = [&](const void* q, const void* k, const void* v, void* out, int Bt, int Tq, int Tk, int hd) {
+        VX(vx_attention_cross_f16(q, k, v, out, part, part_bytes, Bt, H, Tq, Tk, hd, 1.0f / std::sqrt((float)hd), s));
+    };
+    const void* KPE = wa + D.dense_pe.off;
+
+    // ---- layer 0's image side is the same for every prompt (the dense prompt is no_mask_embed for all): once per call
+    // src = image_embeddings + dense prompt (mobile-sam.cpp:437-440), keys + key_pe, t2i's k_proj / v_proj and i2t's q_proj of them
+    VX(vx_add_rows_f16(m.embed.ptr, 1, wa + D.no_mask.off, dim, K0, (int64_t)Nk * dim, s));
+    add(K0, KPE, k10, (long)Nk * dim);
+    linear(L0.t2i.k, k10, Nk, pk0);
+    linear(L0.t2i.v, K0, Nk, pv0);
+    linear(L0.i2t.q, k10, Nk, pq0);
+
+    const i32x2 target = m.image_extent;
+    const float up = float(image_size) / float(std::max(target[0], target[1]));
+    const int sw = int(target[0] * up + 0.5f), sh = int(target[1] * up + 0.5f);
+    const size_t out_px = (size_t)target[0] * target[1];
+    if (m.captures) {
+        m.last_batch_masks.assign((size_t)n * 4 * n_px, 0.0f);
+        m.last_batch_iou.assign((size_t)n * 4, 0.0f);
+    } else {
+        m.last_batch_masks.clear();
+        m.last_batch_iou.clear();
+    }
+
+    for (int p0 = 0; p0 < n; p0 += Bmax) {
+        const int B = std::min(Bmax, n - p0); // every launch below covers rows of these B prompts only: a short last chunk reads no rows behind them
+        const long Rt = (long)B * Nt, Mi = (long)B * Nk;
+        const void* T = static_cast<const uint8_t*>(tok_all) + (size_t)p0 * Nt * dim * 2;
+        VX(vx_memcpy_d2d(Q, T, (size_t)Rt * dim * 2, s));
+        // token-side attention: B prompts x 7 queries; the image side is [B][Nk] rows, or the shared layer-0 operands with all 7 B queries in one batch
+        auto token_attention = [&](sam_attn_weights const& w, const void* q, const void* k_img, const void* v_img, bool shared, const void* res1) {
+            linear(w.q, q, Rt, tq);
+            if (shared) cross(tq, pk0, pv0, ta, 1, (int)Rt, Nk, hd_c); // queries are independent in a softmax
+            else {
+                linear(w.k, k_img, Mi, pk);
+                linear(w.v, v_img, Mi, pv);
+                cross(tq, pk, pv, ta, B, Nt, Nk, hd_c);
+            }
+            linear(w.o, ta, Rt, t2, VX_EPI_F16_ADD, res1);
+        };
+        for (size_t li = 0; li < D.layers.size(); ++li) { // two_way_attention_block (mobile-sam.cpp:322-364)
+            sam_twoway_weights const& L = D.layers[li];
+            const void* sq = Q; // skip_first_layer_pe: queries = self_attn(queries)
+            if (li > 0) { add(Q, T, t1, Rt * dim); sq = t1; }
+            linear(L.self_attn.q, sq, Rt, tq);
+            linear(L.self_attn.k, sq, Rt, tk);
+            linear(L.self_attn.v, Q, Rt, tv);
+            cross(tq, tk, tv, ta, B, Nt, Nt, hd_s);
+            linear(L.self_attn.o, ta, Rt, t2, li > 0 ? VX_EPI_F16_ADD : VX_EPI_F16, li > 0 ? Q : nullptr);
+            norm(L.norm_w[0], L.norm_b[0], t2, Q, Rt, dim);
+            add(Q, T, t1, Rt * dim); // tokens attending to the image embedding
+            if (li > 0) VX(vx_add_rows_f16(K, 0, KPE, (int64_t)Nk * dim, k1, (int64_t)Mi * dim, s));
+            token_attention(L.t2i, t1, k1, K, li == 0, Q);
+            norm(L.norm_w[1], L.norm_b[1], t2, Q, Rt, dim);
+            linear(L.lin1, Q, Rt, hbuf, VX_EPI_F16_RELU); // mlp_block
+            linear(L.lin2, hbuf, Rt, t2, VX_EPI_F16_ADD, Q);
+            norm(L.norm_w[2], L.norm_b[2], t2, Q, Rt, dim);
+            add(Q, T, t1, Rt * dim); // image embedding attending to the tokens (k1 = keys + key_pe from above)
+            if (li == 0) { // the shared rows laid out per prompt: from here on the keys differ
+                VX(vx_sam_tile_rows_f16(pq0, (int64_t)Nk * ci, pq, B, s));
+                VX(vx_sam_tile_rows_f16(K0, (int64_t)Nk * dim, K, B, s));
+            } else {
+                linear(L.i2t.q, k1, Mi, pq);
+            }
+            linear(L.i2t.k, t1, Rt, tk);
+            linear(L.i2t.v, Q, Rt, tv);
+            cross(pq, tk, tv, ao, B, Nk, Nt, hd_c);
+            linear(L.i2t.o, ao, Mi, k2, VX_EPI_F16_ADD, K);
+            norm(L.norm_w[3], L.norm_b[3], k2, K, Mi, dim);
+        }
+        add(Q, T, t1, Rt * dim); // final attention from the points to the image (mobile-sam.cpp:386-392)
+        VX(vx_add_rows_f16(K, 0, KPE, (int64_t)Nk * dim, k1, (int64_t)Mi * dim, s));
+        token_attention(D.final_attn, t1, k1, K, false, Q);
+        norm(D.final_norm_w, D.final_norm_b, t2, Q, Rt, dim);
+
+        // upscale_outputs (mobile-sam.cpp:396-404): convT k2 s2 -> LayerNorm -> GELU -> convT k2 s2 -> GELU, the prompt as the maps' batch
+        auto conv_transpose = [&](packed_gemm const& g, const void* x, int hw, int cin, int cout, void* out) {
+            vx_gemm_args a = gemm_args(g, wa);
+            a.A = x; a.lda = cin;
+            a.M = B * hw * hw;
+            a.epi = VX_EPI_PIXSHUF; a.out = out; a.ldo = cout;
+            a.ps_s = 2; a.ps_Cout = cout; a.ps_H = hw; a.ps_W = hw;
+            VX(vx_gemm_f16(&a, s));
+        };
+        conv_transpose(D.up0, K, res, dim, D.up_c1, u1);
+        norm(D.up_norm_w, D.up_norm_b, u1, u1n, 4 * Mi, D.up_c1);
+        VX(vx_add_gelu_f16(u1n, nullptr, u1, (int64_t)4 * Mi * D.up_c1, s));
+        conv_transpose(D.up3, u1, 2 * res, D.up_c1, D.up_c2, u2p);
+        VX(vx_add_gelu_f16(u2p, nullptr, u2, (int64_t)16 * Mi * D.up_c2, s));
+
+        // hypernetwork MLPs: mask token i of every prompt is one row of an M = B product -> hyper_in [B][4][up_c2]
+        for (int i = 0; i < 4; ++i) {
+            const uint8_t* tok_i = static_cast<const uint8_t*>(Q) + (size_t)(1 + i) * dim * 2;
+            ex.gemm(D.hyper[i][0], tok_i, B, Nt * dim, ha, VX_EPI_F16_RELU, nullptr, "decoder");
+            linear(D.hyper[i][1], ha, B, hb, VX_EPI_F16_RELU);
+            vx_gemm_args a = gemm_args(D.hyper[i][2], wa);
+            a.A = hb; a.lda = D.hyper[i][2].k_real; a.M = B;
+            a.epi = VX_EPI_F16; a.out = static_cast<uint8_t*>(hy) + (size_t)i * D.up_c2 * 2; a.ldo = 4 * D.up_c2;
+            VX(vx_gemm_f16(&a, s));
+        }
+        // masks[b][i][pixel] = <upscaled[b][pixel], hyper_in[b][i]> (mobile-sam.cpp:472-473): four planes of 16 Nk logits per prompt
+        VX(vx_mul_mat_f16(u2, hy, masks_d, 16 * (int64_t)Nk, 4, D.up_c2, B, B, s));
+        // iou prediction head on the iou token (row 0 of each prompt's seven) in f32, and the choice among the first three (vision.cpp:80-82)
+        float* iou_out = iou_dev ? static_cast<float*>(iou_dev) + (size_t)p0 * 4 : static_cast<float*>(iou_ws);
+        int32_t* chosen_out = chosen_dev ? static_cast<int32_t*>(chosen_dev) + p0 : static_cast<int32_t*>(chosen_ws);
+        const uint8_t* ih = static_cast<const uint8_t*>(m.iou_head_dev.ptr);
+        auto ihp = [&](int i) { return reinterpret_cast<const float*>(ih + m.iou_head_off[i]); };
+        VX(vx_sam_iou_head_f32(Q, (int64_t)Nt * dim, B, ihp(0), ihp(1), ihp(2), ihp(3), ihp(4), ihp(5), D.iou_head[0].k_real, D.iou_head[0].n_real, D.iou_head[1].n_real,
+                               D.iou_head[2].n_real, iou_out, chosen_out, s));
+        // sam_process_mask (mobile-sam.cpp:556-583) on each prompt's chosen plane
+        VX(vx_sam_process_masks(masks_d, 4 * n_px, n_px, 1, mask_size, 4, chosen_out, static_cast<float*>(scaled), image_size, sw, sh,
+                                static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, target[0], target[1], B, s));
+        if (m.captures) { // test hook: the four logit planes (f16-rounded) and the iou predictions of every prompt
+            std::vector<uint16_t> mh((size_t)B * 4 * n_px);
+            VX(vx_memcpy_d2h(mh.data(), masks_d, mh.size() * 2, s));
+            VX(vx_memcpy_d2h(m.last_batch_iou.data() + (size_t)p0 * 4, iou_out, (size_t)B * 16, s));
+            VX(vx_stream_sync(s));
+            float* dst = m.last_batch_masks.data() + (size_t)p0 * 4 * n_px;
+            for (size_t i = 0; i < mh.size(); ++i) dst[i] = f16_to_f32(mh[i]);
+        }
+    }
+    if (!stream) VX(vx_stream_sync(s));
+}
+
+void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen) {
+    if (!prompts || !n_args || !masks_u8) throw except("sam: null argument");
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
+    sam_require_decoder(m);
+    device_turn turn(*m.backend);
+    void* s = m.backend->stream;
+    const size_t mask_bytes = (size_t)n * m.image_extent[0] * m.image_extent[1];
+    workspace_layout lay;
+    const size_t o_m = lay.take(mask_bytes), o_i = lay.take((size_t)n * 16), o_c = lay.take((size_t)n * 4);
+    device_buffer out(lay.top);
+    uint8_t* base = static_cast<uint8_t*>(out.ptr);
+    sam_compute_batch_device(m, prompts, n_args, n, base + o_m, base + o_i, base + o_c, s);
+    VX(vx_memcpy_d2h(masks_u8, base + o_m, mask_bytes, s));
+    if (iou) VX(vx_memcpy_d2h(iou, base + o_i, (size_t)n * 16, s));
+    if (chosen) VX(vx_memcpy_d2h(chosen, base + o_c, (size_t)n * 4, s));
+    VX(vx_stream_sync(s));
 }
 
 } // namespace visp

@@ -84,6 +84,17 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // quantised per token on the way in. The decision on accuracy stands (tests/test_fp8_decision.py: mask IoU below the bar); this is the measured form of it.
     bool fp8_mlp = false;
     device_buffer fp8_arena, fp8_ws;
+    // many prompts per embedding (sam_compute_batch_device): a workspace of its own, sized for one chunk of prompts, so that dec_ws and with it
+    // the single-prompt path stay as they are
+    int prompt_chunk = 64;
+    device_buffer batch_ws;
+    device_buffer iou_head_dev;            // f32 [w0 | b0 | w1 | b1 | w2 | b2] of dec.iou_w / iou_b, uploaded by sam_weights_ready
+    size_t iou_head_off[6] = {0, 0, 0, 0, 0, 0}; // byte offsets into it
+    void* prompt_tokens_host = nullptr;    // pinned: the prompt tokens of one call, f16 [n][7][dim]
+    size_t prompt_tokens_bytes = 0;
+    void* prompt_tokens_event = nullptr;   // recorded behind their upload: the next call waits for it before it overwrites them
+    std::vector<float> last_batch_masks, last_batch_iou; // captures: [n][4][mask_size^2] logits (f16-rounded) and [n][4] of the last batch call
+    ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
 
@@ -98,5 +109,11 @@ void sam_encode(sam_model&, image_view image);
 // reference API (vision.cpp:54-92): point (n = 2) or box (n = 4) in pixels of the image given to sam_encode -> alpha_u8 mask
 // at that image's extent (best of the first three masks by predicted iou)
 image_data sam_compute(sam_model&, int const* prompt, int n);
+// n prompts on the embedding of the last sam_encode in one batched pass. prompts host [n][4], n_args host [n] (2 = point, 4 = box); device outputs
+// masks u8 [n][h][w] at the encoded image's extent, iou f32 [n][4], chosen i32 [n] (the last two nullable). Runs in chunks of m.prompt_chunk prompts;
+// no host synchronisation (stream == nullptr: the device's stream, synchronised at the end; captures: synchronised per chunk).
+void sam_compute_batch_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream);
+void sam_compute_batch_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen);
+void sam_set_prompt_chunk(sam_model&, int n); // 1 .. 256
 
 } // namespace visp

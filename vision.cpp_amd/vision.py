@@ -305,6 +305,53 @@ class Model:
         check(self._api.visp_sam_read_masks(self._handle, masks.ctypes.data, masks.size, iou))
         return masks, np.array(list(iou), np.float32)
 
+    # ---- many prompts per sam_encode in one batched pass
+    @staticmethod
+    def _sam_prompt_arrays(prompts):
+        """[[x, y] | [x0, y0, x1, y1], ..] -> (int32 [n, 4], int32 [n]); a count other than 2 or 4 is passed on for the library to refuse"""
+        p = np.zeros((len(prompts), 4), np.int32)
+        k = np.zeros(len(prompts), np.int32)
+        for i, q in enumerate(prompts):
+            q = [int(v) for v in q]
+            k[i] = len(q)
+            p[i, : min(4, len(q))] = q[:4]
+        return p, k
+
+    def sam_image_extent(self):
+        """(width, height) of the image given to the last sam_encode."""
+        w, h = c_int32(), c_int32()
+        check(self._api.visp_sam_image_extent(self._handle, byref(w), byref(h)))
+        return w.value, h.value
+
+    def sam_compute_batch(self, prompts):
+        """prompts: points [x, y] and boxes [x0, y0, x1, y1], mixed as they come, on the last sam_encode ->
+        (masks uint8 [n, h, w] of 0 / 255, iou float32 [n, 4], chosen int32 [n] = best of the first three masks by predicted iou)."""
+        p, k = self._sam_prompt_arrays(prompts)
+        n = len(prompts)
+        w, h = self.sam_image_extent() if n else (0, 0)
+        masks, iou, chosen = np.empty((n, h, w), np.uint8), np.empty((n, 4), np.float32), np.empty(n, np.int32)
+        check(self._api.visp_sam_compute_batch_host(self._handle, p.ctypes.data, k.ctypes.data, n, masks.ctypes.data, iou.ctypes.data, chosen.ctypes.data))
+        self._sam_batch_n = n
+        return masks, iou, chosen
+
+    def sam_compute_batch_device(self, prompts, masks_dev: int, iou_dev: int | None = None, chosen_dev: int | None = None, stream: int | None = None):
+        """The same with device outputs (addresses): masks u8 [n, h, w], iou f32 [n, 4] and chosen i32 [n], the last two optional. Nothing waits for the
+        device when a stream is given."""
+        p, k = self._sam_prompt_arrays(prompts)
+        check(self._api.visp_sam_compute_batch_device(self._handle, p.ctypes.data, k.ctypes.data, len(prompts), masks_dev, iou_dev, chosen_dev, stream))
+        self._sam_batch_n = len(prompts)
+
+    def sam_set_prompt_chunk(self, n: int):
+        """Prompts per internal chunk of the batch calls (1 .. 256, default 64): sizes the workspace, about 27 MB per prompt in flight."""
+        check(self._api.visp_sam_set_prompt_chunk(self._handle, int(n)))
+
+    def sam_read_masks_batch(self):
+        """mask logits [n, 4, 256, 256] and iou predictions [n, 4] of the last batch call (captures enabled)."""
+        n = getattr(self, "_sam_batch_n", 0)
+        masks, iou = np.empty((max(n, 1), 4, 256, 256), np.float32), np.empty((max(n, 1), 4), np.float32)
+        check(self._api.visp_sam_read_masks_batch(self._handle, masks.ctypes.data, masks.size, iou.ctypes.data))
+        return masks[:n], iou[:n]
+
     def sam_encode_batch(self, images: np.ndarray) -> np.ndarray:
         """images: uint8 [B, 1024, 1024, 3] on the host -> image embeddings float32 [B, 64, 64, 256]."""
         imgs = np.ascontiguousarray(images, dtype=np.uint8)
@@ -316,6 +363,14 @@ class Model:
 
     def sam_encode_batch_device(self, rgb_dev: int, batch: int, out_dev: int, stream: int | None = None):
         check(self._api.visp_sam_encode_batch_device(self._handle, rgb_dev, batch, out_dev, stream))
+
+
+def sam_point_grid(n_per_side: int, w: int, h: int) -> np.ndarray:
+    """The point prompts of a "segment everything" pass: pixel centres of an n x n grid over a w x h image, int32 [n * n, 2] of (x, y), row by row."""
+    xs = ((np.arange(n_per_side) + 0.5) * w / n_per_side).astype(np.int32)
+    ys = ((np.arange(n_per_side) + 0.5) * h / n_per_side).astype(np.int32)
+    gx, gy = np.meshgrid(xs, ys)
+    return np.stack([gx.reshape(-1), gy.reshape(-1)], axis=1).astype(np.int32)
 
 
 class DepthPipeline:
