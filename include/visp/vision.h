@@ -511,4 +511,71 @@ inline std::vector<image_data> sam_compute_batch(sam_model& model, span<box_2d c
     return detail::sam_prompts(model, p, 4);
 }
 
+// not in the reference's header: automatic mask generation, SAM's automatic mask generator on one sam_encode (one crop layer, no crop-edge filter).
+// The pixel centres of an n x n grid over an image of `extent`, row by row: the point prompts of a "segment everything" pass
+inline std::vector<i32x2> sam_point_grid(int n_per_side, i32x2 extent) {
+    std::vector<i32x2> out;
+    for (int y = 0; y < n_per_side; ++y)
+        for (int x = 0; x < n_per_side; ++x) out.push_back(i32x2{int((x + 0.5) * extent[0] / n_per_side), int((y + 0.5) * extent[1] / n_per_side)});
+    return out;
+}
+struct sam_generate_params { // SAM's defaults
+    float pred_iou_thresh = 0.88f;
+    float stability_thresh = 0.95f;
+    float stability_offset = 1.0f;
+    float nms_iou_thresh = 0.7f;
+    int max_masks = 256;
+};
+struct sam_mask {
+    image_data segmentation;   // alpha_u8 at the encoded image's extent, 0 / 255
+    int area = 0;              // pixels that are 255
+    i32x2 bbox_top_left{0, 0}, bbox_extent{0, 0}; // of those pixels; 0, 0, 0, 0 for an empty mask
+    float predicted_iou = 0, stability_score = 0;
+    int prompt = 0, plane = 0; // which prompt of the call and which of its three logit planes
+};
+namespace detail {
+inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t> const& prompts, int32_t n_args, sam_generate_params const& p) {
+    const int32_t n = int32_t(prompts.size() / 4), cap = int32_t(p.max_masks);
+    int32_t w = 0, h = 0, counts[2] = {0, 0};
+    check(visp_sam_image_extent(model.handle, &w, &h));
+    const size_t px = size_t(w) * size_t(h), rows = size_t(cap > 0 ? cap : 0);
+    std::vector<int32_t> n_arg(size_t(n), n_args), info_i(rows * 8);
+    std::vector<uint8_t> masks(rows * px);
+    std::vector<float> info_f(rows * 2);
+    check(visp_sam_generate_masks_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh, cap,
+                                       masks.data(), info_i.data(), info_f.data(), counts));
+    std::vector<sam_mask> out;
+    for (int32_t k = 0; k < counts[0]; ++k) {
+        sam_mask s;
+        s.segmentation = image_alloc({w, h}, image_format::alpha_u8);
+        std::memcpy(s.segmentation.data.get(), masks.data() + size_t(k) * px, px);
+        int32_t const* r = info_i.data() + size_t(k) * 8;
+        s.prompt = r[0]; s.plane = r[1];
+        s.bbox_top_left = i32x2{r[2], r[3]};
+        s.bbox_extent = i32x2{r[4], r[5]};
+        s.area = r[6];
+        s.predicted_iou = info_f[size_t(k) * 2];
+        s.stability_score = info_f[size_t(k) * 2 + 1];
+        out.push_back(std::move(s));
+    }
+    return out;
+}
+} // namespace detail
+inline std::vector<sam_mask> sam_generate_masks(sam_model& model, span<i32x2 const> points, sam_generate_params const& params = {}) {
+    std::vector<int32_t> p;
+    for (i32x2 const& pt : points) p.insert(p.end(), {pt[0], pt[1], 0, 0});
+    return detail::sam_generate(model, p, 2, params);
+}
+inline std::vector<sam_mask> sam_generate_masks(sam_model& model, span<box_2d const> boxes, sam_generate_params const& params = {}) {
+    std::vector<int32_t> p;
+    for (box_2d const& b : boxes) p.insert(p.end(), {b.top_left[0], b.top_left[1], b.bottom_right[0], b.bottom_right[1]});
+    return detail::sam_generate(model, p, 4, params);
+}
+inline std::vector<sam_mask> sam_generate_masks(sam_model& model, int points_per_side = 32, sam_generate_params const& params = {}) {
+    int32_t w = 0, h = 0;
+    detail::check(visp_sam_image_extent(model.handle, &w, &h));
+    std::vector<i32x2> grid = sam_point_grid(points_per_side, i32x2{w, h});
+    return sam_generate_masks(model, span<i32x2 const>(grid), params);
+}
+
 } // namespace visp

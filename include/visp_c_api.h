@@ -278,8 +278,29 @@ VISP_API int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* promp
 VISP_API int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height);
 /* prompts per internal chunk of the batch calls: 1 .. 256, default 64. It sizes the workspace: about 27 MB per prompt in flight. */
 VISP_API int32_t visp_sam_set_prompt_chunk(visp_model* m, int32_t n);
+/* Automatic mask generation: SAM's automatic mask generator (one crop layer, no crop-edge filter, no hole / island removal, no RLE) on n prompts in the
+ * format of the batch calls above (at most 5461: three candidates per prompt, logit planes 0 .. 2, candidate = 3 * prompt + plane). A candidate is kept iff its
+ * predicted iou > pred_iou_thresh and its stability score (logits > +offset over logits > -offset, counted on the decoder's 256^2 logits over the part of
+ * the plane the image occupies) >= stability_thresh; the kept are ranked by predicted iou and de-duplicated by greedy NMS on the boxes of their positive
+ * logits at nms_iou_thresh. The first min(kept, capacity) come out in rank order. Outputs are DEVICE pointers: masks_u8 [capacity][h][w] (0 / 255, the
+ * arithmetic of the batch calls' masks), info_i32 [capacity][8] = {prompt, plane, x, y, w, h, area, 0} (box and area of the mask that came out, image
+ * pixels), info_f32 [capacity][2] = {predicted_iou, stability_score}, counts i32 [2] = {returned, kept before the capacity cut}. Rows and masks at and
+ * behind counts[0] are left untouched. The logits of all n prompts stay on the device for the call (0.5 MB per prompt). Waits for the host exactly where
+ * visp_sam_compute_batch_device does (workspace growth, stream = NULL, captures), and shares its ordering rule: one stream per model. */
+VISP_API int32_t visp_sam_generate_masks_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                                float stability_offset, float nms_iou_thresh, int32_t capacity, void* masks_u8_dev, void* info_i32_dev,
+                                                void* info_f32_dev, void* counts_dev, void* stream);
+/* the same with host outputs; blocks */
+VISP_API int32_t visp_sam_generate_masks_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                              float stability_offset, float nms_iou_thresh, int32_t capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
+                                              int32_t* counts);
+/* diagnostics: with visp_sam_enable_timing on, a generate call records events around its stages and waits for them; this reads the last call's
+ * {decode, scoring, rank + NMS, output masks and their records} in ms */
+VISP_API int32_t visp_sam_generate_last_split(visp_model const* m, float out_ms[4]);
+/* SAM's defaults: {pred_iou_thresh 0.88, stability_thresh 0.95, stability_offset 1.0, nms_iou_thresh 0.7} */
+VISP_API int32_t visp_sam_generate_defaults(float out[4]);
 /* test hook, the batch twin of visp_sam_read_masks: with captures enabled, the f16-rounded logit planes [n][4][256][256] and (iou nullable) the iou
- * predictions [n][4] of the last batch call; capacity in floats of `logits` */
+ * predictions [n][4] of the last batch or generate call; capacity in floats of `logits` */
 VISP_API int32_t visp_sam_read_masks_batch(visp_model* m, float* logits, int64_t capacity, float* iou);
 /* rgb: u8 [B, 1024, 1024, 3] already at the model extent -> out f32 [B, 64, 64, 256]; device pointers;
  * stream = hipStream_t or NULL (NULL: the device's stream, synchronised before returning) */

@@ -365,6 +365,33 @@ VX_API int vx_sam_process_masks(const void* planes, int64_t prompt_stride, int64
                                 float* scaled, int image_size, int sw, int sh, uint8_t* out, int dw, int dh, int P, void* stream);
 /* dst f16 [B][n] = B copies of src f16 [n]; n a multiple of 8, both 16-byte aligned */
 VX_API int vx_sam_tile_rows_f16(const void* src, int64_t n, void* dst, int B, void* stream);
+/* ---- MobileSAM automatic mask generation: the selection stage behind a batched decode (kernels_samselect.hip) ----
+ * Candidate c = prompt * n_planes + plane, the first n_planes f16 logit planes of each prompt: plane at planes + prompt * prompt_stride + plane * plane_stride
+ * elements, mask_size^2 logits row by row. Over the region x < cw, y < ch: table i32 [c][6] = {logits > +offset, logits > -offset, then the inclusive box
+ * x0, y0, x1, y1 of the logits > 0, all 0 without one}; stability f32 [c] = table[0] / table[1], 0 when table[1] is 0. One block per candidate; 16-byte loads
+ * when the planes are 16-byte aligned and mask_size and both strides are multiples of 8. */
+VX_API int vx_sam_score_planes_f16(const void* planes, int64_t prompt_stride, int64_t plane_stride, int mask_size, int n_planes, int cw, int ch, float offset,
+                                   int32_t* table, float* stability, int P, void* stream);
+/* Filters, rank and greedy box NMS over N candidates (1 .. 16384) in four launches. Candidate c has the predicted iou iou[(c / n_planes) * iou_stride + c % n_planes]
+ * and the table row above. flags i32 [N]: iou > pred_iou_thresh (a NaN fails), table[1] > 0 and (float)table[0] >= stability_thresh * (float)table[1].
+ * rank i32 [N]: position among the survivors by iou descending, ties to the smaller index; -1 for the others. NMS on the inclusive integer boxes with
+ * torchvision's arithmetic (area (x1 - x0)(y1 - y0)): a KEPT survivor suppresses a later one iff (float)inter > nms_iou_thresh * (float)union.
+ * keep_idx i32 [capacity]: the first min(kept, capacity) kept candidates in rank order, the rest untouched; counts i32 [2] = {returned, kept}.
+ * workspace: vx_sam_rank_nms_workspace_bytes(N) bytes, 16-byte aligned (keys, order, ranked boxes, the suppression bit matrix of N rows of ceil(N / 64) words). */
+VX_API size_t vx_sam_rank_nms_workspace_bytes(int N);
+VX_API int vx_sam_rank_nms(const int32_t* table, const float* iou, int n_planes, int iou_stride, int N, float pred_iou_thresh, float stability_thresh,
+                           float nms_iou_thresh, int capacity, void* workspace, size_t workspace_bytes, int32_t* flags, int32_t* rank, int32_t* keep_idx,
+                           int32_t* counts, void* stream);
+/* vx_sam_process_masks with the plane of output mask k named by keep_idx[k] = prompt * n_scored + plane (clamped to the n_prompts * n_scored candidates), for
+ * k < counts[0] (a device value); masks at and behind counts[0] are neither read nor written. out u8 [capacity][dh][dw]. The masks pass through
+ * scaled f32 [group][image_size^2] a group at a time: two launches per group. */
+VX_API int vx_sam_process_masks_indexed(const void* planes, int64_t prompt_stride, int64_t plane_stride, int step, int mask_size, int n_scored, int n_prompts,
+                                        const int32_t* keep_idx, const int32_t* counts, int capacity, int group, float* scaled, int image_size, int sw, int sh,
+                                        uint8_t* out, int dw, int dh, void* stream);
+/* masks u8 [capacity][h][w] -> info_i32 [k][8] = {prompt, plane (of keep_idx[k], clamped to the n_prompts * n_scored candidates), x, y, w, h of the pixels that are 255 (0, 0, 0, 0 without one), their number, 0} and,
+ * when info_f32 is given, info_f32 [k][2] = {iou of the candidate, stability[candidate]}; rows at and behind counts[0] untouched. One block per mask. */
+VX_API int vx_sam_mask_stats_u8(const uint8_t* masks, int w, int h, const int32_t* keep_idx, const int32_t* counts, int capacity, int n_scored, int n_prompts,
+                                const float* iou, int iou_stride, const float* stability, int32_t* info_i32, float* info_f32, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -784,6 +784,44 @@ int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* prompts, int32
     return handle_errors([&]() { sam_compute_batch_host(as_sam(m), prompts, n_args, n, masks_u8, iou, chosen); });
 }
 
+int32_t visp_sam_generate_masks_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                       float stability_offset, float nms_iou_thresh, int32_t capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev,
+                                       void* counts_dev, void* stream) {
+    return handle_errors([&]() {
+        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity); // before the handle: needs no model
+        sam_generate_masks_device(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, masks_u8_dev, info_i32_dev,
+                                  info_f32_dev, counts_dev, stream);
+    });
+}
+
+int32_t visp_sam_generate_masks_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                     float stability_offset, float nms_iou_thresh, int32_t capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
+                                     int32_t* counts) {
+    return handle_errors([&]() {
+        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+        sam_generate_masks_host(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, masks_u8, info_i32, info_f32,
+                                counts);
+    });
+}
+
+int32_t visp_sam_generate_last_split(visp_model const* m, float out_ms[4]) {
+    return handle_errors([&]() {
+        if (!out_ms) throw except("sam: null argument");
+        sam_model const& sm = as_sam(m);
+        for (int i = 0; i < 4; ++i) out_ms[i] = sm.generate_split_ms[i];
+    });
+}
+
+int32_t visp_sam_generate_defaults(float out[4]) {
+    return handle_errors([&]() {
+        if (!out) throw except("sam: null argument");
+        out[0] = 0.88f; // SAM's automatic mask generator: pred_iou_thresh, stability_score_thresh, stability_score_offset, box_nms_thresh
+        out[1] = 0.95f;
+        out[2] = 1.0f;
+        out[3] = 0.7f;
+    });
+}
+
 int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height) {
     return handle_errors([&]() {
         sam_model& sm = as_sam(m);

@@ -657,9 +657,24 @@ void sam_set_prompt_chunk(sam_model& m, int n) {
     m.prompt_chunk = n;
 }
 
-void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream) {
+namespace {
+
+// what the launches behind a chunk's mask product need of the decode: the stream, the maps the masks pass through and the extents
+struct sam_decode_ctx {
+    void* s = nullptr;
+    float* scaled = nullptr; // f32 [Bmax][image_size^2]
+    int Bmax = 0, image_size = 0, mask_size = 0, sw = 0, sh = 0;
+    int64_t n_px = 0;
+    i32x2 target = {{0, 0}};
+};
+
+// The batched decode both sam_compute_batch_device and sam_generate_masks_device run: the prompt tokens of the call, layer 0's shared image side, then per
+// chunk the decoder, the mask product and the iou head. The logits of a chunk go to the chunk buffer of the workspace, or, with logits_all, to
+// [p0 ..] of a buffer that keeps the planes of every prompt; after_chunk(ctx, p0, B, logits, iou, chosen) launches what follows them.
+template <class F>
+sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* logits_all, void* iou_dev, void* chosen_dev, void* stream,
+                                  F&& after_chunk) {
     samdec_weights const& D = m.dec;
-    if (!prompts || !n_args || !masks_u8_dev) throw except("sam: null argument");
     if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
     for (int i = 0; i < n; ++i)
         if (n_args[i] != 2 && n_args[i] != 4) throw except("sam: bad number of arguments (%d) for prompt %d, must be 2 or 4", n_args[i], i);
@@ -754,7 +769,6 @@ void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t cons
     const i32x2 target = m.image_extent;
     const float up = float(image_size) / float(std::max(target[0], target[1]));
     const int sw = int(target[0] * up + 0.5f), sh = int(target[1] * up + 0.5f);
-    const size_t out_px = (size_t)target[0] * target[1];
     if (m.captures) {
         m.last_batch_masks.assign((size_t)n * 4 * n_px, 0.0f);
         m.last_batch_iou.assign((size_t)n * 4, 0.0f);
@@ -763,6 +777,9 @@ void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t cons
         m.last_batch_iou.clear();
     }
 
+    sam_decode_ctx ctx;
+    ctx.s = s; ctx.scaled = static_cast<float*>(scaled); ctx.Bmax = Bmax; ctx.image_size = image_size; ctx.mask_size = mask_size; ctx.sw = sw; ctx.sh = sh;
+    ctx.n_px = n_px; ctx.target = target;
     for (int p0 = 0; p0 < n; p0 += Bmax) {
         const int B = std::min(Bmax, n - p0); // every launch below covers rows of these B prompts only: a short last chunk reads no rows behind them
         const long Rt = (long)B * Nt, Mi = (long)B * Nk;
@@ -840,7 +857,8 @@ void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t cons
             VX(vx_gemm_f16(&a, s));
         }
         // masks[b][i][pixel] = <upscaled[b][pixel], hyper_in[b][i]> (mobile-sam.cpp:472-473): four planes of 16 Nk logits per prompt
-        VX(vx_mul_mat_f16(u2, hy, masks_d, 16 * (int64_t)Nk, 4, D.up_c2, B, B, s));
+        void* logits = logits_all ? static_cast<uint8_t*>(logits_all) + (size_t)p0 * 4 * n_px * 2 : masks_d;
+        VX(vx_mul_mat_f16(u2, hy, logits, 16 * (int64_t)Nk, 4, D.up_c2, B, B, s));
         // iou prediction head on the iou token (row 0 of each prompt's seven) in f32, and the choice among the first three (vision.cpp:80-82)
         float* iou_out = iou_dev ? static_cast<float*>(iou_dev) + (size_t)p0 * 4 : static_cast<float*>(iou_ws);
         int32_t* chosen_out = chosen_dev ? static_cast<int32_t*>(chosen_dev) + p0 : static_cast<int32_t*>(chosen_ws);
@@ -848,19 +866,32 @@ void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t cons
         auto ihp = [&](int i) { return reinterpret_cast<const float*>(ih + m.iou_head_off[i]); };
         VX(vx_sam_iou_head_f32(Q, (int64_t)Nt * dim, B, ihp(0), ihp(1), ihp(2), ihp(3), ihp(4), ihp(5), D.iou_head[0].k_real, D.iou_head[0].n_real, D.iou_head[1].n_real,
                                D.iou_head[2].n_real, iou_out, chosen_out, s));
-        // sam_process_mask (mobile-sam.cpp:556-583) on each prompt's chosen plane
-        VX(vx_sam_process_masks(masks_d, 4 * n_px, n_px, 1, mask_size, 4, chosen_out, static_cast<float*>(scaled), image_size, sw, sh,
-                                static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, target[0], target[1], B, s));
+        after_chunk(ctx, p0, B, logits, iou_out, chosen_out);
         if (m.captures) { // test hook: the four logit planes (f16-rounded) and the iou predictions of every prompt
             std::vector<uint16_t> mh((size_t)B * 4 * n_px);
-            VX(vx_memcpy_d2h(mh.data(), masks_d, mh.size() * 2, s));
+            VX(vx_memcpy_d2h(mh.data(), logits, mh.size() * 2, s));
             VX(vx_memcpy_d2h(m.last_batch_iou.data() + (size_t)p0 * 4, iou_out, (size_t)B * 16, s));
             VX(vx_stream_sync(s));
             float* dst = m.last_batch_masks.data() + (size_t)p0 * 4 * n_px;
             for (size_t i = 0; i < mh.size(); ++i) dst[i] = f16_to_f32(mh[i]);
         }
     }
-    if (!stream) VX(vx_stream_sync(s));
+    return ctx;
+}
+
+} // namespace
+
+void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream) {
+    if (!prompts || !n_args || !masks_u8_dev) throw except("sam: null argument");
+    device_turn turn(*m.backend);
+    const size_t out_px = (size_t)m.image_extent[0] * m.image_extent[1];
+    // sam_process_mask (mobile-sam.cpp:556-583) on each prompt's chosen plane
+    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, nullptr, iou_dev, chosen_dev, stream,
+                                            [&](sam_decode_ctx const& c, int p0, int B, void* logits, float*, int32_t* chosen) {
+        VX(vx_sam_process_masks(logits, 4 * c.n_px, c.n_px, 1, c.mask_size, 4, chosen, c.scaled, c.image_size, c.sw, c.sh,
+                                static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, c.target[0], c.target[1], B, c.s));
+    });
+    if (!stream) VX(vx_stream_sync(ctx.s));
 }
 
 void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen) {
@@ -879,6 +910,109 @@ void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const*
     if (iou) VX(vx_memcpy_d2h(iou, base + o_i, (size_t)n * 16, s));
     if (chosen) VX(vx_memcpy_d2h(chosen, base + o_c, (size_t)n * 4, s));
     VX(vx_stream_sync(s));
+}
+
+// ---- automatic mask generation: the batched decode with every prompt's planes kept, scored per chunk, then rank + NMS and the masks that survive ------
+
+void sam_generate_check_args(int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                             float nms_iou_thresh, int capacity) {
+    if (!prompts || !n_args) throw except("sam: null argument");
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
+    if (n > kSamGenerateMaxPrompts)
+        throw except("sam: %d prompts in one generate call, at most %d (three candidates each, 16384 candidates per call)", n, kSamGenerateMaxPrompts);
+    if (std::isnan(pred_iou_thresh) || std::isnan(stability_thresh) || std::isnan(stability_offset) || std::isnan(nms_iou_thresh)) throw except("sam: a threshold is NaN");
+    if (nms_iou_thresh < 0.0f || nms_iou_thresh > 1.0f) throw except("sam: nms_iou_thresh %g is outside [0, 1]", (double)nms_iou_thresh);
+    if (stability_offset < 0.0f) throw except("sam: stability_offset %g is below 0", (double)stability_offset);
+    if (capacity < 1) throw except("sam: capacity %d is below 1", capacity);
+}
+
+void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                               float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream) {
+    sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+    if (!masks_u8_dev || !info_i32_dev || !info_f32_dev || !counts_dev) throw except("sam: null argument");
+    sam_require_decoder(m);
+    device_turn turn(*m.backend);
+    void* s = stream ? stream : m.backend->stream;
+    const int N = 3 * n; // the planes the reference chooses among (vision.cpp:80-82) are the candidates of a prompt
+    const int64_t n_px = (int64_t)16 * m.dec.res * m.dec.res;
+    const size_t nms_bytes = vx_sam_rank_nms_workspace_bytes(N);
+    workspace_layout layout;
+    const size_t o_logits = layout.take((size_t)n * 4 * n_px * 2, 256), o_iou = layout.take((size_t)n * 16, 256), o_table = layout.take((size_t)N * 24, 256);
+    const size_t o_stab = layout.take((size_t)N * 4, 256), o_flags = layout.take((size_t)N * 4, 256), o_rank = layout.take((size_t)N * 4, 256);
+    const size_t o_keep = layout.take((size_t)capacity * 4, 256), o_nms = layout.take(nms_bytes, 256);
+    grow(m.generate_ws, layout.top, {m.backend->stream, s});
+    uint8_t* base = static_cast<uint8_t*>(m.generate_ws.ptr);
+    void* logits_all = base + o_logits;
+    float *iou = reinterpret_cast<float*>(base + o_iou), *stab = reinterpret_cast<float*>(base + o_stab);
+    int32_t *table = reinterpret_cast<int32_t*>(base + o_table), *flags = reinterpret_cast<int32_t*>(base + o_flags), *rank = reinterpret_cast<int32_t*>(base + o_rank);
+    int32_t *keep = reinterpret_cast<int32_t*>(base + o_keep), *counts = static_cast<int32_t*>(counts_dev);
+
+    // diagnostics (sam_enable_timing; tools/bench_sam_autogen.py): events around the stages, read after the call, which then waits for the device
+    struct event_list {
+        std::vector<void*> ev;
+        void* s;
+        bool on;
+        void mark() {
+            if (!on) return;
+            void* e = nullptr;
+            VX(vx_event_create(&e));
+            ev.push_back(e);
+            VX(vx_event_record(e, s));
+        }
+        ~event_list() { for (void* e : ev) vx_event_destroy(e); }
+    } marks{{}, s, m.timing};
+    marks.mark();
+    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, logits_all, iou, nullptr, stream,
+                                            [&](sam_decode_ctx const& c, int p0, int B, void* logits, float*, int32_t*) {
+        // the part of the plane the image occupies: SAM scores at image resolution, this scores the decoder's own logits
+        const int cw = (c.sw * c.mask_size + c.image_size - 1) / c.image_size, ch = (c.sh * c.mask_size + c.image_size - 1) / c.image_size;
+        marks.mark();
+        VX(vx_sam_score_planes_f16(logits, 4 * c.n_px, c.n_px, c.mask_size, 3, cw, ch, stability_offset, table + (size_t)p0 * 18, stab + (size_t)p0 * 3, B, c.s));
+        marks.mark();
+    });
+    VX(vx_sam_rank_nms(table, iou, 3, 4, N, pred_iou_thresh, stability_thresh, nms_iou_thresh, capacity, base + o_nms, nms_bytes, flags, rank, keep, counts, s));
+    marks.mark();
+    VX(vx_sam_process_masks_indexed(logits_all, 4 * ctx.n_px, ctx.n_px, 1, ctx.mask_size, 3, n, keep, counts, capacity, ctx.Bmax, ctx.scaled, ctx.image_size, ctx.sw, ctx.sh,
+                                    static_cast<uint8_t*>(masks_u8_dev), ctx.target[0], ctx.target[1], s));
+    VX(vx_sam_mask_stats_u8(static_cast<const uint8_t*>(masks_u8_dev), ctx.target[0], ctx.target[1], keep, counts, capacity, 3, n, iou, 4, stab,
+                            static_cast<int32_t*>(info_i32_dev), static_cast<float*>(info_f32_dev), s));
+    if (marks.on) { // {decode, scoring, rank + NMS, output masks and their records} in ms: events 0 | (before, behind a chunk's scoring) .. | behind NMS | end
+        marks.mark();
+        float* out = m.generate_split_ms;
+        out[0] = out[1] = out[2] = out[3] = 0.0f;
+        const size_t last = marks.ev.size() - 1;
+        for (size_t i = 1; i <= last; ++i) {
+            float ms = 0.0f;
+            VX(vx_event_elapsed_ms(marks.ev[i - 1], marks.ev[i], &ms));
+            out[i == last ? 3 : i == last - 1 ? 2 : (i & 1) ? 0 : 1] += ms;
+        }
+    }
+    if (!stream) VX(vx_stream_sync(s));
+}
+
+void sam_generate_masks_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                             float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts) {
+    sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+    if (!masks_u8 || !info_i32 || !info_f32 || !counts) throw except("sam: null argument");
+    sam_require_decoder(m);
+    device_turn turn(*m.backend);
+    void* s = m.backend->stream;
+    const size_t px = (size_t)m.image_extent[0] * m.image_extent[1];
+    workspace_layout lay;
+    const size_t o_m = lay.take((size_t)capacity * px), o_i = lay.take((size_t)capacity * 32), o_f = lay.take((size_t)capacity * 8), o_c = lay.take(8);
+    device_buffer out(lay.top);
+    uint8_t* base = static_cast<uint8_t*>(out.ptr);
+    sam_generate_masks_device(m, prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, base + o_m, base + o_i, base + o_f,
+                              base + o_c, s);
+    VX(vx_memcpy_d2h(counts, base + o_c, 8, s));
+    VX(vx_stream_sync(s));
+    const size_t k = (size_t)std::min(std::max(counts[0], 0), capacity); // rows and masks behind the returned ones stay as the caller left them
+    if (k) {
+        VX(vx_memcpy_d2h(masks_u8, base + o_m, k * px, s));
+        VX(vx_memcpy_d2h(info_i32, base + o_i, k * 32, s));
+        VX(vx_memcpy_d2h(info_f32, base + o_f, k * 8, s));
+        VX(vx_stream_sync(s));
+    }
 }
 
 } // namespace visp

@@ -93,7 +93,11 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     void* prompt_tokens_host = nullptr;    // pinned: the prompt tokens of one call, f16 [n][7][dim]
     size_t prompt_tokens_bytes = 0;
     void* prompt_tokens_event = nullptr;   // recorded behind their upload: the next call waits for it before it overwrites them
-    std::vector<float> last_batch_masks, last_batch_iou; // captures: [n][4][mask_size^2] logits (f16-rounded) and [n][4] of the last batch call
+    std::vector<float> last_batch_masks, last_batch_iou; // captures: [n][4][mask_size^2] logits (f16-rounded) and [n][4] of the last batch or generate call
+    // automatic mask generation (sam_generate_masks_device): the logit planes and iou predictions of every prompt of the call, the selection stage's tables
+    // and the NMS workspace. A buffer of its own: batch_ws and with it sam_compute_batch_* stay as they are.
+    device_buffer generate_ws;
+    float generate_split_ms[4] = {0, 0, 0, 0}; // with timing enabled: the last generate call's {decode, scoring, rank + NMS, output masks} by events
     ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
@@ -115,5 +119,16 @@ image_data sam_compute(sam_model&, int const* prompt, int n);
 void sam_compute_batch_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream);
 void sam_compute_batch_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen);
 void sam_set_prompt_chunk(sam_model&, int n); // 1 .. 256
+// SAM's automatic mask generator on the prompts of a batch call (one crop layer, no crop-edge filter): every prompt gives three candidates (planes 0 .. 2),
+// filtered by predicted iou and stability score, ranked by predicted iou, de-duplicated by greedy box NMS; the first min(kept, capacity) come out as u8 masks
+// [capacity][h][w] with info_i32 [capacity][8] = {prompt, plane, x, y, w, h, area, 0}, info_f32 [capacity][2] = {predicted_iou, stability_score} and
+// counts i32 [2] = {returned, kept}. Device outputs; rows and masks at and behind counts[0] untouched. No host synchronisation beyond sam_compute_batch_device's.
+constexpr int kSamGenerateMaxPrompts = 5461; // 16384 candidates
+void sam_generate_check_args(int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                             float nms_iou_thresh, int capacity); // throws on what needs neither model nor device to refuse
+void sam_generate_masks_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                               float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream);
+void sam_generate_masks_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                             float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts);
 
 } // namespace visp

@@ -352,6 +352,67 @@ class Model:
         check(self._api.visp_sam_read_masks_batch(self._handle, masks.ctypes.data, masks.size, iou.ctypes.data))
         return masks[:n], iou[:n]
 
+    # ---- automatic mask generation: SAM's automatic mask generator on a prompt grid, selected on the device
+    def _sam_generate_args(self, prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh):
+        if prompts is None:
+            w, h = self.sam_image_extent()
+            prompts = sam_point_grid(int(points_per_side), w, h)
+        d = sam_generate_defaults()
+        given = (pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        params = [float(d[k]) if v is None else float(v) for k, v in zip(("pred_iou_thresh", "stability_thresh", "stability_offset", "nms_iou_thresh"), given)]
+        p, k = self._sam_prompt_arrays(prompts)
+        return p, k, params
+
+    def sam_generate_masks_raw(self, prompts=None, points_per_side: int = 32, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
+                               max_masks: int = 256):
+        """The arrays of visp_sam_generate_masks_host, cut to the masks returned: (masks uint8 [k, h, w] of 0 / 255, info_i32 [k, 8] = {prompt, plane, x, y, w, h,
+        area, 0}, info_f32 [k, 2] = {predicted_iou, stability_score}, counts (returned, kept before the cut to max_masks))."""
+        p, k, params = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        n, cap = len(k), int(max_masks)
+        w, h = self.sam_image_extent() if n and cap > 0 else (0, 0)
+        masks, ii, fi = np.empty((max(cap, 0), h, w), np.uint8), np.empty((max(cap, 0), 8), np.int32), np.empty((max(cap, 0), 2), np.float32)
+        counts = np.zeros(2, np.int32)
+        check(self._api.visp_sam_generate_masks_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, masks.ctypes.data, ii.ctypes.data, fi.ctypes.data,
+                                                     counts.ctypes.data))
+        self._sam_batch_n = n
+        r = int(counts[0])
+        return masks[:r], ii[:r], fi[:r], (r, int(counts[1]))
+
+    def sam_generate_masks(self, points_per_side: int = 32, prompts=None, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
+                           max_masks: int = 256):
+        """SAM's automatic mask generator on the last sam_encode (one crop layer, no crop-edge filter, no hole / island removal): the points_per_side^2 grid
+        of sam_point_grid, or `prompts` (points and boxes as for sam_compute_batch). Thresholds default to SAM's (sam_generate_defaults). Returns at most
+        max_masks records in order of predicted iou, each a dict with SAM's keys: segmentation (bool [h, w]), area, bbox [x, y, w, h] (of the mask, image
+        pixels), predicted_iou, stability_score, and point_coords [[x, y]] for a point prompt or box [x0, y0, x1, y1] for a box prompt."""
+        p, k, _ = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        masks, ii, fi, _ = self.sam_generate_masks_raw([list(q[:c]) for q, c in zip(p, k)], points_per_side, pred_iou_thresh, stability_thresh, stability_offset,
+                                                       nms_iou_thresh, max_masks)
+        out = []
+        for m, row, (piou, stab) in zip(masks, ii, fi):
+            prompt = int(row[0])
+            rec = dict(segmentation=m == 255, area=int(row[6]), bbox=[int(v) for v in row[2:6]], predicted_iou=float(piou), stability_score=float(stab))
+            if k[prompt] == 2:
+                rec["point_coords"] = [[int(p[prompt, 0]), int(p[prompt, 1])]]
+            else:
+                rec["box"] = [int(v) for v in p[prompt]]
+            out.append(rec)
+        return out
+
+    def sam_generate_masks_device(self, prompts, masks_dev: int, info_i32_dev: int, info_f32_dev: int, counts_dev: int, max_masks: int = 256, pred_iou_thresh=None,
+                                  stability_thresh=None, stability_offset=None, nms_iou_thresh=None, stream: int | None = None):
+        """The same into device buffers (addresses): masks u8 [max_masks, h, w], info i32 [max_masks, 8], info f32 [max_masks, 2], counts i32 [2]; rows and masks
+        at and behind counts[0] stay untouched. Nothing waits for the device when a stream is given."""
+        p, k, params = self._sam_generate_args(prompts, 32, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        check(self._api.visp_sam_generate_masks_device(self._handle, p.ctypes.data, k.ctypes.data, len(k), *params, int(max_masks), masks_dev, info_i32_dev, info_f32_dev,
+                                                       counts_dev, stream))
+        self._sam_batch_n = len(k)
+
+    def sam_generate_last_split(self) -> dict:
+        """ms of the last generate call by HIP events, recorded while timing is enabled (enable_timing): decode, scoring, rank + NMS, output masks."""
+        out = (ctypes.c_float * 4)()
+        check(self._api.visp_sam_generate_last_split(self._handle, out))
+        return dict(zip(("decode_ms", "scoring_ms", "rank_nms_ms", "output_ms"), (float(v) for v in out)))
+
     def sam_encode_batch(self, images: np.ndarray) -> np.ndarray:
         """images: uint8 [B, 1024, 1024, 3] on the host -> image embeddings float32 [B, 64, 64, 256]."""
         imgs = np.ascontiguousarray(images, dtype=np.uint8)
@@ -371,6 +432,13 @@ def sam_point_grid(n_per_side: int, w: int, h: int) -> np.ndarray:
     ys = ((np.arange(n_per_side) + 0.5) * h / n_per_side).astype(np.int32)
     gx, gy = np.meshgrid(xs, ys)
     return np.stack([gx.reshape(-1), gy.reshape(-1)], axis=1).astype(np.int32)
+
+
+def sam_generate_defaults() -> dict:
+    """SAM's automatic mask generator defaults, as the library holds them (visp_sam_generate_defaults)."""
+    out = (ctypes.c_float * 4)()
+    check(lib.get_lib().visp_sam_generate_defaults(out))
+    return dict(zip(("pred_iou_thresh", "stability_thresh", "stability_offset", "nms_iou_thresh"), (float(v) for v in out)))
 
 
 class DepthPipeline:
