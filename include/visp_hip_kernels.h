@@ -474,7 +474,7 @@ VX_API int vx_write_cls_rows(float* x, const float* cls, const float* pos, int B
 VX_API int vx_bilinear_ac_f16(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, void* stream);
 
 /* ---- head tail: depth[b,y,x] = max_depth * relu(sum_c x[b,y,x,c]*w[c] + bias), x f16 NHWC
- * (already ReLU-ed conv2 output), C <= 64 (depth-anything.cpp:89-94) ----------------------- */
+ * (already ReLU-ed conv2 output), C = 8, 16, 32 or 64 (depth-anything.cpp:89-94) ----------- */
 VX_API int vx_head_out_f32(const void* x, const float* w, float bias, float max_depth, float* depth,
                            int64_t n_pixels, int C, void* stream);
 
@@ -501,8 +501,9 @@ VX_API int vx_headconv_wide_pack(const void* w_rows, int cin, int Kp, void* out_
 VX_API int vx_headconv_wide_bil_f16(const void* x, int cin, const void* wfrag, const float* bias, const float* w3, float b3, float scale, float* out, int B,
                                     int H, int W, int hs, int ws, void* stream);
 
-/* ---- post-processing: per-image min/max then (v-min)/(max-min) (image.cpp:537-576);
- * minmax: f32 [B,2] scratch ------------------------------------------------------------------ */
+/* ---- post-processing: per-image min/max then (v-min)/(max-min) (image.cpp:537-576), each image by its own extremes; max - min below
+ * 1e-5 divides by 1. The input is finite (no NaN, no infinity). The product and the sum round separately, so an image's minimum maps to
+ * +0.0 exactly. minmax: scratch of 2 B 32-bit words, nothing behind them is written; what the call leaves there is unspecified. B <= 65535 */
 VX_API int vx_minmax_normalize(const float* depth, float* out, float* minmax, int B, int64_t pixels_per_image,
                                void* stream);
 /* alpha_f32 -> alpha_u8: uint8(clamp(v,0,1)*255) (image-impl.h:36-38) */

@@ -49,7 +49,8 @@ __global__ __launch_bounds__(256) void bf_preprocess_half_kernel(const unsigned 
 }
 
 // patches [B, h, w, gw*gh*3]: channel gx + gw (gy + gh c) of pixel (py, px) = normalised image (gy h + py, gx w + px, c).
-// A thread writes 8 consecutive channels (16 bytes); gw*gh*3 is a multiple of 8 for the grids in use (4 .. 32), else scalar tail.
+// A thread writes 8 consecutive channels: 16 bytes at once where gw*gh*3 is a multiple of 8 (the grids in use, 4 .. 32: every pixel's
+// row is then 16-byte aligned), else one by one -- a pixel's row then starts at any 2-byte boundary, and the last chunk is partial.
 __global__ __launch_bounds__(256) void bf_patches_kernel(const unsigned char* __restrict__ rgb, f16* __restrict__ out, int B, int IH, int IW, int h, int w) {
     const int gw = IW / w, gh = IH / h, CP = gw * gh * 3, c8 = (CP + 7) / 8;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -67,9 +68,9 @@ __global__ __launch_bounds__(256) void bf_patches_kernel(const unsigned char* __
             o[j] = (f16)norm_px(rgb[((b * IH + (long)gy * h + py) * IW + (long)gx * w + px) * 3 + c], c);
         }
     }
-    if (ch0 + 8 <= CP) *reinterpret_cast<f16x8*>(out + pix * CP + ch0) = o;
+    if (CP % 8 == 0) *reinterpret_cast<f16x8*>(out + pix * CP + ch0) = o;
     else
-        for (int j = 0; ch0 + j < CP; ++j) out[pix * CP + ch0 + j] = o[j];
+        for (int j = 0; j < 8 && ch0 + j < CP; ++j) out[pix * CP + ch0 + j] = o[j];
 }
 
 // bilinear, align_corners, f16 NHWC; src row stride lds, dst row stride ldd (elements); C % 8 == 0
@@ -205,7 +206,7 @@ int vx_bf_preprocess_half(const uint8_t* rgb, void* out8, int B, int H, int W, v
 }
 
 int vx_bf_patches(const uint8_t* rgb, void* out, int B, int IH, int IW, int h, int w, void* stream) {
-    VX_REQUIRE(rgb && out && B > 0 && h > 0 && w > 0 && IH % h == 0 && IW % w == 0, "vx_bf_patches: grid %dx%d must divide the image %dx%d", w, h, IW, IH);
+    VX_REQUIRE(rgb && out && B > 0 && h > 0 && w > 0 && IH > 0 && IW > 0 && IH % h == 0 && IW % w == 0, "vx_bf_patches: grid %dx%d must divide the image %dx%d", w, h, IW, IH);
     const long n = (long)B * h * w * (((IW / w) * (IH / h) * 3 + 7) / 8);
     hipLaunchKernelGGL(bf_patches_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), rgb, reinterpret_cast<f16*>(out), B, IH, IW, h, w);
     VX_LAUNCH_CHECK();

@@ -256,8 +256,11 @@ int vx_layernorm_f32_f16(const float* x, const float* w, const float* b, void* y
 
 int vx_preprocess_patches(const uint8_t* rgb, void* patches, int B, int H, int W, int ps, int Kp, const float mean[3],
                           const float inv_std[3], void* stream) {
+    VX_REQUIRE(rgb && patches && mean && inv_std, "vx_preprocess_patches: null operand");
+    VX_REQUIRE(B > 0 && H > 0 && W > 0 && ps > 0, "vx_preprocess_patches: empty extent (B = %d, %dx%d, patch size %d)", B, W, H, ps);
+    VX_REQUIRE(B <= 65535, "vx_preprocess_patches: %d images do not fit the grid (65535)", B);
     VX_REQUIRE(H % ps == 0 && W % ps == 0, "vx_preprocess_patches: %dx%d not a multiple of patch size %d", W, H, ps);
-    VX_REQUIRE(Kp % 8 == 0 && Kp >= ps * ps * 3, "vx_preprocess_patches: bad Kp=%d", Kp);
+    VX_REQUIRE(Kp % 8 == 0 && Kp >= (long)ps * ps * 3, "vx_preprocess_patches: bad Kp=%d", Kp);
     const int per_image = (H / ps) * (W / ps) * (Kp / 8);
     if (ps == 14)
         hipLaunchKernelGGL(preprocess_patches_kernel<14>, dim3((per_image + 255) / 256, B), dim3(256), 0, as_stream(stream), rgb,
@@ -271,6 +274,8 @@ int vx_preprocess_patches(const uint8_t* rgb, void* patches, int B, int H, int W
 
 int vx_preprocess_f32(const uint8_t* rgb, float* out, int B, int H, int W, const float mean[3], const float inv_std[3],
                       void* stream) {
+    VX_REQUIRE(rgb && out && mean && inv_std, "vx_preprocess_f32: null operand");
+    VX_REQUIRE(B > 0 && H > 0 && W > 0, "vx_preprocess_f32: empty extent (B = %d, %dx%d)", B, W, H);
     long n = (long)B * H * W * 3;
     hipLaunchKernelGGL(preprocess_f32_kernel, dim3(grid_stride_blocks(n, 256 * 16)), dim3(256), 0, as_stream(stream), rgb, out, n, mean[0],
                        mean[1], mean[2], inv_std[0], inv_std[1], inv_std[2]);
@@ -279,6 +284,9 @@ int vx_preprocess_f32(const uint8_t* rgb, float* out, int B, int H, int W, const
 }
 
 int vx_write_cls_rows(float* x, const float* cls, const float* pos, int B, int T, int C, void* stream) {
+    VX_REQUIRE(x && cls && pos, "vx_write_cls_rows: null operand");
+    VX_REQUIRE(B > 0 && T >= 1 && C >= 1, "vx_write_cls_rows: empty extent (B = %d, T = %d, C = %d)", B, T, C);
+    VX_REQUIRE(B <= 65535, "vx_write_cls_rows: %d images do not fit the grid (65535)", B);
     hipLaunchKernelGGL(write_cls_kernel, dim3(B), dim3(128), 0, as_stream(stream), x, cls, pos, T, C);
     VX_LAUNCH_CHECK();
     return 1;
@@ -302,19 +310,24 @@ int vx_bilinear_ac_f16(const void* x, void* y, int B, int H, int W, int C, int O
 
 int vx_head_out_f32(const void* x, const float* w, float bias, float max_depth, float* depth, int64_t n_pixels, int C,
                     void* stream) {
+    VX_REQUIRE(x && w && depth, "vx_head_out_f32: null operand");
+    VX_REQUIRE(n_pixels > 0, "vx_head_out_f32: empty extent (%lld pixels)", (long long)n_pixels);
+    VX_REQUIRE(C == 8 || C == 16 || C == 32 || C == 64, "vx_head_out_f32: unsupported C=%d", C);
     hipStream_t s = as_stream(stream);
     const f16* xx = reinterpret_cast<const f16*>(x);
     dim3 grid(grid_stride_blocks(n_pixels, 256 * 16)), block(256);
     if (C == 32) hipLaunchKernelGGL(head_out_kernel<32>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
     else if (C == 64) hipLaunchKernelGGL(head_out_kernel<64>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
     else if (C == 8) hipLaunchKernelGGL(head_out_kernel<8>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
-    else if (C == 16) hipLaunchKernelGGL(head_out_kernel<16>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
-    else { vx_set_error("vx_head_out_f32: unsupported C=%d", C); return 0; }
+    else hipLaunchKernelGGL(head_out_kernel<16>, grid, block, 0, s, xx, w, bias, max_depth, depth, (long)n_pixels);
     VX_LAUNCH_CHECK();
     return 1;
 }
 
 int vx_minmax_normalize(const float* depth, float* out, float* minmax, int B, int64_t n, void* stream) {
+    VX_REQUIRE(depth && out && minmax, "vx_minmax_normalize: null operand");
+    VX_REQUIRE(B > 0 && n > 0, "vx_minmax_normalize: empty extent (B = %d, %lld pixels per image)", B, (long long)n);
+    VX_REQUIRE(B <= 65535, "vx_minmax_normalize: %d images do not fit the grid (65535)", B);
     hipStream_t s = as_stream(stream);
     unsigned* mm = reinterpret_cast<unsigned*>(minmax);
     hipLaunchKernelGGL(minmax_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, mm, B);
@@ -327,6 +340,8 @@ int vx_minmax_normalize(const float* depth, float* out, float* minmax, int B, in
 }
 
 int vx_f32_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream) {
+    VX_REQUIRE(src && dst, "vx_f32_to_u8: null operand");
+    VX_REQUIRE(n > 0, "vx_f32_to_u8: empty extent (n = %lld)", (long long)n);
     hipLaunchKernelGGL(f32_to_u8_kernel, dim3(grid_stride_blocks(n, 256 * 16)), dim3(256), 0, as_stream(stream), src, dst, (long)n);
     VX_LAUNCH_CHECK();
     return 1;
