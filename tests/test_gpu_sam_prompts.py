@@ -1,5 +1,5 @@
 """Many prompts per sam_encode in one batched pass (Model.sam_compute_batch / visp_sam_compute_batch_*): against the CPU oracle on the GPU's own
-embedding, against the unchanged single-prompt sam_compute, across chunk sizes, on a non-square image, and the error paths. The model is the
+embedding, against the single-prompt sam_compute (the same decoder with a batch of one), across chunk sizes, on a non-square image, and the error paths. The model is the
 TINYVIT_5M encoder (seed 2) + decoder (seed 11) file of tests/test_gpu_tinyvit.py's sam_full, built here; one sam_encode of the seed-31 image is
 shared by the tests that use it. Tolerances are those of test_decoder_matches_oracle_on_the_same_embedding."""
 import subprocess
@@ -77,6 +77,19 @@ def _batch(s, prompts, chunk):
     return masks, iou, logits
 
 
+def _single(m, prompt):
+    """(mask u8 [h, w], iou [4], logits [4, 256, 256]) of one sam_compute"""
+    mask = m.sam_compute(prompt)
+    logits, iou = m.sam_read_masks()
+    return mask, iou, logits
+
+
+def _assert_same_bytes(one, alone, prompt):
+    """`one` of _single against `alone`, the _batch of that prompt by itself"""
+    for a, b in zip(one, alone):
+        assert b.shape == (1,) + a.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), prompt
+
+
 @pytest.fixture(scope="module")
 def sam(tmp_path_factory):
     s = _build(tmp_path_factory.mktemp("samprompts"), "mobile_sam.gguf")
@@ -142,6 +155,14 @@ def test_batch_matches_the_single_prompt_call_which_keeps_its_bytes(sam, chunk2)
     _assert_close(before, sam["oracle"], "sam_compute against the oracle")
 
 
+def test_sam_compute_is_the_batch_of_one_bit_for_bit(sam):
+    """sam_compute runs the one decoder with n = 1: mask, iou[4] and logits[4, 256, 256] have the bytes of sam_compute_batch with that prompt alone, for
+    points and boxes (test_non_square_image_host_and_device_entries_agree: the same on a 640 x 480 image)."""
+    _encode31(sam)
+    for prompt in PROMPTS:
+        _assert_same_bytes(_single(sam["model"], prompt), _batch(sam, [prompt], 64), prompt)
+
+
 def test_chunk_sizes_and_single_prompt_batches_agree(sam, chunk2):
     """Chunk 2 against chunk 64 (one chunk of five) and each prompt alone: within the tolerances, not bit for bit -- layer 0's token -> image
     attention runs all 7 B queries of a chunk as one batch and splits its keys only up to 32 queries, so its sums change order with the chunk."""
@@ -166,7 +187,7 @@ def test_chunk_sizes_and_single_prompt_batches_agree(sam, chunk2):
 
 def test_near_tied_iou_predictions_in_a_batch(tmp_path):
     """The near-tie of tests/test_gpu_tinyvit.py (rows 0 and 1 of the iou head's last layer equal, biases 1e-4 apart) in a batch of three: the f32 head on
-    the device ranks them as the host's does."""
+    the device ranks them as the oracle does, for every prompt of the batch."""
     from visioncpp_amd import synth
     dec_sd = synth.sam_decoder_state_dict(11)
     wk = [k for k in dec_sd if k.endswith("iou_prediction_head.layers.2.weight")][0]
@@ -212,9 +233,16 @@ def test_non_square_image_host_and_device_entries_agree(sam):
     got = only.to_numpy(np.uint8, (3 * 480 * 640 + 64,))
     np.testing.assert_array_equal(got[: 3 * 480 * 640].reshape(3, 480, 640), masks)
     assert (got[3 * 480 * 640:] == 7).all()
+    kept = m.sam_read_masks_batch()  # of the batch call just made
+    singles = []
     for p, prompt in enumerate(prompts):  # and the single-prompt call on the same embedding
-        one = m.sam_compute(prompt)
+        singles.append(_single(m, prompt))
+        one = singles[-1][0]
         assert (one != masks[p]).mean() < 5e-3, (prompt, (one != masks[p]).mean())
+    for a, b in zip(kept, m.sam_read_masks_batch()):  # sam_compute keeps its logits apart from the batch call's
+        assert a.shape[0] == 3 and a.tobytes() == b.tobytes(), "a sam_compute in between changed the batch call's read-back"
+    for prompt, one in zip(prompts, singles):
+        _assert_same_bytes(one, _batch(sam, [prompt], 64), prompt)
 
 
 def test_errors(sam, tmp_path):

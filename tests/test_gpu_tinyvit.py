@@ -423,7 +423,7 @@ def test_decoder_matches_oracle_on_the_same_embedding(sam_full, prompt):
 
 def test_near_tied_iou_predictions_and_arena_only_load(tmp_path):
     """(1) The iou head decides which mask sam_compute returns (vision.cpp:80-82). With rows 0 and 1 of its last layer equal
-    and biases 1e-4 apart the two predictions differ by a fifth of an f16 ulp (4.9e-4 near 0.9): the host-side f32 head must still rank them
+    and biases 1e-4 apart the two predictions differ by a fifth of an f16 ulp (4.9e-4 near 0.9): the f32 head (vx_sam_iou_head_f32) must still rank them
     (an all-f16 decoder returned the other mask). (2) A model loaded WITHOUT data whose arena is then filled from another
     model's (the RCCL broadcast path) runs sam_compute with the same result: the prompt-encoder tables and the iou head
     are rebuilt from the arena in sam_weights_ready."""

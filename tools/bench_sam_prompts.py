@@ -3,7 +3,7 @@
 file (TinyViT-5M encoder, 64 x 64 x 256 embedding, 1024 x 1024 image). Prints a text record and, last, ONE JSON line. A measurement, not a gate.
 
   * P = 1, 8, 64, 256 and 1024 point prompts: the 32 x 32 grid of vision.sam_point_grid, thinned evenly for the smaller P.
-  * loop: P calls of Model.sam_compute (each: prompt on the host, upload, about 100 launches, a mid-stream synchronise for the iou head, one mask back).
+  * loop: P calls of Model.sam_compute (each: the batched decoder with one prompt -- prompt on the host, upload, about 85 launches -- one mask back, one synchronise).
     batch: one Model.sam_compute_batch_device call into device buffers (masks u8 [P, 1024, 1024], iou, chosen), stream NULL, so it ends in a synchronise.
     Host clock around each; both end synchronised. The loop side brings every mask back to the host (that is what sam_compute does), the batch side leaves its
     masks on the device (that is what the device entry is for): the comparison is of the two calls as their users make them, not of equal work.

@@ -767,11 +767,11 @@ int32_t visp_sam_compute(visp_model* m, int32_t const* prompt, int32_t n_prompt,
 
 int32_t visp_sam_read_masks(visp_model* m, float* masks, int64_t capacity, float iou[4]) {
     return handle_errors([&]() {
-        sam_model& sm = as_sam(m);
-        if (sm.last_masks.empty()) throw except("sam: no mask logits kept: enable captures, then call sam_compute()");
-        if (capacity < (int64_t)sm.last_masks.size()) throw except("sam: mask buffer too small (%lld < %zu)", (long long)capacity, sm.last_masks.size());
-        memcpy(masks, sm.last_masks.data(), sm.last_masks.size() * sizeof(float));
-        memcpy(iou, sm.last_iou, sizeof sm.last_iou);
+        sam_kept_logits const& kept = as_sam(m).last_single;
+        if (kept.masks.empty()) throw except("sam: no mask logits kept: enable captures, then call sam_compute()");
+        if (capacity < (int64_t)kept.masks.size()) throw except("sam: mask buffer too small (%lld < %zu)", (long long)capacity, kept.masks.size());
+        memcpy(masks, kept.masks.data(), kept.masks.size() * sizeof(float));
+        memcpy(iou, kept.iou.data(), kept.iou.size() * sizeof(float));
     });
 }
 
@@ -838,12 +838,12 @@ int32_t visp_sam_set_prompt_chunk(visp_model* m, int32_t n) {
 
 int32_t visp_sam_read_masks_batch(visp_model* m, float* logits, int64_t capacity, float* iou) {
     return handle_errors([&]() {
-        sam_model& sm = as_sam(m);
+        sam_kept_logits const& kept = as_sam(m).last_batch;
         if (!logits) throw except("sam: null argument");
-        if (sm.last_batch_masks.empty()) throw except("sam: no mask logits kept: enable captures, then call sam_compute_batch()");
-        if (capacity < (int64_t)sm.last_batch_masks.size()) throw except("sam: mask buffer too small (%lld < %zu)", (long long)capacity, sm.last_batch_masks.size());
-        memcpy(logits, sm.last_batch_masks.data(), sm.last_batch_masks.size() * sizeof(float));
-        if (iou) memcpy(iou, sm.last_batch_iou.data(), sm.last_batch_iou.size() * sizeof(float));
+        if (kept.masks.empty()) throw except("sam: no mask logits kept: enable captures, then call sam_compute_batch()");
+        if (capacity < (int64_t)kept.masks.size()) throw except("sam: mask buffer too small (%lld < %zu)", (long long)capacity, kept.masks.size());
+        memcpy(logits, kept.masks.data(), kept.masks.size() * sizeof(float));
+        if (iou) memcpy(iou, kept.iou.data(), kept.iou.size() * sizeof(float));
     });
 }
 

@@ -149,7 +149,7 @@ sam_model* sam_load_model(char const* filepath, backend_device const& dev, int f
 }
 
 // The arena is complete (uploaded here, or received from the rank that read the file): rebuild everything the host computes
-// with from it -- the prompt encoder's tables and the f32 copy of the iou head (vision.cpp:80-82 picks a mask by its output).
+// with from it -- the prompt encoder's tables -- and the device's f32 copy of the iou head (vision.cpp:80-82 picks a mask by its output).
 void sam_weights_ready(sam_model& m) {
     samdec_weights& D = m.dec;
     if (D.present) {
@@ -163,28 +163,29 @@ void sam_weights_ready(sam_model& m) {
         for (int i = 0; i < 4; ++i) D.point_embed[i].assign(tb.begin() + (size_t)(1 + i) * dim, tb.begin() + (size_t)(2 + i) * dim);
         D.not_a_point.assign(tb.begin() + (size_t)5 * dim, tb.begin() + (size_t)6 * dim);
         D.output_tokens.assign(tb.begin() + (size_t)6 * dim, tb.end());
+        std::vector<float> iou_w[3], iou_b[3]; // f32 copies [n][k] of the f16-rounded iou head weights, biases
         for (int l = 0; l < 3; ++l) {
             packed_gemm const& g = D.iou_head[l];
             std::vector<uint16_t> w16((size_t)g.N * g.K);
             VX(vx_memcpy_d2h(w16.data(), wa + g.w, w16.size() * 2, s));
-            D.iou_w[l].resize((size_t)g.n_real * g.k_real);
+            iou_w[l].resize((size_t)g.n_real * g.k_real);
             for (int n = 0; n < g.n_real; ++n)
-                for (int k = 0; k < g.k_real; ++k) D.iou_w[l][(size_t)n * g.k_real + k] = f16_to_f32(w16[(size_t)n * g.K + k]);
-            D.iou_b[l].assign((size_t)g.n_real, 0.0f);
-            if (g.b != SIZE_MAX) VX(vx_memcpy_d2h(D.iou_b[l].data(), wa + g.b, (size_t)g.n_real * 4, s));
+                for (int k = 0; k < g.k_real; ++k) iou_w[l][(size_t)n * g.k_real + k] = f16_to_f32(w16[(size_t)n * g.K + k]);
+            iou_b[l].assign((size_t)g.n_real, 0.0f);
+            if (g.b != SIZE_MAX) VX(vx_memcpy_d2h(iou_b[l].data(), wa + g.b, (size_t)g.n_real * 4, s));
         }
         VX(vx_stream_sync(s));
-        // the same f32 values on the device for vx_sam_iou_head_f32 (the batched path ranks the masks there): [w0 | b0 | w1 | b1 | w2 | b2]
+        // those f32 values on the device for vx_sam_iou_head_f32 (the decoder ranks the masks there): [w0 | b0 | w1 | b1 | w2 | b2]
         workspace_layout lay;
         for (int l = 0; l < 3; ++l) {
-            m.iou_head_off[2 * l] = lay.take(D.iou_w[l].size() * 4);
-            m.iou_head_off[2 * l + 1] = lay.take(D.iou_b[l].size() * 4);
+            m.iou_head_off[2 * l] = lay.take(iou_w[l].size() * 4);
+            m.iou_head_off[2 * l + 1] = lay.take(iou_b[l].size() * 4);
         }
         m.iou_head_dev = device_buffer(lay.top);
         uint8_t* base = static_cast<uint8_t*>(m.iou_head_dev.ptr);
         for (int l = 0; l < 3; ++l) {
-            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l], D.iou_w[l].data(), D.iou_w[l].size() * 4, s));
-            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l + 1], D.iou_b[l].data(), D.iou_b[l].size() * 4, s));
+            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l], iou_w[l].data(), iou_w[l].size() * 4, s));
+            VX(vx_memcpy_h2d(base + m.iou_head_off[2 * l + 1], iou_b[l].data(), iou_b[l].size() * 4, s));
         }
         VX(vx_stream_sync(s));
     }
@@ -442,7 +443,13 @@ void sam_encode(sam_model& m, image_view image) {
     m.image_extent = image.extent;
 }
 
-// ---- sam_compute: prompt encoder + mask decoder + mask post-processing ------------------------------------------------
+// ---- prompt encoder + mask decoder + mask post-processing: one schedule, the prompt index folded into the rows of its launches ---------
+// (sam_compute is a batch of one prompt)
+
+void sam_set_prompt_chunk(sam_model& m, int n) {
+    if (n < 1 || n > 256) throw except("sam: prompt chunk %d is outside 1 .. 256", n);
+    m.prompt_chunk = n;
+}
 
 namespace {
 
@@ -453,8 +460,7 @@ float sam_transform_coord(int p, float scale, int image_size) { // mobile-sam.cp
 
 constexpr int kSamTokens = 7; // [iou | 4 mask tokens | 2 prompt points]
 
-// prompt encoder on the host (two points of 256 sin/cos values; mobile-sam.cpp:219-286): the decoder's token rows of one prompt, f16 [7][dim].
-// Both sam_compute and the batched path call it: one prompt gives the same bits on either.
+// prompt encoder on the host (two points of 256 sin/cos values; mobile-sam.cpp:219-286): the decoder's token rows of one prompt, f16 [7][dim]
 void sam_prompt_tokens(sam_model const& m, int const* prompt, int n_prompt, uint16_t* out) {
     samdec_weights const& D = m.dec;
     const int dim = D.dim, F = dim / 2, image_size = m.params.img_size;
@@ -486,179 +492,6 @@ void sam_require_decoder(sam_model const& m) {
     if (!m.embed.ptr || m.image_extent[0] <= 0) throw except("Missing image embeds, call sam_encode() first");
 }
 
-} // namespace
-
-image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
-    samdec_weights const& D = m.dec;
-    if (n_prompt != 2 && n_prompt != 4) throw except("sam: bad number of arguments (%d), must be 2 or 4", n_prompt);
-    sam_require_decoder(m);
-    device_turn turn(*m.backend);
-    void* s = m.backend->stream;
-    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = kSamTokens;
-    const int image_size = m.params.img_size, mask_size = 4 * res;
-
-    std::vector<uint16_t> tokens_h((size_t)8 * dim, 0);
-    sam_prompt_tokens(m, prompt, n_prompt, tokens_h.data());
-
-    // ---- scratch (f16 elements)
-    const size_t big = (size_t)Nk * dim, tok = (size_t)8 * dim;
-    workspace_layout layout;
-    auto take = [&](size_t elems) { return layout.take(elems * 2, 256); };
-    const size_t o_T = take(tok), o_Q = take(tok), o_t1 = take(tok), o_t2 = take(tok), o_h = take((size_t)8 * 2048 + 64);
-    const size_t o_K = take(big), o_k1 = take(big), o_k2 = take(big), o_pq = take(big), o_pk = take(big), o_pv = take(big), o_ao = take(big);
-    const size_t o_u1 = take((size_t)4 * Nk * D.up_c1), o_u1n = take((size_t)4 * Nk * D.up_c1), o_u2p = take((size_t)16 * Nk * D.up_c2), o_u2 = take((size_t)16 * Nk * D.up_c2 + 64);
-    const size_t o_hy = take((size_t)32 * 64), o_ha = take(tok), o_hb = take(tok), o_mask = take((size_t)16 * Nk * 8), o_iou = take(64);
-    const size_t o_scaled = take((size_t)image_size * image_size * 2 /* f32 */), o_out = take(((size_t)m.image_extent[0] * m.image_extent[1] + 1) / 2);
-    grow(m.dec_ws, layout.top, {s}, s);
-    uint8_t* base = static_cast<uint8_t*>(m.dec_ws.ptr);
-    auto P = [&](size_t off) { return static_cast<void*>(base + off); };
-    void *T = P(o_T), *Q = P(o_Q), *t1 = P(o_t1), *t2 = P(o_t2), *hbuf = P(o_h), *K = P(o_K), *k1 = P(o_k1), *k2 = P(o_k2);
-    void *pq = P(o_pq), *pk = P(o_pk), *pv = P(o_pv), *ao = P(o_ao), *u1 = P(o_u1), *u1n = P(o_u1n), *u2p = P(o_u2p), *u2 = P(o_u2);
-    void *hy = P(o_hy), *ha = P(o_ha), *hb = P(o_hb), *masks_d = P(o_mask), *iou_d = P(o_iou), *scaled = P(o_scaled), *mask_u8 = P(o_out);
-
-    tv_exec ex(m, s, m.weight_arena.ptr);
-    const bool timing = m.timing;
-    m.timing = false; // the per-group table belongs to the encoder
-    const uint8_t* wa = ex.wa;
-    VX(vx_memcpy_h2d(T, tokens_h.data(), tokens_h.size() * 2, s));
-    VX(vx_memcpy_d2d(Q, T, tok * 2, s));
-    // src = image_embeddings + dense prompt (no_mask_embed broadcast over the pixels), mobile-sam.cpp:437-440
-    VX(vx_add_rows_f16(m.embed.ptr, 1, wa + D.no_mask.off, dim, K, (int64_t)Nk * dim, s));
-    const void* KPE = wa + D.dense_pe.off;
-
-    auto linear = [&](packed_gemm const& g, const void* A, int M, void* out, int epi = VX_EPI_F16, const void* res1 = nullptr) {
-        ex.gemm(g, A, M, g.k_real, out, epi, res1, "decoder");
-    };
-    auto norm = [&](packed_vec const& w, packed_vec const& b, const void* x, void* y, long rows, int C) {
-        VX(vx_layernorm_f16(x, ex.vec(w), ex.vec(b), y, rows, C, 1e-5f, 0, 0, 0, s));
-    };
-    // decoder_attention (mobile-sam.cpp:306-320); out = [res1 +] out_proj(attention(q_proj(q), k_proj(k), v_proj(v)))
-    auto attention = [&](sam_attn_weights const& w, const void* q, int Nq, const void* k, const void* v, int Nkv, void* out, const void* res1) {
-        linear(w.q, q, Nq, pq);
-        linear(w.k, k, Nkv, pk);
-        linear(w.v, v, Nkv, pv);
-        VX(vx_small_attention_f16(pq, pk, pv, ao, Nq, Nkv, H, w.q.n_real / H, s));
-        linear(w.o, ao, Nq, out, res1 ? VX_EPI_F16_ADD : VX_EPI_F16, res1);
-    };
-    auto add = [&](const void* a, const void* b, void* y, long n) { VX(vx_add_rows_f16(a, 0, b, n, y, n, s)); };
-
-    for (size_t li = 0; li < D.layers.size(); ++li) { // two_way_attention_block (mobile-sam.cpp:322-364)
-        sam_twoway_weights const& L = D.layers[li];
-        if (li == 0) { // skip_first_layer_pe: queries = self_attn(queries)
-            attention(L.self_attn, Q, Nt, Q, Q, Nt, t2, nullptr);
-        } else {
-            add(Q, T, t1, (long)Nt * dim);
-            attention(L.self_attn, t1, Nt, t1, Q, Nt, t2, Q);
-        }
-        norm(L.norm_w[0], L.norm_b[0], t2, Q, Nt, dim);
-        add(Q, T, t1, (long)Nt * dim); // tokens attending to the image embedding
-        add(K, KPE, k1, (long)Nk * dim);
-        attention(L.t2i, t1, Nt, k1, K, Nk, t2, Q);
-        norm(L.norm_w[1], L.norm_b[1], t2, Q, Nt, dim);
-        linear(L.lin1, Q, Nt, hbuf, VX_EPI_F16_RELU); // mlp_block
-        linear(L.lin2, hbuf, Nt, t2, VX_EPI_F16_ADD, Q);
-        norm(L.norm_w[2], L.norm_b[2], t2, Q, Nt, dim);
-        add(Q, T, t1, (long)Nt * dim); // image embedding attending to the tokens (k1 = keys + key_pe from above)
-        attention(L.i2t, k1, Nk, t1, Q, Nt, k2, K);
-        norm(L.norm_w[3], L.norm_b[3], k2, K, Nk, dim);
-    }
-    add(Q, T, t1, (long)Nt * dim); // final attention from the points to the image (mobile-sam.cpp:386-392)
-    add(K, KPE, k1, (long)Nk * dim);
-    attention(D.final_attn, t1, Nt, k1, K, Nk, t2, Q);
-    norm(D.final_norm_w, D.final_norm_b, t2, Q, Nt, dim);
-
-    // upscale_outputs (mobile-sam.cpp:396-404): convT k2 s2 -> LayerNorm -> GELU -> convT k2 s2 -> GELU
-    auto conv_transpose = [&](packed_gemm const& g, const void* x, int hw, int cin, int cout, void* out) {
-        vx_gemm_args a = gemm_args(g, wa);
-        a.A = x; a.lda = cin;
-        a.M = hw * hw;
-        a.epi = VX_EPI_PIXSHUF; a.out = out; a.ldo = cout;
-        a.ps_s = 2; a.ps_Cout = cout; a.ps_H = hw; a.ps_W = hw;
-        VX(vx_gemm_f16(&a, s));
-    };
-    conv_transpose(D.up0, K, res, dim, D.up_c1, u1);
-    norm(D.up_norm_w, D.up_norm_b, u1, u1n, (long)4 * Nk, D.up_c1);
-    VX(vx_add_gelu_f16(u1n, nullptr, u1, (int64_t)4 * Nk * D.up_c1, s));
-    conv_transpose(D.up3, u1, 2 * res, D.up_c1, D.up_c2, u2p);
-    VX(vx_add_gelu_f16(u2p, nullptr, u2, (int64_t)16 * Nk * D.up_c2, s));
-
-    // hypernetwork MLPs on the four mask tokens -> hyper_in rows (a [32][64] f16 operand, zero padded)
-    auto raw_gemm = [&](const void* A, int M, int lda, const void* W, const float* bias, int N, int Kp, int n_valid, void* out, int ldo, int epi) {
-        vx_gemm_args a;
-        memset(&a, 0, sizeof a);
-        a.A = A; a.lda = lda; a.W = W; a.bias = bias; a.M = M; a.N = N; a.K = Kp; a.n_valid = n_valid; a.epi = epi; a.out = out; a.ldo = ldo;
-        VX(vx_gemm_f16(&a, s));
-    };
-    for (int i = 0; i < 4; ++i) {
-        const uint8_t* tok_i = static_cast<const uint8_t*>(Q) + (size_t)(1 + i) * dim * 2;
-        linear(D.hyper[i][0], tok_i, 1, ha, VX_EPI_F16_RELU);
-        linear(D.hyper[i][1], ha, 1, hb, VX_EPI_F16_RELU);
-        vx_gemm_args a = gemm_args(D.hyper[i][2], wa);
-        a.A = hb; a.lda = D.hyper[i][2].k_real; a.M = 1;
-        a.epi = VX_EPI_F16; a.out = static_cast<uint8_t*>(hy) + (size_t)i * 64 * 2; a.ldo = 64;
-        VX(vx_gemm_f16(&a, s));
-    }
-    // masks[i][pixel] = <upscaled[pixel], hyper_in[i]> (mobile-sam.cpp:472-473): M = 16 Nk pixels, K = up_c2, 4 of 8 stored columns real
-    raw_gemm(u2, 16 * Nk, D.up_c2, hy, nullptr, 32, 64, 8, masks_d, 8, VX_EPI_F16);
-    // iou prediction head on the iou token (mobile-sam.cpp:476-481): three small linears on ONE token whose output decides
-    // which mask is returned (vision.cpp:80-82), so it runs in f32 on the host from the token's values: an f16 pipeline
-    // (ulp 5e-4 near 1) can flip the choice between near-tied predictions and return an entirely different mask
-    const size_t n_px = (size_t)mask_size * mask_size;
-    (void)iou_d;
-    {
-        std::vector<uint16_t> t16((size_t)dim);
-        VX(vx_memcpy_d2h(t16.data(), Q, t16.size() * 2, s));
-        VX(vx_stream_sync(s));
-        std::vector<float> cur((size_t)dim), nxt;
-        for (int i = 0; i < dim; ++i) cur[(size_t)i] = f16_to_f32(t16[(size_t)i]);
-        for (int l = 0; l < 3; ++l) {
-            packed_gemm const& g = D.iou_head[l];
-            nxt.assign((size_t)g.n_real, 0.0f);
-            for (int n = 0; n < g.n_real; ++n) {
-                float acc = 0.0f;
-                const float* wr = D.iou_w[l].data() + (size_t)n * g.k_real;
-                for (int k = 0; k < g.k_real; ++k) acc += wr[k] * cur[(size_t)k];
-                acc += D.iou_b[l][(size_t)n];
-                nxt[(size_t)n] = l < 2 ? std::max(acc, 0.0f) : acc;
-            }
-            cur.swap(nxt);
-        }
-        for (int i = 0; i < 4; ++i) m.last_iou[i] = cur[(size_t)i];
-    }
-    // the decoder's only host decision: best of the FIRST THREE masks by predicted iou (vision.cpp:80-82)
-    const int idx = int(std::max_element(m.last_iou, m.last_iou + 3) - m.last_iou);
-    // sam_process_mask (mobile-sam.cpp:556-583): mask -> image_size^2, crop to the scaled extent, resize to the image, threshold
-    const i32x2 target = m.image_extent;
-    const float up = float(image_size) / float(std::max(target[0], target[1]));
-    const int sw = int(target[0] * up + 0.5f), sh = int(target[1] * up + 0.5f);
-    VX(vx_sam_interpolate(static_cast<const uint16_t*>(masks_d) + idx, 1, mask_size, mask_size, mask_size, 8, scaled, image_size, image_size, 0, s));
-    VX(vx_sam_interpolate(scaled, 0, sw, sh, image_size, 1, mask_u8, target[0], target[1], 1, s));
-    image_data out = image_alloc(target, image_format::alpha_u8);
-    VX(vx_memcpy_d2h(out.data.get(), mask_u8, (size_t)target[0] * target[1], s));
-    if (m.captures) { // test hook: the four logit planes (f16-rounded)
-        std::vector<uint16_t> mh(n_px * 8);
-        VX(vx_memcpy_d2h(mh.data(), masks_d, mh.size() * 2, s));
-        VX(vx_stream_sync(s));
-        m.last_masks.resize(4 * n_px);
-        for (size_t px = 0; px < n_px; ++px)
-            for (int i = 0; i < 4; ++i) m.last_masks[(size_t)i * n_px + px] = f16_to_f32(mh[px * 8 + i]);
-    } else {
-        m.last_masks.clear();
-    }
-    VX(vx_stream_sync(s));
-    m.timing = timing;
-    return out;
-}
-
-// ---- many prompts per embedding: the decoder above with the prompt index folded into the rows of its launches ---------------------
-
-void sam_set_prompt_chunk(sam_model& m, int n) {
-    if (n < 1 || n > 256) throw except("sam: prompt chunk %d is outside 1 .. 256", n);
-    m.prompt_chunk = n;
-}
-
-namespace {
-
 // what the launches behind a chunk's mask product need of the decode: the stream, the maps the masks pass through and the extents
 struct sam_decode_ctx {
     void* s = nullptr;
@@ -668,12 +501,13 @@ struct sam_decode_ctx {
     i32x2 target = {{0, 0}};
 };
 
-// The batched decode both sam_compute_batch_device and sam_generate_masks_device run: the prompt tokens of the call, layer 0's shared image side, then per
+// The decoder, which sam_compute, sam_compute_batch_* and sam_generate_masks_* all run: the prompt tokens of the call, layer 0's shared image side, then per
 // chunk the decoder, the mask product and the iou head. The logits of a chunk go to the chunk buffer of the workspace, or, with logits_all, to
-// [p0 ..] of a buffer that keeps the planes of every prompt; after_chunk(ctx, p0, B, logits, iou, chosen) launches what follows them.
+// [p0 ..] of a buffer that keeps the planes of every prompt; after_chunk(ctx, p0, B, logits, iou, chosen) launches what follows them. With captures on,
+// `kept` receives the logits and iou predictions of every prompt (a synchronisation per chunk); with captures off it is emptied.
 template <class F>
 sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* logits_all, void* iou_dev, void* chosen_dev, void* stream,
-                                  F&& after_chunk) {
+                                  sam_kept_logits& kept, F&& after_chunk) {
     samdec_weights const& D = m.dec;
     if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
     for (int i = 0; i < n; ++i)
@@ -769,13 +603,8 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
     const i32x2 target = m.image_extent;
     const float up = float(image_size) / float(std::max(target[0], target[1]));
     const int sw = int(target[0] * up + 0.5f), sh = int(target[1] * up + 0.5f);
-    if (m.captures) {
-        m.last_batch_masks.assign((size_t)n * 4 * n_px, 0.0f);
-        m.last_batch_iou.assign((size_t)n * 4, 0.0f);
-    } else {
-        m.last_batch_masks.clear();
-        m.last_batch_iou.clear();
-    }
+    kept.masks.assign(m.captures ? (size_t)n * 4 * n_px : 0, 0.0f);
+    kept.iou.assign(m.captures ? (size_t)n * 4 : 0, 0.0f);
 
     sam_decode_ctx ctx;
     ctx.s = s; ctx.scaled = static_cast<float*>(scaled); ctx.Bmax = Bmax; ctx.image_size = image_size; ctx.mask_size = mask_size; ctx.sw = sw; ctx.sh = sh;
@@ -859,7 +688,9 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
         // masks[b][i][pixel] = <upscaled[b][pixel], hyper_in[b][i]> (mobile-sam.cpp:472-473): four planes of 16 Nk logits per prompt
         void* logits = logits_all ? static_cast<uint8_t*>(logits_all) + (size_t)p0 * 4 * n_px * 2 : masks_d;
         VX(vx_mul_mat_f16(u2, hy, logits, 16 * (int64_t)Nk, 4, D.up_c2, B, B, s));
-        // iou prediction head on the iou token (row 0 of each prompt's seven) in f32, and the choice among the first three (vision.cpp:80-82)
+        // iou prediction head on the iou token (row 0 of each prompt's seven; mobile-sam.cpp:476-481), and the choice among the first three (vision.cpp:80-82).
+        // Three small linears on ONE token whose output decides which mask is returned, so they run in f32 from the token's values: an f16 pipeline
+        // (ulp 5e-4 near 1) can flip the choice between near-tied predictions and return an entirely different mask
         float* iou_out = iou_dev ? static_cast<float*>(iou_dev) + (size_t)p0 * 4 : static_cast<float*>(iou_ws);
         int32_t* chosen_out = chosen_dev ? static_cast<int32_t*>(chosen_dev) + p0 : static_cast<int32_t*>(chosen_ws);
         const uint8_t* ih = static_cast<const uint8_t*>(m.iou_head_dev.ptr);
@@ -870,23 +701,21 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
         if (m.captures) { // test hook: the four logit planes (f16-rounded) and the iou predictions of every prompt
             std::vector<uint16_t> mh((size_t)B * 4 * n_px);
             VX(vx_memcpy_d2h(mh.data(), logits, mh.size() * 2, s));
-            VX(vx_memcpy_d2h(m.last_batch_iou.data() + (size_t)p0 * 4, iou_out, (size_t)B * 16, s));
+            VX(vx_memcpy_d2h(kept.iou.data() + (size_t)p0 * 4, iou_out, (size_t)B * 16, s));
             VX(vx_stream_sync(s));
-            float* dst = m.last_batch_masks.data() + (size_t)p0 * 4 * n_px;
+            float* dst = kept.masks.data() + (size_t)p0 * 4 * n_px;
             for (size_t i = 0; i < mh.size(); ++i) dst[i] = f16_to_f32(mh[i]);
         }
     }
     return ctx;
 }
 
-} // namespace
-
-void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream) {
-    if (!prompts || !n_args || !masks_u8_dev) throw except("sam: null argument");
+// the decode with sam_process_mask (mobile-sam.cpp:556-583) on each prompt's chosen plane: masks u8 [n][h][w], iou, chosen on the device
+void sam_decode_masks(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream,
+                      sam_kept_logits& kept) {
     device_turn turn(*m.backend);
     const size_t out_px = (size_t)m.image_extent[0] * m.image_extent[1];
-    // sam_process_mask (mobile-sam.cpp:556-583) on each prompt's chosen plane
-    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, nullptr, iou_dev, chosen_dev, stream,
+    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, nullptr, iou_dev, chosen_dev, stream, kept,
                                             [&](sam_decode_ctx const& c, int p0, int B, void* logits, float*, int32_t* chosen) {
         VX(vx_sam_process_masks(logits, 4 * c.n_px, c.n_px, 1, c.mask_size, 4, chosen, c.scaled, c.image_size, c.sw, c.sh,
                                 static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, c.target[0], c.target[1], B, c.s));
@@ -894,22 +723,45 @@ void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t cons
     if (!stream) VX(vx_stream_sync(ctx.s));
 }
 
-void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen) {
-    if (!prompts || !n_args || !masks_u8) throw except("sam: null argument");
-    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
-    sam_require_decoder(m);
+// The host entries (their callers have checked the decoder and n): masks, iou and chosen into `stage` on the device's stream, then what the caller asked for
+// to the host. `stage` grows to what the call needs; every use of it ends synchronised, so nothing in flight holds it.
+void sam_decode_masks_to_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen, device_buffer& stage,
+                              sam_kept_logits& kept) {
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
     const size_t mask_bytes = (size_t)n * m.image_extent[0] * m.image_extent[1];
     workspace_layout lay;
     const size_t o_m = lay.take(mask_bytes), o_i = lay.take((size_t)n * 16), o_c = lay.take((size_t)n * 4);
-    device_buffer out(lay.top);
-    uint8_t* base = static_cast<uint8_t*>(out.ptr);
-    sam_compute_batch_device(m, prompts, n_args, n, base + o_m, base + o_i, base + o_c, s);
-    VX(vx_memcpy_d2h(masks_u8, base + o_m, mask_bytes, s));
+    grow(stage, lay.top, {});
+    uint8_t* base = static_cast<uint8_t*>(stage.ptr);
+    sam_decode_masks(m, prompts, n_args, n, base + o_m, base + o_i, base + o_c, s, kept);
+    VX(vx_memcpy_d2h(masks_u8, base + o_m, mask_bytes, s)); // waits for the stream
     if (iou) VX(vx_memcpy_d2h(iou, base + o_i, (size_t)n * 16, s));
     if (chosen) VX(vx_memcpy_d2h(chosen, base + o_c, (size_t)n * 4, s));
-    VX(vx_stream_sync(s));
+}
+
+} // namespace
+
+image_data sam_compute(sam_model& m, int const* prompt, int n_prompt) {
+    if (n_prompt != 2 && n_prompt != 4) throw except("sam: bad number of arguments (%d), must be 2 or 4", n_prompt);
+    sam_require_decoder(m);
+    const int32_t args[4] = {prompt[0], prompt[1], n_prompt == 4 ? prompt[2] : 0, n_prompt == 4 ? prompt[3] : 0}, n_args = n_prompt;
+    image_data out = image_alloc(m.image_extent, image_format::alpha_u8);
+    sam_decode_masks_to_host(m, args, &n_args, 1, out.data.get(), nullptr, nullptr, m.single_out, m.last_single); // the device side of the mask stays with the model
+    return out;
+}
+
+void sam_compute_batch_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream) {
+    if (!prompts || !n_args || !masks_u8_dev) throw except("sam: null argument");
+    sam_decode_masks(m, prompts, n_args, n, masks_u8_dev, iou_dev, chosen_dev, stream, m.last_batch);
+}
+
+void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen) {
+    if (!prompts || !n_args || !masks_u8) throw except("sam: null argument");
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
+    sam_require_decoder(m);
+    device_buffer stage; // of this call
+    sam_decode_masks_to_host(m, prompts, n_args, n, masks_u8, iou, chosen, stage, m.last_batch);
 }
 
 // ---- automatic mask generation: the batched decode with every prompt's planes kept, scored per chunk, then rank + NMS and the masks that survive ------
@@ -962,7 +814,7 @@ void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t con
         ~event_list() { for (void* e : ev) vx_event_destroy(e); }
     } marks{{}, s, m.timing};
     marks.mark();
-    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, logits_all, iou, nullptr, stream,
+    sam_decode_ctx ctx = sam_decode_prompts(m, prompts, n_args, n, logits_all, iou, nullptr, stream, m.last_batch,
                                             [&](sam_decode_ctx const& c, int p0, int B, void* logits, float*, int32_t*) {
         // the part of the plane the image occupies: SAM scores at image resolution, this scores the decoder's own logits
         const int cw = (c.sw * c.mask_size + c.image_size - 1) / c.image_size, ch = (c.sh * c.mask_size + c.image_size - 1) / c.image_size;

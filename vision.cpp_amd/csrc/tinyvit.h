@@ -1,7 +1,8 @@
 // TinyViT image encoder of MobileSAM on the MI355X backend (BASELINE.json configs[4]): model
 // load (mobile-sam GGUF -> packed f16 weights), static schedule, batched executor. Mirrors sam_load_model / sam_encode
 // (reference src/visp/vision.cpp:26-52; graph src/visp/arch/mobile-sam.cpp:20-215, sam_process_input :533-547), and the
-// prompt encoder + mask decoder + mask post-processing behind sam_compute (vision.cpp:54-92, mobile-sam.cpp:207-583).
+// prompt encoder + mask decoder + mask post-processing (vision.cpp:54-92, mobile-sam.cpp:207-583): ONE decoder schedule with the
+// prompt index folded into its rows, behind sam_compute (one prompt), sam_compute_batch_* and sam_generate_masks_*.
 #pragma once
 #include <vector>
 
@@ -59,12 +60,13 @@ struct samdec_weights {
     packed_vec up_norm_w, up_norm_b;
     int up_c1 = 0, up_c2 = 0;
     packed_gemm hyper[4][3], iou_head[3];
-    // The prompt encoder's tables above and the iou head are host arithmetic: their f32 values ALSO live in the weight arena
-    // (tables_off: gaussian | point_embed[4] | not_a_point | output_tokens = 11 dim floats; the iou head as its packed GEMMs),
-    // so that a rank whose arena arrived by RCCL broadcast (load_no_upload) rebuilds them in sam_weights_ready.
+    // The prompt encoder's tables above are host arithmetic: their f32 values ALSO live in the weight arena (tables_off: gaussian |
+    // point_embed[4] | not_a_point | output_tokens = 11 dim floats), so that a rank whose arena arrived by RCCL broadcast
+    // (load_no_upload) rebuilds them in sam_weights_ready; the f32 iou head of the device (sam_model::iou_head_dev) is made there too.
     size_t tables_off = SIZE_MAX;
-    std::vector<float> iou_w[3], iou_b[3]; // host f32 copies [n][k] of the f16-rounded iou head weights, biases
 };
+// test hook (captures on): the logit planes [n][4][mask_size^2] (f16-rounded) and the iou predictions [n][4] a decode left; empty with captures off
+struct sam_kept_logits { std::vector<float> masks, iou; };
 
 struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     sam_model() : model_base(family_sam) {}
@@ -74,9 +76,8 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     bool weights_uploaded = false;
     device_buffer ws;
     samdec_weights dec;
-    device_buffer dec_ws;         // decoder scratch
-    std::vector<float> last_masks; // [4][mask_size^2] logits of the last sam_compute (f16-rounded), and their iou predictions
-    float last_iou[4] = {0, 0, 0, 0};
+    sam_kept_logits last_single;  // of the last sam_compute (n = 1), for visp_sam_read_masks
+    device_buffer single_out;     // sam_compute's mask on the device, on its way to the host
     device_buffer embed;          // image embedding of the last sam_encode: f32 [64, 64, 256] (NHWC)
     i32x2 image_extent = {{0, 0}}; // extent of the image passed to sam_encode (vision.h sam_model::image_extent)
     // BASELINE.json configs[4] ("fp8 GGUF weights on CDNA4 fp8 MFMA"), opt-in and never the default: the MLPs of the transformer stages
@@ -84,18 +85,18 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // quantised per token on the way in. The decision on accuracy stands (tests/test_fp8_decision.py: mask IoU below the bar); this is the measured form of it.
     bool fp8_mlp = false;
     device_buffer fp8_arena, fp8_ws;
-    // many prompts per embedding (sam_compute_batch_device): a workspace of its own, sized for one chunk of prompts, so that dec_ws and with it
-    // the single-prompt path stay as they are
+    // the decoder (sam_compute is a batch of one, sam_compute_batch_*, sam_generate_masks_*): prompts run in chunks of prompt_chunk, the workspace is
+    // sized for one chunk of the largest call so far
     int prompt_chunk = 64;
     device_buffer batch_ws;
-    device_buffer iou_head_dev;            // f32 [w0 | b0 | w1 | b1 | w2 | b2] of dec.iou_w / iou_b, uploaded by sam_weights_ready
+    device_buffer iou_head_dev;            // f32 [w0 | b0 | w1 | b1 | w2 | b2]: the f16-rounded iou head, uploaded by sam_weights_ready
     size_t iou_head_off[6] = {0, 0, 0, 0, 0, 0}; // byte offsets into it
     void* prompt_tokens_host = nullptr;    // pinned: the prompt tokens of one call, f16 [n][7][dim]
     size_t prompt_tokens_bytes = 0;
     void* prompt_tokens_event = nullptr;   // recorded behind their upload: the next call waits for it before it overwrites them
-    std::vector<float> last_batch_masks, last_batch_iou; // captures: [n][4][mask_size^2] logits (f16-rounded) and [n][4] of the last batch or generate call
+    sam_kept_logits last_batch;            // of the last batch or generate call, for visp_sam_read_masks_batch; a sam_compute in between leaves it alone
     // automatic mask generation (sam_generate_masks_device): the logit planes and iou predictions of every prompt of the call, the selection stage's tables
-    // and the NMS workspace. A buffer of its own: batch_ws and with it sam_compute_batch_* stay as they are.
+    // and the NMS workspace, next to the decoder's batch_ws
     device_buffer generate_ws;
     float generate_split_ms[4] = {0, 0, 0, 0}; // with timing enabled: the last generate call's {decode, scoring, rank + NMS, output masks} by events
     ~sam_model() override;
@@ -111,7 +112,8 @@ void sam_encode_batch_host(sam_model&, uint8_t const* rgb, int batch, float* out
 // square (sam_process_input); the embedding stays on the device in model.embed
 void sam_encode(sam_model&, image_view image);
 // reference API (vision.cpp:54-92): point (n = 2) or box (n = 4) in pixels of the image given to sam_encode -> alpha_u8 mask
-// at that image's extent (best of the first three masks by predicted iou)
+// at that image's extent (best of the first three masks by predicted iou). A batch of one prompt through the decoder of
+// sam_compute_batch_*: the same bytes as that call with this prompt alone; one synchronisation, at the end.
 image_data sam_compute(sam_model&, int const* prompt, int n);
 // n prompts on the embedding of the last sam_encode in one batched pass. prompts host [n][4], n_args host [n] (2 = point, 4 = box); device outputs
 // masks u8 [n][h][w] at the encoded image's extent, iou f32 [n][4], chosen i32 [n] (the last two nullable). Runs in chunks of m.prompt_chunk prompts;
