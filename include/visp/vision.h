@@ -193,6 +193,20 @@ inline void image_erosion(image_view const& src, image_span const& dst, int radi
     detail::check(visp_image_erosion(nullptr, &in, radius, &out, &owner));
     detail::take_into(out, owner, dst, "image_erosion");
 }
+// not in the reference's header: SAM's remove_small_regions on an alpha_u8 mask, in place on the device (non-zero = foreground, 8-connectivity). Components of
+// fewer than min_area pixels go: holes (background) become 255, islands (foreground) 0 -- but where every island is small the largest stays --, `both` the
+// holes first. Returns whether a pixel changed.
+enum class region_mode { holes = VISP_REGIONS_HOLES, islands = VISP_REGIONS_ISLANDS, both = VISP_REGIONS_BOTH };
+inline bool image_remove_small_regions(image_span const& mask, int min_area, region_mode mode = region_mode::both) {
+    if (mask.format != image_format::alpha_u8) throw exception("image_remove_small_regions: expected an alpha_u8 mask");
+    const size_t w = size_t(mask.extent[0]), h = size_t(mask.extent[1]);
+    std::vector<uint8_t> packed(w * h);
+    for (size_t y = 0; y < h; ++y) std::memcpy(packed.data() + y * w, static_cast<uint8_t const*>(mask.data) + y * size_t(mask.stride), w);
+    int32_t changed = 0;
+    detail::check(visp_image_remove_small_regions_host(packed.data(), 1, mask.extent[0], mask.extent[1], min_area, int32_t(mode), &changed, nullptr));
+    for (size_t y = 0; y < h; ++y) std::memcpy(static_cast<uint8_t*>(mask.data) + y * size_t(mask.stride), packed.data() + y * w, w);
+    return changed != 0;
+}
 // image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
 inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
     visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};
@@ -525,6 +539,9 @@ struct sam_generate_params { // SAM's defaults
     float stability_offset = 1.0f;
     float nms_iou_thresh = 0.7f;
     int max_masks = 256;
+    // SAM's min_mask_region_area: above 0, holes and islands of fewer pixels are removed from the masks on the device and a second NMS runs
+    // (postprocess_small_regions); unchanged masks then come first and changed ones behind them, each by predicted iou -- not the order without cleaning
+    int min_mask_region_area = 0;
 };
 struct sam_mask {
     image_data segmentation;   // alpha_u8 at the encoded image's extent, 0 / 255
@@ -532,18 +549,23 @@ struct sam_mask {
     i32x2 bbox_top_left{0, 0}, bbox_extent{0, 0}; // of those pixels; 0, 0, 0, 0 for an empty mask
     float predicted_iou = 0, stability_score = 0;
     int prompt = 0, plane = 0; // which prompt of the call and which of its three logit planes
+    bool cleaned = false;      // min_mask_region_area changed a pixel of it
 };
 namespace detail {
 inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t> const& prompts, int32_t n_args, sam_generate_params const& p) {
     const int32_t n = int32_t(prompts.size() / 4), cap = int32_t(p.max_masks);
-    int32_t w = 0, h = 0, counts[2] = {0, 0};
+    int32_t w = 0, h = 0, counts[4] = {0, 0, 0, 0};
     check(visp_sam_image_extent(model.handle, &w, &h));
     const size_t px = size_t(w) * size_t(h), rows = size_t(cap > 0 ? cap : 0);
     std::vector<int32_t> n_arg(size_t(n), n_args), info_i(rows * 8);
     std::vector<uint8_t> masks(rows * px);
     std::vector<float> info_f(rows * 2);
-    check(visp_sam_generate_masks_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh, cap,
-                                       masks.data(), info_i.data(), info_f.data(), counts));
+    if (p.min_mask_region_area != 0)
+        check(visp_sam_generate_masks_clean_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh,
+                                                 cap, p.min_mask_region_area, masks.data(), info_i.data(), info_f.data(), counts));
+    else
+        check(visp_sam_generate_masks_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh, cap,
+                                           masks.data(), info_i.data(), info_f.data(), counts));
     std::vector<sam_mask> out;
     for (int32_t k = 0; k < counts[0]; ++k) {
         sam_mask s;
@@ -554,6 +576,7 @@ inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t>
         s.bbox_top_left = i32x2{r[2], r[3]};
         s.bbox_extent = i32x2{r[4], r[5]};
         s.area = r[6];
+        s.cleaned = r[7] != 0;
         s.predicted_iou = info_f[size_t(k) * 2];
         s.stability_score = info_f[size_t(k) * 2 + 1];
         out.push_back(std::move(s));

@@ -294,6 +294,29 @@ VISP_API int32_t visp_sam_generate_masks_device(visp_model* m, int32_t const* pr
 VISP_API int32_t visp_sam_generate_masks_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
                                               float stability_offset, float nms_iou_thresh, int32_t capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
                                               int32_t* counts);
+/* The generate calls with SAM's min_mask_region_area (postprocess_small_regions), all on the device. min_region_area = 0: exactly the launches and the bytes of
+ * the entries above (counts [2] written). min_region_area > 0: the first k = min(kept, capacity) masks are produced exactly as above, then
+ *  1. cleaned as visp_image_remove_small_regions_device cleans them (mode 3: holes, then islands, components below min_region_area pixels, 8-connectivity);
+ *  2. area and box are taken again from the cleaned masks;
+ *  3. a second greedy NMS runs over the k with SAM's scores, 1 for an unchanged mask and 0 for a changed one, equal scores in first-stage rank order (torchvision
+ *     leaves that tie open), on the inclusive boxes of the cleaned masks in image pixels [x, y, x + w - 1, y + h - 1] ([0, 0, 0, 0] for an empty mask), with the
+ *     arithmetic and the nms_iou_thresh of the first NMS;
+ *  4. the survivors come out in SAM's order: unchanged masks first, then changed ones, each group by predicted iou. THIS IS NOT THE ORDER WITHOUT CLEANING.
+ * info_i32 column 7 is 1 for a changed mask; counts i32 [4] = {returned, kept by the first NMS before the capacity cut, returned masks that cleaning changed,
+ * masks the second NMS removed}. The first NMS still runs on the boxes of the logit grid (the difference from SAM stated above). Memory: the k masks are staged
+ * on the device next to the logits (capacity * h * w bytes, 256 MB for 256 masks of 1024^2: the reordering needs them somewhere other than their final place)
+ * and pass through a labelling workspace 64 masks at a time (8 bytes per pixel each, 512 MB at 1024^2). Waits for the host where the entries above do. */
+VISP_API int32_t visp_sam_generate_masks_clean_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh,
+                                                      float stability_thresh, float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area,
+                                                      void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream);
+/* the same with host outputs (counts i32 [4]; with min_region_area = 0 only its first two are written); blocks */
+VISP_API int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                                    float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, uint8_t* masks_u8,
+                                                    int32_t* info_i32, float* info_f32, int32_t* counts);
+/* diagnostics, as visp_sam_generate_last_split: its four figures and a fifth, the cleaning stage of the last call (0 without one); and that stage alone as
+ * {clean, records + second NMS, gather} */
+VISP_API int32_t visp_sam_generate_last_split5(visp_model const* m, float out_ms[5]);
+VISP_API int32_t visp_sam_generate_last_clean_split(visp_model const* m, float out_ms[3]);
 /* diagnostics: with visp_sam_enable_timing on, a generate call records events around its stages and waits for them; this reads the last call's
  * {decode, scoring, rank + NMS, output masks and their records} in ms */
 VISP_API int32_t visp_sam_generate_last_split(visp_model const* m, float out_ms[4]);
@@ -342,6 +365,22 @@ VISP_API int32_t visp_birefnet_cutout(visp_model* m, visp_image_view const* imag
 VISP_API int32_t visp_image_blur(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data);
 /* image_erosion: minimum over the clamped (2 radius + 1)^2 neighbourhood; alpha_u8 or alpha_f32; bit-exact; 1 <= radius <= 64 */
 VISP_API int32_t visp_image_erosion(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data);
+/* SAM's remove_small_regions on n u8 masks [n][h][w] in place, for masks from visp_sam_compute_batch_device, BiRefNet or anywhere else. A pixel is foreground iff
+ * its byte is non-zero; 8-connectivity; a component is small iff it has fewer than min_area (>= 0) pixels. mode VISP_REGIONS_HOLES (1): every small component of
+ * the background becomes 255, none exempt for touching the border; VISP_REGIONS_ISLANDS (2): every small component of the foreground becomes 0, but where every
+ * one is small the largest stays (of equal ones the one whose first pixel in row-major order comes first); VISP_REGIONS_BOTH (3): the holes, then the islands of
+ * the result (SAM's order: a filled hole can join two small islands into one that stays). Only flipped pixels are written. changed i32 [n] (nullable): 1 where a
+ * pixel of the mask flipped. masks and changed are DEVICE pointers; stream NULL = the stream of `dev`; dev NULL = the calling thread's current device. The
+ * labelling workspace (8 bytes per pixel and mask in flight, at most 256 MB) is allocated per CALL and freed behind a synchronisation: the call returns with
+ * the work done. Every argument check happens before anything touches a device. */
+#define VISP_REGIONS_HOLES 1
+#define VISP_REGIONS_ISLANDS 2
+#define VISP_REGIONS_BOTH 3
+VISP_API int32_t visp_image_remove_small_regions_device(void* masks_u8_dev, int32_t n, int32_t w, int32_t h, int32_t min_area, int32_t mode, void* changed_i32_dev,
+                                                        void* stream, visp_device const* dev);
+/* the same on host arrays: up, clean, down; blocks */
+VISP_API int32_t visp_image_remove_small_regions_host(uint8_t* masks_u8, int32_t n, int32_t w, int32_t h, int32_t min_area, int32_t mode, int32_t* changed_i32,
+                                                      visp_device const* dev);
 /* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
  * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
 VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,

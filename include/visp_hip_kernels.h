@@ -392,6 +392,32 @@ VX_API int vx_sam_process_masks_indexed(const void* planes, int64_t prompt_strid
  * when info_f32 is given, info_f32 [k][2] = {iou of the candidate, stability[candidate]}; rows at and behind counts[0] untouched. One block per mask. */
 VX_API int vx_sam_mask_stats_u8(const uint8_t* masks, int w, int h, const int32_t* keep_idx, const int32_t* counts, int capacity, int n_scored, int n_prompts,
                                 const float* iou, int iou_stride, const float* stability, int32_t* info_i32, float* info_f32, void* stream);
+/* ---- connected components of u8 masks: SAM's remove_small_regions on the device (kernels_regions.hip) ----
+ * masks u8 [n][h][w], any w, h >= 1, no alignment. A pixel is foreground iff its byte is non-zero; 8-connectivity; a component is small iff it has fewer than
+ * min_area (>= 0) pixels. VX_REGIONS_HOLES: every small component of the background becomes 255 (none is exempt for touching the border).
+ * VX_REGIONS_ISLANDS: every small component of the foreground becomes 0, except that where EVERY one is small the largest stays (of equal ones the one whose
+ * first pixel in row-major order comes first). VX_REGIONS_BOTH: the holes, then the islands of the result. Only flipped pixels are written; with min_area 0 or 1
+ * no mask byte is read or written. changed i32 [n] (nullable): 1 where a pixel of the mask flipped, else 0. counts (nullable): a device i32; masks at and behind
+ * counts[0] are neither read nor written, nor are their `changed`. The masks pass through the workspace `group` at a time: labels and areas i32 per pixel,
+ * vx_mask_regions_workspace_bytes(w, h, group) bytes (8 MB per mask in flight at 1024^2; 0 for arguments the launcher refuses), 16-byte aligned. Per group
+ * and step five or six launches; union-find, parents only decrease; integer min / add / max atomics only: the same bytes on every run. */
+#define VX_REGIONS_HOLES 1
+#define VX_REGIONS_ISLANDS 2
+#define VX_REGIONS_BOTH 3
+VX_API size_t vx_mask_regions_workspace_bytes(int w, int h, int group);
+VX_API int vx_mask_remove_small_regions_u8(uint8_t* masks, int w, int h, int n, const int32_t* counts, int min_area, int mode, int32_t* changed, void* workspace,
+                                           size_t workspace_bytes, int group, void* stream);
+/* The second NMS of SAM's postprocess_small_regions as an input of vx_sam_rank_nms (n_planes 1, iou_stride 1, pred_iou_thresh below 0, any stability threshold
+ * up to 1). info_i32 [N][8] as vx_sam_mask_stats_u8 writes it for the cleaned masks, changed i32 [N] -> table i32 [N][6] = {1, 1, the mask's inclusive box
+ * x, y, x + w - 1, y + h - 1 in image pixels, 0 0 0 0 for an empty mask}, key f32 [N] = 1 for an unchanged mask, 0 for a changed one, NaN (refused by the
+ * filter) for rows at and behind counts[0]. Equal keys rank by row, which is the first stage's rank. */
+VX_API int vx_sam_clean_nms_inputs(const int32_t* info_i32, const int32_t* changed, const int32_t* counts, int N, int32_t* table, float* key, void* stream);
+/* Output mask i < second_counts[0] = staged mask keep_idx[i] (clamped to 0 .. N - 1) with its rows, column 7 of info_i32 = 1 for a changed mask; masks u8
+ * [N][h][w], any alignment (16 bytes per thread where both buffers and h * w allow it). out_counts i32 [4] = {second_counts[0], first_counts[1], the returned
+ * masks with `changed` set, min(first_counts[0], N) - second_counts[1]}. Masks and rows at and behind the count are untouched. One launch. */
+VX_API int vx_sam_gather_clean_masks(const uint8_t* masks, int w, int h, const int32_t* info_i32, const float* info_f32, const int32_t* changed, const int32_t* keep_idx,
+                                     const int32_t* first_counts, const int32_t* second_counts, int N, uint8_t* out_masks, int32_t* out_info_i32, float* out_info_f32,
+                                     int32_t* out_counts, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

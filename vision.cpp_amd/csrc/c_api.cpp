@@ -804,6 +804,45 @@ int32_t visp_sam_generate_masks_host(visp_model* m, int32_t const* prompts, int3
     });
 }
 
+int32_t visp_sam_generate_masks_clean_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                             float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, void* masks_u8_dev,
+                                             void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream) {
+    return handle_errors([&]() {
+        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity); // before the handle: needs no model
+        sam_generate_check_region_area(min_region_area);
+        sam_generate_masks_clean_device(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area,
+                                        masks_u8_dev, info_i32_dev, info_f32_dev, counts_dev, stream);
+    });
+}
+
+int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                           float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, uint8_t* masks_u8, int32_t* info_i32,
+                                           float* info_f32, int32_t* counts) {
+    return handle_errors([&]() {
+        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+        sam_generate_check_region_area(min_region_area);
+        sam_generate_masks_clean_host(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area, masks_u8,
+                                      info_i32, info_f32, counts);
+    });
+}
+
+int32_t visp_sam_generate_last_split5(visp_model const* m, float out_ms[5]) {
+    return handle_errors([&]() {
+        if (!out_ms) throw except("sam: null argument");
+        sam_model const& sm = as_sam(m);
+        for (int i = 0; i < 4; ++i) out_ms[i] = sm.generate_split_ms[i];
+        out_ms[4] = sm.generate_split_ms[4] + sm.generate_split_ms[5] + sm.generate_split_ms[6];
+    });
+}
+
+int32_t visp_sam_generate_last_clean_split(visp_model const* m, float out_ms[3]) {
+    return handle_errors([&]() {
+        if (!out_ms) throw except("sam: null argument");
+        sam_model const& sm = as_sam(m);
+        for (int i = 0; i < 3; ++i) out_ms[i] = sm.generate_split_ms[4 + i];
+    });
+}
+
 int32_t visp_sam_generate_last_split(visp_model const* m, float out_ms[4]) {
     return handle_errors([&]() {
         if (!out_ms) throw except("sam: null argument");
@@ -913,6 +952,23 @@ int32_t visp_image_blur(visp_device const* dev, visp_image_view const* src, int3
     return handle_errors([&]() {
         if (!out_image || !out_data) throw except("visp_image_blur: null argument");
         return_image(image_blur(dev, host_view("visp_image_blur", src), radius), out_image, out_data);
+    });
+}
+
+int32_t visp_image_remove_small_regions_device(void* masks_u8_dev, int32_t n, int32_t w, int32_t h, int32_t min_area, int32_t mode, void* changed_i32_dev, void* stream,
+                                               visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!masks_u8_dev) throw except("visp_image_remove_small_regions_device: null argument");
+        check_remove_small_regions(n, w, h, min_area, mode);
+        remove_small_regions_device(dev, masks_u8_dev, n, w, h, min_area, mode, changed_i32_dev, stream);
+    });
+}
+
+int32_t visp_image_remove_small_regions_host(uint8_t* masks_u8, int32_t n, int32_t w, int32_t h, int32_t min_area, int32_t mode, int32_t* changed_i32, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!masks_u8) throw except("visp_image_remove_small_regions_host: null argument");
+        check_remove_small_regions(n, w, h, min_area, mode);
+        remove_small_regions_host(dev, masks_u8, n, w, h, min_area, mode, changed_i32);
     });
 }
 

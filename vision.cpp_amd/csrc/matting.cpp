@@ -1,5 +1,6 @@
 #include "matting.h"
 
+#include <algorithm>
 #include <optional>
 
 #include "visp_util.h"
@@ -138,6 +139,38 @@ image_data image_estimate_foreground(backend_device const* dev, image_view const
     device_buffer i = upload(pi, on.stream), m = upload(pm, on.stream), out(n_bytes(img)), ws(foreground_workspace_bytes(1, w, h));
     estimate_foreground_batch(i.ptr, img.format, static_cast<float*>(m.ptr), 1, w, h, radius, out.ptr, image_format::rgba_f32, ws.ptr, on.stream);
     return download(out, img.extent, image_format::rgba_f32, on.stream);
+}
+
+void check_remove_small_regions(int n, int w, int h, int min_area, int mode) {
+    if (n < 1) throw except("remove_small_regions: empty batch of masks (n = %d)", n);
+    if (w < 1 || h < 1 || (int64_t)w * h > (int64_t(1) << 31) - 256) throw except("remove_small_regions: extent %dx%d", w, h);
+    if (min_area < 0) throw except("remove_small_regions: min_area %d is below 0", min_area);
+    if (mode < VX_REGIONS_HOLES || mode > VX_REGIONS_BOTH) throw except("remove_small_regions: unknown mode %d (1 holes, 2 islands, 3 both)", mode);
+}
+
+void remove_small_regions_device(backend_device const* dev, void* masks_dev, int n, int w, int h, int min_area, int mode, void* changed_dev, void* stream) {
+    if (!masks_dev) throw except("remove_small_regions: null pointer");
+    check_remove_small_regions(n, w, h, min_area, mode);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    const int64_t per_mask = (int64_t)w * h * 8; // labels and areas
+    const int group = (int)std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(256) << 20) / per_mask));
+    const size_t bytes = vx_mask_regions_workspace_bytes(w, h, group);
+    device_buffer ws(bytes);
+    VX(vx_mask_remove_small_regions_u8(static_cast<uint8_t*>(masks_dev), w, h, n, nullptr, min_area, mode, static_cast<int32_t*>(changed_dev), ws.ptr, bytes, group, s));
+    VX(vx_stream_sync(s));
+}
+
+void remove_small_regions_host(backend_device const* dev, uint8_t* masks, int n, int w, int h, int min_area, int mode, int32_t* changed) {
+    if (!masks) throw except("remove_small_regions: null pointer");
+    check_remove_small_regions(n, w, h, min_area, mode);
+    device_scope on(dev);
+    const size_t bytes = (size_t)n * w * h;
+    device_buffer m(bytes), c((size_t)n * 4);
+    VX(vx_memcpy_h2d(m.ptr, masks, bytes, on.stream));
+    remove_small_regions_device(dev, m.ptr, n, w, h, min_area, mode, c.ptr, on.stream);
+    VX(vx_memcpy_d2h(masks, m.ptr, bytes, on.stream));
+    if (changed) VX(vx_memcpy_d2h(changed, c.ptr, (size_t)n * 4, on.stream));
 }
 
 void birefnet_cutout_batch_device(birefnet_model& m, void const* rgb_dev, int B, int w, int h, int radius, void* rgba_dev, void* stream) {

@@ -24,6 +24,13 @@ void estimate_foreground_batch(void const* img, image_format img_format, float c
 void estimate_foreground_batch_device(backend_device const* dev, void const* img, image_format img_format, float const* mask, int B, int w, int h, int radius, void* out,
                                       image_format out_format, void* stream);
 
+// SAM's remove_small_regions on n u8 masks [n, h, w] (non-zero = foreground; vx_mask_remove_small_regions_u8): mode 1 fills the holes, 2 removes the islands, 3 both in
+// that order; changed i32 [n], nullable. The labelling workspace is allocated for the CALL (at most 256 MB: the masks pass through it in groups) and freed behind
+// a synchronisation of the stream, so both entries return with the work done.
+void check_remove_small_regions(int n, int w, int h, int min_area, int mode); // throws, touches no device
+void remove_small_regions_device(backend_device const* dev, void* masks_dev, int n, int w, int h, int min_area, int mode, void* changed_dev, void* stream);
+void remove_small_regions_host(backend_device const* dev, uint8_t* masks, int n, int w, int h, int min_area, int mode, int32_t* changed);
+
 // birefnet_compute_batch_device as it stands, then the estimator on the mask where it lies: rgb_u8 [B, h, w, 3] -> rgba_u8 [B, h, w, 4] cutout
 void birefnet_cutout_batch_device(birefnet_model& m, void const* rgb_dev, int B, int w, int h, int radius, void* rgba_dev, void* stream);
 void birefnet_cutout_batch_host(birefnet_model& m, uint8_t const* rgb, int B, int w, int h, int radius, uint8_t* rgba);

@@ -778,9 +778,18 @@ void sam_generate_check_args(int32_t const* prompts, int32_t const* n_args, int 
     if (capacity < 1) throw except("sam: capacity %d is below 1", capacity);
 }
 
-void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
-                               float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream) {
+void sam_generate_check_region_area(int min_region_area) {
+    if (min_region_area < 0) throw except("sam: min_region_area %d is below 0", min_region_area);
+}
+
+// masks in flight through the labelling workspace of the cleaning stage: labels and areas, 8 bytes per pixel each (512 MB at 1024^2)
+constexpr int kSamCleanGroup = 64;
+
+void sam_generate_masks_clean_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
+                                     float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, void* masks_u8_dev, void* info_i32_dev,
+                                     void* info_f32_dev, void* counts_dev, void* stream) {
     sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+    sam_generate_check_region_area(min_region_area);
     if (!masks_u8_dev || !info_i32_dev || !info_f32_dev || !counts_dev) throw except("sam: null argument");
     sam_require_decoder(m);
     device_turn turn(*m.backend);
@@ -792,6 +801,22 @@ void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t con
     const size_t o_logits = layout.take((size_t)n * 4 * n_px * 2, 256), o_iou = layout.take((size_t)n * 16, 256), o_table = layout.take((size_t)N * 24, 256);
     const size_t o_stab = layout.take((size_t)N * 4, 256), o_flags = layout.take((size_t)N * 4, 256), o_rank = layout.take((size_t)N * 4, 256);
     const size_t o_keep = layout.take((size_t)capacity * 4, 256), o_nms = layout.take(nms_bytes, 256);
+    // the cleaning stage (min_region_area > 0) needs the masks somewhere other than their final place, since its second NMS reorders them: the first stage's
+    // masks and records are staged here, capacity * h * w bytes (256 MB at 256 masks of 1024^2), next to the labelling workspace and the second NMS's tables
+    const bool clean = min_region_area > 0;
+    const size_t out_px = (size_t)m.image_extent[0] * m.image_extent[1];
+    const int N2 = std::min(capacity, N), clean_group = std::min(N2, kSamCleanGroup);
+    const size_t nms2_bytes = clean ? vx_sam_rank_nms_workspace_bytes(N2) : 0;
+    const size_t regions_bytes = clean ? vx_mask_regions_workspace_bytes(m.image_extent[0], m.image_extent[1], clean_group) : 0;
+    size_t o_smasks = 0, o_sinfo = 0, o_sinfof = 0, o_scounts = 0, o_changed = 0, o_table2 = 0, o_key2 = 0, o_flags2 = 0, o_rank2 = 0, o_keep2 = 0, o_counts2 = 0, o_nms2 = 0,
+           o_regions = 0;
+    if (clean) {
+        if (m.image_extent[0] <= 0) throw except("Missing image embeds, call sam_encode() first");
+        o_smasks = layout.take((size_t)N2 * out_px, 256), o_sinfo = layout.take((size_t)N2 * 32, 256), o_sinfof = layout.take((size_t)N2 * 8, 256);
+        o_scounts = layout.take(8, 256), o_changed = layout.take((size_t)N2 * 4, 256), o_table2 = layout.take((size_t)N2 * 24, 256), o_key2 = layout.take((size_t)N2 * 4, 256);
+        o_flags2 = layout.take((size_t)N2 * 4, 256), o_rank2 = layout.take((size_t)N2 * 4, 256), o_keep2 = layout.take((size_t)N2 * 4, 256), o_counts2 = layout.take(8, 256);
+        o_nms2 = layout.take(nms2_bytes, 256), o_regions = layout.take(regions_bytes, 256);
+    }
     grow(m.generate_ws, layout.top, {m.backend->stream, s});
     uint8_t* base = static_cast<uint8_t*>(m.generate_ws.ptr);
     void* logits_all = base + o_logits;
@@ -822,41 +847,70 @@ void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t con
         VX(vx_sam_score_planes_f16(logits, 4 * c.n_px, c.n_px, c.mask_size, 3, cw, ch, stability_offset, table + (size_t)p0 * 18, stab + (size_t)p0 * 3, B, c.s));
         marks.mark();
     });
-    VX(vx_sam_rank_nms(table, iou, 3, 4, N, pred_iou_thresh, stability_thresh, nms_iou_thresh, capacity, base + o_nms, nms_bytes, flags, rank, keep, counts, s));
+    // the first stage's outputs: the caller's buffers, or with cleaning the staging buffers (of min(capacity, N) masks: no more can come out)
+    uint8_t* masks1 = clean ? base + o_smasks : static_cast<uint8_t*>(masks_u8_dev);
+    int32_t *info1 = clean ? reinterpret_cast<int32_t*>(base + o_sinfo) : static_cast<int32_t*>(info_i32_dev), *counts1 = clean ? reinterpret_cast<int32_t*>(base + o_scounts) : counts;
+    float* infof1 = clean ? reinterpret_cast<float*>(base + o_sinfof) : static_cast<float*>(info_f32_dev);
+    const int cap1 = clean ? N2 : capacity;
+    VX(vx_sam_rank_nms(table, iou, 3, 4, N, pred_iou_thresh, stability_thresh, nms_iou_thresh, cap1, base + o_nms, nms_bytes, flags, rank, keep, counts1, s));
     marks.mark();
-    VX(vx_sam_process_masks_indexed(logits_all, 4 * ctx.n_px, ctx.n_px, 1, ctx.mask_size, 3, n, keep, counts, capacity, ctx.Bmax, ctx.scaled, ctx.image_size, ctx.sw, ctx.sh,
-                                    static_cast<uint8_t*>(masks_u8_dev), ctx.target[0], ctx.target[1], s));
-    VX(vx_sam_mask_stats_u8(static_cast<const uint8_t*>(masks_u8_dev), ctx.target[0], ctx.target[1], keep, counts, capacity, 3, n, iou, 4, stab,
-                            static_cast<int32_t*>(info_i32_dev), static_cast<float*>(info_f32_dev), s));
-    if (marks.on) { // {decode, scoring, rank + NMS, output masks and their records} in ms: events 0 | (before, behind a chunk's scoring) .. | behind NMS | end
+    VX(vx_sam_process_masks_indexed(logits_all, 4 * ctx.n_px, ctx.n_px, 1, ctx.mask_size, 3, n, keep, counts1, cap1, ctx.Bmax, ctx.scaled, ctx.image_size, ctx.sw, ctx.sh,
+                                    masks1, ctx.target[0], ctx.target[1], s));
+    VX(vx_sam_mask_stats_u8(masks1, ctx.target[0], ctx.target[1], keep, counts1, cap1, 3, n, iou, 4, stab, info1, infof1, s));
+    if (clean) { // SAM's postprocess_small_regions: clean, measure again, a second NMS with the scores 1 (unchanged) / 0 (changed), the survivors in its order
+        int32_t *changed = reinterpret_cast<int32_t*>(base + o_changed), *table2 = reinterpret_cast<int32_t*>(base + o_table2), *keep2 = reinterpret_cast<int32_t*>(base + o_keep2);
+        int32_t* counts2 = reinterpret_cast<int32_t*>(base + o_counts2);
+        float* key2 = reinterpret_cast<float*>(base + o_key2);
+        marks.mark();
+        VX(vx_mask_remove_small_regions_u8(masks1, ctx.target[0], ctx.target[1], N2, counts1, min_region_area, VX_REGIONS_BOTH, changed, base + o_regions, regions_bytes,
+                                           clean_group, s));
+        marks.mark();
+        VX(vx_sam_mask_stats_u8(masks1, ctx.target[0], ctx.target[1], keep, counts1, N2, 3, n, iou, 4, stab, info1, infof1, s));
+        VX(vx_sam_clean_nms_inputs(info1, changed, counts1, N2, table2, key2, s));
+        VX(vx_sam_rank_nms(table2, key2, 1, 1, N2, -1.0f, 0.0f, nms_iou_thresh, N2, base + o_nms2, nms2_bytes, reinterpret_cast<int32_t*>(base + o_flags2),
+                           reinterpret_cast<int32_t*>(base + o_rank2), keep2, counts2, s));
+        marks.mark();
+        VX(vx_sam_gather_clean_masks(masks1, ctx.target[0], ctx.target[1], info1, infof1, changed, keep2, counts1, counts2, N2, static_cast<uint8_t*>(masks_u8_dev),
+                                     static_cast<int32_t*>(info_i32_dev), static_cast<float*>(info_f32_dev), counts, s));
+    }
+    if (marks.on) { // {decode, scoring, rank + NMS, output masks and their records | clean, records + second NMS, gather} in ms: events 0 | (before, behind a chunk's
+                    // scoring) .. | behind NMS | behind the records [| behind the cleaning | behind the second NMS] | end
         marks.mark();
         float* out = m.generate_split_ms;
-        out[0] = out[1] = out[2] = out[3] = 0.0f;
-        const size_t last = marks.ev.size() - 1;
+        for (int i = 0; i < 7; ++i) out[i] = 0.0f;
+        const size_t last = marks.ev.size() - 1, tail = clean ? 5 : 2; // intervals behind the chunks
         for (size_t i = 1; i <= last; ++i) {
             float ms = 0.0f;
             VX(vx_event_elapsed_ms(marks.ev[i - 1], marks.ev[i], &ms));
-            out[i == last ? 3 : i == last - 1 ? 2 : (i & 1) ? 0 : 1] += ms;
+            out[i + tail > last ? 2 + (i + tail - last - 1) : (i & 1) ? 0 : 1] += ms;
         }
     }
     if (!stream) VX(vx_stream_sync(s));
 }
 
-void sam_generate_masks_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
-                             float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts) {
+void sam_generate_masks_device(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                               float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream) {
+    sam_generate_masks_clean_device(m, prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, 0, masks_u8_dev, info_i32_dev,
+                                    info_f32_dev, counts_dev, stream);
+}
+
+void sam_generate_masks_clean_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
+                                   float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
+                                   int32_t* counts) {
     sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
+    sam_generate_check_region_area(min_region_area);
     if (!masks_u8 || !info_i32 || !info_f32 || !counts) throw except("sam: null argument");
     sam_require_decoder(m);
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
     const size_t px = (size_t)m.image_extent[0] * m.image_extent[1];
     workspace_layout lay;
-    const size_t o_m = lay.take((size_t)capacity * px), o_i = lay.take((size_t)capacity * 32), o_f = lay.take((size_t)capacity * 8), o_c = lay.take(8);
+    const size_t o_m = lay.take((size_t)capacity * px), o_i = lay.take((size_t)capacity * 32), o_f = lay.take((size_t)capacity * 8), o_c = lay.take(16);
     device_buffer out(lay.top);
     uint8_t* base = static_cast<uint8_t*>(out.ptr);
-    sam_generate_masks_device(m, prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, base + o_m, base + o_i, base + o_f,
-                              base + o_c, s);
-    VX(vx_memcpy_d2h(counts, base + o_c, 8, s));
+    sam_generate_masks_clean_device(m, prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area, base + o_m,
+                                    base + o_i, base + o_f, base + o_c, s);
+    VX(vx_memcpy_d2h(counts, base + o_c, min_region_area > 0 ? 16 : 8, s));
     VX(vx_stream_sync(s));
     const size_t k = (size_t)std::min(std::max(counts[0], 0), capacity); // rows and masks behind the returned ones stay as the caller left them
     if (k) {
@@ -865,6 +919,12 @@ void sam_generate_masks_host(sam_model& m, int32_t const* prompts, int32_t const
         VX(vx_memcpy_d2h(info_f32, base + o_f, k * 8, s));
         VX(vx_stream_sync(s));
     }
+}
+
+void sam_generate_masks_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
+                             float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts) {
+    sam_generate_masks_clean_host(m, prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, 0, masks_u8, info_i32, info_f32,
+                                  counts);
 }
 
 } // namespace visp

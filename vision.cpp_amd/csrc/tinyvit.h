@@ -98,7 +98,8 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // automatic mask generation (sam_generate_masks_device): the logit planes and iou predictions of every prompt of the call, the selection stage's tables
     // and the NMS workspace, next to the decoder's batch_ws
     device_buffer generate_ws;
-    float generate_split_ms[4] = {0, 0, 0, 0}; // with timing enabled: the last generate call's {decode, scoring, rank + NMS, output masks} by events
+    // with timing enabled: the last generate call's {decode, scoring, rank + NMS, output masks | clean, records + second NMS, gather} by events
+    float generate_split_ms[7] = {0, 0, 0, 0, 0, 0, 0};
     ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
@@ -132,5 +133,19 @@ void sam_generate_masks_device(sam_model&, int32_t const* prompts, int32_t const
                                float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream);
 void sam_generate_masks_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
                              float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts);
+// The same with SAM's min_mask_region_area (postprocess_small_regions) behind the first stage: its first k = min(kept, capacity) masks, produced exactly as above
+// into a staging buffer in generate_ws (capacity * h * w bytes: the second NMS reorders them, so they cannot be cleaned in their final place), are cleaned
+// (vx_mask_remove_small_regions_u8: holes, then islands, below min_region_area pixels; 64 masks in flight, 8 bytes per pixel each), measured again, and passed
+// through a second greedy NMS on their inclusive image-pixel boxes with the scores 1 (unchanged) / 0 (changed), equal scores in first-stage order. The survivors
+// come out in that order -- unchanged masks first, then changed ones, each by predicted iou: NOT the order without cleaning --, info_i32 column 7 = 1 for a changed
+// mask, counts i32 [4] = {returned, kept by the first NMS, returned masks that cleaning changed, masks the second NMS removed}. min_region_area 0: exactly the
+// launches and bytes of the entries above (counts [2]). Nothing waits for the host beyond where those do.
+void sam_generate_check_region_area(int min_region_area);
+void sam_generate_masks_clean_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
+                                     float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, void* masks_u8_dev, void* info_i32_dev,
+                                     void* info_f32_dev, void* counts_dev, void* stream);
+void sam_generate_masks_clean_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
+                                   float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
+                                   int32_t* counts);
 
 } // namespace visp

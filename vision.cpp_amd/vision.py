@@ -364,29 +364,39 @@ class Model:
         return p, k, params
 
     def sam_generate_masks_raw(self, prompts=None, points_per_side: int = 32, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
-                               max_masks: int = 256):
+                               max_masks: int = 256, min_mask_region_area: int = 0):
         """The arrays of visp_sam_generate_masks_host, cut to the masks returned: (masks uint8 [k, h, w] of 0 / 255, info_i32 [k, 8] = {prompt, plane, x, y, w, h,
-        area, 0}, info_f32 [k, 2] = {predicted_iou, stability_score}, counts (returned, kept before the cut to max_masks))."""
+        area, 0}, info_f32 [k, 2] = {predicted_iou, stability_score}, counts (returned, kept before the cut to max_masks)).
+        min_mask_region_area > 0 (visp_sam_generate_masks_clean_host): holes and islands below that many pixels are removed on the device and a second NMS runs,
+        as SAM's postprocess_small_regions does; the masks then come in SAM's order, unchanged ones first and changed ones behind them, each by predicted iou --
+        not the order without cleaning --, info_i32 column 7 is 1 for a changed mask and counts is (returned, kept by the first NMS, returned masks that
+        cleaning changed, masks the second NMS removed)."""
         p, k, params = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
         n, cap = len(k), int(max_masks)
         w, h = self.sam_image_extent() if n and cap > 0 else (0, 0)
         masks, ii, fi = np.empty((max(cap, 0), h, w), np.uint8), np.empty((max(cap, 0), 8), np.int32), np.empty((max(cap, 0), 2), np.float32)
-        counts = np.zeros(2, np.int32)
-        check(self._api.visp_sam_generate_masks_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, masks.ctypes.data, ii.ctypes.data, fi.ctypes.data,
-                                                     counts.ctypes.data))
+        area = int(min_mask_region_area)
+        counts = np.zeros(4 if area else 2, np.int32)
+        if area:
+            check(self._api.visp_sam_generate_masks_clean_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, area, masks.ctypes.data, ii.ctypes.data,
+                                                               fi.ctypes.data, counts.ctypes.data))
+        else:
+            check(self._api.visp_sam_generate_masks_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, masks.ctypes.data, ii.ctypes.data, fi.ctypes.data,
+                                                         counts.ctypes.data))
         self._sam_batch_n = n
         r = int(counts[0])
-        return masks[:r], ii[:r], fi[:r], (r, int(counts[1]))
+        return masks[:r], ii[:r], fi[:r], (r, *(int(c) for c in counts[1:]))
 
     def sam_generate_masks(self, points_per_side: int = 32, prompts=None, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
-                           max_masks: int = 256):
-        """SAM's automatic mask generator on the last sam_encode (one crop layer, no crop-edge filter, no hole / island removal): the points_per_side^2 grid
+                           max_masks: int = 256, min_mask_region_area: int = 0):
+        """SAM's automatic mask generator on the last sam_encode (one crop layer, no crop-edge filter; min_mask_region_area as in SAM: holes and islands below
+        that many pixels are removed and a second NMS runs, after which unchanged masks come first and changed ones behind them): the points_per_side^2 grid
         of sam_point_grid, or `prompts` (points and boxes as for sam_compute_batch). Thresholds default to SAM's (sam_generate_defaults). Returns at most
         max_masks records in order of predicted iou, each a dict with SAM's keys: segmentation (bool [h, w]), area, bbox [x, y, w, h] (of the mask, image
         pixels), predicted_iou, stability_score, and point_coords [[x, y]] for a point prompt or box [x0, y0, x1, y1] for a box prompt."""
         p, k, _ = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
         masks, ii, fi, _ = self.sam_generate_masks_raw([list(q[:c]) for q, c in zip(p, k)], points_per_side, pred_iou_thresh, stability_thresh, stability_offset,
-                                                       nms_iou_thresh, max_masks)
+                                                       nms_iou_thresh, max_masks, min_mask_region_area)
         out = []
         for m, row, (piou, stab) in zip(masks, ii, fi):
             prompt = int(row[0])
@@ -399,12 +409,17 @@ class Model:
         return out
 
     def sam_generate_masks_device(self, prompts, masks_dev: int, info_i32_dev: int, info_f32_dev: int, counts_dev: int, max_masks: int = 256, pred_iou_thresh=None,
-                                  stability_thresh=None, stability_offset=None, nms_iou_thresh=None, stream: int | None = None):
+                                  stability_thresh=None, stability_offset=None, nms_iou_thresh=None, stream: int | None = None, min_mask_region_area: int = 0):
         """The same into device buffers (addresses): masks u8 [max_masks, h, w], info i32 [max_masks, 8], info f32 [max_masks, 2], counts i32 [2]; rows and masks
-        at and behind counts[0] stay untouched. Nothing waits for the device when a stream is given."""
+        at and behind counts[0] stay untouched. Nothing waits for the device when a stream is given. min_mask_region_area > 0: counts i32 [4] and SAM's order
+        behind the cleaning, as sam_generate_masks_raw describes."""
         p, k, params = self._sam_generate_args(prompts, 32, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
-        check(self._api.visp_sam_generate_masks_device(self._handle, p.ctypes.data, k.ctypes.data, len(k), *params, int(max_masks), masks_dev, info_i32_dev, info_f32_dev,
-                                                       counts_dev, stream))
+        if int(min_mask_region_area):
+            check(self._api.visp_sam_generate_masks_clean_device(self._handle, p.ctypes.data, k.ctypes.data, len(k), *params, int(max_masks), int(min_mask_region_area),
+                                                                 masks_dev, info_i32_dev, info_f32_dev, counts_dev, stream))
+        else:
+            check(self._api.visp_sam_generate_masks_device(self._handle, p.ctypes.data, k.ctypes.data, len(k), *params, int(max_masks), masks_dev, info_i32_dev,
+                                                           info_f32_dev, counts_dev, stream))
         self._sam_batch_n = len(k)
 
     def sam_generate_last_split(self) -> dict:
@@ -412,6 +427,14 @@ class Model:
         out = (ctypes.c_float * 4)()
         check(self._api.visp_sam_generate_last_split(self._handle, out))
         return dict(zip(("decode_ms", "scoring_ms", "rank_nms_ms", "output_ms"), (float(v) for v in out)))
+
+    def sam_generate_last_split5(self) -> dict:
+        """sam_generate_last_split with the cleaning stage of the last call as a fifth figure, and that stage's parts: clean, records + second NMS, gather."""
+        out, parts = (ctypes.c_float * 5)(), (ctypes.c_float * 3)()
+        check(self._api.visp_sam_generate_last_split5(self._handle, out))
+        check(self._api.visp_sam_generate_last_clean_split(self._handle, parts))
+        names = ("decode_ms", "scoring_ms", "rank_nms_ms", "output_ms", "cleaning_ms", "clean_ms", "records_nms2_ms", "gather_ms")
+        return dict(zip(names, (float(v) for v in (*out, *parts))))
 
     def sam_encode_batch(self, images: np.ndarray) -> np.ndarray:
         """images: uint8 [B, 1024, 1024, 3] on the host -> image embeddings float32 [B, 64, 64, 256]."""
@@ -550,6 +573,33 @@ def image_erosion(mask: np.ndarray, radius: int, device: Device | None = None) -
     """Minimum over the (2 radius + 1)^2 neighbourhood: [h, w] uint8 (alpha_u8) or float32 (alpha_f32), same type out."""
     fmt = ImageFormat.alpha_u8 if np.asarray(mask).dtype == np.uint8 else ImageFormat.alpha_f32
     return _image_op("visp_image_erosion", [_view_of(mask, fmt)], int(radius), on=_on(device))
+
+
+REGION_MODES = {"holes": 1, "islands": 2, "both": 3}
+
+
+def remove_small_regions(masks: np.ndarray, min_area: int, mode: str = "both", device: Device | None = None):
+    """SAM's remove_small_regions on the device: masks uint8 [n, h, w] or [h, w] (non-zero = foreground) -> (masks, changed). "holes": background components
+    of fewer than min_area pixels (8-connectivity, none exempt for touching the border) become 255; "islands": such foreground components become 0, but where
+    every one is small the largest stays; "both": the holes, then the islands of the result. Only flipped pixels differ from the input. changed: bool [n], or
+    a bool for a single mask."""
+    if mode not in REGION_MODES:
+        raise ValueError(f"unknown mode {mode!r}: one of {sorted(REGION_MODES)}")
+    m = np.array(masks, dtype=np.uint8, order="C", copy=True)
+    if m.ndim not in (2, 3):
+        raise ValueError(f"expected masks [n, h, w] or [h, w], got shape {m.shape}")
+    n, (h, w) = (1 if m.ndim == 2 else m.shape[0]), m.shape[-2:]
+    changed = np.zeros(max(n, 1), np.int32)
+    check(lib.get_lib().visp_image_remove_small_regions_host(m.ctypes.data, n, w, h, int(min_area), REGION_MODES[mode], changed.ctypes.data, *_on(device)))
+    return m, (bool(changed[0]) if m.ndim == 2 else changed[:n].astype(bool))
+
+
+def remove_small_regions_device(masks_dev: int, n: int, w: int, h: int, min_area: int, mode: str = "both", changed_dev: int | None = None, device: Device | None = None,
+                                stream: int | None = None):
+    """The same in place on device-resident masks u8 [n, h, w] (addresses; changed i32 [n] optional). Returns with the work done."""
+    if mode not in REGION_MODES:
+        raise ValueError(f"unknown mode {mode!r}: one of {sorted(REGION_MODES)}")
+    check(lib.get_lib().visp_image_remove_small_regions_device(masks_dev, int(n), int(w), int(h), int(min_area), REGION_MODES[mode], changed_dev, stream, *_on(device)))
 
 
 def image_estimate_foreground(image: np.ndarray, mask: np.ndarray, radius: int = 30, device: Device | None = None) -> np.ndarray:
