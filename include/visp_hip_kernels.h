@@ -631,7 +631,8 @@ VX_API int vx_im2col_patches_f32(const float* x, void* patches, int B, int H, in
 
 
 /* ---- MI-GAN inpainting (migan.cpp, kernels_migan.hip): NHWC f16, f32 arithmetic, lrelu_agc = clamp(lrelu_0.2(v) * sqrt2, +-256).
- * Depthwise weights f16 [9][C] tap-major + f32 bias [C]; 4x4 FIR filters f32 [16][C]. */
+ * Depthwise weights f16 [9][C] tap-major + f32 bias [C]; 4x4 FIR filters f32 [16][C]: per channel, any 16 taps (nothing assumes the symmetric
+ * filter of the trained file). The f16 operands (x, w, y, feat, out) are read and written 16 bytes at a time and must be 16-byte aligned. */
 /* y = lrelu_agc(dw3x3(x) + bias) [B,H,W,C]; with down_fir: then the 4x4 / stride 2 / pad 1 FIR, y [B,H/2,W/2,C] (C % 64 == 0) */
 VX_API int vx_migan_dwconv_f16(const void* x, const void* w, const float* bias, const float* down_fir, void* y, int B, int H, int W, int C,
                                void* stream);

@@ -36,6 +36,17 @@ def perturbed_fir(rng, C: int, gain: float = 4.0) -> np.ndarray:
     return f[:, :, None] * (1.0 + 0.05 * rng.standard_normal(C))[None, None, :]
 
 
+def asymmetric_fir(rng, C: int, gain: float = 4.0) -> np.ndarray:
+    """the same [1, 3, 3, 1] outer product as [4, 4, C] with each of the 16 taps of every channel perturbed on its own by 15 .. 25 %, the signs drawn
+    at random except that the centre taps differ in sign from their mirror images ((1, 1) from (2, 2), (1, 2) from (2, 1)): f[ky][kx] != f[kx][ky] !=
+    f[3 - ky][3 - kx] in every channel, so a kernel that flips, transposes or mispairs its taps shows (the symmetric filter hides all three)"""
+    f = np.outer([1.0, 3.0, 3.0, 1.0], [1.0, 3.0, 3.0, 1.0])
+    f = f / f.sum() * gain
+    sign = rng.choice([-1.0, 1.0], (4, 4, C))
+    sign[2, 2], sign[2, 1] = -sign[1, 1], -sign[1, 2]
+    return f[:, :, None] * (1.0 + sign * rng.uniform(0.15, 0.25, (4, 4, C)))
+
+
 def upfirdn2x_raw(x, fir) -> np.ndarray:
     """out[Y, X, c] = sum_{i,j} fir[i, j, c] z[Y + i - 2, X + j - 2, c], z[2a, 2b] = x[a, b], zero elsewhere and outside 2h x 2w"""
     x, fir = np.asarray(x, np.float64), np.asarray(fir, np.float64)

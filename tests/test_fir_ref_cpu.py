@@ -1,5 +1,6 @@
 """tests/fir_ref.py, the float64 reference of the MI-GAN graph tests, pinned to the literal node chain in torch (repeat_interleave x2, the mask tile,
-conv2d(groups = C, padding = 2), crop) and to tests/migan_ref.py::upsample, to 1e-6; clamp and lrelu_agc to torch."""
+conv2d(groups = C, padding = 2), crop) and to tests/migan_ref.py::upsample, to 1e-6, on the symmetric filter of the trained file and on an asymmetric one
+(asymmetric_fir: flipped or transposed taps show); clamp and lrelu_agc to torch."""
 import numpy as np
 import pytest
 import torch
@@ -27,6 +28,28 @@ def test_upfirdn2x_equals_the_literal_chain(case):
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6)
     ref = migan_ref.upsample(x.astype(np.float32), np.ascontiguousarray(fir.transpose(2, 0, 1)[:, None]).astype(np.float32))
     np.testing.assert_allclose(got, ref, rtol=1e-6, atol=1e-6)  # (migan_ref computes in f32)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_upfirdn2x_equals_migan_ref_on_an_asymmetric_filter(case):
+    """the symmetric filter above satisfies f[ky][kx] == f[kx][ky] == f[3 - ky][3 - kx]: a reference that flipped or transposed its taps would pass there"""
+    B, h, w, C = case
+    rng = np.random.default_rng(100 + sum(case))
+    x = R.f16(rng.standard_normal(case))
+    sym, fir = R.f16(R.perturbed_fir(rng, C)), R.f16(R.asymmetric_fir(rng, C))
+    flipped, transposed = fir[::-1, ::-1], fir.transpose(1, 0, 2)
+    assert np.array_equal(sym, sym[::-1, ::-1]) and np.array_equal(sym, sym.transpose(1, 0, 2))
+    # every channel tells its taps apart: a flip or a transpose moves a tap by more than a tenth of the largest one
+    assert (np.abs(fir - flipped).max((0, 1)) > 0.1 * fir.max((0, 1))).all() and (np.abs(fir - transposed).max((0, 1)) > 0.1 * fir.max((0, 1))).all()
+    got = R.upfirdn2x(x, fir)
+    ref = migan_ref.upsample(x.astype(np.float32), np.ascontiguousarray(fir.transpose(2, 0, 1)[:, None]).astype(np.float32))
+    np.testing.assert_allclose(got, ref, rtol=1e-6, atol=1e-6)
+    t = torch.from_numpy(x).permute(0, 3, 1, 2)
+    tile = torch.tensor([[1.0, 0.0], [0.0, 0.0]], dtype=torch.float64).repeat(h, w)
+    k = torch.from_numpy(fir.copy()).permute(2, 0, 1)[:, None]
+    want = F.conv2d(t.repeat_interleave(2, 2).repeat_interleave(2, 3) * tile, k, padding=2, groups=C)[:, :, :2 * h, :2 * w].permute(0, 2, 3, 1).numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6)
+    assert R.rel_err(R.upfirdn2x(x, flipped), got) > 0.02 and R.rel_err(R.upfirdn2x(x, transposed), got) > 0.02
 
 
 def test_upfirdn2x_epilogue_order():

@@ -162,10 +162,12 @@ def test_image4_pad8_and_the_conv_on_a_four_channel_image(device, k):
 # ---- vx_upfirdn2x_f16 ---------------------------------------------------------------------------------------------------------------------------------
 
 # (B, h, w, C), plane, agc, res: every tap at a border; non-square with an odd width; a channel slice into a slice of a wider buffer (direct only); the whole
-# epilogue; a residual alone
+# epilogue; a residual alone; then, on a filter with f[ky][kx] != f[kx][ky] != f[3 - ky][3 - kx] (fir_ref.asymmetric_fir: the symmetric filter of the cases
+# before hides flipped, transposed and mispaired taps): bare, and the whole epilogue
 UP_CASES = [((2, 1, 1, 8), False, False, False), ((1, 2, 3, 24), False, False, False), ((1, 5, 9, 16), False, False, False), ((2, 4, 4, 8), True, True, True),
-            ((1, 3, 4, 8), False, False, True)]
+            ((1, 3, 4, 8), False, False, True), ((1, 2, 3, 24), False, False, False), ((2, 4, 4, 8), True, True, True)]
 SLICE_CASE = 2
+ASYMMETRIC_CASES = (5, 6)
 _up_cache = {}
 
 
@@ -174,7 +176,7 @@ def _up_case(i):
         (B, h, w, C), plane, agc, res = UP_CASES[i]
         rng = np.random.default_rng(700 + i)
         x = R.f16(rng.standard_normal((B, h, w, 32 if i == SLICE_CASE else C)) * (400.0 if agc else 1.0))
-        fir = R.f16(R.perturbed_fir(rng, C))
+        fir = R.f16((R.asymmetric_fir if i in ASYMMETRIC_CASES else R.perturbed_fir)(rng, C))
         pl = rng.standard_normal((2 * h, 2 * w)).astype(np.float32).astype(np.float64) if plane else None
         rs = R.f16(rng.standard_normal((B, 2 * h, 2 * w, C)) * 2) if res else None
         a = (SQRT2, 256.0) if agc else None

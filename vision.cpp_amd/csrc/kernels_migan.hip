@@ -238,6 +238,7 @@ extern "C" {
 VX_API int vx_migan_dwconv_f16(const void* x, const void* w, const float* bias, const float* down_fir, void* y, int B, int H, int W, int C,
                                void* stream) {
     VX_REQUIRE(x && w && bias && y, "vx_migan_dwconv_f16: null pointer");
+    VX_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), "vx_migan_dwconv_f16: x, w and y must be 16-byte aligned");
     VX_REQUIRE(B > 0 && H >= 2 && W >= 2, "vx_migan_dwconv_f16: bad extent B=%d H=%d W=%d", B, H, W);
     VX_REQUIRE(C > 0 && C % 64 == 0, "vx_migan_dwconv_f16: C=%d must be a positive multiple of 64", C);
     if (down_fir) {
@@ -258,6 +259,7 @@ VX_API int vx_migan_dwconv_f16(const void* x, const void* w, const float* bias, 
 VX_API int vx_migan_upsample_f16(const void* y, const float* fir, const float* noise, const void* feat, void* out, int B, int h, int w, int C,
                                  void* stream) {
     VX_REQUIRE(y && fir && out, "vx_migan_upsample_f16: null pointer");
+    VX_REQUIRE(aligned16(y) && aligned16(feat) && aligned16(out), "vx_migan_upsample_f16: y, feat and out must be 16-byte aligned");
     VX_REQUIRE(B > 0 && h > 0 && w > 0, "vx_migan_upsample_f16: bad extent B=%d h=%d w=%d", B, h, w);
     VX_REQUIRE(C > 0 && C % 8 == 0, "vx_migan_upsample_f16: C=%d must be a positive multiple of 8", C);
     hipLaunchKernelGGL(migan_upsample_agc_kernel, dim3(blocks_for((int64_t)B * 4 * h * w * (C / 8))), dim3(256), 0, as_stream(stream),
@@ -269,6 +271,7 @@ VX_API int vx_migan_upsample_f16(const void* y, const float* fir, const float* n
 VX_API int vx_migan_torgb(const void* x, const float* w, const float* bias, const float* img_prev, const float* fir, float* img, int B, int H, int W,
                           int C, void* stream) {
     VX_REQUIRE(x && w && bias && img, "vx_migan_torgb: null pointer");
+    VX_REQUIRE(aligned16(x), "vx_migan_torgb: x must be 16-byte aligned");
     VX_REQUIRE(!img_prev || (fir && H % 2 == 0 && W % 2 == 0), "vx_migan_torgb: the image path needs its FIR and an even extent");
     VX_REQUIRE(B > 0 && H > 0 && W > 0, "vx_migan_torgb: bad extent B=%d H=%d W=%d", B, H, W);
     VX_REQUIRE(C > 0 && C % 8 == 0 && C <= 512, "vx_migan_torgb: C=%d must be a multiple of 8 in [8, 512]", C);
@@ -281,6 +284,7 @@ VX_API int vx_migan_torgb(const void* x, const float* w, const float* bias, cons
 VX_API int vx_migan_preprocess(const uint8_t* img, int img_channels, const uint8_t* mask, const float* in4, const float* w, const float* bias,
                                void* out, int64_t n_pixels, int C, void* stream) {
     VX_REQUIRE(w && bias && out, "vx_migan_preprocess: null pointer");
+    VX_REQUIRE(aligned16(out), "vx_migan_preprocess: out must be 16-byte aligned");
     VX_REQUIRE(in4 || (img && mask && (img_channels == 3 || img_channels == 4)), "vx_migan_preprocess: need an f32 input or a 3/4-channel u8 image and a mask");
     VX_REQUIRE(n_pixels > 0 && C > 0 && C % 8 == 0, "vx_migan_preprocess: bad shape pixels=%lld C=%d", (long long)n_pixels, C);
     hipLaunchKernelGGL(migan_preprocess_kernel, dim3(blocks_for(n_pixels * (C / 8))), dim3(256), 0, as_stream(stream), img, img_channels, mask, in4, w,
