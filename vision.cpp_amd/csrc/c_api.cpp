@@ -737,11 +737,7 @@ int32_t visp_sam_weights_ready(visp_model* m) {
 int32_t visp_sam_encode(visp_model* m, visp_image_view const* image) {
     return handle_errors([&]() {
         if (!image) throw except("sam: null image");
-        image_view in;
-        in.extent = {{image->width, image->height}};
-        in.stride = image->stride;
-        in.format = image_format(image->format);
-        in.data = image->data;
+        image_view in{i32x2{{image->width, image->height}}, image->stride, image_format(image->format), image->data};
         sam_encode(as_sam(m), in);
     });
 }
@@ -788,9 +784,9 @@ int32_t visp_sam_generate_masks_device(visp_model* m, int32_t const* prompts, in
                                        float stability_offset, float nms_iou_thresh, int32_t capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev,
                                        void* counts_dev, void* stream) {
     return handle_errors([&]() {
-        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity); // before the handle: needs no model
-        sam_generate_masks_device(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, masks_u8_dev, info_i32_dev,
-                                  info_f32_dev, counts_dev, stream);
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, 0};
+        sam_generate_check(prompts, n_args, n, p); // before the handle: needs no model
+        sam_generate_masks_device(as_sam(m), prompts, n_args, n, p, {masks_u8_dev, info_i32_dev, info_f32_dev, counts_dev}, stream);
     });
 }
 
@@ -798,9 +794,9 @@ int32_t visp_sam_generate_masks_host(visp_model* m, int32_t const* prompts, int3
                                      float stability_offset, float nms_iou_thresh, int32_t capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
                                      int32_t* counts) {
     return handle_errors([&]() {
-        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
-        sam_generate_masks_host(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, masks_u8, info_i32, info_f32,
-                                counts);
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, 0};
+        sam_generate_check(prompts, n_args, n, p);
+        sam_generate_masks_host(as_sam(m), prompts, n_args, n, p, {masks_u8, info_i32, info_f32, counts});
     });
 }
 
@@ -808,10 +804,9 @@ int32_t visp_sam_generate_masks_clean_device(visp_model* m, int32_t const* promp
                                              float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, void* masks_u8_dev,
                                              void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream) {
     return handle_errors([&]() {
-        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity); // before the handle: needs no model
-        sam_generate_check_region_area(min_region_area);
-        sam_generate_masks_clean_device(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area,
-                                        masks_u8_dev, info_i32_dev, info_f32_dev, counts_dev, stream);
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area};
+        sam_generate_check(prompts, n_args, n, p); // before the handle: needs no model
+        sam_generate_masks_device(as_sam(m), prompts, n_args, n, p, {masks_u8_dev, info_i32_dev, info_f32_dev, counts_dev}, stream);
     });
 }
 
@@ -819,36 +814,33 @@ int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const* prompts
                                            float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, uint8_t* masks_u8, int32_t* info_i32,
                                            float* info_f32, int32_t* counts) {
     return handle_errors([&]() {
-        sam_generate_check_args(prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity);
-        sam_generate_check_region_area(min_region_area);
-        sam_generate_masks_clean_host(as_sam(m), prompts, n_args, n, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area, masks_u8,
-                                      info_i32, info_f32, counts);
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area};
+        sam_generate_check(prompts, n_args, n, p);
+        sam_generate_masks_host(as_sam(m), prompts, n_args, n, p, {masks_u8, info_i32, info_f32, counts});
     });
+}
+
+// the last generate call's ms of the stages named, in that order (0 for a stage the call did not run)
+static void sam_stage_ms(visp_model const* m, float* out_ms, std::initializer_list<sam_generate_stage> stages) {
+    if (!out_ms) throw except("sam: null argument");
+    for (sam_generate_stage st : stages) *out_ms++ = as_sam(m).generate_split_ms[st];
 }
 
 int32_t visp_sam_generate_last_split5(visp_model const* m, float out_ms[5]) {
     return handle_errors([&]() {
-        if (!out_ms) throw except("sam: null argument");
-        sam_model const& sm = as_sam(m);
-        for (int i = 0; i < 4; ++i) out_ms[i] = sm.generate_split_ms[i];
-        out_ms[4] = sm.generate_split_ms[4] + sm.generate_split_ms[5] + sm.generate_split_ms[6];
+        float parts[3];
+        sam_stage_ms(m, out_ms, {sam_stage_decode, sam_stage_scoring, sam_stage_rank_nms, sam_stage_output});
+        sam_stage_ms(m, parts, {sam_stage_clean, sam_stage_records_nms2, sam_stage_gather});
+        out_ms[4] = parts[0] + parts[1] + parts[2];
     });
 }
 
 int32_t visp_sam_generate_last_clean_split(visp_model const* m, float out_ms[3]) {
-    return handle_errors([&]() {
-        if (!out_ms) throw except("sam: null argument");
-        sam_model const& sm = as_sam(m);
-        for (int i = 0; i < 3; ++i) out_ms[i] = sm.generate_split_ms[4 + i];
-    });
+    return handle_errors([&]() { sam_stage_ms(m, out_ms, {sam_stage_clean, sam_stage_records_nms2, sam_stage_gather}); });
 }
 
 int32_t visp_sam_generate_last_split(visp_model const* m, float out_ms[4]) {
-    return handle_errors([&]() {
-        if (!out_ms) throw except("sam: null argument");
-        sam_model const& sm = as_sam(m);
-        for (int i = 0; i < 4; ++i) out_ms[i] = sm.generate_split_ms[i];
-    });
+    return handle_errors([&]() { sam_stage_ms(m, out_ms, {sam_stage_decode, sam_stage_scoring, sam_stage_rank_nms, sam_stage_output}); });
 }
 
 int32_t visp_sam_generate_defaults(float out[4]) {

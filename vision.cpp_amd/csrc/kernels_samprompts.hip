@@ -1,4 +1,4 @@
-// Kernels of the batched MobileSAM decode (many prompts per encoded image; csrc/tinyvit.cpp sam_compute_batch_device): what the single-prompt
+// Kernels of the batched MobileSAM decode (many prompts per encoded image; csrc/sam_decoder.cpp sam_compute_batch_device): what the single-prompt
 // path does on the host between its launches, here on the device so that a chunk of prompts never waits for the host.
 //   vx_sam_iou_head_f32     iou_prediction_head (mobile-sam.cpp:476-481) on the iou token of each prompt, f32 weights and sums, and the choice of
 //                           vision.cpp:80-82: the best of the first three predictions, the first index on ties

@@ -1,4 +1,4 @@
-// Kernels of MobileSAM's automatic mask generation (csrc/tinyvit.cpp sam_generate_masks_device): the selection stage between the logit planes of a
+// Kernels of MobileSAM's automatic mask generation (csrc/sam_generate.cpp sam_generate_masks_device): the selection stage between the logit planes of a
 // batched decode and the masks a caller gets -- SAM's automatic mask generator on the device, so that a "segment everything" pass never waits for the host.
 //   vx_sam_score_planes_f16        per candidate (prompt, plane): the counts behind the stability score and the box of the positive logits, over the
 //                                  part of the plane the image occupies

@@ -52,6 +52,19 @@ struct workspace_layout {
     size_t top = 0;
     size_t take(size_t bytes, size_t slack = 0);
 };
+// The slots of one workspace, each written once: add() lays a slot out as take() does and returns it, and the slot reads as its address from when `base`
+// is set (after the grow to layout.top). A slot that is not added (when = false) takes no room and reads as null. Slots point back at their table: do not copy or move it.
+struct workspace_table {
+    workspace_layout layout;
+    uint8_t* base = nullptr;
+    template <class T> struct slot {
+        workspace_table const* table; size_t off;
+        operator T*() const { return table ? static_cast<T*>(static_cast<void*>(table->base + off)) : nullptr; }
+    };
+    template <class T = void> slot<T> add(size_t bytes, size_t slack = 0, bool when = true) {
+        return when ? slot<T>{this, layout.take(bytes, slack)} : slot<T>{nullptr, 0};
+    }
+};
 
 // Device memory with one owner: freed by the destructor, moved but never copied. Kernel arguments and the weight store's packs
 // keep raw pointers into it.

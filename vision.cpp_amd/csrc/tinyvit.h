@@ -65,6 +65,8 @@ struct samdec_weights {
     // (load_no_upload) rebuilds them in sam_weights_ready; the f32 iou head of the device (sam_model::iou_head_dev) is made there too.
     size_t tables_off = SIZE_MAX;
 };
+// the stages sam_model::generate_split_ms tells apart; the last three run with min_region_area > 0 only
+enum sam_generate_stage { sam_stage_decode, sam_stage_scoring, sam_stage_rank_nms, sam_stage_output, sam_stage_clean, sam_stage_records_nms2, sam_stage_gather, sam_stage_count };
 // test hook (captures on): the logit planes [n][4][mask_size^2] (f16-rounded) and the iou predictions [n][4] a decode left; empty with captures off
 struct sam_kept_logits { std::vector<float> masks, iou; };
 
@@ -98,8 +100,8 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // automatic mask generation (sam_generate_masks_device): the logit planes and iou predictions of every prompt of the call, the selection stage's tables
     // and the NMS workspace, next to the decoder's batch_ws
     device_buffer generate_ws;
-    // with timing enabled: the last generate call's {decode, scoring, rank + NMS, output masks | clean, records + second NMS, gather} by events
-    float generate_split_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+    // with timing enabled: the last generate call's ms per sam_generate_stage, by events
+    float generate_split_ms[sam_stage_count] = {};
     ~sam_model() override;
 };
 void sam_set_fp8_mlp(sam_model&, bool enable); // builds the e4m3 weight images on first use (from the f16 weights on the device)
@@ -127,25 +129,18 @@ void sam_set_prompt_chunk(sam_model&, int n); // 1 .. 256
 // [capacity][h][w] with info_i32 [capacity][8] = {prompt, plane, x, y, w, h, area, 0}, info_f32 [capacity][2] = {predicted_iou, stability_score} and
 // counts i32 [2] = {returned, kept}. Device outputs; rows and masks at and behind counts[0] untouched. No host synchronisation beyond sam_compute_batch_device's.
 constexpr int kSamGenerateMaxPrompts = 5461; // 16384 candidates
-void sam_generate_check_args(int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
-                             float nms_iou_thresh, int capacity); // throws on what needs neither model nor device to refuse
-void sam_generate_masks_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
-                               float nms_iou_thresh, int capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev, void* counts_dev, void* stream);
-void sam_generate_masks_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh, float stability_offset,
-                             float nms_iou_thresh, int capacity, uint8_t* masks_u8, int32_t* info_i32, float* info_f32, int32_t* counts);
-// The same with SAM's min_mask_region_area (postprocess_small_regions) behind the first stage: its first k = min(kept, capacity) masks, produced exactly as above
-// into a staging buffer in generate_ws (capacity * h * w bytes: the second NMS reorders them, so they cannot be cleaned in their final place), are cleaned
+// With min_region_area > 0, SAM's min_mask_region_area (postprocess_small_regions) runs behind that first stage: its first k = min(kept, capacity) masks, produced
+// exactly as above into a staging buffer in generate_ws (capacity * h * w bytes: the second NMS reorders them, so they cannot be cleaned in their final place), are cleaned
 // (vx_mask_remove_small_regions_u8: holes, then islands, below min_region_area pixels; 64 masks in flight, 8 bytes per pixel each), measured again, and passed
 // through a second greedy NMS on their inclusive image-pixel boxes with the scores 1 (unchanged) / 0 (changed), equal scores in first-stage order. The survivors
 // come out in that order -- unchanged masks first, then changed ones, each by predicted iou: NOT the order without cleaning --, info_i32 column 7 = 1 for a changed
-// mask, counts i32 [4] = {returned, kept by the first NMS, returned masks that cleaning changed, masks the second NMS removed}. min_region_area 0: exactly the
-// launches and bytes of the entries above (counts [2]). Nothing waits for the host beyond where those do.
-void sam_generate_check_region_area(int min_region_area);
-void sam_generate_masks_clean_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
-                                     float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, void* masks_u8_dev, void* info_i32_dev,
-                                     void* info_f32_dev, void* counts_dev, void* stream);
-void sam_generate_masks_clean_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, float pred_iou_thresh, float stability_thresh,
-                                   float stability_offset, float nms_iou_thresh, int capacity, int min_region_area, uint8_t* masks_u8, int32_t* info_i32, float* info_f32,
-                                   int32_t* counts);
+// mask, counts i32 [4] = {returned, kept by the first NMS, returned masks that cleaning changed, masks the second NMS removed}. min_region_area 0: the first
+// stage alone (counts [2]). Nothing waits for the host beyond where that does.
+struct sam_select_params { float pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh; int capacity, min_region_area; };
+struct sam_generate_outputs { void *masks, *info_i32, *info_f32, *counts; }; // all on the device, or all on the host
+// throws on what needs neither model nor device to refuse: the C entries call it before they look the handle up, the two functions below do not repeat it
+void sam_generate_check(int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const&);
+void sam_generate_masks_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const&, sam_generate_outputs const& dev, void* stream);
+void sam_generate_masks_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const&, sam_generate_outputs const& host);
 
 } // namespace visp
