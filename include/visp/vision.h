@@ -256,6 +256,16 @@ inline backend_device backend_init(backend_type t) { // backend_type::cpu throws
 }
 inline bool backend_is_available(backend_type t) { return t == backend_type::gpu; }
 
+// not in the reference's header: image_scale on the device (one fused launch between an upload and a download), the bytes of the host function
+inline image_data image_scale(image_view const& img, i32x2 target, backend_device const& dev) {
+    const size_t row = size_t(img.extent[0]) * size_t(n_bytes(img.format)), h = size_t(img.extent[1]);
+    std::vector<uint8_t> packed(row * h);
+    for (size_t y = 0; y < h; ++y) std::memcpy(packed.data() + y * row, static_cast<uint8_t const*>(img.data) + y * size_t(img.stride), row);
+    image_data out = image_alloc(target, img.format);
+    detail::check(visp_image_scale_batch_host(dev.handle, packed.data(), int32_t(img.format), 1, img.extent[0], img.extent[1], out.data.get(), target[0], target[1]));
+    return out;
+}
+
 //
 // models (include/visp/vision.h)
 
@@ -292,6 +302,15 @@ inline image_data depthany_compute(depthany_model& model, image_view image) { //
     visp_image_data* owner = nullptr;
     detail::check(visp_depthany_compute_f32(model.handle, &in, &out, &owner));
     return detail::take(out, owner);
+}
+// not in the reference's header: depthany_compute for a batch of rgb_u8 images [batch, h, w, 3] of one extent, ANY extent, scaled on the device
+// on the way in and out (the bits of depthany_compute per image) -> depth f32 [batch, h, w] in [0, 1]
+inline std::vector<float> depthany_compute_scaled_batch(depthany_model& model, std::span<uint8_t const> rgb, int batch, i32x2 extent) {
+    if (batch < 1 || extent[0] < 1 || extent[1] < 1 || rgb.size() != size_t(batch) * size_t(extent[0]) * size_t(extent[1]) * 3)
+        throw exception("depthany_compute_scaled_batch: the images do not hold batch x h x w x 3 bytes");
+    std::vector<float> out(size_t(batch) * size_t(extent[0]) * size_t(extent[1]));
+    detail::check(visp_depthany_compute_scaled_batch_host(model.handle, rgb.data(), batch, extent[0], extent[1], out.data()));
+    return out;
 }
 
 // --- Depth Anything pipeline (vision.h:236-252, arch/depth-anything.cpp:112-149). The reference reads the parameters from a

@@ -104,6 +104,15 @@ VISP_API int32_t visp_depthany_compute_f32(visp_model* m, visp_image_view const*
 /* same with host buffers (H2D + compute + D2H on the model's stream, blocking) */
 VISP_API int32_t visp_depthany_compute_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w,
                                                   int32_t h, float* out, float* raw_out);
+/* Any extent, nothing leaves the device: rgb_u8 [batch,h,w,3] of ANY extent -> depth f32 [batch,h,w] in [0,1] at that extent. It is
+ * depthany_compute per image: visp_image_scale_batch_device to visp_depthany_image_extent(w, h), visp_depthany_compute_batch_device as it
+ * stands, the normalised map scaled back as alpha_f32 -- the bits of that composition on the host. At the model's own extent it issues exactly
+ * visp_depthany_compute_batch_device. The two buffers at the model's extent and the tap tables belong to the model (kept between calls, replaced
+ * behind a synchronisation when a call needs more or another extent). stream as above. */
+VISP_API int32_t visp_depthany_compute_scaled_batch_device(visp_model* m, void const* rgb_u8_dev, int32_t batch, int32_t w, int32_t h, void* out_f32_dev,
+                                                           void* stream);
+/* the same with host buffers (H2D + the above + D2H on the model's stream, blocking) */
+VISP_API int32_t visp_depthany_compute_scaled_batch_host(visp_model* m, uint8_t const* rgb_u8, int32_t batch, int32_t w, int32_t h, float* out);
 /* Multi-GPU from C: models[i] is a depth_anything model loaded on its own device (visp_hip_device_init(i) + visp_model_load);
  * the batch is cut into n_models contiguous shards (sizes differ by at most one), each shard runs on its model's device from
  * its own host thread, outputs land at the matching offsets of `out` [batch, h, w] f32. No collective is involved: images are
@@ -165,6 +174,17 @@ VISP_API int32_t visp_gguf_validate(char const* filepath, int32_t* out_n_tensors
  * any supported format; the result is owned by *out_data (visp_image_destroy) */
 VISP_API int32_t visp_image_scale(visp_image_view const* src, int32_t width, int32_t height, visp_image_view* out_image,
                                   visp_image_data** out_data);
+/* image_scale on the device, batched: src [batch, h, w, ch] -> dst [batch, out_h, out_w, ch], contiguous DEVICE arrays of one format (any of the
+ * eight) and extent, one launch (both passes fused: csrc/kernels_imgscale.hip). Byte-equal to visp_image_scale for the u8 formats and bit-equal
+ * for the f32 ones, equal extents included (image_scale filters at scale 1). dev NULL = the calling thread's current device; stream NULL = the
+ * device's stream. The tap tables are made per call and live for it: the stream is synchronised before the call returns. Refused, before
+ * anything touches a device: null pointers, an unknown format, batch or an extent below 1, and a reduction that needs more than 768 taps per
+ * output sample on an axis (about 190:1). */
+VISP_API int32_t visp_image_scale_batch_device(visp_device const* dev, void const* src, int32_t format, int32_t batch, int32_t w, int32_t h, void* dst, int32_t out_w,
+                                               int32_t out_h, void* stream);
+/* the same on host arrays: up, scale, down; blocks */
+VISP_API int32_t visp_image_scale_batch_host(visp_device const* dev, void const* src, int32_t format, int32_t batch, int32_t w, int32_t h, void* dst, int32_t out_w,
+                                             int32_t out_h);
 /* host-only image_u8_to_f32 of the reference (src/visp/image.cpp:215-255, image-impl.h:17-34): dst = (src / 255 + offset) * scale per
  * channel, any u8 format -> the float format `format` (what *_process_input applies); result owned by *out_data */
 VISP_API int32_t visp_image_u8_to_f32(visp_image_view const* src, int32_t format, float const offset[4], float const scale[4],

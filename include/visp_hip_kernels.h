@@ -695,6 +695,15 @@ VX_API int vx_foreground_stage(const void* img, int img_format, const float* fg,
  * mask u8. f32 arithmetic without fused multiply-adds: the bits of the reference's host code. */
 VX_API int vx_alpha_composite_u8(const uint8_t* fg_rgba, const uint8_t* bg, int bg_channels, const uint8_t* mask, uint8_t* out_rgba, int64_t n_pixels, void* stream);
 
+/* ---- image_scale (kernels_imgscale.hip): src [B, h, w, ch] -> dst [B, oh, ow, ch] of one image format (any of the eight of visp_c_api.h), contiguous, with the bits of
+ * the host's image_scale: Catmull-Rom enlarging, stretched Mitchell reducing, sRGB-correct u8, alpha-weighted, edge clamp; horizontal then vertical
+ * pass in one launch, no intermediate image, no scratch, no atomics. tables: the device copy of the block csrc/image_scale_tables.h lays out (lookup
+ * tables, per-axis taps, per-tile spans), table_bytes its size; tile_w the output columns of a block (1 .. 64), taps_x / taps_y the padded tap counts
+ * (at most 768), span the widest source span of a tile in columns: what csrc/image_scale_device.cpp computes for the shape. Refuses null and
+ * misaligned pointers (four-channel pixels are read whole), extents below 1, tables of another size, a tile beyond 64 KB of LDS, overlapping images. */
+VX_API int vx_image_scale(const void* src, int format, int B, int h, int w, void* dst, int oh, int ow, const void* tables, size_t table_bytes, int tile_w, int taps_x,
+                          int taps_y, int span, void* stream);
+
 /* ---- image ops and pixel gates of BiRefNet on the graph layer (kernels_imgops.hip; birefnet.cpp:20-73, 147-260). Memory-bound passes, no atomics: the
  * same bits on every launch. */
 /* bilinear | align_corners resize of an f32 image: x [B, H, W, C] -> y [B, OH, OW, C], C 1..4. Source coordinate o * fl((in - 1) / (out - 1)) in f32 (0 where

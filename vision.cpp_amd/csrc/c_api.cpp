@@ -166,6 +166,16 @@ int32_t visp_image_scale(visp_image_view const* src, int32_t width, int32_t heig
     });
 }
 
+// the same function on the device (image_scale_device.cpp): every check runs inside, before the first device call
+int32_t visp_image_scale_batch_device(visp_device const* dev, void const* src, int32_t format, int32_t batch, int32_t w, int32_t h, void* dst, int32_t out_w, int32_t out_h,
+                                      void* stream) {
+    return handle_errors([&]() { image_scale_batch_device(dev, src, image_format(format), batch, w, h, dst, out_w, out_h, stream); });
+}
+
+int32_t visp_image_scale_batch_host(visp_device const* dev, void const* src, int32_t format, int32_t batch, int32_t w, int32_t h, void* dst, int32_t out_w, int32_t out_h) {
+    return handle_errors([&]() { image_scale_batch_host(dev, src, image_format(format), batch, w, h, dst, out_w, out_h); });
+}
+
 int32_t visp_image_u8_to_f32(visp_image_view const* src, int32_t format, float const offset[4], float const scale[4], visp_image_view* out_image,
                              visp_image_data** out_data) {
     return handle_errors([&]() {
@@ -340,6 +350,14 @@ int32_t visp_depthany_compute_batch_device(visp_model* m, void const* rgb, int32
         if (!rgb || !out) throw except("depthany: null input/output pointer");
         depthany_compute_batch_device(as_depthany(m), rgb, batch, w, h, out, raw_out, stream);
     });
+}
+
+int32_t visp_depthany_compute_scaled_batch_device(visp_model* m, void const* rgb, int32_t batch, int32_t w, int32_t h, void* out, void* stream) {
+    return handle_errors([&]() { depthany_compute_scaled_batch_device(as_depthany(m), rgb, batch, w, h, out, stream); });
+}
+
+int32_t visp_depthany_compute_scaled_batch_host(visp_model* m, uint8_t const* rgb, int32_t batch, int32_t w, int32_t h, float* out) {
+    return handle_errors([&]() { depthany_compute_scaled_batch_host(as_depthany(m), rgb, batch, w, h, out); });
 }
 
 int32_t visp_depthany_compute_f32(visp_model* m, visp_image_view const* image, visp_image_view* out_image, visp_image_data** out_data) {

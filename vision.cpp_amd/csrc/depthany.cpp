@@ -493,6 +493,58 @@ void depthany_compute_batch_host(depthany_model& m, uint8_t const* rgb, int batc
     if (raw_out) VX(vx_memcpy_d2h(raw_out, r, out_bytes, s));
 }
 
+namespace {
+void check_scaled_batch(void const* in, void const* out, int batch, int w, int h) {
+    if (!in || !out) throw except("depthany: null input/output pointer");
+    if (batch < 1 || w < 1 || h < 1) throw except("depthany: batch %d of %dx%d images", batch, w, h);
+}
+} // namespace
+
+void depthany_compute_scaled_batch_device(depthany_model& m, void const* rgb_dev, int batch, int w, int h, void* out_dev, void* stream) {
+    check_scaled_batch(rgb_dev, out_dev, batch, w, h);
+    const i32x2 res = depthany_image_extent(i32x2{{w, h}}, m.params);
+    if (res == i32x2{{w, h}}) return depthany_compute_batch_device(m, rgb_dev, batch, w, h, out_dev, nullptr, stream);
+    // both plans before anything is enqueued: a ratio past the kernel's limit is refused here
+    const bool keep = m.scale_in.serves(image_format::rgb_u8, w, h, res[0], res[1]) && m.scale_out.serves(image_format::alpha_f32, res[0], res[1], w, h);
+    image_scale_plan in_plan, out_plan;
+    if (!keep) {
+        in_plan = image_scale_make_plan(image_format::rgb_u8, w, h, res[0], res[1]);
+        out_plan = image_scale_make_plan(image_format::alpha_f32, res[0], res[1], w, h);
+    }
+    device_turn turn(*m.backend);
+    void* s = stream ? stream : m.backend->stream;
+    if (!keep) {
+        if (m.scale_in.tables.ptr) { // launches of an earlier call may still read the old tables
+            VX(vx_stream_sync(m.backend->stream));
+            VX(vx_stream_sync(s));
+        }
+        m.scale_in = std::move(in_plan);
+        m.scale_out = std::move(out_plan);
+        image_scale_upload(m.scale_in, s);
+        image_scale_upload(m.scale_out, s);
+    }
+    const size_t n = (size_t)batch * res[0] * res[1], in_bytes = round_up<size_t>(n * 3, 256);
+    grow(m.scaled_io, in_bytes + n * sizeof(float), {m.backend->stream, s});
+    uint8_t* rgb_res = static_cast<uint8_t*>(m.scaled_io.ptr);
+    float* map_res = reinterpret_cast<float*>(rgb_res + in_bytes);
+    image_scale_run(m.scale_in, rgb_dev, batch, rgb_res, s);
+    depthany_compute_batch_device(m, rgb_res, batch, res[0], res[1], map_res, nullptr, s);
+    image_scale_run(m.scale_out, map_res, batch, out_dev, s);
+    if (!stream) VX(vx_stream_sync(s));
+}
+
+void depthany_compute_scaled_batch_host(depthany_model& m, uint8_t const* rgb, int batch, int w, int h, float* out) {
+    check_scaled_batch(rgb, out, batch, w, h);
+    device_turn turn(*m.backend);
+    void* s = m.backend->stream;
+    const size_t n = (size_t)batch * h * w, in_bytes = round_up<size_t>(n * 3, 256);
+    grow(m.host_io, in_bytes + n * sizeof(float), {s});
+    uint8_t* in = static_cast<uint8_t*>(m.host_io.ptr);
+    VX(vx_memcpy_h2d(in, rgb, n * 3, s));
+    depthany_compute_scaled_batch_device(m, in, batch, w, h, in + in_bytes, s);
+    VX(vx_memcpy_d2h(out, in + in_bytes, n * sizeof(float), s));
+}
+
 //
 // overlapped host pipeline
 

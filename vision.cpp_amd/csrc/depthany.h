@@ -13,6 +13,7 @@
 
 #include "gguf.h"
 #include "image.h"
+#include "image_scale_device.h"
 #include "model.h"
 
 namespace visp {
@@ -45,6 +46,8 @@ struct depthany_model : model_base { // vision.h:339-347 counterpart: {backend, 
     std::vector<std::unique_ptr<depthany_step>> steps; // a few lowered shapes, least recently used first out
     long step_clock = 0;                                // ticks of steps[i]->last_use
     device_buffer host_io;    // device staging of the blocking host entry
+    device_buffer scaled_io;  // the any-extent entry's two buffers at the model's extent: the scaled input and the map before it is scaled back
+    image_scale_plan scale_in, scale_out; // that entry's tap tables for the last caller extent (rgb_u8 to the model's extent, alpha_f32 back)
     int split = 0; // sub-batches of a step on parallel streams: 0 = automatic (3 from batch 24, 2 from batch 8; $VISP_SPLIT overrides), 1 = none, 2..4
     bool timing_split = false; // with timing: keep the step's sub-batch split (launches timed per stream while the other streams run)
     depthany_pipeline* shard_pipeline = nullptr; // visp_depthany_compute_sharded's overlapped host pipeline for this model (owned, lazily made)
@@ -71,6 +74,12 @@ void depthany_reserve(depthany_model&, int batch, int w, int h);
 void depthany_compute_batch_device(depthany_model&, void const* rgb_dev, int batch, int w, int h, void* out_dev,
                                    void* raw_out_dev, void* stream);
 void depthany_compute_batch_host(depthany_model&, uint8_t const* rgb, int batch, int w, int h, float* out, float* raw_out);
+// depthany_compute per image with nothing leaving the device: rgb_u8 [B,h,w,3] of ANY extent -> image_scale on the device to
+// depthany_image_extent(w, h) -> depthany_compute_batch_device as it stands -> the normalised map scaled back as alpha_f32 -> out f32 [B,h,w].
+// At the model's own extent it is exactly depthany_compute_batch_device. The two buffers at the model's extent and the tap tables belong to the
+// model and grow like a reserved step's: kept while they fit, replaced (behind a synchronisation) when a call needs more or another extent.
+void depthany_compute_scaled_batch_device(depthany_model&, void const* rgb_dev, int batch, int w, int h, void* out_dev, void* stream);
+void depthany_compute_scaled_batch_host(depthany_model&, uint8_t const* rgb, int batch, int w, int h, float* out);
 
 // Overlapped host pipeline: batches of `batch` images of one extent flow through n_slots slots; for slot k the upload of its
 // input (pinned staging -> HBM on a copy stream), the forward (the model's compute stream) and the download of its output

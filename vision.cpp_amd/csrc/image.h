@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 namespace visp {
 
@@ -48,6 +49,23 @@ image_data image_normalize(image_view const& img, float min = 0, float max = 1);
 // image.cpp:328-356: stb_image_resize v1 semantics (Catmull-Rom enlarging, Mitchell reducing, sRGB-correct for u8, alpha-weighted,
 // edge clamp), restated in image_resize.cpp
 image_data image_scale(image_view const& img, i32x2 target);
+// what image_scale is made of (image_resize.cpp), shared with its device form:
+// one output sample of an axis = sum of w[i] * src[clamp(first + i)], i ascending
+struct taps { int first = 0; std::vector<float> w; };
+std::vector<taps> axis_taps(int in_size, int out_size);
+const float* srgb_to_linear_table();      // 256 entries: sRGB code -> linear light
+const uint32_t* linear_to_srgb_table();   // 104 entries: the fp32 -> sRGB8 encoder's bias / scale pairs
+int alpha_channel(image_format);          // index of the alpha channel, -1 without one
+
+// image_scale on the device (image_scale_device.cpp, kernels_imgscale.hip): B images [B, h, w, ch] of one format and extent -> [B, oh, ow, ch],
+// byte-equal to image_scale for the u8 formats and bit-equal for the f32 ones. Every argument check -- null, format, extents, tap limit -- throws
+// before anything touches a device. dev == nullptr: the calling thread's current HIP device; stream == nullptr: the device's stream. The tap
+// tables are packed and uploaded per call and live for it, so both entries return with the stream synchronised (a caller that must not wait keeps
+// a plan of its own: image_scale_device.h). Equal extents are scaled like any other -- image_scale filters at scale 1 -- a caller that wants a
+// copy there copies.
+struct backend_device;
+void image_scale_batch_device(backend_device const* dev, void const* src, image_format format, int B, int w, int h, void* dst, int ow, int oh, void* stream);
+void image_scale_batch_host(backend_device const* dev, void const* src, image_format format, int B, int w, int h, void* dst, int ow, int oh);
 // converts any supported u8 format to tightly packed rgb_u8 (channel map of image.cpp get_channel_map)
 image_data image_to_rgb_u8(image_view const& img);
 // image.cpp:290-308: the first channel of every pixel as alpha_u8 (any u8 format)

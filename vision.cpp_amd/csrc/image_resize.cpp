@@ -37,8 +37,7 @@ float mitchell(float x) {
     return 0.0f;
 }
 
-// one output sample = sum of w[i] * src[clamp(first + i)]
-struct taps { int first = 0; std::vector<float> w; };
+} // namespace
 
 std::vector<taps> axis_taps(int in_size, int out_size) {
     const float scale = (float)out_size / (float)in_size;
@@ -131,8 +130,7 @@ const float* srgb_to_linear_table() {
     return table;
 }
 
-// fp32 -> sRGB8 as stb_image_resize.h does it (table-driven piecewise-linear conversion over 13 binades x 8 segments)
-uint8_t linear_to_srgb_u8(float in) {
+const uint32_t* linear_to_srgb_table() {
     static const uint32_t tab[104] = {
         0x0073000d, 0x007a000d, 0x0080000d, 0x0087000d, 0x008d000d, 0x0094000d, 0x009a000d, 0x00a1000d, 0x00a7001a, 0x00b4001a, 0x00c1001a,
         0x00ce001a, 0x00da001a, 0x00e7001a, 0x00f4001a, 0x0101001a, 0x010e0033, 0x01280033, 0x01410033, 0x015b0033, 0x01750033, 0x018f0033,
@@ -144,6 +142,14 @@ uint8_t linear_to_srgb_u8(float in) {
         0x2d1d0341, 0x2ebe031f, 0x304d0300, 0x31d105b0, 0x34a80555, 0x37520507, 0x39d504c5, 0x3c37048b, 0x3e7c0458, 0x40a8042a, 0x42bd0401,
         0x44c20798, 0x488e071e, 0x4c1c06b6, 0x4f76065d, 0x52a50610, 0x55ac05cc, 0x5892058f, 0x5b590559, 0x5e0c0a23, 0x631c0980, 0x67db08f6,
         0x6c55087f, 0x70940818, 0x74a007bd, 0x787d076c, 0x7c330723};
+    return tab;
+}
+
+namespace {
+
+// fp32 -> sRGB8 as stb_image_resize.h does it (table-driven piecewise-linear conversion over 13 binades x 8 segments)
+uint8_t linear_to_srgb_u8(float in) {
+    const uint32_t* tab = linear_to_srgb_table();
     const uint32_t min_u = (127u - 13u) << 23, almost_one_u = 0x3f7fffffu;
     float min_f, almost_one;
     memcpy(&min_f, &min_u, 4);
@@ -157,6 +163,8 @@ uint8_t linear_to_srgb_u8(float in) {
     return (uint8_t)((bias + scale * ((u >> 12) & 0xff)) >> 16);
 }
 
+} // namespace
+
 int alpha_channel(image_format f) { // reference src/visp/image.cpp:57-67
     switch (f) {
         case image_format::bgra_u8: return 3;
@@ -168,8 +176,6 @@ int alpha_channel(image_format f) { // reference src/visp/image.cpp:57-67
         default: return 3;
     }
 }
-
-} // namespace
 
 image_data image_scale(image_view const& img, i32x2 target) {
     const int ch = n_channels(img.format), ac = alpha_channel(img.format);

@@ -179,6 +179,19 @@ class Model:
                              stream: int | None = None):
         check(self._api.visp_depthany_compute_batch_device(self._handle, rgb_dev, batch, w, h, out_dev, raw_dev, stream))
 
+    def compute_scaled_batch(self, images: np.ndarray) -> np.ndarray:
+        """images: uint8 [B, h, w, 3] of ANY extent on the host -> float32 [B, h, w] in [0, 1]: depthany_compute per image, scaled on the device."""
+        imgs = np.ascontiguousarray(images, dtype=np.uint8)
+        b, h, w, c = imgs.shape
+        assert c == 3
+        out = np.empty((b, h, w), np.float32)
+        check(self._api.visp_depthany_compute_scaled_batch_host(self._handle, imgs.ctypes.data, b, w, h, out.ctypes.data))
+        return out
+
+    def compute_scaled_batch_device(self, rgb_dev: int, batch: int, w: int, h: int, out_dev: int, stream: int | None = None):
+        """The same on device-resident arrays (addresses): rgb_u8 [batch, h, w, 3] -> f32 [batch, h, w]; nothing leaves the device."""
+        check(self._api.visp_depthany_compute_scaled_batch_device(self._handle, rgb_dev, batch, w, h, out_dev, stream))
+
     def enable_captures(self, enable: bool = True):
         check(self._family_fn("enable_captures")(self._handle, int(enable)))
 
@@ -506,13 +519,20 @@ class DepthPipeline:
         self.close()
 
 
-def image_scale(image: np.ndarray, width: int, height: int, format: ImageFormat = ImageFormat.rgb_u8) -> np.ndarray:
-    """The reference's image_scale (src/visp/image.cpp:328-356) on the host: [h, w, ch] u8 or f32 -> [height, width, ch]."""
+def image_scale(image: np.ndarray, width: int, height: int, format: ImageFormat = ImageFormat.rgb_u8, device: "Device | None" = None) -> np.ndarray:
+    """The reference's image_scale (src/visp/image.cpp:328-356): [h, w, ch] u8 or f32 -> [height, width, ch]. On the host by default; with a
+    device, on that device (up, one fused launch, down), where a leading batch axis [B, h, w, ch] is allowed too. The same bytes either way."""
     api = lib.get_lib()
     is_f32 = format.value >= ImageFormat.rgba_f32.value
     img = np.ascontiguousarray(image, dtype=np.float32 if is_f32 else np.uint8)
-    h, w = img.shape[:2]
     ch = _CHANNELS[format.value]
+    if device is not None:
+        batched = img.ndim == (3 if ch == 1 else 4)
+        b, (h, w) = (img.shape[0] if batched else 1), img.shape[1:3] if batched else img.shape[:2]
+        out = np.empty(((b,) if batched else ()) + (height, width) + (() if ch == 1 else (ch,)), img.dtype)
+        check(api.visp_image_scale_batch_host(device._handle, img.ctypes.data, format.value, b, w, h, out.ctypes.data, width, height))
+        return out
+    h, w = img.shape[:2]
     view = lib.ImageView(w, h, w * ch * img.itemsize, format.value, img.ctypes.data)
     out_view, out_data = lib.ImageView(), c_void_p()
     check(api.visp_image_scale(byref(view), width, height, byref(out_view), byref(out_data)))
@@ -523,6 +543,14 @@ def image_scale(image: np.ndarray, width: int, height: int, format: ImageFormat 
     finally:
         api.visp_image_destroy(out_data)
     return res[..., 0] if ch == 1 else res
+
+
+def image_scale_batch_device(src_dev: int, format: ImageFormat, batch: int, w: int, h: int, dst_dev: int, out_w: int, out_h: int,
+                             device: "Device | None" = None, stream: int | None = None):
+    """image_scale on device-resident batches (addresses): src [batch, h, w, ch] -> dst [batch, out_h, out_w, ch] of one format, one fused launch,
+    the bytes of image_scale. Returns with the stream synchronised (the tap tables live for the call)."""
+    check(lib.get_lib().visp_image_scale_batch_device(device._handle if device is not None else None, src_dev, format.value, int(batch), int(w), int(h), dst_dev,
+                                                      int(out_w), int(out_h), stream))
 
 
 # ---- the matting image ops (reference include/visp/image.h:141-170). Arrays are [h, w] or [h, w, ch]; a view of a wider array keeps its row stride.
