@@ -473,6 +473,15 @@ inline std::vector<detected_obj> yolov9t_detect(yolov9t_model& model, image_view
     out.resize(size_t(std::min<int32_t>(n, int32_t(out.size()))));
     return out;
 }
+// batch letterboxed u8 images [batch, size, size, channels] on the device -> out_dev [batch][p.max_det] detections and counts_dev [batch] on the
+// device, in input pixels; enqueued on stream (hipStream_t or null), not synchronised
+inline void yolov9t_detect_batch_resident(yolov9t_model& model, void const* img_dev, int channels, int batch, int size, detected_obj* out_dev,
+                                          int32_t* counts_dev, NMSParams const& p = {}, void* stream = nullptr) {
+    const visp_yolov9t_nms_params c{p.conf_thres, p.iou_thres, p.max_det, p.max_nms, p.max_wh};
+    detail::check(visp_yolov9t_detect_batch_resident(model.handle, img_dev, channels, batch, size, &c, out_dev, counts_dev, stream));
+}
+// the NMS of yolov9t_detect on the device (same detections, less read back); off by default
+inline void yolov9t_set_device_nms(yolov9t_model& model, bool enable) { detail::check(visp_yolov9t_set_device_nms(model.handle, enable ? 1 : 0)); }
 } // namespace yolov9t
 
 // ESRGAN (vision.h:284-304): any size, tiled, -> rgba_u8 at scale x the input extent (vision.cpp:220-253)

@@ -252,13 +252,24 @@ VISP_API int32_t visp_yolov9t_detect_batch_host(visp_model* m, uint8_t const* im
                                                 visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts);
 VISP_API int32_t visp_yolov9t_detect_batch_device(visp_model* m, void const* img, int32_t channels, int32_t batch, int32_t size,
                                                   visp_yolov9t_nms_params const* params, visp_detection* out, int32_t* counts, void* stream);
+/* The device form with device results: out_dev [B][max_det] visp_detection and counts_dev i32 [B] are device pointers, rows at and behind
+ * counts_dev[b] are left as they were. The copy-in, the launch list and the NMS kernels (vx_yolo_nms, the host NMS's decisions bit for
+ * bit) are enqueued on the stream and the call returns without synchronising; iou, max_det, max_nms and max_wh are read at every call.
+ * max_det above 4096 is refused. */
+VISP_API int32_t visp_yolov9t_detect_batch_resident(visp_model* m, void const* img, int32_t channels, int32_t batch, int32_t size,
+                                                    visp_yolov9t_nms_params const* params, void* out_dev, int32_t* counts_dev, void* stream);
+/* enable != 0: detect and detect_batch_host / _device run the NMS on the device too and read back counts and B x max_det detections instead
+ * of the dense boxes and the candidate lists; the results are the same bytes. A max_det above 4096 takes the host path for that call.
+ * Off by default. */
+VISP_API int32_t visp_yolov9t_set_device_nms(visp_model* m, int32_t enable);
 /* the network on f32 rgb [n, size, size, 3] in [0, 1] -> boxes f32 [n, A, 4] (xyxy, input pixels), scores f32 [n, A, nc] (host buffers) */
 VISP_API int32_t visp_yolov9t_forward_host(visp_model* m, float const* rgb, int32_t n, int32_t size, float* boxes, float* scores);
 /* host only: letterbox (rgb_u8 / rgba_u8 of any extent -> rgb_u8 [size, size, 3]) and NMS over dense boxes [A, 4] / scores [A, nc] */
 VISP_API int32_t visp_yolov9t_letterbox(visp_image_view const* image, int32_t size, uint8_t* out_rgb, float* gain, float* pad_w, float* pad_h);
 /* host only: scale_boxes (yolov9t.cpp:1255-1281) in place: (v - pad) / gain with the unrounded pads, clamped to [0, width] / [0, height] */
 VISP_API int32_t visp_yolov9t_scale_boxes(visp_detection* dets, int32_t n, int32_t width, int32_t height, float gain, float pad_w, float pad_h);
-/* the last batch call (detect, detect_batch_*) split in ms: {launch list on the device (HIP events), candidate readback, host NMS} */
+/* the last batch call (detect, detect_batch_host / _device) split in ms: {launch list on the device (HIP events), candidate readback, host NMS};
+ * with the device NMS on: {launch list + NMS on the device, readback of the detections, 0} */
 VISP_API int32_t visp_yolov9t_last_split(visp_model const* m, float out_ms[3]);
 VISP_API int32_t visp_yolov9t_nms(float const* boxes, float const* scores, int32_t n_anchors, int32_t nc, visp_yolov9t_nms_params const* params,
                                   visp_detection* out, int32_t capacity, int32_t* n);

@@ -670,6 +670,19 @@ VX_API int vx_yolo_upsample2_f16(const void* x, int64_t x_pix, void* y, int64_t 
  * deterministic). cand_* may be NULL (dense outputs only). nc % 8 == 0 */
 VX_API int vx_yolo_decode(const void* raw0, const void* raw1, const void* raw2, int B, int S, int nc, float* boxes, float* scores, float conf,
                           int* cand_count, int* cand_idx, float* cand_score, void* stream);
+/* non_max_suppression (yolov9t.cpp:1117-1253) over what vx_yolo_decode leaves on the device (kernels_yolo_nms.hip): per image b the
+ * min(max(cand_count[b], 0), A * nc) candidates of its list, in any order, are ranked by (score descending, idx ascending; scores are not
+ * negative and not NaN, every idx of a list is distinct and below A * nc), the first max_nms go through the greedy pass -- a candidate is
+ * dropped iff an earlier kept one overlaps it by more than iou, the class offset float(class * max_wh) added to x1 and x2 only, a union
+ * that is not positive gives 0 -- and the first max_det kept are written in that order: out [B][max_det] rows of seven 4-byte words
+ * {x1, y1, x2, y2, score, class, score} (visp_detection), counts i32 [B]. Rows at and behind counts[b] are not written. The decisions and
+ * the bytes are those of the host's visp_yolov9t_nms on the same candidates. Nothing depends on a host-side count; the call only
+ * enqueues. 1 <= max_det <= 4096 (the kept list is 16 bytes a row in LDS), max_nms >= 1, 0 <= iou <= 1, B <= 65535; boxes and workspace
+ * 16-byte aligned, the other pointers 4-byte; workspace: vx_yolo_nms_workspace_bytes(B, A, nc, max_nms) bytes = the ranked
+ * min(A * nc, max_nms) entries of every image, 16 + 8 bytes each in two arrays rounded up to 256 bytes (0 for arguments the launcher refuses). */
+VX_API size_t vx_yolo_nms_workspace_bytes(int B, int A, int nc, int max_nms);
+VX_API int vx_yolo_nms(const float* boxes, const int* cand_count, const int* cand_idx, const float* cand_score, int B, int A, int nc, float iou,
+                       int max_det, int max_nms, int max_wh, void* workspace, size_t workspace_bytes, void* out, int* counts, void* stream);
 
 /* ---- matting image ops (kernels_matting.hip; image_blur, image_erosion, image_estimate_foreground, image_alpha_composite of the reference's
  * src/visp/image.cpp:358-535). Images are [B, h, w] pixels, rows *_row ELEMENTS apart (image b starts h rows behind image b - 1), or

@@ -2,8 +2,10 @@
 """YOLOv9t throughput on one GPU (synthetic weights of the real channel table), one JSON line:
 batch-1 detect latency from a 1280x720 host image, images/s at batch 1, 16 and 64 with each call split into the replayed launch
 list's device time (HIP events), the candidate readback and the host NMS, the
-schedule's own GFLOP / bytes per image and the share of the HBM or MFMA bound (whichever binds)."""
+schedule's own GFLOP / bytes per image and the share of the HBM or MFMA bound (whichever binds). Next to each batch's figures, from the same
+run: the same call with the NMS on the device (set_device_nms, windows alternated with the host-NMS ones) and detect_batch_resident by device events."""
 import argparse
+import ctypes as C
 import json
 import sys
 import tempfile
@@ -16,6 +18,7 @@ from __graft_entry__ import load_package  # noqa: E402
 load_package()
 import numpy as np  # noqa: E402
 
+from visioncpp_amd import _lib as L  # noqa: E402
 from visioncpp_amd import synth, vision  # noqa: E402
 
 HBM_BPS, MFMA_FLOPS = 8.0e12, 2.5e15  # MI355X: HBM3E bandwidth, dense f16 MFMA peak
@@ -44,6 +47,40 @@ flops, byts = sum(r["flops"] for r in rows), sum(r["bytes"] for r in rows)
 res["gflop_per_image"] = round(flops / 1e9, 3)
 res["mbytes_per_image"] = round(byts / 1e6, 2)
 res["groups_ms_b1"] = {r["name"]: round(r["ms"], 4) for r in rows}
+
+
+def timed_calls(imgs, n, device_nms):
+    """seconds per detect_batch call over a window of n, and the split of its last call"""
+    model.set_device_nms(device_nms)
+    model.detect_batch(imgs)
+    t0 = time.perf_counter()
+    for _ in range(n):
+        model.detect_batch(imgs)
+    return (time.perf_counter() - t0) / n, model.last_split
+
+
+def resident_ms(imgs, n):
+    """device ms per detect_batch_resident call: HIP events around n calls enqueued back to back on one stream"""
+    api, B = L.get_lib(), len(imgs)
+    src, out, counts = vision.DeviceBuffer.from_numpy(imgs), vision.DeviceBuffer(B * 300 * 28), vision.DeviceBuffer(B * 4)
+    stream, e0, e1, ms = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_float()
+    L.vx_check(api.vx_stream_create(C.byref(stream)))
+    L.vx_check(api.vx_event_create(C.byref(e0)))
+    L.vx_check(api.vx_event_create(C.byref(e1)))
+    for timed in (False, True):
+        L.vx_check(api.vx_event_record(e0, stream))
+        for _ in range(n if timed else 2):
+            model.detect_batch_resident(src.ptr, imgs.shape[3], B, S, out.ptr, counts.ptr, stream=stream)
+        L.vx_check(api.vx_event_record(e1, stream))
+        L.vx_check(api.vx_stream_sync(stream))
+    L.vx_check(api.vx_event_elapsed_ms(e0, e1, C.byref(ms)))
+    kept = counts.to_numpy(np.int32, (B,))
+    for h in (e0, e1):
+        api.vx_event_destroy(h)
+    api.vx_stream_destroy(stream)
+    return ms.value / n, int(kept.sum())
+
+
 for B in (1, 16, 64):
     imgs = synth.images(B, S, S, seed=3)
     for _ in range(3):
@@ -57,6 +94,14 @@ for B in (1, 16, 64):
     res[f"batch{B}_split_ms"] = {k: round(v, 3) for k, v in sp.items()}
     res[f"batch{B}_ms"] = round(dt * 1e3, 3)
     res[f"batch{B}_images_per_s"] = round(B / dt, 1)
+    # the device NMS against the host path toggled in this run: three windows each, alternated; the best window of each
+    windows = [[timed_calls(imgs, n, on) for on in (False, True)] for _ in range(3)]
+    model.set_device_nms(False)
+    (host_dt, _), (dev_dt, dev_sp) = (min((w[i] for w in windows), key=lambda r: r[0]) for i in (0, 1))
+    r_ms, kept = resident_ms(imgs, n)
+    res[f"batch{B}_device_nms"] = dict(host_nms_images_per_s=round(B / host_dt, 1), images_per_s=round(B / dev_dt, 1), ms=round(dev_dt * 1e3, 3),
+                                       split_ms={k: round(v, 3) for k, v in dev_sp.items()}, resident_device_ms=round(r_ms, 3),
+                                       resident_images_per_s=round(B / r_ms * 1e3, 1), detections=kept)
     if B == 64:
         model.enable_timing(True)
         model.detect_batch(imgs)

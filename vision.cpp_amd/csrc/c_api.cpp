@@ -679,6 +679,17 @@ int32_t visp_yolov9t_detect_batch_device(visp_model* m, void const* img, int32_t
     });
 }
 
+int32_t visp_yolov9t_detect_batch_resident(visp_model* m, void const* img, int32_t channels, int32_t batch, int32_t size,
+                                           visp_yolov9t_nms_params const* params, void* out_dev, int32_t* counts_dev, void* stream) {
+    return handle_errors([&]() {
+        yolov9t_detect_batch_resident(as_yolov9t(m), img, channels, batch, size, nms_params(params), out_dev, counts_dev, stream);
+    });
+}
+
+int32_t visp_yolov9t_set_device_nms(visp_model* m, int32_t enable) {
+    return handle_errors([&]() { as_yolov9t(m).device_nms = enable != 0; });
+}
+
 int32_t visp_yolov9t_forward_host(visp_model* m, float const* rgb, int32_t n, int32_t size, float* boxes, float* scores) {
     return handle_errors([&]() { yolov9t_forward_host(as_yolov9t(m), rgb, n, size, boxes, scores); });
 }

@@ -190,10 +190,20 @@ struct yolo_exec : model_pass<yolov9t_model> {
     // fixed buffers (laid out first, in this order)
     uint8_t *in_u8 = nullptr, *in_f32 = nullptr, *boxes = nullptr, *scores = nullptr, *cand_count = nullptr, *cand_idx = nullptr, *cand_score = nullptr,
             *cap_tmp = nullptr;
+    // the device NMS's buffers, placed behind everything else by make_exec (their size follows max_nms / max_det: no other offset may depend on it)
+    uint8_t *nms_ws = nullptr, *det_out = nullptr, *det_count = nullptr;
+    size_t nms_ws_bytes = 0;
+    struct nms_place { size_t ws = 0, ws_bytes = 0, out = 0, count = 0; }; // offsets into the workspace
     fmap in8, raw[3];
 
-    yolo_exec(yolov9t_model& mm, void* s, int b, int size, bool d)
+    yolo_exec(yolov9t_model& mm, void* s, int b, int size, bool d, const nms_place* nms = nullptr)
         : model_pass(mm, s, mm.weight_arena.ptr, d), ws(static_cast<uint8_t*>(mm.ws.ptr)), B(b), S(size), A(yolov9t_anchors(size)), nc(mm.num_classes) {
+        if (nms) {
+            nms_ws = ws + nms->ws;
+            nms_ws_bytes = nms->ws_bytes;
+            det_out = ws + nms->out;
+            det_count = ws + nms->count;
+        }
         in_u8 = alloc((size_t)B * S * S * 4);
         in_f32 = alloc((size_t)B * S * S * 12);
         boxes = alloc((size_t)B * A * 16);
@@ -390,17 +400,28 @@ void check_extent(int B, int S) {
     if (S < 64 || S % 32 != 0 || S > 4096) throw except("yolov9t: input size %d is not a multiple of 32 in [64, 4096]", S);
 }
 
-// a workspace that holds the layout of (B, S); graphs of other extents stay valid unless the buffer moves
-yolo_exec make_exec(yolov9t_model& m, int B, int S, void* stream) {
+// whether vx_yolo_nms takes these parameters (check_params has passed): the kept list of max_det rows must fit its LDS
+bool device_nms_takes(yolo_nms_params const& p) { return p.max_det <= yolov9t_device_nms_max_det; }
+
+// a workspace that holds the layout of (B, S); graphs of other extents stay valid unless the buffer moves. nms: the device NMS's ranked
+// workspace for nms->max_nms and its batch x max_det output follow the launch list's buffers, whose offsets they leave alone
+yolo_exec make_exec(yolov9t_model& m, int B, int S, void* stream, const yolo_nms_params* nms = nullptr) {
     check_extent(B, S);
     size_t total;
+    yolo_exec::nms_place place;
     {
         yolo_exec dry(m, stream, B, S, true);
         dry.run_u8(3, 0.0f);
+        if (nms) {
+            place.ws_bytes = vx_yolo_nms_workspace_bytes(B, dry.A, dry.nc, nms->max_nms);
+            place.ws = dry.layout.take(place.ws_bytes);
+            place.out = dry.layout.take((size_t)B * nms->max_det * sizeof(yolo_detection));
+            place.count = dry.layout.take((size_t)B * 4);
+        }
         total = dry.layout.top;
     }
     if (grow(m.ws, total, {m.backend->stream, stream})) m.graphs.clear();
-    return yolo_exec(m, stream, B, S, false);
+    return yolo_exec(m, stream, B, S, false, nms ? &place : nullptr);
 }
 
 void check_params(yolo_nms_params const& p) {
@@ -507,14 +528,10 @@ namespace {
 using clock_type = std::chrono::steady_clock;
 float ms_since(clock_type::time_point t0) { return std::chrono::duration<float, std::milli>(clock_type::now() - t0).count(); }
 
-// the batch entry once the images are in the workspace's in_u8: the launch list (hipGraph replay after the first call of a key), then the
-// candidate lists back to the host and NMS per image; m.last_split_ms = {launch list on the device, readback, host NMS}
-std::vector<std::vector<yolo_detection>> run_batch(yolov9t_model& m, yolo_exec& ex, int channels, yolo_nms_params const& p) {
+// the launch list of (batch, S, channels, conf) on ex's stream: a hipGraph replay after the first call of a key
+void enqueue_launch_list(yolov9t_model& m, yolo_exec& ex, int channels, yolo_nms_params const& p) {
     void* s = ex.stream;
     const int batch = ex.B, S = ex.S;
-    for (void*& e : m.events)
-        if (!e) VX(vx_event_create(&e));
-    VX(vx_event_record(m.events[0], s));
     uint32_t conf_bits;
     memcpy(&conf_bits, &p.conf, 4);
     const auto gkey = std::make_tuple(batch * 8 + channels, S, (int)conf_bits); // the decode's threshold is part of the launch list
@@ -523,6 +540,54 @@ std::vector<std::vector<yolo_detection>> run_batch(yolov9t_model& m, yolo_exec& 
         pass.run_u8(channels, p.conf);
         pass.finish_timing();
     });
+}
+
+// vx_yolo_nms on the lists the launch list left, behind the replay (not captured: its arguments are this call's)
+void enqueue_nms(yolov9t_model& m, yolo_exec& ex, yolo_nms_params const& p, void* out_dev, int32_t* counts_dev) {
+    ex.mark("nms", 0, 0);
+    VX(vx_yolo_nms(reinterpret_cast<const float*>(ex.boxes), reinterpret_cast<const int*>(ex.cand_count), reinterpret_cast<const int*>(ex.cand_idx),
+                   reinterpret_cast<const float*>(ex.cand_score), ex.B, ex.A, ex.nc, p.iou, p.max_det, p.max_nms, p.max_wh, ex.nms_ws, ex.nms_ws_bytes, out_dev,
+                   counts_dev, ex.stream));
+    ex.finish_timing(m.last_timing, /*append=*/true);
+}
+
+// the batch entry with the device NMS: counts and batch x max_det rows come back; m.last_split_ms = {launch list + NMS on the device, readback, 0}
+std::vector<std::vector<yolo_detection>> run_batch_device_nms(yolov9t_model& m, yolo_exec& ex, int channels, yolo_nms_params const& p) {
+    void* s = ex.stream;
+    const size_t batch = (size_t)ex.B, max_det = (size_t)p.max_det;
+    for (void*& e : m.events)
+        if (!e) VX(vx_event_create(&e));
+    VX(vx_event_record(m.events[0], s));
+    enqueue_launch_list(m, ex, channels, p);
+    enqueue_nms(m, ex, p, ex.det_out, reinterpret_cast<int32_t*>(ex.det_count));
+    VX(vx_event_record(m.events[1], s));
+    VX(vx_event_elapsed_ms(m.events[0], m.events[1], &m.last_split_ms[0]));
+    const clock_type::time_point t_read = clock_type::now();
+    std::vector<int32_t> counts(batch);
+    std::vector<yolo_detection> rows(batch * max_det);
+    VX(vx_memcpy_d2h(counts.data(), ex.det_count, batch * 4, s));
+    VX(vx_memcpy_d2h(rows.data(), ex.det_out, rows.size() * sizeof(yolo_detection), s));
+    VX(vx_stream_sync(s));
+    m.last_split_ms[1] = ms_since(t_read);
+    m.last_split_ms[2] = 0;
+    std::vector<std::vector<yolo_detection>> out(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        if (counts[b] < 0 || counts[b] > p.max_det) throw except("yolov9t: detection count %d out of range", counts[b]);
+        out[b].assign(rows.begin() + (ptrdiff_t)(b * max_det), rows.begin() + (ptrdiff_t)(b * max_det + (size_t)counts[b]));
+    }
+    return out;
+}
+
+// the batch entry once the images are in the workspace's in_u8: the launch list (hipGraph replay after the first call of a key), then the
+// candidate lists back to the host and NMS per image; m.last_split_ms = {launch list on the device, readback, host NMS}
+std::vector<std::vector<yolo_detection>> run_batch(yolov9t_model& m, yolo_exec& ex, int channels, yolo_nms_params const& p) {
+    if (ex.nms_ws) return run_batch_device_nms(m, ex, channels, p);
+    void* s = ex.stream;
+    const int batch = ex.B;
+    for (void*& e : m.events)
+        if (!e) VX(vx_event_create(&e));
+    VX(vx_event_record(m.events[0], s));
+    enqueue_launch_list(m, ex, channels, p);
     VX(vx_event_record(m.events[1], s));
     VX(vx_event_elapsed_ms(m.events[0], m.events[1], &m.last_split_ms[0])); // waits for the launch list
     const clock_type::time_point t_read = clock_type::now();
@@ -572,9 +637,22 @@ std::vector<std::vector<yolo_detection>> yolov9t_detect_batch_device(yolov9t_mod
     check_batch_args(img_dev, channels, p);
     device_turn turn(*m.backend);
     void* s = stream ? stream : m.backend->stream;
-    yolo_exec ex = make_exec(m, batch, S, s);
+    yolo_exec ex = make_exec(m, batch, S, s, m.device_nms && device_nms_takes(p) ? &p : nullptr);
     VX(vx_memcpy_d2d(ex.in_u8, img_dev, (size_t)batch * S * S * channels, s));
     return run_batch(m, ex, channels, p);
+}
+
+void yolov9t_detect_batch_resident(yolov9t_model& m, void const* img_dev, int channels, int batch, int S, yolo_nms_params const& p, void* out_dev,
+                                   int32_t* counts_dev, void* stream) {
+    check_batch_args(img_dev, channels, p);
+    if (!out_dev || !counts_dev) throw except("yolov9t: null output pointer");
+    if (!device_nms_takes(p)) throw except("yolov9t: max_det %d is above the device NMS's %d rows", p.max_det, yolov9t_device_nms_max_det);
+    device_turn turn(*m.backend);
+    void* s = stream ? stream : m.backend->stream;
+    yolo_exec ex = make_exec(m, batch, S, s, &p);
+    VX(vx_memcpy_d2d(ex.in_u8, img_dev, (size_t)batch * S * S * channels, s));
+    enqueue_launch_list(m, ex, channels, p);
+    enqueue_nms(m, ex, p, out_dev, counts_dev);
 }
 
 std::vector<std::vector<yolo_detection>> yolov9t_detect_batch_host(yolov9t_model& m, uint8_t const* img, int channels, int batch, int S,
@@ -582,7 +660,7 @@ std::vector<std::vector<yolo_detection>> yolov9t_detect_batch_host(yolov9t_model
     check_batch_args(img, channels, p);
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
-    yolo_exec ex = make_exec(m, batch, S, s);
+    yolo_exec ex = make_exec(m, batch, S, s, m.device_nms && device_nms_takes(p) ? &p : nullptr);
     VX(vx_memcpy_h2d(ex.in_u8, img, (size_t)batch * S * S * channels, s)); // straight into the workspace's input
     return run_batch(m, ex, channels, p);
 }

@@ -52,6 +52,9 @@ struct yolov9t_model : model_base {
     std::map<std::tuple<int, int, int>, captured_graph> graphs;
     void* events[2] = {nullptr, nullptr};     // around the launch list of a batch call
     float last_split_ms[3] = {0, 0, 0};       // last batch call: launch list on the device (events), candidate readback, host NMS
+    // off (the default): the batch entries read the dense boxes and the candidate lists back and run the NMS on the host. On: vx_yolo_nms
+    // behind the launch list, and only counts + batch x max_det detections come back; last_split_ms = {launch list + NMS, readback, 0}
+    bool device_nms = false;
     ~yolov9t_model() override;
 };
 
@@ -71,6 +74,13 @@ std::vector<std::vector<yolo_detection>> yolov9t_detect_batch_device(yolov9t_mod
                                                                      yolo_nms_params const& p, void* stream);
 std::vector<std::vector<yolo_detection>> yolov9t_detect_batch_host(yolov9t_model&, uint8_t const* img, int channels, int batch, int S,
                                                                    yolo_nms_params const& p);
+// The same input, nothing returned to the host: out_dev [batch][max_det] detections (7 x 4 bytes, visp_detection) and counts_dev i32 [batch] on the
+// device, rows at and behind counts_dev[b] left as they were. Enqueues the copy-in, the launch list and vx_yolo_nms on the stream and returns without
+// synchronising. The NMS launches follow the replayed graph, so iou / max_det / max_nms / max_wh are those of this call; max_det above
+// yolov9t_device_nms_max_det is refused (this entry has no host path to fall back to).
+void yolov9t_detect_batch_resident(yolov9t_model&, void const* img_dev, int channels, int batch, int S, yolo_nms_params const& p, void* out_dev,
+                                   int32_t* counts_dev, void* stream);
+constexpr int yolov9t_device_nms_max_det = 4096; // vx_yolo_nms keeps its list of kept boxes in LDS
 // the network on f32 rgb [n, S, S, 3] in [0, 1] (host) -> boxes f32 [n, A, 4], scores f32 [n, A, nc] (host): parity tests
 void yolov9t_forward_host(yolov9t_model&, float const* rgb, int n, int S, float* boxes, float* scores);
 // one image of any extent -> detections in its own pixel coordinates (inference_yolov9t.cpp:300-405)

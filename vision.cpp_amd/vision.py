@@ -884,9 +884,20 @@ class Yolov9t(Model):
                                                          counts.ctypes.data_as(ctypes.POINTER(c_int32)), stream))
         return [out[i, : counts[i]].copy() for i in range(batch)]
 
+    def detect_batch_resident(self, img_dev: int, channels: int, batch: int, size: int, out_dev: int, counts_dev: int, stream: int | None = None, **nms) -> None:
+        """letterboxed u8 [batch, size, size, channels] at device address img_dev -> DETECTION_DTYPE [batch, max_det] at out_dev and i32 [batch] at
+        counts_dev, both on the device (rows behind a count are left as they were). Enqueued on `stream`, not synchronised."""
+        p = _nms_params(**nms)
+        check(self._api.visp_yolov9t_detect_batch_resident(self._handle, img_dev, channels, batch, size, byref(p), out_dev, counts_dev, stream))
+
+    def set_device_nms(self, enable: bool) -> None:
+        """detect / detect_batch / detect_batch_device with the NMS on the device: the same detections, only they are read back. Off by default."""
+        check(self._api.visp_yolov9t_set_device_nms(self._handle, int(bool(enable))))
+
     @property
     def last_split(self) -> dict:
-        """The last batch call in ms: the launch list on the device (HIP events), the candidate readback, the host NMS."""
+        """The last batch call in ms: the launch list on the device (HIP events), the candidate readback, the host NMS; with the device NMS
+        on: the launch list and the NMS on the device, the readback of the detections, 0."""
         out = (ctypes.c_float * 3)()
         check(self._api.visp_yolov9t_last_split(self._handle, out))
         return dict(device_ms=out[0], readback_ms=out[1], nms_ms=out[2])
