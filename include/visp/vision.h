@@ -207,6 +207,32 @@ inline bool image_remove_small_regions(image_span const& mask, int min_area, reg
     for (size_t y = 0; y < h; ++y) std::memcpy(static_cast<uint8_t*>(mask.data) + y * size_t(mask.stride), packed.data() + y * w, w);
     return changed != 0;
 }
+// not in the reference's header: COCO's uncompressed RLE of an alpha_u8 mask as SAM writes it, encoded on the device (non-zero = foreground). size is
+// {width, height}; counts are the runs in column-major pixel order, alternating from background (counts[0] is 0 when the top-left pixel is foreground).
+struct mask_rle {
+    i32x2 size{0, 0};
+    std::vector<uint32_t> counts;
+};
+// releases the library's buffer of an RLE host call when the scope ends, also by an exception
+struct rle_owner {
+    visp_rle_data* data;
+    explicit rle_owner(visp_rle_data* d) : data(d) {}
+    rle_owner(rle_owner const&) = delete;
+    rle_owner& operator=(rle_owner const&) = delete;
+    ~rle_owner() { visp_rle_destroy(data); }
+};
+// runs on the calling thread's current HIP device, like image_remove_small_regions above: the image ops of this header take no device
+inline mask_rle image_rle_encode(image_view const& mask) {
+    if (mask.format != image_format::alpha_u8) throw exception("image_rle_encode: expected an alpha_u8 mask");
+    const size_t w = size_t(mask.extent[0]), h = size_t(mask.extent[1]);
+    std::vector<uint8_t> packed(w * h);
+    for (size_t y = 0; y < h; ++y) std::memcpy(packed.data() + y * w, static_cast<uint8_t const*>(mask.data) + y * size_t(mask.stride), w);
+    int64_t offsets[2] = {0, 0};
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_encode_host(packed.data(), 1, mask.extent[0], mask.extent[1], offsets, &runs, &owner.data, nullptr));
+    return mask_rle{mask.extent, std::vector<uint32_t>(runs, runs + offsets[1])};
+}
 // image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
 inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
     visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};
@@ -570,9 +596,13 @@ struct sam_generate_params { // SAM's defaults
     // SAM's min_mask_region_area: above 0, holes and islands of fewer pixels are removed from the masks on the device and a second NMS runs
     // (postprocess_small_regions); unchanged masks then come first and changed ones behind them, each by predicted iou -- not the order without cleaning
     int min_mask_region_area = 0;
+    // SAM's output_mode "uncompressed_rle": the masks are run-length encoded on the device behind the generate call and come as sam_mask::rle; no mask byte
+    // is read back and sam_mask::segmentation stays empty
+    bool output_rle = false;
 };
 struct sam_mask {
     image_data segmentation;   // alpha_u8 at the encoded image's extent, 0 / 255
+    mask_rle rle;              // with sam_generate_params::output_rle, in place of segmentation
     int area = 0;              // pixels that are 255
     i32x2 bbox_top_left{0, 0}, bbox_extent{0, 0}; // of those pixels; 0, 0, 0, 0 for an empty mask
     float predicted_iou = 0, stability_score = 0;
@@ -586,9 +616,15 @@ inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t>
     check(visp_sam_image_extent(model.handle, &w, &h));
     const size_t px = size_t(w) * size_t(h), rows = size_t(cap > 0 ? cap : 0);
     std::vector<int32_t> n_arg(size_t(n), n_args), info_i(rows * 8);
-    std::vector<uint8_t> masks(rows * px);
+    std::vector<uint8_t> masks(p.output_rle ? 0 : rows * px);
     std::vector<float> info_f(rows * 2);
-    if (p.min_mask_region_area != 0)
+    std::vector<int64_t> offsets(rows + 1);
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr); // holds the library's buffer with output_rle
+    if (p.output_rle)
+        check(visp_sam_generate_masks_rle_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh,
+                                               cap, p.min_mask_region_area, info_i.data(), info_f.data(), counts, offsets.data(), &runs, &owner.data));
+    else if (p.min_mask_region_area != 0)
         check(visp_sam_generate_masks_clean_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh,
                                                  cap, p.min_mask_region_area, masks.data(), info_i.data(), info_f.data(), counts));
     else
@@ -597,8 +633,12 @@ inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t>
     std::vector<sam_mask> out;
     for (int32_t k = 0; k < counts[0]; ++k) {
         sam_mask s;
-        s.segmentation = image_alloc({w, h}, image_format::alpha_u8);
-        std::memcpy(s.segmentation.data.get(), masks.data() + size_t(k) * px, px);
+        if (p.output_rle) {
+            s.rle = mask_rle{i32x2{w, h}, std::vector<uint32_t>(runs + offsets[size_t(k)], runs + offsets[size_t(k) + 1])};
+        } else {
+            s.segmentation = image_alloc({w, h}, image_format::alpha_u8);
+            std::memcpy(s.segmentation.data.get(), masks.data() + size_t(k) * px, px);
+        }
         int32_t const* r = info_i.data() + size_t(k) * 8;
         s.prompt = r[0]; s.plane = r[1];
         s.bbox_top_left = i32x2{r[2], r[3]};

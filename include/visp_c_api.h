@@ -48,6 +48,7 @@ typedef struct visp_image_view {
 typedef struct visp_image_data visp_image_data; /* visp::image_data, owned by the library */
 typedef struct visp_device visp_device;         /* visp::backend_device */
 typedef struct visp_model visp_model;           /* any_model (c-api.cpp:193) */
+typedef struct visp_rle_data visp_rle_data;     /* the runs of an RLE host call, owned by the library */
 
 /* ---- Part 1: the reference's symbols ------------------------------------------------- */
 VISP_API char const* visp_get_last_error(void);                                   /* c-api.cpp:147 */
@@ -309,7 +310,7 @@ VISP_API int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* promp
 VISP_API int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height);
 /* prompts per internal chunk of the batch calls: 1 .. 256, default 64. It sizes the workspace: about 27 MB per prompt in flight. */
 VISP_API int32_t visp_sam_set_prompt_chunk(visp_model* m, int32_t n);
-/* Automatic mask generation: SAM's automatic mask generator (one crop layer, no crop-edge filter, no hole / island removal, no RLE) on n prompts in the
+/* Automatic mask generation: SAM's automatic mask generator (one crop layer, no crop-edge filter, no hole / island removal, no RLE: visp_sam_generate_masks_rle_host) on n prompts in the
  * format of the batch calls above (at most 5461: three candidates per prompt, logit planes 0 .. 2, candidate = 3 * prompt + plane). A candidate is kept iff its
  * predicted iou > pred_iou_thresh and its stability score (logits > +offset over logits > -offset, counted on the decoder's 256^2 logits over the part of
  * the plane the image occupies) >= stability_thresh; the kept are ranked by predicted iou and de-duplicated by greedy NMS on the boxes of their positive
@@ -344,6 +345,15 @@ VISP_API int32_t visp_sam_generate_masks_clean_device(visp_model* m, int32_t con
 VISP_API int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
                                                     float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, uint8_t* masks_u8,
                                                     int32_t* info_i32, float* info_f32, int32_t* counts);
+/* The generate call with RLE records out instead of mask bytes (SAM's output_mode "uncompressed_rle"): visp_sam_generate_masks_clean_device on the same arguments
+ * into a staging buffer the model owns on the device (capacity * h * w bytes), then visp_image_rle_encode_* 's encoder on the first counts[0] masks behind it on
+ * the same stream. info_i32, info_f32 and counts are those of visp_sam_generate_masks_clean_host on the same arguments (counts i32 [4]; min_region_area = 0
+ * writes its first two). Mask k's runs are runs[offsets[k] .. offsets[k + 1]), offsets i64 [capacity + 1] (entries behind counts[0] repeat the last one); the
+ * runs lie in a library-owned buffer, released by visp_rle_destroy(*out_data). Only the records, the run counts and the runs cross to the host: no mask byte
+ * does. Blocks. */
+VISP_API int32_t visp_sam_generate_masks_rle_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                                  float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, int32_t* info_i32,
+                                                  float* info_f32, int32_t* counts, int64_t* offsets_i64, uint32_t const** runs_u32, visp_rle_data** out_data);
 /* diagnostics, as visp_sam_generate_last_split: its four figures and a fifth, the cleaning stage of the last call (0 without one); and that stage alone as
  * {clean, records + second NMS, gather} */
 VISP_API int32_t visp_sam_generate_last_split5(visp_model const* m, float out_ms[5]);
@@ -412,6 +422,21 @@ VISP_API int32_t visp_image_remove_small_regions_device(void* masks_u8_dev, int3
 /* the same on host arrays: up, clean, down; blocks */
 VISP_API int32_t visp_image_remove_small_regions_host(uint8_t* masks_u8, int32_t n, int32_t w, int32_t h, int32_t min_area, int32_t mode, int32_t* changed_i32,
                                                       visp_device const* dev);
+/* COCO's uncompressed RLE of n u8 masks [n][h][w] as SAM's mask_to_rle_pytorch writes it, on the device: a pixel is foreground iff its byte is non-zero, pixels
+ * are visited in column-major order p = x * h + y, the runs alternate from background (the first is 0 when pixel 0 is foreground), continue across column ends
+ * and sum to w * h; w * h below 2^31 - 1. n_runs i32 [n]: each mask's TRUE number of runs; runs u32 [n][run_stride]: the first min(n_runs[b], run_stride) of mask b,
+ * nothing behind them (runs NULL or run_stride 0: the count alone). counts (nullable): a device i32, masks at and behind counts[0] are neither read nor written,
+ * nor are their rows and n_runs -- the rule of the generate calls' outputs, so the call chains behind one. masks, counts, runs and n_runs are DEVICE pointers;
+ * stream, dev and the workspace (one bit per pixel and mask in flight, allocated per CALL, freed behind a synchronisation: the call returns with the work done)
+ * as for visp_image_remove_small_regions_device. Every argument check happens before anything touches a device. */
+VISP_API int32_t visp_image_rle_encode_device(void const* masks_u8_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, void* runs_u32_dev, int64_t run_stride,
+                                              void* n_runs_i32_dev, void* stream, visp_device const* dev);
+/* the same on host masks: up, a count-only pass, the encode into rows of exactly those counts, the runs down in one copy (nothing but runs crosses). Mask b's runs are runs[offsets[b] .. offsets[b + 1]),
+ * offsets i64 [n + 1]. The size of the output is known only behind the call, so, like the images of this file, it comes in a library-owned buffer: *runs_u32
+ * points into *out_data, which visp_rle_destroy releases. Blocks. */
+VISP_API void visp_rle_destroy(visp_rle_data* rle);
+VISP_API int32_t visp_image_rle_encode_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32,
+                                            visp_rle_data** out_data, visp_device const* dev);
 /* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
  * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
 VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,

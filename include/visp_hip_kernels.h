@@ -418,6 +418,22 @@ VX_API int vx_sam_clean_nms_inputs(const int32_t* info_i32, const int32_t* chang
 VX_API int vx_sam_gather_clean_masks(const uint8_t* masks, int w, int h, const int32_t* info_i32, const float* info_f32, const int32_t* changed, const int32_t* keep_idx,
                                      const int32_t* first_counts, const int32_t* second_counts, int N, uint8_t* out_masks, int32_t* out_info_i32, float* out_info_f32,
                                      int32_t* out_counts, void* stream);
+/* ---- run-length encoding of u8 masks: COCO's uncompressed RLE as SAM's mask_to_rle_pytorch writes it (kernels_rle.hip) ----
+ * masks u8 [n][h][w], any w, h >= 1 with w * h below 2^31 - 1 (so that the largest count, w h + 1, is an i32), no alignment (16-byte aligned masks with w a multiple of 16 take 16-byte loads). A pixel is foreground
+ * iff its byte is non-zero. Pixels are visited in column-major order p = x * h + y; a run continues across the end of a column. Mask b's runs alternate from
+ * background: runs[b * run_stride + 0] is the number of leading background pixels (0 when pixel 0 is foreground) and the runs sum to w * h; an empty mask is
+ * {w h}, a full one {0, w h}. n_runs i32 [n]: the TRUE number of runs of each mask (1 .. w h + 1), also above run_stride; only the first
+ * min(n_runs[b], run_stride) entries of row b are written. runs NULL or run_stride 0: the count-only form. counts (nullable): a device i32; masks at and behind
+ * counts[0] are neither read nor written, nor are their n_runs and rows. The masks pass `group` at a time through the workspace, one bit per pixel:
+ * vx_mask_rle_workspace_bytes(w, h, group) bytes (0 for arguments the launcher refuses), 16-byte aligned. Two launches per group; integers only, no atomics:
+ * the same bytes on every run. */
+VX_API size_t vx_mask_rle_workspace_bytes(int w, int h, int group);
+VX_API int vx_mask_rle_u8(const uint8_t* masks, int w, int h, int n, const int32_t* counts, uint32_t* runs, int64_t run_stride, int32_t* n_runs, void* workspace,
+                          size_t workspace_bytes, int group, void* stream);
+/* the same with rows of their own lengths: mask b's runs go to runs + offsets[b], at most offsets[b + 1] - offsets[b] of them; offsets a device i64 [n + 1]
+ * (from the n_runs of a count-only call, the packed rows are CSR and hold nothing but runs). n_runs as above. */
+VX_API int vx_mask_rle_packed_u8(const uint8_t* masks, int w, int h, int n, const int64_t* offsets, uint32_t* runs, int32_t* n_runs, void* workspace,
+                                 size_t workspace_bytes, int group, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -12,10 +12,10 @@ import ctypes
 import keyword
 import re
 from collections import namedtuple
-from ctypes import POINTER, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_void_p
+from ctypes import POINTER, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_void_p
 
 SCALARS = {"char": c_char, "int": c_int, "float": c_float, "double": c_double, "size_t": c_size_t,
-           "int32_t": c_int32, "int64_t": c_int64, "uint8_t": c_uint8}
+           "int32_t": c_int32, "int64_t": c_int64, "uint8_t": c_uint8, "uint32_t": c_uint32}
 
 # A declared object (field, parameter, return type) is the tuple (text, base, stars, name, array) that _OBJECTS finds: its text,
 # the base type, the run of `*` and `const` behind it, the name ("" for a return type) and "[n]" / "[]" / "".

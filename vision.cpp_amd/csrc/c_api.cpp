@@ -22,6 +22,7 @@
 #include "swin.h"
 #include "birefnet.h"
 #include "matting.h"
+#include "mask_rle.h"
 #include "graph.h"
 #include "visp_util.h"
 
@@ -29,6 +30,7 @@ using namespace visp;
 
 struct visp_image_data : image_data {};
 struct visp_device : backend_device {};
+struct visp_rle_data { std::vector<uint32_t> runs; };
 struct visp_graph : graph {};
 struct visp_weights { std::shared_ptr<weight_store> store; };
 struct visp_file { model_file file; };
@@ -136,6 +138,12 @@ void return_image(image_data&& img, visp_image_view* out_image, visp_image_data*
     out_image->stride = owned->extent[0] * n_bytes(owned->format);
     out_image->format = int32_t(owned->format);
     out_image->data = owned->data.get();
+}
+
+void return_rle(std::vector<uint32_t>&& runs, uint32_t const** out_runs, visp_rle_data** out_data) {
+    auto* owned = new visp_rle_data{std::move(runs)};
+    *out_data = owned;
+    *out_runs = owned->runs.data();
 }
 
 // a caller's view as visp::image_view: present, with data, a format of the enum, a positive extent and rows no shorter than their pixels
@@ -849,6 +857,17 @@ int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const* prompts
     });
 }
 
+int32_t visp_sam_generate_masks_rle_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                         float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, int32_t* info_i32, float* info_f32,
+                                         int32_t* counts, int64_t* offsets_i64, uint32_t const** runs_u32, visp_rle_data** out_data) {
+    return handle_errors([&]() {
+        if (!info_i32 || !info_f32 || !counts || !offsets_i64 || !runs_u32 || !out_data) throw except("visp_sam_generate_masks_rle_host: null argument");
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area};
+        sam_generate_check(prompts, n_args, n, p);
+        return_rle(sam_generate_masks_rle_host(as_sam(m), prompts, n_args, n, p, info_i32, info_f32, counts, offsets_i64), runs_u32, out_data);
+    });
+}
+
 // the last generate call's ms of the stages named, in that order (0 for a stage the call did not run)
 static void sam_stage_ms(visp_model const* m, float* out_ms, std::initializer_list<sam_generate_stage> stages) {
     if (!out_ms) throw except("sam: null argument");
@@ -990,6 +1009,26 @@ int32_t visp_image_remove_small_regions_host(uint8_t* masks_u8, int32_t n, int32
         if (!masks_u8) throw except("visp_image_remove_small_regions_host: null argument");
         check_remove_small_regions(n, w, h, min_area, mode);
         remove_small_regions_host(dev, masks_u8, n, w, h, min_area, mode, changed_i32);
+    });
+}
+
+void visp_rle_destroy(visp_rle_data* rle) { delete rle; }
+
+int32_t visp_image_rle_encode_device(void const* masks_u8_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, void* runs_u32_dev, int64_t run_stride,
+                                     void* n_runs_i32_dev, void* stream, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!masks_u8_dev || !n_runs_i32_dev) throw except("visp_image_rle_encode_device: null argument");
+        check_rle_encode(n, w, h, run_stride);
+        rle_encode_device(dev, masks_u8_dev, n, w, h, counts_dev, runs_u32_dev, run_stride, n_runs_i32_dev, stream);
+    });
+}
+
+int32_t visp_image_rle_encode_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32, visp_rle_data** out_data,
+                                   visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!masks_u8 || !offsets_i64 || !runs_u32 || !out_data) throw except("visp_image_rle_encode_host: null argument");
+        check_rle_encode(n, w, h, 0);
+        return_rle(rle_encode_host(dev, masks_u8, n, w, h, offsets_i64), runs_u32, out_data);
     });
 }
 

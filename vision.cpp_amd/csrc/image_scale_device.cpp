@@ -3,7 +3,6 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
-#include <optional>
 
 #include "image_scale_tables.h"
 #include "visp_util.h"
@@ -14,18 +13,6 @@ namespace {
 
 using visp_scale::MAX_TAPS;
 using visp_scale::TH;
-
-// the device a call runs on: the given one (its turn held, its stream), or whatever is current for the thread (default stream)
-struct device_scope {
-    std::optional<device_turn> turn;
-    void* stream = nullptr;
-    explicit device_scope(backend_device const* dev) {
-        if (dev) {
-            turn.emplace(*dev);
-            stream = dev->stream;
-        }
-    }
-};
 
 uint32_t bits(float f) {
     uint32_t u;

@@ -1,25 +1,12 @@
 #include "matting.h"
 
 #include <algorithm>
-#include <optional>
 
 #include "visp_util.h"
 
 namespace visp {
 
 namespace {
-
-// the device a host-view op runs on: the given one (its turn held, its stream), or whatever is current for the thread (default stream)
-struct device_scope {
-    std::optional<device_turn> turn;
-    void* stream = nullptr;
-    explicit device_scope(backend_device const* dev) {
-        if (dev) {
-            turn.emplace(*dev);
-            stream = dev->stream;
-        }
-    }
-};
 
 void require_view(char const* who, image_view const& v) {
     if (!v.data) throw except("%s: null image data", who);

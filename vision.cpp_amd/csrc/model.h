@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -35,6 +36,17 @@ struct device_turn {
     explicit device_turn(backend_device const& dev);
 };
 backend_device* backend_init(int device_index); // throws visp::exception if no gfx950 device
+// the device a host-view op runs on: the given one (its turn held, its stream), or whatever is current for the thread (default stream)
+struct device_scope {
+    std::optional<device_turn> turn;
+    void* stream = nullptr;
+    explicit device_scope(backend_device const* dev) {
+        if (dev) {
+            turn.emplace(*dev);
+            stream = dev->stream;
+        }
+    }
+};
 
 // One GEMM-shaped weight in a packed arena: f16 [N][K] (both padded for the kernel's tiles, pads are zero) + optional f32 bias [N]
 // (the model loaders that pack for hand schedules: tinyvit.cpp, swin.cpp, birefnet.cpp)

@@ -100,6 +100,8 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     // automatic mask generation (sam_generate_masks_device): the logit planes and iou predictions of every prompt of the call, the selection stage's tables
     // and the NMS workspace, next to the decoder's batch_ws
     device_buffer generate_ws;
+    // sam_generate_masks_rle_host (mask_rle.h): the masks and records of the call, staged on the device for the encoder behind it (capacity * h * w bytes)
+    device_buffer generate_rle_stage;
     // with timing enabled: the last generate call's ms per sam_generate_stage, by events
     float generate_split_ms[sam_stage_count] = {};
     ~sam_model() override;

@@ -400,20 +400,40 @@ class Model:
         r = int(counts[0])
         return masks[:r], ii[:r], fi[:r], (r, *(int(c) for c in counts[1:]))
 
+    def sam_generate_masks_rle_raw(self, prompts=None, points_per_side: int = 32, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
+                                   max_masks: int = 256, min_mask_region_area: int = 0):
+        """sam_generate_masks_raw with RLE dicts (mask_to_rle's) in place of the mask array (visp_sam_generate_masks_rle_host): the masks are encoded on the
+        device behind the generate call and no mask byte is read back. counts always has four entries; the last two are 0 without min_mask_region_area."""
+        p, k, params = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        n, cap = len(k), int(max_masks)
+        w, h = self.sam_image_extent() if n and cap > 0 else (0, 0)
+        ii, fi, counts = np.empty((max(cap, 0), 8), np.int32), np.empty((max(cap, 0), 2), np.float32), np.zeros(4, np.int32)
+        offsets, runs, owner = np.zeros(max(cap, 0) + 1, np.int64), c_void_p(), c_void_p()
+        check(self._api.visp_sam_generate_masks_rle_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, int(min_mask_region_area), ii.ctypes.data,
+                                                         fi.ctypes.data, counts.ctypes.data, offsets.ctypes.data, byref(runs), byref(owner)))
+        self._sam_batch_n = n
+        r = int(counts[0])
+        return _rle_records(offsets, runs, owner, r, w, h), ii[:r], fi[:r], (r, *(int(c) for c in counts[1:]))
+
     def sam_generate_masks(self, points_per_side: int = 32, prompts=None, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
-                           max_masks: int = 256, min_mask_region_area: int = 0):
+                           max_masks: int = 256, min_mask_region_area: int = 0, output_mode: str = "binary_mask"):
         """SAM's automatic mask generator on the last sam_encode (one crop layer, no crop-edge filter; min_mask_region_area as in SAM: holes and islands below
         that many pixels are removed and a second NMS runs, after which unchanged masks come first and changed ones behind them): the points_per_side^2 grid
         of sam_point_grid, or `prompts` (points and boxes as for sam_compute_batch). Thresholds default to SAM's (sam_generate_defaults). Returns at most
         max_masks records in order of predicted iou, each a dict with SAM's keys: segmentation (bool [h, w]), area, bbox [x, y, w, h] (of the mask, image
-        pixels), predicted_iou, stability_score, and point_coords [[x, y]] for a point prompt or box [x0, y0, x1, y1] for a box prompt."""
+        pixels), predicted_iou, stability_score, and point_coords [[x, y]] for a point prompt or box [x0, y0, x1, y1] for a box prompt.
+        output_mode "uncompressed_rle": segmentation is SAM's RLE dict {"size": [h, w], "counts": [...]}, encoded on the device (no mask byte is read back);
+        every other key is as with "binary_mask"."""
+        if output_mode not in ("binary_mask", "uncompressed_rle"):
+            raise ValueError(f"unknown output_mode {output_mode!r}: one of 'binary_mask', 'uncompressed_rle'")
         p, k, _ = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
-        masks, ii, fi, _ = self.sam_generate_masks_raw([list(q[:c]) for q, c in zip(p, k)], points_per_side, pred_iou_thresh, stability_thresh, stability_offset,
-                                                       nms_iou_thresh, max_masks, min_mask_region_area)
+        raw = self.sam_generate_masks_raw if output_mode == "binary_mask" else self.sam_generate_masks_rle_raw
+        masks, ii, fi, _ = raw([list(q[:c]) for q, c in zip(p, k)], points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, max_masks,
+                               min_mask_region_area)
         out = []
         for m, row, (piou, stab) in zip(masks, ii, fi):
             prompt = int(row[0])
-            rec = dict(segmentation=m == 255, area=int(row[6]), bbox=[int(v) for v in row[2:6]], predicted_iou=float(piou), stability_score=float(stab))
+            rec = dict(segmentation=m == 255 if output_mode == "binary_mask" else m, area=int(row[6]), bbox=[int(v) for v in row[2:6]], predicted_iou=float(piou), stability_score=float(stab))
             if k[prompt] == 2:
                 rec["point_coords"] = [[int(p[prompt, 0]), int(p[prompt, 1])]]
             else:
@@ -628,6 +648,51 @@ def remove_small_regions_device(masks_dev: int, n: int, w: int, h: int, min_area
     if mode not in REGION_MODES:
         raise ValueError(f"unknown mode {mode!r}: one of {sorted(REGION_MODES)}")
     check(lib.get_lib().visp_image_remove_small_regions_device(masks_dev, int(n), int(w), int(h), int(min_area), REGION_MODES[mode], changed_dev, stream, *_on(device)))
+
+
+def _rle_records(offsets, runs_ptr, owner, count: int, w: int, h: int) -> list:
+    """the library-owned runs of an RLE host call as SAM's dicts, one per mask; releases the buffer"""
+    try:
+        total = int(offsets[count])
+        runs = np.ctypeslib.as_array(ctypes.cast(runs_ptr, ctypes.POINTER(ctypes.c_uint32)), (total,)).copy() if total else np.empty(0, np.uint32)
+    finally:
+        lib.get_lib().visp_rle_destroy(owner)
+    return [{"size": [int(h), int(w)], "counts": runs[int(offsets[b]):int(offsets[b + 1])].tolist()} for b in range(count)]
+
+
+def mask_to_rle(masks: np.ndarray, device: Device | None = None):
+    """COCO's uncompressed RLE on the device, SAM's mask_to_rle_pytorch: masks [n, h, w] or [h, w] (non-zero = foreground) -> a list of
+    {"size": [h, w], "counts": [...]} (one dict for a single mask). Pixels are visited column by column; counts alternate from background, the first is 0 when
+    the top-left pixel is foreground."""
+    a = np.asarray(masks)
+    m = np.ascontiguousarray(a if a.dtype == np.uint8 else a != 0, dtype=np.uint8)
+    if m.ndim not in (2, 3):
+        raise ValueError(f"expected masks [n, h, w] or [h, w], got shape {m.shape}")
+    n, (h, w) = (1 if m.ndim == 2 else m.shape[0]), m.shape[-2:]
+    offsets, runs, owner = np.zeros(max(n, 0) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_encode_host(m.ctypes.data, n, w, h, offsets.ctypes.data, byref(runs), byref(owner), *_on(device)))
+    out = _rle_records(offsets, runs, owner, n, w, h)
+    return out[0] if m.ndim == 2 else out
+
+
+def mask_to_rle_device(masks_dev: int, n: int, w: int, h: int, runs_dev: int | None, run_stride: int, n_runs_dev: int, counts_dev: int | None = None,
+                       device: Device | None = None, stream: int | None = None):
+    """The same on device-resident masks u8 [n, h, w] (addresses): n_runs i32 [n] receives each mask's true number of runs, runs u32 [n, run_stride] the first
+    min(n_runs, run_stride) of them (runs_dev None or run_stride 0: the counts alone). counts_dev: a device i32, masks at and behind counts[0] are skipped.
+    Returns with the work done."""
+    check(lib.get_lib().visp_image_rle_encode_device(masks_dev, int(n), int(w), int(h), counts_dev, runs_dev, int(run_stride), n_runs_dev, stream, *_on(device)))
+
+
+def rle_to_mask(rle: dict) -> np.ndarray:
+    """SAM's rle_to_mask on the host: {"size": [h, w], "counts": [...]} -> bool [h, w]."""
+    h, w = rle["size"]
+    flat = np.zeros(h * w, bool)
+    pos, value = 0, False
+    for c in rle["counts"]:
+        flat[pos:pos + c] = value
+        pos += c
+        value = not value
+    return flat.reshape(w, h).T
 
 
 def image_estimate_foreground(image: np.ndarray, mask: np.ndarray, radius: int = 30, device: Device | None = None) -> np.ndarray:
