@@ -24,6 +24,7 @@
 #include <cstring>
 #include <exception>
 #include <memory>
+#include <optional>
 #include <span>
 #include <string>
 #include <utility>
@@ -577,6 +578,75 @@ inline std::vector<image_data> sam_compute_batch(sam_model& model, span<box_2d c
     std::vector<int32_t> p;
     for (box_2d const& b : boxes) p.insert(p.end(), {b.top_left[0], b.top_left[1], b.bottom_right[0], b.bottom_right[1]});
     return detail::sam_prompts(model, p, 4);
+}
+
+// not in the reference's header: SAM's SamPredictor.predict on one sam_encode. A prompt is any number of labelled points (1 positive, 0 negative, -1 not a point),
+// an optional box and an optional mask input: the low_res_logits of an earlier result (alpha_f32, sam_mask_input_size on both sides; the file needs the
+// prompt_encoder.mask_downscaling tensors). plane -1 picks the best of the first three masks by predicted iou, as sam_compute; 0 .. 3 that mask (SAM's
+// single-mask output is 0). All prompts of one call have the same number of points, and all or none a box, and all or none a mask input.
+struct sam_prompt {
+    std::vector<i32x2> points;
+    std::vector<int32_t> labels; // empty: every point positive
+    std::optional<box_2d> box;
+    std::optional<image_view> mask_input;
+};
+struct sam_prediction {
+    image_data mask;           // alpha_u8 at the encoded image's extent
+    float iou[4];              // predicted iou of the four masks
+    int chosen;                // the mask returned
+    image_data low_res_logits; // alpha_f32, the chosen mask's logits: the next call's mask_input
+};
+inline int sam_mask_input_size(sam_model& model) {
+    int32_t s = 0;
+    detail::check(visp_sam_mask_input_size(model.handle, &s));
+    return s;
+}
+inline std::vector<sam_prediction> sam_predict(sam_model& model, span<sam_prompt const> prompts, int plane = -1) {
+    const int32_t n = int32_t(prompts.size());
+    if (n == 0) return {};
+    const size_t k = prompts[0].points.size();
+    const bool box = prompts[0].box.has_value(), mask = prompts[0].mask_input.has_value();
+    int32_t w = 0, h = 0, S = 256;
+    detail::check(visp_sam_image_extent(model.handle, &w, &h));
+    if (mask) S = prompts[0].mask_input->extent[0];
+    std::vector<int32_t> points, labels, boxes;
+    std::vector<float> mask_in;
+    for (sam_prompt const& p : prompts) {
+        if (p.points.size() != k || p.box.has_value() != box || p.mask_input.has_value() != mask || (!p.labels.empty() && p.labels.size() != k))
+            throw exception("sam_predict: the prompts of one call must have one shape (points, box, mask input)");
+        for (size_t i = 0; i < k; ++i) {
+            points.insert(points.end(), {p.points[i][0], p.points[i][1]});
+            labels.push_back(p.labels.empty() ? 1 : p.labels[i]);
+        }
+        if (box) boxes.insert(boxes.end(), {p.box->top_left[0], p.box->top_left[1], p.box->bottom_right[0], p.box->bottom_right[1]});
+        if (mask) {
+            image_view const& v = *p.mask_input;
+            if (v.format != image_format::alpha_f32 || v.extent[0] != S || v.extent[1] != S) throw exception("sam_predict: a mask input is a square alpha_f32 image");
+            for (int y = 0; y < S; ++y) {
+                float const* row = reinterpret_cast<float const*>(static_cast<uint8_t const*>(v.data) + size_t(y) * size_t(v.stride));
+                mask_in.insert(mask_in.end(), row, row + S);
+            }
+        }
+    }
+    int32_t side = sam_mask_input_size(model);
+    if (side == 0) side = 256; // a file without mask_downscaling still returns its low-resolution logits
+    std::vector<uint8_t> masks(size_t(n) * size_t(w) * size_t(h));
+    std::vector<float> iou(size_t(n) * 4), low(size_t(n) * size_t(side) * size_t(side));
+    std::vector<int32_t> chosen(size_t(n), 0);
+    detail::check(visp_sam_predict_host(model.handle, k ? points.data() : nullptr, k ? labels.data() : nullptr, int32_t(k), box ? boxes.data() : nullptr,
+                                        mask ? mask_in.data() : nullptr, mask ? S : 0, n, plane, masks.data(), iou.data(), chosen.data(), low.data()));
+    std::vector<sam_prediction> out;
+    for (int32_t i = 0; i < n; ++i) {
+        sam_prediction r{image_alloc({w, h}, image_format::alpha_u8), {}, chosen[size_t(i)], image_alloc({side, side}, image_format::alpha_f32)};
+        std::memcpy(r.mask.data.get(), masks.data() + size_t(i) * size_t(w) * size_t(h), size_t(w) * size_t(h));
+        std::memcpy(r.iou, iou.data() + size_t(i) * 4, sizeof r.iou);
+        std::memcpy(r.low_res_logits.data.get(), low.data() + size_t(i) * size_t(side) * size_t(side), size_t(side) * size_t(side) * sizeof(float));
+        out.push_back(std::move(r));
+    }
+    return out;
+}
+inline sam_prediction sam_predict(sam_model& model, sam_prompt const& prompt, int plane = -1) {
+    return std::move(sam_predict(model, span<sam_prompt const>(&prompt, 1), plane)[0]);
 }
 
 // not in the reference's header: automatic mask generation, SAM's automatic mask generator on one sam_encode (one crop layer, no crop-edge filter).

@@ -306,6 +306,22 @@ VISP_API int32_t visp_sam_compute_batch_device(visp_model* m, int32_t const* pro
 /* the same with host outputs (masks u8 [n][h][w], iou f32 [n][4], chosen i32 [n]; iou and chosen may be NULL); blocks */
 VISP_API int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, uint8_t* masks_u8, float* iou,
                                              int32_t* chosen);
+/* SAM's SamPredictor.predict on the embedding of the last visp_sam_encode: labelled points, a box with points, and the mask-input prompt. n prompts of ONE shape:
+ * points host i32 [n][k][2] in pixels of the encoded image with labels host i32 [n][k] (1 positive, 0 negative, -1 not a point; k >= 0, NULL with k = 0), boxes host
+ * i32 [n][4] or NULL (k >= 1 without boxes), mask_input f32 [n][S][S] or NULL: the low_res output of an earlier call, S = visp_sam_mask_input_size. plane -1: the
+ * best of the first three masks by predicted iou, as visp_sam_compute_batch_*; 0 .. 3: that mask (SAM's single-mask output is 0). Outputs as
+ * visp_sam_compute_batch_device (iou, chosen nullable), and low_res (nullable) f32 [n][S][S], the chosen mask's logits. mask_input and the outputs are DEVICE pointers
+ * here, host pointers in the _host entry. One positive point, or a box alone, without mask input and with plane -1 gives the bytes of visp_sam_compute_batch_*; chunks,
+ * streams and captures as there. A mask input needs a file with the prompt_encoder.mask_downscaling.* tensors. */
+VISP_API int32_t visp_sam_predict_device(visp_model* m, int32_t const* points, int32_t const* labels, int32_t k, int32_t const* boxes, float const* mask_input,
+                                         int32_t mask_side, int32_t n, int32_t plane, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* low_res_dev,
+                                         void* stream);
+VISP_API int32_t visp_sam_predict_host(visp_model* m, int32_t const* points, int32_t const* labels, int32_t k, int32_t const* boxes, float const* mask_input,
+                                       int32_t mask_side, int32_t n, int32_t plane, uint8_t* masks_u8, float* iou, int32_t* chosen, float* low_res);
+/* side S of a mask input: 4 x the embedding's side (256), or 0 when the model file holds no prompt_encoder.mask_downscaling.* tensors */
+VISP_API int32_t visp_sam_mask_input_size(visp_model* m, int32_t* size);
+/* token rows the decoder runs per prompt of that shape: 5 + k + (2 with a box, else 1). Needs no model. */
+VISP_API int32_t visp_sam_prompt_token_count(int32_t k, int32_t has_box, int32_t* n_tokens);
 /* extent in pixels of the image given to the last visp_sam_encode: what sizes the masks of the calls above */
 VISP_API int32_t visp_sam_image_extent(visp_model* m, int32_t* width, int32_t* height);
 /* prompts per internal chunk of the batch calls: 1 .. 256, default 64. It sizes the workspace: about 27 MB per prompt in flight. */

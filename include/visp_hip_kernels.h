@@ -365,6 +365,23 @@ VX_API int vx_sam_process_masks(const void* planes, int64_t prompt_stride, int64
                                 float* scaled, int image_size, int sw, int sh, uint8_t* out, int dw, int dh, int P, void* stream);
 /* dst f16 [B][n] = B copies of src f16 [n]; n a multiple of 8, both 16-byte aligned */
 VX_API int vx_sam_tile_rows_f16(const void* src, int64_t n, void* dst, int B, void* stream);
+/* ---- MobileSAM mask-input prompt (kernels_samdense.hip) ----
+ * SAM's PromptEncoder._embed_masks added to the image embedding, one launch: mask f32 [n][4 res][4 res] (prompt b at mask + b * mask_prompt_stride, rows
+ * mask_row_stride elements apart; both multiples of 4, mask 16-byte aligned) -> conv 2x2 s2 (1 -> c1; w1 [c1][1][2][2], b1), LayerNorm2d (ln1_w, ln1_b), erf GELU,
+ * conv 2x2 s2 (c1 -> c2; w2 [c2][c1][2][2], b2), LayerNorm2d (ln2_w, ln2_b), erf GELU, conv 1x1 (c2 -> dim; w3 f16 [dim][c2], b3 f32 [dim]); all but w3 f32.
+ * K f16 [n][res^2][dim] = that + embed [res^2][dim] (f16, or f32 with embed_is_f32); with pe (f16 [res^2][dim]) also k1 = K + pe, from K as stored (pe and k1 are
+ * both given or both NULL). Stages 1 and 2 run in f32; the c2 activations are rounded to f16 for the last product (f32 sums). c1 = 4 and c2 = 16 only; dim any
+ * multiple of 16; n res^2 need not be a multiple of the 16-row tile. */
+VX_API int vx_sam_dense_prompt_f16(const float* mask, int64_t mask_prompt_stride, int mask_row_stride, const float* w1, const float* b1, const float* ln1_w,
+                                   const float* ln1_b, int c1, const float* w2, const float* b2, const float* ln2_w, const float* ln2_b, int c2, const void* w3,
+                                   const float* b3, const void* embed, int embed_is_f32, const void* pe, void* K, void* k1, int n, int res, int dim, float eps,
+                                   void* stream);
+/* out f32 [P][n_px] = plane chosen[p] (clamped to 0 .. n_planes - 1) of prompt p's f16 logits, planes[p * prompt_stride + c * plane_stride + i]: the low-resolution
+ * logits a caller feeds back as the next mask input */
+VX_API int vx_sam_gather_plane_f32(const void* planes, int64_t prompt_stride, int64_t plane_stride, int64_t n_px, int n_planes, const int32_t* chosen, float* out,
+                                   int P, void* stream);
+/* chosen i32 [P] = plane (>= 0): a caller's fixed plane in place of vx_sam_iou_head_f32's choice */
+VX_API int vx_sam_fix_plane_i32(int32_t* chosen, int plane, int P, void* stream);
 /* ---- MobileSAM automatic mask generation: the selection stage behind a batched decode (kernels_samselect.hip) ----
  * Candidate c = prompt * n_planes + plane, the first n_planes f16 logit planes of each prompt: plane at planes + prompt * prompt_stride + plane * plane_stride
  * elements, mask_size^2 logits row by row. Over the region x < cw, y < ch: table i32 [c][6] = {logits > +offset, logits > -offset, then the inclusive box

@@ -817,6 +817,46 @@ int32_t visp_sam_compute_batch_host(visp_model* m, int32_t const* prompts, int32
     return handle_errors([&]() { sam_compute_batch_host(as_sam(m), prompts, n_args, n, masks_u8, iou, chosen); });
 }
 
+static sam_predict_args predict_args(int32_t const* points, int32_t const* labels, int32_t k, int32_t const* boxes, float const* mask_input, int32_t mask_side, int32_t n,
+                                     int32_t plane) {
+    sam_predict_check(points, labels, k, boxes, n, plane); // before the handle: needs no model
+    sam_predict_args a;
+    a.points = points; a.labels = labels; a.k = k; a.boxes = boxes; a.mask_input = mask_input; a.mask_side = mask_side; a.n = n; a.plane = plane;
+    return a;
+}
+
+int32_t visp_sam_predict_device(visp_model* m, int32_t const* points, int32_t const* labels, int32_t k, int32_t const* boxes, float const* mask_input, int32_t mask_side,
+                                int32_t n, int32_t plane, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* low_res_dev, void* stream) {
+    return handle_errors([&]() {
+        const sam_predict_args a = predict_args(points, labels, k, boxes, mask_input, mask_side, n, plane);
+        sam_predict_device(as_sam(m), a, masks_u8_dev, iou_dev, chosen_dev, static_cast<float*>(low_res_dev), stream);
+    });
+}
+
+int32_t visp_sam_predict_host(visp_model* m, int32_t const* points, int32_t const* labels, int32_t k, int32_t const* boxes, float const* mask_input, int32_t mask_side,
+                              int32_t n, int32_t plane, uint8_t* masks_u8, float* iou, int32_t* chosen, float* low_res) {
+    return handle_errors([&]() {
+        const sam_predict_args a = predict_args(points, labels, k, boxes, mask_input, mask_side, n, plane);
+        sam_predict_host(as_sam(m), a, masks_u8, iou, chosen, low_res);
+    });
+}
+
+int32_t visp_sam_mask_input_size(visp_model* m, int32_t* size) {
+    return handle_errors([&]() {
+        if (!size) throw except("sam: null argument");
+        *size = sam_mask_input_size(as_sam(m));
+    });
+}
+
+int32_t visp_sam_prompt_token_count(int32_t k, int32_t has_box, int32_t* n_tokens) {
+    return handle_errors([&]() {
+        if (!n_tokens) throw except("sam: null argument");
+        if (k < 0 || k > 64) throw except("sam: %d points per prompt (0 .. 64)", k);
+        if (k < 1 && !has_box) throw except("sam: a prompt needs a point or a box (k = %d, no box)", k);
+        *n_tokens = sam_prompt_token_count(k, has_box != 0);
+    });
+}
+
 int32_t visp_sam_generate_masks_device(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
                                        float stability_offset, float nms_iou_thresh, int32_t capacity, void* masks_u8_dev, void* info_i32_dev, void* info_f32_dev,
                                        void* counts_dev, void* stream) {

@@ -20,34 +20,58 @@ float sam_transform_coord(int p, float scale, int image_size) { // mobile-sam.cp
     return 2.f * center_normalized - 1.f;
 }
 
-constexpr int kSamTokens = 7; // [iou | 4 mask tokens | 2 prompt points]
+constexpr int kSamTokens = 7; // of a point or a box alone: [iou | 4 mask tokens | point, padding] or [.. | two corners]
 
-// prompt encoder on the host (two points of 256 sin/cos values; mobile-sam.cpp:219-286): the decoder's token rows of one prompt, f16 [7][dim]
-void sam_prompt_tokens(sam_model const& m, int const* prompt, int n_prompt, uint16_t* out) {
+} // namespace
+
+int sam_prompt_token_count(int k, bool box) { return 5 + k + (box ? 2 : 1); }
+
+void sam_predict_check(int32_t const* points, int32_t const* labels, int k, int32_t const* boxes, int n, int plane) {
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
+    if (k < 0 || k > 64) throw except("sam: %d points per prompt (0 .. 64)", k);
+    if (k < 1 && !boxes) throw except("sam: a prompt needs a point or a box (k = %d, no box)", k);
+    if (k > 0 && (!points || !labels)) throw except("sam: null argument (points or labels)");
+    if (plane < -1 || plane > 3) throw except("sam: plane %d is outside -1 .. 3 (-1: the best of the first three by predicted iou)", plane);
+    for (int64_t i = 0; i < (int64_t)n * k; ++i)
+        if (labels[i] < -1 || labels[i] > 1) throw except("sam: label %d of point %d of prompt %d (1 positive, 0 negative, -1 not a point)", labels[i], (int)(i % k), (int)(i / k));
+}
+
+// SAM's PromptEncoder.forward on the host for one prompt (a few points of 256 sin/cos values; mobile-sam.cpp:219-286 for a point or a box alone): the decoder's
+// token rows, f16 [sam_prompt_token_count(k, box)][dim] = [iou | 4 mask tokens | k points | one padding not-a-point without a box, else the box's two corners]
+void sam_prompt_tokens(sam_model const& m, int32_t const* points, int32_t const* labels, int k, int32_t const* box, uint16_t* out) {
     samdec_weights const& D = m.dec;
     const int dim = D.dim, F = dim / 2, image_size = m.params.img_size;
-    const bool is_box = n_prompt == 4;
     const float scale = float(image_size) / float(std::max(m.image_extent[0], m.image_extent[1]));
-    float coords[4] = {sam_transform_coord(prompt[0], scale, image_size), sam_transform_coord(prompt[1], scale, image_size), 0.f, 0.f};
-    if (is_box) { coords[2] = sam_transform_coord(prompt[2], scale, image_size); coords[3] = sam_transform_coord(prompt[3], scale, image_size); }
     std::vector<float> tokens(D.output_tokens); // [iou | 4 mask tokens]
-    tokens.resize((size_t)kSamTokens * dim);
-    for (int i = 0; i < 2; ++i) {
-        float* t = tokens.data() + (size_t)(5 + i) * dim;
+    tokens.resize((size_t)sam_prompt_token_count(k, box != nullptr) * dim);
+    float* t = tokens.data() + (size_t)5 * dim;
+    auto encode = [&](int32_t const* xy, std::vector<float> const& label_embed) { // positional encoding of a pixel + its label's embedding
+        const float cx = sam_transform_coord(xy[0], scale, image_size), cy = sam_transform_coord(xy[1], scale, image_size);
         for (int f = 0; f < F; ++f) {
-            float v = coords[2 * i] * D.gaussian[f] + coords[2 * i + 1] * D.gaussian[F + f];
+            float v = cx * D.gaussian[f] + cy * D.gaussian[F + f];
             v *= 2.f * 3.14159265358979323846f;
             t[f] = std::sin(v);
             t[F + f] = std::cos(v);
         }
-        if (is_box) for (int c = 0; c < dim; ++c) t[c] += D.point_embed[2 + i][c];
-        else if (i == 0) for (int c = 0; c < dim; ++c) t[c] += D.point_embed[1][c];
-        else for (int c = 0; c < dim; ++c) t[c] = D.not_a_point[c];
+        for (int c = 0; c < dim; ++c) t[c] += label_embed[c];
+        t += dim;
+    };
+    auto not_a_point = [&]() { // SAM zeroes the encoding of a label -1 and adds not_a_point_embed
+        for (int c = 0; c < dim; ++c) t[c] = D.not_a_point[c];
+        t += dim;
+    };
+    for (int i = 0; i < k; ++i) {
+        if (labels[i] < 0) not_a_point();
+        else encode(points + 2 * i, D.point_embed[labels[i]]);
+    }
+    if (box) {
+        encode(box, D.point_embed[2]);
+        encode(box + 2, D.point_embed[3]);
+    } else {
+        not_a_point();
     }
     for (size_t i = 0; i < tokens.size(); ++i) out[i] = f32_to_f16(tokens[i]);
 }
-
-} // namespace
 
 void sam_require_decoder(sam_model const& m) {
     samdec_weights const& D = m.dec;
@@ -58,15 +82,32 @@ void sam_require_decoder(sam_model const& m) {
 
 sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* logits_all, void* iou_dev, void* chosen_dev, void* stream,
                                   sam_kept_logits& kept, sam_chunk_hook const& after_chunk) {
-    samdec_weights const& D = m.dec;
     if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
     for (int i = 0; i < n; ++i)
         if (n_args[i] != 2 && n_args[i] != 4) throw except("sam: bad number of arguments (%d) for prompt %d, must be 2 or 4", n_args[i], i);
+    sam_prompt_set ps;
+    ps.n = n;
+    ps.n_tokens = kSamTokens;
+    ps.tokens = [&](int i, uint16_t* out) { // a point is one positive point and the padding, a box its two corners: seven rows either way
+        const int32_t* p = prompts + (size_t)i * 4, positive = 1;
+        if (n_args[i] == 4) sam_prompt_tokens(m, nullptr, nullptr, 0, p, out);
+        else sam_prompt_tokens(m, p, &positive, 1, nullptr, out);
+    };
+    return sam_decode_prompts(m, ps, logits_all, iou_dev, chosen_dev, stream, kept, after_chunk);
+}
+
+sam_decode_ctx sam_decode_prompts(sam_model& m, sam_prompt_set const& ps, void* logits_all, void* iou_dev, void* chosen_dev, void* stream, sam_kept_logits& kept,
+                                  sam_chunk_hook const& after_chunk) {
+    samdec_weights const& D = m.dec;
+    const int n = ps.n;
+    if (n < 1) throw except("sam: empty batch of prompts (n = %d)", n);
     sam_require_decoder(m);
+    const float* mask_in = ps.mask_input;
+    if (mask_in && !D.mask_input) throw except("sam: this model file holds no mask-input prompt (prompt_encoder.mask_downscaling.* tensors)");
     if (!m.iou_head_dev.ptr) throw except("sam: weights have not been uploaded (load_no_upload without weights_ready)");
     device_turn turn(*m.backend);
     void* s = stream ? stream : m.backend->stream;
-    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = kSamTokens;
+    const int dim = D.dim, H = D.heads, res = D.res, Nk = res * res, Nt = ps.n_tokens;
     const int image_size = m.params.img_size, mask_size = 4 * res;
     const int64_t n_px = (int64_t)mask_size * mask_size;
     const int Bmax = std::min(n, m.prompt_chunk);
@@ -94,7 +135,7 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
         m.prompt_tokens_bytes = tok_bytes;
     }
     uint16_t* tok_host = static_cast<uint16_t*>(m.prompt_tokens_host);
-    for (int i = 0; i < n; ++i) sam_prompt_tokens(m, prompts + (size_t)i * 4, n_args[i], tok_host + (size_t)i * Nt * dim);
+    for (int i = 0; i < n; ++i) ps.tokens(i, tok_host + (size_t)i * Nt * dim);
 
     // ---- workspace: what every prompt shares, then the buffers of one chunk of Bmax prompts (f16 unless said otherwise)
     const size_t R = (size_t)Bmax * Nt, big = (size_t)Bmax * Nk;
@@ -137,13 +178,15 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
     };
     const void* KPE = wa + D.dense_pe.off;
 
-    // ---- layer 0's image side is the same for every prompt (the dense prompt is no_mask_embed for all): once per call
+    // ---- without mask inputs layer 0's image side is the same for every prompt (the dense prompt is no_mask_embed for all): once per call
     // src = image_embeddings + dense prompt (mobile-sam.cpp:437-440), keys + key_pe, t2i's k_proj / v_proj and i2t's q_proj of them
-    VX(vx_add_rows_f16(m.embed.ptr, 1, wa + D.no_mask.off, dim, K0, (int64_t)Nk * dim, s));
-    add(K0, KPE, k10, (long)Nk * dim);
-    linear(L0.t2i.k, k10, Nk, pk0);
-    linear(L0.t2i.v, K0, Nk, pv0);
-    linear(L0.i2t.q, k10, Nk, pq0);
+    if (!mask_in) {
+        VX(vx_add_rows_f16(m.embed.ptr, 1, wa + D.no_mask.off, dim, K0, (int64_t)Nk * dim, s));
+        add(K0, KPE, k10, (long)Nk * dim);
+        linear(L0.t2i.k, k10, Nk, pk0);
+        linear(L0.t2i.v, K0, Nk, pv0);
+        linear(L0.i2t.q, k10, Nk, pq0);
+    }
 
     const i32x2 target = m.image_extent;
     const float up = float(image_size) / float(std::max(target[0], target[1]));
@@ -157,7 +200,14 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
         const long Rt = (long)B * Nt, Mi = (long)B * Nk;
         const void* T = static_cast<const uint8_t*>(tok_all) + (size_t)p0 * Nt * dim * 2;
         VX(vx_memcpy_d2d(Q, T, (size_t)Rt * dim * 2, s));
-        // token-side attention: B prompts x 7 queries; the image side is [B][Nk] rows, or the shared layer-0 operands with all 7 B queries in one batch
+        // with mask inputs the dense prompt differs per prompt: K = embedding + mask_downscaling(mask) and k1 = K + key_pe of this chunk in one launch, and
+        // layer 0 runs its image side on B Nk rows as the later layers do
+        if (mask_in) {
+            auto fv = [&](packed_vec const& v) { return reinterpret_cast<const float*>(wa + v.off); };
+            VX(vx_sam_dense_prompt_f16(mask_in + (size_t)p0 * n_px, n_px, mask_size, fv(D.md_w1), fv(D.md_b1), fv(D.md_ln1_w), fv(D.md_ln1_b), D.md_c1, fv(D.md_w2),
+                                       fv(D.md_b2), fv(D.md_ln2_w), fv(D.md_ln2_b), D.md_c2, wa + D.md_w3.off, fv(D.md_b3), m.embed.ptr, 1, KPE, K, k1, B, res, dim, 1e-6f, s));
+        }
+        // token-side attention: B prompts x Nt queries; the image side is [B][Nk] rows, or the shared layer-0 operands with all Nt B queries in one batch
         auto token_attention = [&](sam_attn_weights const& w, const void* q, const void* k_img, const void* v_img, bool shared, const void* res1) {
             linear(w.q, q, Rt, tq);
             if (shared) cross(tq, pk0, pv0, ta, 1, (int)Rt, Nk, hd_c); // queries are independent in a softmax
@@ -180,13 +230,13 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
             norm(L.norm_w[0], L.norm_b[0], t2, Q, Rt, dim);
             add(Q, T, t1, Rt * dim); // tokens attending to the image embedding
             if (li > 0) VX(vx_add_rows_f16(K, 0, KPE, (int64_t)Nk * dim, k1, (int64_t)Mi * dim, s));
-            token_attention(L.t2i, t1, k1, K, li == 0, Q);
+            token_attention(L.t2i, t1, k1, K, li == 0 && !mask_in, Q);
             norm(L.norm_w[1], L.norm_b[1], t2, Q, Rt, dim);
             linear(L.lin1, Q, Rt, hbuf, VX_EPI_F16_RELU); // mlp_block
             linear(L.lin2, hbuf, Rt, t2, VX_EPI_F16_ADD, Q);
             norm(L.norm_w[2], L.norm_b[2], t2, Q, Rt, dim);
             add(Q, T, t1, Rt * dim); // image embedding attending to the tokens (k1 = keys + key_pe from above)
-            if (li == 0) { // the shared rows laid out per prompt: from here on the keys differ
+            if (li == 0 && !mask_in) { // the shared rows laid out per prompt: from here on the keys differ
                 VX(vx_sam_tile_rows_f16(pq0, (int64_t)Nk * ci, pq, B, s));
                 VX(vx_sam_tile_rows_f16(K0, (int64_t)Nk * dim, K, B, s));
             } else {
@@ -240,6 +290,7 @@ sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t 
         auto ihp = [&](int i) { return reinterpret_cast<const float*>(ih + m.iou_head_off[i]); };
         VX(vx_sam_iou_head_f32(Q, (int64_t)Nt * dim, B, ihp(0), ihp(1), ihp(2), ihp(3), ihp(4), ihp(5), D.iou_head[0].k_real, D.iou_head[0].n_real, D.iou_head[1].n_real,
                                D.iou_head[2].n_real, iou_out, chosen_out, s));
+        if (ps.plane >= 0) VX(vx_sam_fix_plane_i32(chosen_out, ps.plane, B, s)); // a fixed plane in place of the best predicted iou (SAM's single-mask output: 0)
         after_chunk(ctx, p0, B, logits, iou_out, chosen_out);
         if (m.captures) { // test hook: the four logit planes (f16-rounded) and the iou predictions of every prompt
             std::vector<uint16_t> mh((size_t)B * 4 * n_px);
@@ -266,6 +317,31 @@ void sam_decode_masks(sam_model& m, int32_t const* prompts, int32_t const* n_arg
                                 static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, c.target[0], c.target[1], B, c.s));
     });
     if (!stream) VX(vx_stream_sync(ctx.s));
+}
+
+// the same on a prompt set, with the chosen plane's logits as f32 [n][mask_size^2] (low_res_dev nullable): what the next call takes as its mask input
+void sam_decode_predict(sam_model& m, sam_prompt_set const& ps, void* masks_u8_dev, void* iou_dev, void* chosen_dev, float* low_res_dev, void* stream) {
+    device_turn turn(*m.backend);
+    const size_t out_px = (size_t)m.image_extent[0] * m.image_extent[1];
+    sam_decode_ctx ctx = sam_decode_prompts(m, ps, nullptr, iou_dev, chosen_dev, stream, m.last_batch,
+                                            [&](sam_decode_ctx const& c, int p0, int B, void* logits, float*, int32_t* chosen) {
+        VX(vx_sam_process_masks(logits, 4 * c.n_px, c.n_px, 1, c.mask_size, 4, chosen, c.scaled, c.image_size, c.sw, c.sh,
+                                static_cast<uint8_t*>(masks_u8_dev) + (size_t)p0 * out_px, c.target[0], c.target[1], B, c.s));
+        if (low_res_dev) VX(vx_sam_gather_plane_f32(logits, 4 * c.n_px, c.n_px, c.n_px, 4, chosen, low_res_dev + (size_t)p0 * c.n_px, B, c.s));
+    });
+    if (!stream) VX(vx_stream_sync(ctx.s));
+}
+
+sam_prompt_set sam_predict_set(sam_model& m, sam_predict_args const& a, float const* mask_dev) {
+    sam_prompt_set ps;
+    ps.n = a.n;
+    ps.n_tokens = sam_prompt_token_count(a.k, a.boxes != nullptr);
+    ps.tokens = [&m, a](int i, uint16_t* out) {
+        sam_prompt_tokens(m, a.points + (size_t)i * a.k * 2, a.labels + (size_t)i * a.k, a.k, a.boxes ? a.boxes + (size_t)i * 4 : nullptr, out);
+    };
+    ps.mask_input = mask_dev;
+    ps.plane = a.plane;
+    return ps;
 }
 
 // The host entries (their callers have checked the decoder and n): masks, iou and chosen into `stage` on the device's stream, then what the caller asked for
@@ -307,6 +383,41 @@ void sam_compute_batch_host(sam_model& m, int32_t const* prompts, int32_t const*
     sam_require_decoder(m);
     device_buffer stage; // of this call
     sam_decode_masks_to_host(m, prompts, n_args, n, masks_u8, iou, chosen, stage, m.last_batch);
+}
+
+int sam_mask_input_size(sam_model const& m) { return m.dec.present && m.dec.mask_input ? 4 * m.dec.res : 0; }
+
+void sam_predict_device(sam_model& m, sam_predict_args const& a, void* masks_u8_dev, void* iou_dev, void* chosen_dev, float* low_res_dev, void* stream) {
+    sam_predict_check(a.points, a.labels, a.k, a.boxes, a.n, a.plane);
+    if (!masks_u8_dev) throw except("sam: null argument");
+    sam_require_decoder(m);
+    if (a.mask_input && a.mask_side != 4 * m.dec.res) throw except("sam: a mask input of side %d, this model takes %d (4 x the embedding's side)", a.mask_side, 4 * m.dec.res);
+    sam_decode_predict(m, sam_predict_set(m, a, a.mask_input), masks_u8_dev, iou_dev, chosen_dev, low_res_dev, stream);
+}
+
+void sam_predict_host(sam_model& m, sam_predict_args const& a, uint8_t* masks_u8, float* iou, int32_t* chosen, float* low_res) {
+    sam_predict_check(a.points, a.labels, a.k, a.boxes, a.n, a.plane);
+    if (!masks_u8) throw except("sam: null argument");
+    sam_require_decoder(m);
+    const int S = 4 * m.dec.res, n = a.n;
+    if (a.mask_input && a.mask_side != S) throw except("sam: a mask input of side %d, this model takes %d (4 x the embedding's side)", a.mask_side, S);
+    if (a.mask_input && !m.dec.mask_input) throw except("sam: this model file holds no mask-input prompt (prompt_encoder.mask_downscaling.* tensors)");
+    device_turn turn(*m.backend);
+    void* s = m.backend->stream;
+    const size_t mask_bytes = (size_t)n * m.image_extent[0] * m.image_extent[1], plane_bytes = (size_t)n * S * S * 4;
+    workspace_layout lay;
+    const size_t o_m = lay.take(mask_bytes), o_i = lay.take((size_t)n * 16), o_c = lay.take((size_t)n * 4), o_l = lay.take(low_res ? plane_bytes : 0),
+                 o_in = lay.take(a.mask_input ? plane_bytes : 0);
+    device_buffer stage; // of this call
+    grow(stage, lay.top, {});
+    uint8_t* base = static_cast<uint8_t*>(stage.ptr);
+    float* mask_dev = a.mask_input ? reinterpret_cast<float*>(base + o_in) : nullptr;
+    if (mask_dev) VX(vx_memcpy_h2d(mask_dev, a.mask_input, plane_bytes, s));
+    sam_decode_predict(m, sam_predict_set(m, a, mask_dev), base + o_m, base + o_i, base + o_c, low_res ? reinterpret_cast<float*>(base + o_l) : nullptr, s);
+    VX(vx_memcpy_d2h(masks_u8, base + o_m, mask_bytes, s)); // waits for the stream
+    if (iou) VX(vx_memcpy_d2h(iou, base + o_i, (size_t)n * 16, s));
+    if (chosen) VX(vx_memcpy_d2h(chosen, base + o_c, (size_t)n * 4, s));
+    if (low_res) VX(vx_memcpy_d2h(low_res, base + o_l, plane_bytes, s));
 }
 
 } // namespace visp

@@ -74,10 +74,25 @@ struct sam_decode_ctx {
 // launches what follows the logits of prompts [p0, p0 + B) on ctx.s
 using sam_chunk_hook = std::function<void(sam_decode_ctx const& ctx, int p0, int B, void* logits, float* iou, int32_t* chosen)>;
 
-// The decoder, which sam_compute, sam_compute_batch_* and sam_generate_masks_* all run: the prompt tokens of the call, layer 0's shared image side, then per
+// The prompts of one decode. Every prompt has n_tokens token rows, [iou | 4 mask tokens | its sparse prompt], which `tokens` writes for prompt i as f16
+// [n_tokens][dim]; mask_input: SAM's mask-input prompt on the device, f32 [n][4 res][4 res], or null (the dense prompt is no_mask_embed); plane: the logit plane
+// `chosen` names, 0 .. 3, or -1 for the best of the first three by predicted iou (vision.cpp:80-83)
+struct sam_prompt_set {
+    int n = 0, n_tokens = 7;
+    std::function<void(int i, uint16_t* out)> tokens;
+    float const* mask_input = nullptr;
+    int plane = -1;
+};
+// SAM's PromptEncoder.forward for one prompt on the host: k points [k][2] in image pixels with labels (1 positive, 0 negative, -1 not a point), box [4] or null
+void sam_prompt_tokens(sam_model const& m, int32_t const* points, int32_t const* labels, int k, int32_t const* box, uint16_t* out);
+
+// The decoder, which sam_compute, sam_compute_batch_*, sam_predict_* and sam_generate_masks_* all run: the prompt tokens of the call, layer 0's shared image side, then per
 // chunk the decoder, the mask product and the iou head. The logits of a chunk go to the chunk buffer of the workspace, or, with logits_all, to
 // [p0 ..] of a buffer that keeps the planes of every prompt; after_chunk launches what follows them. With captures on, `kept` receives the logits and iou
 // predictions of every prompt (a synchronisation per chunk); with captures off it is emptied.
+sam_decode_ctx sam_decode_prompts(sam_model& m, sam_prompt_set const& prompts, void* logits_all, void* iou_dev, void* chosen_dev, void* stream, sam_kept_logits& kept,
+                                  sam_chunk_hook const& after_chunk);
+// points (n_args 2: one positive point) and boxes (n_args 4), mixed: seven token rows each, no mask input, plane -1
 sam_decode_ctx sam_decode_prompts(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, void* logits_all, void* iou_dev, void* chosen_dev, void* stream,
                                   sam_kept_logits& kept, sam_chunk_hook const& after_chunk);
 

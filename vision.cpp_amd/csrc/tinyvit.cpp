@@ -134,6 +134,42 @@ sam_model* sam_load_model(char const* filepath, backend_device const& dev, int f
             memcpy(tb + (size_t)5 * dim, D.not_a_point.data(), (size_t)dim * 4);
             memcpy(tb + (size_t)6 * dim, D.output_tokens.data(), (size_t)5 * dim * 4);
         }
+        const std::string md = "prompt_encoder.mask_downscaling.";
+        if (file.find(md + "0.weight")) { // SAM's mask-input prompt: behind everything else, so a file without it packs to the bytes it always did
+            D.mask_input = true;
+            // a k x k kernel, f32 (f16 for the 1x1): torch's OIHW as the file keeps it (the converters pass prompt_encoder.* through: never permuted, never listed)
+            auto kernel = [&](std::string const& name, int k, int* cout, int* cin, bool half) {
+                gguf_tensor const& t = pk.get(name);
+                *cout = (int)t.ne[3];
+                *cin = (int)t.ne[2];
+                if (t.ne[0] != k || t.ne[1] != k) throw except("mobile-sam: %s is no %dx%d kernel", name.c_str(), k, k);
+                packed_vec v;
+                v.n = (int)t.n_elements();
+                v.off = ab.alloc((size_t)v.n * (half ? 2 : 4));
+                for (int i = 0; with_data && i < v.n; ++i) {
+                    if (half) reinterpret_cast<uint16_t*>(ab.data.data() + v.off)[i] = f32_to_f16(tensor_at(t, i));
+                    else reinterpret_cast<float*>(ab.data.data() + v.off)[i] = tensor_at(t, i);
+                }
+                return v;
+            };
+            int cin = 0, cout = 0;
+            D.md_w1 = kernel(md + "0.weight", 2, &D.md_c1, &cin, false);
+            if (cin != 1) throw except("mobile-sam: mask_downscaling.0 reads %d channels, expected 1", cin);
+            D.md_w2 = kernel(md + "3.weight", 2, &D.md_c2, &cin, false);
+            if (cin != D.md_c1) throw except("mobile-sam: mask_downscaling.3 reads %d channels behind %d", cin, D.md_c1);
+            D.md_w3 = kernel(md + "6.weight", 1, &cout, &cin, true);
+            if (cin != D.md_c2 || cout != dim) throw except("mobile-sam: mask_downscaling.6 is %d -> %d, expected %d -> %d", cin, cout, D.md_c2, dim);
+            D.md_b1 = pk.vec(md + "0.bias");
+            D.md_ln1_w = pk.vec(md + "1.weight");
+            D.md_ln1_b = pk.vec(md + "1.bias");
+            D.md_b2 = pk.vec(md + "3.bias");
+            D.md_ln2_w = pk.vec(md + "4.weight");
+            D.md_ln2_b = pk.vec(md + "4.bias");
+            D.md_b3 = pk.vec(md + "6.bias");
+            if (D.md_b1.n != D.md_c1 || D.md_ln1_w.n != D.md_c1 || D.md_ln1_b.n != D.md_c1 || D.md_b2.n != D.md_c2 || D.md_ln2_w.n != D.md_c2 || D.md_ln2_b.n != D.md_c2 ||
+                D.md_b3.n != dim)
+                throw except("mobile-sam: mask_downscaling's biases and norms do not match its widths %d -> %d -> %d", D.md_c1, D.md_c2, dim);
+        }
     }
 
     device_turn turn(dev);

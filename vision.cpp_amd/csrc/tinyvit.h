@@ -64,6 +64,12 @@ struct samdec_weights {
     // point_embed[4] | not_a_point | output_tokens = 11 dim floats), so that a rank whose arena arrived by RCCL broadcast
     // (load_no_upload) rebuilds them in sam_weights_ready; the f32 iou head of the device (sam_model::iou_head_dev) is made there too.
     size_t tables_off = SIZE_MAX;
+    // SAM's mask-input prompt (prompt_encoder.mask_downscaling.{0,1,3,4,6}: conv 2x2 s2 1 -> md_c1, LayerNorm2d, GELU, conv 2x2 s2 -> md_c2, LayerNorm2d, GELU,
+    // conv 1x1 -> dim), optional: the reference's graph never reads it. Operands of vx_sam_dense_prompt_f16 in the arena, behind everything a file without
+    // them has: f32 but the 1x1 weight, f16 [dim][md_c2]. Kernels OIHW.
+    bool mask_input = false;
+    int md_c1 = 0, md_c2 = 0;
+    packed_vec md_w1, md_b1, md_ln1_w, md_ln1_b, md_w2, md_b2, md_ln2_w, md_ln2_b, md_w3, md_b3;
 };
 // the stages sam_model::generate_split_ms tells apart; the last three run with min_region_area > 0 only
 enum sam_generate_stage { sam_stage_decode, sam_stage_scoring, sam_stage_rank_nms, sam_stage_output, sam_stage_clean, sam_stage_records_nms2, sam_stage_gather, sam_stage_count };
@@ -93,7 +99,7 @@ struct sam_model : model_base { // vision.h sam_model counterpart (encoder part)
     device_buffer batch_ws;
     device_buffer iou_head_dev;            // f32 [w0 | b0 | w1 | b1 | w2 | b2]: the f16-rounded iou head, uploaded by sam_weights_ready
     size_t iou_head_off[6] = {0, 0, 0, 0, 0, 0}; // byte offsets into it
-    void* prompt_tokens_host = nullptr;    // pinned: the prompt tokens of one call, f16 [n][7][dim]
+    void* prompt_tokens_host = nullptr;    // pinned: the prompt tokens of one call, f16 [n][tokens per prompt][dim]
     size_t prompt_tokens_bytes = 0;
     void* prompt_tokens_event = nullptr;   // recorded behind their upload: the next call waits for it before it overwrites them
     sam_kept_logits last_batch;            // of the last batch or generate call, for visp_sam_read_masks_batch; a sam_compute in between leaves it alone
@@ -126,6 +132,24 @@ image_data sam_compute(sam_model&, int const* prompt, int n);
 void sam_compute_batch_device(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, void* masks_u8_dev, void* iou_dev, void* chosen_dev, void* stream);
 void sam_compute_batch_host(sam_model&, int32_t const* prompts, int32_t const* n_args, int n, uint8_t* masks_u8, float* iou, int32_t* chosen);
 void sam_set_prompt_chunk(sam_model&, int n); // 1 .. 256
+// SAM's SamPredictor.predict on the embedding of the last sam_encode: n prompts of ONE shape (SAM's own batched contract), each k points [n][k][2] in image pixels
+// with labels [n][k] (1 positive, 0 negative, -1 not a point), an optional box [n][4] and an optional mask input f32 [n][mask_side][mask_side] (the low_res logits
+// of an earlier call; sam_mask_input_size: 4 x the embedding's side, 0 for a file without prompt_encoder.mask_downscaling). plane -1: the best of the first three
+// masks by predicted iou, as sam_compute; 0 .. 3: that plane (SAM's single-mask output is 0). Outputs as sam_compute_batch_*, and low_res (nullable) f32
+// [n][mask_side^2]: the chosen plane's logits. One positive point or one box alone, no mask, plane -1: the bytes of sam_compute_batch_*. With a mask input
+// layer 0's image side runs per prompt (vx_sam_dense_prompt_f16). Host arrays but mask_input, which is where the outputs are (device / host entry).
+struct sam_predict_args {
+    int32_t const* points = nullptr; int32_t const* labels = nullptr; int k = 0;
+    int32_t const* boxes = nullptr;
+    float const* mask_input = nullptr; int mask_side = 0;
+    int n = 0, plane = -1;
+};
+// throws on what needs neither model nor device to refuse
+void sam_predict_check(int32_t const* points, int32_t const* labels, int k, int32_t const* boxes, int n, int plane);
+int sam_mask_input_size(sam_model const&);
+int sam_prompt_token_count(int k, bool box); // token rows per prompt: 5 + k points + (the box's two corners, or one padding token)
+void sam_predict_device(sam_model&, sam_predict_args const&, void* masks_u8_dev, void* iou_dev, void* chosen_dev, float* low_res_dev, void* stream);
+void sam_predict_host(sam_model&, sam_predict_args const&, uint8_t* masks_u8, float* iou, int32_t* chosen, float* low_res);
 // SAM's automatic mask generator on the prompts of a batch call (one crop layer, no crop-edge filter): every prompt gives three candidates (planes 0 .. 2),
 // filtered by predicted iou and stability score, ranked by predicted iou, de-duplicated by greedy box NMS; the first min(kept, capacity) come out as u8 masks
 // [capacity][h][w] with info_i32 [capacity][8] = {prompt, plane, x, y, w, h, area, 0}, info_f32 [capacity][2] = {predicted_iou, stability_score} and

@@ -433,9 +433,10 @@ def write_tinyvit_gguf(path: str | Path, cfg: TinyVitConfig = TINYVIT_5M, seed: 
 
 # ---- MobileSAM prompt encoder + mask decoder (reference tests/test_mobile_sam.py:796-1470, scripts/convert.py:204-282) ----
 
-def sam_decoder_state_dict(seed: int = 0, dim: int = 256, heads: int = 8, mlp_dim: int = 2048, depth: int = 2) -> dict[str, np.ndarray]:
-    """float32 tensors under the names of a SAM checkpoint (prompt_encoder.*, mask_decoder.*); mask_downscaling is never read
-    by the reference's graph and is left out."""
+def sam_decoder_state_dict(seed: int = 0, dim: int = 256, heads: int = 8, mlp_dim: int = 2048, depth: int = 2, mask_input: bool = False) -> dict[str, np.ndarray]:
+    """float32 tensors under the names of a SAM checkpoint (prompt_encoder.*, mask_decoder.*). mask_downscaling (SAM's mask-input prompt) is never read
+    by the reference's graph and is left out unless mask_input is set: its tensors come last and from a generator of their own, so every other tensor
+    has the same bits either way."""
     rng = np.random.default_rng(seed)
     sd: dict[str, np.ndarray] = {}
 
@@ -488,6 +489,15 @@ def sam_decoder_state_dict(seed: int = 0, dim: int = 256, heads: int = 8, mlp_di
     linear(f"{p}.0", 256, dim)
     linear(f"{p}.1", 256, 256)
     linear(f"{p}.2", 4, 256)
+    if mask_input:  # Conv2d(1, 4, 2, 2) LayerNorm2d GELU Conv2d(4, 16, 2, 2) LayerNorm2d GELU Conv2d(16, dim, 1)
+        rng = np.random.default_rng([seed, 0x6D61736B])
+        p = f"{pe}.mask_downscaling"
+        for i, (co, ci, k) in ((0, (4, 1, 2)), (3, (16, 4, 2)), (6, (dim, 16, 1))):
+            sd[f"{p}.{i}.weight"] = (rng.standard_normal((co, ci, k, k)) / np.sqrt(ci * k * k)).astype(np.float32) * np.float32(0.3 if i == 6 else 1.0)
+            sd[f"{p}.{i}.bias"] = (0.05 * rng.standard_normal(co)).astype(np.float32)
+        for i, c in ((1, 4), (4, 16)):
+            sd[f"{p}.{i}.weight"] = (1 + 0.1 * rng.standard_normal(c)).astype(np.float32)
+            sd[f"{p}.{i}.bias"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
     return sd
 
 

@@ -354,6 +354,60 @@ class Model:
         check(self._api.visp_sam_compute_batch_device(self._handle, p.ctypes.data, k.ctypes.data, len(prompts), masks_dev, iou_dev, chosen_dev, stream))
         self._sam_batch_n = len(prompts)
 
+    # ---- SAM's SamPredictor.predict: labelled points, a box with points, the previous low-resolution logits as mask input
+    def sam_mask_input_size(self) -> int:
+        """side of a mask input (256), 0 when the file has no prompt_encoder.mask_downscaling tensors"""
+        s = c_int32()
+        check(self._api.visp_sam_mask_input_size(self._handle, byref(s)))
+        return s.value
+
+    @staticmethod
+    def _sam_predict_arrays(points, labels, box, mask_input):
+        """one prompt (points [k, 2], box [4], mask_input [S, S]) or a batch of one shape ([n, k, 2], [n, 4], [n, S, S]) -> batch arrays, and whether it was one"""
+        pts = np.zeros((0, 0, 2), np.int32) if points is None else np.ascontiguousarray(points, np.int32)
+        bx = None if box is None else np.ascontiguousarray(box, np.int32)
+        one = pts.ndim == 2 if points is not None else (bx is not None and bx.ndim == 1)
+        if one:
+            pts = pts[None] if points is not None else pts
+            bx = None if bx is None else bx[None]
+        n = pts.shape[0] if points is not None else (0 if bx is None else bx.shape[0])
+        pts = pts.reshape(n, -1, 2)
+        k = pts.shape[1]
+        lab = np.ones((n, k), np.int32) if labels is None else np.ascontiguousarray(labels, np.int32).reshape(n, k)
+        mi = None
+        if mask_input is not None:
+            mi = np.ascontiguousarray(mask_input, np.float32)
+            mi = mi[None] if mi.ndim == 2 else mi
+            if mi.ndim != 3 or mi.shape[0] != n or mi.shape[1] != mi.shape[2]:
+                raise ValueError(f"mask_input of shape {mi.shape} for {n} prompts: expected [n, S, S]")
+        if bx is not None and bx.shape != (n, 4):
+            raise ValueError(f"box of shape {bx.shape} for {n} prompts: expected [n, 4]")
+        return pts, lab, k, bx, mi, n, one
+
+    def sam_predict(self, points, labels=None, box=None, mask_input=None, plane: int = -1):
+        """SamPredictor.predict on the last sam_encode: points [k, 2] in image pixels with labels [k] (1 positive, the default; 0 negative; -1 not a point), an
+        optional box [x0, y0, x1, y1] and an optional mask_input [S, S] (the low_res_logits of an earlier call) -- or a batch of prompts of one shape, every
+        array with a leading n. plane -1: the best of the first three masks by predicted iou; 0 .. 3: that one (SAM's single-mask output is 0).
+        -> (masks uint8 [h, w] of 0 / 255, iou float32 [4], chosen int, low_res_logits float32 [S, S]), each with a leading n for a batch."""
+        pts, lab, k, bx, mi, n, one = self._sam_predict_arrays(points, labels, box, mask_input)
+        w, h = self.sam_image_extent() if n else (0, 0)
+        S = 4 * 64
+        masks, iou, chosen, low = np.empty((n, h, w), np.uint8), np.empty((n, 4), np.float32), np.empty(n, np.int32), np.empty((n, S, S), np.float32)
+        check(self._api.visp_sam_predict_host(self._handle, pts.ctypes.data if k else None, lab.ctypes.data if k else None, k, None if bx is None else bx.ctypes.data,
+                                              None if mi is None else mi.ctypes.data, 0 if mi is None else mi.shape[1], n, int(plane), masks.ctypes.data, iou.ctypes.data,
+                                              chosen.ctypes.data, low.ctypes.data))
+        self._sam_batch_n = n
+        return (masks[0], iou[0], int(chosen[0]), low[0]) if one else (masks, iou, chosen, low)
+
+    def sam_predict_device(self, points, labels=None, box=None, mask_input_dev: int | None = None, plane: int = -1, *, masks_dev: int, iou_dev: int | None = None,
+                           chosen_dev: int | None = None, low_res_dev: int | None = None, stream: int | None = None):
+        """The same with the mask input and the outputs as device addresses (mask_input_dev f32 [n, S, S]; masks u8 [n, h, w], iou f32 [n, 4], chosen i32 [n],
+        low_res f32 [n, S, S], the last three optional). Nothing waits for the device inside a chunk, or at all when a stream is given."""
+        pts, lab, k, bx, _, n, _ = self._sam_predict_arrays(points, labels, box, None)
+        check(self._api.visp_sam_predict_device(self._handle, pts.ctypes.data if k else None, lab.ctypes.data if k else None, k, None if bx is None else bx.ctypes.data,
+                                                mask_input_dev, 4 * 64 if mask_input_dev else 0, n, int(plane), masks_dev, iou_dev, chosen_dev, low_res_dev, stream))
+        self._sam_batch_n = n
+
     def sam_set_prompt_chunk(self, n: int):
         """Prompts per internal chunk of the batch calls (1 .. 256, default 64): sizes the workspace, about 27 MB per prompt in flight."""
         check(self._api.visp_sam_set_prompt_chunk(self._handle, int(n)))
