@@ -256,7 +256,7 @@ inline uint16_t f32_to_f16(float f) { // IEEE binary16, round to nearest even
     return uint16_t(sign | (e < -14 ? q : (uint32_t(e + 14) << 10) + q));
 }
 inline tensor op(model_ref const& m, int32_t kind, std::initializer_list<tensor> src, std::initializer_list<int64_t> ip = {}, std::initializer_list<float> fp = {}) {
-    int32_t ids[4] = {-1, -1, -1, -1}, n = 0, id = -1;
+    int32_t ids[5] = {-1, -1, -1, -1, -1}, n = 0, id = -1;
     for (tensor const& t : src) ids[n++] = t.id;
     check(visp_graph_op(m.handle(), kind, ids, n, ip.begin(), int32_t(ip.size()), fp.begin(), int32_t(fp.size()), &id));
     return tensor(m.handle(), id);

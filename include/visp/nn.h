@@ -132,6 +132,12 @@ inline tensor attention(model_ref m, tensor q, tensor k, tensor v, tensor mask, 
 inline tensor attention_cross(model_ref m, tensor q, tensor k, tensor v, float scale_, model_ref m_out) {
     return linear(m_out, detail::op(m, VISP_OP_ATTENTION_CROSS, {q, k, v}, {}, {scale_}));
 }
+// self-attention with SAM's decomposed relative-position bias and an output linear layer (transformers' SamVisionAttention; the reference has no SAM ViT encoder):
+// q, k, v [64, n_heads, gw * gh, batch], tokens in row-major grid order; the tables m["rel_pos_h"] [64, 2 gh - 1] and m["rel_pos_w"] [64, 2 gw - 1] are shared by all
+// heads. softmax(scale q k^T + bias) v with bias[(qy, qx), (ky, kx)] = q . rel_h[qy - ky + gh - 1] + q . rel_w[qx - kx + gw - 1], from the unscaled q.
+inline tensor attention_rel_pos(model_ref m, tensor q, tensor k, tensor v, int gw, int gh, float scale_, model_ref m_out) {
+    return linear(m_out, detail::op(m, VISP_OP_ATTENTION_REL_POS, {q, k, v, m.weights("rel_pos_h"), m.weights("rel_pos_w")}, {gw, gh}, {scale_}));
+}
 // the ggml calls of the SAM prompt encoder and mask decoder beyond the above (mobile-sam.cpp:243-246, 471)
 inline tensor mul_mat(model_ref const& m, tensor a, tensor b) { return detail::op(m, VISP_OP_MUL_MAT, {a, b}); } // a [K, M, Ba], b [K, N, B] -> [M, N, B]
 inline tensor sin(model_ref const& m, tensor x) { return detail::op(m, VISP_OP_SIN, {x}); }

@@ -593,7 +593,16 @@ enum visp_graph_op {
      * WHCN, which this layer keeps only as views. src an f32 image [C, W, H, N] with C <= 4 (the graph input, or INTERPOLATE of it: INTERPOLATE takes such an image
      * in mode bilinear | align_corners and gives an f32 image every reader of the input takes); i0 = w, i1 = h. The result is f16 [gw gh C, w, h, N] with gw = W / w,
      * gh = H / h: channel gx + gw (gy + gh c) of pixel (py, px) is image (gy h + py, gx w + px, c). w and h divide the image; gw gh C is a multiple of 8. */
-    VISP_OP_IMAGE_PATCHES = 43
+    VISP_OP_IMAGE_PATCHES = 43,
+    /* the node of the SAM ViT image encoder (ViT-B, ViT-L) beyond the above: attention with decomposed relative-position bias (transformers' SamVisionAttention,
+     * segment-anything's add_decomposed_rel_pos). src q, k, v [head_dim, heads, T, B] f16 activations, rel_h [head_dim, 2 gh - 1], rel_w [head_dim, 2 gw - 1]
+     * constants (f16 or f32 in the store, read as f16, shared by all heads); i0 = gw, i1 = gh, f0 = scale. T = gw gh tokens of a grid in row-major order: token t at
+     * (y, x) = (t / gw, t % gw); for windowed layers B is windows x batch. -> [head_dim * heads, T, B] = softmax(scale q k^T + bias) v with
+     * bias[(qy, qx), (ky, kx)] = q . rel_h[qy - ky + gh - 1] + q . rel_w[qx - kx + gw - 1], the bias from the UNSCALED q. Built for head_dim 64 and gw, gh in
+     * 1..64; another head_dim (ViT-H's 80), T != gw gh, a table whose row count is not 2 g - 1 (interpolating a table of another length is a conversion-time
+     * job), non-f16 activations and shapes that do not match are refused when the node is made. One launch on q, k, v where they are; nothing of size T x T
+     * exists in HBM. */
+    VISP_OP_ATTENTION_REL_POS = 44
 };
 /* every f16 / f32 tensor of the file becomes a weight (model_load + model_transfer, ml.cpp:206-217, 449-516); conv kernels listed in
  * <arch>.conv2d_weights of a whcn file are presented as [Cin,kw,kh,Cout]. Device images are made when a graph that uses a tensor is

@@ -344,6 +344,14 @@ VX_API int vx_attention_cross_f16(const void* q, const void* k, const void* v, v
 /* the two launches of a split one by one (the graph layer lists them as two): step 1 the attention launch, step 2 the combine launch (nothing when parts == 1) */
 VX_API int vx_attention_cross_step_f16(int step, const void* q, const void* k, const void* v, void* out, void* partial, size_t partial_bytes, int B, int H, int Tq,
                                        int Tk, int head_dim, float scale, void* stream);
+/* self-attention with SAM's decomposed relative-position bias, head_dim 64 (kernels_attn_relpos.hip; transformers' SamVisionAttention): q, k, v f16
+ * [B][T][H][64] with T = gw * gh tokens of a grid in row-major order (token t at (y, x) = (t / gw, t % gw)) -- token-major rows of H * 64, NOT head-major and
+ * NOT pre-scaled; rel_h f16 [2 gh - 1][64], rel_w f16 [2 gw - 1][64], shared by all heads. out f16 [B][T][H * 64] = softmax(scale q k^T + bias) v with
+ * bias[(qy, qx), (ky, kx)] = q . rel_h[qy - ky + gh - 1] + q . rel_w[qx - kx + gw - 1] from the unscaled q. gw, gh in 1..64. One launch, no workspace, no
+ * atomics: the same bits on every run. vx_attention_relpos_aligned: 1 where key blocks are aligned to grid rows (gw == 64) and the row-aligned form runs. */
+VX_API int vx_attention_relpos_aligned(int gw, int gh);
+VX_API int vx_attention_relpos_f16(const void* q, const void* k, const void* v, const void* rel_h, const void* rel_w, void* out, int B, int H, int gw, int gh,
+                                   int head_dim, float scale, void* stream);
 /* ggml_mul_mat of two f16 activations (kernels_samdec.hip; mobile-sam.cpp:471): a [Ba][M][K], b [B][N][K] -> out [B][N][M], out[b][n][m] = sum_k a[b or 0][m][k]
  * b[b][n][k], f32 sums with k ascending, one f16 rounding. K a multiple of 8 and <= 256, N <= 16, Ba 1 or B; a 16-byte aligned. One thread per row m. */
 VX_API int vx_mul_mat_f16(const void* a, const void* b, void* out, int64_t M, int N, int K, int B, int Ba, void* stream);

@@ -20,7 +20,7 @@ const char* const op_names[gop_count] = {"input", "weight", "linear", "layer_nor
                                          "conv_transpose_2d", "interpolate", "attention", "concat", "slice", "reshape", "repeat",
                                          "patch_embed", "cont", "image_u8_to_f32", "image_normalize", "leaky_relu", "permute", "roll", "pad", "get_rows",
                                          "cast", "attention_masked", "conv_2d_deform", "sigmoid", "mean_2d", "conv_2d_depthwise", "silu", "pool_2d", "soft_max",
-                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos", "rope", "image_patches"};
+                                         "sum_rows", "sub", "clamp", "attention_cross", "mul_mat", "sin", "cos", "rope", "image_patches", "attention_rel_pos"};
 
 // ---- host evaluation of constants (f32, ggml index order: i0 fastest) ------------------------------------------------------
 
@@ -401,7 +401,7 @@ void graph_output(graph& g, int t, char const* name) {
 int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip, int n_ip, const float* fp, int n_fp) {
     require_building(g, "graph_add");
     if (op <= gop_weight || op >= gop_count) throw except("graph_add: op %d is not a node op", op);
-    if (n_src < 1 || n_src > 4 || n_ip < 0 || n_ip > 12 || n_fp < 0 || n_fp > 8) throw except("graph_add(%s): bad argument counts", graph_op_name(op));
+    if (n_src < 1 || n_src > 5 || n_ip < 0 || n_ip > 12 || n_fp < 0 || n_fp > 8) throw except("graph_add(%s): bad argument counts", graph_op_name(op));
     graph_node n;
     n.op = op;
     n.n_src = n_src;
@@ -661,6 +661,32 @@ int graph_add(graph& g, int32_t op, const int* src, int n_src, const int64_t* ip
             if (q.ne[0] != 16 && q.ne[0] != 32 && q.ne[0] != 64) throw except("attention_cross: head_dim %lld; the kernel is built for head_dim 16, 32 and 64", (long long)q.ne[0]);
             for (int i = 0; i < 3; ++i)
                 if (S(i).constant || S(i).dtype != gdt_f16) throw except("attention_cross: operand %d (%s) is %s; q, k and v are f16 activations", i, i == 0 ? "q" : (i == 1 ? "k" : "v"), S(i).constant ? "a constant" : "f32");
+            n.ne[0] = q.ne[0] * q.ne[1];
+            n.ne[1] = q.ne[2];
+            n.ne[2] = q.ne[3];
+            n.ne[3] = 1;
+        } break;
+        case gop_attention_rel_pos: {
+            need_src(5, 5);
+            graph_node const &q = S(0), &k = S(1), &v = S(2);
+            const int64_t gw = n.ip[0], gh = n.ip[1];
+            for (int i = 0; i < 4; ++i)
+                if (k.ne[i] != q.ne[i] || v.ne[i] != q.ne[i])
+                    throw except("attention_rel_pos: q %s, k %s, v %s do not match ([head_dim, heads, tokens, batch], self-attention)", shape_str(q.ne).c_str(), shape_str(k.ne).c_str(), shape_str(v.ne).c_str());
+            if (q.ne[0] != 64) throw except("attention_rel_pos: head_dim %lld; the kernel is built for head_dim 64 (ViT-B, ViT-L); ViT-H's 80 is out of scope", (long long)q.ne[0]);
+            if (n_ip != 2 || gw < 1 || gw > 64 || gh < 1 || gh > 64) throw except("attention_rel_pos: grid %lld x %lld; gw and gh are 1..64", (long long)gw, (long long)gh);
+            if (q.ne[2] != gw * gh) throw except("attention_rel_pos: %lld tokens on a %lld x %lld grid (T == gw * gh, row-major)", (long long)q.ne[2], (long long)gw, (long long)gh);
+            for (int i = 0; i < 3; ++i)
+                if (S(i).constant || S(i).dtype != gdt_f16) throw except("attention_rel_pos: operand %d (%s) is %s; q, k and v are f16 activations", i, i == 0 ? "q" : (i == 1 ? "k" : "v"), S(i).constant ? "a constant" : "f32");
+            for (int i = 3; i < 5; ++i) {
+                graph_node const& tab = S(i);
+                const int64_t g_ = i == 3 ? gh : gw;
+                if (!tab.constant || tab.dtype == gdt_i32) throw except("attention_rel_pos: %s is an f16 / f32 constant", i == 3 ? "rel_h" : "rel_w");
+                if (tab.ne[0] != q.ne[0] || tab.ne[2] != 1 || tab.ne[3] != 1) throw except("attention_rel_pos: %s %s does not match head_dim %lld ([head_dim, 2 g - 1])", i == 3 ? "rel_h" : "rel_w", shape_str(tab.ne).c_str(), (long long)q.ne[0]);
+                if (tab.ne[1] != 2 * g_ - 1)
+                    throw except("attention_rel_pos: %s has %lld rows, a grid of %lld needs 2 g - 1 = %lld (interpolating a table of another length is a conversion-time job)", i == 3 ? "rel_h" : "rel_w",
+                                 (long long)tab.ne[1], (long long)g_, (long long)(2 * g_ - 1));
+            }
             n.ne[0] = q.ne[0] * q.ne[1];
             n.ne[1] = q.ne[2];
             n.ne[2] = q.ne[3];

@@ -82,6 +82,8 @@ enum graph_op : int32_t {
     gop_rope,             // x [n, heads, T, B] f16, pos i32 constant [T]; i0 = n_dims (== n), i1 = mode (0: NORMAL); f0 = freq_base, f1 = freq_scale   ggml_rope_ext
     // the node of BiRefNet's decoder beyond the above (birefnet.cpp:153-162); interpolate also takes an f32 image [C <= 4, W, H, N] (birefnet.cpp:36-41)
     gop_image_patches,    // f32 image [C <= 4, W, H, N]; i0 = w, i1 = h -> f16 [gw gh C, w, h, N], channel gx + gw (gy + gh c)   image_to_patches
+    // the node of the SAM ViT image encoder beyond the above (transformers' SamVisionAttention; segment-anything's add_decomposed_rel_pos)
+    gop_attention_rel_pos,// q, k, v [64, heads, T, B] f16, rel_h [64, 2 gh - 1], rel_w [64, 2 gw - 1] constants; i0 = gw, i1 = gh (T = gw gh), f0 = scale -> [64 * heads, T, B]
     gop_count
 };
 const char* graph_op_name(int32_t op);
@@ -92,7 +94,7 @@ struct graph_node {
     int32_t op = gop_input;
     int32_t dtype = gdt_f16;
     int64_t ne[4] = {1, 1, 1, 1};
-    int src[4] = {-1, -1, -1, -1};
+    int src[5] = {-1, -1, -1, -1, -1}; // (five: attention_rel_pos reads q, k, v and its two tables)
     int n_src = 0;
     int64_t ip[12] = {0};
     float fp[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -126,6 +126,7 @@ void lowering::run() {
             case gop_attention: attention(t); break;
             case gop_attention_masked: attention_masked(t); break;
             case gop_attention_cross: attention_cross(t); break;
+            case gop_attention_rel_pos: attention_rel_pos(t); break;
             case gop_mul_mat: mul_mat(t); break;
             case gop_sin:
             case gop_cos: sincos(t); break;

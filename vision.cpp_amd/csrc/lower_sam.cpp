@@ -1,5 +1,6 @@
 // Graph lowering: the nodes of the SAM prompt encoder and mask decoder (mobile-sam.cpp:210-478; see lowering.h) -- attention without a mask on q, k, v
-// where the graph has them, ggml_mul_mat of two activations, sin / cos, and the Fourier-feature group of position_embedding_random.
+// where the graph has them, ggml_mul_mat of two activations, sin / cos, and the Fourier-feature group of position_embedding_random -- and the attention of the
+// original SAM ViT image encoder, with decomposed relative-position bias.
 #include "lowering.h"
 
 #include <cmath>
@@ -102,6 +103,25 @@ void lowering::attention_cross(int t) {
     snprintf(d, sizeof d, "attention_cross_combine B=%d heads=%d Tq=%d parts=%d hd=%d", B, H, Tq, parts, hd);
     emit(d, {pbuf}, {obuf}, [=](void* st) { VX(vx_attention_cross_step_f16(2, qp(), kp(), vp(), op(), pp(), part_bytes, B, H, Tq, Tk, hd, scale, st)); });
     tag("attention", 0, (double)part_bytes);
+}
+
+// softmax(scale q k^T + decomposed rel-pos bias) v (transformers' SamVisionAttention) on q, k, v where the graph has them: ONE launch in both lowering modes
+// (kernels_attn_relpos.hip), no workspace -- the bias never exists as a [T, T] tensor. The two tables go to the device as f16 images, once per constant.
+void lowering::attention_rel_pos(int t) {
+    graph_node& n = g.nodes[t];
+    graph_node const& q = g.nodes[n.src[0]];
+    const int hd = (int)q.ne[0], H = (int)q.ne[1], T = (int)q.ne[2], B = (int)q.ne[3], gw = (int)n.ip[0], gh = (int)n.ip[1];
+    const int qb = token_rows(n.src[0], "attention_rel_pos"), kb = token_rows(n.src[1], "attention_rel_pos"), vb = token_rows(n.src[2], "attention_rel_pos");
+    void *rel_h = const_f16(n.src[3]), *rel_w = const_f16(n.src[4]);
+    materialise(t);
+    const int obuf = n.buffer;
+    auto qp = ptr(qb), kp = ptr(kb), vp = ptr(vb), op = ptr(obuf);
+    const float scale = n.fp[0];
+    char d[200];
+    snprintf(d, sizeof d, "attention_rel_pos%s B=%d heads=%d grid=%dx%d hd=%d", vx_attention_relpos_aligned(gw, gh) ? "[row-aligned]" : "", B, H, gw, gh, hd);
+    emit(d, {qb, kb, vb}, {obuf}, [=](void* st) { VX(vx_attention_relpos_f16(qp(), kp(), vp(), rel_h, rel_w, op(), B, H, gw, gh, hd, scale, st)); });
+    // QK^T and PV, and the two bias products of every query with its tables' 2 g - 1 rows
+    tag("attention", 4.0 * B * H * (double)T * T * hd + 2.0 * B * H * (double)T * (2 * gw + 2 * gh - 2) * hd, (double)B * H * T * hd * 2 * 4);
 }
 
 void lowering::mul_mat(int t) {

@@ -6,7 +6,7 @@
 //   lower_encoder.cpp  attention, the fused q|k|v product, patch embedding, the DINOv2 encoder chain on the block kernel
 //   lower_yolo.cpp     SiLU epilogues, the folded RepConv, channel slices and concats in place, pooling, softmax and the DFL decode
 //   lower_migan.cpp    lrelu_agc epilogues, the x2 FIR upsample group, clamp and plane-broadcast launches
-//   lower_sam.cpp      attention without a mask on token-major q / k / v, mul_mat of activations, sin / cos, the Fourier-feature group
+//   lower_sam.cpp      attention without a mask and with decomposed rel-pos bias on token-major q / k / v, mul_mat of activations, sin / cos, the Fourier-feature group
 //   lower_sam3.cpp     ROPE, the rope_2d group (alone, and in place behind the fused q|k|v product), get_rows with a run-time index
 //   lower_birefnet.cpp resize and patches of an f32 image, the pixel gate group, bilinear resizes and LayerNorms that write into a concat's buffer
 //   lower_run.cpp      liveness, the per-node dispatch, element-wise / copy / interpolate / image ops, the buffer plan
@@ -349,6 +349,7 @@ struct lowering {
     void fourier_features(int t, fourier_group const& G);
     int token_rows(int t, const char* who);
     void attention_cross(int t);
+    void attention_rel_pos(int t);
     void mul_mat(int t);
     void sincos(int t);
 

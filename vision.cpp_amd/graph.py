@@ -304,6 +304,13 @@ def attention_cross(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, scale: float, 
     return linear(m_out, m.graph.op(OP_ATTENTION_CROSS, [q, k, v], fparams=[scale]))
 
 
+def attention_rel_pos(m: ModelRef, q: Tensor, k: Tensor, v: Tensor, gw: int, gh: int, scale: float, m_out: ModelRef) -> Tensor:  # transformers' SamVisionAttention
+    """Self-attention with SAM's decomposed relative-position bias. q, k, v [64, n_heads, gw * gh, batch], tokens in row-major grid order (token t at
+    (y, x) = (t // gw, t % gw)); the tables m["rel_pos_h"] [64, 2 gh - 1] and m["rel_pos_w"] [64, 2 gw - 1] are shared by all heads.
+    softmax(scale q k^T + bias) v with bias[(qy, qx), (ky, kx)] = q . rel_h[qy - ky + gh - 1] + q . rel_w[qx - kx + gw - 1], the bias from the unscaled q."""
+    return linear(m_out, m.graph.op(OP_ATTENTION_REL_POS, [q, k, v, m.weights("rel_pos_h"), m.weights("rel_pos_w")], [gw, gh], [scale]))
+
+
 # ---- ml.h tensor operations + the ggml ops the arch code uses directly ----------------------------------------------------------
 
 def slice_(m: ModelRef, x: Tensor, s0=SLICE_ALL, s1=SLICE_ALL, s2=SLICE_ALL, s3=SLICE_ALL) -> Tensor:  # ml.cpp:746-768
@@ -1575,3 +1582,53 @@ def sam3_encode_vision(m: ModelRef, image: Tensor, p: Sam3VitParams):  # sam3.h:
     x = sam3_vision_transformer(m["backbone"], image, p)
     x = reshape(m, x, x.ne[0], w // p.patch_size, h // p.patch_size, b)
     return sam3_vision_neck(m["neck"], x)
+
+
+
+# ---- the original SAM image encoder (ViT-B / ViT-L) -------------------------------------------------------------------------------------------------------
+# transformers' SamVisionEncoder (models/sam/modeling_sam.py), module for module under its tensor names; the reference has no source for it ("only supports
+# MobileSAM (TinyViT) for now"). Maps are CWHN, so HF's [B, H, W, C] hidden states are this layer's [C, W, H, B] as they are; the window helpers are SAM3's
+# (the same partition: zero padding at the right and bottom, padded tokens take part as keys, unmasked). HF's activation is the erf GELU; GELU here is ggml's
+# tanh form, as for every encoder of this layer.
+
+class SamVitParams:  # SamVisionConfig's fields this graph reads
+    def __init__(self, image_size=1024, patch_size=16, window_size=14, n_layers=12, n_heads=12, global_attn_indexes=(2, 5, 8, 11)):
+        self.image_size, self.patch_size, self.window_size, self.n_layers, self.n_heads = image_size, patch_size, window_size, n_layers, n_heads
+        self.global_attn_indexes = tuple(global_attn_indexes)
+
+
+def sam_vit_attention(m: ModelRef, x: Tensor, n_heads: int, gw: int, gh: int) -> Tensor:  # SamVisionAttention; x [C, gw * gh, B]
+    q, k, v = split_qkv(m["qkv"], x, n_heads, 2)  # HF: reshape(B, H * W, 3, heads, -1)
+    return attention_rel_pos(m, q, k, v, gw, gh, 1.0 / math.sqrt(float(x.ne[0] // n_heads)), m["proj"])
+
+
+def sam_vit_mlp(m: ModelRef, x: Tensor) -> Tensor:  # SamMLPBlock
+    return linear(m["lin2"], gelu(m, linear(m["lin1"], x)))
+
+
+def sam_vit_layer(m: ModelRef, x: Tensor, window_size: int, n_heads: int) -> Tensor:  # SamVisionLayer; x [C, W, H, B]
+    residual = x
+    x = layer_norm(m["layer_norm1"], x, 1e-6)
+    c, w, h, b = x.ne
+    if window_size > 0:
+        x = sam3_window_partition(m, x, window_size)
+        x = sam_vit_attention(m["attn"], x, n_heads, window_size, window_size)
+        x = sam3_window_reverse(m, x, w, h, window_size, b)
+    else:
+        x = reshape(m, sam_vit_attention(m["attn"], reshape(m, x, c, w * h, b), n_heads, w, h), c, w, h, b)
+    x = add(m, x, residual)
+    x = add(m, sam_vit_mlp(m["mlp"], layer_norm(m["layer_norm2"], x, 1e-6)), x)
+    return named(m, x)
+
+
+def sam_vit_neck(m: ModelRef, x: Tensor) -> Tensor:  # SamVisionNeck: SamLayerNorm(channels_first) is a LayerNorm over ne[0] of a CWHN map
+    x = layer_norm(m["layer_norm1"], conv_2d(m["conv1"], x, 1, 0), 1e-6)
+    return layer_norm(m["layer_norm2"], conv_2d(m["conv2"], x, 1, 1), 1e-6)
+
+
+def sam_vit_encode(m: ModelRef, image: Tensor, p: SamVitParams) -> Tensor:  # SamVisionEncoder; image f32 [3, W, H, N] -> [out_channels, W / patch, H / patch, N]
+    x = patch_embed(m["patch_embed"], image, p.patch_size)  # SamPatchEmbeddings
+    x = add(m, x, m.weights("pos_embed"))                   # [C, W, H, 1] broadcast over the batch (use_abs_pos)
+    for i in range(p.n_layers):
+        x = sam_vit_layer(m["layers"][i], x, 0 if i in p.global_attn_indexes else p.window_size, p.n_heads)
+    return sam_vit_neck(m["neck"], x)

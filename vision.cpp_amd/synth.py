@@ -1121,3 +1121,65 @@ def write_sam3_gguf(path: str | Path, vit: Sam3VitConfig | None = SAM3_VIT_MINI,
         w.add_tensor(name, t)
     w.write()
     return Path(path)
+
+
+# ---- the original SAM image encoder, ViT-B / ViT-L (transformers' SamVisionEncoder; graph.py::sam_vit_encode) ----
+
+@dataclass
+class SamVitConfig:
+    """SamVisionConfig's fields, with ViT-B's values."""
+    hidden: int = 768
+    heads: int = 12
+    mlp: int = 3072
+    patch: int = 16
+    window: int = 14
+    image_size: int = 1024
+    n_layers: int = 12
+    global_layers: tuple = (2, 5, 8, 11)
+    out_channels: int = 256
+    name: str = "sam_vit_b"
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch
+
+
+SAM_VIT_B = SamVitConfig()
+# a 6 x 6 grid: layer 0 in windows of 4 (the map pads to 8 x 8, four windows of which three hold padding), layer 1 global
+SAM_VIT_MINI = SamVitConfig(hidden=128, heads=2, mlp=256, patch=16, window=4, image_size=96, n_layers=2, global_layers=(1,), out_channels=32, name="sam_vit_mini")
+
+
+def sam_vit_state_dict(cfg: SamVitConfig = SAM_VIT_MINI, seed: int = 0) -> dict[str, np.ndarray]:
+    """float32 tensors under the names of transformers' SamVisionEncoder (the `vision_encoder.` part of SamModel's keys left off), torch shapes. The rel-pos
+    tables are random, not symmetric in their index, and rel_pos_h differs from rel_pos_w: an axis or sign mix-up changes the output."""
+    rng = np.random.default_rng(seed)
+    sd: dict[str, np.ndarray] = {}
+    normal, lin, norm = _sam3_helpers(rng, sd)
+    C, hd, g = cfg.hidden, cfg.hidden // cfg.heads, cfg.grid
+    sd["pos_embed"] = normal((1, g, g, C), 0.5)
+    sd["patch_embed.projection.weight"] = normal((C, 3, cfg.patch, cfg.patch), 1.0 / np.sqrt(3 * cfg.patch ** 2))
+    sd["patch_embed.projection.bias"] = normal((C,), 0.02)
+    for i in range(cfg.n_layers):
+        p, side = f"layers.{i}", g if i in cfg.global_layers else cfg.window
+        norm(f"{p}.layer_norm1", C)
+        sd[f"{p}.attn.rel_pos_h"] = normal((2 * side - 1, hd), 0.2)
+        sd[f"{p}.attn.rel_pos_w"] = normal((2 * side - 1, hd), 0.2)
+        lin(f"{p}.attn.qkv", 3 * C, C, gain=1.5)
+        lin(f"{p}.attn.proj", C, C)
+        norm(f"{p}.layer_norm2", C)
+        lin(f"{p}.mlp.lin1", cfg.mlp, C, gain=1.4)
+        lin(f"{p}.mlp.lin2", C, cfg.mlp, gain=1.4)
+    sd["neck.conv1.weight"] = normal((cfg.out_channels, C, 1, 1), 1.0 / np.sqrt(C))
+    norm("neck.layer_norm1", cfg.out_channels)
+    sd["neck.conv2.weight"] = normal((cfg.out_channels, cfg.out_channels, 3, 3), 1.0 / np.sqrt(9 * cfg.out_channels))
+    norm("neck.layer_norm2", cfg.out_channels)
+    return sd
+
+
+def sam_vit_graph_tensors(sd: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
+    """The tensors as a weight store presents them: f16-rounded f32, conv kernels OHWI (ne [Cin, kw, kh, Cout]); pos_embed [1, H, W, C] is CWHN as it is."""
+    out = {}
+    for name, t in sd.items():
+        t = t.astype(np.float16).astype(np.float32)
+        out[name] = np.ascontiguousarray(t.transpose(0, 2, 3, 1)) if t.ndim == 4 and name.endswith(".weight") else t
+    return out
