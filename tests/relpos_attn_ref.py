@@ -78,9 +78,10 @@ def evaluate_relpos(a, guard_rows=0, with_bias=True):
     return want, allow, written
 
 
-# (gw, gh, heads, B): a single token; gw != gh with head and batch strides, and its transpose; SAM's window (T = 196 is no tile multiple, key tiles straddle
-# rows); a row wider than half a tile; the row-aligned form with the fewest rows; the global shape
-CASES = [(1, 1, 1, 1), (3, 5, 2, 2), (5, 3, 2, 2), (14, 14, 2, 3), (20, 7, 1, 1), (64, 2, 1, 1), (64, 64, 1, 1)]
+# (gw, gh, heads, B): a single token; gw != gh with head and batch strides, and its transpose; two query tiles in one block, the second ragged (T = 49: the
+# only case on the two-wave kernel); SAM's window (T = 196 is no tile multiple, key tiles straddle rows); a row wider than half a tile; the row-aligned form
+# with the fewest rows; the global shape
+CASES = [(1, 1, 1, 1), (3, 5, 2, 2), (5, 3, 2, 2), (7, 7, 2, 1), (14, 14, 2, 3), (20, 7, 1, 1), (64, 2, 1, 1), (64, 64, 1, 1)]
 
 
 def operands(case, seed=0):

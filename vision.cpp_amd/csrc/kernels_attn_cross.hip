@@ -4,12 +4,7 @@
 //
 // q f16 [B][T_q][H][HD], k and v f16 [B][T_k][H][HD] -- token-major rows of H * HD, where the graph has them: no head-major copies in front.
 // out f16 [B][T_q][H * HD]. The kernel multiplies the f32 scores by scale * log2(e) itself (q is NOT pre-scaled).
-// The orientation is that of kernels_attn_mask.hip: one block = NW wave64 = 32 NW queries of one (batch, head); S^T = K Q^T on
-// v_mfma_f32_32x32x16_f16 (head_dim 16 is exactly one k-step), so a lane owns ONE query column (lane & 31) and 16 keys of the 32-key block
-// in its accumulator registers (key = 8 (e >> 2) + 4 (lane >> 5) + (e & 3)); online softmax over the 32-key blocks in the exp2 domain with
-// the finite running-maximum floor (-1e30: a block that is all -inf while nothing has been seen gives exp2(-inf + 1e30) = 0, never NaN);
-// P^T feeds O^T = V^T P^T straight from the accumulators, V^T fragments come from ds_read_b64_tr_b16. At head_dim 16 the transposed reads
-// of lanes 16..31 of a half fetch d = 0..15 again: rows 16..31 of O^T are computed and never stored.
+// The 32-key block step -- orientation, accumulator layout, LDS tile, online softmax -- is vx_attn_tile.h's.
 //   * keys at or beyond the end of the block's key range score -inf (P exactly 0); queries >= T_q are computed on a clamped row, not stored.
 //
 // Key splitting. With T_q <= 32 there is one block per (batch, head): 8 blocks at the decoder's 7 x 4096. From CX_SPLIT_MIN keys on, the keys
@@ -18,34 +13,20 @@
 // m = max m_i, l = sum l_i 2^(m_i - m), O = sum O_i 2^(m_i - m), every sum a sequential f32 chain from part 0 upwards. No atomics: the
 // same bits on every run. The few-keys side (T_k <= 32, many queries) is one key block per wave tile: one staging step, no ring.
 #include "vx_common.h"
+#include "vx_attn_tile.h"
 
 namespace {
 
-constexpr float CX_LOG2E = 1.44269504088896340736f;
 constexpr int CX_SPLIT_KEYS = 128; // keys per part (a multiple of 32)
 constexpr int CX_SPLIT_MIN = 256;  // fewer keys than this: one part
-
-typedef __fp16 hv4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-template <int HD>
-__device__ __forceinline__ int cx_k_swz(int row, int chunk) { return HD == 64 ? chunk ^ ((row >> 1) & 7) : (HD == 32 ? chunk ^ ((row >> 2) & 3) : chunk); }
-template <int HD>
-__device__ __forceinline__ int cx_v_swz(int row, int chunk) { return HD == 64 ? chunk ^ (((row >> 1) & 1) << 2) : chunk; }
 
 template <int HD, int NW>
 __global__ __launch_bounds__(64 * NW) void attention_cross_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ V, f16* __restrict__ O,
                                                                   float* __restrict__ partial, int H, int Tq, int Tk, int n_split, float qs) {
-    constexpr int ROW = HD * 2;           // bytes per K / V row in LDS
-    constexpr int CH = HD / 8;            // 16-byte chunks per row
-    constexpr int N_CH = 32 * CH;         // chunks per 32-key block
-    constexpr int THREADS = 64 * NW;
-    constexpr int PER = (N_CH + THREADS - 1) / THREADS;
-    constexpr int DS = HD / 16;           // d-steps of the score product
-    constexpr int DB = HD == 64 ? 2 : 1;  // 32-row blocks of O^T
-    constexpr int G_OUT = HD == 16 ? 2 : 4; // groups of four accumulator rows that hold real d
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 32 * ROW];
+    using G = attn_tile<HD>;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::BYTES];
     unsigned char* const sk = smem;
-    unsigned char* const sv = smem + 32 * ROW;
+    unsigned char* const sv = smem + G::BYTES;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,110 +49,44 @@ __global__ __launch_bounds__(64 * NW) void attention_cross_kernel(const f16* __r
 
     const int q = q0 + r;
     const int qc = q < Tq ? q : Tq - 1;
-    f16x8 qf[DS];
+    f16x8 qf[G::DS];
 #pragma unroll
-    for (int s = 0; s < DS; ++s) qf[s] = *reinterpret_cast<const f16x8*>(Qb + (long)qc * ld + 16 * s + 8 * h);
+    for (int s = 0; s < G::DS; ++s) qf[s] = *reinterpret_cast<const f16x8*>(Qb + (long)qc * ld + 16 * s + 8 * h);
 
-    // ---- staging: chunk cid = tid + i * THREADS of the block is row cid / CH, 16-byte chunk cid % CH
-    f16x8 kreg[PER], vreg[PER];
-    auto load_block = [&](int k0) {
+    f16x8 kreg[attn_stage<HD, NW>::PER], vreg[attn_stage<HD, NW>::PER];
+    // loop-invariant LDS offsets: K fragment of d-step s = row r, chunk 2 s + h; V^T transposed reads of O^T block db, k-step 0 (vx_attn_tile.h)
+    int k_off[G::DS], v_off[G::DB];
 #pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int cid = tid + i * THREADS, row = cid / CH, c = cid - row * CH, key = k0 + row;
-            f16x8 z = {(f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0};
-            kreg[i] = z;
-            vreg[i] = z;
-            if (cid < N_CH && key < k_end) {
-                kreg[i] = *reinterpret_cast<const f16x8*>(Kb + (long)key * ld + c * 8);
-                vreg[i] = *reinterpret_cast<const f16x8*>(Vb + (long)key * ld + c * 8);
-            }
-        }
-    };
-    auto store_block = [&]() {
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int cid = tid + i * THREADS, row = cid / CH, c = cid - row * CH;
-            if (cid < N_CH) {
-                *reinterpret_cast<f16x8*>(sk + row * ROW + cx_k_swz<HD>(row, c) * 16) = kreg[i];
-                *reinterpret_cast<f16x8*>(sv + row * ROW + cx_v_swz<HD>(row, c) * 16) = vreg[i];
-            }
-        }
-    };
-
-    // loop-invariant LDS offsets: K fragment of d-step s = row r, chunk 2 s + h; V^T transposed reads as in kernels_attn_mask.hip (16-lane
-    // group g covers d = 16 (g & 1) .. +15 of key half g >> 1 == h; lane 4 t + p of the group supplies key row t, columns 4 p .. +3)
-    int k_off[DS], v_off[DB];
-#pragma unroll
-    for (int s = 0; s < DS; ++s) k_off[s] = r * ROW + cx_k_swz<HD>(r, 2 * s + h) * 16;
+    for (int s = 0; s < G::DS; ++s) k_off[s] = r * G::ROW + attn_k_swz<HD>(r, 2 * s + h) * 16;
     {
         const int key = 4 * h + ((lane & 15) >> 2), dd = ((16 * ((lane >> 4) & 1)) & (HD - 1)) + 4 * (lane & 3);
 #pragma unroll
-        for (int db = 0; db < DB; ++db) v_off[db] = key * ROW + cx_v_swz<HD>(key, (dd + 32 * db) >> 3) * 16 + (dd & 7) * 2;
+        for (int db = 0; db < G::DB; ++db) v_off[db] = key * G::ROW + attn_v_swz<HD>(key, (dd + 32 * db) >> 3) * 16 + (dd & 7) * 2;
     }
-
-    f32x16 o[DB];
+    f32x16 o[G::DB];
 #pragma unroll
-    for (int db = 0; db < DB; ++db)
+    for (int db = 0; db < G::DB; ++db)
 #pragma unroll
         for (int e = 0; e < 16; ++e) o[db][e] = 0.0f;
-    float m_run = -1e30f, l_run = 0.0f; // finite floor: see the header
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float m_run = ATTN_M_FLOOR, l_run = 0.0f;
 
     const int n_blocks = (k_end - k_begin + 31) / 32;
-    load_block(k_begin);
+    attn_kv_load<HD, NW>(tid, kreg, vreg, Kb, Vb, ld, k_begin, k_end);
     for (int kb = 0; kb < n_blocks; ++kb) {
         const int k0 = k_begin + kb * 32;
-        __syncthreads(); // every wave is done with block kb - 1
-        store_block();
-        __syncthreads();
-        if (kb + 1 < n_blocks) load_block(k0 + 32);
+        attn_kv_store_sync<HD, NW>(tid, kreg, vreg, sk, sv);
+        if (kb + 1 < n_blocks) attn_kv_load<HD, NW>(tid, kreg, vreg, Kb, Vb, ld, k0 + 32, k_end);
         if (!active) continue;
 
-        f32x16 s = zero;
-#pragma unroll
-        for (int st = 0; st < DS; ++st) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(sk + k_off[st]), qf[st], s, 0, 0, 0);
-
+        f32x16 s = attn_scores<HD>(sk, k_off, qf);
         float mloc = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int key = k0 + 8 * (e >> 2) + 4 * h + (e & 3);
-            const float v = key < k_end ? s[e] * qs : -INFINITY;
+            const float v = k0 + attn_key_of(e, h) < k_end ? s[e] * qs : -INFINITY;
             s[e] = v;
             mloc = fmaxf(mloc, v);
         }
-        mloc = fmaxf(mloc, other_half(mloc)); // lanes l and l + 32 own the same query
-        const float m_new = fmaxf(m_run, mloc);
-        if (__any(m_new > m_run)) {
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-            m_run = m_new;
-        }
-        float psum = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float p = __builtin_amdgcn_exp2f(s[e] - m_run);
-            s[e] = p;
-            psum += p;
-        }
-        l_run += psum;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { // element j of the k-step <-> key k0 + 16 ks + 8 (j >> 2) + 4 h + (j & 3)
-            f16x8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = (f16)s[8 * ks + j];
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const unsigned char* vrow = sv + v_off[db] + ks * 16 * ROW;
-                hv4 va = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hv4*)(vrow));
-                hv4 vb = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hv4*)(vrow + 8 * ROW));
-                f16x8 vf = {(f16)va[0], (f16)va[1], (f16)va[2], (f16)va[3], (f16)vb[0], (f16)vb[1], (f16)vb[2], (f16)vb[3]};
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[db], 0, 0, 0);
-            }
-        }
+        attn_softmax_pv<HD>(s, mloc, m_run, l_run, o, sv, v_off);
     }
 
     if (!active || q >= Tq) return;
@@ -180,9 +95,9 @@ __global__ __launch_bounds__(64 * NW) void attention_cross_kernel(const f16* __r
         float* prow = partial + (((long)bh * n_split + part) * 32 + q) * (HD + 2);
         if (h == 0) { prow[0] = m_run; prow[1] = l_tot; }
 #pragma unroll
-        for (int db = 0; db < DB; ++db)
+        for (int db = 0; db < G::DB; ++db)
 #pragma unroll
-            for (int g = 0; g < G_OUT; ++g)
+            for (int g = 0; g < G::G_OUT; ++g)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) prow[2 + db * 32 + 8 * g + 4 * h + j] = o[db][g * 4 + j];
         return;
@@ -190,9 +105,9 @@ __global__ __launch_bounds__(64 * NW) void attention_cross_kernel(const f16* __r
     const float inv = 1.0f / l_tot;
     f16* orow = O + ((long)b * Tq + q) * ld + head * HD;
 #pragma unroll
-    for (int db = 0; db < DB; ++db)
+    for (int db = 0; db < G::DB; ++db)
 #pragma unroll
-        for (int g = 0; g < G_OUT; ++g) {
+        for (int g = 0; g < G::G_OUT; ++g) { // accumulator rows d = 32 db + 8 g + 4 h + j
             f16x4 v;
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = (f16)(o[db][g * 4 + j] * inv);
@@ -208,7 +123,7 @@ __global__ __launch_bounds__(256) void attention_cross_combine_kernel(const floa
     for (int idx = threadIdx.x; idx < Tq * HD; idx += 256) {
         const int q = idx / HD, d = idx - q * HD;
         const float* p = base + (long)q * (HD + 2);
-        float m = -1e30f;
+        float m = ATTN_M_FLOOR;
         for (int i = 0; i < n_split; ++i) m = fmaxf(m, p[(long)i * 32 * (HD + 2)]);
         float l = 0.0f, acc = 0.0f;
         for (int i = 0; i < n_split; ++i) {
@@ -262,7 +177,7 @@ static int attention_cross_steps(const void* q, const void* k, const void* v, vo
     const f16 *qp = reinterpret_cast<const f16*>(q), *kp = reinterpret_cast<const f16*>(k), *vp = reinterpret_cast<const f16*>(v);
     f16* op = reinterpret_cast<f16*>(out);
     float* pp = reinterpret_cast<float*>(partial);
-    const float qs = scale * CX_LOG2E;
+    const float qs = scale * ATTN_LOG2E;
     if (head_dim == 16) launch_cross<16>(qp, kp, vp, op, pp, B, H, Tq, Tk, qs, steps, as_stream(stream));
     else if (head_dim == 32) launch_cross<32>(qp, kp, vp, op, pp, B, H, Tq, Tk, qs, steps, as_stream(stream));
     else launch_cross<64>(qp, kp, vp, op, pp, B, H, Tq, Tk, qs, steps, as_stream(stream));

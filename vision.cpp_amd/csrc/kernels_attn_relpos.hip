@@ -4,9 +4,8 @@
 // over the T = gw * gh tokens of a grid in row-major order, the bias from the UNSCALED q. Nothing of size T x T exists outside registers.
 //
 // q, k, v f16 [B][T][H][64] -- token-major rows of H * 64, where the graph has them; rel_h f16 [2 gh - 1][64], rel_w f16 [2 gw - 1][64], shared by all heads;
-// out f16 [B][T][H * 64]. The orientation is that of kernels_attn_cross.hip: one block = NW wave64 = 32 NW queries of one (batch, head), S^T = K Q^T on
-// v_mfma_f32_32x32x16_f16, so a lane owns ONE query column r = lane & 31 and 16 keys of a 32-key block (key = 8 (e >> 2) + 4 (lane >> 5) + (e & 3)); online
-// softmax in the exp2 domain with the finite running-maximum floor; P^T feeds O^T = V^T P^T from the accumulators, V^T through ds_read_b64_tr_b16.
+// out f16 [B][T][H * 64]. The 32-key block step -- orientation, accumulator layout, LDS tile, online softmax -- is vx_attn_tile.h's: a lane owns ONE query
+// column r = lane & 31 and the 16 keys attn_key_of(e, h) of a 32-key block.
 //
 // The bias. It is the sum of a part that depends on (query, key ROW) and a part that depends on (query, key COLUMN): per query only gh + gw numbers, not T.
 // Before the key loop every wave makes them for its 32 queries with the matrix cores and keeps them in its own slice of LDS:
@@ -22,24 +21,16 @@
 //   aligned   gw == 64 (the global layers of a 1024^2 image, 64 x 64): a 32-key block is half a grid row. ky is the same for the whole block: ONE LDS read per
 //             lane per block. kx is 32 (block & 1) + the lane's 16 offsets: the RW part is loop-invariant, read out of LDS once into 2 x 16 registers in the
 //             accumulator's own layout; the loop is unrolled by the two phases so the register file is indexed statically.
-// K / V staging is the cross kernel's: 32-key blocks through registers into one swizzled LDS tile, the next block's global loads in flight under the MFMAs.
 // No atomics, no workspace; the same bits on every run.
 #include "vx_common.h"
+#include "vx_attn_tile.h"
 
 #include <type_traits>
 
 namespace {
 
-constexpr float RP_LOG2E = 1.44269504088896340736f;
 constexpr int RP_HD = 64;
-constexpr int RP_ROW = RP_HD * 2;      // bytes per K / V row in LDS
-constexpr int RP_TILE = 32 * RP_ROW;   // bytes of one 32-key K (or V) tile
-
-typedef __fp16 hv4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-__device__ __forceinline__ int rp_k_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-__device__ __forceinline__ int rp_v_swz(int row, int chunk) { return chunk ^ (((row >> 1) & 1) << 2); }
-__device__ __forceinline__ int rp_key_of(int e, int h) { return 8 * (e >> 2) + 4 * h + (e & 3); } // accumulator element e of half h -> key (table row) within a 32-block
+constexpr int RP_TILE = attn_tile<RP_HD>::BYTES; // one 32-key K (or V) tile
 
 __host__ __device__ constexpr int rp_stride(int g) { return g | 1; } // floats per query row of a bias table in LDS: odd, so rows land in different banks
 
@@ -47,11 +38,8 @@ template <bool ALIGNED, int NW>
 __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __restrict__ Q, const f16* __restrict__ K, const f16* __restrict__ V,
                                                                    const f16* __restrict__ RelH, const f16* __restrict__ RelW, f16* __restrict__ O, int H, int gw,
                                                                    int gh, float qs) {
-    constexpr int CH = RP_HD / 8;          // 16-byte chunks per row
-    constexpr int N_CH = 32 * CH;          // chunks per 32-key block
-    constexpr int THREADS = 64 * NW;
-    constexpr int PER = N_CH / THREADS;    // 4, 2, 1
-    constexpr int DS = RP_HD / 16;         // d-steps of a product with Q
+    using G = attn_tile<RP_HD>;
+    constexpr int DS = G::DS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const sk = smem;
     unsigned char* const sv = smem + RP_TILE;
@@ -99,8 +87,8 @@ __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __
                     d = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(rel + row * RP_HD + 16 * s + 8 * h), qf[s], d, 0, 0, 0);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int kk = pos + g - 1 - (j0 + rp_key_of(e, h)); // >= 0 implies the table row exists
-                    if (kk >= 0 && kk < g) dst[kk] = d[e] * RP_LOG2E;
+                    const int kk = pos + g - 1 - (j0 + attn_key_of(e, h)); // >= 0 implies the table row exists
+                    if (kk >= 0 && kk < g) dst[kk] = d[e] * ATTN_LOG2E;
                 }
             }
         }
@@ -108,46 +96,22 @@ __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) rw_reg[ph][e] = rw_row[32 * ph + rp_key_of(e, h)];
+                for (int e = 0; e < 16; ++e) rw_reg[ph][e] = rw_row[32 * ph + attn_key_of(e, h)];
         }
     }
 
-    // ---- staging: chunk cid = tid + i * THREADS of the block is row cid / CH, 16-byte chunk cid % CH
-    f16x8 kreg[PER], vreg[PER];
-    auto load_block = [&](int k0) {
+    f16x8 kreg[attn_stage<RP_HD, NW>::PER], vreg[attn_stage<RP_HD, NW>::PER];
+    // loop-invariant LDS offsets: K fragment of d-step s = row r, chunk 2 s + h; V^T transposed reads of O^T block db, k-step 0 (vx_attn_tile.h)
+    int k_off[G::DS], v_off[G::DB];
 #pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int cid = tid + i * THREADS, row = cid / CH, c = cid - row * CH, key = k0 + row;
-            f16x8 z = {(f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0, (f16)0};
-            kreg[i] = z;
-            vreg[i] = z;
-            if (key < T) {
-                kreg[i] = *reinterpret_cast<const f16x8*>(Kb + (long)key * ld + c * 8);
-                vreg[i] = *reinterpret_cast<const f16x8*>(Vb + (long)key * ld + c * 8);
-            }
-        }
-    };
-    auto store_block = [&]() {
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int cid = tid + i * THREADS, row = cid / CH, c = cid - row * CH;
-            *reinterpret_cast<f16x8*>(sk + row * RP_ROW + rp_k_swz(row, c) * 16) = kreg[i];
-            *reinterpret_cast<f16x8*>(sv + row * RP_ROW + rp_v_swz(row, c) * 16) = vreg[i];
-        }
-    };
-
-    // loop-invariant LDS offsets: K fragment of d-step s = row r, chunk 2 s + h; V^T transposed reads as in kernels_attn_cross.hip
-    int k_off[DS], v_off[2];
-#pragma unroll
-    for (int s = 0; s < DS; ++s) k_off[s] = r * RP_ROW + rp_k_swz(r, 2 * s + h) * 16;
+    for (int s = 0; s < G::DS; ++s) k_off[s] = r * G::ROW + attn_k_swz<RP_HD>(r, 2 * s + h) * 16;
     {
         const int key = 4 * h + ((lane & 15) >> 2), dd = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
 #pragma unroll
-        for (int db = 0; db < 2; ++db) v_off[db] = key * RP_ROW + rp_v_swz(key, (dd + 32 * db) >> 3) * 16 + (dd & 7) * 2;
+        for (int db = 0; db < G::DB; ++db) v_off[db] = key * G::ROW + attn_v_swz<RP_HD>(key, (dd + 32 * db) >> 3) * 16 + (dd & 7) * 2;
     }
-
-    f32x16 o[2] = {zero, zero};
-    float m_run = -1e30f, l_run = 0.0f; // finite floor: a block that is all -inf while nothing has been seen gives exp2(-inf + 1e30) = 0, never NaN
+    f32x16 o[G::DB] = {zero, zero};
+    float m_run = ATTN_M_FLOOR, l_run = 0.0f;
     const float inv_gw = 1.0f / (float)gw;
 
     // one 32-key block: stage, scores, bias, online softmax, PV. PH: the half-row phase (ALIGNED; 0 otherwise)
@@ -155,21 +119,16 @@ __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __
     auto step = [&](int kb, auto phase) {
         constexpr int PH = decltype(phase)::value;
         const int k0 = kb * 32;
-        __syncthreads(); // every wave is done with block kb - 1
-        store_block();
-        __syncthreads();
-        if (kb + 1 < n_blocks) load_block(k0 + 32);
+        attn_kv_store_sync<RP_HD, NW>(tid, kreg, vreg, sk, sv);
+        if (kb + 1 < n_blocks) attn_kv_load<RP_HD, NW>(tid, kreg, vreg, Kb, Vb, ld, k0 + 32, T);
         if (!active) return;
 
-        f32x16 s = zero;
-#pragma unroll
-        for (int st = 0; st < DS; ++st) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(sk + k_off[st]), qf[st], s, 0, 0, 0);
-
+        f32x16 s = attn_scores<RP_HD>(sk, k_off, qf);
         float mloc = -INFINITY;
         const float rh_blk = ALIGNED ? rh_row[kb >> 1] : 0.0f; // ALIGNED: the block lies in grid row kb / 2
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int key = k0 + rp_key_of(e, h);
+            const int key = k0 + attn_key_of(e, h);
             float bias;
             if (ALIGNED) bias = rh_blk + rw_reg[PH][e];
             else {
@@ -181,42 +140,10 @@ __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __
             s[e] = v;
             mloc = fmaxf(mloc, v);
         }
-        mloc = fmaxf(mloc, other_half(mloc)); // lanes l and l + 32 own the same query
-        const float m_new = fmaxf(m_run, mloc);
-        if (__any(m_new > m_run)) {
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-            m_run = m_new;
-        }
-        float psum = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float p = __builtin_amdgcn_exp2f(s[e] - m_run);
-            s[e] = p;
-            psum += p;
-        }
-        l_run += psum;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { // element j of the k-step <-> key k0 + 16 ks + 8 (j >> 2) + 4 h + (j & 3)
-            f16x8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = (f16)s[8 * ks + j];
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const unsigned char* vrow = sv + v_off[db] + ks * 16 * RP_ROW;
-                hv4 va = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hv4*)(vrow));
-                hv4 vb = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) hv4*)(vrow + 8 * RP_ROW));
-                f16x8 vf = {(f16)va[0], (f16)va[1], (f16)va[2], (f16)va[3], (f16)vb[0], (f16)vb[1], (f16)vb[2], (f16)vb[3]};
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[db], 0, 0, 0);
-            }
-        }
+        attn_softmax_pv<RP_HD>(s, mloc, m_run, l_run, o, sv, v_off);
     };
 
-    load_block(0);
+    attn_kv_load<RP_HD, NW>(tid, kreg, vreg, Kb, Vb, ld, 0, T);
     if (ALIGNED) { // T = 64 gh: an even number of blocks
         for (int kb = 0; kb < n_blocks; kb += 2) {
             step(kb, std::integral_constant<int, 0>{});
@@ -228,11 +155,11 @@ __global__ __launch_bounds__(64 * NW) void attention_relpos_kernel(const f16* __
 
     if (!active || q >= T) return;
     const float inv = 1.0f / (l_run + other_half(l_run));
-    f16* orow = O + ((long)b * T + q) * ld + head * RP_HD; // accumulator rows d = 32 db + 8 g + 4 h + j
+    f16* orow = O + ((long)b * T + q) * ld + head * RP_HD;
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < G::DB; ++db)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < G::G_OUT; ++g) { // accumulator rows d = 32 db + 8 g + 4 h + j
             f16x4 v;
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = (f16)(o[db][g * 4 + j] * inv);
@@ -269,7 +196,7 @@ extern "C" int vx_attention_relpos_f16(const void* q, const void* k, const void*
     const f16 *qp = reinterpret_cast<const f16*>(q), *kp = reinterpret_cast<const f16*>(k), *vp = reinterpret_cast<const f16*>(v);
     const f16 *hp = reinterpret_cast<const f16*>(rel_h), *wp = reinterpret_cast<const f16*>(rel_w);
     f16* op = reinterpret_cast<f16*>(out);
-    const float qs = scale * RP_LOG2E;
+    const float qs = scale * ATTN_LOG2E;
     hipStream_t s = as_stream(stream);
     int ok;
     if (vx_attention_relpos_aligned(gw, gh)) ok = launch_relpos<true, 4>(qp, kp, vp, hp, wp, op, B, H, gw, gh, qs, s); // T >= 64: gh == 1 has two query tiles
