@@ -234,6 +234,55 @@ inline mask_rle image_rle_encode(image_view const& mask) {
     detail::check(visp_image_rle_encode_host(packed.data(), 1, mask.extent[0], mask.extent[1], offsets, &runs, &owner.data, nullptr));
     return mask_rle{mask.extent, std::vector<uint32_t>(runs, runs + offsets[1])};
 }
+namespace detail {
+// records of one extent as the CSR rows of the C entries
+struct rle_rows {
+    std::vector<int64_t> offsets{0};
+    std::vector<uint32_t> runs;
+    i32x2 size{0, 0};
+    explicit rle_rows(std::span<mask_rle const> rles) {
+        if (rles.empty()) throw exception("mask_rle: expected at least one record");
+        size = rles[0].size;
+        for (mask_rle const& r : rles) {
+            if (r.size[0] != size[0] || r.size[1] != size[1]) throw exception("mask_rle: the records differ in size");
+            runs.insert(runs.end(), r.counts.begin(), r.counts.end());
+            offsets.push_back(int64_t(runs.size()));
+        }
+        runs.push_back(0); // an address also without runs
+    }
+};
+} // namespace detail
+// the way back on the device, pycocotools' decode: one alpha_u8 image per record (0 / value); records whose counts do not sum to width * height are refused
+inline std::vector<image_data> image_rle_decode(std::span<mask_rle const> rles, uint8_t value = 255) {
+    detail::rle_rows rows(rles);
+    const size_t px = size_t(rows.size[0]) * size_t(rows.size[1]);
+    std::vector<uint8_t> masks(rles.size() * px);
+    detail::check(visp_image_rle_decode_host(rows.offsets.data(), rows.runs.data(), int32_t(rles.size()), rows.size[0], rows.size[1], value, masks.data(), nullptr));
+    std::vector<image_data> out;
+    for (size_t k = 0; k < rles.size(); ++k) {
+        out.push_back(image_alloc(rows.size, image_format::alpha_u8));
+        std::memcpy(out.back().data.get(), masks.data() + k * px, px);
+    }
+    return out;
+}
+inline image_data image_rle_decode(mask_rle const& rle, uint8_t value = 255) { return std::move(image_rle_decode(std::span<mask_rle const>(&rle, 1), value)[0]); }
+// pycocotools' area: the foreground pixels of each record
+inline std::vector<int64_t> mask_rle_area(std::span<mask_rle const> rles) {
+    detail::rle_rows rows(rles);
+    std::vector<int64_t> area(rles.size());
+    detail::check(visp_image_rle_area_host(rows.offsets.data(), rows.runs.data(), int32_t(rles.size()), area.data()));
+    return area;
+}
+// pycocotools' iou on the device: row-major [a.size()][b.size()], intersection over union, or over the area of a's mask where iscrowd[j] is set
+inline std::vector<float> mask_rle_iou(std::span<mask_rle const> a, std::span<mask_rle const> b, std::span<bool const> iscrowd = {}) {
+    detail::rle_rows ra(a), rb(b);
+    if (!iscrowd.empty() && iscrowd.size() != b.size()) throw exception("mask_rle_iou: one iscrowd flag per record of b");
+    std::vector<uint8_t> crowd(iscrowd.begin(), iscrowd.end());
+    std::vector<float> iou(a.size() * b.size());
+    detail::check(visp_image_mask_iou_host(nullptr, ra.runs.data(), ra.offsets.data(), int32_t(a.size()), ra.size[0], ra.size[1], nullptr, rb.runs.data(), rb.offsets.data(),
+                                           int32_t(b.size()), rb.size[0], rb.size[1], crowd.empty() ? nullptr : crowd.data(), iou.data(), nullptr, nullptr));
+    return iou;
+}
 // image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
 inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
     visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};

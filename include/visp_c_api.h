@@ -453,6 +453,31 @@ VISP_API int32_t visp_image_rle_encode_device(void const* masks_u8_dev, int32_t 
 VISP_API void visp_rle_destroy(visp_rle_data* rle);
 VISP_API int32_t visp_image_rle_encode_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32,
                                             visp_rle_data** out_data, visp_device const* dev);
+/* The way back, on the device: n RLE records of one extent w x h -> u8 masks [n][h][w], row-major, foreground bytes `value` (1 .. 255), background 0. The records
+ * are CSR rows as the encoder writes them: mask b's runs are runs[offsets[b] .. offsets[b + 1]), offsets i64 [n + 1], alternating from background in the order
+ * p = x * h + y. status i32 [n] (nullable): 0 = the runs sum to w h; 1 = short, pixels behind the last run are background; 2 = long, runs and parts of runs
+ * behind w h are ignored. area i64 [n] (nullable): the foreground pixels written. counts (nullable): a device i32, masks at and behind counts[0] are skipped and
+ * their masks, status and area left as they were, so the call chains behind a generate call. n is 1 .. 65535. All pointers but dev are DEVICE pointers; stream, dev
+ * and the workspace (bit words and run positions, allocated per CALL) as for visp_image_rle_encode_device. The offsets are read back (n + 1 values) and held to
+ * be non-decreasing before the first launch. */
+VISP_API int32_t visp_image_rle_decode_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, int32_t value,
+                                              void* masks_u8_dev, void* status_i32_dev, void* area_i64_dev, void* stream, visp_device const* dev);
+/* the same on host arrays: up, decode, the masks down. A row whose runs do not sum to w h is refused before any launch; the message names the row and its sum. Blocks. */
+VISP_API int32_t visp_image_rle_decode_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int32_t w, int32_t h, int32_t value, uint8_t* masks_u8,
+                                            visp_device const* dev);
+/* area_i64 [n]: the sum of each row's odd runs (pycocotools' area). Host code: one pass over runs that are on the host already. */
+VISP_API int32_t visp_image_rle_area_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* area_i64);
+/* The pairwise IoU of na masks against nb masks of one extent (pycocotools' iou): iou f32 [na][nb] = inter / (area_a + area_b - inter), or inter / area_a where
+ * iscrowd[j] (u8 [nb], nullable) is non-zero; 0 where the denominator is 0. inter i32 [na][nb] (nullable): the pixels both masks have. Each side is EITHER u8
+ * masks [n][h][w] (non-zero = foreground) OR runs with offsets as above, the other form's pointers NULL; both sides have the same extent. Both become bit words
+ * on the device (1/8 byte per pixel), na and nb are 1 .. 65535. Pointers, stream, dev and workspace as for visp_image_rle_decode_device. */
+VISP_API int32_t visp_image_mask_iou_device(void const* a_masks_u8_dev, void const* a_runs_u32_dev, void const* a_offsets_i64_dev, int32_t na, int32_t wa, int32_t ha,
+                                            void const* b_masks_u8_dev, void const* b_runs_u32_dev, void const* b_offsets_i64_dev, int32_t nb, int32_t wb, int32_t hb,
+                                            void const* iscrowd_u8_dev, void* iou_f32_dev, void* inter_i32_dev, void* stream, visp_device const* dev);
+/* the same on host arrays; rows of runs are held to their sum w h before any launch. Blocks. */
+VISP_API int32_t visp_image_mask_iou_host(uint8_t const* a_masks_u8, uint32_t const* a_runs_u32, int64_t const* a_offsets_i64, int32_t na, int32_t wa, int32_t ha,
+                                          uint8_t const* b_masks_u8, uint32_t const* b_runs_u32, int64_t const* b_offsets_i64, int32_t nb, int32_t wb, int32_t hb,
+                                          uint8_t const* iscrowd_u8, float* iou_f32, int32_t* inter_i32, visp_device const* dev);
 /* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
  * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
 VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,

@@ -459,6 +459,32 @@ VX_API int vx_mask_rle_u8(const uint8_t* masks, int w, int h, int n, const int32
  * (from the n_runs of a count-only call, the packed rows are CSR and hold nothing but runs). n_runs as above. */
 VX_API int vx_mask_rle_packed_u8(const uint8_t* masks, int w, int h, int n, const int64_t* offsets, uint32_t* runs, int32_t* n_runs, void* workspace,
                                  size_t workspace_bytes, int group, void* stream);
+/* ---- RLE back to masks, and masks as bit words (kernels_rle_decode.hip) ----
+ * The bit-word form of a mask of w x h (the extents of the encoder above): one 64-bit word per (column x, 64-row segment s) at x * S + s, S = ceil(h / 64); bit r
+ * is pixel (64 s + r, x); bits at and behind row h are zero. Mask b's words start vx_mask_rle_workspace_bytes(w, h, 1) bytes behind mask b - 1's; `words` is
+ * 8-byte aligned. counts (nullable): a device i32; mask m of the call is skipped, nothing of it read or written, when first + m >= counts[0] (first: the index
+ * of the call's mask 0 in the caller's batch). n is 1 .. 65535. Integers only, no atomics: the same bytes on every run.
+ *
+ * vx_rle_to_bits: CSR rows as vx_mask_rle_packed_u8 writes them -- mask b's runs at runs + offsets[b], offsets[b + 1] - offsets[b] of them, alternating from
+ * background in the order p = x * h + y; offsets a device i64 [n + 1], non-decreasing, offsets[n] - offsets[0] == total_runs (a row outside that range is treated
+ * as empty). area i64 [n] (nullable): the foreground pixels, the odd runs each cut at h w. status i32 [n] (nullable): 0 = the runs sum to h w, 1 = short
+ * (pixels behind the last run are background), 2 = long (runs and parts of runs behind h w are ignored). workspace: vx_rle_to_bits_workspace_bytes(total_runs, n)
+ * bytes, 16-byte aligned (the run start positions as i32; 0 for arguments the launcher refuses). Two launches. */
+VX_API size_t vx_rle_to_bits_workspace_bytes(int64_t total_runs, int n);
+VX_API int vx_rle_to_bits(const uint32_t* runs, const int64_t* offsets, int64_t total_runs, int n, int w, int h, const int32_t* counts, int first, void* words,
+                          int64_t* area, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* words -> u8 masks [n][h][w], row-major: foreground bytes are `value` (1 .. 255), background 0; every byte of a mask that is not skipped is written exactly
+ * once. 16-byte aligned masks with w a multiple of 16 leave as 16-byte stores, anything else byte by byte. One launch. */
+VX_API int vx_bits_to_mask_u8(const void* words, int n, int w, int h, const int32_t* counts, int first, int value, uint8_t* masks, void* stream);
+/* u8 masks [n][h][w] (non-zero = foreground) -> words; words of columns and segments the mask has are all written, nothing else is. One launch. */
+VX_API int vx_mask_to_bits_u8(const uint8_t* masks, int n, int w, int h, const int32_t* counts, int first, void* words, void* stream);
+/* The pairwise matrix of na masks against nb masks of one extent, both in words: inter i32 [na][nb] (nullable) = the pixels both have; iou f32 [na][nb] =
+ * (float)inter / (float)den, den = area_a + area_b - inter, or area_a where iscrowd[j] (u8 [nb], nullable) is non-zero -- COCO's rule; 0 where den is 0.
+ * counts_a / counts_b (nullable): rows at and behind counts_a[0], columns at and behind counts_b[0] are neither read nor written.
+ * workspace: vx_bitmask_iou_workspace_bytes(na, nb) bytes, 16-byte aligned (the areas). Three launches. */
+VX_API size_t vx_bitmask_iou_workspace_bytes(int na, int nb);
+VX_API int vx_bitmask_iou(const void* a_words, int na, const void* b_words, int nb, int w, int h, const int32_t* counts_a, const int32_t* counts_b,
+                          const uint8_t* iscrowd, int32_t* inter, float* iou, void* workspace, size_t workspace_bytes, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -1072,7 +1072,38 @@ int32_t visp_image_rle_encode_host(uint8_t const* masks_u8, int32_t n, int32_t w
     });
 }
 
-int32_t visp_image_erosion(visp_device const* dev, visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data) {
+int32_t visp_image_rle_decode_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, int32_t value,
+                                     void* masks_u8_dev, void* status_i32_dev, void* area_i64_dev, void* stream, visp_device const* dev) {
+    return handle_errors([&]() { rle_decode_device(dev, runs_u32_dev, offsets_i64_dev, n, w, h, counts_dev, value, masks_u8_dev, status_i32_dev, area_i64_dev, stream); });
+}
+
+int32_t visp_image_rle_decode_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int32_t w, int32_t h, int32_t value, uint8_t* masks_u8,
+                                   visp_device const* dev) {
+    return handle_errors([&]() { rle_decode_host(dev, offsets_i64, runs_u32, n, w, h, value, masks_u8); });
+}
+
+int32_t visp_image_rle_area_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* area_i64) {
+    return handle_errors([&]() { rle_area_host(offsets_i64, runs_u32, n, area_i64); });
+}
+
+int32_t visp_image_mask_iou_device(void const* a_masks_u8_dev, void const* a_runs_u32_dev, void const* a_offsets_i64_dev, int32_t na, int32_t wa, int32_t ha,
+                                   void const* b_masks_u8_dev, void const* b_runs_u32_dev, void const* b_offsets_i64_dev, int32_t nb, int32_t wb, int32_t hb,
+                                   void const* iscrowd_u8_dev, void* iou_f32_dev, void* inter_i32_dev, void* stream, visp_device const* dev) {
+    return handle_errors([&]() {
+        mask_iou_device(dev, {a_masks_u8_dev, a_runs_u32_dev, a_offsets_i64_dev, na, wa, ha}, {b_masks_u8_dev, b_runs_u32_dev, b_offsets_i64_dev, nb, wb, hb}, iscrowd_u8_dev,
+                        iou_f32_dev, inter_i32_dev, stream);
+    });
+}
+
+int32_t visp_image_mask_iou_host(uint8_t const* a_masks_u8, uint32_t const* a_runs_u32, int64_t const* a_offsets_i64, int32_t na, int32_t wa, int32_t ha,
+                                 uint8_t const* b_masks_u8, uint32_t const* b_runs_u32, int64_t const* b_offsets_i64, int32_t nb, int32_t wb, int32_t hb,
+                                 uint8_t const* iscrowd_u8, float* iou_f32, int32_t* inter_i32, visp_device const* dev) {
+    return handle_errors([&]() {
+        mask_iou_host(dev, {a_masks_u8, a_runs_u32, a_offsets_i64, na, wa, ha}, {b_masks_u8, b_runs_u32, b_offsets_i64, nb, wb, hb}, iscrowd_u8, iou_f32, inter_i32);
+    });
+}
+
+int32_t visp_image_erosion(visp_device const* dev,visp_image_view const* src, int32_t radius, visp_image_view* out_image, visp_image_data** out_data) {
     return handle_errors([&]() {
         if (!out_image || !out_data) throw except("visp_image_erosion: null argument");
         return_image(image_erosion(dev, host_view("visp_image_erosion", src), radius), out_image, out_data);

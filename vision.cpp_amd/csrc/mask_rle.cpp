@@ -100,4 +100,173 @@ std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* p
     return runs;
 }
 
+// ---- the way back: decode, area, IoU ----
+
+namespace {
+
+// the offsets of n device rows on the host, held to be non-decreasing before anything is launched on them
+std::vector<int64_t> read_offsets(char const* who, void const* offsets_dev, int n, void* s) {
+    std::vector<int64_t> off((size_t)n + 1);
+    VX(vx_memcpy_d2h(off.data(), offsets_dev, off.size() * 8, s));
+    VX(vx_stream_sync(s));
+    for (int b = 0; b < n; ++b)
+        if (off[(size_t)b + 1] < off[(size_t)b]) throw except("%s: offsets decrease at row %d (%lld then %lld)", who, b, (long long)off[(size_t)b], (long long)off[(size_t)b + 1]);
+    return off;
+}
+
+void decode_on(uint32_t const* runs_dev, int64_t const* offsets_dev, std::vector<int64_t> const& off, int n, int w, int h, int32_t const* counts_dev, int value,
+               uint8_t* masks_dev, int32_t* status_dev, int64_t* area_dev, void* s) {
+    const int group = std::min(n, kRleGroup);
+    int64_t most = 0; // runs of the largest group
+    for (int b0 = 0; b0 < n; b0 += group) most = std::max(most, off[(size_t)std::min(n, b0 + group)] - off[(size_t)b0]);
+    const size_t pos_bytes = vx_rle_to_bits_workspace_bytes(most, group);
+    device_buffer words((size_t)group * vx_mask_rle_workspace_bytes(w, h, 1)), pos(pos_bytes);
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int g = std::min(group, n - b0);
+        VX(vx_rle_to_bits(runs_dev, offsets_dev + b0, off[(size_t)b0 + g] - off[(size_t)b0], g, w, h, counts_dev, b0, words.ptr, area_dev ? area_dev + b0 : nullptr,
+                          status_dev ? status_dev + b0 : nullptr, pos.ptr, pos_bytes, s));
+        VX(vx_bits_to_mask_u8(words.ptr, g, w, h, counts_dev, b0, value, masks_dev + (size_t)b0 * w * h, s));
+    }
+    VX(vx_stream_sync(s));
+}
+
+// a host array on the device (at least 16 bytes, so that an empty one still has an address)
+device_buffer uploaded(void const* host, size_t bytes, void* s) {
+    device_buffer d(std::max<size_t>(bytes, 16));
+    if (bytes) VX(vx_memcpy_h2d(d.ptr, host, bytes, s));
+    return d;
+}
+
+// one side of an IoU call, on the device, as bit words
+device_buffer words_of(char const* who, mask_set const& d, void* s) {
+    device_buffer words((size_t)d.n * vx_mask_rle_workspace_bytes(d.w, d.h, 1));
+    if (d.masks) {
+        VX(vx_mask_to_bits_u8(static_cast<uint8_t const*>(d.masks), d.n, d.w, d.h, nullptr, 0, words.ptr, s));
+        return words;
+    }
+    const std::vector<int64_t> off = read_offsets(who, d.offsets, d.n, s);
+    const int64_t total = off.back() - off.front();
+    const size_t pos_bytes = vx_rle_to_bits_workspace_bytes(total, d.n);
+    device_buffer pos(pos_bytes);
+    VX(vx_rle_to_bits(static_cast<uint32_t const*>(d.runs), static_cast<int64_t const*>(d.offsets), total, d.n, d.w, d.h, nullptr, 0, words.ptr, nullptr, nullptr, pos.ptr,
+                      pos_bytes, s));
+    VX(vx_stream_sync(s)); // the positions are freed behind this
+    return words;
+}
+
+void iou_on(mask_set const& a, mask_set const& b, void const* iscrowd_dev, void* iou_dev, void* inter_dev, void* s) {
+    device_buffer wa = words_of("mask_iou", a, s), wb = words_of("mask_iou", b, s);
+    const size_t bytes = vx_bitmask_iou_workspace_bytes(a.n, b.n);
+    device_buffer areas(bytes);
+    VX(vx_bitmask_iou(wa.ptr, a.n, wb.ptr, b.n, a.w, a.h, nullptr, nullptr, static_cast<uint8_t const*>(iscrowd_dev), static_cast<int32_t*>(inter_dev),
+                      static_cast<float*>(iou_dev), areas.ptr, bytes, s));
+    VX(vx_stream_sync(s));
+}
+
+// a host side of an IoU call moved to the device; `keep` owns what was uploaded
+mask_set side_uploaded(mask_set const& d, std::vector<device_buffer>& keep, void* s) {
+    mask_set out = d;
+    if (d.masks) {
+        keep.push_back(uploaded(d.masks, (size_t)d.n * d.w * d.h, s));
+        out.masks = keep.back().ptr;
+        return out;
+    }
+    int64_t const* off = static_cast<int64_t const*>(d.offsets);
+    keep.push_back(uploaded(static_cast<uint32_t const*>(d.runs) + off[0], (size_t)(off[d.n] - off[0]) * 4, s));
+    out.runs = keep.back().ptr;
+    std::vector<int64_t> rel(off, off + d.n + 1);
+    for (int64_t& v : rel) v -= off[0];
+    keep.push_back(uploaded(rel.data(), rel.size() * 8, s));
+    VX(vx_stream_sync(s)); // rel leaves scope
+    out.offsets = keep.back().ptr;
+    return out;
+}
+
+} // namespace
+
+void check_rle_extent(char const* who, int n, int w, int h) {
+    if (n < 1 || n > 65535) throw except("%s: %d masks (1 .. 65535)", who, n);
+    if (w < 1 || h < 1 || (int64_t)w * h >= (int64_t(1) << 31) - 1) throw except("%s: extent %dx%d", who, w, h);
+}
+
+void check_rle_rows(char const* who, int64_t const* offsets, uint32_t const* runs, int n, int64_t hw) {
+    for (int b = 0; b < n; ++b) {
+        if (offsets[b + 1] < offsets[b] || offsets[b] < 0) throw except("%s: offsets decrease at row %d", who, b);
+        int64_t sum = 0;
+        for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) sum += runs[i];
+        if (hw >= 0 && sum != hw) throw except("%s: the runs of row %d sum to %lld, the extent has %lld pixels", who, b, (long long)sum, (long long)hw);
+    }
+}
+
+void rle_decode_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, int w, int h, void const* counts_dev, int value, void* masks_dev,
+                       void* status_dev, void* area_dev, void* stream) {
+    if (!runs_dev || !offsets_dev || !masks_dev) throw except("rle_decode: null pointer");
+    check_rle_extent("rle_decode", n, w, h);
+    if (value < 1 || value > 255) throw except("rle_decode: foreground value %d (1 .. 255)", value);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    decode_on(static_cast<uint32_t const*>(runs_dev), static_cast<int64_t const*>(offsets_dev), read_offsets("rle_decode", offsets_dev, n, s), n, w, h,
+              static_cast<int32_t const*>(counts_dev), value, static_cast<uint8_t*>(masks_dev), static_cast<int32_t*>(status_dev), static_cast<int64_t*>(area_dev), s);
+}
+
+void rle_decode_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int w, int h, int value, uint8_t* masks) {
+    if (!offsets || !runs || !masks) throw except("rle_decode: null pointer");
+    check_rle_extent("rle_decode", n, w, h);
+    if (value < 1 || value > 255) throw except("rle_decode: foreground value %d (1 .. 255)", value);
+    check_rle_rows("rle_decode", offsets, runs, n, (int64_t)w * h);
+    device_scope on(dev);
+    void* s = on.stream;
+    std::vector<int64_t> rel(offsets, offsets + n + 1);
+    for (int64_t& v : rel) v -= offsets[0];
+    device_buffer r = uploaded(runs + offsets[0], (size_t)rel.back() * 4, s), o = uploaded(rel.data(), rel.size() * 8, s);
+    const size_t bytes = (size_t)n * w * h;
+    device_buffer m(bytes);
+    decode_on(static_cast<uint32_t const*>(r.ptr), static_cast<int64_t const*>(o.ptr), rel, n, w, h, nullptr, value, static_cast<uint8_t*>(m.ptr), nullptr, nullptr, s);
+    VX(vx_memcpy_d2h(masks, m.ptr, bytes, s));
+    VX(vx_stream_sync(s));
+}
+
+void rle_area_host(int64_t const* offsets, uint32_t const* runs, int n, int64_t* area) {
+    if (!offsets || !runs || !area) throw except("rle_area: null pointer");
+    if (n < 1) throw except("rle_area: empty batch of rows (n = %d)", n);
+    check_rle_rows("rle_area", offsets, runs, n, -1);
+    for (int b = 0; b < n; ++b) {
+        area[b] = 0;
+        for (int64_t i = offsets[b] + 1; i < offsets[b + 1]; i += 2) area[b] += runs[i];
+    }
+}
+
+void check_mask_iou(char const* who, mask_set const& a, mask_set const& b) {
+    for (mask_set const* d : {&a, &b}) {
+        if (d->masks ? (d->runs || d->offsets) : (!d->runs || !d->offsets)) throw except("%s: each side is u8 masks, or runs with offsets: null pointer, or both forms", who);
+        check_rle_extent(who, d->n, d->w, d->h);
+    }
+    if (a.w != b.w || a.h != b.h) throw except("%s: the extents differ, %dx%d and %dx%d", who, a.w, a.h, b.w, b.h);
+}
+
+void mask_iou_device(backend_device const* dev, mask_set const& a, mask_set const& b, void const* iscrowd_dev, void* iou_dev, void* inter_dev, void* stream) {
+    check_mask_iou("mask_iou", a, b);
+    if (!iou_dev) throw except("mask_iou: null pointer");
+    device_scope on(dev);
+    iou_on(a, b, iscrowd_dev, iou_dev, inter_dev, stream ? stream : on.stream);
+}
+
+void mask_iou_host(backend_device const* dev, mask_set const& a, mask_set const& b, uint8_t const* iscrowd, float* iou, int32_t* inter) {
+    check_mask_iou("mask_iou", a, b);
+    if (!iou) throw except("mask_iou: null pointer");
+    for (mask_set const* d : {&a, &b})
+        if (!d->masks) check_rle_rows("mask_iou", static_cast<int64_t const*>(d->offsets), static_cast<uint32_t const*>(d->runs), d->n, (int64_t)d->w * d->h);
+    device_scope on(dev);
+    void* s = on.stream;
+    std::vector<device_buffer> keep;
+    const mask_set da = side_uploaded(a, keep, s), db = side_uploaded(b, keep, s);
+    const size_t pairs = (size_t)a.n * b.n;
+    device_buffer crowd, out(pairs * 4), out_inter(pairs * 4);
+    if (iscrowd) crowd = uploaded(iscrowd, (size_t)b.n, s);
+    iou_on(da, db, crowd.ptr, out.ptr, out_inter.ptr, s);
+    VX(vx_memcpy_d2h(iou, out.ptr, pairs * 4, s));
+    if (inter) VX(vx_memcpy_d2h(inter, out_inter.ptr, pairs * 4, s));
+    VX(vx_stream_sync(s));
+}
+
 } // namespace visp

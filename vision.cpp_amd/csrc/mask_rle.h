@@ -21,4 +21,31 @@ std::vector<uint32_t> rle_encode_host(backend_device const* dev, uint8_t const* 
 std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
                                                   float* info_f32, int32_t* counts, int64_t* offsets);
 
+
+// ---- the way back (kernels_rle_decode.hip): decode, area and pairwise IoU of CSR rows of runs ----
+void check_rle_extent(char const* who, int n, int w, int h); // throws, touches no device
+// host CSR rows: offsets non-decreasing from 0 .. ; with hw >= 0 every row sums to exactly hw. Throws naming the row and its sum.
+void check_rle_rows(char const* who, int64_t const* offsets, uint32_t const* runs, int n, int64_t hw);
+// device runs u32 and offsets i64 [n + 1] -> device masks u8 [n, h, w] with foreground `value`; status i32 [n] and area i64 [n] nullable (vx_rle_to_bits);
+// counts_dev (nullable): only the first counts[0] masks. The offsets are read back and checked before the first launch; workspaces are allocated for the CALL,
+// at most 256 masks in flight through the bit words; returns with the work done.
+void rle_decode_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, int w, int h, void const* counts_dev, int value, void* masks_dev,
+                       void* status_dev, void* area_dev, void* stream);
+// host rows -> host masks; a row whose runs do not sum to h w is refused before any launch
+void rle_decode_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int w, int h, int value, uint8_t* masks);
+// area[b] = the sum of row b's odd runs. Host code: the runs are on the host and the sum is one pass over them.
+void rle_area_host(int64_t const* offsets, uint32_t const* runs, int n, int64_t* area);
+// One side of an IoU call: u8 masks [n, h, w], or CSR rows (runs, offsets [n + 1]) -- exactly one of the two.
+struct mask_set {
+    void const* masks = nullptr;
+    void const* runs = nullptr;
+    void const* offsets = nullptr;
+    int n = 0, w = 0, h = 0;
+};
+void check_mask_iou(char const* who, mask_set const& a, mask_set const& b); // throws, touches no device
+// iou f32 [na, nb], inter i32 [na, nb] (nullable), iscrowd u8 [nb] (nullable): vx_bitmask_iou on both sides' bit words. All pointers on the device.
+void mask_iou_device(backend_device const* dev, mask_set const& a, mask_set const& b, void const* iscrowd_dev, void* iou_dev, void* inter_dev, void* stream);
+// the same on host arrays: up, the matrix, down; rows of runs are held to their sum h w before any launch
+void mask_iou_host(backend_device const* dev, mask_set const& a, mask_set const& b, uint8_t const* iscrowd, float* iou, int32_t* inter);
+
 } // namespace visp

@@ -749,6 +749,79 @@ def rle_to_mask(rle: dict) -> np.ndarray:
     return flat.reshape(w, h).T
 
 
+def _rle_rows(rles) -> tuple:
+    """RLE dicts of one extent -> (offsets i64 [n + 1], runs u32, w, h): the CSR rows of the C entries"""
+    if not rles:
+        raise ValueError("expected at least one RLE record")
+    h, w = (int(v) for v in rles[0]["size"])
+    if any([int(v) for v in r["size"]] != [h, w] for r in rles):
+        raise ValueError(f"the records differ in size: expected [{h}, {w}] in all of them")
+    rows = [np.asarray(r["counts"], np.int64) for r in rles]
+    if any(c.size and (c.min() < 0 or c.max() >= 2 ** 32) for c in rows):
+        raise ValueError("counts must lie in 0 .. 2^32 - 1")
+    offsets = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([c.size for c in rows], out=offsets[1:])
+    runs = np.concatenate(rows).astype(np.uint32) if offsets[-1] else np.zeros(1, np.uint32)
+    return offsets, runs, w, h
+
+
+def rle_decode(rles, value: int = 1, device: Device | None = None) -> np.ndarray:
+    """pycocotools' decode on the device: the record dicts mask_to_rle and sam_generate_masks return ({"size": [h, w], "counts": [...]}, all of one size) ->
+    uint8 [n, h, w] with foreground bytes `value` ([h, w] for a single dict). A record whose counts do not sum to h * w is refused."""
+    single = isinstance(rles, dict)
+    offsets, runs, w, h = _rle_rows([rles] if single else list(rles))
+    out = np.empty((len(offsets) - 1, h, w), np.uint8)
+    check(lib.get_lib().visp_image_rle_decode_host(offsets.ctypes.data, runs.ctypes.data, len(offsets) - 1, w, h, int(value), out.ctypes.data, *_on(device)))
+    return out[0] if single else out
+
+
+def rle_decode_device(runs_dev: int, offsets_dev: int, n: int, w: int, h: int, masks_dev: int, value: int = 1, counts_dev: int | None = None, status_dev: int | None = None,
+                      area_dev: int | None = None, device: Device | None = None, stream: int | None = None):
+    """The same on device-resident rows (addresses): runs u32 and offsets i64 [n + 1] as the encoder's packed form -> masks u8 [n, h, w]; status i32 [n]
+    (0 exact, 1 short, 2 long) and area i64 [n] optional. counts_dev: a device i32, masks at and behind counts[0] are skipped. Returns with the work done."""
+    check(lib.get_lib().visp_image_rle_decode_device(runs_dev, offsets_dev, int(n), int(w), int(h), counts_dev, int(value), masks_dev, status_dev, area_dev, stream,
+                                                     *_on(device)))
+
+
+def rle_area(rles) -> np.ndarray:
+    """pycocotools' area: the foreground pixels of each record, int64 [n] (a scalar for a single dict). Host code."""
+    single = isinstance(rles, dict)
+    offsets, runs, _, _ = _rle_rows([rles] if single else list(rles))
+    area = np.zeros(len(offsets) - 1, np.int64)
+    check(lib.get_lib().visp_image_rle_area_host(offsets.ctypes.data, runs.ctypes.data, len(area), area.ctypes.data))
+    return int(area[0]) if single else area
+
+
+def mask_iou(a, b, iscrowd=None, device: Device | None = None, return_intersection: bool = False):
+    """pycocotools' iou on the device: a and b are each a list of record dicts or masks [n, h, w] (non-zero = foreground), all of one extent -> float32 [na, nb] =
+    intersection / union, or intersection / area of a where iscrowd[j] is set; 0 where that denominator is 0. return_intersection: also int32 [na, nb]."""
+    keep, sides = [], []
+    for s in (a, b):
+        if isinstance(s, np.ndarray):
+            m = np.ascontiguousarray(s if s.dtype == np.uint8 else s != 0, dtype=np.uint8)
+            if m.ndim != 3:
+                raise ValueError(f"expected masks [n, h, w], got shape {m.shape}")
+            keep.append(m)
+            sides.append((m.ctypes.data, None, None, m.shape[0], m.shape[2], m.shape[1]))
+        else:
+            offsets, runs, w, h = _rle_rows(list(s))
+            keep += [offsets, runs]
+            sides.append((None, runs.ctypes.data, offsets.ctypes.data, len(offsets) - 1, w, h))
+    na, nb = sides[0][3], sides[1][3]
+    crowd = None if iscrowd is None else np.ascontiguousarray(np.asarray(iscrowd) != 0, dtype=np.uint8)
+    if crowd is not None and crowd.shape != (nb,):
+        raise ValueError(f"iscrowd: expected {nb} flags, got shape {crowd.shape}")
+    iou, inter = np.empty((na, nb), np.float32), np.empty((na, nb), np.int32)
+    check(lib.get_lib().visp_image_mask_iou_host(*sides[0], *sides[1], None if crowd is None else crowd.ctypes.data, iou.ctypes.data, inter.ctypes.data, *_on(device)))
+    return (iou, inter) if return_intersection else iou
+
+
+def mask_iou_device(a: tuple, b: tuple, iou_dev: int, iscrowd_dev: int | None = None, inter_dev: int | None = None, device: Device | None = None, stream: int | None = None):
+    """The same on device-resident sides (addresses): each of a, b is (masks_dev, None, None, n, w, h) or (None, runs_dev, offsets_dev, n, w, h); iou f32 [na, nb],
+    inter i32 [na, nb] optional, iscrowd u8 [nb] optional. Returns with the work done."""
+    check(lib.get_lib().visp_image_mask_iou_device(*a, *b, iscrowd_dev, iou_dev, inter_dev, stream, *_on(device)))
+
+
 def image_estimate_foreground(image: np.ndarray, mask: np.ndarray, radius: int = 30, device: Device | None = None) -> np.ndarray:
     """image f32 [h, w, 4] (rgba_f32), mask f32 [h, w] -> f32 [h, w, 4]: foreground colours, alpha = mask (blur-fusion, two stages)."""
     return _image_op("visp_image_estimate_foreground", [_view_of(image, ImageFormat.rgba_f32), _view_of(mask, ImageFormat.alpha_f32)], int(radius), on=_on(device))
