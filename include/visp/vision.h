@@ -283,6 +283,47 @@ inline std::vector<float> mask_rle_iou(std::span<mask_rle const> a, std::span<ma
                                            int32_t(b.size()), rb.size[0], rb.size[1], crowd.empty() ? nullptr : crowd.data(), iou.data(), nullptr, nullptr));
     return iou;
 }
+// COCO's compressed counts strings on the device (pycocotools' rleToString / rleFrString): one string per record, the text of a COCO file's segmentation.counts
+inline std::vector<std::string> mask_rle_compress(std::span<mask_rle const> rles) {
+    detail::rle_rows rows(rles);
+    std::vector<int64_t> byte_offsets(rles.size() + 1);
+    uint8_t const* bytes = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_compress_host(rows.offsets.data(), rows.runs.data(), int32_t(rles.size()), byte_offsets.data(), &bytes, &owner.data, nullptr));
+    std::vector<std::string> out;
+    for (size_t k = 0; k < rles.size(); ++k) out.emplace_back(reinterpret_cast<char const*>(bytes) + byte_offsets[k], size_t(byte_offsets[k + 1] - byte_offsets[k]));
+    return out;
+}
+// the way back: strings of records of one size {width, height}; a malformed string is refused, the message names the record, the byte and the status
+inline std::vector<mask_rle> mask_rle_decompress(std::span<std::string const> strings, i32x2 size) {
+    if (strings.empty()) throw exception("mask_rle_decompress: expected at least one string");
+    std::vector<int64_t> byte_offsets{0}, offsets(strings.size() + 1);
+    std::string all;
+    for (std::string const& s : strings) {
+        all += s;
+        byte_offsets.push_back(int64_t(all.size()));
+    }
+    all.push_back('0'); // an address also without bytes
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_decompress_host(byte_offsets.data(), reinterpret_cast<uint8_t const*>(all.data()), int32_t(strings.size()), offsets.data(), &runs, &owner.data,
+                                                 nullptr));
+    std::vector<mask_rle> out;
+    for (size_t k = 0; k < strings.size(); ++k) out.push_back(mask_rle{size, std::vector<uint32_t>(runs + offsets[k], runs + offsets[k + 1])});
+    return out;
+}
+// image_rle_encode and mask_rle_compress in one call (pycocotools' encode): the runs never leave the device
+inline std::string image_rle_encode_compressed(image_view const& mask) {
+    if (mask.format != image_format::alpha_u8) throw exception("image_rle_encode_compressed: expected an alpha_u8 mask");
+    const size_t w = size_t(mask.extent[0]), h = size_t(mask.extent[1]);
+    std::vector<uint8_t> packed(w * h);
+    for (size_t y = 0; y < h; ++y) std::memcpy(packed.data() + y * w, static_cast<uint8_t const*>(mask.data) + y * size_t(mask.stride), w);
+    int64_t byte_offsets[2] = {0, 0};
+    uint8_t const* bytes = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_encode_compressed_host(packed.data(), 1, mask.extent[0], mask.extent[1], byte_offsets, &bytes, &owner.data, nullptr));
+    return std::string(reinterpret_cast<char const*>(bytes), size_t(byte_offsets[1]));
+}
 // image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
 inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
     visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};
@@ -718,10 +759,14 @@ struct sam_generate_params { // SAM's defaults
     // SAM's output_mode "uncompressed_rle": the masks are run-length encoded on the device behind the generate call and come as sam_mask::rle; no mask byte
     // is read back and sam_mask::segmentation stays empty
     bool output_rle = false;
+    // SAM's output_mode "coco_rle": the runs are further compressed on the device into COCO's counts string and come as sam_mask::coco_rle (with the extent in
+    // sam_mask::rle.size, its counts empty); neither a mask byte nor a run is read back. Takes precedence over output_rle.
+    bool output_coco_rle = false;
 };
 struct sam_mask {
     image_data segmentation;   // alpha_u8 at the encoded image's extent, 0 / 255
     mask_rle rle;              // with sam_generate_params::output_rle, in place of segmentation
+    std::string coco_rle;      // with sam_generate_params::output_coco_rle: the compressed counts string of rle (rle.size is set, rle.counts stays empty)
     int area = 0;              // pixels that are 255
     i32x2 bbox_top_left{0, 0}, bbox_extent{0, 0}; // of those pixels; 0, 0, 0, 0 for an empty mask
     float predicted_iou = 0, stability_score = 0;
@@ -735,12 +780,18 @@ inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t>
     check(visp_sam_image_extent(model.handle, &w, &h));
     const size_t px = size_t(w) * size_t(h), rows = size_t(cap > 0 ? cap : 0);
     std::vector<int32_t> n_arg(size_t(n), n_args), info_i(rows * 8);
-    std::vector<uint8_t> masks(p.output_rle ? 0 : rows * px);
+    const bool encoded = p.output_rle || p.output_coco_rle;
+    std::vector<uint8_t> masks(encoded ? 0 : rows * px);
     std::vector<float> info_f(rows * 2);
     std::vector<int64_t> offsets(rows + 1);
     uint32_t const* runs = nullptr;
-    rle_owner owner(nullptr); // holds the library's buffer with output_rle
-    if (p.output_rle)
+    uint8_t const* strings = nullptr;
+    rle_owner owner(nullptr); // holds the library's buffer with output_rle / output_coco_rle
+    if (p.output_coco_rle)
+        check(visp_sam_generate_masks_coco_rle_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset,
+                                                    p.nms_iou_thresh, cap, p.min_mask_region_area, info_i.data(), info_f.data(), counts, offsets.data(), &strings,
+                                                    &owner.data));
+    else if (p.output_rle)
         check(visp_sam_generate_masks_rle_host(model.handle, prompts.data(), n_arg.data(), n, p.pred_iou_thresh, p.stability_thresh, p.stability_offset, p.nms_iou_thresh,
                                                cap, p.min_mask_region_area, info_i.data(), info_f.data(), counts, offsets.data(), &runs, &owner.data));
     else if (p.min_mask_region_area != 0)
@@ -752,7 +803,10 @@ inline std::vector<sam_mask> sam_generate(sam_model& model, std::vector<int32_t>
     std::vector<sam_mask> out;
     for (int32_t k = 0; k < counts[0]; ++k) {
         sam_mask s;
-        if (p.output_rle) {
+        if (p.output_coco_rle) {
+            s.rle.size = i32x2{w, h};
+            s.coco_rle.assign(reinterpret_cast<char const*>(strings) + offsets[size_t(k)], size_t(offsets[size_t(k) + 1] - offsets[size_t(k)]));
+        } else if (p.output_rle) {
             s.rle = mask_rle{i32x2{w, h}, std::vector<uint32_t>(runs + offsets[size_t(k)], runs + offsets[size_t(k) + 1])};
         } else {
             s.segmentation = image_alloc({w, h}, image_format::alpha_u8);

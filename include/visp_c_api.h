@@ -370,6 +370,12 @@ VISP_API int32_t visp_sam_generate_masks_clean_host(visp_model* m, int32_t const
 VISP_API int32_t visp_sam_generate_masks_rle_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
                                                   float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, int32_t* info_i32,
                                                   float* info_f32, int32_t* counts, int64_t* offsets_i64, uint32_t const** runs_u32, visp_rle_data** out_data);
+/* the same with COCO's compressed counts strings out (SAM's output mode coco_rle; the codec: visp_image_rle_compress_device): mask b's string is
+ * bytes[byte_offsets[b] .. byte_offsets[b + 1]), byte_offsets i64 [capacity + 1]. The runs stay on the device; sizes and strings are all that is read back. */
+VISP_API int32_t visp_sam_generate_masks_coco_rle_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh,
+                                                       float stability_thresh, float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area,
+                                                       int32_t* info_i32, float* info_f32, int32_t* counts, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
+                                                       visp_rle_data** out_data);
 /* diagnostics, as visp_sam_generate_last_split: its four figures and a fifth, the cleaning stage of the last call (0 without one); and that stage alone as
  * {clean, records + second NMS, gather} */
 VISP_API int32_t visp_sam_generate_last_split5(visp_model const* m, float out_ms[5]);
@@ -478,6 +484,27 @@ VISP_API int32_t visp_image_mask_iou_device(void const* a_masks_u8_dev, void con
 VISP_API int32_t visp_image_mask_iou_host(uint8_t const* a_masks_u8, uint32_t const* a_runs_u32, int64_t const* a_offsets_i64, int32_t na, int32_t wa, int32_t ha,
                                           uint8_t const* b_masks_u8, uint32_t const* b_runs_u32, int64_t const* b_offsets_i64, int32_t nb, int32_t wb, int32_t hb,
                                           uint8_t const* iscrowd_u8, float* iou_f32, int32_t* inter_i32, visp_device const* dev);
+/* COCO's compressed counts strings, pycocotools' rleToString / rleFrString, on the device. Records are CSR rows of runs as above (each run below 2^31) on one side,
+ * CSR rows of bytes on the other: record b's string is bytes[byte_offsets[b] .. byte_offsets[b + 1]), byte_offsets i64 [n + 1]. Run i of a record is coded as
+ * c[i] for i <= 2 and c[i] - c[i - 2] behind, in 5-bit groups from the least significant: byte = group + 48 (48 .. 111), bit 5 = more groups follow, the last
+ * group's bit 4 = the sign above it; 1 .. 7 bytes a run. n is 1 .. 65535; counts as for visp_image_rle_decode_device.
+ * The device forms count, then write: with bytes (runs) NULL they write sizes i32 [n], each record's bytes (runs); with byte_offsets (offsets) made from the
+ * running sum of those sizes they write the packed output, sizes then nullable. status i32 [n] (nullable): 0 = good, 1 = a byte outside 48 .. 111, 2 = the last
+ * byte has bit 5 set, 3 = a value of more than 7 bytes, 4 = a count outside 0 .. 2^31 - 1; such a record reports 0 runs and gets none written. All pointers but
+ * dev are DEVICE pointers; the compress form reads the run offsets back (n + 1 values) before its first launch. Both return with the work done. */
+VISP_API int32_t visp_image_rle_compress_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, void const* counts_dev, void* bytes_u8_dev,
+                                                void const* byte_offsets_i64_dev, void* sizes_i32_dev, void* stream, visp_device const* dev);
+VISP_API int32_t visp_image_rle_decompress_device(void const* bytes_u8_dev, void const* byte_offsets_i64_dev, int32_t n, void const* counts_dev, void* runs_u32_dev,
+                                                  void const* offsets_i64_dev, void* sizes_i32_dev, void* status_i32_dev, void* stream, visp_device const* dev);
+/* the same on host arrays, both passes in one call, the output in a library-owned buffer (visp_rle_destroy); only sizes and the final rows are read back.
+ * compress refuses a run at or above 2^31, decompress a malformed record (the message names the record, the byte and the status), before any launch. Blocks. */
+VISP_API int32_t visp_image_rle_compress_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
+                                              visp_rle_data** out_data, visp_device const* dev);
+VISP_API int32_t visp_image_rle_decompress_host(int64_t const* byte_offsets_i64, uint8_t const* bytes_u8, int32_t n, int64_t* offsets_i64, uint32_t const** runs_u32,
+                                                visp_rle_data** out_data, visp_device const* dev);
+/* u8 masks -> strings in one call: the encoder's count and packed passes, then the compressor's two, on one stream; the runs never leave the device */
+VISP_API int32_t visp_image_rle_encode_compressed_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
+                                                       visp_rle_data** out_data, visp_device const* dev);
 /* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
  * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
 VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,

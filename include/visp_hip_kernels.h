@@ -485,6 +485,28 @@ VX_API int vx_mask_to_bits_u8(const uint8_t* masks, int n, int w, int h, const i
 VX_API size_t vx_bitmask_iou_workspace_bytes(int na, int nb);
 VX_API int vx_bitmask_iou(const void* a_words, int na, const void* b_words, int nb, int w, int h, const int32_t* counts_a, const int32_t* counts_b,
                           const uint8_t* iscrowd, int32_t* inter, float* iou, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- COCO's compressed counts strings (kernels_rle_codec.hip): pycocotools' rleToString / rleFrString on CSR rows ----
+ * Runs as above (runs u32 + offsets i64 [n + 1]); strings as a second CSR: record b's bytes at bytes + byte_offsets[b], byte_offsets a device i64 [n + 1]. Run i
+ * of a record is coded as x = c[i] for i <= 2 and c[i] - c[i - 2] behind, in 5-bit groups from the least significant: byte = group + 48, bit 5 = more groups
+ * follow, the last group's bit 4 = the sign above it; 1 .. 7 bytes for runs below 2^31. Both launchers count, then write: with a NULL output they write only the
+ * per-record sizes i32 [n]; with offsets made from the running sum of those sizes they write the packed output, and no store leaves a record's own row
+ * (offsets[b + 1] - offsets[b] entries), whatever the offsets say. counts / first as above: record m is skipped, nothing of it read or written, when
+ * first + m >= counts[0]. n is 1 .. 65535. Integers only, no atomics: the same bytes on every run.
+ *
+ * vx_rle_compress: runs below 2^31 -> strings. bytes NULL: sizes [n] = each record's bytes (required). Else byte_offsets is required and sizes nullable.
+ * total_runs = offsets[n] - offsets[0], at most (2^31 - 1) / 7 (a row outside that range is treated as empty); max_runs: the longest record's runs, a hint that
+ * sizes the grid (any value is correct, total_runs always serves). A record is cut into chunks of 1024 runs, a block each. workspace:
+ * vx_rle_compress_workspace_bytes(total_runs, n) bytes, 16-byte aligned (the chunks' byte sums; 0 for arguments the launcher refuses). Two launches, three
+ * with bytes. */
+VX_API size_t vx_rle_compress_workspace_bytes(int64_t total_runs, int n);
+VX_API int vx_rle_compress(const uint32_t* runs, const int64_t* offsets, int64_t total_runs, int64_t max_runs, int n, const int32_t* counts, int first, uint8_t* bytes,
+                           const int64_t* byte_offsets, int32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+/* vx_rle_decompress: strings -> runs. runs NULL: sizes [n] = each record's runs (required). Else offsets is required and sizes nullable. status i32 [n]
+ * (nullable): 0 = good, 1 = a byte outside 48 .. 111, 2 = the last byte has bit 5 set (unterminated), 3 = a value of more than 7 bytes, 4 = a count outside
+ * 0 .. 2^31 - 1 after the sum; the lowest one met. A record with a non-zero status reports 0 runs, so offsets made from the sizes leave it no row and none of
+ * its runs are written. A record's string is shorter than 2^31 bytes. One block per record, one launch. */
+VX_API int vx_rle_decompress(const uint8_t* bytes, const int64_t* byte_offsets, int n, const int32_t* counts, int first, uint32_t* runs, const int64_t* offsets,
+                             int32_t* sizes, int32_t* status, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -30,7 +30,7 @@ using namespace visp;
 
 struct visp_image_data : image_data {};
 struct visp_device : backend_device {};
-struct visp_rle_data { std::vector<uint32_t> runs; };
+struct visp_rle_data { std::vector<uint32_t> runs; std::vector<uint8_t> bytes; }; // one of the two: runs, or the bytes of compressed strings
 struct visp_graph : graph {};
 struct visp_weights { std::shared_ptr<weight_store> store; };
 struct visp_file { model_file file; };
@@ -141,9 +141,15 @@ void return_image(image_data&& img, visp_image_view* out_image, visp_image_data*
 }
 
 void return_rle(std::vector<uint32_t>&& runs, uint32_t const** out_runs, visp_rle_data** out_data) {
-    auto* owned = new visp_rle_data{std::move(runs)};
+    auto* owned = new visp_rle_data{std::move(runs), {}};
     *out_data = owned;
     *out_runs = owned->runs.data();
+}
+
+void return_rle(std::vector<uint8_t>&& bytes, uint8_t const** out_bytes, visp_rle_data** out_data) {
+    auto* owned = new visp_rle_data{{}, std::move(bytes)};
+    *out_data = owned;
+    *out_bytes = owned->bytes.data();
 }
 
 // a caller's view as visp::image_view: present, with data, a format of the enum, a positive extent and rows no shorter than their pixels
@@ -908,6 +914,17 @@ int32_t visp_sam_generate_masks_rle_host(visp_model* m, int32_t const* prompts, 
     });
 }
 
+int32_t visp_sam_generate_masks_coco_rle_host(visp_model* m, int32_t const* prompts, int32_t const* n_args, int32_t n, float pred_iou_thresh, float stability_thresh,
+                                              float stability_offset, float nms_iou_thresh, int32_t capacity, int32_t min_region_area, int32_t* info_i32, float* info_f32,
+                                              int32_t* counts, int64_t* byte_offsets_i64, uint8_t const** bytes_u8, visp_rle_data** out_data) {
+    return handle_errors([&]() {
+        if (!info_i32 || !info_f32 || !counts || !byte_offsets_i64 || !bytes_u8 || !out_data) throw except("visp_sam_generate_masks_coco_rle_host: null argument");
+        const sam_select_params p{pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, capacity, min_region_area};
+        sam_generate_check(prompts, n_args, n, p);
+        return_rle(sam_generate_masks_coco_rle_host(as_sam(m), prompts, n_args, n, p, info_i32, info_f32, counts, byte_offsets_i64), bytes_u8, out_data);
+    });
+}
+
 // the last generate call's ms of the stages named, in that order (0 for a stage the call did not run)
 static void sam_stage_ms(visp_model const* m, float* out_ms, std::initializer_list<sam_generate_stage> stages) {
     if (!out_ms) throw except("sam: null argument");
@@ -1080,6 +1097,41 @@ int32_t visp_image_rle_decode_device(void const* runs_u32_dev, void const* offse
 int32_t visp_image_rle_decode_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int32_t w, int32_t h, int32_t value, uint8_t* masks_u8,
                                    visp_device const* dev) {
     return handle_errors([&]() { rle_decode_host(dev, offsets_i64, runs_u32, n, w, h, value, masks_u8); });
+}
+
+int32_t visp_image_rle_compress_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, void const* counts_dev, void* bytes_u8_dev,
+                                       void const* byte_offsets_i64_dev, void* sizes_i32_dev, void* stream, visp_device const* dev) {
+    return handle_errors([&]() { rle_compress_device(dev, runs_u32_dev, offsets_i64_dev, n, counts_dev, bytes_u8_dev, byte_offsets_i64_dev, sizes_i32_dev, stream); });
+}
+
+int32_t visp_image_rle_compress_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
+                                     visp_rle_data** out_data, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!bytes_u8 || !out_data) throw except("rle_compress: null pointer");
+        return_rle(rle_compress_host(dev, offsets_i64, runs_u32, n, byte_offsets_i64), bytes_u8, out_data);
+    });
+}
+
+int32_t visp_image_rle_decompress_device(void const* bytes_u8_dev, void const* byte_offsets_i64_dev, int32_t n, void const* counts_dev, void* runs_u32_dev,
+                                         void const* offsets_i64_dev, void* sizes_i32_dev, void* status_i32_dev, void* stream, visp_device const* dev) {
+    return handle_errors(
+        [&]() { rle_decompress_device(dev, bytes_u8_dev, byte_offsets_i64_dev, n, counts_dev, runs_u32_dev, offsets_i64_dev, sizes_i32_dev, status_i32_dev, stream); });
+}
+
+int32_t visp_image_rle_decompress_host(int64_t const* byte_offsets_i64, uint8_t const* bytes_u8, int32_t n, int64_t* offsets_i64, uint32_t const** runs_u32,
+                                       visp_rle_data** out_data, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!runs_u32 || !out_data) throw except("rle_decompress: null pointer");
+        return_rle(rle_decompress_host(dev, byte_offsets_i64, bytes_u8, n, offsets_i64), runs_u32, out_data);
+    });
+}
+
+int32_t visp_image_rle_encode_compressed_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
+                                              visp_rle_data** out_data, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!bytes_u8 || !out_data) throw except("rle_encode: null pointer");
+        return_rle(rle_encode_compressed_host(dev, masks_u8, n, w, h, byte_offsets_i64), bytes_u8, out_data);
+    });
 }
 
 int32_t visp_image_rle_area_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* area_i64) {

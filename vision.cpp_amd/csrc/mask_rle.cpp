@@ -15,7 +15,9 @@ constexpr int64_t kRlePassBytes = int64_t(256) << 20; // runs on the device in o
 // right behind the previous mask's (vx_mask_rle_packed_u8), so exactly the runs cross to the host, in one copy per pass straight into the result. A pass holds at
 // most kRlePassBytes of runs on the device (a single mask with more has a pass of its own). counts_dev (nullable) cuts the masks to its first entry, which the count
 // pass's readback brings along into counts_host [n_counts].
-std::vector<uint32_t> encode_to_host(uint8_t const* masks_dev, int n, int w, int h, int32_t const* counts_dev, int32_t* counts_host, int n_counts, int64_t* offsets, void* s) {
+// `sink(b0, b1, rows_dev, offsets_dev, rel)` takes each pass's rows off the device: masks b0 .. b1, rel their offsets from 0.
+template <class Sink>
+void encode_passes(uint8_t const* masks_dev, int n, int w, int h, int32_t const* counts_dev, int32_t* counts_host, int n_counts, int64_t* offsets, void* s, Sink&& sink) {
     const int group = std::min(n, kRleGroup);
     const size_t ws_bytes = vx_mask_rle_workspace_bytes(w, h, group);
     device_buffer ws(ws_bytes), nr((size_t)n * 4);
@@ -28,7 +30,6 @@ std::vector<uint32_t> encode_to_host(uint8_t const* masks_dev, int n, int w, int
     const int k = counts_dev ? std::min(std::max(counts_host[0], 0), n) : n;
     offsets[0] = 0;
     for (int b = 0; b < n; ++b) offsets[b + 1] = offsets[b] + (b < k ? n_runs[(size_t)b] : 0);
-    std::vector<uint32_t> out((size_t)offsets[n]);
     device_buffer rows, off_dev;
     std::vector<int64_t> rel;
     for (int b0 = 0, b1; b0 < k; b0 = b1) {
@@ -40,9 +41,68 @@ std::vector<uint32_t> encode_to_host(uint8_t const* masks_dev, int n, int w, int
         VX(vx_memcpy_h2d(off_dev.ptr, rel.data(), rel.size() * 8, s));
         VX(vx_mask_rle_packed_u8(masks_dev + (size_t)b0 * w * h, w, h, b1 - b0, static_cast<int64_t const*>(off_dev.ptr), static_cast<uint32_t*>(rows.ptr), nr_dev + b0, ws.ptr,
                                  ws_bytes, group, s));
-        VX(vx_memcpy_d2h(out.data() + offsets[b0], rows.ptr, (size_t)rel.back() * 4, s));
-        VX(vx_stream_sync(s));
+        sink(b0, b1, static_cast<uint32_t const*>(rows.ptr), static_cast<int64_t const*>(off_dev.ptr), rel);
     }
+}
+
+std::vector<uint32_t> encode_to_host(uint8_t const* masks_dev, int n, int w, int h, int32_t const* counts_dev, int32_t* counts_host, int n_counts, int64_t* offsets, void* s) {
+    std::vector<uint32_t> out;
+    encode_passes(masks_dev, n, w, h, counts_dev, counts_host, n_counts, offsets, s, [&](int b0, int, uint32_t const* rows_dev, int64_t const*, std::vector<int64_t> const& rel) {
+        out.resize((size_t)offsets[n]);
+        VX(vx_memcpy_d2h(out.data() + offsets[b0], rows_dev, (size_t)rel.back() * 4, s));
+        VX(vx_stream_sync(s));
+    });
+    return out;
+}
+
+constexpr int kCodecGroup = 65535; // records of one launch of the codec
+
+// Device CSR rows (off_dev [n + 1], `off` the same values on the host) -> their strings appended to `out`, byte_offsets[1 .. n] continued from byte_offsets[0].
+// The compressor's count pass, one readback of the sizes, their running sum uploaded, the write pass, one copy of the bytes: per group of kCodecGroup records.
+void compress_rows(uint32_t const* runs_dev, int64_t const* off_dev, int64_t const* off, int n, std::vector<uint8_t>& out, int64_t* byte_offsets, void* s) {
+    device_buffer ws, sizes_dev, boff_dev, bytes_dev;
+    std::vector<int32_t> sizes;
+    std::vector<int64_t> brel;
+    for (int g0 = 0; g0 < n; g0 += kCodecGroup) {
+        const int g = std::min(kCodecGroup, n - g0);
+        const int64_t total = off[g0 + g] - off[g0];
+        int64_t longest = 0;
+        for (int b = g0; b < g0 + g; ++b) longest = std::max(longest, off[b + 1] - off[b]);
+        const size_t ws_bytes = vx_rle_compress_workspace_bytes(total, g);
+        if (!ws_bytes) throw except("rle_compress: %lld runs in the %d records from %d: too many for one pass", (long long)total, g, g0);
+        grow(ws, ws_bytes, {s});
+        grow(sizes_dev, (size_t)g * 4, {s});
+        VX(vx_rle_compress(runs_dev, off_dev + g0, total, longest, g, nullptr, 0, nullptr, nullptr, static_cast<int32_t*>(sizes_dev.ptr), ws.ptr, ws_bytes, s));
+        sizes.resize((size_t)g);
+        VX(vx_memcpy_d2h(sizes.data(), sizes_dev.ptr, (size_t)g * 4, s));
+        VX(vx_stream_sync(s));
+        brel.assign((size_t)g + 1, 0);
+        for (int b = 0; b < g; ++b) brel[(size_t)b + 1] = brel[(size_t)b] + sizes[(size_t)b];
+        grow(boff_dev, brel.size() * 8, {s});
+        grow(bytes_dev, std::max<size_t>((size_t)brel.back(), 16), {s});
+        VX(vx_memcpy_h2d(boff_dev.ptr, brel.data(), brel.size() * 8, s));
+        VX(vx_rle_compress(runs_dev, off_dev + g0, total, longest, g, nullptr, 0, static_cast<uint8_t*>(bytes_dev.ptr), static_cast<int64_t const*>(boff_dev.ptr), nullptr, ws.ptr,
+                           ws_bytes, s));
+        const size_t at = out.size();
+        out.resize(at + (size_t)brel.back());
+        if (brel.back()) VX(vx_memcpy_d2h(out.data() + at, bytes_dev.ptr, (size_t)brel.back(), s));
+        VX(vx_stream_sync(s));
+        for (int b = 0; b < g; ++b) byte_offsets[g0 + b + 1] = byte_offsets[g0] + brel[(size_t)b + 1];
+    }
+}
+
+// masks on the device -> strings on the host: each encode pass's rows go through the compressor while they are on the device
+std::vector<uint8_t> encode_compressed_to_host(uint8_t const* masks_dev, int n, int w, int h, int32_t const* counts_dev, int32_t* counts_host, int n_counts, int64_t* byte_offsets,
+                                               void* s) {
+    std::vector<int64_t> offsets((size_t)n + 1);
+    std::vector<uint8_t> out;
+    byte_offsets[0] = 0;
+    encode_passes(masks_dev, n, w, h, counts_dev, counts_host, n_counts, offsets.data(), s,
+                  [&](int b0, int b1, uint32_t const* rows_dev, int64_t const* off_dev, std::vector<int64_t> const& rel) {
+                      compress_rows(rows_dev, off_dev, rel.data(), b1 - b0, out, byte_offsets + b0, s);
+                  });
+    const int k = counts_dev ? std::min(std::max(counts_host[0], 0), n) : n;
+    for (int b = k; b < n; ++b) byte_offsets[b + 1] = byte_offsets[b]; // no pass reaches the masks behind the count
     return out;
 }
 
@@ -78,8 +138,12 @@ std::vector<uint32_t> rle_encode_host(backend_device const* dev, uint8_t const* 
     return encode_to_host(static_cast<uint8_t const*>(m.ptr), n, w, h, nullptr, nullptr, 0, offsets, on.stream);
 }
 
-std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
-                                                  float* info_f32, int32_t* counts, int64_t* offsets) {
+namespace {
+
+// the generate call into the model's staging buffer, `encode` of its masks behind it on the same stream, then the info rows of the masks returned
+template <class Out, class Encode>
+std::vector<Out> generate_encoded(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32, float* info_f32,
+                                  int32_t* counts, int64_t* offsets, Encode&& encode) {
     if (!info_i32 || !info_f32 || !counts || !offsets) throw except("sam: null argument");
     device_turn turn(*m.backend);
     void* s = m.backend->stream;
@@ -90,7 +154,7 @@ std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* p
     uint8_t* base = static_cast<uint8_t*>(m.generate_rle_stage.ptr);
     sam_generate_masks_device(m, prompts, n_args, n, p, {base + o_m, base + o_i, base + o_f, base + o_c}, s); // checks the model: decoder, encoded image
     const int n_counts = p.min_region_area > 0 ? 4 : 2;
-    std::vector<uint32_t> runs = encode_to_host(base + o_m, p.capacity, w, h, reinterpret_cast<int32_t const*>(base + o_c), counts, n_counts, offsets, s);
+    std::vector<Out> runs = encode(base + o_m, p.capacity, w, h, reinterpret_cast<int32_t const*>(base + o_c), counts, n_counts, offsets, s);
     const size_t k = (size_t)std::min(std::max(counts[0], 0), p.capacity); // rows behind the returned ones stay as the caller left them
     if (k) {
         VX(vx_memcpy_d2h(info_i32, base + o_i, k * 32, s));
@@ -98,6 +162,18 @@ std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* p
         VX(vx_stream_sync(s));
     }
     return runs;
+}
+
+} // namespace
+
+std::vector<uint32_t> sam_generate_masks_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
+                                                  float* info_f32, int32_t* counts, int64_t* offsets) {
+    return generate_encoded<uint32_t>(m, prompts, n_args, n, p, info_i32, info_f32, counts, offsets, encode_to_host);
+}
+
+std::vector<uint8_t> sam_generate_masks_coco_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
+                                                      float* info_f32, int32_t* counts, int64_t* byte_offsets) {
+    return generate_encoded<uint8_t>(m, prompts, n_args, n, p, info_i32, info_f32, counts, byte_offsets, encode_compressed_to_host);
 }
 
 // ---- the way back: decode, area, IoU ----
@@ -267,6 +343,127 @@ void mask_iou_host(backend_device const* dev, mask_set const& a, mask_set const&
     VX(vx_memcpy_d2h(iou, out.ptr, pairs * 4, s));
     if (inter) VX(vx_memcpy_d2h(inter, out_inter.ptr, pairs * 4, s));
     VX(vx_stream_sync(s));
+}
+
+// ---- COCO's compressed counts strings (kernels_rle_codec.hip) ----
+
+void check_rle_codec(char const* who, int n) {
+    if (n < 1 || n > 65535) throw except("%s: %d records (1 .. 65535)", who, n);
+}
+
+rle_string_fault check_rle_strings(int64_t const* byte_offsets, uint8_t const* bytes, int n) {
+    for (int b = 0; b < n; ++b) {
+        if (byte_offsets[b + 1] < byte_offsets[b] || byte_offsets[b] < 0) throw except("rle_decompress: byte offsets decrease at record %d", b);
+        const int64_t begin = byte_offsets[b], end = byte_offsets[b + 1];
+        int64_t chain[2] = {0, 0}, i = 0; // c[i - 2] by the parity of i
+        for (int64_t p = begin; p < end; ++i) {
+            int64_t x = 0;
+            int k = 0;
+            for (bool more = true; more; ++k, ++p) {
+                if (p == end) return {b, end - 1 - begin, 2};
+                const int g = bytes[p] - 48;
+                if (g < 0 || g > 63) return {b, p - begin, 1};
+                if (k == 7) return {b, p - begin, 3};
+                x |= int64_t(g & 31) << (5 * k);
+                more = g & 32;
+                if (!more && (g & 16)) x -= int64_t(1) << (5 * (k + 1)); // the sign above the bits read
+            }
+            if (i > 2) x += chain[i & 1];
+            if (x < 0 || x > 0x7fffffffLL) return {b, p - 1 - begin, 4};
+            chain[i & 1] = x;
+        }
+    }
+    return {-1, 0, 0};
+}
+
+void rle_compress_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, void const* counts_dev, void* bytes_dev, void const* byte_offsets_dev,
+                         void* sizes_dev, void* stream) {
+    if (!runs_dev || !offsets_dev || (bytes_dev ? !byte_offsets_dev : !sizes_dev)) throw except("rle_compress: null pointer");
+    check_rle_codec("rle_compress", n);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    const std::vector<int64_t> off = read_offsets("rle_compress", offsets_dev, n, s);
+    int64_t longest = 0;
+    for (int b = 0; b < n; ++b) longest = std::max(longest, off[(size_t)b + 1] - off[(size_t)b]);
+    const int64_t total = off.back() - off.front();
+    const size_t ws_bytes = vx_rle_compress_workspace_bytes(total, n);
+    if (!ws_bytes) throw except("rle_compress: %lld runs: too many for one call", (long long)total);
+    device_buffer ws(ws_bytes);
+    VX(vx_rle_compress(static_cast<uint32_t const*>(runs_dev), static_cast<int64_t const*>(offsets_dev), total, longest, n, static_cast<int32_t const*>(counts_dev), 0,
+                       static_cast<uint8_t*>(bytes_dev), static_cast<int64_t const*>(byte_offsets_dev), static_cast<int32_t*>(sizes_dev), ws.ptr, ws_bytes, s));
+    VX(vx_stream_sync(s)); // the workspace is freed behind this
+}
+
+std::vector<uint8_t> rle_compress_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int64_t* byte_offsets) {
+    if (!offsets || !runs || !byte_offsets) throw except("rle_compress: null pointer");
+    check_rle_codec("rle_compress", n);
+    check_rle_rows("rle_compress", offsets, runs, n, -1);
+    for (int b = 0; b < n; ++b)
+        for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i)
+            if (runs[i] >= 0x80000000u) throw except("rle_compress: run %lld of record %d is %u, at or above 2^31", (long long)(i - offsets[b]), b, runs[i]);
+    device_scope on(dev);
+    void* s = on.stream;
+    std::vector<int64_t> rel(offsets, offsets + n + 1);
+    for (int64_t& v : rel) v -= offsets[0];
+    device_buffer r = uploaded(runs + offsets[0], (size_t)rel.back() * 4, s), o = uploaded(rel.data(), rel.size() * 8, s);
+    std::vector<uint8_t> out;
+    byte_offsets[0] = 0;
+    compress_rows(static_cast<uint32_t const*>(r.ptr), static_cast<int64_t const*>(o.ptr), rel.data(), n, out, byte_offsets, s);
+    return out;
+}
+
+void rle_decompress_device(backend_device const* dev, void const* bytes_dev, void const* byte_offsets_dev, int n, void const* counts_dev, void* runs_dev,
+                           void const* offsets_dev, void* sizes_dev, void* status_dev, void* stream) {
+    if (!bytes_dev || !byte_offsets_dev || (runs_dev ? !offsets_dev : !sizes_dev)) throw except("rle_decompress: null pointer");
+    check_rle_codec("rle_decompress", n);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    VX(vx_rle_decompress(static_cast<uint8_t const*>(bytes_dev), static_cast<int64_t const*>(byte_offsets_dev), n, static_cast<int32_t const*>(counts_dev), 0,
+                         static_cast<uint32_t*>(runs_dev), static_cast<int64_t const*>(offsets_dev), static_cast<int32_t*>(sizes_dev), static_cast<int32_t*>(status_dev), s));
+    VX(vx_stream_sync(s));
+}
+
+std::vector<uint32_t> rle_decompress_host(backend_device const* dev, int64_t const* byte_offsets, uint8_t const* bytes, int n, int64_t* offsets) {
+    if (!byte_offsets || !bytes || !offsets) throw except("rle_decompress: null pointer");
+    check_rle_codec("rle_decompress", n);
+    const rle_string_fault bad = check_rle_strings(byte_offsets, bytes, n);
+    if (bad.status) {
+        static char const* const what[] = {"", "a byte outside 48 .. 111", "the last byte has bit 5 set (unterminated)", "a value of more than 7 bytes", "a count outside 0 .. 2^31 - 1"};
+        throw except("rle_decompress: record %d, byte %lld: status %d, %s", bad.record, (long long)bad.byte, bad.status, what[bad.status]);
+    }
+    device_scope on(dev);
+    void* s = on.stream;
+    std::vector<int64_t> brel(byte_offsets, byte_offsets + n + 1);
+    for (int64_t& v : brel) v -= byte_offsets[0];
+    device_buffer src = uploaded(bytes + byte_offsets[0], (size_t)brel.back(), s), bo = uploaded(brel.data(), brel.size() * 8, s), sizes_dev((size_t)n * 4);
+    uint8_t const* src_dev = static_cast<uint8_t const*>(src.ptr);
+    int64_t const* bo_dev = static_cast<int64_t const*>(bo.ptr);
+    VX(vx_rle_decompress(src_dev, bo_dev, n, nullptr, 0, nullptr, nullptr, static_cast<int32_t*>(sizes_dev.ptr), nullptr, s));
+    std::vector<int32_t> sizes((size_t)n);
+    VX(vx_memcpy_d2h(sizes.data(), sizes_dev.ptr, (size_t)n * 4, s));
+    VX(vx_stream_sync(s));
+    offsets[0] = 0;
+    for (int b = 0; b < n; ++b) offsets[b + 1] = offsets[b] + sizes[(size_t)b];
+    std::vector<uint32_t> out((size_t)offsets[n]);
+    device_buffer o = uploaded(offsets, ((size_t)n + 1) * 8, s), rows(std::max<size_t>(out.size() * 4, 16)), st((size_t)n * 4);
+    VX(vx_rle_decompress(src_dev, bo_dev, n, nullptr, 0, static_cast<uint32_t*>(rows.ptr), static_cast<int64_t const*>(o.ptr), nullptr, static_cast<int32_t*>(st.ptr), s));
+    std::vector<int32_t> status((size_t)n);
+    VX(vx_memcpy_d2h(status.data(), st.ptr, (size_t)n * 4, s));
+    if (!out.empty()) VX(vx_memcpy_d2h(out.data(), rows.ptr, out.size() * 4, s));
+    VX(vx_stream_sync(s));
+    for (int b = 0; b < n; ++b)
+        if (status[(size_t)b]) throw except("rle_decompress: record %d: the device reports status %d on a string the host check passed", b, status[(size_t)b]);
+    return out;
+}
+
+std::vector<uint8_t> rle_encode_compressed_host(backend_device const* dev, uint8_t const* masks, int n, int w, int h, int64_t* byte_offsets) {
+    if (!masks || !byte_offsets) throw except("rle_encode: null pointer");
+    check_rle_encode(n, w, h, 0);
+    device_scope on(dev);
+    const size_t bytes = (size_t)n * w * h;
+    device_buffer m(bytes);
+    VX(vx_memcpy_h2d(m.ptr, masks, bytes, on.stream));
+    return encode_compressed_to_host(static_cast<uint8_t const*>(m.ptr), n, w, h, nullptr, nullptr, 0, byte_offsets, on.stream);
 }
 
 } // namespace visp

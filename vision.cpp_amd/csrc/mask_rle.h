@@ -48,4 +48,26 @@ void mask_iou_device(backend_device const* dev, mask_set const& a, mask_set cons
 // the same on host arrays: up, the matrix, down; rows of runs are held to their sum h w before any launch
 void mask_iou_host(backend_device const* dev, mask_set const& a, mask_set const& b, uint8_t const* iscrowd, float* iou, int32_t* inter);
 
+// ---- COCO's compressed counts strings (kernels_rle_codec.hip): CSR rows of runs <-> CSR rows of bytes (bytes u8, byte_offsets i64 [n + 1]) ----
+void check_rle_codec(char const* who, int n); // throws, touches no device
+// the first malformed record of host strings by pycocotools' rleFrString, the loop as it reads: status as vx_rle_decompress gives it, 0 (record -1) = all good
+struct rle_string_fault { int record; int64_t byte; int status; };
+rle_string_fault check_rle_strings(int64_t const* byte_offsets, uint8_t const* bytes, int n);
+// count, then write, as the launcher: bytes_dev null -> sizes i32 [n] alone; else the strings at byte_offsets_dev. The run offsets are read back and checked before
+// the first launch; the workspace is allocated for the CALL; returns with the work done.
+void rle_compress_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, void const* counts_dev, void* bytes_dev, void const* byte_offsets_dev,
+                         void* sizes_dev, void* stream);
+// host rows -> the strings one behind the other, byte_offsets i64 [n + 1]; a run at or above 2^31 is refused before any launch. Only sizes and strings come back.
+std::vector<uint8_t> rle_compress_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int64_t* byte_offsets);
+// runs_dev null -> sizes i32 [n] alone; else the runs at offsets_dev; status i32 [n] nullable
+void rle_decompress_device(backend_device const* dev, void const* bytes_dev, void const* byte_offsets_dev, int n, void const* counts_dev, void* runs_dev,
+                           void const* offsets_dev, void* sizes_dev, void* status_dev, void* stream);
+// host strings -> the runs one behind the other, offsets i64 [n + 1]; a malformed record is refused before any launch, naming the record, the byte and the status
+std::vector<uint32_t> rle_decompress_host(backend_device const* dev, int64_t const* byte_offsets, uint8_t const* bytes, int n, int64_t* offsets);
+// host masks -> strings: the encoder's two passes and the compressor's on one stream; only sizes and string bytes cross to the host
+std::vector<uint8_t> rle_encode_compressed_host(backend_device const* dev, uint8_t const* masks, int n, int w, int h, int64_t* byte_offsets);
+// sam_generate_masks_rle_host with strings out: byte_offsets i64 [capacity + 1]
+std::vector<uint8_t> sam_generate_masks_coco_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
+                                                      float* info_f32, int32_t* counts, int64_t* byte_offsets);
+
 } // namespace visp

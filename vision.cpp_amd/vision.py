@@ -480,14 +480,42 @@ class Model:
         every other key is as with "binary_mask"."""
         if output_mode not in ("binary_mask", "uncompressed_rle"):
             raise ValueError(f"unknown output_mode {output_mode!r}: one of 'binary_mask', 'uncompressed_rle'")
-        p, k, _ = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
         raw = self.sam_generate_masks_raw if output_mode == "binary_mask" else self.sam_generate_masks_rle_raw
+        return self._sam_generate_records(raw, output_mode == "binary_mask", points_per_side, prompts, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh,
+                                          max_masks, min_mask_region_area)
+
+    def sam_generate_masks_coco_rle(self, points_per_side: int = 32, prompts=None, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
+                                    max_masks: int = 256, min_mask_region_area: int = 0):
+        """sam_generate_masks in SAM's output mode coco_rle: segmentation is {"size": [h, w], "counts": bytes}, COCO's compressed counts string as pycocotools
+        exchanges it, encoded and compressed on the device (visp_sam_generate_masks_coco_rle_host: neither a mask byte nor a run is read back); every other key
+        is as with "uncompressed_rle"."""
+        return self._sam_generate_records(self.sam_generate_masks_coco_rle_raw, False, points_per_side, prompts, pred_iou_thresh, stability_thresh, stability_offset,
+                                          nms_iou_thresh, max_masks, min_mask_region_area)
+
+    def sam_generate_masks_coco_rle_raw(self, prompts=None, points_per_side: int = 32, pred_iou_thresh=None, stability_thresh=None, stability_offset=None, nms_iou_thresh=None,
+                                        max_masks: int = 256, min_mask_region_area: int = 0):
+        """sam_generate_masks_rle_raw with the records' counts as compressed strings (bytes)"""
+        p, k, params = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
+        n, cap = len(k), int(max_masks)
+        w, h = self.sam_image_extent() if n and cap > 0 else (0, 0)
+        ii, fi, counts = np.empty((max(cap, 0), 8), np.int32), np.empty((max(cap, 0), 2), np.float32), np.zeros(4, np.int32)
+        offsets, data, owner = np.zeros(max(cap, 0) + 1, np.int64), c_void_p(), c_void_p()
+        check(self._api.visp_sam_generate_masks_coco_rle_host(self._handle, p.ctypes.data, k.ctypes.data, n, *params, cap, int(min_mask_region_area), ii.ctypes.data,
+                                                              fi.ctypes.data, counts.ctypes.data, offsets.ctypes.data, byref(data), byref(owner)))
+        self._sam_batch_n = n
+        r = int(counts[0])
+        return _string_records(offsets, data, owner, [[h, w]] * r), ii[:r], fi[:r], (r, *(int(c) for c in counts[1:]))
+
+    def _sam_generate_records(self, raw, binary: bool, points_per_side, prompts, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, max_masks,
+                              min_mask_region_area):
+        """the records of sam_generate_masks from one of the raw calls"""
+        p, k, _ = self._sam_generate_args(prompts, points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh)
         masks, ii, fi, _ = raw([list(q[:c]) for q, c in zip(p, k)], points_per_side, pred_iou_thresh, stability_thresh, stability_offset, nms_iou_thresh, max_masks,
                                min_mask_region_area)
         out = []
         for m, row, (piou, stab) in zip(masks, ii, fi):
             prompt = int(row[0])
-            rec = dict(segmentation=m == 255 if output_mode == "binary_mask" else m, area=int(row[6]), bbox=[int(v) for v in row[2:6]], predicted_iou=float(piou), stability_score=float(stab))
+            rec = dict(segmentation=m == 255 if binary else m, area=int(row[6]), bbox=[int(v) for v in row[2:6]], predicted_iou=float(piou), stability_score=float(stab))
             if k[prompt] == 2:
                 rec["point_coords"] = [[int(p[prompt, 0]), int(p[prompt, 1])]]
             else:
@@ -749,27 +777,98 @@ def rle_to_mask(rle: dict) -> np.ndarray:
     return flat.reshape(w, h).T
 
 
-def _rle_rows(rles) -> tuple:
-    """RLE dicts of one extent -> (offsets i64 [n + 1], runs u32, w, h): the CSR rows of the C entries"""
+def _rle_rows(rles, device: Device | None = None) -> tuple:
+    """RLE dicts of one extent -> (offsets i64 [n + 1], runs u32, w, h): the CSR rows of the C entries. Records whose counts are a compressed string (bytes or
+    str) are decompressed on the device first."""
     if not rles:
         raise ValueError("expected at least one RLE record")
     h, w = (int(v) for v in rles[0]["size"])
     if any([int(v) for v in r["size"]] != [h, w] for r in rles):
         raise ValueError(f"the records differ in size: expected [{h}, {w}] in all of them")
+    packed = [i for i, r in enumerate(rles) if isinstance(r["counts"], (bytes, str))]
+    if packed:
+        rles = list(rles)
+        for i, r in zip(packed, rle_decompress([rles[i] for i in packed], device)):
+            rles[i] = r
+    return *_run_rows(rles), w, h
+
+
+def _run_rows(rles) -> tuple:
+    """the list counts of RLE dicts -> (offsets i64 [n + 1], runs u32), one row behind the other"""
     rows = [np.asarray(r["counts"], np.int64) for r in rles]
     if any(c.size and (c.min() < 0 or c.max() >= 2 ** 32) for c in rows):
         raise ValueError("counts must lie in 0 .. 2^32 - 1")
     offsets = np.zeros(len(rows) + 1, np.int64)
     np.cumsum([c.size for c in rows], out=offsets[1:])
     runs = np.concatenate(rows).astype(np.uint32) if offsets[-1] else np.zeros(1, np.uint32)
-    return offsets, runs, w, h
+    return offsets, runs
+
+
+def _string_records(byte_offsets, data_ptr, owner, sizes) -> list:
+    """the library-owned strings of a compress call as records {"size": .., "counts": bytes}, one per entry of sizes; releases the buffer"""
+    try:
+        data = ctypes.string_at(data_ptr, int(byte_offsets[len(sizes)])) if len(sizes) and byte_offsets[len(sizes)] else b""
+    finally:
+        lib.get_lib().visp_rle_destroy(owner)
+    return [{"size": [int(v) for v in s], "counts": data[int(byte_offsets[b]):int(byte_offsets[b + 1])]} for b, s in enumerate(sizes)]
+
+
+def rle_compress(rles, device: Device | None = None):
+    """pycocotools' compressed form on the device (its rleToString): records {"size": [h, w], "counts": [...]} -> the same records with counts as bytes, the
+    string a COCO file holds in segmentation.counts (.decode("ascii") for json). A list in, a list out; one dict in, one dict out. Counts lie below 2^31."""
+    single = isinstance(rles, dict)
+    recs = [rles] if single else list(rles)
+    if not recs:
+        raise ValueError("expected at least one RLE record")
+    offsets, runs = _run_rows(recs)
+    byte_offsets, data, owner = np.zeros(len(recs) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_compress_host(offsets.ctypes.data, runs.ctypes.data, len(recs), byte_offsets.ctypes.data, byref(data), byref(owner), *_on(device)))
+    out = _string_records(byte_offsets, data, owner, [r["size"] for r in recs])
+    return out[0] if single else out
+
+
+def rle_decompress(rles, device: Device | None = None):
+    """The way back (pycocotools' rleFrString): records whose counts are bytes, or str read as ASCII -> records with list counts. A malformed string is refused;
+    the message names the record, the byte and the status (1 a byte outside 48 .. 111, 2 unterminated, 3 a value of more than 7 bytes, 4 a count outside
+    0 .. 2^31 - 1)."""
+    single = isinstance(rles, dict)
+    recs = [rles] if single else list(rles)
+    if not recs:
+        raise ValueError("expected at least one RLE record")
+    rows = [r["counts"].encode("ascii") if isinstance(r["counts"], str) else bytes(r["counts"]) for r in recs]
+    byte_offsets = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(c) for c in rows], out=byte_offsets[1:])
+    data = np.frombuffer(b"".join(rows) or b"\0", np.uint8)
+    offsets, runs, owner = np.zeros(len(rows) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_decompress_host(byte_offsets.ctypes.data, data.ctypes.data, len(rows), offsets.ctypes.data, byref(runs), byref(owner), *_on(device)))
+    try:
+        total = int(offsets[-1])
+        flat = np.ctypeslib.as_array(ctypes.cast(runs, ctypes.POINTER(ctypes.c_uint32)), (total,)).copy() if total else np.empty(0, np.uint32)
+    finally:
+        lib.get_lib().visp_rle_destroy(owner)
+    out = [{"size": [int(v) for v in r["size"]], "counts": flat[int(offsets[b]):int(offsets[b + 1])].tolist()} for b, r in enumerate(recs)]
+    return out[0] if single else out
+
+
+def mask_to_coco_rle(masks: np.ndarray, device: Device | None = None):
+    """mask_to_rle and rle_compress in one call on the device (pycocotools' encode): masks [n, h, w] or [h, w] -> records with counts as bytes. The runs never
+    leave the device."""
+    a = np.asarray(masks)
+    m = np.ascontiguousarray(a if a.dtype == np.uint8 else a != 0, dtype=np.uint8)
+    if m.ndim not in (2, 3):
+        raise ValueError(f"expected masks [n, h, w] or [h, w], got shape {m.shape}")
+    n, (h, w) = (1 if m.ndim == 2 else m.shape[0]), m.shape[-2:]
+    byte_offsets, data, owner = np.zeros(max(n, 0) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_encode_compressed_host(m.ctypes.data, n, w, h, byte_offsets.ctypes.data, byref(data), byref(owner), *_on(device)))
+    out = _string_records(byte_offsets, data, owner, [[h, w]] * n)
+    return out[0] if m.ndim == 2 else out
 
 
 def rle_decode(rles, value: int = 1, device: Device | None = None) -> np.ndarray:
     """pycocotools' decode on the device: the record dicts mask_to_rle and sam_generate_masks return ({"size": [h, w], "counts": [...]}, all of one size) ->
     uint8 [n, h, w] with foreground bytes `value` ([h, w] for a single dict). A record whose counts do not sum to h * w is refused."""
     single = isinstance(rles, dict)
-    offsets, runs, w, h = _rle_rows([rles] if single else list(rles))
+    offsets, runs, w, h = _rle_rows([rles] if single else list(rles), device)
     out = np.empty((len(offsets) - 1, h, w), np.uint8)
     check(lib.get_lib().visp_image_rle_decode_host(offsets.ctypes.data, runs.ctypes.data, len(offsets) - 1, w, h, int(value), out.ctypes.data, *_on(device)))
     return out[0] if single else out
@@ -804,7 +903,7 @@ def mask_iou(a, b, iscrowd=None, device: Device | None = None, return_intersecti
             keep.append(m)
             sides.append((m.ctypes.data, None, None, m.shape[0], m.shape[2], m.shape[1]))
         else:
-            offsets, runs, w, h = _rle_rows(list(s))
+            offsets, runs, w, h = _rle_rows(list(s), device)
             keep += [offsets, runs]
             sides.append((None, runs.ctypes.data, offsets.ctypes.data, len(offsets) - 1, w, h))
     na, nb = sides[0][3], sides[1][3]
