@@ -324,6 +324,57 @@ inline std::string image_rle_encode_compressed(image_view const& mask) {
     detail::check(visp_image_rle_encode_compressed_host(packed.data(), 1, mask.extent[0], mask.extent[1], byte_offsets, &bytes, &owner.data, nullptr));
     return std::string(reinterpret_cast<char const*>(bytes), size_t(byte_offsets[1]));
 }
+namespace detail {
+inline std::vector<mask_rle> rle_records(i32x2 size, std::vector<int64_t> const& offsets, uint32_t const* runs) {
+    std::vector<mask_rle> out;
+    for (size_t k = 0; k + 1 < offsets.size(); ++k) out.push_back(mask_rle{size, std::vector<uint32_t>(runs + offsets[k], runs + offsets[k + 1])});
+    return out;
+}
+} // namespace detail
+// pycocotools' frPoly on the device: each polygon, a flat list x0 y0 x1 y1 .. of one vertex or more, becomes one record of size {width, height}. A coordinate
+// that is not finite or beyond 2^20 is refused; the message names the polygon.
+inline std::vector<mask_rle> mask_rle_from_polygons(std::span<std::vector<double> const> polygons, i32x2 size) {
+    if (polygons.empty()) throw exception("mask_rle_from_polygons: expected at least one polygon");
+    std::vector<double> xy;
+    std::vector<int64_t> poly_offsets{0}, offsets(polygons.size() + 1);
+    for (std::vector<double> const& p : polygons) {
+        if (p.size() % 2) throw exception("mask_rle_from_polygons: a polygon is x y pairs");
+        xy.insert(xy.end(), p.begin(), p.end());
+        poly_offsets.push_back(int64_t(xy.size() / 2));
+    }
+    xy.push_back(0); // an address also without vertices
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_from_poly_host(xy.data(), poly_offsets.data(), int32_t(polygons.size()), size[0], size[1], offsets.data(), &runs, &owner.data, nullptr));
+    return detail::rle_records(size, offsets, runs);
+}
+// pycocotools' frBbox: boxes {x, y, width, height}, each as its four-vertex polygon
+inline std::vector<mask_rle> mask_rle_from_boxes(std::span<std::array<double, 4> const> boxes, i32x2 size) {
+    if (boxes.empty()) throw exception("mask_rle_from_boxes: expected at least one box");
+    std::vector<int64_t> offsets(boxes.size() + 1);
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_from_bbox_host(boxes[0].data(), int32_t(boxes.size()), size[0], size[1], offsets.data(), &runs, &owner.data, nullptr));
+    return detail::rle_records(size, offsets, runs);
+}
+// pycocotools' merge on the device: the union of the records, or their intersection
+inline mask_rle mask_rle_merge(std::span<mask_rle const> rles, bool intersect = false) {
+    detail::rle_rows rows(rles);
+    const int64_t groups[2] = {0, int64_t(rles.size())};
+    std::vector<int64_t> offsets(2);
+    uint32_t const* runs = nullptr;
+    rle_owner owner(nullptr);
+    detail::check(visp_image_rle_merge_host(rows.offsets.data(), rows.runs.data(), int32_t(rles.size()), groups, 1, rows.size[0], rows.size[1], intersect ? 1 : 0, offsets.data(),
+                                            &runs, &owner.data, nullptr));
+    return std::move(detail::rle_records(rows.size, offsets, runs)[0]);
+}
+// pycocotools' toBbox on the device: {x, y, width, height} of each record's foreground, zeros for an empty mask
+inline std::vector<std::array<int32_t, 4>> mask_rle_bbox(std::span<mask_rle const> rles) {
+    detail::rle_rows rows(rles);
+    std::vector<std::array<int32_t, 4>> boxes(rles.size());
+    detail::check(visp_image_rle_to_bbox_host(rows.offsets.data(), rows.runs.data(), int32_t(rles.size()), rows.size[0], rows.size[1], boxes[0].data(), nullptr));
+    return boxes;
+}
 // image.cpp:471-476: img rgba_f32 (its alpha is not used), mask alpha_f32 -> rgba_f32 foreground colours, alpha = mask
 inline image_data image_estimate_foreground(image_view const& img, image_view const& mask, int radius = 30) {
     visp_image_view in = detail::c_view(img), mk = detail::c_view(mask), out{};

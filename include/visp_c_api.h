@@ -505,6 +505,41 @@ VISP_API int32_t visp_image_rle_decompress_host(int64_t const* byte_offsets_i64,
 /* u8 masks -> strings in one call: the encoder's count and packed passes, then the compressor's two, on one stream; the runs never leave the device */
 VISP_API int32_t visp_image_rle_encode_compressed_host(uint8_t const* masks_u8, int32_t n, int32_t w, int32_t h, int64_t* byte_offsets_i64, uint8_t const** bytes_u8,
                                                        visp_rle_data** out_data, visp_device const* dev);
+/* Polygons and boxes to RLE records, pycocotools' rleFrPoly / rleFrBbox, on the device. n polygons of one extent w x h are a CSR: xy f64 [total_vertices][2] = (x, y),
+ * poly_offsets i64 [n + 1], polygon b has poly_offsets[b + 1] - poly_offsets[b] >= 1 vertices; n is 1 .. 65535. Each becomes one record of runs as above, by the
+ * loop as pycocotools writes it in IEEE doubles: vertices upsampled by 5 with a truncating cast, the edges walked, a boundary where a walked point enters a column
+ * at a pixel centre, boundaries sorted and cancelled in pairs. Coordinates are finite and at most 2^20 in size, a polygon walks fewer than 2^31 points.
+ * The device form counts, then writes: with runs NULL it writes sizes i32 [n], each record's runs; with offsets i64 [n + 1] made from the running sum of those
+ * sizes it writes the packed rows, sizes then nullable. status i32 [n] (nullable): 0 = good, 1 = no vertex or bad offsets, 2 = a coordinate not finite or beyond
+ * 2^20, 3 = 2^31 points or more; such a record reports 0 runs and gets none written. counts as for visp_image_rle_decode_device. All pointers but dev are DEVICE
+ * pointers; the polygon offsets (n + 1 values), then each polygon's points and keys (2 n values) are read back to size the workspace, allocated per CALL. */
+VISP_API int32_t visp_image_rle_from_poly_device(void const* xy_f64_dev, void const* poly_offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev,
+                                                 void* runs_u32_dev, void const* offsets_i64_dev, void* sizes_i32_dev, void* status_i32_dev, void* stream, visp_device const* dev);
+/* the same on host arrays, all passes in one call, the rows in a library-owned buffer (visp_rle_destroy). Bad input (a NaN, a coordinate beyond 2^20, a polygon
+ * without vertices, decreasing offsets, w h too large) is refused before any launch; the message names the polygon. Blocks. */
+VISP_API int32_t visp_image_rle_from_poly_host(double const* xy_f64, int64_t const* poly_offsets_i64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64,
+                                               uint32_t const** runs_u32, visp_rle_data** out_data, visp_device const* dev);
+/* rleFrPoly's loop on the host, polygon by polygon: what the host entries hold their input against and what the device is measured against
+ * (tools/bench_mask_rle_poly.py). Touches no device; no entry falls back to it. */
+VISP_API int32_t visp_image_rle_from_poly_reference_host(double const* xy_f64, int64_t const* poly_offsets_i64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64,
+                                                         uint32_t const** runs_u32, visp_rle_data** out_data);
+/* boxes f64 [n][4] = {x, y, bw, bh}: each the polygon (x, y) (x, y + bh) (x + bw, y + bh) (x + bw, y) through visp_image_rle_from_poly_host */
+VISP_API int32_t visp_image_rle_from_bbox_host(double const* boxes_f64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32,
+                                               visp_rle_data** out_data, visp_device const* dev);
+/* pycocotools' merge: records group_offsets[g] .. group_offsets[g + 1] of the n records (group_offsets i64 [groups + 1] over 0 .. n) become one mask per group, the OR
+ * of their masks, the AND with intersect != 0; an empty group gives an empty mask. The device form writes u8 masks [groups][h][w] (0 / value) and reads both offset
+ * arrays back before its first launch; the host form returns the merged records (records -> bit words -> merged words -> masks -> the encoder, all on the device). */
+VISP_API int32_t visp_image_rle_merge_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, void const* group_offsets_i64_dev, int32_t groups, int32_t w,
+                                             int32_t h, int32_t intersect, int32_t value, void* masks_u8_dev, void* stream, visp_device const* dev);
+VISP_API int32_t visp_image_rle_merge_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t const* group_offsets_i64, int32_t groups, int32_t w,
+                                           int32_t h, int32_t intersect, int64_t* out_offsets_i64, uint32_t const** runs_u32_out, visp_rle_data** out_data,
+                                           visp_device const* dev);
+/* pycocotools' toBbox: boxes i32 [n][4] = {x, y, bw, bh}, the tight box of each record's foreground, {0, 0, 0, 0} for an empty one; short and long rows take the
+ * clamp of visp_image_rle_decode_device. */
+VISP_API int32_t visp_image_rle_to_bbox_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev,
+                                               void* boxes_i32_dev, void* stream, visp_device const* dev);
+VISP_API int32_t visp_image_rle_to_bbox_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int32_t w, int32_t h, int32_t* boxes_i32,
+                                             visp_device const* dev);
 /* image_estimate_foreground: image rgba_f32, mask alpha_f32 of the same extent -> rgba_f32 foreground colours, alpha = mask. Two blur-fusion stages, radius
  * (the reference's default: 30) then 3; radius <= min(w, h) / 2, extent at least 6x6 */
 VISP_API int32_t visp_image_estimate_foreground(visp_device const* dev, visp_image_view const* image, visp_image_view const* mask, int32_t radius,

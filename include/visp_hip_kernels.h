@@ -507,6 +507,33 @@ VX_API int vx_rle_compress(const uint32_t* runs, const int64_t* offsets, int64_t
  * its runs are written. A record's string is shorter than 2^31 bytes. One block per record, one launch. */
 VX_API int vx_rle_decompress(const uint8_t* bytes, const int64_t* byte_offsets, int n, const int32_t* counts, int first, uint32_t* runs, const int64_t* offsets,
                              int32_t* sizes, int32_t* status, void* stream);
+/* ---- polygons to RLE, merged records and boxes (kernels_rle_poly.hip): pycocotools' rleFrPoly, rleMerge and rleToBbox on CSR rows ----
+ * Polygons are a CSR: xy f64 [total_vertices][2] (x, y), poly_offsets a device i64 [n + 1]; polygon b has poly_offsets[b + 1] - poly_offsets[b] >= 1 vertices,
+ * total_vertices = poly_offsets[n] - poly_offsets[0]. All of a call share the extent w x h; each becomes one record of runs as above. counts / first as above.
+ * n is 1 .. 65535. IEEE doubles as rleFrPoly's loop writes them (no fused multiply-add), integers behind; no atomics: the same bytes on every run.
+ *
+ * vx_poly_rle runs in three forms, each from the vertices on:
+ *   keys NULL: mk i64 [n][2] (required) = each polygon's walked points M and its keys K + 1 (the boundary keys and h w); {0, 0} for a refused one.
+ *   keys, runs NULL: sizes i32 [n] (required) = each record's runs.
+ *   keys, runs: offsets (device i64 [n + 1]) required, sizes nullable; the packed rows; no store leaves a record's own row.
+ * keys: u32 [total_keys] the call sorts in, total_keys at least the sum of vx_poly_rle_key_row(K + 1) over the polygons (K + 1 up to 8192, which are sorted in
+ * LDS; the next power of two beyond, sorted in the row). status i32 [n] (nullable): 0 = good, 1 = no vertex or offsets outside total_vertices, 2 = a coordinate
+ * that is not finite or beyond 2^20 in size, 3 = M at or above 2^31, 4 = the key row does not fit into total_keys; such a record reports 0 runs and gets none
+ * written. max_points: the largest M, a hint that sizes the grid (any value is correct; 0 = unknown) -- the workspace is sized with the same value:
+ * vx_poly_rle_workspace_bytes(total_vertices, n, max_points) bytes, 16-byte aligned (32 bytes an edge, the blocks' key counts; 0 for refused arguments).
+ * Three launches, six with keys. */
+VX_API int64_t vx_poly_rle_key_row(int64_t keys);
+VX_API size_t vx_poly_rle_workspace_bytes(int64_t total_vertices, int n, int64_t max_points);
+VX_API int vx_poly_rle(const double* xy, const int64_t* poly_offsets, int64_t total_vertices, int64_t max_points, int n, int w, int h, const int32_t* counts, int first,
+                       uint32_t* keys, int64_t total_keys, uint32_t* runs, const int64_t* offsets, int32_t* sizes, int64_t* mk, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Bit words (the layout of vx_rle_to_bits) of n masks -> one mask per group: out word i of group g = the OR (intersect 0) or the AND of word i of masks
+ * group_offsets[g] .. group_offsets[g + 1] (a device i64 [groups + 1] over 0 .. n); an empty group gives an empty mask. Every word of the columns and segments
+ * a mask has is written, nothing else. One launch. */
+VX_API int vx_bits_merge(const void* words, int n, const int64_t* group_offsets, int groups, int w, int h, int intersect, void* out_words, void* stream);
+/* CSR rows of runs -> boxes i32 [n][4] = {x, y, bw, bh}, the tight box of each record's foreground, {0, 0, 0, 0} for an empty one. A short or long row takes
+ * vx_rle_to_bits' clamp: pixels behind the last run are background, runs behind h w are ignored. One block per record, one launch. */
+VX_API int vx_rle_bbox(const uint32_t* runs, const int64_t* offsets, int64_t total_runs, int n, int w, int h, const int32_t* counts, int first, int32_t* boxes, void* stream);
 /* test hook: a lane's partial row sum above `limit` sends a key tile from the lagging-reference fast path to the full path
  * (0 = always the full path; negative = restore the default 1024) */
 VX_API void vx_attention_set_fast_limit(float limit);

@@ -1134,6 +1134,66 @@ int32_t visp_image_rle_encode_compressed_host(uint8_t const* masks_u8, int32_t n
     });
 }
 
+int32_t visp_image_rle_from_poly_device(void const* xy_f64_dev, void const* poly_offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, void* runs_u32_dev,
+                                        void const* offsets_i64_dev, void* sizes_i32_dev, void* status_i32_dev, void* stream, visp_device const* dev) {
+    return handle_errors(
+        [&]() { rle_from_poly_device(dev, xy_f64_dev, poly_offsets_i64_dev, n, w, h, counts_dev, runs_u32_dev, offsets_i64_dev, sizes_i32_dev, status_i32_dev, stream); });
+}
+
+int32_t visp_image_rle_from_poly_host(double const* xy_f64, int64_t const* poly_offsets_i64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32,
+                                      visp_rle_data** out_data, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!runs_u32 || !out_data) throw except("rle_from_poly: null pointer");
+        return_rle(rle_from_poly_host(dev, xy_f64, poly_offsets_i64, n, w, h, offsets_i64), runs_u32, out_data);
+    });
+}
+
+int32_t visp_image_rle_from_poly_reference_host(double const* xy_f64, int64_t const* poly_offsets_i64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64,
+                                                uint32_t const** runs_u32, visp_rle_data** out_data) {
+    return handle_errors([&]() {
+        if (!xy_f64 || !poly_offsets_i64 || !offsets_i64 || !runs_u32 || !out_data) throw except("rle_from_poly: null pointer");
+        check_polygons("rle_from_poly", xy_f64, poly_offsets_i64, n, w, h);
+        std::vector<uint32_t> all;
+        offsets_i64[0] = 0;
+        for (int b = 0; b < n; ++b) {
+            const std::vector<uint32_t> r = poly_rle_reference(xy_f64 + 2 * poly_offsets_i64[b], poly_offsets_i64[b + 1] - poly_offsets_i64[b], w, h);
+            all.insert(all.end(), r.begin(), r.end());
+            offsets_i64[b + 1] = (int64_t)all.size();
+        }
+        return_rle(std::move(all), runs_u32, out_data);
+    });
+}
+
+int32_t visp_image_rle_from_bbox_host(double const* boxes_f64, int32_t n, int32_t w, int32_t h, int64_t* offsets_i64, uint32_t const** runs_u32, visp_rle_data** out_data,
+                                      visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!runs_u32 || !out_data) throw except("rle_from_bbox: null pointer");
+        return_rle(rle_from_bbox_host(dev, boxes_f64, n, w, h, offsets_i64), runs_u32, out_data);
+    });
+}
+
+int32_t visp_image_rle_merge_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, void const* group_offsets_i64_dev, int32_t groups, int32_t w, int32_t h,
+                                    int32_t intersect, int32_t value, void* masks_u8_dev, void* stream, visp_device const* dev) {
+    return handle_errors([&]() { rle_merge_device(dev, runs_u32_dev, offsets_i64_dev, n, group_offsets_i64_dev, groups, w, h, intersect, value, masks_u8_dev, stream); });
+}
+
+int32_t visp_image_rle_merge_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t const* group_offsets_i64, int32_t groups, int32_t w, int32_t h,
+                                  int32_t intersect, int64_t* out_offsets_i64, uint32_t const** runs_u32_out, visp_rle_data** out_data, visp_device const* dev) {
+    return handle_errors([&]() {
+        if (!runs_u32_out || !out_data) throw except("rle_merge: null pointer");
+        return_rle(rle_merge_host(dev, offsets_i64, runs_u32, n, group_offsets_i64, groups, w, h, intersect, out_offsets_i64), runs_u32_out, out_data);
+    });
+}
+
+int32_t visp_image_rle_to_bbox_device(void const* runs_u32_dev, void const* offsets_i64_dev, int32_t n, int32_t w, int32_t h, void const* counts_dev, void* boxes_i32_dev,
+                                      void* stream, visp_device const* dev) {
+    return handle_errors([&]() { rle_to_bbox_device(dev, runs_u32_dev, offsets_i64_dev, n, w, h, counts_dev, boxes_i32_dev, stream); });
+}
+
+int32_t visp_image_rle_to_bbox_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int32_t w, int32_t h, int32_t* boxes_i32, visp_device const* dev) {
+    return handle_errors([&]() { rle_to_bbox_host(dev, offsets_i64, runs_u32, n, w, h, boxes_i32); });
+}
+
 int32_t visp_image_rle_area_host(int64_t const* offsets_i64, uint32_t const* runs_u32, int32_t n, int64_t* area_i64) {
     return handle_errors([&]() { rle_area_host(offsets_i64, runs_u32, n, area_i64); });
 }

@@ -1,6 +1,7 @@
 #include "mask_rle.h"
 
 #include <algorithm>
+#include <cmath>
 
 #include "visp_util.h"
 
@@ -464,6 +465,284 @@ std::vector<uint8_t> rle_encode_compressed_host(backend_device const* dev, uint8
     device_buffer m(bytes);
     VX(vx_memcpy_h2d(m.ptr, masks, bytes, on.stream));
     return encode_compressed_to_host(static_cast<uint8_t const*>(m.ptr), n, w, h, nullptr, nullptr, 0, byte_offsets, on.stream);
+}
+
+// ---- polygons and boxes to records, merged records, boxes of records (kernels_rle_poly.hip) ----
+
+std::vector<uint32_t> poly_rle_reference(double const* xy, int64_t k, int w, int h) {
+    std::vector<int> x((size_t)k + 1), y((size_t)k + 1), u, v;
+    for (int64_t j = 0; j < k; ++j) {
+        x[(size_t)j] = (int)(5.0 * xy[2 * j] + 0.5);
+        y[(size_t)j] = (int)(5.0 * xy[2 * j + 1] + 0.5);
+    }
+    x[(size_t)k] = x[0];
+    y[(size_t)k] = y[0];
+    for (int64_t j = 0; j < k; ++j) {
+        int xs = x[(size_t)j], xe = x[(size_t)j + 1], ys = y[(size_t)j], ye = y[(size_t)j + 1];
+        const int dx = std::abs(xe - xs), dy = std::abs(ys - ye);
+        const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
+        if (flip) {
+            std::swap(xs, xe);
+            std::swap(ys, ye);
+        }
+        if (dx == 0 && dy == 0) { // a single point; its v is never read below
+            u.push_back(xs);
+            v.push_back(ys);
+            continue;
+        }
+        const double s = dx >= dy ? (double)(ye - ys) / dx : (double)(xe - xs) / dy;
+        if (dx >= dy) {
+            for (int d = 0; d <= dx; ++d) {
+                const int t = flip ? dx - d : d;
+                u.push_back(t + xs);
+                v.push_back((int)(ys + s * t + 0.5));
+            }
+        } else {
+            for (int d = 0; d <= dy; ++d) {
+                const int t = flip ? dy - d : d;
+                v.push_back(t + ys);
+                u.push_back((int)(xs + s * t + 0.5));
+            }
+        }
+    }
+    std::vector<uint32_t> a;
+    for (size_t j = 1; j < u.size(); ++j) {
+        if (u[j] == u[j - 1]) continue;
+        double xd = (double)(u[j] < u[j - 1] ? u[j] : u[j] - 1);
+        xd = (xd + 0.5) / 5.0 - 0.5;
+        if (std::floor(xd) != xd || xd < 0 || xd > w - 1) continue;
+        double yd = (double)(v[j] < v[j - 1] ? v[j] : v[j - 1]);
+        yd = (yd + 0.5) / 5.0 - 0.5;
+        if (yd < 0) yd = 0;
+        else if (yd > h) yd = h;
+        yd = std::ceil(yd);
+        a.push_back((uint32_t)((int)xd * h + (int)yd));
+    }
+    a.push_back((uint32_t)((int64_t)h * w));
+    std::sort(a.begin(), a.end());
+    uint32_t p = 0;
+    for (uint32_t& t : a) {
+        const uint32_t key = t;
+        t -= p;
+        p = key;
+    }
+    std::vector<uint32_t> b{a[0]};
+    for (size_t i = 1; i < a.size();) {
+        if (a[i] > 0) {
+            b.push_back(a[i++]);
+        } else {
+            ++i;
+            if (i < a.size()) b.back() += a[i++];
+        }
+    }
+    return b;
+}
+
+int64_t check_polygons(char const* who, double const* xy, int64_t const* poly_offsets, int n, int w, int h) {
+    check_rle_extent(who, n, w, h);
+    int64_t longest = 0;
+    for (int b = 0; b < n; ++b) {
+        if (poly_offsets[b] < 0 || poly_offsets[b + 1] < poly_offsets[b]) throw except("%s: offsets decrease at polygon %d", who, b);
+        if (poly_offsets[b + 1] == poly_offsets[b]) throw except("%s: polygon %d has no vertex", who, b);
+        const int64_t k = poly_offsets[b + 1] - poly_offsets[b];
+        double const* p = xy + 2 * poly_offsets[b];
+        for (int64_t j = 0; j < 2 * k; ++j)
+            if (!(std::fabs(p[j]) <= 1048576.0)) throw except("%s: polygon %d, vertex %lld: coordinate %g is not finite or beyond 2^20", who, b, (long long)(j / 2), p[j]);
+        int64_t points = 0;
+        for (int64_t j = 0; j < k; ++j) {
+            const int64_t j1 = j + 1 < k ? j + 1 : 0;
+            const int dx = std::abs((int)(5.0 * p[2 * j1] + 0.5) - (int)(5.0 * p[2 * j] + 0.5)), dy = std::abs((int)(5.0 * p[2 * j1 + 1] + 0.5) - (int)(5.0 * p[2 * j + 1] + 0.5));
+            points += std::max(dx, dy) + 1;
+        }
+        if (points >= (int64_t(1) << 31)) throw except("%s: polygon %d walks %lld points, at or above 2^31", who, b, (long long)points);
+        longest = std::max(longest, points);
+    }
+    return longest;
+}
+
+namespace {
+
+// vx_poly_rle on device polygons: the sizing form and one readback of {M, K + 1} per polygon when made, then the forms with keys as often as asked
+struct poly_pass {
+    double const* xy;
+    int64_t const* poff;
+    int64_t total_vertices, max_points = 0, total_keys = 0;
+    int n, w, h;
+    int32_t const* counts;
+    void* s;
+    size_t ws_bytes = 0;
+    device_buffer ws, keys;
+
+    poly_pass(void const* xy_dev, void const* poff_dev, int64_t total_vertices, int n, int w, int h, void const* counts_dev, void* status_dev, void* s)
+        : xy(static_cast<double const*>(xy_dev)), poff(static_cast<int64_t const*>(poff_dev)), total_vertices(total_vertices), n(n), w(w), h(h),
+          counts(static_cast<int32_t const*>(counts_dev)), s(s) {
+        size_t bytes = vx_poly_rle_workspace_bytes(total_vertices, n, 0);
+        if (!bytes) throw except("rle_from_poly: %lld vertices in %d polygons: no workspace", (long long)total_vertices, n);
+        std::vector<int64_t> mk((size_t)n * 2, 0);
+        device_buffer first(bytes), mk_dev(mk.size() * 8);
+        VX(vx_memcpy_h2d(mk_dev.ptr, mk.data(), mk.size() * 8, s)); // a polygon behind the device count stays {0, 0}
+        VX(vx_poly_rle(xy, poff, total_vertices, 0, n, w, h, counts, 0, nullptr, 0, nullptr, nullptr, nullptr, static_cast<int64_t*>(mk_dev.ptr),
+                       static_cast<int32_t*>(status_dev), first.ptr, bytes, s));
+        VX(vx_memcpy_d2h(mk.data(), mk_dev.ptr, mk.size() * 8, s));
+        VX(vx_stream_sync(s));
+        for (int b = 0; b < n; ++b) {
+            max_points = std::max(max_points, mk[(size_t)b * 2]);
+            total_keys += vx_poly_rle_key_row(mk[(size_t)b * 2 + 1]);
+        }
+        ws_bytes = vx_poly_rle_workspace_bytes(total_vertices, n, max_points);
+        grow(ws, ws_bytes, {s});
+        grow(keys, std::max<size_t>((size_t)total_keys * 4, 16), {s});
+    }
+    void run(void* runs_dev, void const* offsets_dev, void* sizes_dev, void* status_dev) {
+        VX(vx_poly_rle(xy, poff, total_vertices, max_points, n, w, h, counts, 0, static_cast<uint32_t*>(keys.ptr), total_keys, static_cast<uint32_t*>(runs_dev),
+                       static_cast<int64_t const*>(offsets_dev), static_cast<int32_t*>(sizes_dev), nullptr, static_cast<int32_t*>(status_dev), ws.ptr, ws_bytes, s));
+    }
+};
+
+// host rows held to their offsets, then on the device: the runs from offsets[0] on and the offsets from 0
+struct uploaded_rows {
+    std::vector<int64_t> rel;
+    device_buffer runs, offsets;
+    uploaded_rows(int64_t const* off, uint32_t const* r, int n, void* s) : rel(off, off + n + 1) {
+        for (int64_t& v : rel) v -= off[0];
+        runs = uploaded(r + off[0], (size_t)rel.back() * 4, s);
+        offsets = uploaded(rel.data(), rel.size() * 8, s);
+    }
+};
+
+void check_groups(char const* who, int64_t const* group_offsets, int groups, int n) {
+    for (int g = 0; g < groups; ++g)
+        if (group_offsets[g] < 0 || group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n)
+            throw except("%s: group %d is records %lld .. %lld of %d", who, g, (long long)group_offsets[g], (long long)group_offsets[g + 1], n);
+}
+
+// device records -> the groups' masks u8 [groups, h, w] on the device; `off` the records' offsets on the host
+void merge_on(uint32_t const* runs_dev, int64_t const* offsets_dev, std::vector<int64_t> const& off, int n, int64_t const* group_offsets_dev, int groups, int w, int h,
+              int intersect, int value, uint8_t* masks_dev, void* s) {
+    const size_t per = vx_mask_rle_workspace_bytes(w, h, 1);
+    const int64_t total = off.back() - off.front();
+    const size_t pos_bytes = vx_rle_to_bits_workspace_bytes(total, n);
+    device_buffer words((size_t)n * per), merged((size_t)groups * per), pos(pos_bytes);
+    VX(vx_rle_to_bits(runs_dev, offsets_dev, total, n, w, h, nullptr, 0, words.ptr, nullptr, nullptr, pos.ptr, pos_bytes, s));
+    VX(vx_bits_merge(words.ptr, n, group_offsets_dev, groups, w, h, intersect, merged.ptr, s));
+    VX(vx_bits_to_mask_u8(merged.ptr, groups, w, h, nullptr, 0, value, masks_dev, s));
+    VX(vx_stream_sync(s)); // the words are freed behind this
+}
+
+} // namespace
+
+void rle_from_poly_device(backend_device const* dev, void const* xy_dev, void const* poly_offsets_dev, int n, int w, int h, void const* counts_dev, void* runs_dev,
+                          void const* offsets_dev, void* sizes_dev, void* status_dev, void* stream) {
+    if (!xy_dev || !poly_offsets_dev || (runs_dev ? !offsets_dev : !sizes_dev)) throw except("rle_from_poly: null pointer");
+    check_rle_extent("rle_from_poly", n, w, h);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    const std::vector<int64_t> poff = read_offsets("rle_from_poly", poly_offsets_dev, n, s);
+    if (poff.back() == poff.front()) throw except("rle_from_poly: no vertex in %d polygons", n);
+    poly_pass pass(xy_dev, poly_offsets_dev, poff.back() - poff.front(), n, w, h, counts_dev, status_dev, s);
+    pass.run(runs_dev, offsets_dev, sizes_dev, status_dev);
+    VX(vx_stream_sync(s)); // the workspaces are freed behind this
+}
+
+std::vector<uint32_t> rle_from_poly_host(backend_device const* dev, double const* xy, int64_t const* poly_offsets, int n, int w, int h, int64_t* offsets) {
+    if (!xy || !poly_offsets || !offsets) throw except("rle_from_poly: null pointer");
+    check_polygons("rle_from_poly", xy, poly_offsets, n, w, h);
+    device_scope on(dev);
+    void* s = on.stream;
+    std::vector<int64_t> rel(poly_offsets, poly_offsets + n + 1);
+    for (int64_t& v : rel) v -= poly_offsets[0];
+    device_buffer xy_dev = uploaded(xy + 2 * poly_offsets[0], (size_t)rel.back() * 16, s), poff_dev = uploaded(rel.data(), rel.size() * 8, s), sizes_dev((size_t)n * 4),
+                  st_dev((size_t)n * 4);
+    poly_pass pass(xy_dev.ptr, poff_dev.ptr, rel.back(), n, w, h, nullptr, nullptr, s);
+    pass.run(nullptr, nullptr, sizes_dev.ptr, st_dev.ptr);
+    std::vector<int32_t> sizes((size_t)n), status((size_t)n);
+    VX(vx_memcpy_d2h(sizes.data(), sizes_dev.ptr, (size_t)n * 4, s));
+    VX(vx_memcpy_d2h(status.data(), st_dev.ptr, (size_t)n * 4, s));
+    VX(vx_stream_sync(s));
+    offsets[0] = 0;
+    for (int b = 0; b < n; ++b) {
+        if (status[(size_t)b]) throw except("rle_from_poly: polygon %d: the device reports status %d on input the host check passed", b, status[(size_t)b]);
+        offsets[b + 1] = offsets[b] + sizes[(size_t)b];
+    }
+    std::vector<uint32_t> out((size_t)offsets[n]);
+    device_buffer o = uploaded(offsets, ((size_t)n + 1) * 8, s), rows(std::max<size_t>(out.size() * 4, 16));
+    pass.run(rows.ptr, o.ptr, nullptr, nullptr);
+    if (!out.empty()) VX(vx_memcpy_d2h(out.data(), rows.ptr, out.size() * 4, s));
+    VX(vx_stream_sync(s));
+    return out;
+}
+
+std::vector<uint32_t> rle_from_bbox_host(backend_device const* dev, double const* boxes, int n, int w, int h, int64_t* offsets) {
+    if (!boxes || !offsets) throw except("rle_from_bbox: null pointer");
+    check_rle_extent("rle_from_bbox", n, w, h);
+    std::vector<double> xy((size_t)n * 8);
+    std::vector<int64_t> poff((size_t)n + 1);
+    for (int b = 0; b < n; ++b) {
+        const double x = boxes[4 * b], y = boxes[4 * b + 1], xe = x + boxes[4 * b + 2], ye = y + boxes[4 * b + 3];
+        const double ring[8] = {x, y, x, ye, xe, ye, xe, y};
+        std::copy(ring, ring + 8, xy.begin() + (size_t)b * 8);
+        poff[(size_t)b + 1] = 4 * ((int64_t)b + 1);
+    }
+    check_polygons("rle_from_bbox", xy.data(), poff.data(), n, w, h);
+    return rle_from_poly_host(dev, xy.data(), poff.data(), n, w, h, offsets);
+}
+
+void check_rle_merge(char const* who, int n, int groups, int w, int h) {
+    check_rle_extent(who, n, w, h);
+    if (groups < 1 || groups > 65535) throw except("%s: %d groups (1 .. 65535)", who, groups);
+}
+
+void rle_merge_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, void const* group_offsets_dev, int groups, int w, int h, int intersect,
+                      int value, void* masks_dev, void* stream) {
+    if (!runs_dev || !offsets_dev || !group_offsets_dev || !masks_dev) throw except("rle_merge: null pointer");
+    check_rle_merge("rle_merge", n, groups, w, h);
+    if (value < 1 || value > 255) throw except("rle_merge: foreground value %d (1 .. 255)", value);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    const std::vector<int64_t> off = read_offsets("rle_merge", offsets_dev, n, s), goff = read_offsets("rle_merge", group_offsets_dev, groups, s);
+    check_groups("rle_merge", goff.data(), groups, n);
+    merge_on(static_cast<uint32_t const*>(runs_dev), static_cast<int64_t const*>(offsets_dev), off, n, static_cast<int64_t const*>(group_offsets_dev), groups, w, h, intersect,
+             value, static_cast<uint8_t*>(masks_dev), s);
+}
+
+std::vector<uint32_t> rle_merge_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int64_t const* group_offsets, int groups, int w, int h,
+                                     int intersect, int64_t* out_offsets) {
+    if (!offsets || !runs || !group_offsets || !out_offsets) throw except("rle_merge: null pointer");
+    check_rle_merge("rle_merge", n, groups, w, h);
+    check_rle_rows("rle_merge", offsets, runs, n, (int64_t)w * h);
+    check_groups("rle_merge", group_offsets, groups, n);
+    device_scope on(dev);
+    void* s = on.stream;
+    uploaded_rows rows(offsets, runs, n, s);
+    device_buffer g = uploaded(group_offsets, ((size_t)groups + 1) * 8, s), masks((size_t)groups * w * h);
+    merge_on(static_cast<uint32_t const*>(rows.runs.ptr), static_cast<int64_t const*>(rows.offsets.ptr), rows.rel, n, static_cast<int64_t const*>(g.ptr), groups, w, h, intersect,
+             1, static_cast<uint8_t*>(masks.ptr), s);
+    return encode_to_host(static_cast<uint8_t const*>(masks.ptr), groups, w, h, nullptr, nullptr, 0, out_offsets, s);
+}
+
+void rle_to_bbox_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, int w, int h, void const* counts_dev, void* boxes_dev, void* stream) {
+    if (!runs_dev || !offsets_dev || !boxes_dev) throw except("rle_to_bbox: null pointer");
+    check_rle_extent("rle_to_bbox", n, w, h);
+    device_scope on(dev);
+    void* s = stream ? stream : on.stream;
+    const std::vector<int64_t> off = read_offsets("rle_to_bbox", offsets_dev, n, s);
+    VX(vx_rle_bbox(static_cast<uint32_t const*>(runs_dev), static_cast<int64_t const*>(offsets_dev), off.back() - off.front(), n, w, h, static_cast<int32_t const*>(counts_dev), 0,
+                   static_cast<int32_t*>(boxes_dev), s));
+    VX(vx_stream_sync(s));
+}
+
+void rle_to_bbox_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int w, int h, int32_t* boxes) {
+    if (!offsets || !runs || !boxes) throw except("rle_to_bbox: null pointer");
+    check_rle_extent("rle_to_bbox", n, w, h);
+    check_rle_rows("rle_to_bbox", offsets, runs, n, -1);
+    device_scope on(dev);
+    void* s = on.stream;
+    uploaded_rows rows(offsets, runs, n, s);
+    device_buffer out((size_t)n * 16);
+    VX(vx_rle_bbox(static_cast<uint32_t const*>(rows.runs.ptr), static_cast<int64_t const*>(rows.offsets.ptr), rows.rel.back(), n, w, h, nullptr, 0, static_cast<int32_t*>(out.ptr),
+                   s));
+    VX(vx_memcpy_d2h(boxes, out.ptr, (size_t)n * 16, s));
+    VX(vx_stream_sync(s));
 }
 
 } // namespace visp

@@ -70,4 +70,32 @@ std::vector<uint8_t> rle_encode_compressed_host(backend_device const* dev, uint8
 std::vector<uint8_t> sam_generate_masks_coco_rle_host(sam_model& m, int32_t const* prompts, int32_t const* n_args, int n, sam_select_params const& p, int32_t* info_i32,
                                                       float* info_f32, int32_t* counts, int64_t* byte_offsets);
 
+// ---- polygons and boxes to records, merged records, boxes of records (kernels_rle_poly.hip) ----
+// Polygons are a CSR: xy f64 [total_vertices][2], poly_offsets i64 [n + 1], one extent w x h for all.
+// pycocotools' rleFrPoly on one polygon of k >= 1 vertices, the loop as it reads, on the host: what the host entries hold their input against and what
+// tools/bench_mask_rle_poly.py measures against. No entry falls back to it.
+std::vector<uint32_t> poly_rle_reference(double const* xy, int64_t k, int w, int h);
+// host polygons: offsets non-decreasing with k >= 1 everywhere, coordinates finite and at most 2^20 in size, fewer than 2^31 walked points, 1 .. 65535 polygons,
+// w h below 2^31 - 1. Throws naming the polygon, touches no device. Returns the largest number of walked points.
+int64_t check_polygons(char const* who, double const* xy, int64_t const* poly_offsets, int n, int w, int h);
+// count, then write, as vx_poly_rle: runs_dev null -> sizes i32 [n] alone; else the runs at offsets_dev; status i32 [n] nullable. The polygon offsets are read
+// back and checked, then each polygon's points and keys (2 n values) before the key rows are sized; workspaces are allocated for the CALL; returns with the work done.
+void rle_from_poly_device(backend_device const* dev, void const* xy_dev, void const* poly_offsets_dev, int n, int w, int h, void const* counts_dev, void* runs_dev,
+                          void const* offsets_dev, void* sizes_dev, void* status_dev, void* stream);
+// host polygons -> the runs one behind the other, offsets i64 [n + 1]; bad input is refused before any launch
+std::vector<uint32_t> rle_from_poly_host(backend_device const* dev, double const* xy, int64_t const* poly_offsets, int n, int w, int h, int64_t* offsets);
+// boxes f64 [n][4] = {x, y, bw, bh} -> the polygons (x, y) (x, y + bh) (x + bw, y + bh) (x + bw, y), through rle_from_poly_host
+std::vector<uint32_t> rle_from_bbox_host(backend_device const* dev, double const* boxes, int n, int w, int h, int64_t* offsets);
+void check_rle_merge(char const* who, int n, int groups, int w, int h); // throws, touches no device
+// device records and group_offsets i64 [groups + 1] over them -> device masks u8 [groups, h, w] (0 / value): the OR of each group's masks, the AND with intersect.
+// Both offset arrays are read back and checked before the first launch.
+void rle_merge_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, void const* group_offsets_dev, int groups, int w, int h, int intersect,
+                      int value, void* masks_dev, void* stream);
+// host records -> the merged records: vx_rle_to_bits, vx_bits_merge, vx_bits_to_mask_u8 and the encoder's two passes on one stream; only runs come back
+std::vector<uint32_t> rle_merge_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int64_t const* group_offsets, int groups, int w, int h,
+                                     int intersect, int64_t* out_offsets);
+// boxes i32 [n][4] = {x, y, bw, bh} of device / host records
+void rle_to_bbox_device(backend_device const* dev, void const* runs_dev, void const* offsets_dev, int n, int w, int h, void const* counts_dev, void* boxes_dev, void* stream);
+void rle_to_bbox_host(backend_device const* dev, int64_t const* offsets, uint32_t const* runs, int n, int w, int h, int32_t* boxes);
+
 } // namespace visp

@@ -921,6 +921,82 @@ def mask_iou_device(a: tuple, b: tuple, iou_dev: int, iscrowd_dev: int | None = 
     check(lib.get_lib().visp_image_mask_iou_device(*a, *b, iscrowd_dev, iou_dev, inter_dev, stream, *_on(device)))
 
 
+def _polygon_rows(polygons) -> tuple:
+    """polygons, each [k, 2] or COCO's flat [x0, y0, x1, y1, ..] -> (xy f64 [total, 2], poly_offsets i64 [n + 1])"""
+    rows = [np.asarray(p, np.float64).reshape(-1, 2) for p in polygons]
+    if not rows:
+        raise ValueError("expected at least one polygon")
+    offsets = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=offsets[1:])
+    return np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, 2))])), offsets  # an address also without vertices
+
+
+def poly_to_rle(polygons, h: int, w: int, device: Device | None = None) -> list:
+    """pycocotools' frPoly on the device: polygons (each [k, 2], or COCO's flat [x0, y0, x1, y1, ..]) on an h x w image -> one record
+    {"size": [h, w], "counts": [...]} per polygon. A NaN, a coordinate beyond 2^20 or a polygon without vertices is refused; the message names the polygon."""
+    xy, poff = _polygon_rows(polygons)
+    offsets, runs, owner = np.zeros(len(poff), np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_from_poly_host(xy.ctypes.data, poff.ctypes.data, len(poff) - 1, int(w), int(h), offsets.ctypes.data, byref(runs), byref(owner), *_on(device)))
+    return _rle_records(offsets, runs, owner, len(poff) - 1, w, h)
+
+
+def bbox_to_rle(boxes, h: int, w: int, device: Device | None = None) -> list:
+    """pycocotools' frBbox: boxes [n, 4] = (x, y, bw, bh) -> one record per box, each box as its four-vertex polygon through poly_to_rle's kernels."""
+    b = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+    offsets, runs, owner = np.zeros(len(b) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_from_bbox_host(b.ctypes.data, len(b), int(w), int(h), offsets.ctypes.data, byref(runs), byref(owner), *_on(device)))
+    return _rle_records(offsets, runs, owner, len(b), w, h)
+
+
+def rle_merge(records, intersect: bool = False, device: Device | None = None):
+    """pycocotools' merge on the device: a list of records -> the record of their union (of their intersection with intersect); a list of lists of records ->
+    one merged record per inner list, an empty inner list giving an empty mask. All records have one size."""
+    recs = list(records)
+    single = not recs or isinstance(recs[0], dict)
+    groups = [recs] if single else [list(g) for g in recs]
+    flat = [r for g in groups for r in g]
+    offsets, runs, w, h = _rle_rows(flat, device)
+    goff = np.zeros(len(groups) + 1, np.int64)
+    np.cumsum([len(g) for g in groups], out=goff[1:])
+    out_offsets, out_runs, owner = np.zeros(len(groups) + 1, np.int64), c_void_p(), c_void_p()
+    check(lib.get_lib().visp_image_rle_merge_host(offsets.ctypes.data, runs.ctypes.data, len(flat), goff.ctypes.data, len(groups), w, h, int(bool(intersect)),
+                                                  out_offsets.ctypes.data, byref(out_runs), byref(owner), *_on(device)))
+    out = _rle_records(out_offsets, out_runs, owner, len(groups), w, h)
+    return out[0] if single else out
+
+
+def rle_to_bbox(rles, device: Device | None = None) -> np.ndarray:
+    """pycocotools' toBbox on the device: records -> int32 [n, 4] = (x, y, bw, bh), the tight box of each record's foreground, zeros for an empty mask
+    ([4] for a single dict)."""
+    single = isinstance(rles, dict)
+    offsets, runs, w, h = _rle_rows([rles] if single else list(rles), device)
+    boxes = np.zeros((len(offsets) - 1, 4), np.int32)
+    check(lib.get_lib().visp_image_rle_to_bbox_host(offsets.ctypes.data, runs.ctypes.data, len(boxes), w, h, boxes.ctypes.data, *_on(device)))
+    return boxes[0] if single else boxes
+
+
+def fr_py_objects(obj, h: int, w: int, device: Device | None = None):
+    """pycocotools' frPyObjects: an RLE dict is passed through as it is; a list of boxes ([n, 4] array, or lists of four numbers) gives a list of box records;
+    a list of polygon lists (each object a list of flat [x0, y0, x1, y1, ..] polygons of six numbers or more) gives one merged record per object."""
+    if isinstance(obj, dict):
+        return obj
+    if isinstance(obj, np.ndarray) and obj.ndim == 2 and obj.shape[1] == 4:
+        return bbox_to_rle(obj, h, w, device)
+    objs = list(obj)
+    if not objs:
+        raise ValueError("expected at least one object")
+    flat = [len(o) > 0 and np.isscalar(o[0]) for o in objs]  # numbers, not polygons
+    if all(flat) and all(len(o) == 4 for o in objs):
+        return bbox_to_rle(objs, h, w, device)
+    if all(flat):  # one object given as its polygons' coordinates
+        return rle_merge(poly_to_rle(objs, h, w, device), device=device)
+    records, at, out = poly_to_rle([p for o in objs for p in o], h, w, device), 0, []
+    for o in objs:
+        out.append(records[at:at + len(o)])
+        at += len(o)
+    return rle_merge(out, device=device)
+
+
 def image_estimate_foreground(image: np.ndarray, mask: np.ndarray, radius: int = 30, device: Device | None = None) -> np.ndarray:
     """image f32 [h, w, 4] (rgba_f32), mask f32 [h, w] -> f32 [h, w, 4]: foreground colours, alpha = mask (blur-fusion, two stages)."""
     return _image_op("visp_image_estimate_foreground", [_view_of(image, ImageFormat.rgba_f32), _view_of(mask, ImageFormat.alpha_f32)], int(radius), on=_on(device))
